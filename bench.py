@@ -4,7 +4,8 @@ on the BASELINE configs[2] workload (generic Hamiltonian, Nbasis=100, Nchol=500,
 RHF trial with 25+25 electrons, 256 walkers per GPU), plus the fp64-MFMA roofline
 fraction of the Cholesky exchange-energy kernel and the CPU-oracle baseline.
 
-  python bench.py --gpus N --steps K --warmup W            (N > 1 without a launcher: bench.py starts its N ranks itself,
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+                                                           (N > 1 without a launcher: bench.py starts its N ranks itself,
                                                             as child processes, before anything touches the GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -296,6 +297,8 @@ def run_config(args, name, state, comm=None, world=1, rank=0, backend="nccl"):
             el_ = float(t.item())
         regions.append(el_)
         first += steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, afqmc, dev, eshift, world, rank)
     order = sorted(range(repeats), key=lambda i: regions[i])
     imed = order[(repeats - 1) // 2]
     elapsed = regions[imed]
@@ -742,6 +745,9 @@ def main():
     ap.add_argument("--open-shell", action="store_true",
                     help="C3: start every walker with its beta block perturbed by 1e-3 (open-shell walkers: none of the "
                          "closed-shell paths of the Green's function, the exchange energy and the fused propagator applies)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the last timed step left the caller (walkers, block rows, "
+                         "energy shift) to DIR/<name>.npy, float64, 64 MB at most")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-window", type=float, default=8.0, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -814,6 +820,47 @@ def main():
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64 << 20          # --dump-outputs: all files of one run together
+
+
+def dump_outputs(dirname, afqmc, dev, eshift, world=1, rank=0, prefix="", sets=1):
+    """--dump-outputs DIR: what the timed path hands a caller of AFQMC.run_batched after its last timed step, read from
+    the device before anything else runs: every walker's phi, weight, overlap with the trial and log|det R|, the mixed
+    estimator's block rows (the wall-clock column dropped) and the energy shift.  float64 .npy files; complex arrays get
+    a trailing [real, imag] axis.  When the walkers would exceed this rank's share of DUMP_BUDGET_BYTES, a fixed seeded
+    sample of them is written (walker_index.npy names it); the ``sets`` dumps of one run (--scaling both) split the
+    budget.  With several ranks every rank writes its own walkers (<name>_rank<r>.npy); the block rows and the shift are
+    rank 0's."""
+    from pauxy_amd import _lib as L
+
+    def as_f64(a):
+        a = numpy.asarray(a)
+        if numpy.iscomplexobj(a):
+            a = numpy.stack([a.real, a.imag], axis=-1)
+        return numpy.ascontiguousarray(a, dtype=numpy.float64)
+
+    def save(name, a):
+        tag = "_rank%d" % rank if world > 1 else ""
+        numpy.save(os.path.join(dirname, "%s%s%s.npy" % (prefix, name, tag)), as_f64(a))
+
+    os.makedirs(dirname, exist_ok=True)
+    dev.sync()
+    fields = [("phi", L.F_PHI), ("weight", L.F_WEIGHT), ("overlap", L.F_OT), ("log_detR", L.F_LOG_DETR)]
+    per_walker = sum(as_f64(dev.get(f, 0, 1)).nbytes for _, f in fields)
+    nw = dev.nw
+    fit = max(1, min(nw, (DUMP_BUDGET_BYTES // (world * sets) - (1 << 20)) // per_walker))
+    index = numpy.arange(nw) if fit == nw else numpy.sort(numpy.random.RandomState(2024).choice(nw, fit, replace=False))
+    for name, f in fields:
+        a = dev.get(f)
+        save(name, a[index])
+    save("walker_index", index)
+    if rank == 0:
+        blocks = afqmc.estimators.estimators['mixed'].blocks
+        if blocks:
+            save("block_rows", numpy.array(blocks)[:, :-1])
+        save("eshift", numpy.atleast_1d(numpy.asarray(eshift, dtype=numpy.complex128)))
 
 
 def last_block_energy(afqmc):
@@ -1017,6 +1064,9 @@ def run_bench(args, scaling, comm, world, rank, backend, system, trial, state, w
     dev.kernel_trace(False)
     dev.kernel_trace_stride(L.K_PROPAGATOR, 1)
     state["phase"] = "after the timed region"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, afqmc, dev, eshift, world, rank,
+                     prefix=scaling + "_" if args.scaling == "both" else "", sets=2 if args.scaling == "both" else 1)
     order = sorted(range(repeats), key=lambda i: regions[i])
     imed = order[(repeats - 1) // 2]                     # lower median: an actually measured region
     elapsed = regions[imed]

@@ -23,6 +23,15 @@ def run_bench(extra, env_extra=None):
     return [json.loads(ln) for ln in lines]
 
 
+def require_gpus(n):
+    """The eight-rank cases run one rank per GPU (the smaller cases share one GPU): skip, before
+    any work, when the node has fewer than n GPUs."""
+    import torch
+    found = torch.cuda.device_count()
+    if found < n:
+        pytest.skip("needs %d GPUs (one per rank), found %d" % (n, found))
+
+
 def check_line(out, n_gpus, steps, walkers_total):
     assert out["metric"] == "walker_steps_per_sec" and out["unit"] == "walker-steps/s"
     assert out["n_gpus"] == n_gpus and out["steps"] == steps and out["dtype"] == "f64"
@@ -82,7 +91,8 @@ def test_bench_eight_ranks_print_their_line_when_one_rank_cannot_bring_rccl_up()
     """`python bench.py --gpus 8` on the whole candidate chain (walkers/handler.py:225-338 on the device, with agreed
     fall-backs) when rank 3 of 8 reports that it cannot load librccl (AFQ_COMM_FAULT): nobody enters ncclCommInitRank,
     every rank moves on to the peer-window communicator, the probe passes and rank 0 prints the line -- saying which
-    communicator ran and why the preferred one was dropped.  (The eight ranks share this box's one GPU over gloo.)"""
+    communicator ran and why the preferred one was dropped.  (The ranks run over gloo, one per GPU.)"""
+    require_gpus(8)
     (out,) = run_bench(["--gpus", "8", "--steps", "10", "--warmup", "10", "--walkers-per-gpu", "64"],
                        {"AFQ_BENCH_BACKEND": "gloo", "AFQ_BENCH_DEVICE_COMM": "auto", "AFQ_COMM_FAULT": "rccl:avail:3", "AFQ_ALLOW_FAULT_INJECTION": "1"})
     check_line(out, 8, 10, 512)
@@ -96,6 +106,7 @@ def test_bench_eight_ranks_print_their_line_when_one_rank_cannot_bring_rccl_up()
 def test_bench_eight_ranks_reach_the_host_path_when_every_candidate_fails_on_one_rank():
     """... and when rank 3 also fails the probe of the peer-window communicator: every rank tears it down, the population
     control goes through the host (pop_control_distributed), rank 0 still prints its line with the reasons."""
+    require_gpus(8)
     (out,) = run_bench(["--gpus", "8", "--steps", "10", "--warmup", "10", "--walkers-per-gpu", "64"],
                        {"AFQ_BENCH_BACKEND": "gloo", "AFQ_BENCH_DEVICE_COMM": "auto",
                         "AFQ_COMM_FAULT": "rccl:avail:3,ipc:probe:3", "AFQ_ALLOW_FAULT_INJECTION": "1"})

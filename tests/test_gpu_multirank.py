@@ -90,10 +90,10 @@ def drive(comm, nw_total, first, count, walkers=None, nr=2):
                 comm_stats=afqmc.psi.dev.comm_stats() if getattr(afqmc.psi, 'device_comm', False) else None)
 
 
-def _worker(rank, port, walkers, q, nr=2):
+def _worker(rank, port, walkers, q, nr=2, one_gpu=True):
     try:
         os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(nr),
-                          LOCAL_RANK='0')
+                          LOCAL_RANK='0' if one_gpu else str(rank))
         import torch
         import torch.distributed as dist
         from pauxy_amd.comm import TorchComm
@@ -116,11 +116,20 @@ def free_port():
     return p
 
 
-def many_ranks(nr, walkers=None):
+def require_gpus(n):
+    """The eight-rank cases run one rank per GPU (the smaller cases share one GPU): skip, before
+    any work, when the node has fewer than n GPUs."""
+    import torch
+    found = torch.cuda.device_count()
+    if found < n:
+        pytest.skip("needs %d GPUs (one per rank), found %d" % (n, found))
+
+
+def many_ranks(nr, walkers=None, one_gpu=True):
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
     port = free_port()
-    procs = [ctx.Process(target=_worker, args=(r, port, walkers, q, nr)) for r in range(nr)]
+    procs = [ctx.Process(target=_worker, args=(r, port, walkers, q, nr, one_gpu)) for r in range(nr)]
     for p in procs:
         p.start()
     try:
@@ -214,9 +223,9 @@ def test_device_comb_over_ipc_windows_two_processes():
     check_ipc(one, a, b)
 
 
-def check_many(nr, bench_mode=False):
+def check_many(nr, bench_mode=False, one_gpu=True):
     one = single_rank(nr)
-    outs = many_ranks(nr, {'device_comm': 'ipc'})
+    outs = many_ranks(nr, {'device_comm': 'ipc'}, one_gpu)
     from pauxy_amd.walkers.handler import comb_pairs
     assert all(o['device_comm'] and o['device_comm_kind'] == 'ipc' for o in outs)
     got_phi = numpy.concatenate([o['phi'] for o in outs])
@@ -254,19 +263,21 @@ def test_device_comb_over_ipc_windows_four_processes():
 
 
 def test_device_comb_over_ipc_windows_eight_processes():
-    """The rank count of the node the scaling bench runs on: eight processes (here all on the one GPU), seven mapped
-    windows per rank, 48 walkers in all.  Must equal the single-rank run with eight times the walkers, comb decisions
-    and per-rank traffic included."""
-    check_many(8)
+    """The rank count of the node the scaling bench runs on: eight processes, one per GPU, seven mapped windows per rank,
+    48 walkers in all.  Must equal the single-rank run with eight times the walkers, comb decisions and per-rank traffic
+    included."""
+    require_gpus(8)
+    check_many(8, one_gpu=False)
 
 
 def test_eight_processes_bench_mode_overlapped_block_boundary(monkeypatch):
     """Eight ranks driven exactly as bench.py --gpus 8 drives them: no per-step callback, nothing read back at the comb,
     estimator terms riding on the weight updates, the head of the next block queued before the window-reduced sums of the
     block are waited for."""
+    require_gpus(8)
     monkeypatch.setenv('AFQ_TEST_ONE_RDM', '0')
     monkeypatch.setenv('AFQ_TEST_NO_CALLBACK', '1')
-    check_many(8, bench_mode=True)
+    check_many(8, bench_mode=True, one_gpu=False)
 
 
 def _timeout_worker(rank, port, q):
