@@ -96,6 +96,15 @@ int afq_sync(afq_handle *h);
 int afq_set_system_generic(afq_handle *h, int M, int K, int na, int nb,
                            const double *hs_pot, const double *rchol,
                            const double *H1, double ecore);
+/* The same system with complex Cholesky vectors (periodic / k-point Hamiltonians, complex orbitals;
+ * pauxy/utils/io.py:200-206).  hs_pot c128[M*M, K], row p*M+q as above; the other arguments as
+ * afq_set_system_generic.  The vectors are classified bitwise on upload: Hermitian
+ * (L_n[q,p] == conj(L_n[p,q]) for every n) or general.  An hs_pot without imaginary parts takes the
+ * real path (bitwise the results of afq_set_system_generic).  Back-propagation needs Hermitian
+ * vectors: afq_bp_configure refuses general complex ones with AFQ_EUNSUPPORTED.                   */
+int afq_set_system_generic_c128(afq_handle *h, int M, int K, int na, int nb,
+                                const double *hs_pot, const double *rchol,
+                                const double *H1, double ecore);
 /* systems/hubbard.py:46-104.  T c128[2,M,M]; fields K = M.                    */
 int afq_set_system_hubbard(afq_handle *h, int M, int na, int nb, double U,
                            const double *T);

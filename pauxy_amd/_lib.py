@@ -34,6 +34,7 @@ SIGNATURES = {
     "afq_last_error": [_h],
     "afq_sync": [_h],
     "afq_set_system_generic": [_h, c_int, c_int, c_int, c_int, _dp, _dp, _dp, c_double],
+    "afq_set_system_generic_c128": [_h, c_int, c_int, c_int, c_int, _dp, _dp, _dp, c_double],
     "afq_set_system_hubbard": [_h, c_int, c_int, c_int, c_double, _dp],
     "afq_set_system_ueg": [_h, c_int, c_int, c_int, c_int, _ip, _ip, _dp, _ip, _ip, _dp,
                            _ip, _ip, _ip, _ip, _ip, _ip, _dp, c_double, _dp, c_double],

@@ -89,9 +89,7 @@ class Context(object):
             if rchol is None:
                 raise ValueError("Generic system needs half-rotated Cholesky vectors (trial.half_rotate)")
             hs = numpy.asarray(s.hs_pot)
-            if numpy.iscomplexobj(hs):
-                if numpy.abs(hs.imag).max() > 0:
-                    raise NotImplementedError("complex Cholesky vectors are not supported on the device path")
+            if numpy.iscomplexobj(hs) and not numpy.any(hs.imag != 0):
                 hs = hs.real
             M = s.nbasis
             dev.set_system_generic(hs, numpy.asarray(rchol)[:(na + nb) * M], numpy.asarray(s.H1, dtype=complex),

@@ -72,12 +72,13 @@ void free_dets(afq_handle *h) {
     h->dets.clear();
     h->ndet = 1; h->cur_det = 0;
     if (h->coeffs) { hipFree(h->coeffs); h->coeffs = nullptr; }
-    dev_free(h->msd_psicT); h->msd_fb_gbar = false;
+    dev_free(h->msd_psicT); dev_free(h->msd_psicT_neg); h->msd_fb_gbar = false;
 }
 
 void free_system(afq_handle *h) {
     free_dets(h);
-    dev_free(h->hs_pot); dev_free(h->hs_pair); dev_free(h->hs_pk); dev_free(h->L_full); dev_free(h->rchol_re); dev_free(h->rchol_im);
+    dev_free(h->hs_pot); dev_free(h->hs_pair); dev_free(h->hs_pk); dev_free(h->L_full);
+    dev_free(h->hs_pot_im); dev_free(h->hs_pair_im); dev_free(h->hs_pk_im); dev_free(h->L_full_c); h->hs_cplx = 0; dev_free(h->rchol_re); dev_free(h->rchol_im);
     for (int s = 0; s < 2; ++s) { dev_free(h->rchol_frag[s]); dev_free(h->rchol_frag_im[s]); }
     k_free_atil(h->atil);
     dev_free(h->H1); dev_free(h->rH1);
@@ -101,7 +102,7 @@ void free_walkers(afq_handle *h) {
     dev_free(h->xi); dev_free(h->vbias_all); h->vbias = nullptr; dev_free(h->ghalf_sum); h->gsum_version = 0; h->vbias_version = 0;
     dev_free(h->gdiag); h->gdiag_version = 0; h->gdiag_parts = 0;
     dev_free(h->detd); dev_free(h->detd_a); dev_free(h->detw); dev_free(h->energy_all);
-    dev_free(h->msd_gs); dev_free(h->msd_S); h->msd_fb_gbar = false;
+    dev_free(h->msd_gs); dev_free(h->msd_S); dev_free(h->msd_D); h->msd_fb_gbar = false;
     dev_free(h->hs_oinv); dev_free(h->hs_u); dev_free(h->hs_fields); dev_free(h->hs_used); dev_free(h->hs_alive0);
     dev_free(h->hs_fbfac);
     dev_free(h->bp_hist); dev_free(h->bp_n); dev_free(h->bp_flag); dev_free(h->bp_cos); dev_free(h->bp_ph);
@@ -386,6 +387,70 @@ int afq_set_system_generic(afq_handle *h, int M, int K, int na, int nb, const do
     return AFQ_OK;
 }
 
+// complex Cholesky vectors: Re and Im parts as two transposed real panels (afq_internal.h: hs_cplx)
+int afq_set_system_generic_c128(afq_handle *h, int M, int K, int na, int nb, const double *hs_pot,
+                                const double *rchol, const double *H1, double ecore) {
+    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (!h || !hs_pot || !rchol || !H1) return AFQ_EINVAL;
+    if (M <= 0 || K <= 0) AFQ_FAIL(h, AFQ_EINVAL, "bad dimensions");
+    const size_t mm = (size_t)M * M, nq = (size_t)(na + nb) * M;
+    bool real = true;
+    for (size_t e = 0; e < mm * K && real; ++e) real = hs_pot[2 * e + 1] == 0.0;
+    if (real) {
+        std::vector<double> re(mm * K);
+        for (size_t e = 0; e < mm * K; ++e) re[e] = hs_pot[2 * e];
+        return afq_set_system_generic(h, M, K, na, nb, re.data(), rchol, H1, ecore);
+    }
+    int rc = set_dims(h, AFQ_SYS_GENERIC, M, K, na, nb);
+    if (rc) return rc;
+    h->ecore = ecore;
+    auto at = [&](int p, int q, int n, int c) { return hs_pot[2 * (((size_t)p * M + q) * K + n) + c]; };
+    bool herm = true;                    // bitwise, as the symmetry test of the real entry point
+    for (int p = 0; p < M && herm; ++p)
+        for (int q = p; q < M && herm; ++q)
+            for (int n = 0; n < K; ++n)
+                if (at(p, q, n, 0) != at(q, p, n, 0) || at(p, q, n, 1) != -at(q, p, n, 1)) { herm = false; break; }
+    h->hs_sym = false;
+    h->hs_cplx = herm ? AFQ_HS_HERMITIAN : AFQ_HS_GENERAL;
+    if (herm) {
+        // Re L_n symmetric: columns p <= q (the layout of the real packed path); Im L_n antisymmetric: columns p < q
+        const size_t np = (size_t)M * (M + 1) / 2, nu = (size_t)M * (M - 1) / 2;
+        h->ld_hs = (long)((np + 1) & ~(size_t)1);
+        h->ld_hs_im = (long)((nu + 1) & ~(size_t)1);
+        std::vector<double> tr((size_t)K * h->ld_hs, 0.0), ti((size_t)K * h->ld_hs_im, 0.0);
+        std::vector<int> pq(2 * np), pqi(2 * (nu ? nu : 1));
+        size_t c = 0, ci = 0;
+        for (int p = 0; p < M; ++p)
+            for (int q = p; q < M; ++q, ++c) {
+                pq[2 * c] = p; pq[2 * c + 1] = q;
+                for (int n = 0; n < K; ++n) tr[(size_t)n * h->ld_hs + c] = at(p, q, n, 0);
+                if (q == p) continue;
+                pqi[2 * ci] = p; pqi[2 * ci + 1] = q;
+                for (int n = 0; n < K; ++n) ti[(size_t)n * h->ld_hs_im + ci] = at(p, q, n, 1);
+                ++ci;
+            }
+        if ((rc = dev_upload(h, &h->hs_pot, tr.data(), tr.size()))) return rc;
+        if ((rc = dev_upload(h, &h->hs_pot_im, ti.data(), ti.size()))) return rc;
+        if ((rc = dev_upload(h, &h->hs_pair, pq.data(), np))) return rc;
+        if (nu && (rc = dev_upload(h, &h->hs_pair_im, pqi.data(), nu))) return rc;
+    } else {
+        h->ld_hs = h->ld_hs_im = (long)((mm + 1) & ~(size_t)1);
+        std::vector<double> tr((size_t)K * h->ld_hs, 0.0), ti((size_t)K * h->ld_hs, 0.0);
+        for (size_t r = 0; r < mm; ++r)
+            for (int n = 0; n < K; ++n) {
+                tr[(size_t)n * h->ld_hs + r] = hs_pot[2 * (r * K + n)];
+                ti[(size_t)n * h->ld_hs + r] = hs_pot[2 * (r * K + n) + 1];
+            }
+        if ((rc = dev_upload(h, &h->hs_pot, tr.data(), tr.size()))) return rc;
+        if ((rc = dev_upload(h, &h->hs_pot_im, ti.data(), ti.size()))) return rc;
+    }
+    h->ld_rc = (long)((K + 1) & ~1);
+    if ((rc = upload_rchol(h, rchol, rchol_is_real(rchol, nq * K)))) return rc;
+    if ((rc = dev_upload(h, &h->H1, H1, 2 * mm))) return rc;
+    cache_of(h)->H1.assign(H1, H1 + 4 * mm);
+    return AFQ_OK;
+}
+
 int afq_set_system_hubbard(afq_handle *h, int M, int na, int nb, double U, const double *T) {
     if (h) { h->greens_valid = false; h->gsum_only = false; }
     if (!h || !T) return AFQ_EINVAL;
@@ -554,6 +619,10 @@ int afq_set_trial_multi(afq_handle *h, int ndet, const double *psi, const double
                     dst[0] = src[0]; dst[1] = -src[1];
                 }
         if ((rc = dev_upload(h, &h->msd_psicT, pt.data(), kkp * M))) return rc;
+        if (h->hs_cplx == AFQ_HS_HERMITIAN) {
+            for (double &v : pt) v = -v;
+            if ((rc = dev_upload(h, &h->msd_psicT_neg, pt.data(), kkp * M))) return rc;
+        }
     }
     return AFQ_OK;
 }
@@ -1817,6 +1886,9 @@ int afq_bp_configure(afq_handle *h, int nbp) {
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagation of a Hubbard system: discrete fields only (the reference's propagation/hubbard.py:568-672 reads the history as 0 / 1 fields)");
     if (h->hirsch && h->K != h->M) AFQ_FAIL(h, AFQ_ESTATE, "discrete fields: one per site expected");
     if (h->flags & AFQ_PROP_FREE_PROJECTION) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "no field history in free projection");
+    // the backward step reuses the forward one with fields -conj(x): B(x)^H only when every L_n^H == L_n
+    if (h->hs_cplx == AFQ_HS_GENERAL)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagation with non-Hermitian complex Cholesky vectors");
     const size_t per = (size_t)h->M * h->nt, n = h->nw;
     if ((rc = dev_alloc(h, &h->bp_hist, n * nbp * h->K))) return rc;
     if ((rc = dev_alloc(h, &h->bp_n, n))) return rc;

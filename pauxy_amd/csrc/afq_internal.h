@@ -35,6 +35,7 @@ __device__ inline cplx cdiv(cplx a, cplx b) {
 }
 
 #define AFQ_NSCAL 12
+enum { AFQ_HS_HERMITIAN = 1, AFQ_HS_GENERAL = 2 };       // afq_handle::hs_cplx
 enum { T_GREENS = 0, T_ONEBODY, T_FB, T_VHS, T_EXP, T_OVLP, T_QR, T_ENERGY, T_COUNT };
 
 #define AFQ_NCOUNTERS 8     // afq_counters_ext (include/afqmc_hip.h)
@@ -53,6 +54,14 @@ struct afq_handle {
     bool hs_sym = false;            // L_n symmetric: hs_pot holds only the columns (p <= q), [K, ld_hs]
     double *L_full = nullptr;       // [K, M, Mp] every L_n as a padded row-major matrix (full-G energy; built on first use)
     int2 *hs_pair = nullptr;        // [M(M+1)/2] (p, q) of every packed column
+    // complex Cholesky vectors (afq_set_system_generic_c128): hs_pot holds Re L and hs_pot_im Im L, both transposed.
+    // Hermitian L (L_n[q,p] == conj(L_n[p,q])): Re L packed p <= q as in the symmetric real case (hs_pair), Im L
+    // packed p < q (hs_pair_im); general L: both panels with all M*M columns.  hs_sym stays false.
+    int hs_cplx = 0;                // 0 real, AFQ_HS_HERMITIAN, AFQ_HS_GENERAL
+    double *hs_pot_im = nullptr;    // [K, ld_hs_im]
+    int2 *hs_pair_im = nullptr;     // [M(M-1)/2] (p, q), p < q, of every packed Im column (Hermitian)
+    long ld_hs_im = 0;
+    cplx *L_full_c = nullptr;       // [K, M, Mp] complex L_n for the full-G energy (complex vectors only)
     long ld_hs = 0, ld_rc = 0;      // leading dimensions of hs_pot^T and of rchol_re/im (K rounded up to even)
     bool rchol_real = true;
     double *rchol_re = nullptr;     // f64 [nt*M, ld_rc]
@@ -146,6 +155,10 @@ struct afq_handle {
     cplx *msd_gs = nullptr;         // [nw, ndet nt, M] Ghalf_d scaled by w_d / sum_d w_d
     cplx *msd_S = nullptr;          // [nw, ld_hs] (Gbar + Gbar^T) on the packed columns p <= q (the diagonal: Gbar[p,p])
     double *hs_pk = nullptr;        // [M (M + 1) / 2, ld_rc] packed hs_pot with the field index contiguous
+    // Hermitian complex L (hs_cplx): the antisymmetric half of the averaged-G force bias (k_force_bias_msd_gbar)
+    cplx *msd_psicT_neg = nullptr;  // [ndet nt, M] -conj(psi_d)^T
+    cplx *msd_D = nullptr;          // [nw, ld_hs_im] (Gbar - Gbar^T) on the packed columns p < q
+    double *hs_pk_im = nullptr;     // [M (M - 1) / 2, ld_rc] packed Im L with the field index contiguous
 
     // ---- back-propagation (estimators/back_propagation.py, walkers/stack.py FieldConfig)
     int nbp = 0;                    // field configurations kept per walker (0 = off)

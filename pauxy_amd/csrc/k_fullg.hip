@@ -9,28 +9,34 @@
 // the work-group MFMA GEMM engine in chunks of Cholesky vectors (T is 16 M^2 bytes per (G, n) and is
 // only kept for one chunk); it is O(M/N) more work than the half-rotated energy kernel and is not on
 // the per-step hot path.
+#include <type_traits>
 #include "mfma_gemm_wg.h"
 
-struct FullGTProb {
-    static constexpr bool A_CPLX = true, B_CPLX = false;
+__device__ inline cplx fullg_c(double v) { return cmake(v, 0.0); }
+__device__ inline cplx fullg_c(cplx v) { return v; }
+
+// LT = double: real Cholesky vectors; LT = cplx: complex ones (afq_set_system_generic_c128)
+template <class LT>
+struct FullGTProbT {
+    static constexpr bool A_CPLX = true, B_CPLX = std::is_same<LT, cplx>::value;
     int batch, rows, cols, kdim;     // ng * 2 * nc, M, M, M
     int nc, n0, M, Mp;
     const cplx *G;                   // [ng, 2, M, M]
-    const double *L;                 // [K, M, Mp] (Mp = M rounded up to even, zero padded)
+    const LT *L;                     // [K, M, Mp] (Mp = M rounded up to even, zero padded)
     cplx *T;                         // [batch, M, M]
     __device__ bool active(int) const { return true; }
     __device__ cplx loadA(int b, int row, int k) const { return G[((long)(b / nc) * M + k) * M + row]; }
     __device__ cplx loadB(int b, int k, int col) const {
-        return cmake(L[((long)(n0 + b % nc) * M + k) * Mp + col], 0.0);
+        return fullg_c(L[((long)(n0 + b % nc) * M + k) * Mp + col]);
     }
     __device__ const cplx *ptrA(int b, int row, int k) const { return G + ((long)(b / nc) * M + k) * M + row; }
-    __device__ const double *ptrB(int b, int k, int col) const {
+    __device__ const LT *ptrB(int b, int k, int col) const {
         return L + ((long)(n0 + b % nc) * M + k) * Mp + col;
     }
     static constexpr bool INCR = true;       // incremental refill of the ring engine
     __device__ int klimit(int) const { return kdim; }
     __device__ const cplx *baseA(int b, int row) const { return G + (long)(b / nc) * M * M + row; }
-    __device__ const double *baseB(int b, int col) const { return L + (long)(n0 + b % nc) * M * Mp + col; }
+    __device__ const LT *baseB(int b, int col) const { return L + (long)(n0 + b % nc) * M * Mp + col; }
     __device__ long kstepA() const { return M; }
     __device__ long kstepB(int) const { return Mp; }
     __device__ bool rowok(int, int) const { return true; }
@@ -58,18 +64,48 @@ __global__ void fullg_expand_kernel(const double *hsT, long ld, int sym, int M, 
     L[e] = v;
 }
 
-// one wave per (g, s, n): X = sum_pq L_n[p,q] G_s[p,q]
-__global__ void fullg_coulomb_kernel(const cplx *G, const double *L, cplx *X, int ng2, int M, int Mp, int K) {
+// complex L_n[i][k] from the Re / Im panels of complex Cholesky vectors (afq_internal.h: hs_cplx); Hermitian vectors
+// are packed p <= q (Re, symmetric) and p < q (Im, antisymmetric)
+__global__ void fullg_expand_cplx_kernel(const double *hsR, long ldR, const double *hsI, long ldI, int herm, int M,
+                                         int Mp, int K, cplx *L) {
+    const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    const long per = (long)M * Mp;
+    if (e >= per * K) return;
+    const int n = (int)(e / per), r = (int)(e % per), i = r / Mp, k = r % Mp;
+    double vr = 0.0, vi = 0.0;
+    if (k < M) {
+        if (herm) {
+            const int p = i < k ? i : k, q = i < k ? k : i;
+            vr = hsR[(long)n * ldR + ((long)p * M - (long)p * (p - 1) / 2 + (q - p))];
+            if (p != q) {
+                const double v = hsI[(long)n * ldI + ((long)p * M - (long)p * (p + 1) / 2 + (q - p - 1))];
+                vi = i < k ? v : -v;
+            }
+        } else {
+            vr = hsR[(long)n * ldR + (long)i * M + k];
+            vi = hsI[(long)n * ldI + (long)i * M + k];
+        }
+    }
+    L[e] = cmake(vr, vi);
+}
+
+__device__ inline void fullg_acc(double v, cplx g, double &sx, double &sy) { sx += v * g.x; sy += v * g.y; }
+__device__ inline void fullg_acc(cplx v, cplx g, double &sx, double &sy) {
+    sx += v.x * g.x - v.y * g.y; sy += v.x * g.y + v.y * g.x;
+}
+
+// one wave per (g, s, n): X = sum_pq L_n[p,q] G_s[p,q]  (unconjugated L, estimators/generic.py:156-221)
+template <class LT>
+__global__ void fullg_coulomb_kernel(const cplx *G, const LT *L, cplx *X, int ng2, int M, int Mp, int K) {
     const long t = blockIdx.x * (long)(blockDim.x >> 6) + (threadIdx.x >> 6);
     if (t >= (long)ng2 * K) return;
     const int gs = (int)(t / K), n = (int)(t % K), lane = threadIdx.x & 63;
     const cplx *g = G + (long)gs * M * M;
-    const double *l = L + (long)n * M * Mp;
+    const LT *l = L + (long)n * M * Mp;
     double sx = 0.0, sy = 0.0;
     for (int e = lane; e < M * M; e += 64) {
         const int i = e / M, k = e % M;
-        const double v = l[i * Mp + k];
-        sx += v * g[e].x; sy += v * g[e].y;
+        fullg_acc(l[i * Mp + k], g[e], sx, sy);
     }
     for (int o = 32; o > 0; o >>= 1) { sx += __shfl_down(sx, o); sy += __shfl_down(sy, o); }
     if (lane == 0) X[t] = cmake(sx, sy);
@@ -145,15 +181,9 @@ template <class T> struct Scratch {
 }  // namespace
 
 // G_dev [ng, 2, M, M] -> E_dev [ng, 3]
-int k_energy_full_g(afq_handle *h, const cplx *G_dev, int ng, cplx *E_dev) {
+template <class LT>
+static int energy_full_g(afq_handle *h, const LT *Lf, const cplx *G_dev, int ng, cplx *E_dev) {
     const int M = h->M, K = h->K, Mp = (M + 1) & ~1;
-    if (!h->L_full) {
-        AFQ_HIP(h, hipMalloc(&h->L_full, sizeof(double) * (size_t)K * M * Mp));
-        const long n = (long)K * M * Mp;
-        AFQ_LAUNCH(h, fullg_expand_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->hs_pot,
-                           h->ld_hs, h->hs_sym ? 1 : 0, M, Mp, K, h->L_full);
-        AFQ_POST(h);
-    }
     const int ng2 = 2 * ng;
     // chunk of Cholesky vectors: T workspace <= ~1.5 GB
     const size_t per_n = (size_t)ng2 * M * M * sizeof(cplx);
@@ -167,18 +197,18 @@ int k_energy_full_g(afq_handle *h, const cplx *G_dev, int ng, cplx *E_dev) {
     AFQ_HIP(h, hipMemsetAsync(exx, 0, sizeof(cplx) * (size_t)ng2, h->stream));
     {
         const long nt = (long)ng2 * K;
-        AFQ_LAUNCH(h, fullg_coulomb_kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, h->stream, G_dev,
-                           h->L_full, X, ng2, M, Mp, K);
+        AFQ_LAUNCH(h, fullg_coulomb_kernel<LT>, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, h->stream, G_dev,
+                           Lf, X, ng2, M, Mp, K);
         AFQ_POST(h);
     }
     int rc = AFQ_OK;
     for (int n0 = 0; n0 < K && !rc; n0 += nc) {
         const int cur = std::min(nc, K - n0);
-        FullGTProb p;
+        FullGTProbT<LT> p;
         p.batch = ng2 * cur; p.rows = M; p.cols = M; p.kdim = M; p.nc = cur; p.n0 = n0; p.M = M; p.Mp = Mp;
-        p.G = G_dev; p.L = h->L_full; p.T = T;
+        p.G = G_dev; p.L = Lf; p.T = T;
         afq_note_launch(h, "FullGTProb GEMM");
-        hipError_t e = launch_mfma_gemm_wg<2, 2, 2, 2, 4, FullGTProb, MAP_COLS_FAST>(p, h->stream, h->zero_page);
+        hipError_t e = launch_mfma_gemm_wg<2, 2, 2, 2, 4, FullGTProbT<LT>, MAP_COLS_FAST>(p, h->stream, h->zero_page);
         if (e == hipSuccess) e = afq_post_launch(h);
         if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = AFQ_EHIP; break; }
         AFQ_LAUNCH(h, fullg_trace_kernel, dim3((unsigned)p.batch), dim3(256), 0, h->stream, T, part, M);
@@ -192,4 +222,26 @@ int k_energy_full_g(afq_handle *h, const cplx *G_dev, int ng, cplx *E_dev) {
     }
     hipStreamSynchronize(h->stream);       // the scratch buffers are released on return
     return rc;
+}
+
+int k_energy_full_g(afq_handle *h, const cplx *G_dev, int ng, cplx *E_dev) {
+    const int M = h->M, K = h->K, Mp = (M + 1) & ~1;
+    const long n = (long)K * M * Mp;
+    if (h->hs_cplx) {
+        if (!h->L_full_c) {
+            AFQ_HIP(h, hipMalloc(&h->L_full_c, sizeof(cplx) * (size_t)n));
+            AFQ_LAUNCH(h, fullg_expand_cplx_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
+                       h->hs_pot, h->ld_hs, h->hs_pot_im, h->ld_hs_im, h->hs_cplx == AFQ_HS_HERMITIAN ? 1 : 0, M, Mp,
+                       K, h->L_full_c);
+            AFQ_POST(h);
+        }
+        return energy_full_g<cplx>(h, h->L_full_c, G_dev, ng, E_dev);
+    }
+    if (!h->L_full) {
+        AFQ_HIP(h, hipMalloc(&h->L_full, sizeof(double) * (size_t)n));
+        AFQ_LAUNCH(h, fullg_expand_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->hs_pot,
+                           h->ld_hs, h->hs_sym ? 1 : 0, M, Mp, K, h->L_full);
+        AFQ_POST(h);
+    }
+    return energy_full_g<double>(h, h->L_full, G_dev, ng, E_dev);
 }

@@ -387,6 +387,9 @@ static int force_bias_generic_impl(afq_handle *h) {
 //        S[p,q] = sum_k X[k,p] Y[k,q],  X = [conj(psi)^T ; gs],  Y = [gs ; conj(psi)^T]   (k over 2 ndet nt),
 //      strictly lower work-group tiles skipped, the diagonal halved, stored straight into the packed columns
 //   3. ForceBiasProb with A = S [nw, P] and B = the packed hs_pot with the field index contiguous [P, K]
+// Hermitian complex L (hs_cplx): sum_pq L_pq Gbar_pq = sum_{p<=q} Re L_pq S_pq + i sum_{p<q} Im L_pq D_pq with the
+// antisymmetric D = Gbar - Gbar^T on the columns p < q -- the same doubled-contraction product against -conj(psi)^T in its
+// second segment (GbarProbT<true>) -- and a second contraction with the packed Im L added as i (D . Im L) (imag_pass).
 __global__ void msd_scale_ghalf_kernel(const cplx *__restrict__ ghalf_all, const cplx *__restrict__ detw,
                                        cplx *__restrict__ gs, int nw, int ndet, long per, long wstride) {
     const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -417,12 +420,14 @@ __global__ void transpose_f64_kernel(const double *__restrict__ in, double *__re
     }
 }
 
-struct GbarSymProb {
+template <bool ANTI>
+struct GbarProbT {
     static constexpr bool A_CPLX = true, B_CPLX = true, TILE_SKIP = true;
     int batch, rows, cols, kdim;     // nw, M, M, 2 KK
     int KK, M;
     long ldS;
     const cplx *psicT;               // [KK, M]
+    const cplx *psicT2;              // B's second segment: psicT, or -conj(psi)^T for ANTI
     const cplx *gs;                  // [nw, KK, M]
     cplx *S;                         // [nw, ldS]
     __device__ bool active(int) const { return true; }
@@ -431,7 +436,7 @@ struct GbarSymProb {
         return k < KK ? psicT + (long)k * M + row : gs + ((long)b * KK + (k - KK)) * M + row;
     }
     __device__ const cplx *ptrB(int b, int k, int col) const {
-        return k < KK ? gs + ((long)b * KK + k) * M + col : psicT + (long)(k - KK) * M + col;
+        return k < KK ? gs + ((long)b * KK + k) * M + col : psicT2 + (long)(k - KK) * M + col;
     }
     __device__ cplx loadA(int b, int row, int k) const { return *ptrA(b, row, k); }
     __device__ cplx loadB(int b, int k, int col) const { return *ptrB(b, k, col); }
@@ -443,28 +448,38 @@ struct GbarSymProb {
     __device__ const cplx *baseA(int, int row) const { return psicT + row; }
     __device__ const cplx *baseB(int b, int col) const { return gs + (long)b * KK * M + col; }
     __device__ const cplx *baseA2(int b, int row) const { return gs + (long)b * KK * M + row; }
-    __device__ const cplx *baseB2(int, int col) const { return psicT + col; }
+    __device__ const cplx *baseB2(int, int col) const { return psicT2 + col; }
     __device__ long kstepA() const { return M; }
     __device__ long kstepB(int) const { return M; }
     __device__ bool rowok(int, int) const { return true; }
     __device__ bool colok(int, int) const { return true; }
     __device__ void store(int b, int row, int col, double re, double im) const {
+        if constexpr (ANTI) {
+            if (row >= col) return;
+            S[(long)b * ldS + (long)row * M - (long)row * (row + 1) / 2 + (col - row - 1)] = cmake(re, im);
+            return;
+        }
         if (row > col) return;
         const double f = row == col ? 0.5 : 1.0;
         S[(long)b * ldS + (long)row * M - (long)row * (row - 1) / 2 + (col - row)] = cmake(f * re, f * im);
     }
 };
 
+typedef GbarProbT<false> GbarSymProb;
+
 static double msd_fb_cost_per_det(const afq_handle *h) {
     return (double)h->ndet * (h->rchol_real ? 1.0 : 2.0) * h->K * (double)h->nt * h->M;
 }
 static double msd_fb_cost_gbar(const afq_handle *h) {
     // real-by-complex products; a 3-multiplication complex product counts 1.5
+    if (h->hs_cplx == AFQ_HS_HERMITIAN)          // two packed contractions and two fold products
+        return (double)h->K * h->M * h->M + 3.0 * (double)h->M * h->M * h->ndet * h->nt;
     return (double)h->K * h->M * (h->M + 1) / 2.0 + 1.5 * (double)h->M * h->M * h->ndet * h->nt;
 }
 
 bool k_msd_gbar_wanted(afq_handle *h) {
-    if (h->ndet <= 1 || h->kind != AFQ_SYS_GENERIC || !h->hs_sym || h->no_ring || !h->msd_psicT) return false;
+    if (h->ndet <= 1 || h->kind != AFQ_SYS_GENERIC || h->no_ring || !h->msd_psicT) return false;
+    if (!h->hs_sym && !(h->hs_cplx == AFQ_HS_HERMITIAN && h->msd_psicT_neg)) return false;
     if (2 * h->fb_split > FB_MAX_BATCH) return false;
     if (h->msd_fb_mode == 1) return false;
     if (h->msd_fb_mode == 2) return true;
@@ -496,7 +511,7 @@ int k_force_bias_msd_gbar(afq_handle *h) {
     {
         GbarSymProb p;
         p.batch = nw; p.rows = M; p.cols = M; p.kdim = 2 * KK; p.KK = KK; p.M = M; p.ldS = h->ld_hs;
-        p.psicT = h->msd_psicT; p.gs = h->msd_gs; p.S = h->msd_S;
+        p.psicT = h->msd_psicT; p.psicT2 = h->msd_psicT; p.gs = h->msd_gs; p.S = h->msd_S;
 #ifdef AFQ_TUNING
         const int gcfg = AFQ_KNOB_INT("AFQ_GBAR_CFG", 0);
         if (gcfg == 1) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GbarSymProb, MAP_BATCH_XCD, true, 1, 3>(p, h->stream, h->zero_page)));
@@ -523,6 +538,28 @@ int k_force_bias_msd_gbar(afq_handle *h) {
         else
             AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 1, 1, 4, GbarSymProb, MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
     }
+    const bool herm = h->hs_cplx == AFQ_HS_HERMITIAN;
+    const long PI = (long)M * (M - 1) / 2;
+    if (herm && PI > 0) {
+        if (!h->hs_pk_im) {
+            AFQ_HIP(h, hipMalloc(&h->hs_pk_im, sizeof(double) * (size_t)PI * h->ld_rc));
+            AFQ_HIP(h, hipMemsetAsync(h->hs_pk_im, 0, sizeof(double) * (size_t)PI * h->ld_rc, h->stream));
+            AFQ_LAUNCH(h, transpose_f64_kernel, dim3((unsigned)((PI + 31) / 32), (unsigned)((h->K + 31) / 32)), dim3(32, 8), 0,
+                       h->stream, h->hs_pot_im, h->hs_pk_im, h->K, PI, h->ld_hs_im, h->ld_rc);
+            AFQ_POST(h);
+        }
+        if (!h->msd_D) {
+            AFQ_HIP(h, hipMalloc(&h->msd_D, sizeof(cplx) * (size_t)nw * h->ld_hs_im));
+            AFQ_HIP(h, hipMemsetAsync(h->msd_D, 0, sizeof(cplx) * (size_t)nw * h->ld_hs_im, h->stream));
+        }
+        GbarProbT<true> p;
+        p.batch = nw; p.rows = M; p.cols = M; p.kdim = 2 * KK; p.KK = KK; p.M = M; p.ldS = h->ld_hs_im;
+        p.psicT = h->msd_psicT; p.psicT2 = h->msd_psicT_neg; p.gs = h->msd_gs; p.S = h->msd_D;
+        if (M > 64)
+            AFQ_GEMM_AS(h, "msd_gbar_fold_anti GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GbarProbT<true>, MAP_COLS_FAST, true, 1, 5, 4>(p, h->stream, h->zero_page)));
+        else
+            AFQ_GEMM_AS(h, "msd_gbar_fold_anti GEMM", (launch_mfma_gemm_wg<2, 2, 1, 1, 4, GbarProbT<true>, MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
+    }
     {
         ForceBiasProb<false> p;
         fill_force_bias(p, h);
@@ -537,13 +574,32 @@ int k_force_bias_msd_gbar(afq_handle *h) {
         p.kdim = kmax; p.ghalf = h->msd_S; p.astride = h->ld_hs; p.rre = h->hs_pk; p.rim = nullptr; p.out = h->vbias_all;
         AFQ_GEMM_AS(h, "msd_gbar_contract GEMM", (launch_mfma_gemm_wg<4, 2, 1, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
     }
+    if (herm && PI > 0) {
+        // + i sum_{p<q} Im L_pq D_pq, added onto the partials above (every consumer sums all 2 * fb_split of them)
+        ForceBiasProb<false> p;
+        fill_force_bias(p, h);
+        const int ns2 = 2 * h->fb_split;
+        const long slice = (PI + ns2 - 1) / ns2;
+        int kmax = 0;
+        for (int b = 0; b < ns2; ++b) {
+            long l = PI - b * slice; if (l > slice) l = slice; if (l < 0) l = 0;
+            p.q0[b] = b * slice; p.len[b] = (int)l;
+            if (l > kmax) kmax = (int)l;
+        }
+        p.kdim = kmax; p.ghalf = h->msd_D; p.astride = h->ld_hs_im; p.rre = h->hs_pk_im; p.rim = nullptr;
+        p.out = h->vbias_all; p.imag_pass = 1;
+        AFQ_GEMM_AS(h, "msd_gbar_contract_im GEMM", (launch_mfma_gemm_wg<4, 2, 1, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
+    }
     return AFQ_OK;
 }
 
 // --------------------------------------------------------------------- VHS
 // rows = walkers, cols = (p,q) pairs, contraction over fields.
 // hsT is hs_pot transposed, [K, M*M], so a B fragment is 128 contiguous bytes.
-struct VhsProb {
+// IM: the second launch of complex Cholesky vectors (k_vhs_generic_cplx): hsT is the Im L panel and the product is ADDED
+// as i sqrt(dt) * i * (re + i im); with pair, Im L_n is antisymmetric and (q,p) receives the negated value.
+template <bool IM>
+struct VhsProbT {
     static constexpr bool A_CPLX = true, B_CPLX = false;
     int batch, rows, cols, kdim;     // 1, nw, M*M, K
     const cplx *xs;                  // [nw, K]
@@ -573,6 +629,19 @@ struct VhsProb {
     __device__ bool rowok(int, int) const { return true; }
     __device__ bool colok(int, int) const { return true; }
     __device__ void store(int, int row, int col, double re, double im) const {
+        if constexpr (IM) {
+            // -sqrt(dt)*(re + i im); out already holds the Re L product of the same launch order
+            const cplx v = cmake(-sqrt_dt * re, -sqrt_dt * im);
+            cplx *o = out + (long)row * mm;
+            if (pair) {
+                const int2 pq = pair[col];
+                o[pq.x * M + pq.y] = cadd(o[pq.x * M + pq.y], v);
+                o[pq.y * M + pq.x] = cmake(o[pq.y * M + pq.x].x - v.x, o[pq.y * M + pq.x].y - v.y);
+            } else {
+                o[col] = cadd(o[col], v);
+            }
+            return;
+        }
         // i*sqrt(dt)*(re + i im)
         const cplx v = cmake(-sqrt_dt * im, sqrt_dt * re);
         if (pair) {
@@ -585,6 +654,8 @@ struct VhsProb {
         }
     }
 };
+
+typedef VhsProbT<false> VhsProb;
 
 #ifdef AFQ_TUNING
 static void gemm_ts_dump(afq_handle *h, const char *what) {
@@ -607,7 +678,57 @@ static void gemm_ts_dump(afq_handle *h, const char *what) {
 }
 #endif
 
+// complex Cholesky vectors L_n = R_n + i I_n:  VHS = i sqrt(dt) (x R + i x I), two real-B products in stream order --
+// the Re panel writes VHS (Hermitian: packed p <= q columns, R symmetric, mirrored store; general: all M*M columns), the
+// Im panel adds to it (Hermitian: packed p < q columns, I antisymmetric; general: all M*M).  Hermitian vectors cost
+// twice the MFMA work of the packed real product, general ones twice the unpacked real product.  VHS is neither
+// symmetric nor Hermitian: both triangles are stored (vhs_upper is never set: hs_sym is false).
+template <class P>
+static int vhs_cplx_launch(afq_handle *h, P p, bool packed, double *flops) {
+    if (h->nw > 32 && !h->no_ring) {
+        if (packed) {
+            AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, P, MAP_COLPANEL_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
+            *flops += mfma_gemm_wg_issued_flops<2, 2, 1, 5, P>(p, [&](int, int, int) -> long { return p.kdim; });
+        } else {
+            AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 5, 4, P, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
+            *flops += mfma_gemm_wg_issued_flops<2, 2, 2, 5, P>(p, [&](int, int, int) -> long { return p.kdim; });
+        }
+        return AFQ_OK;
+    }
+    static const TileChoice cand[] = {{2, 4}, {2, 2}, {1, 4}, {1, 2}};
+    const TileChoice tc = pick_tiles(p.batch, p.rows, p.cols, cand, 4);
+    const int tiles_m = (p.rows + 16 * tc.tm - 1) / (16 * tc.tm);
+    int wpb = tiles_m <= 8 ? (tiles_m < 1 ? 1 : tiles_m) : 8;
+    const long ntask = mfma_gemm_tasks(p.batch, p.rows, p.cols, tc.tm, tc.tn);
+    while (wpb > 1 && ntask / wpb < 200) wpb >>= 1;
+    DISPATCH_TILES(h, p, tc, MAP_ROWS_FAST, wpb);
+    // (small-tile engine: every wave-task runs the whole contraction in chunks of 8, two real MFMAs per fragment pair)
+    const long tm = (p.rows + 16 * tc.tm - 1) / (16 * tc.tm), tn = (p.cols + 16 * tc.tn - 1) / (16 * tc.tn);
+    *flops += 2.0 * 2.0 * (double)tm * tn * 256.0 * tc.tm * tc.tn * (double)((p.kdim + 7) / 8 * 8);
+    return AFQ_OK;
+}
+
+static int k_vhs_generic_cplx(afq_handle *h) {
+    const bool herm = h->hs_cplx == AFQ_HS_HERMITIAN;
+    const int M = h->M;
+    VhsProbT<false> pr;
+    pr.batch = 1; pr.rows = h->nw; pr.cols = herm ? M * (M + 1) / 2 : M * M; pr.kdim = h->K;
+    pr.xs = h->xs; pr.hsT = h->hs_pot; pr.ldb = h->ld_hs; pr.out = h->vhs; pr.sqrt_dt = h->sqrt_dt; pr.alive = h->alive;
+    pr.pair = herm ? h->hs_pair : nullptr; pr.M = M; pr.mm = (long)M * M; pr.mirror = true;
+    VhsProbT<true> pi;
+    pi.batch = 1; pi.rows = h->nw; pi.cols = herm ? M * (M - 1) / 2 : M * M; pi.kdim = h->K;
+    pi.xs = h->xs; pi.hsT = h->hs_pot_im; pi.ldb = h->ld_hs_im; pi.out = h->vhs; pi.sqrt_dt = h->sqrt_dt;
+    pi.alive = h->alive; pi.pair = herm ? h->hs_pair_im : nullptr; pi.M = M; pi.mm = (long)M * M; pi.mirror = true;
+    KernelTrace kt(h, AFQ_K_VHS);
+    double flops = 0.0;
+    int rc = vhs_cplx_launch(h, pr, herm, &flops);
+    if (!rc && pi.cols > 0) rc = vhs_cplx_launch(h, pi, herm, &flops);
+    h->issued_flops[AFQ_K_VHS] = flops;
+    return rc;
+}
+
 int k_vhs_generic(afq_handle *h) {
+    if (h->hs_cplx) return k_vhs_generic_cplx(h);
 #ifdef AFQ_TUNING
     struct Dump { afq_handle *h; ~Dump() { gemm_ts_dump(h, "after VHS"); } } dump_{h};
     // timing ablations of the ring loop (mfma_gemm_wg.h: afq_gemm_abl), for this GEMM only: set and cleared in stream order

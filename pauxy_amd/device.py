@@ -75,12 +75,15 @@ class AfqDevice(object):
     def set_system_generic(self, hs_pot, rchol, H1, ecore, na, nb):
         H1 = _c128(H1)
         M = H1.shape[-1]
-        hs_pot = _f64(hs_pot)
+        # complex Cholesky vectors with an imaginary part go to the c128 entry point; everything else
+        # takes the real one unchanged
+        cplx = numpy.iscomplexobj(hs_pot) and bool(numpy.any(numpy.asarray(hs_pot).imag != 0))
+        hs_pot = _c128(hs_pot) if cplx else _f64(hs_pot)
         K = hs_pot.shape[1]
         assert hs_pot.shape == (M * M, K)
         rchol = _c128(rchol, ((na + nb) * M, K))
-        self._ck(self.lib.afq_set_system_generic(self.h, M, K, na, nb, _p(hs_pot), _p(rchol), _p(H1),
-                                                 float(numpy.real(ecore))))
+        fn = self.lib.afq_set_system_generic_c128 if cplx else self.lib.afq_set_system_generic
+        self._ck(fn(self.h, M, K, na, nb, _p(hs_pot), _p(rchol), _p(H1), float(numpy.real(ecore))))
         self.kind, self.M, self.K, self.na, self.nb = 'generic', M, K, na, nb
 
     def set_system_hubbard(self, T, U, na, nb):

@@ -41,6 +41,13 @@ class BackPropagation(object):
             raise NotImplementedError("device back-propagation: one-body RDM and energies; no two_rdm / EKT")
         if self.eval_energy and system.name != "Generic":
             raise NotImplementedError("back-propagated energies: Generic systems")
+        if (system.name == "Generic" and numpy.iscomplexobj(system.hs_pot)
+                and numpy.any(numpy.asarray(system.hs_pot).imag != 0)):
+            # the backward step applies B(-conj(x)) with the same L_n: B(x)^H only when every L_n is Hermitian
+            M = system.nbasis
+            L3 = numpy.asarray(system.hs_pot).reshape(M, M, -1)
+            if not numpy.array_equal(L3, L3.conj().transpose(1, 0, 2)):
+                raise NotImplementedError("back-propagation with non-Hermitian complex Cholesky vectors")
         if self.nmax < 1:
             raise ValueError("tau_bp shorter than one time step")
         M = system.nbasis
