@@ -271,7 +271,8 @@ int afq_exchange_algorithm(afq_handle *h, int *mode_out);
  *      conj(c_d) <D_d|phi> afterwards (ndet, or 2 ndet for complex vectors, times K (Na + Nb) M products)
  *   2  the reference's own formulation: the weights go into ONE determinant-averaged Green's function
  *      Gbar = sum_d w_d conj(psi_d) Ghalf_d / sum_d w_d, contracted once with the symmetric-packed hs_pot
- *      (K M (M + 1) / 2 products + the build of Gbar); needs symmetric L_n
+ *      (K M (M + 1) / 2 products + the build of Gbar); needs symmetric real or Hermitian complex L_n (general complex
+ *      L_n always run mode 1, whatever is asked for)
  * mode 0 (default) picks 2 when it is the cheaper one for more than 32 walkers.  afq_msd_force_bias: what the next
  * force bias will use (0 for a single-determinant trial).                                                          */
 int afq_set_msd_force_bias(afq_handle *h, int mode);

@@ -585,8 +585,10 @@ static int launch_exx_quadratic(afq_handle *h, int *S_out, bool *two_pass) {
     // Ghalf comes from: closed_checked_version) and one Atil for both spins: the 2 S slices of the FIRST launch all belong to
     // spin alpha (every XCD busy), the second launch holds spin beta's and returns at once on the device when the flag says
     // closed; energy_finish_kernel then counts the alpha sums twice.  Nothing is decided on the host.
-    if (h->closed_bad && h->closed_checked_version != h->ghalf_version && k_greens_big_supported(h) && h->ndet == 1 &&
-        h->na == h->nb && h->atil[0] == h->atil[1] && !h->exx_open_hint && !AFQ_KNOB_SET("AFQ_NO_CLOSED_EXX")) {
+    // (the small Green's function kernel checks the spin blocks only beside the spin sum of real half-rotated vectors,
+    //  k_fb_use_sum: complex ones -- a complex trial, or complex Cholesky vectors -- are checked here, as the large systems are)
+    if (h->closed_bad && h->closed_checked_version != h->ghalf_version && (k_greens_big_supported(h) || !h->rchol_real) &&
+        h->ndet == 1 && h->na == h->nb && h->atil[0] == h->atil[1] && !h->exx_open_hint && !AFQ_KNOB_SET("AFQ_NO_CLOSED_EXX")) {
         // (an open-shell population is found out by the first evaluation's published verdict, exx_open_hint: no check, and
         //  the two-spin launch, from then on)
         AFQ_LAUNCH(h, ghalf_closed_check_kernel, dim3(h->nw), dim3(256), 0, h->stream, h->ghalf, nma, h->closed_bad, ++h->closed_epoch);

@@ -61,6 +61,13 @@ def ueg_model(d, tag, systag=''):
                         ecore=float(d[systag + 'ecore']))
 
 
+def cplx_chol(M, K, herm, rng):
+    """Complex Cholesky vectors [M*M, K]: Hermitian L_n (herm) or general ones, entries O(0.3 / sqrt(M))."""
+    A = (rng.normal(size=(K, M, M)) + 1j * rng.normal(size=(K, M, M))) * (0.3 / numpy.sqrt(M))
+    Ln = 0.5 * (A + A.conj().transpose(0, 2, 1)) if herm else A
+    return numpy.ascontiguousarray(Ln.reshape(K, M * M).T)
+
+
 def make_device(model, nw, device_id=0, **prop_kw):
     """RefModel (plain arrays) -> AfqDevice with nw walkers allocated."""
     from pauxy_amd.device import AfqDevice
@@ -85,3 +92,16 @@ def make_device(model, nw, device_id=0, **prop_kw):
     dev.set_propagator(model.BH1, model.mf_shift, model.dt, exp_order=model.exp_order, **prop_kw)
     dev.walkers_alloc(nw)
     return dev
+
+
+def lform_params(rows, lforms, extra_ids=None):
+    """pytest.param rows x Cholesky forms ('real', 'hermitian', 'general'), lform the last argument.  The real rows keep
+    the ids pytest gives the bare rows; the complex ones are prefixed with their form.  extra_ids: {row: id} for rows
+    whose id is not the plain join of their values."""
+    import pytest
+    out = []
+    for lf in lforms:
+        for r in rows:
+            rid = (extra_ids or {}).get(r) or "-".join(str(x) for x in r)
+            out.append(pytest.param(*r, lf, id=rid if lf == 'real' else lf + "-" + rid))
+    return out

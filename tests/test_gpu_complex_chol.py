@@ -13,7 +13,7 @@ from pauxy_amd import systems, trial as trial_mod
 from pauxy_amd.context import release_context
 from pauxy_amd.device import AfqDevice
 from pauxy_amd.propagation import setup
-from tests.helpers import generic_model, make_device, msd_model
+from tests.helpers import cplx_chol, generic_model, make_device, msd_model
 from tests.test_gpu_traj import replay
 
 pytestmark = pytest.mark.gpu
@@ -28,17 +28,15 @@ def close(a, b, tol=TOL):
     assert err <= tol, err
 
 
-def cplx_chol(M, K, herm, rng):
-    A = (rng.normal(size=(K, M, M)) + 1j * rng.normal(size=(K, M, M))) * (0.3 / numpy.sqrt(M))
-    Ln = 0.5 * (A + A.conj().transpose(0, 2, 1)) if herm else A
-    return numpy.ascontiguousarray(Ln.reshape(K, M * M).T)
-
-
-def build(M, K, na, nb, herm, complex_trial=True, seed=3, dt=0.01):
+def build(M, K, na, nb, herm, complex_trial=True, seed=3, dt=0.01, edit=None):
+    """edit: a function of the drawn Cholesky vectors [M*M, K] returning the ones the system gets."""
     rng = numpy.random.RandomState(seed)
     h = rng.normal(size=(M, M))
     h1e = 0.5 * (h + h.T) - 2.0 * numpy.eye(M)
-    s = systems.Generic((na, nb), numpy.array([h1e, h1e]), cplx_chol(M, K, herm, rng), ecore=0.37)
+    chol = cplx_chol(M, K, herm, rng)
+    if edit is not None:
+        chol = numpy.ascontiguousarray(edit(chol))
+    s = systems.Generic((na, nb), numpy.array([h1e, h1e]), chol, ecore=0.37)
     e, v = numpy.linalg.eigh(h1e)
     psi = numpy.zeros((M, na + nb), dtype=complex)
     psi[:, :na] = v[:, :na]
@@ -282,32 +280,158 @@ def test_c3_closed_shell_walkers():
     dev.close()
 
 
-@pytest.mark.parametrize("M,nw", [(21, 5), (37, 40)])
-def test_real_values_as_c128_bitwise(M, nw):
-    """An hs_pot with zero imaginary parts through the c128 entry point takes the real path: bitwise equal results."""
+@pytest.mark.parametrize("M,nw,na,nb,imag", [
+    pytest.param(21, 5, 4, 3, 0.0, id="21-5"), pytest.param(37, 40, 4, 3, 0.0, id="37-40"),
+    pytest.param(21, 5, 4, 3, -0.0, id="negzero-21-5"), pytest.param(37, 40, 4, 3, -0.0, id="negzero-37-40"),
+    pytest.param(105, 33, 4, 3, -0.0, id="negzero-105-33"),             # M = 105: the separate-GEMM propagator
+    pytest.param(136, 64, 40, 40, -0.0, id="negzero-136-64-closed"),    # the large-system chain, closed-shell walkers
+])
+def test_real_values_as_c128_bitwise(M, nw, na, nb, imag):
+    """An hs_pot with zero imaginary parts (+0.0 or -0.0) through the c128 entry point takes the real path: bitwise
+    equal results."""
     from tests.test_gpu_sizes import build as build_real
-    model, rng = build_real(M, 30, 4, 3, True)
+    closed = na == nb
+    model, rng = build_real(M, 30, na, nb, not closed)
     phis = walkers(model, rng, nw)
+    if closed:
+        phis[:, :, nb:] = phis[:, :, :na]                   # bitwise equal spin blocks: the closed-shell forms engage
     xi = rng.normal(size=(nw, 30))
     res = []
     for entry in ('f64', 'c128'):
         dev = AfqDevice(0)
-        hs = numpy.ascontiguousarray(model.hs_pot, dtype=numpy.complex128)
+        hs = numpy.empty(model.hs_pot.shape, dtype=numpy.complex128)
+        hs.real = model.hs_pot.real
+        hs.imag = imag
+        assert numpy.all(numpy.signbit(hs.imag) == numpy.signbit(imag))
         rchol = numpy.ascontiguousarray(model.rchol, dtype=numpy.complex128)
         H1 = numpy.ascontiguousarray(model.H1, dtype=numpy.complex128)
         f = dev.lib.afq_set_system_generic_c128 if entry == 'c128' else dev.lib.afq_set_system_generic
         hs_arg = hs if entry == 'c128' else numpy.ascontiguousarray(model.hs_pot, dtype=numpy.float64)
-        dev._ck(f(dev.h, M, 30, 4, 3, hs_arg.ctypes.data_as(ctypes.c_void_p), rchol.ctypes.data_as(ctypes.c_void_p),
+        dev._ck(f(dev.h, M, 30, na, nb, hs_arg.ctypes.data_as(ctypes.c_void_p), rchol.ctypes.data_as(ctypes.c_void_p),
                   H1.ctypes.data_as(ctypes.c_void_p), 0.37))
-        dev.kind, dev.M, dev.K, dev.na, dev.nb = 'generic', M, 30, 4, 3
+        dev.kind, dev.M, dev.K, dev.na, dev.nb = 'generic', M, 30, na, nb
         dev.set_trial(model.psi)
         dev.set_propagator(model.BH1, model.mf_shift, model.dt)
         dev.walkers_alloc(nw)
         dev.set(L.F_PHI, phis)
         dev.set(L.F_OT, dev.calc_overlap())
+        dev.counters(reset=True, n=8)
         dev.propagate(xi, -1.5)
+        if closed:
+            assert int(dev.counters(n=8)[7]) == nw
         dev.greens()
         res.append((dev.get(L.F_PHI), dev.get(L.F_WEIGHT), dev.local_energy()))
         dev.close()
     for a, b in zip(*res):
         assert numpy.array_equal(a, b)
+
+
+def scaled_hermitian(chol, re, im):
+    """Hermitian L_n = R_n + i I_n -> re R_n + i im I_n, set part by part (R stays exactly symmetric, I exactly
+    antisymmetric, a zero factor gives +0.0)."""
+    out = numpy.empty_like(chol)
+    out.real = re * chol.real if re else 0.0
+    out.imag = im * chol.imag
+    return out
+
+
+SCALINGS = {"re>>im": (1.0, 1e-8), "im>>re": (1e-8, 1.0), "imaginary": (0.0, 1.0)}
+
+
+@pytest.mark.parametrize("M,K,na,nb,nw", [(37, 45, 7, 6, 40), (120, 40, 9, 9, 20)])
+@pytest.mark.parametrize("scaling", list(SCALINGS))
+def test_badly_scaled_hermitian_cholesky_vectors(M, K, na, nb, nw, scaling):
+    """Hermitian L = R + i s I with s = 1e-8 and s = 1e8 (written 1e-8 R + i I: |L| stays O(1)) and purely imaginary L
+    (R = 0: the Re panel is all zeros).  Green's function, force bias (complex half-rotated vectors), the two-launch VHS,
+    the local energy under both exchange algorithms, one phaseless step (ring VHS and fused propagator at M = 37,
+    small-tile VHS and the separate GEMMs at M = 120) and the NOMSD force bias of mode 2 (packed Re and Im contractions
+    of the averaged G) against the oracle.  Pins of test_gpu_sizes.test_badly_scaled_operands_through_the_three_
+    multiplication_products: 1e-13 normwise, 1e-10 componentwise on the parts within four decades of the largest."""
+    from tests.test_gpu_sizes import _component_errors
+    re, im = SCALINGS[scaling]
+    model, rng = build(M, K, na, nb, True, edit=lambda c: scaled_hermitian(c, re, im))
+    if scaling == "imaginary":
+        assert numpy.all(model.hs_pot.real == 0.0) and not numpy.any(numpy.signbit(model.hs_pot.real))
+    dev = make_device(model, nw)
+    phis = walkers(model, rng, nw)
+    dev.set(L.F_PHI, phis)
+    det = dev.greens(want_G=True)
+    refs = [model.greens(p) for p in phis]
+    checks = {"det": _component_errors(det, numpy.array([r[0] for r in refs])),
+              "G": _component_errors(dev.get(L.F_G), numpy.array([r[2] for r in refs]))}
+    xbar = dev.force_bias()
+    checks["xbar"] = _component_errors(xbar, numpy.array([model.force_bias(r[1], r[2]) for r in refs]))
+    xs = rng.normal(size=(nw, K)) + 1j * rng.normal(size=(nw, K))
+    checks["vhs"] = _component_errors(dev.vhs(xs)[:, 0], numpy.array([model.vhs(x) for x in xs]))
+    want = numpy.array([model.local_energy(r[2], r[1]) for r in refs])
+    for mode in (1, 2):
+        dev.set_exchange_algorithm(mode)
+        dev.greens()
+        checks["energy%d" % mode] = _component_errors(dev.local_energy(), want)
+    dev.set(L.F_PHI, phis)
+    dev.set(L.F_OT, det)
+    xi = rng.normal(size=(nw, K))
+    dev.propagate(xi, -0.2)
+    sub = sorted({0, 1, nw // 2, nw - 1})
+    ws = [ref.new_walker(model, phis[i]) for i in sub]
+    for w, i in zip(ws, sub):
+        ref.propagate_walker_phaseless(model, w, xi[i], -0.2)
+    checks["phi"] = _component_errors(dev.get(L.F_PHI)[sub], numpy.array([w['phi'] for w in ws]))
+    checks["ot"] = _component_errors(dev.get(L.F_OT)[sub], numpy.array([w['ot'] for w in ws]))
+    checks["weight"] = _component_errors(dev.get(L.F_WEIGHT)[sub], numpy.array([w['weight'] for w in ws]))
+    dev.bp_configure(2)                                   # classified Hermitian: back-propagation is accepted
+    dev.close()
+    # NOMSD, averaged-G force bias with the antisymmetric fold
+    ndet, nt = 3, na + nb
+    dets = numpy.array([model.psi + 0.05 * (rng.rand(M, nt) + 1j * rng.rand(M, nt)) for _ in range(ndet)])
+    coeffs = rng.rand(ndet) + 0.2 + 0.3j * rng.rand(ndet)
+    m = ref.RefModel('generic_msd', M, na, nb, dets, model.BH1, model.mf_shift, model.dt, coeffs=coeffs,
+                     hs_pot=model.hs_pot, H1=model.H1, ecore=model.ecore)
+    dev = make_device(m, nw)
+    dev.set_msd_force_bias(2)
+    assert dev.msd_force_bias() == 2
+    dev.set(L.F_PHI, phis)
+    dev.greens()
+    mrefs = [m.greens(p) for p in phis[sub]]
+    checks["msd_xbar"] = _component_errors(dev.force_bias()[sub], numpy.array([m.force_bias(r[1], r[2]) for r in mrefs]))
+    dev.close()
+    print("badly scaled Hermitian L %s M=%d: " % (scaling, M) +
+          "  ".join("%s %.1e/%.1e" % (k, v[0], v[1]) for k, v in checks.items()))
+    for k, (norm, comp) in checks.items():
+        assert norm <= 1e-13, (k, norm)
+        assert comp <= 1e-10, (k, comp)
+
+
+def test_one_ulp_from_hermitian_is_general():
+    """Hermitian L with the imaginary part of ONE element moved by one ulp is classified general (the test is bitwise):
+    every operator and one step still match the oracle (general form), back-propagation is refused, NOMSD runs mode 1."""
+    from tests.test_gpu_sizes import check_operators_and_step
+
+    def one_ulp(c):
+        c = c.copy()
+        r = 5 * 21 + 9                                   # L_n[5, 9], n = 3
+        c[r, 3] = complex(c[r, 3].real, numpy.nextafter(c[r, 3].imag, numpy.inf))
+        return c
+    M, K, na, nb, nw = 21, 30, 5, 4, 40
+    model, rng = build(M, K, na, nb, True, edit=one_ulp)
+    Ln = model.hs_pot.reshape(M, M, K)
+    assert numpy.count_nonzero(Ln != Ln.conj().transpose(1, 0, 2)) == 2
+    check_operators_and_step(model, rng, nw, 'general')
+    dev = make_device(model, 3)
+    with pytest.raises(L.AfqError) as err:
+        dev.bp_configure(3)
+    assert 'Hermitian' in str(err.value)
+    dev.close()
+    ndet = 3
+    dets = numpy.array([model.psi + 0.05 * (rng.rand(M, na + nb) + 1j * rng.rand(M, na + nb)) for _ in range(ndet)])
+    coeffs = rng.rand(ndet) + 0.2 + 0.3j * rng.rand(ndet)
+    m = ref.RefModel('generic_msd', M, na, nb, dets, model.BH1, model.mf_shift, model.dt, coeffs=coeffs,
+                     hs_pot=model.hs_pot, H1=model.H1, ecore=model.ecore)
+    dev = make_device(m, nw)
+    dev.set_msd_force_bias(2)
+    assert dev.msd_force_bias() == 1
+    phis = walkers(model, rng, nw)
+    dev.set(L.F_PHI, phis)
+    dev.greens()
+    close(dev.force_bias()[:4], numpy.array([m.force_bias(r[1], r[2]) for r in (m.greens(p) for p in phis[:4])]))
+    dev.close()

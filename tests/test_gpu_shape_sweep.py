@@ -3,27 +3,38 @@ electrons per spin (LDS Gauss-Jordan, GEMM-chain propagator), M just above / at 
 128, 130, 200), unequal spins, real and complex trials, populations above and below the work-group-tiled GEMM threshold."""
 import pytest
 
-from tests.test_gpu_sizes import test_midsize_generic as run_shape
+from tests.helpers import lform_params
+from tests.test_gpu_sizes import build, check_operators_and_step
 
 pytestmark = pytest.mark.gpu
+LFORMS = ["real", "hermitian", "general"]
 
 
-@pytest.mark.parametrize("M,K,na,nb,nw,cplx", [
+def run_shape(M, K, na, nb, nw, cplx, lform='real'):
+    """cplx selects a complex trial; lform the Cholesky vectors (real symmetric, Hermitian or general complex)."""
+    model, rng = build(M, K, na, nb, cplx, lform=lform)
+    check_operators_and_step(model, rng, nw, lform)
+
+
+@pytest.mark.parametrize("M,K,na,nb,nw,cplx,lform", lform_params([
     (64, 20, 40, 37, 70, False), (100, 30, 45, 33, 66, True), (130, 16, 20, 20, 70, False), (48, 10, 33, 33, 8, False),
     (200, 12, 10, 9, 65, True), (128, 8, 32, 32, 64, False), (104, 9, 32, 31, 64, False), (105, 9, 26, 25, 64, True),
-])
-def test_operators_and_step_on_boundary_shapes(M, K, na, nb, nw, cplx):
-    run_shape(M, K, na, nb, nw, cplx)
+    # packed Re / Im column counts of Hermitian L (171 / 153, 190 / 171) on either side of the 160-column ring tile,
+    # populations on the 32-walker switch between the small-tile and the ring VHS
+    (18, 5, 4, 3, 33, True), (19, 4, 3, 3, 32, False),
+], LFORMS))
+def test_operators_and_step_on_boundary_shapes(M, K, na, nb, nw, cplx, lform):
+    run_shape(M, K, na, nb, nw, cplx, lform)
 
 
-@pytest.mark.parametrize("M,K,na,nb,nw,cplx", [
+@pytest.mark.parametrize("M,K,na,nb,nw,cplx,lform", lform_params([
     (2, 1, 1, 1, 1, False), (3, 2, 2, 1, 2, True), (4, 2, 4, 3, 5, False), (6, 3, 2, 0, 7, False), (5, 3, 1, 1, 257, True),
     (20, 10, 3, 2, 600, False), (16, 5, 16, 15, 64, False), (33, 4, 1, 0, 64, True), (17, 1, 8, 8, 63, False),
-])
-def test_operators_and_step_on_degenerate_shapes(M, K, na, nb, nw, cplx):
+], LFORMS))
+def test_operators_and_step_on_degenerate_shapes(M, K, na, nb, nw, cplx, lform):
     """The other end: two orbitals, one field, one walker; a filled band (na = M); no beta electrons; populations that are
     not a multiple of any tile (257, 600)."""
-    run_shape(M, K, na, nb, nw, cplx)
+    run_shape(M, K, na, nb, nw, cplx, lform)
 
 
 @pytest.mark.parametrize("nx,ny,na,nb,nw,spin", [
@@ -58,28 +69,40 @@ def test_hirsch_on_small_and_odd_lattices(nx, ny, na, nb, charge, nw):
     run_hirsch_lattice(nx, ny, na, nb, charge, nw)
 
 
-@pytest.mark.parametrize("M,K,na,nb,ndet,nw", [
-    (24, 10, 5, 4, 2, 9), (100, 30, 25, 25, 7, 64), (64, 12, 40, 37, 3, 20), (130, 8, 20, 19, 2, 33), (37, 9, 7, 6, 16, 65),
-    (16, 4, 3, 0, 2, 5), (48, 6, 33, 33, 2, 8),
-])
-def test_distinct_complex_determinants_on_boundary_shapes(M, K, na, nb, ndet, nw):
+_NOMSD_ROWS = [
+    (24, 10, 5, 4, 2, 9, False), (100, 30, 25, 25, 7, 64, False), (64, 12, 40, 37, 3, 20, False),
+    (130, 8, 20, 19, 2, 33, False), (37, 9, 7, 6, 16, 65, False), (16, 4, 3, 0, 2, 5, False), (48, 6, 33, 33, 2, 8, False),
+    # the first shape on the M > 64 templates of the averaged-G folds; a determinant with coefficient exactly 0 (its slice
+    # of the averaged G is zeroed, msd_scale_ghalf_kernel) there and on the M <= 64 templates
+    (65, 10, 20, 19, 3, 40, True), (24, 10, 5, 4, 3, 33, True),
+]
+
+
+@pytest.mark.parametrize("M,K,na,nb,ndet,nw,zero_coeff,lform", lform_params(
+    _NOMSD_ROWS, LFORMS, {r: "-".join(str(x) for x in r[:6]) + ("-zero-coeff" if r[6] else "") for r in _NOMSD_ROWS}))
+def test_distinct_complex_determinants_on_boundary_shapes(M, K, na, nb, ndet, nw, zero_coeff, lform):
     """NOMSD trials of 2..16 distinct complex determinants (walkers/multi_det.py:27-77, propagation/generic.py:154-157,
     estimators/mixed.py:439-448) on the dispatch boundaries of the single-determinant kernels they reuse: determinant
-    weights, total overlap, weighted force bias and energy per walker against the oracle, both exchange algorithms."""
+    weights, total overlap, weighted force bias and energy per walker against the oracle, both exchange algorithms.
+    Complex L: Hermitian vectors take the averaged-G force bias with its antisymmetric fold and imaginary contraction
+    (mode 2), general ones always the per-determinant contraction (mode 1)."""
     import numpy
     from oracle import afqmc_ref as ref
     from pauxy_amd import _lib as L
-    from pauxy_amd import systems, trial as trial_mod
+    from pauxy_amd import trial as trial_mod
     from pauxy_amd.device import AfqDevice
     from pauxy_amd.propagation import setup
+    from tests.test_gpu_sizes import generic_system
     from tests.test_gpu_traj import close
     dt = 0.005
-    s = systems.synthetic_generic(M, K, (na, nb), seed=7)
+    s = generic_system(M, K, (na, nb), 7, lform)
     t0 = trial_mod.rhf_trial_generic(s)
     rng = numpy.random.RandomState(3)
     nt = na + nb
     dets = numpy.array([t0.psi + (0.0 if d == 0 else 0.05) * (rng.rand(M, nt) + 1j * rng.rand(M, nt)) for d in range(ndet)])
     coeffs = (rng.rand(ndet) + 0.2) * numpy.exp(1j * rng.rand(ndet))
+    if zero_coeff:
+        coeffs[1] = 0.0
     t = trial_mod.MultiDetTrial(s, (coeffs, dets), init=t0.psi)
     BH1, mf = setup.generic_propagator_arrays(s, t, dt)
     phis = t0.psi[None] + 0.05 * (rng.rand(nw, M, nt) + 1j * rng.rand(nw, M, nt))
@@ -101,8 +124,18 @@ def test_distinct_complex_determinants_on_boundary_shapes(M, K, na, nb, ndet, nw
         xb = {}
         for fbm in (1, 2):
             dev.set_msd_force_bias(fbm)
-            assert dev.msd_force_bias() == fbm
+            dev.launch_trace(True)
+            # (general complex L has no packed form: the averaged G is not taken, whatever the mode asks for)
+            assert dev.msd_force_bias() == (1 if lform == 'general' else fbm)
             xb[fbm] = dev.force_bias()
+            names = set(dev.launch_trace_get())
+            dev.launch_trace(False)
+            gbar = fbm == 2 and lform != 'general'
+            assert ('msd_gbar_fold GEMM' in names) == gbar, names
+            assert ('msd_gbar_fold_anti GEMM' in names) == (gbar and lform == 'hermitian'), names
+            assert ('msd_gbar_contract_im GEMM' in names) == (gbar and lform == 'hermitian'), names
+            if not gbar:
+                assert not any(n.startswith('msd_gbar') for n in names), names
         close(xb[1], xb[2], 1e-11)
         close(xbar, xb[2], 1e-11)
         dev.set_msd_force_bias(0)
@@ -233,11 +266,12 @@ def test_ueg_on_other_densities_and_cutoffs(rs, nup, ndown, ecut, nw):
     run_fullsize(model, nw, sorted({0, 2, nw // 2, nw - 1}))
 
 
-@pytest.mark.parametrize("K,nw", [(1, 1), (255, 33), (256, 65), (257, 31), (513, 64), (2, 129)])
-def test_field_counts_and_populations_on_kernel_boundaries(K, nw):
+@pytest.mark.parametrize("K,nw,lform", lform_params([(1, 1), (255, 33), (256, 65), (257, 31), (513, 64), (2, 129)],
+                                                    ["real", "hermitian"]))
+def test_field_counts_and_populations_on_kernel_boundaries(K, nw, lform):
     """Field counts around the work-group size of the fields kernel (a thread per field up to 256, a Philox pair per thread
     above), one field, populations around the 32 / 64-walker thresholds of the work-group-tiled GEMMs and a single walker."""
-    run_shape(20, K, 4, 3, nw, K % 2 == 1)
+    run_shape(20, K, 4, 3, nw, K % 2 == 1, lform)
 
 
 @pytest.mark.parametrize("nw", [2, 3, 63, 64, 65, 257, 1000, 4096])
@@ -290,6 +324,22 @@ def _generic_m130():
     return build_afqmc(s, trial_mod.rhf_trial_generic(s), 65)
 
 
+def _generic_40_hermitian():
+    from pauxy_amd import trial as trial_mod
+    from tests.test_gpu_batched import build_afqmc
+    from tests.test_gpu_sizes import generic_system
+    s = generic_system(64, 12, (40, 40), 5, 'hermitian')
+    return build_afqmc(s, trial_mod.rhf_trial_generic(s), 66)
+
+
+def _generic_m130_general():
+    from pauxy_amd import trial as trial_mod
+    from tests.test_gpu_batched import build_afqmc
+    from tests.test_gpu_sizes import generic_system
+    s = generic_system(130, 10, (20, 20), 6, 'general')
+    return build_afqmc(s, trial_mod.rhf_trial_generic(s), 65)
+
+
 def _hubbard_10x10():
     from pauxy_amd import systems, trial as trial_mod
     from tests.test_gpu_batched import build_afqmc
@@ -297,7 +347,9 @@ def _hubbard_10x10():
     return build_afqmc(s, trial_mod.uhf_trial_hubbard(s, ueff=0.4), 64, False, {'hubbard_stratonovich': 'continuous'})
 
 
-@pytest.mark.parametrize("make", [_generic_40, _generic_m130, _hubbard_10x10], ids=["generic-40e", "generic-M130", "hubbard-10x10-45e"])
+@pytest.mark.parametrize("make", [_generic_40, _generic_m130, _hubbard_10x10, _generic_40_hermitian, _generic_m130_general],
+                         ids=["generic-40e", "generic-M130", "hubbard-10x10-45e", "generic-40e-hermitian-L",
+                              "generic-M130-general-L"])
 def test_driver_loops_agree_on_boundary_shapes(make):
     """20 steps of the per-walker loop, the batched loop and the batched loop with the estimator terms riding on the weight
     update (which also announces the steps whose per-spin Ghalf is not stored) on shapes that take the dispatch paths

@@ -8,7 +8,7 @@ from oracle import afqmc_ref as ref
 from pauxy_amd import _lib as L
 from pauxy_amd import systems, trial as trial_mod
 from pauxy_amd.propagation import setup
-from tests.helpers import make_device
+from tests.helpers import cplx_chol, lform_params, make_device
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -22,9 +22,28 @@ def close(a, b, tol=TOL):
     assert err <= tol, err
 
 
-def build(M, K, na, nb, complex_trial, seed=3, dt=0.01):
+def generic_system(M, K, nelec, seed, lform='real'):
+    """systems.synthetic_generic, or its H1 with complex Cholesky vectors: lform 'hermitian' or 'general'."""
+    s = systems.synthetic_generic(M, K, nelec, seed=seed)
+    if lform == 'real':
+        return s
+    assert lform in ('hermitian', 'general'), lform
+    chol = cplx_chol(M, K, lform == 'hermitian', numpy.random.RandomState(seed + 1000))
+    return systems.Generic(nelec, s.H1, chol, ecore=s.ecore)
+
+
+def assert_complex_rchol(model, lform):
+    """Complex L makes the half-rotated vectors complex even for a real trial: the device takes its complex-rchol forms."""
+    if lform != 'real':
+        assert numpy.abs(numpy.imag(model.rchol)).max() > 0.0
+
+
+def build(M, K, na, nb, complex_trial, seed=3, dt=0.01, lform='real'):
+    """Synthetic generic system and a single-determinant trial.  lform: 'real' (symmetric real L_n), 'hermitian' or
+    'general' complex L_n (helpers.cplx_chol) with the same H1, trial and walker draws -- the complex vectors come from a
+    stream of their own, afq_set_system_generic_c128 takes them."""
     rng = numpy.random.RandomState(seed)
-    s = systems.synthetic_generic(M, K, (na, nb), seed=seed)
+    s = generic_system(M, K, (na, nb), seed, lform)
     e, v = numpy.linalg.eigh(s.H1[0])
     psi = numpy.zeros((M, na + nb), dtype=complex)
     psi[:, :na] = v[:, :na]
@@ -38,9 +57,18 @@ def build(M, K, na, nb, complex_trial, seed=3, dt=0.01):
     return model, rng
 
 
-@pytest.mark.parametrize("M,K,na,nb,nw,cplx", [(37, 45, 7, 6, 70, False), (24, 50, 5, 5, 130, True)])
-def test_midsize_generic(M, K, na, nb, nw, cplx):
-    model, rng = build(M, K, na, nb, cplx)
+def vhs_work(M, K, nw, lform):
+    """Matrix-pipe flops of the VHS products without padding: nw x K x (contracted columns), 2 flops per real
+    multiply-add, two real MFMA products per complex-by-real pair; Hermitian L contracts the packed p <= q / p < q
+    columns of its Re / Im panels, general L all M^2 of both."""
+    cols = [M * (M + 1) // 2, M * (M - 1) // 2] if lform == 'hermitian' else [M * M, M * M]
+    return 4.0 * nw * K * sum(cols), cols
+
+
+def check_operators_and_step(model, rng, nw, lform='real'):
+    """Green's functions, force bias, VHS, local energy (both exchange algorithms), the full-G energy of the device's G,
+    one full step with a third of the walkers dead and a re-orthogonalisation: every walker against the oracle."""
+    M, K, na, nb = model.M, model.nfields, model.na, model.nb
     dev = make_device(model, nw)
     phis = numpy.array([model.psi + 0.1 * (rng.rand(M, na + nb) + 1j * rng.rand(M, na + nb)) for _ in range(nw)])
     dev.set(L.F_PHI, phis)
@@ -48,16 +76,40 @@ def test_midsize_generic(M, K, na, nb, nw, cplx):
     refs = [ref.greens_function(p, model.psi, na, nb) for p in phis]
     close(det, numpy.array([r[0] for r in refs]))
     close(dev.get(L.F_GHALF), numpy.array([numpy.concatenate([r[1][0], r[1][1]]) for r in refs]))
-    close(dev.get(L.F_G), numpy.array([r[2] for r in refs]))
+    G = dev.get(L.F_G)
+    close(G, numpy.array([r[2] for r in refs]))
     xbar = dev.force_bias()
     close(xbar, numpy.array([model.force_bias(r[1], r[2]) for r in refs]))
     xi = rng.normal(size=(nw, K))
     xs = numpy.array([ref.shift_fields(xi[i], xbar[i], model.mf_shift, model.sqrt_dt)[0] for i in range(nw)])
     vhs = dev.vhs(xs)
     close(vhs[:, 0], numpy.array([model.vhs(x) for x in xs]))
+    if lform != 'real':
+        # the two launches of k_vhs_generic_cplx issue at least the unpadded work; exactly that when no small tile pads
+        # (rows of 32 walkers, columns of 64, contraction chunks of 8)
+        work, cols = vhs_work(M, K, nw, lform)
+        issued = dev.kernel_issued_flops(L.K_VHS)
+        assert work <= issued, (work, issued)
+        if nw <= 32 and nw % 32 == 0 and K % 8 == 0 and all(c % 64 == 0 for c in cols):
+            assert issued == work, (work, issued)
     E = dev.local_energy()
-    close(E, numpy.array([model.local_energy(r[2], r[1]) for r in refs]))
-    # full step: half the walkers dead
+    want = numpy.array([model.local_energy(r[2], r[1]) for r in refs])
+    close(E, want)
+    # both exchange algorithms (T-intermediate, quadratic form), whichever the automatic choice took above
+    Ex = {}
+    for mode in (1, 2):
+        dev.set_exchange_algorithm(mode)
+        dev.greens(want_G=True)
+        Ex[mode] = dev.local_energy()
+        close(Ex[mode], want)
+    close(Ex[1], Ex[2], 1e-11)
+    dev.set_exchange_algorithm(0)
+    # full-G Cholesky energy (estimators/generic.py:398-434) of the device's own G
+    sample = sorted({0, min(1, nw - 1), nw // 2, nw - 1})
+    Efull = dev.local_energy_full_g(G[sample])
+    close(Efull, numpy.array([ref.local_energy_generic_cholesky(model.H1, model.ecore, G[i], model.hs_pot)
+                              for i in sample]))
+    # full step: a third of the walkers dead
     w0 = numpy.ones(nw)
     w0[::3] = 0.0
     dev.set(L.F_WEIGHT, w0)
@@ -83,6 +135,12 @@ def test_midsize_generic(M, K, na, nb, nw, cplx):
     dev.close()
 
 
+@pytest.mark.parametrize("M,K,na,nb,nw,cplx", [(37, 45, 7, 6, 70, False), (24, 50, 5, 5, 130, True)])
+def test_midsize_generic(M, K, na, nb, nw, cplx):
+    model, rng = build(M, K, na, nb, cplx)
+    check_operators_and_step(model, rng, nw)
+
+
 def test_vhs_nonsymmetric_cholesky():
     """The HS-potential GEMM contracts only the columns p <= q when every L_n is symmetric (the
     usual case, all other generic tests); a non-symmetric hs_pot must take the full-column path."""
@@ -99,13 +157,15 @@ def test_vhs_nonsymmetric_cholesky():
     dev.close()
 
 
-@pytest.mark.parametrize("M,K,na,nb,restore", [(37, 45, 7, 6, None), (120, 40, 9, 9, 'full'), (64, 12, 40, 40, None), (100, 10, 45, 45, None)])
-def test_back_propagation_with_reortho(M, K, na, nb, restore):
+@pytest.mark.parametrize("M,K,na,nb,restore,lform", lform_params(
+    [(37, 45, 7, 6, None), (120, 40, 9, 9, 'full'), (64, 12, 40, 40, None), (100, 10, 45, 45, None)], ['real', 'hermitian']))
+def test_back_propagation_with_reortho(M, K, na, nb, restore, lform):
     """afq_bp_update against the oracle with a window longer than the stabilisation period (the
     re-orthogonalisation inside the back-propagation, propagation/generic.py:286-288, is not reached by
     the reference's own 5-step test), a walker copy in the middle of the window (history travels with
-    the walker) and both propagator paths (fused kernel for M=37, separate GEMMs for M=120)."""
-    model, rng = build(M, K, na, nb, True)
+    the walker) and both propagator paths (fused kernel for M=37, separate GEMMs for M=120).  Hermitian complex L:
+    the energies go through the complex full-G contraction, odd and even M."""
+    model, rng = build(M, K, na, nb, True, lform=lform)
     nw, nbp, nstblz = 5, 7, 3
     dev = make_device(model, nw)
     phis = numpy.array([model.psi + 0.1 * (rng.rand(M, na + nb) + 1j * rng.rand(M, na + nb)) for _ in range(nw)])
@@ -714,7 +774,7 @@ def test_closed_shell_walkers_take_the_one_spin_path_of_the_greens_kernel(M, N):
     dev.close()
 
 
-@pytest.mark.parametrize("M,N,deal", [
+@pytest.mark.parametrize("M,N,deal,lform", lform_params([
     (100, 25, True),     # contiguous columns, twins in like slots: column slot 1 left out
     (100, 30, True),     # two slots per spin, seven row tiles with the 4-row remainder unit: the alpha half only
     (100, 20, True),     # ... 40 columns
@@ -724,15 +784,16 @@ def test_closed_shell_walkers_take_the_one_spin_path_of_the_greens_kernel(M, N):
     (93, 7, True),       # one column tile per spin, six row tiles (prop_fused_kernel<true, 6>)
     (70, 7, False),      # narrow, generic tile tests: no closed-shell deal
     (60, 20, False),     # wide, generic tile tests: no closed-shell deal
-])
-def test_fused_propagator_closed_shell_deals(M, N, deal):
+], ['real', 'hermitian', 'general']))
+def test_fused_propagator_closed_shell_deals(M, N, deal, lform):
     """Walkers whose spin blocks are bitwise equal take the fused propagator's closed-shell deal (the kernel checks every walker
     on its LDS image): the Taylor products of the alpha half only -- of everything but the redundant slot in the
     contiguous-column layout -- copied into the beta half ahead of the closing one-body pass.  A population of closed, open and
     dead walkers, two steps against the oracle (propagation/continuous.py:232-262); afq_counters [3] counts exactly the live
-    closed walkers; closed walkers stay closed bit for bit."""
+    closed walkers; closed walkers stay closed bit for bit.  Complex L: the deal consumes the two-launch VHS."""
     K, nw = 24, 21
-    model, rng = build(M, K, N, N, False, seed=31)
+    model, rng = build(M, K, N, N, False, seed=31, lform=lform)
+    assert_complex_rchol(model, lform)
     assert numpy.array_equal(model.BH1[0], model.BH1[1])
     half = model.psi[None, :, :N] + 0.1 * (rng.rand(nw, M, N) + 1j * rng.rand(nw, M, N))
     phis = numpy.concatenate([half, half], axis=2)
@@ -763,15 +824,16 @@ def test_fused_propagator_closed_shell_deals(M, N, deal):
     dev.close()
 
 
-@pytest.mark.parametrize("M,N", [(136, 40), (200, 50), (150, 70)])
-def test_large_system_chain_leaves_out_the_beta_tiles_of_closed_shell_walkers(M, N):
+@pytest.mark.parametrize("M,N,lform", lform_params([(136, 40), (200, 50), (150, 70)], ['real', 'hermitian']))
+def test_large_system_chain_leaves_out_the_beta_tiles_of_closed_shell_walkers(M, N, lform):
     """The GEMM chain of the large systems (M > 128: k_onebody / k_apply_exponential) checks at every step which walkers have
     bitwise equal spin blocks and does not compute the work-group tiles that lie wholly in their beta columns; the propagated
     alpha block is copied over the beta block behind the closing one-body product.  A population of closed, open and dead
     walkers (at least 64: the ring path), two steps against the oracle (propagation/continuous.py:232-262); closed walkers stay
     closed bit for bit, open ones open, dead ones untouched."""
     K, nw = 16, 66
-    model, rng = build(M, K, N, N, False, seed=37)
+    model, rng = build(M, K, N, N, False, seed=37, lform=lform)
+    assert_complex_rchol(model, lform)
     assert numpy.array_equal(model.BH1[0], model.BH1[1])
     half = model.psi[None, :, :N] + 0.1 * (rng.rand(nw, M, N) + 1j * rng.rand(nw, M, N))
     phis = numpy.concatenate([half, half], axis=2)
@@ -804,15 +866,17 @@ def test_large_system_chain_leaves_out_the_beta_tiles_of_closed_shell_walkers(M,
     dev.close()
 
 
-@pytest.mark.parametrize("M,N", [(136, 40), (150, 70)])
-def test_large_system_exchange_energy_evaluates_one_spin_of_a_closed_shell_population(M, N):
+@pytest.mark.parametrize("M,N,lform", lform_params([(136, 40), (150, 70)], ['real', 'hermitian', 'general']))
+def test_large_system_exchange_energy_evaluates_one_spin_of_a_closed_shell_population(M, N, lform):
     """The Green's function of the large systems (k_greens_big: three GEMM-shaped launches) holds no whole walker anywhere, so
     the exchange energy compares the spin blocks of the Ghalf it is about to contract itself (ghalf_closed_check_kernel) and
     evaluates ONE spin when every walker's are bitwise equal (estimators/generic.py:84-119 contracts each spin alike).  A closed
     population, then one with an open walker in it, against the oracle; the two-spin evaluation of the same closed walkers (the
-    T-intermediate algorithm) agrees; afq_counters_ext [4] counts the one-spin walker evaluations."""
+    T-intermediate algorithm) agrees; afq_counters_ext [4] counts the one-spin walker evaluations.  Complex L: complex
+    half-rotated vectors (launch_exx_quadratic<true>)."""
     K, nw = 12, 40
-    model, rng = build(M, K, N, N, False, seed=41)
+    model, rng = build(M, K, N, N, False, seed=41, lform=lform)
+    assert_complex_rchol(model, lform)
     half = model.psi[None, :, :N] + 0.1 * (rng.rand(nw, M, N) + 1j * rng.rand(nw, M, N))
     closed_phis = numpy.concatenate([half, half], axis=2)
     dev = make_device(model, nw)
@@ -848,16 +912,27 @@ def test_large_system_exchange_energy_evaluates_one_spin_of_a_closed_shell_popul
 
 
 def test_exchange_energy_with_both_spins_slices_in_one_launch():
+    check_exchange_energy_with_both_spins_slices_in_one_launch('real')
+
+
+@pytest.mark.parametrize("lform", ['hermitian', 'general'])
+def test_exchange_energy_with_both_spins_slices_in_one_launch_complex_chol(lform):
+    """The same with complex L: complex half-rotated vectors, one-spin and merged slices of launch_exx_quadratic<true>."""
+    check_exchange_energy_with_both_spins_slices_in_one_launch(lform)
+
+
+def check_exchange_energy_with_both_spins_slices_in_one_launch(lform):
     """256 walkers at the benchmark's shape (M = 100, 25 + 25): each spin's contraction slices make one whole round over the eight
     XCDs, so the closed-shell try puts the beta slices behind the alpha slices of ONE launch (launch_exx_quadratic: `merged`) --
     work-groups that return at once for a closed population, that multiply for an open one.  Both populations against the oracle
     (estimators/generic.py:156-221) and against the T-intermediate algorithm; afq_counters_ext [4] says which form ran."""
     M, N, K, nw = 100, 25, 30, 256
-    s = systems.synthetic_generic(M, K, (N, N), seed=19)
+    s = generic_system(M, K, (N, N), 19, lform)
     t = trial_mod.rhf_trial_generic(s)
     BH1, mf = setup.generic_propagator_arrays(s, t, 0.005)
     model = ref.RefModel('generic', M, N, N, t.psi, BH1, mf, 0.005, hs_pot=s.hs_pot, rchol=t._rchol,
                          H1=s.H1.astype(complex), ecore=s.ecore)
+    assert_complex_rchol(model, lform)
     rng = numpy.random.RandomState(23)
     half = t.psi[None, :, :N] + 0.05 * (rng.rand(nw, M, N) + 1j * rng.rand(nw, M, N))
     closed_phis = numpy.concatenate([half, half], axis=2)
