@@ -187,6 +187,27 @@ int afq_bp_steps(afq_handle *h, int32_t *steps_out);
  * sum_w wt_w (E, E1b, E2b)[G_bp[w]] from the full-G Cholesky energy (generic systems).          */
 int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
                   int reset, double *est_out);
+/* Back-propagated two-body RDM and extended Koopmans' theorem (EKT) Fock matrices (estimators/back_propagation.py:
+ * 168-175,178-186, estimators/ekt.py:10-73).  Call after afq_bp_configure; says what afq_bp_update_ext may be asked for.
+ *   two_rdm  spin-summed two_rdm[p,r,q,s] = S[p,r] S[q,s] - sum_s G_s[p,s] G_s[q,r], S = G_a + G_b (layout [p][r][q][s]).
+ *            AFQ_ENOMEM (with the byte count) when its 16 M^4 bytes exceed half of the free device memory.
+ *   ekt      F1p / F1h of ekt_1p_fock_opt / ekt_1h_fock_opt with h1 c128[M, M] and the vectors L c128[nL, M, M]:
+ *            the UEG passes 2 chol_vecs^T reshaped (nL = nq); generic systems pass L = NULL (nL = K) for their own
+ *            vectors, L_x[i,k] = hs_pot[i*M+k, x] (the reference's ekt.py refuses the [M*M, K] layout of a Generic
+ *            system; this is its function applied to that reshape).  AFQ_EUNSUPPORTED on Hubbard systems and for
+ *            L = NULL with complex vectors (afq_set_system_generic_c128).
+ * The hot path is k_bp_obs.hip: the EKT quadratic terms in rank-N form from the factors of G_bp (phi_bp and the
+ * half-rotated G_bp), the terms linear in G once per window on sum_w wt_w G_bp[w]; the two-body RDM as one MFMA GEMM
+ * per (p, q) over the stacked walker contraction.                                                   */
+int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, const double *L, int nL);
+/* afq_bp_update plus, where the pointers are not NULL, two_rdm_out c128[M^4] = sum_w wt_w two_rdm[G_bp[w]] and
+ * fock_out c128[2, M, M] = sum_w wt_w (F1p, F1h)[G_bp[w]] with the weights of est_out (complex with restore_weights).
+ * With both NULL it is afq_bp_update, bitwise.                                                       */
+/* Cholesky vectors per chunk of the EKT: nc for the rank-N panels, ncy for the term linear in G (0 = automatic: as
+ * many as fit 1 GiB of scratch, independent of the free memory, so that the order of the sums is reproducible). */
+int afq_bp_ekt_chunks(afq_handle *h, int nc, int ncy);
+int afq_bp_update_ext(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
+                      int reset, double *est_out, double *two_rdm_out, double *fock_out);
 
 /* Multi-determinant (NOMSD / PHMSD) trial |psi_T> = sum_d c_d |D_d> for a generic system, replacing
  * the single-determinant operands of afq_set_system_generic / afq_set_trial.  Call after the

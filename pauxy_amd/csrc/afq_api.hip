@@ -108,6 +108,8 @@ void free_walkers(afq_handle *h) {
     dev_free(h->bp_hist); dev_free(h->bp_n); dev_free(h->bp_flag); dev_free(h->bp_cos); dev_free(h->bp_ph);
     dev_free(h->phi_old); dev_free(h->phi_bp); dev_free(h->BH1dag); dev_free(h->bp_xs); dev_free(h->bp_est);
     h->nbp = 0; dev_free(h->xbar); dev_free(h->xs);
+    dev_free(h->bpo_h1); dev_free(h->bpo_L); dev_free(h->bpo_wt); dev_free(h->bpo_out); dev_free(h->bpo_ws);
+    h->bpo_ws_len = 0; h->bpo_two = h->bpo_ekt = 0; h->bpo_nL = 0;
     dev_free(h->cmf); dev_free(h->cfb); dev_free(h->vhs); dev_free(h->lu_ws);
     dev_free(h->gj_flag); dev_free(h->big_ws); dev_free(h->big_ws2); dev_free(h->detm); dev_free(h->dete); dev_free(h->qr_logd); dev_free(h->qr_fail);
     dev_free(h->energy); dev_free(h->exx_part); dev_free(h->gfrag); dev_free(h->exq_y); h->exq_y_len = 0;
@@ -1920,9 +1922,8 @@ int afq_bp_steps(afq_handle *h, int32_t *steps_out) {
     return rc;
 }
 
-int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
-                  int reset, double *est_out) {
-    AFQ_API(h, "afq_bp_update");
+static int bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
+                     int reset, double *est_out, double *two_rdm_out, double *fock_out) {
     if (h) { h->greens_valid = false; h->gsum_only = false; }
     if (!h || !phi_bp0 || !est_out || nstblz < 1 || restore_weights < 0 || restore_weights > 2) return AFQ_EINVAL;
     int rc = need_ready(h, true);
@@ -1985,13 +1986,77 @@ int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_
         if ((rc = k_energy_full_g(h, h->G, h->nw, h->energy))) return rc;
     }
     if ((rc = k_bp_accumulate(h, restore_weights, eval_energy))) return rc;
+    const size_t m4 = (size_t)h->M * h->M * h->M * h->M, m2 = (size_t)h->M * h->M;
+    if (two_rdm_out || fock_out) {
+        // sum_w wt_w two_rdm[G_bp[w]] and (F1p, F1h)[G_bp[w]] (k_bp_obs.hip), before the reset clears the weight factors
+        if ((rc = k_bp_observables(h, restore_weights, two_rdm_out ? h->bpo_out : nullptr,
+                                   fock_out ? h->bpo_out + (h->bpo_two ? m4 : 0) : nullptr))) return rc;
+    }
     if (reset) {
         // FieldConfig.reset + Walkers.copy_historic_wfn (walkers/stack.py:124-127, handler.py:200-203)
         if ((rc = k_bp_reset(h, false))) return rc;
         AFQ_HIP(h, hipMemcpyAsync(h->phi_old, h->phi, sizeof(cplx) * per * n, hipMemcpyDeviceToDevice, h->stream));
     }
     if ((rc = k_alive(h))) return rc;
+    if (two_rdm_out && (rc = copy_out(h, two_rdm_out, h->bpo_out, sizeof(cplx) * m4))) return rc;
+    if (fock_out && (rc = copy_out(h, fock_out, h->bpo_out + (h->bpo_two ? m4 : 0), sizeof(cplx) * 2 * m2))) return rc;
     return copy_out(h, est_out, h->bp_est, sizeof(cplx) * ((size_t)4 + 2 * h->M * h->M));
+}
+
+int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
+                  int reset, double *est_out) {
+    AFQ_API(h, "afq_bp_update");
+    return bp_update(h, phi_bp0, nstblz, restore_weights, eval_energy, reset, est_out, nullptr, nullptr);
+}
+
+int afq_bp_update_ext(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
+                      int reset, double *est_out, double *two_rdm_out, double *fock_out) {
+    AFQ_API(h, "afq_bp_update_ext");
+    if (h && two_rdm_out && !h->bpo_two) AFQ_FAIL(h, AFQ_ESTATE, "two-body RDM: afq_bp_observables(h, 1, ...) first");
+    if (h && fock_out && !h->bpo_ekt) AFQ_FAIL(h, AFQ_ESTATE, "EKT Fock matrices: afq_bp_observables(h, ., 1, ...) first");
+    return bp_update(h, phi_bp0, nstblz, restore_weights, eval_energy, reset, est_out, two_rdm_out, fock_out);
+}
+
+int afq_bp_ekt_chunks(afq_handle *h, int nc, int ncy) {
+    if (!h || nc < 0 || ncy < 0) return AFQ_EINVAL;
+    h->bpo_nc = nc; h->bpo_ncy = ncy;
+    return AFQ_OK;
+}
+
+// share of the free device memory the M^4 two-body RDM (one copy on the device) may take
+#define AFQ_BPO_MEM_SHARE 0.5
+
+int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, const double *L, int nL) {
+    if (!h || (ekt && (!h1 || nL < 1 || (L == nullptr && nL != h->K)))) return AFQ_EINVAL;
+    int rc = need_ready(h, true);
+    if (rc) return rc;
+    if (!h->nbp) AFQ_FAIL(h, AFQ_ESTATE, "back-propagation is not configured: afq_bp_configure first");
+    if (ekt && h->kind == AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "EKT: the Hubbard model has no Cholesky vectors");
+    if (ekt && !L && h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EINVAL, "EKT: pass the vectors L_x of this system");
+    if (ekt && !L && h->hs_cplx)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "EKT with complex Cholesky vectors: the reference's 4-fold-symmetry form pins nothing");
+    const size_t M = (size_t)h->M, m4 = M * M * M * M;
+    hipSetDevice(h->device);
+    dev_free(h->bpo_out);              // a buffer of an earlier call does not count against the budget
+    if (two_rdm) {
+        size_t fr = 0, tot = 0;
+        AFQ_HIP(h, hipMemGetInfo(&fr, &tot));
+        const double need = 16.0 * (double)m4;
+        if (need > AFQ_BPO_MEM_SHARE * (double)fr)
+            AFQ_FAIL(h, AFQ_ENOMEM, "two-body RDM: " + std::to_string((unsigned long long)need) +
+                                        " bytes (16 M^4) exceed half of the free device memory (" +
+                                        std::to_string((unsigned long long)fr) + " bytes)");
+    }
+    dev_free(h->bpo_h1); dev_free(h->bpo_L);
+    h->bpo_two = h->bpo_ekt = 0; h->bpo_nL = 0;
+    if (ekt) {
+        if ((rc = dev_upload(h, &h->bpo_h1, h1, M * M))) return rc;
+        if (L && (rc = dev_upload(h, &h->bpo_L, L, (size_t)nL * M * M))) return rc;
+        h->bpo_nL = nL;
+    }
+    if ((two_rdm || ekt) && (rc = dev_alloc(h, &h->bpo_out, (two_rdm ? m4 : 0) + (ekt ? 2 * M * M : 0)))) return rc;
+    h->bpo_two = two_rdm ? 1 : 0; h->bpo_ekt = ekt ? 1 : 0;
+    return AFQ_OK;
 }
 
 int afq_local_energy_full_g(afq_handle *h, const double *G, int n, double *E_out) {

@@ -172,6 +172,16 @@ struct afq_handle {
     cplx *BH1dag = nullptr;         // [2, M, M] BH1^H
     cplx *bp_xs = nullptr;          // [nw, K]
     cplx *bp_est = nullptr;         // [4 + 2 M M]
+    // back-propagated two-body RDM / EKT Fock matrices (afq_bp_observables, k_bp_obs.hip)
+    int bpo_two = 0, bpo_ekt = 0;   // what afq_bp_update_ext may be asked for
+    int bpo_nL = 0;                 // EKT vectors L_x, x < nL
+    cplx *bpo_h1 = nullptr;         // [M, M] h1 of the EKT
+    cplx *bpo_L = nullptr;          // [nL, M, M] the caller's vectors (null: the handle's own real L_full)
+    cplx *bpo_wt = nullptr;         // [nw] accumulation weights of the window
+    cplx *bpo_out = nullptr;        // [M^4 (two_rdm) + 2 M M (fock)] results of the window
+    cplx *bpo_ws = nullptr;         // scratch, grown on demand
+    size_t bpo_ws_len = 0;
+    int bpo_nc = 0, bpo_ncy = 0;    // afq_bp_ekt_chunks: x per chunk of the panels / of the linear term (0: automatic)
 
     // ---- discrete Hirsch propagator (propagation/hubbard.py:12-343)
     bool hirsch = false;
@@ -443,6 +453,10 @@ int k_hirsch_free(afq_handle *h, double eshift);           // free-projection st
 int k_rng_uniform(afq_handle *h, double *u, long n);
 // k_fullg.hip
 int k_energy_full_g(afq_handle *h, const cplx *G_dev, int ng, cplx *E_dev);   // estimators/generic.py:398-434
+int k_fullg_expand(afq_handle *h);                         // L_full (real vectors) built on first use
+// k_bp_obs.hip: sum_w wt_w two_rdm[G_bp[w]] -> two_out [M^4], sum_w wt_w (F1p, F1h)[G_bp[w]] -> fock_out [2, M, M]
+// (either may be null); after afq_bp_update's accumulation, before its reset
+int k_bp_observables(afq_handle *h, int restore, cplx *two_out, cplx *fock_out);
 // k_bigdet.hip
 int k_greens_big_supported(afq_handle *h);
 struct WeightArgs;

@@ -237,11 +237,19 @@ int k_energy_full_g(afq_handle *h, const cplx *G_dev, int ng, cplx *E_dev) {
         }
         return energy_full_g<cplx>(h, h->L_full_c, G_dev, ng, E_dev);
     }
+    int rc = k_fullg_expand(h);
+    if (rc) return rc;
+    return energy_full_g<double>(h, h->L_full, G_dev, ng, E_dev);
+}
+
+int k_fullg_expand(afq_handle *h) {
+    const int M = h->M, K = h->K, Mp = (M + 1) & ~1;
+    const long n = (long)K * M * Mp;
     if (!h->L_full) {
         AFQ_HIP(h, hipMalloc(&h->L_full, sizeof(double) * (size_t)n));
         AFQ_LAUNCH(h, fullg_expand_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->hs_pot,
                            h->ld_hs, h->hs_sym ? 1 : 0, M, Mp, K, h->L_full);
         AFQ_POST(h);
     }
-    return energy_full_g<double>(h, h->L_full, G_dev, ng, E_dev);
+    return AFQ_OK;
 }

@@ -178,14 +178,50 @@ class AfqDevice(object):
         self._ck(self.lib.afq_local_energy_full_g(self.h, _p(G), n, _p(out)))
         return out
 
-    def bp_update(self, phi_bp0, nstblz, restore_weights=None, eval_energy=False, reset=True):
-        """-> (energies_sum[3], denominator, G_bp_sum[2, M, M]); restore_weights in (None, 'partial', 'full')."""
+    def bp_observables(self, two_rdm=False, ekt=False, h1=None, L=None):
+        """afq_bp_observables: what bp_update may be asked for.  EKT: h1 [M, M] and L [nL, M, M] (None: a generic
+        system's own vectors)."""
+        M = self.M
+        h1p = Lp = None
+        nL = 0
+        if ekt:
+            h1 = _c128(h1, (M, M))
+            h1p = _p(h1)
+            if L is None:
+                nL = self.K
+            else:
+                L = _c128(L)
+                nL = L.shape[0]
+                L = _c128(L, (nL, M, M))
+                Lp = _p(L)
+        self._ck(self.lib.afq_bp_observables(self.h, int(bool(two_rdm)), int(bool(ekt)), h1p, Lp, int(nL)))
+
+    def bp_ekt_chunks(self, nc=0, ncy=0):
+        """afq_bp_ekt_chunks: Cholesky vectors per EKT chunk (0: automatic)."""
+        self._ck(self.lib.afq_bp_ekt_chunks(self.h, int(nc), int(ncy)))
+
+    def bp_update(self, phi_bp0, nstblz, restore_weights=None, eval_energy=False, reset=True, two_rdm=False,
+                  ekt=False):
+        """-> (energies_sum[3], denominator, G_bp_sum[2, M, M]); restore_weights in (None, 'partial', 'full').
+        With two_rdm / ekt (after bp_observables) a fourth item {'two_rdm': [M]*4, 'fock_1p': [M, M], 'fock_1h':
+        [M, M]} holds the weighted sums of what was asked for."""
         mode = {None: 0, 'partial': 1, 'full': 2}.get(restore_weights, 1)
         phi0 = _c128(phi_bp0, (self.M, self.na + self.nb))
-        out = numpy.zeros(4 + 2 * self.M * self.M, dtype=numpy.complex128)
-        self._ck(self.lib.afq_bp_update(self.h, _p(phi0), int(nstblz), mode, int(bool(eval_energy)), int(bool(reset)),
-                                        _p(out)))
-        return out[:3], out[3], out[4:].reshape(2, self.M, self.M)
+        M = self.M
+        out = numpy.zeros(4 + 2 * M * M, dtype=numpy.complex128)
+        if not (two_rdm or ekt):
+            self._ck(self.lib.afq_bp_update(self.h, _p(phi0), int(nstblz), mode, int(bool(eval_energy)),
+                                            int(bool(reset)), _p(out)))
+            return out[:3], out[3], out[4:].reshape(2, M, M)
+        two = numpy.zeros((M, M, M, M), dtype=numpy.complex128) if two_rdm else None
+        fock = numpy.zeros((2, M, M), dtype=numpy.complex128) if ekt else None
+        self._ck(self.lib.afq_bp_update_ext(self.h, _p(phi0), int(nstblz), mode, int(bool(eval_energy)),
+                                            int(bool(reset)), _p(out), None if two is None else _p(two),
+                                            None if fock is None else _p(fock)))
+        extra = {'two_rdm': two}
+        if fock is not None:
+            extra['fock_1p'], extra['fock_1h'] = fock[0], fock[1]
+        return out[:3], out[3], out[4:].reshape(2, M, M), extra
 
     def set_trial_multi(self, psi, coeffs, rchol):
         """psi [ndet, M, na+nb], coeffs [ndet], rchol [ndet * (na+nb) M, K] (stacked per determinant)."""

@@ -11,6 +11,14 @@ Output: the per-window results are appended to ``self.one_rdm`` / ``self.denomin
 ``self.energies`` (lists; ``rdm()`` returns their ratio like pauxy.analysis.extraction.extract_rdm)
 and, when the container was given a file name, pushed by the root rank to the reference's
 groups ``back_propagated/{denominator,energies,one_rdm}_<n>/<block>`` (back_propagation.py:288-324).
+
+``two_rdm: True`` (the full spin-summed two-body RDM, back_propagation.py:168-175) and ``evaluate_ekt: True`` (the EKT
+Fock matrices of estimators/ekt.py) add the lists ``self.two_rdm`` / ``self.fock_1p`` / ``self.fock_1h`` and the groups
+``two_rdm_<n>`` / ``fock_1p_<n>`` / ``fock_1h_<n>``; the flat ``estimates`` vector and its slicing are the reference's,
+including the Fock matrices' offset with ``one_rdm: False``.  These attributes exist only when the option is set.
+EKT on a Generic system uses L_x[i, k] = hs_pot[i*M + k, x] (the reference's ekt.py asserts a 3-D array and fails on
+the [M*M, K] vectors of a Generic system); it is refused for the Hubbard model and for complex Generic vectors.
+``two_rdm: 'structure_factor'`` is refused (it needs back-propagated UEG energies).
 """
 import numpy
 
@@ -37,8 +45,14 @@ class BackPropagation(object):
             # without weight factors (hubbard.py:215-216, walkers/stack.py:35-49); afq_bp_configure refuses the
             # continuous Hubbard propagator
             raise NotImplementedError("restore_weights with the discrete Hubbard fields")
-        if self.calc_two_rdm is not None or self.eval_ekt:
-            raise NotImplementedError("device back-propagation: one-body RDM and energies; no two_rdm / EKT")
+        if self.calc_two_rdm is not None and isinstance(self.calc_two_rdm, str) and self.calc_two_rdm == "structure_factor":
+            # the structure factor needs back-propagated UEG energies, which are refused below (DESIGN row 8f-2)
+            raise NotImplementedError("back-propagated two_rdm: 'structure_factor'")
+        if self.eval_ekt and system.name == "Hubbard":
+            raise NotImplementedError("EKT: the Hubbard model has no Cholesky vectors")
+        if (self.eval_ekt and system.name == "Generic" and numpy.iscomplexobj(system.hs_pot)
+                and numpy.any(numpy.asarray(system.hs_pot).imag != 0)):
+            raise NotImplementedError("EKT with complex Cholesky vectors (ekt.py's 4-fold-symmetry formula)")
         if self.eval_energy and system.name != "Generic":
             raise NotImplementedError("back-propagated energies: Generic systems")
         if (system.name == "Generic" and numpy.iscomplexobj(system.hs_pot)
@@ -55,8 +69,17 @@ class BackPropagation(object):
         self.nstblz = qmc.nstblz
         self.BT2 = BT2
         self.dt = qmc.dt
-        self.estimates = numpy.zeros(self.nreg + 1 + self.G.size, dtype=dtype)
-        self.global_estimates = numpy.zeros(self.nreg + 1 + self.G.size, dtype=dtype)
+        dms_size = self.G.size
+        if self.calc_two_rdm is not None:         # back_propagation.py:86-99,100-104: the flat layout of the reference
+            self.two_rdm = []
+            self.two_rdm_size = M ** 4
+            dms_size += M ** 4
+        if self.eval_ekt:
+            self.fock_1p = []
+            self.fock_1h = []
+            dms_size += 2 * M * M
+        self.estimates = numpy.zeros(self.nreg + 1 + dms_size, dtype=dtype)
+        self.global_estimates = numpy.zeros(self.nreg + 1 + dms_size, dtype=dtype)
         self.key = {'ETotal': "BP estimate for total energy.", 'E1B': "BP estimate for one-body energy.",
                     'E2B': "BP estimate for two-body energy."}
         self.root = root
@@ -83,11 +106,24 @@ class BackPropagation(object):
         phi0 = numpy.asarray(trial.init if self.init_walker else trial.psi, dtype=numpy.complex128)
         if phi0.ndim == 3:
             phi0 = phi0[0]
-        energies, denom, G = dev.bp_update(phi0, self.nstblz, self.restore_weights, self.eval_energy,
-                                           reset=bool(buff_ix == self.splits[-1]))     # back_propagation.py:219-222
+        two, ekt = self.calc_two_rdm is not None, bool(self.eval_ekt)
+        if (two or ekt) and getattr(self, '_obs_dev', None) is not dev:
+            self._setup_observables(dev, system)
+        extra = {'two_rdm': two, 'ekt': ekt} if (two or ekt) else {}
+        res = dev.bp_update(phi0, self.nstblz, self.restore_weights, self.eval_energy,
+                            reset=bool(buff_ix == self.splits[-1]), **extra)     # back_propagation.py:219-222
+        energies, denom, G = res[:3]
         self.estimates[:self.nreg] += energies
         self.estimates[self.nreg] += denom
-        self.estimates[self.nreg + 1:] += G.ravel()
+        end = self.nreg + 1 + G.size
+        self.estimates[self.nreg + 1:end] += G.ravel()
+        if two:                                    # back_propagation.py:199-206
+            self.estimates[end:end + self.two_rdm_size] += res[3]['two_rdm'].ravel()
+            end += self.two_rdm_size
+        if ekt:
+            m2 = self.G[0].size
+            self.estimates[end:end + m2] += res[3]['fock_1p'].ravel()
+            self.estimates[end + m2:end + 2 * m2] += res[3]['fock_1h'].ravel()
         psi._greens_version = -1
         self.accumulated = True
         self.buff_ix = buff_ix
@@ -114,10 +150,43 @@ class BackPropagation(object):
                 self.one_rdm.append(self.global_estimates[start:start + self.G.size].reshape(self.G.shape).copy())
                 if out is not None:
                     out.push(self.one_rdm[-1], 'one_rdm_%d' % self.buff_ix)
+            if self.calc_two_rdm:                      # back_propagation.py:304-308
+                start = self.nreg + 1 + self.G.size
+                M = self.G.shape[-1]
+                self.two_rdm.append(self.global_estimates[start:start + self.two_rdm_size].reshape((M,) * 4).copy())
+                if out is not None:
+                    out.push(self.two_rdm[-1], 'two_rdm_%d' % self.buff_ix)
+            if self.eval_ekt:
+                # back_propagation.py:310-324, slicing included: the offset skips the one-body RDM only when it is
+                # output, so that with one_rdm: False the Fock matrices are read from its region, as there
+                start = self.nreg + 1
+                if self.calc_one_rdm:
+                    start += self.G.size
+                if self.calc_two_rdm:
+                    start += self.two_rdm_size
+                m2 = self.G[0].size
+                shape = self.G[0].shape
+                self.fock_1p.append(self.global_estimates[start:start + m2].reshape(shape).copy())
+                self.fock_1h.append(self.global_estimates[start + m2:start + 2 * m2].reshape(shape).copy())
+                if out is not None:
+                    out.push(self.fock_1p[-1], 'fock_1p_%d' % self.buff_ix)
+                    out.push(self.fock_1h[-1], 'fock_1h_%d' % self.buff_ix)
             if out is not None and self.buff_ix == self.splits[-1]:
                 out.increment()
         self.accumulated = False
         self.zero()
+
+    def _setup_observables(self, dev, system):
+        """afq_bp_observables: the EKT's h1 = system.H1[0] and vectors (back_propagation.py:177-186)."""
+        h1 = L = None
+        if self.eval_ekt:
+            h1 = numpy.asarray(system.H1[0])
+            if system.name == "UEG":
+                cv = system.chol_vecs
+                cv = cv.toarray() if hasattr(cv, 'toarray') else numpy.asarray(cv)
+                L = 2.0 * cv.T.reshape((system.nchol, system.nbasis, system.nbasis))
+        dev.bp_observables(two_rdm=self.calc_two_rdm is not None, ekt=bool(self.eval_ekt), h1=h1, L=L)
+        self._obs_dev = dev
 
     def rdm(self):
         """one_rdm / denominator per window (analysis/extraction.py:36-62)."""
