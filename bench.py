@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: whole-step phaseless-AFQMC throughput in walker-steps/s
 on the BASELINE configs[2] workload (generic Hamiltonian, Nbasis=100, Nchol=500,
-RHF trial with 25+25 electrons, 256 walkers per GPU), plus the fp64-MFMA roofline
-fraction of the Cholesky exchange-energy kernel and the CPU-oracle baseline.
+RHF trial with 25+25 electrons, 256 walkers per GPU).  A plain run sets up, warms
+up, times the steps, writes --dump-outputs and prints the headline line.  With
+--full the line also carries the rooflines of the hot kernels (fp64-MFMA fraction
+of the Cholesky exchange-energy kernel among them), the exchange-step timing and
+the CPU-oracle baseline, from passes of their own after the timed regions; the
+other configurations and sizes (--config, --scaling, --walkers-per-gpu,
+--open-shell, --host-rng, --exchange-stress) run with --full only.
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
                                                            (N > 1 without a launcher: bench.py starts its N ranks itself,
                                                             as child processes, before anything touches the GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -737,7 +742,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=None,
                     help="timed regions of --steps steps each (default: 5 below 100 steps, 3 below 500, else 1); "
                          "the median is reported")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed regions, also the passes behind the rooflines and the exchange-step timing, and the "
+                         "CPU-oracle baseline; needed by every configuration other than the headline's")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle baseline")
     ap.add_argument("--host-rng", action="store_true", help="draw fields with numpy on the host (parity mode)")
     ap.add_argument("--exchange-stress", type=float, default=0.0,
                     help="N > 1: in the exchange-timing pass behind the timed regions, skew the weights between even and odd "
@@ -756,6 +764,13 @@ def main():
         args.steps = 100
     if args.warmup is None:
         args.warmup = 20
+    if not args.full:
+        other = [flag for flag, given in (("--config", args.config != "C3"), ("--scaling", args.scaling != "weak"),
+                                          ("--walkers-per-gpu", args.walkers_per_gpu is not None),
+                                          ("--host-rng", args.host_rng), ("--open-shell", args.open_shell),
+                                          ("--exchange-stress", args.exchange_stress != 0.0)) if given]
+        if other:
+            ap.error("%s: configurations other than the headline's run with --full" % ", ".join(other))
     if args.cpu_worker:                 # child of cpu_socket_processes: numpy only, never touches the GPU
         cpu_worker(args.cpu_worker, args.cpu_window)
         return
@@ -812,7 +827,7 @@ def main():
     scalings = ["weak", "strong"] if args.scaling == "both" else [args.scaling]
     for i, scaling in enumerate(scalings):
         out = run_bench(args, scaling, comm, world, rank, backend, system, trial, state,
-                        with_cpu_baseline=(i == 0 and not args.no_cpu_baseline and world == 1))
+                        with_cpu_baseline=(args.full and i == 0 and not args.no_cpu_baseline and world == 1))
         if rank == 0:
             print(json.dumps(out))
             sys.stdout.flush()
@@ -1035,7 +1050,8 @@ def run_bench(args, scaling, comm, world, rank, backend, system, trial, state, w
     state["phase"] = "timed region"
     # Event pairs around a sample of the launches of the dominant kernel (fused propagator), read after the timed
     # region.  An event pair costs a few microseconds of pipeline bubble on either side of the launch: with every hot
-    # kernel traced the step is 4 % slower, so the other kernels are timed in a separate, untimed pass below.
+    # kernel traced the step is 4 % slower, so the other kernels are timed in a separate, untimed pass below.  A plain run
+    # (no --full) reads none of it but samples the same launches, so that it times the same steps as a --full run.
     from pauxy_amd import _lib as L
     in_region = [L.K_PROPAGATOR]
     # only a sample of the propagator's launches: the event pair around a launch opens a ~5.6 us bubble on either side of
@@ -1075,6 +1091,35 @@ def run_bench(args, scaling, comm, world, rank, backend, system, trial, state, w
         gathered = numpy.zeros(world)
         comm.Allgather(numpy.array(rank_ms), gathered)
         rank_ms = gathered.tolist()
+    out = None
+    if rank == 0:
+        total_walkers = nw * world
+        out = {
+            "metric": "walker_steps_per_sec",
+            "value": total_walkers * args.steps / elapsed,
+            "unit": "walker-steps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps,
+            "ms_per_step_min": 1e3 * min(regions) / args.steps, "ms_per_step_max": 1e3 * max(regions) / args.steps,
+            "repeats": repeats, "timed_regions_ms": [1e3 * r for r in regions],
+            "statistic": "median of %d timed regions of %d steps each (max over ranks per region)" % (repeats, args.steps),
+            "higher_is_better": True, "scaling": scaling if args.walkers_per_gpu is None else "weak",
+            "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "generic Cholesky AFQMC: Nbasis=100, Nchol=500, RHF trial 25+25 electrons, "
+                                   "%d walkers/GPU, dt=0.005, reortho/10, comb/5, energy/10 "
+                                   "(BASELINE configs[2])%s" % (nw, "; OPEN-SHELL walkers (--open-shell: beta blocks perturbed by 1e-3)"
+                                                                if getattr(args, "open_shell", False) else ""),
+                       "walkers_total": total_walkers, "rng": "host-numpy" if args.host_rng else "device-philox",
+                       "backend": ("rccl" if backend == "nccl" else backend) if world > 1 else None,
+                       "population_control": pc_label},
+            "population_control": pc_label,
+            "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms), "per_rank": rank_ms},
+        }
+    if not args.full:
+        state["dev"] = None
+        release_context(system, trial)
+        return out
 
     # Rooflines of the hot kernels from HIP events recorded on the library's stream around every launch
     # (afq_kernel_trace): the dominant kernel INSIDE the timed region, the GEMMs and the exchange energy in an extra pass
@@ -1211,29 +1256,8 @@ def run_bench(args, scaling, comm, world, rank, backend, system, trial, state, w
                                                                   first + extra_steps, eshift,
                                                                   stress=getattr(args, "exchange_stress", 0.0), rank=rank)
     exq = next((r for r in rows if "exchange energy" in r["kernel"]), None)
-    out = None
     if rank == 0:
-        total_walkers = nw * world
-        out = {
-            "metric": "walker_steps_per_sec",
-            "value": total_walkers * args.steps / elapsed,
-            "unit": "walker-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "ms_per_step_min": 1e3 * min(regions) / args.steps, "ms_per_step_max": 1e3 * max(regions) / args.steps,
-            "repeats": repeats, "timed_regions_ms": [1e3 * r for r in regions],
-            "statistic": "median of %d timed regions of %d steps each (max over ranks per region)" % (repeats, args.steps),
-            "higher_is_better": True, "scaling": scaling if args.walkers_per_gpu is None else "weak",
-            "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "generic Cholesky AFQMC: Nbasis=100, Nchol=500, RHF trial 25+25 electrons, "
-                                   "%d walkers/GPU, dt=0.005, reortho/10, comb/5, energy/10 "
-                                   "(BASELINE configs[2])%s" % (nw, "; OPEN-SHELL walkers (--open-shell: beta blocks perturbed by 1e-3)"
-                                                                if getattr(args, "open_shell", False) else ""),
-                       "walkers_total": total_walkers, "rng": "host-numpy" if args.host_rng else "device-philox",
-                       "backend": ("rccl" if backend == "nccl" else backend) if world > 1 else None,
-                       "population_control": pc_label},
-            "population_control": pc_label,
+        out.update({
             "comm_stats": comm_stats,
             "comm_stats_per_rank": comm_per_rank,
             # Walkers._init_device_comm returns a communicator only after afq_comm_probe (known-answer all-gather, one
@@ -1241,7 +1265,6 @@ def run_bench(args, scaling, comm, world, rank, backend, system, trial, state, w
             "comm_probe": ("passed on every rank (%s)" % comm_kind) if device_comm else
                           (None if world == 1 else "no device communicator: " + (comm_note or "not requested")),
             "exchange_timing": exchange_timing,
-            "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms), "per_rank": rank_ms},
             # (device Philox streams: the same library gives the same number every run; kernel variants that claim
             #  bit-equal results can be held against it)
             "last_block_ETotal": last_block_energy(afqmc),
@@ -1271,7 +1294,7 @@ def run_bench(args, scaling, comm, world, rank, backend, system, trial, state, w
                              "frac_vs_reference_formulation": exq.get("effective_vs_reference_formulation"),
                              "measured": exq["measured"]}},
             "roofline_all": rows,
-        }
+        })
         if with_cpu_baseline:                                   # reported at N = 1 only
             state["phase"] = "cpu baseline"
             out["cpu_baseline"] = cpu_baseline(system, trial)

@@ -37,6 +37,16 @@ def test_bench_rejects_mismatched_launcher():
     assert p.returncode != 0 and "WORLD_SIZE=3" in p.stderr
 
 
+@pytest.mark.parametrize("extra", [["--config", "C5"], ["--scaling", "strong"], ["--walkers-per-gpu", "64"],
+                                   ["--host-rng"], ["--open-shell"], ["--exchange-stress", "0.1"]])
+def test_bench_other_configurations_need_full(extra):
+    """A plain run is the headline configuration only: any other one is refused before anything else runs."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0"] + extra,
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and p.stdout == ""
+    assert "%s: configurations other than the headline's run with --full" % extra[0] in p.stderr, p.stderr
+
+
 def test_roofline_tool_prices_what_closed_shell_walkers_execute():
     """tools/roofline_configs.py prices the profiler's launches with the `closed_shell` object of the bench line the same run
     printed (the device's counts): executed columns of the large-system GEMM chain, one spin of the exchange energy, the

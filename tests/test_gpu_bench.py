@@ -6,6 +6,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -13,10 +14,13 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(extra, env_extra=None):
+def run_bench(extra, env_extra=None, full=True):
+    """bench.py's JSON lines; `full`: with the passes behind the rooflines and the exchange timing (--full), without the
+    CPU-oracle baseline."""
+    extra = (["--full", "--no-cpu-baseline"] if full else []) + extra
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(env_extra or {})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + extra, env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, env=env,
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -32,19 +36,24 @@ def require_gpus(n):
         pytest.skip("needs %d GPUs (one per rank), found %d" % (n, found))
 
 
-def check_line(out, n_gpus, steps, walkers_total):
+def check_headline(out, n_gpus, steps, walkers_total):
     assert out["metric"] == "walker_steps_per_sec" and out["unit"] == "walker-steps/s"
     assert out["n_gpus"] == n_gpus and out["steps"] == steps and out["dtype"] == "f64"
+    assert out["higher_is_better"] is True
     assert out["config"]["walkers_total"] == walkers_total
     assert out["repeats"] == len(out["timed_regions_ms"]) >= 1
     assert out["ms_per_step_min"] <= out["ms_per_step"] <= out["ms_per_step_max"]
     assert out["value"] == pytest.approx(walkers_total * 1e3 / out["ms_per_step"], rel=1e-9)
+    assert len(out["rank_ms_per_step"]["per_rank"]) == n_gpus
+
+
+def check_line(out, n_gpus, steps, walkers_total):
+    check_headline(out, n_gpus, steps, walkers_total)
     r = out["roofline"]
     assert r["bound"] == "mfma" and 0.0 < r["frac"] < 1.0
     assert 0.0 < r["frac_issued"] < 1.0                               # a utilisation: can never exceed the peak
     for row in out["roofline_all"]:
         assert 0.0 < row["frac_issued"] < 1.0, row["kernel"]
-    assert len(out["rank_ms_per_step"]["per_rank"]) == n_gpus
     # device-timed cost of one population-control event and one block reduction
     et = out["exchange_timing"]
     assert et["popcontrol_event_us"] > 0.0 and et["per_popcontrol_event_us"]
@@ -68,6 +77,19 @@ def test_bench_one_gpu_short_region_is_repeated():
     assert r["flops_per_launch"] == pytest.approx(100 * 100 * (8.0 * 6 * 25 + 4.0 * 2 * 50) * 256)
     assert "one spin evaluated" in r["cholesky_energy"]["kernel"]
     assert out["last_block_ETotal"] is not None and abs(out["last_block_ETotal"]) < 1e4
+
+
+def test_bench_plain_run_prints_the_headline_only():
+    """Without --full the line holds the timed regions and nothing measured after them: no rooflines, no exchange timing,
+    no CPU-oracle baseline; the whole process spends less than 30 s outside its steps."""
+    t0 = time.perf_counter()
+    (out,) = run_bench(["--steps", "20", "--warmup", "10"], full=False)
+    wall = time.perf_counter() - t0
+    check_headline(out, 1, 20, 256)
+    assert out["repeats"] == 5 and out["scaling"] == "weak"
+    for key in ("roofline", "roofline_all", "exchange_timing", "cpu_baseline", "last_block_ETotal"):
+        assert key not in out, key
+    assert wall - (10 + 5 * 20) * 1e-3 * out["ms_per_step"] < 30.0, wall
 
 
 def test_bench_two_ranks_self_launched_strong():

@@ -3,7 +3,7 @@ walkers, device Philox fields, `run_batched` with overlapped block boundaries, r
 ORACLE fed with the same stream restated on the host (tests/philox_ref.py) and the same comb uniforms: every block row must
 agree -- the total energy of the last block is the `last_block_ETotal` of the bench line.  The oracle runs as a pool of
 processes (a walker-step costs it ~45 ms): by default 60 steps; AFQ_BENCH_ORACLE_STEPS=580 is the schedule of the default
-`python bench.py` (20 warm-up + 5 x 100 timed + 40 + 20 traced steps), whose result is kept under profiles/."""
+`python bench.py --full` (20 warm-up + 5 x 100 timed + 40 + 20 traced steps), whose result is kept under profiles/."""
 import multiprocessing
 import os
 

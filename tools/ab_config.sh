@@ -6,7 +6,7 @@ export AFQ_LIBRARY=$PWD/pauxy_amd/libafqmc_hip_tuning.so
 i=0
 for envs in "$@"; do
   i=$((i+1))
-  ( export $envs; python3 bench.py --config $cfg --no-cpu-baseline > $out/run$i.json 2> $out/run$i.err )
+  ( export $envs; python3 bench.py --full --config $cfg --no-cpu-baseline > $out/run$i.json 2> $out/run$i.err )
   python3 - "$out/run$i.json" "$envs" <<'PY'
 import json, sys
 try:

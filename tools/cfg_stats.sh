@@ -3,7 +3,7 @@
 out=gpurun_out/$1; cfg=$2; shift; shift
 mkdir -p $out
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$cfg -o $cfg -- python3 bench.py --config $cfg --no-cpu-baseline "$@" > $out/$cfg.json 2> $out/$cfg.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$cfg -o $cfg -- python3 bench.py --full --config $cfg --no-cpu-baseline "$@" > $out/$cfg.json 2> $out/$cfg.err
 f=$(ls $out/prof_$cfg/*kernel_stats.csv $out/prof_$cfg/*/*kernel_stats.csv 2>/dev/null | head -1)
 [ -n "$f" ] && cp $f $out/${cfg}_kernel_stats.csv && python3 - $out/${cfg}_kernel_stats.csv <<'PY'
 import csv, sys

@@ -7,7 +7,7 @@ for mode in ipc auto; do
   for r in 2 4 8; do
     ok=0
     for i in $(seq $n); do
-      if AFQ_BENCH_BACKEND=gloo AFQ_BENCH_DEVICE_COMM=$mode timeout 300 python3 bench.py --gpus $r --walkers-per-gpu $((512/r)) --steps 20 --warmup 10 --no-cpu-baseline > $out/_mr.json 2> $out/_mr.err; then
+      if AFQ_BENCH_BACKEND=gloo AFQ_BENCH_DEVICE_COMM=$mode timeout 300 python3 bench.py --full --gpus $r --walkers-per-gpu $((512/r)) --steps 20 --warmup 10 --no-cpu-baseline > $out/_mr.json 2> $out/_mr.err; then
         python3 - $out/_mr.json "$mode $r ranks run $i" >> $out/multirank_repeat.txt <<'PY' && ok=$((ok+1))
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -17,10 +17,10 @@ run_pmc() {     # name, counter, command...
   rocprofv3 --pmc $ctr --output-format csv -d $out/${name}_$ctr -o pmc -- "$@" > /dev/null 2> $out/${name}_$ctr.err
   f=$(ls $out/${name}_$ctr/*counter_collection.csv $out/${name}_$ctr/*/*counter_collection.csv 2>/dev/null | head -1); [ -n "$f" ] && python3 tools/pmc_csv.py $f > $out/${name}_pmc_$ctr.txt
 }
-run_stats bench_c3 python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline
-for c in C1 C2 C4 C5sd C5; do run_stats cfg_$c python3 bench.py --config $c --no-cpu-baseline; done
+run_stats bench_c3 python3 bench.py --full --steps 100 --warmup 20 --no-cpu-baseline
+for c in C1 C2 C4 C5sd C5; do run_stats cfg_$c python3 bench.py --full --config $c --no-cpu-baseline; done
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  run_pmc bench_c3 $ctr python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
-  for c in C2 C4 C5; do run_pmc cfg_$c $ctr python3 bench.py --config $c --no-cpu-baseline --repeats 1; done
+  run_pmc bench_c3 $ctr python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
+  for c in C2 C4 C5; do run_pmc cfg_$c $ctr python3 bench.py --full --config $c --no-cpu-baseline --repeats 1; done
 done
 ls $out

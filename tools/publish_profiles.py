@@ -75,8 +75,8 @@ def main():
         return out
     tag = os.path.basename(os.path.normpath(src))
     traffic = {
-        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps 20 --warmup 5 "
-                  "--no-cpu-baseline, and -- python3 bench.py --config C2 | C4 | C5 --no-cpu-baseline --repeats 1 under "
+        "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 20 --warmup 5 "
+                  "--no-cpu-baseline, and -- python3 bench.py --full --config C2 | C4 | C5 --no-cpu-baseline --repeats 1 under "
                   "'configs' (tools/profile_round.sh %s); per-kernel means in profiles/%s_*_pmc_FETCH_SIZE.txt / "
                   "_WRITE_SIZE.txt" % (tag, rnd),
         "note": "FETCH_SIZE / WRITE_SIZE are KB of L2 memory-side requests (Infinity-Cache hits included); FETCH_SIZE is doubled "

@@ -6,7 +6,7 @@ mkdir -p $out
 export AFQ_LIBRARY=$PWD/pauxy_amd/libafqmc_hip_tuning.so
 export TMPDIR=/tmp
 for abl in "$@"; do
-  ( export AFQ_VHS_ABL=$abl AFQ_GEMM_TS=1; rocprofv3 --kernel-trace --stats --output-format csv -d $out/p$abl -o p -- python3 bench.py --steps 40 --warmup 10 --repeats 1 --no-cpu-baseline > $out/run$abl.json 2> $out/run$abl.err )
+  ( export AFQ_VHS_ABL=$abl AFQ_GEMM_TS=1; rocprofv3 --kernel-trace --stats --output-format csv -d $out/p$abl -o p -- python3 bench.py --full --steps 40 --warmup 10 --repeats 1 --no-cpu-baseline > $out/run$abl.json 2> $out/run$abl.err )
   f=$(ls $out/p$abl/*kernel_stats.csv $out/p$abl/*/*kernel_stats.csv 2>/dev/null | head -1)
   python3 - "$f" "$abl" <<'PY'
 import csv, sys
