@@ -209,6 +209,26 @@ int afq_bp_ekt_chunks(afq_handle *h, int nc, int ncy);
 int afq_bp_update_ext(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
                       int reset, double *est_out, double *two_rdm_out, double *fock_out);
 
+/* Imaginary-time single-particle Green's function (the ITCF estimator, estimators/itcf.py of the reference).
+ * afq_itcf_configure: windows of n = nmax + neqlb steps (nmax >= 1, neqlb >= 0); sizes the field history of
+ * afq_bp_configure to n (a history of another length configured before: AFQ_ESTATE), which comb, copy and pack carry
+ * as for back-propagation.  stable: 1 the Feldbacher-Assaad chain, 0 the plain products; restore_weights: 1 weighs a
+ * walker by weight * (phase product / cosine product) of the window, 0 by its weight.
+ * AFQ_EUNSUPPORTED: M > 128, plane-wave (UEG) systems, continuous Hubbard fields, multi-determinant trials, general
+ * complex Cholesky vectors, restore_weights with discrete fields, free projection.
+ * afq_itcf_update: one window over the recorded history and the trial psi_T c128[M, na+nb] (the window's left end):
+ *   B_t = BT2 E(x_t) BT2 (E the order-6 Taylor exponential of the VHS, or diag(auxf) for discrete fields),
+ *   psi_R(0) the walkers at the window start, psi_R(t+1) = B_t psi_R(t); psi_L(n) = psi_T, psi_L(t) = B_t^H psi_L(t+1);
+ *   both re-orthogonalised every nstblz steps; P(t) = gab(psi_L(t), psi_R(t)) per spin;
+ *   stable: Ggr(t+1) = B_t (I - P(t)) Ggr(t), Gls(t+1) = Gls(t) P(t) B_t^-1 from Ggr(0) = I - P(0), Gls(0) = P(0);
+ *   unstable: Ggr(t+1) = B_t Ggr(t), Gls(t+1) = Gls(t) B_t^-1;
+ *   spgf_out c128[nmax+1][2 spin][2: greater, lesser][M][M] = sum_w wfac_w Re G_w(t), denom_out c128 = sum_w wfac_w
+ *   (walkers without a complete window count 0).  Then the history restarts and the window start is the walkers now.
+ * AFQ_ESTATE before afq_itcf_configure; AFQ_ENOMEM when the stored psi_L
+ * (16 nw nmax M (na+nb) bytes) exceed half of the free device memory.                                 */
+int afq_itcf_configure(afq_handle *h, int nmax, int neqlb, int stable, int restore_weights);
+int afq_itcf_update(afq_handle *h, const double *psi_T, int nstblz, double *spgf_out, double *denom_out);
+
 /* Multi-determinant (NOMSD / PHMSD) trial |psi_T> = sum_d c_d |D_d> for a generic system, replacing
  * the single-determinant operands of afq_set_system_generic / afq_set_trial.  Call after the
  * system and before afq_walkers_alloc.

@@ -110,6 +110,7 @@ void free_walkers(afq_handle *h) {
     h->nbp = 0; dev_free(h->xbar); dev_free(h->xs);
     dev_free(h->bpo_h1); dev_free(h->bpo_L); dev_free(h->bpo_wt); dev_free(h->bpo_out); dev_free(h->bpo_ws);
     h->bpo_ws_len = 0; h->bpo_two = h->bpo_ekt = 0; h->bpo_nL = 0;
+    dev_free(h->it_ws); h->it_ws_len = 0; h->it_nmax = 0;
     dev_free(h->cmf); dev_free(h->cfb); dev_free(h->vhs); dev_free(h->lu_ws);
     dev_free(h->gj_flag); dev_free(h->big_ws); dev_free(h->big_ws2); dev_free(h->detm); dev_free(h->dete); dev_free(h->qr_logd); dev_free(h->qr_fail);
     dev_free(h->energy); dev_free(h->exx_part); dev_free(h->gfrag); dev_free(h->exq_y); h->exq_y_len = 0;
@@ -1922,6 +1923,53 @@ int afq_bp_steps(afq_handle *h, int32_t *steps_out) {
     return rc;
 }
 
+// phi_bp <- B(x_0)^H ... B(x_{n-1})^H phi_bp over the recorded history, re-orthogonalised after the i-th step from the end
+// when i != 0 and i % nstblz == 0 (propagation/generic.py:279-288, hubbard.py:661-671).  With keep, phi_bp after the
+// step of window slice t (= nbp - 1 - i) is copied to keep + t nw M nt for t < nkeep (the ITCF's psi_L(t)).
+static int bp_backward(afq_handle *h, int nstblz, cplx *keep, int nkeep) {
+    const size_t n = h->nw, per = (size_t)h->M * h->nt;
+    // borrow the step machinery: phi <- phi_bp, BH1 <- BH1^H, fields <- -conj(x), every walker "alive"
+    // while it still has recorded steps; the walkers' own overlaps / detR / weights are parked
+    cplx *s_phi = h->phi, *s_xs = h->xs, *s_BH1 = h->BH1, *s_ot = h->ot;
+    double *s_detR = h->detR;
+    const int s_flags = h->flags;
+    cplx *tmp_ot = nullptr; double *tmp_detR = nullptr;
+    int rc;
+    if ((rc = dev_alloc(h, &tmp_ot, n))) return rc;
+    if ((rc = dev_alloc(h, &tmp_detR, n))) { dev_free(tmp_ot); return rc; }
+    h->phi = h->phi_bp; h->xs = h->bp_xs; h->BH1 = h->BH1dag; h->ot = tmp_ot; h->detR = tmp_detR;
+    h->flags &= ~AFQ_PROP_FREE_PROJECTION;
+    const bool fused = k_prop_fused_supported(h);
+    rc = AFQ_OK;
+    for (int i = 0; i < h->nbp && !rc; ++i) {                       // propagation/generic.py:279-288
+        if (h->hirsch) {                                            // propagation/hubbard.py:661-671
+            rc = k_bp_hirsch_step(h, i);
+        } else {
+            if ((rc = k_bp_fields(h, i))) break;
+            h->vhs_upper = fused && h->hs_sym && !h->no_vhs_upper;
+            rc = build_vhs(h);
+            if (!rc && fused) rc = k_prop_fused(h);
+            h->vhs_upper = false;
+            if (rc) break;
+            if (!fused) {
+                if ((rc = k_onebody(h))) break;
+                if ((rc = apply_exp(h, h->vhs))) break;
+                rc = k_onebody(h);
+            }
+        }
+        if (!rc && i != 0 && i % nstblz == 0) rc = k_reortho(h);    // utils/linalg.py:82-105 on both spins
+        const int t = h->nbp - 1 - i;
+        if (!rc && keep && t < nkeep) {
+            const hipError_t e = hipMemcpyAsync(keep + (size_t)t * n * per, h->phi_bp, sizeof(cplx) * n * per,
+                                                hipMemcpyDeviceToDevice, h->stream);
+            if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = AFQ_EHIP; }
+        }
+    }
+    h->phi = s_phi; h->xs = s_xs; h->BH1 = s_BH1; h->ot = s_ot; h->detR = s_detR; h->flags = s_flags;
+    dev_free(tmp_ot); dev_free(tmp_detR);
+    return rc;
+}
+
 static int bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
                      int reset, double *est_out, double *two_rdm_out, double *fock_out) {
     if (h) { h->greens_valid = false; h->gsum_only = false; }
@@ -1935,44 +1983,11 @@ static int bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int resto
     // trial (or initial) determinant for every walker; the second half of phi_bp is upload scratch first
     AFQ_HIP(h, hipMemcpyAsync(h->phi_bp + per * n, phi_bp0, sizeof(cplx) * per, hipMemcpyHostToDevice, h->stream));
     if ((rc = k_bp_init(h, h->phi_bp + per * n))) return rc;
-    // borrow the step machinery: phi <- phi_bp, BH1 <- BH1^H, fields <- -conj(x), every walker "alive"
-    // while it still has recorded steps; the walkers' own overlaps / detR / weights are parked
-    cplx *s_phi = h->phi, *s_xs = h->xs, *s_BH1 = h->BH1, *s_ot = h->ot;
-    double *s_detR = h->detR;
-    const int s_flags = h->flags;
-    cplx *tmp_ot = nullptr; double *tmp_detR = nullptr;
-    if ((rc = dev_alloc(h, &tmp_ot, n))) return rc;
-    if ((rc = dev_alloc(h, &tmp_detR, n))) { dev_free(tmp_ot); return rc; }
-    h->phi = h->phi_bp; h->xs = h->bp_xs; h->BH1 = h->BH1dag; h->ot = tmp_ot; h->detR = tmp_detR;
-    h->flags &= ~AFQ_PROP_FREE_PROJECTION;
-    const bool fused = k_prop_fused_supported(h);
-    rc = AFQ_OK;
-    for (int i = 0; i < h->nbp && !rc; ++i) {                       // propagation/generic.py:279-288
-        if (h->hirsch) {                                            // propagation/hubbard.py:661-671
-            rc = k_bp_hirsch_step(h, i);
-            if (!rc && i != 0 && i % nstblz == 0) rc = k_reortho(h);
-            continue;
-        }
-        if ((rc = k_bp_fields(h, i))) break;
-        h->vhs_upper = fused && h->hs_sym && !h->no_vhs_upper;
-        rc = build_vhs(h);
-        if (!rc && fused) rc = k_prop_fused(h);
-        h->vhs_upper = false;
-        if (rc) break;
-        if (!fused) {
-            if ((rc = k_onebody(h))) break;
-            if ((rc = apply_exp(h, h->vhs))) break;
-            rc = k_onebody(h);
-        }
-        if (!rc && i != 0 && i % nstblz == 0) rc = k_reortho(h);    // utils/linalg.py:82-105 on both spins
-    }
-    h->phi = s_phi; h->xs = s_xs; h->BH1 = s_BH1; h->ot = s_ot; h->detR = s_detR; h->flags = s_flags;
-    dev_free(tmp_ot); dev_free(tmp_detR);
-    if (rc) return rc;
+    if ((rc = bp_backward(h, nstblz, nullptr, 0))) return rc;
     // G_bp[w] = gab(phi_bp, phi_old)^T (back_propagation.py:156-157) = the Green's function of phi_old with
     // phi_bp[w] in the role of the trial
     if ((rc = k_conj_copy(h, h->phi_bp, h->phi_bp + per * n, (long)(per * n)))) return rc;
-    cplx *s_psi = h->psi, *s_psic = h->psic;
+    cplx *s_phi = h->phi, *s_psi = h->psi, *s_psic = h->psic;
     h->phi = h->phi_old; h->psi = h->phi_bp; h->psic = h->phi_bp + per * n; h->psi_stride = (long)per;
     rc = k_greens(h, h->ovlp_old);
     if (!rc) rc = ensure_G(h);
@@ -2057,6 +2072,160 @@ int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, co
     if ((two_rdm || ekt) && (rc = dev_alloc(h, &h->bpo_out, (two_rdm ? m4 : 0) + (ekt ? 2 * M * M : 0)))) return rc;
     h->bpo_two = two_rdm ? 1 : 0; h->bpo_ekt = ekt ? 1 : 0;
     return AFQ_OK;
+}
+
+// ---------------------------------------------------------------- imaginary-time Green's function (k_itcf.hip)
+int afq_itcf_configure(afq_handle *h, int nmax, int neqlb, int stable, int restore_weights) {
+    if (!h || nmax < 1 || neqlb < 0) return AFQ_EINVAL;
+    int rc = need_ready(h, true);
+    if (rc) return rc;
+    if (h->M > 128) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "ITCF: M > 128 (the batched Gauss-Jordan inverse)");
+    if (h->kind == AFQ_SYS_UEG) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "ITCF: no propagator matrix for the UEG (itcf.py:114-122)");
+    if (h->hirsch && restore_weights)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "restore_weights with discrete fields: FieldConfig.push records no weight factors (walkers/stack.py:35-49)");
+    const int n = nmax + neqlb;
+    if (h->nbp && h->nbp != n)
+        AFQ_FAIL(h, AFQ_ESTATE, "ITCF: a field history of " + std::to_string(h->nbp) + " steps is configured, the window needs " +
+                                    std::to_string(n));
+    // (afq_bp_configure refuses multi-determinant trials, continuous Hubbard fields, free projection and general
+    //  complex Cholesky vectors)
+    if (!h->nbp && (rc = afq_bp_configure(h, n))) return rc;
+    h->it_nmax = nmax; h->it_neqlb = neqlb; h->it_stable = stable ? 1 : 0; h->it_restore = restore_weights ? 1 : 0;
+    return AFQ_OK;
+}
+
+// the window's device scratch, kept on the handle and grown on demand (a larger window frees the old buffer first)
+static int itcf_scratch(afq_handle *h, size_t n, cplx **out) {
+    if (n > h->it_ws_len) {
+        if (h->it_ws) { hipStreamSynchronize(h->stream); dev_free(h->it_ws); h->it_ws_len = 0; }
+        const int rc = dev_alloc(h, &h->it_ws, n);
+        if (rc) return rc;
+        h->it_ws_len = n;
+    }
+    *out = h->it_ws;
+    return AFQ_OK;
+}
+
+static int itcf_greens(afq_handle *h, cplx *psiR, cplx *psiL, cplx *psiLc, cplx *ovlp, cplx *P, cplx *Q) {
+    // P = gab(psi_L, psi_R) per spin: the Green's function of psi_R with psi_L[w] in the role of the trial, as the
+    // back-propagated G of bp_update
+    const size_t per = (size_t)h->M * h->nt;
+    int rc = k_conj_copy(h, psiL, psiLc, (long)(per * h->nw));
+    if (rc) return rc;
+    cplx *s_phi = h->phi, *s_psi = h->psi, *s_psic = h->psic;
+    h->phi = psiR; h->psi = psiL; h->psic = psiLc; h->psi_stride = (long)per;
+    rc = k_greens(h, ovlp);
+    if (!rc) rc = ensure_G(h);
+    if (!rc) rc = k_full_G(h);
+    h->phi = s_phi; h->psi = s_psi; h->psic = s_psic; h->psi_stride = 0;
+    if (rc) return rc;
+    return k_itcf_projectors(h, h->G, P, Q);
+}
+
+int afq_itcf_update(afq_handle *h, const double *psi_T, int nstblz, double *spgf_out, double *denom_out) {
+    AFQ_API(h, "afq_itcf_update");
+    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (!h || !psi_T || !spgf_out || !denom_out || nstblz < 1) return AFQ_EINVAL;
+    int rc = need_ready(h, true);
+    if (rc) return rc;
+    if (!h->it_nmax) AFQ_FAIL(h, AFQ_ESTATE, "ITCF is not configured: afq_itcf_configure first");
+    if (h->nbp != h->it_nmax + h->it_neqlb) AFQ_FAIL(h, AFQ_ESTATE, "ITCF: the field history changed length");
+    const int M = h->M, nw = h->nw, nmax = h->it_nmax;
+    const size_t per = (size_t)M * h->nt, mm = (size_t)M * M, g2 = 2 * mm * nw, nspgf = (size_t)(nmax + 1) * 4 * mm;
+    // psi_L(t) is read for every slice by the stable chain, for t = 0 only by the unstable one
+    const bool stable = h->it_stable != 0;
+    const int nkeep = stable ? nmax : 1;
+    const bool gen = !h->hirsch;
+    // scratch in complex units: psi_L, psi_R (x2), conj(psi_L), BT2^-1, B, B^-1, P, Q, Ggr, Gls, T, the Generic Taylor
+    // workspace and fields or the discrete diagonals, wfac, [denom | spgf], determinants (mantissa, exponent), overlaps
+    // and the parked ot / detR of the re-orthogonalisation
+    const size_t sizes[] = {(size_t)nkeep * nw * per, nw * per, nw * per, nw * per, 2 * mm, g2, g2, g2, g2, g2, g2, g2,
+                            gen ? 2 * nw * mm + g2 : 0, gen ? (size_t)nw * h->K : 2 * (size_t)nw * M, (size_t)nw,
+                            1 + nspgf, (size_t)nw + 2, (size_t)nw + 2, (size_t)nw, (size_t)nw, (size_t)nw};
+    size_t total = 0;
+    for (size_t x : sizes) total += x;
+    {
+        size_t fr = 0, tot = 0;
+        AFQ_HIP(h, hipMemGetInfo(&fr, &tot));
+        const double need = 16.0 * (double)nw * nkeep * per;
+        const double avail = (double)fr + 16.0 * (double)h->it_ws_len;   // (a buffer that has to grow is freed first)
+        if (need > 0.5 * avail)
+            AFQ_FAIL(h, AFQ_ENOMEM, "ITCF: the stored psi_L take " + std::to_string((unsigned long long)need) +
+                                        " bytes, more than half of the free device memory (" +
+                                        std::to_string((unsigned long long)avail) + " bytes)");
+    }
+    cplx *base;
+    if ((rc = itcf_scratch(h, total, &base))) return rc;
+    cplx *part[sizeof(sizes) / sizeof(sizes[0])];
+    for (size_t i = 0, off = 0; i < sizeof(sizes) / sizeof(sizes[0]); off += sizes[i], ++i) part[i] = base + off;
+    cplx *psiL = part[0], *psiR = part[1], *psiR2 = part[2], *psiLc = part[3], *BT2inv = part[4], *B = part[5];
+    cplx *Binv = part[6], *P = part[7], *Q = part[8], *Ggr = part[9], *Gls = part[10], *T = part[11];
+    cplx *ws = part[12], *xs = part[13], *wfac = part[14], *est = part[15], *detm = part[16];
+    int *dete = (int *)part[17];
+    cplx *ovlp = part[18], *tmp_ot = part[19];
+    double *tmp_detR = (double *)part[20], *f = (double *)part[13];
+    // BT2^-1 per spin
+    AFQ_HIP(h, hipMemcpyAsync(BT2inv, h->BH1, sizeof(cplx) * 2 * mm, hipMemcpyDeviceToDevice, h->stream));
+    if ((rc = k_gj_inverse(h, BT2inv, M, 2, detm, dete))) return rc;
+    // 1. psi_L(t) = B_t^H psi_L(t+1) from psi_L(n) = psi_T: the back-propagation of bp_update, psi_L(t < nkeep) kept
+    AFQ_HIP(h, hipMemcpyAsync(h->phi_bp + per * nw, psi_T, sizeof(cplx) * per, hipMemcpyHostToDevice, h->stream));
+    if ((rc = k_bp_init(h, h->phi_bp + per * nw))) return rc;
+    if ((rc = bp_backward(h, nstblz, psiL, nkeep))) return rc;
+    // 2. weights of the window (the alive flags of the last backward step mark the walkers with a complete window)
+    AFQ_HIP(h, hipMemsetAsync(est, 0, sizeof(cplx) * (1 + nspgf), h->stream));
+    if ((rc = k_itcf_weights(h, h->it_restore, wfac, est))) return rc;
+    // 3. forward: psi_R, P(t), the B matrices and the chains
+    AFQ_HIP(h, hipMemcpyAsync(psiR, h->phi_old, sizeof(cplx) * nw * per, hipMemcpyDeviceToDevice, h->stream));
+    for (int tau = 0; tau < nmax; ++tau) {
+        if (stable || tau == 0) {
+            if ((rc = itcf_greens(h, psiR, psiL + (size_t)tau * nw * per, psiLc, ovlp, P, Q))) return rc;
+        }
+        if (tau == 0) {
+            AFQ_HIP(h, hipMemcpyAsync(Ggr, Q, sizeof(cplx) * g2, hipMemcpyDeviceToDevice, h->stream));
+            AFQ_HIP(h, hipMemcpyAsync(Gls, P, sizeof(cplx) * g2, hipMemcpyDeviceToDevice, h->stream));
+            if ((rc = k_itcf_accumulate(h, Ggr, Gls, wfac, est + 1))) return rc;
+        }
+        if (gen) {
+            cplx *s_xs = h->xs;
+            h->xs = xs;
+            rc = k_itcf_fields(h, xs, tau);
+            if (!rc) rc = build_vhs(h);
+            h->xs = s_xs;
+            if (!rc) rc = k_itcf_generic_b(h, h->vhs, h->BH1, BT2inv, B, Binv, ws, detm, dete);
+        } else {
+            rc = k_itcf_hirsch_b(h, tau, h->BH1, BT2inv, B, Binv, f);
+        }
+        if (rc) return rc;
+        if (stable) {                                   // Ggr <- B (I - P) Ggr, Gls <- Gls P B^-1
+            if ((rc = k_itcf_mul(h, Q, Ggr, T)) || (rc = k_itcf_mul(h, B, T, Ggr))) return rc;
+            if ((rc = k_itcf_mul(h, Gls, P, T)) || (rc = k_itcf_mul(h, T, Binv, Gls))) return rc;
+        } else {                                        // Ggr <- B Ggr, Gls <- Gls B^-1
+            if ((rc = k_itcf_mul(h, B, Ggr, T))) return rc;
+            std::swap(Ggr, T);
+            if ((rc = k_itcf_mul(h, Gls, Binv, T))) return rc;
+            std::swap(Gls, T);
+        }
+        if ((rc = k_itcf_accumulate(h, Ggr, Gls, wfac, est + 1 + (size_t)(tau + 1) * 4 * mm))) return rc;
+        if (stable && tau + 1 < nmax) {
+            if ((rc = k_itcf_propagate(h, B, psiR, psiR2))) return rc;
+            std::swap(psiR, psiR2);
+            if (tau != 0 && tau % nstblz == 0) {
+                cplx *s_phi = h->phi, *s_ot = h->ot;
+                double *s_detR = h->detR;
+                const int s_flags = h->flags;
+                h->phi = psiR; h->ot = tmp_ot; h->detR = tmp_detR; h->flags &= ~AFQ_PROP_FREE_PROJECTION;
+                rc = k_reortho(h);
+                h->phi = s_phi; h->ot = s_ot; h->detR = s_detR; h->flags = s_flags;
+                if (rc) return rc;
+            }
+        }
+    }
+    // 4. FieldConfig.reset + copy_init_wfn: the next window starts from the walkers now
+    if ((rc = k_bp_reset(h, false))) return rc;
+    AFQ_HIP(h, hipMemcpyAsync(h->phi_old, h->phi, sizeof(cplx) * per * nw, hipMemcpyDeviceToDevice, h->stream));
+    if ((rc = k_alive(h))) return rc;
+    if ((rc = copy_out(h, denom_out, est, sizeof(cplx)))) return rc;
+    return copy_out(h, spgf_out, est + 1, sizeof(cplx) * nspgf);
 }
 
 int afq_local_energy_full_g(afq_handle *h, const double *G, int n, double *E_out) {

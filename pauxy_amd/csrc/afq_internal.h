@@ -182,6 +182,11 @@ struct afq_handle {
     cplx *bpo_ws = nullptr;         // scratch, grown on demand
     size_t bpo_ws_len = 0;
     int bpo_nc = 0, bpo_ncy = 0;    // afq_bp_ekt_chunks: x per chunk of the panels / of the linear term (0: automatic)
+    // imaginary-time Green's function (afq_itcf_configure / afq_itcf_update, k_itcf.hip): window of nmax + neqlb steps
+    // on the field history above (nbp == nmax + neqlb); 0 = off
+    int it_nmax = 0, it_neqlb = 0, it_stable = 1, it_restore = 0;
+    cplx *it_ws = nullptr;          // the window's scratch, grown on demand
+    size_t it_ws_len = 0;
 
     // ---- discrete Hirsch propagator (propagation/hubbard.py:12-343)
     bool hirsch = false;
@@ -457,12 +462,23 @@ int k_fullg_expand(afq_handle *h);                         // L_full (real vecto
 // k_bp_obs.hip: sum_w wt_w two_rdm[G_bp[w]] -> two_out [M^4], sum_w wt_w (F1p, F1h)[G_bp[w]] -> fock_out [2, M, M]
 // (either may be null); after afq_bp_update's accumulation, before its reset
 int k_bp_observables(afq_handle *h, int restore, cplx *two_out, cplx *fock_out);
+// k_itcf.hip: the pieces of one imaginary-time Green's function window (afq_itcf_update)
+int k_itcf_fields(afq_handle *h, cplx *xs, int t);           // xs[w] = recorded fields of window step t
+int k_itcf_generic_b(afq_handle *h, const cplx *vhs, const cplx *BT2, const cplx *BT2inv, cplx *B, cplx *Binv, cplx *ws,
+                     cplx *detm, int *dete);                 // B, B^-1 [nw, 2, M, M] of the VHS [nw, M, M]
+int k_itcf_hirsch_b(afq_handle *h, int t, const cplx *BT2, const cplx *BT2inv, cplx *B, cplx *Binv, double *f);
+int k_itcf_mul(afq_handle *h, const cplx *A, const cplx *B, cplx *C);                // C = A B per (walker, spin)
+int k_itcf_propagate(afq_handle *h, const cplx *B, const cplx *src, cplx *dst);     // dst = B src per spin block
+int k_itcf_projectors(afq_handle *h, const cplx *G, cplx *P, cplx *Q);              // P = G^T, Q = I - P
+int k_itcf_weights(afq_handle *h, int restore, cplx *wfac, cplx *denom);
+int k_itcf_accumulate(afq_handle *h, const cplx *Ggr, const cplx *Gls, const cplx *wfac, cplx *spgf_tau);
 // k_bigdet.hip
 int k_greens_big_supported(afq_handle *h);
 struct WeightArgs;
 int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv = nullptr, const WeightArgs *wa = nullptr);   // ghalf may be null
                                 // (overlap only); wa: the step's weight update rides on the determinant kernel
 int k_reortho_big(afq_handle *h);                           // Cholesky-QR2; sets qr_fail for breakdowns
+int k_gj_inverse(afq_handle *h, cplx *O, int n, int batch, cplx *detm, int *dete);   // in place, n <= 128
 // k_small.hip
 int k_alive(afq_handle *h);
 int k_greens(afq_handle *h, cplx *det_out);                 // ghalf + det

@@ -795,6 +795,18 @@ __global__ void det_combine_kernel(const cplx *detm, const int *dete, cplx *det,
     if (wa.weight) weight_update_and_cap(wa, w);
 }
 
+// In-place inverses of batch n x n matrices O [batch, n, n] (n <= GJ_N) by the step-by-step kernel; detm / dete [batch]
+// receive the determinants
+int k_gj_inverse(afq_handle *h, cplx *O, int n, int batch, cplx *detm, int *dete) {
+    if (n > GJ_N) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "Gauss-Jordan inverse: n > 128");
+    GjArgs a;
+    a.na = a.nb = a.ld = n; a.write_inverse = 1;
+    a.O = O; a.detm = detm; a.dete = dete;
+    AFQ_LAUNCH(h, gj_big_kernel, dim3(batch), dim3(512), 0, h->stream, a);
+    AFQ_POST(h);
+    return AFQ_OK;
+}
+
 // N > 45, or a smaller determinant whose walker does not fit the one-work-group kernel of k_small.hip (M > 128, or walker +
 // overlap matrices above 160 KB of LDS: e.g. 45 + 45 electrons on 100 sites)
 int k_greens_big_supported(afq_handle *h) {

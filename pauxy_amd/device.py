@@ -223,6 +223,22 @@ class AfqDevice(object):
             extra['fock_1p'], extra['fock_1h'] = fock[0], fock[1]
         return out[:3], out[3], out[4:].reshape(2, M, M), extra
 
+    # ---- imaginary-time Green's function
+    def itcf_configure(self, nmax, neqlb=0, stable=True, restore_weights=False):
+        """afq_itcf_configure: windows of nmax + neqlb steps on the field history (sized here when none is set)."""
+        self._ck(self.lib.afq_itcf_configure(self.h, int(nmax), int(neqlb), int(bool(stable)), int(bool(restore_weights))))
+        self.nbp = int(nmax) + int(neqlb)
+        self.itcf_nmax = int(nmax)
+
+    def itcf_update(self, psi_T, nstblz):
+        """One window -> (spgf_sum [nmax+1, 2, 2, M, M], denominator): sum_w wfac_w Re G_w(tau) and sum_w wfac_w."""
+        psi = _c128(psi_T, (self.M, self.na + self.nb))
+        M = self.M
+        spgf = numpy.zeros((self.itcf_nmax + 1, 2, 2, M, M), dtype=numpy.complex128)
+        den = numpy.zeros(1, dtype=numpy.complex128)
+        self._ck(self.lib.afq_itcf_update(self.h, _p(psi), int(nstblz), _p(spgf), _p(den)))
+        return spgf, den[0]
+
     def set_trial_multi(self, psi, coeffs, rchol):
         """psi [ndet, M, na+nb], coeffs [ndet], rchol [ndet * (na+nb) M, K] (stacked per determinant)."""
         nt = self.na + self.nb

@@ -1,6 +1,7 @@
 """Container the driver calls (pauxy/estimators/handler.py:56-162): owns the
-``mixed`` estimator (and, when requested, ``back_prop``) and forwards ``update`` /
-``print_step``.  The ITCF estimator is not on the device path.
+``mixed`` estimator (and, when requested, ``back_prop`` or ``itcf``) and forwards ``update`` /
+``print_step``.  ``discrete``: the run propagates with discrete Hubbard fields (the ITCF needs them on a Hubbard
+model), None when unknown; ``free_projection``: the run projects freely (the ITCF refuses it).
 
 Output file (handler.py:60-71,117-124): ``<basename>.<index>.h5`` (or ``filename``),
 created empty by the root rank, ``metadata`` = JSON description of the run; as in
@@ -11,6 +12,7 @@ variable only changes the default: a run that names its file still gets it)."""
 import os
 
 from pauxy_amd.estimators.back_propagation import BackPropagation
+from pauxy_amd.estimators.itcf import ITCF
 from pauxy_amd.estimators.mixed import Mixed
 from pauxy_amd.utils import io as _io
 
@@ -26,7 +28,8 @@ def _touch(filename):
 
 
 class Estimators(object):
-    def __init__(self, estimates, root, qmc, system, trial, BT2, verbose=False):
+    def __init__(self, estimates, root, qmc, system, trial, BT2, verbose=False, discrete=None,
+                 free_projection=False):
         opts = estimates
         self.index = opts.get('index', 0)
         self.basename = opts.get('basename', 'estimates')                    # handler.py:62
@@ -47,9 +50,11 @@ class Estimators(object):
         self.estimators = {}
         mixed_opts = dict(opts.get('mixed', {}), flush_every=opts.get('mixed', {}).get('flush_every', self.flush_every))
         self.estimators['mixed'] = Mixed(mixed_opts, system, root, name, qmc, trial, complex)
-        if opts.get('itcf') is not None:
-            raise NotImplementedError("itcf estimator is not on the device path yet")
         bp_opts = opts.get('back_propagation', opts.get('back_propagated'))              # handler.py:83-85
+        self.calc_itcf = opts.get('itcf') is not None
+        if self.calc_itcf and bp_opts is not None:
+            # one field history per walker: the two estimators would close their windows on the same record
+            raise NotImplementedError("itcf together with back_propagation")
         self.back_propagation = bp_opts is not None
         self.nprop_tot = self.nbp = None
         if self.back_propagation:
@@ -57,7 +62,12 @@ class Estimators(object):
             est = BackPropagation(bp_opts, root, name, qmc, system, trial, complex, BT2)
             self.estimators['back_prop'] = est
             self.nprop_tot = self.nbp = est.nmax                                         # handler.py:91-92
-        self.calc_itcf = False
+        if self.calc_itcf:                                                               # handler.py:101-107
+            itcf_opts = dict(opts['itcf'], flush_every=opts['itcf'].get('flush_every', self.flush_every))
+            est = ITCF(itcf_opts, qmc, trial, root, name, system, complex, BT2, discrete=discrete,
+                       free_projection=free_projection)
+            self.estimators['itcf'] = est
+            self.nprop_tot = est.nprop_tot
         self.json_string = ''
 
     def dump_metadata(self):

@@ -44,7 +44,9 @@ class AFQMC(object):
         self.propagators = get_propagator_driver(system, trial, self.qmc, options=prop_opt, verbose=verbose)
         est_opts = options.get('estimators', options.get('estimates', options.get('estimator', {})))
         self.estimators = Estimators(est_opts, self.comm.rank == 0, self.qmc, system, trial,
-                                     self.propagators.BT_BP, verbose)
+                                     self.propagators.BT_BP, verbose,
+                                     discrete=getattr(self.propagators, 'hs_type', '') == 'discrete',
+                                     free_projection=bool(getattr(self.propagators, 'free_projection', False)))
         self.qmc.nwalkers = max(1, int(self.qmc.nwalkers / self.comm.size))       # afqmc.py:167-176
         self.qmc.ntot_walkers = self.qmc.nwalkers * self.comm.size
         self.psi = Walkers(system, trial, self.qmc, walker_opts=options.get('walkers', {}), comm=self.comm,

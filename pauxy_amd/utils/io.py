@@ -367,6 +367,11 @@ def extract_bp_estimates(filename, skip=0):
     return {k: v[skip:] for k, v in extract_data(filename, 'back_propagated', 'energies').items()}
 
 
+def extract_itcf(filename):
+    """The ITCF of every window, [nwindows, nmax + 1, 2, 2, ...] (spin, greater / lesser, then what ``mode`` wrote)."""
+    return extract_data(filename, 'single_particle_greens_function', 'real_space', raw=True)
+
+
 def extract_rdm(filename, est_type='back_propagated', rdm_type='one_rdm', ix=None):
     """Back-propagated density matrices divided by their denominators (analysis/extraction.py:36-62)."""
     if ix is None:

@@ -204,7 +204,9 @@ class Walkers(object):
         self.shift_counter = 1
         self.log_shift = self.detR_shift = self.log_detR_shift = 0.0
         if nbp is not None and nprop_tot is not None and nprop_tot != nbp:
-            raise NotImplementedError("ITCF field history (nprop_tot != nbp) is not on the device path")
+            raise NotImplementedError("one field history per walker: nprop_tot != nbp")
+        if nbp is None and nprop_tot is not None:
+            nbp = nprop_tot                       # the ITCF's window (handler.py:104-107): the same device history
         self.walker_type = 'SD' if getattr(trial, 'ndets', 1) == 1 else 'MSD'     # walkers/handler.py:53-68
         if (self.walker_type == 'SD' and getattr(trial, 'name', '') == 'MultiSlater'
                 and numpy.asarray(trial.psi).ndim == 3):
