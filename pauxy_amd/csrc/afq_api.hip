@@ -256,10 +256,6 @@ int afq_create(int device_id, afq_handle **out) {
     *h->retired = 0;
     h->debug_sync = getenv("AFQ_DEBUG_SYNC") != nullptr && atoi(getenv("AFQ_DEBUG_SYNC")) != 0;
     h->debug_markers = getenv("AFQ_DEBUG_MARKERS") != nullptr && atoi(getenv("AFQ_DEBUG_MARKERS")) != 0;
-    h->no_ring = AFQ_KNOB_SET("AFQ_NO_RING");
-    h->no_fused = AFQ_KNOB_SET("AFQ_NO_FUSED");
-    h->no_vhs_upper = AFQ_KNOB_SET("AFQ_VHS_MIRROR");
-    h->greens_cache = !AFQ_KNOB_SET("AFQ_NO_GREENS_CACHE");
     *out = h;
     return AFQ_OK;
 }
@@ -354,7 +350,7 @@ int afq_set_system_generic(afq_handle *h, int M, int K, int na, int nb, const do
     {   // hs_pot^T : [K, ld_hs] so that a VHS B-fragment is contiguous (even, zero-padded rows: the
         // LDS-DMA path moves 16-byte pairs of doubles).  Cholesky matrices of real orbitals are
         // symmetric in (p, q); then only the columns p <= q are kept and the VHS GEMM does half the work.
-        bool sym = !AFQ_KNOB_SET("AFQ_VHS_FULL");
+        bool sym = true;
         for (int p = 0; p < M && sym; ++p)
             for (int q = p + 1; q < M && sym; ++q) {
                 const double *a = hs_pot + ((size_t)p * M + q) * K, *b = hs_pot + ((size_t)q * M + p) * K;
@@ -689,7 +685,6 @@ int afq_walkers_alloc(afq_handle *h, int nw) {
         // both spins share the Cholesky block: the contraction runs once over Ghalf_a + Ghalf_b (k_force_bias_generic),
         // half as long -- measured at C3: 4 slices (8 partials for fields_kernel to add) beat 8 by 1 % of the step
         if (h->rchol_same && h->rchol_real && h->ndet == 1 && h->na == h->nb && nw > 32 && sp > 1) sp = (sp + 1) / 2;
-        sp = AFQ_KNOB_INT("AFQ_FB_SPLIT", sp);
         const int nmax = std::max(h->na, h->nb) * h->M;
         while (sp > 1 && nmax / sp < 64) --sp;
         h->fb_split = sp;
@@ -961,7 +956,7 @@ int afq_propagate_begin(afq_handle *h, const double *xi) {
     if (h->hirsch) AFQ_FAIL(h, AFQ_ESTATE, "discrete Hirsch propagator set: use afq_propagate_hirsch");
     // Hubbard, continuous fields, one field per site: fields_kernel makes the fields (and draws them), the diagonal HS
     // potential and its Taylor factors.  ONE flag decides the inline draw, the branch below and who writes the factors.
-    const bool hubbard_fused = h->vhs_diag && !h->no_fused;
+    const bool hubbard_fused = h->vhs_diag;
     const bool hubbard_fused_fields = hubbard_fused && h->K == h->M;
     if (xi) {
         if ((rc = k_alive(h))) return rc;
@@ -1044,7 +1039,7 @@ int afq_propagate_begin(afq_handle *h, const double *xi) {
     // B exp(V) B.  Checked on the walkers themselves at every step (closed_flags_kernel); the GEMMs then leave out the tiles of
     // the beta columns of such walkers and the alpha block is copied over the beta block behind the closing one-body product.
     h->closed_large = !fused && h->kind == AFQ_SYS_GENERIC && h->nv == 1 && h->bh1_same && h->na == h->nb && h->na > 0 &&
-                      h->M > 128 && h->nt > 32 && h->nw >= 64 && !h->no_ring && !AFQ_KNOB_SET("AFQ_NO_CLOSED_LARGE");
+                      h->M > 128 && h->nt > 32 && h->nw >= 64;
     struct ClosedLargeOff { afq_handle *h; ~ClosedLargeOff() { h->closed_large = false; } } closed_large_off{h};   // on every way out
     if (h->closed_large && (rc = k_closed_flags(h))) return rc;
     if (!fused) { PhaseTimer t(h, T_ONEBODY); if ((rc = k_onebody(h))) return rc; }   // :251
@@ -1055,7 +1050,7 @@ int afq_propagate_begin(afq_handle *h, const double *xi) {
     }
     // symmetric L_n and the fused propagator as the only consumer: the HS potential is stored as its upper
     // triangle only (no scattered mirror writes) and the propagator fetches V[k][row] for k < row
-    h->vhs_upper = fused && h->hs_sym && !h->no_vhs_upper;
+    h->vhs_upper = fused && h->hs_sym;
     { PhaseTimer t(h, T_VHS); rc = build_vhs(h); }                                  // :161
     if (rc) { h->vhs_upper = false; return rc; }
     if (fused) {
@@ -1100,7 +1095,7 @@ int afq_propagate_finish(afq_handle *h, double eshift_re, double eshift_im) {
             const bool fb_diag = h->kind == AFQ_SYS_HUBBARD && !h->hirsch && h->psicT && k_greens_big_supported(h);
             h->ghalf_skip_store = h->fuse_est_req && h->ndet == 1 && (fb_sum || fb_diag) &&
                                   (h->flags & AFQ_PROP_HYBRID) && (h->flags & AFQ_PROP_FORCE_BIAS) && !h->rdm_on &&
-                                  h->nbp == 0 && h->psi_stride == 0 && !AFQ_KNOB_SET("AFQ_NO_GHALF_SKIP");
+                                  h->nbp == 0 && h->psi_stride == 0;
             h->ghalf_skipped = false;
             rc = greens_any(h, h->ovlp_new, true);
             h->fuse_weight_req = false;
@@ -1946,7 +1941,7 @@ static int bp_backward(afq_handle *h, int nstblz, cplx *keep, int nkeep) {
             rc = k_bp_hirsch_step(h, i);
         } else {
             if ((rc = k_bp_fields(h, i))) break;
-            h->vhs_upper = fused && h->hs_sym && !h->no_vhs_upper;
+            h->vhs_upper = fused && h->hs_sym;
             rc = build_vhs(h);
             if (!rc && fused) rc = k_prop_fused(h);
             h->vhs_upper = false;

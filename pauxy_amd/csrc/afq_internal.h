@@ -295,10 +295,7 @@ struct afq_handle {
     // Ghalf / ovlp_new describe the CURRENT phi of every walker (set by the end-of-step Green's
     // function of afq_propagate, cleared by everything that writes phi, psi or Ghalf)
     bool greens_valid = false;
-    bool greens_cache = true;       // AFQ_NO_GREENS_CACHE=1 or a handed-out device pointer turns it off
-    bool no_fused = false;          // AFQ_NO_FUSED=1: separate one-body / Taylor launches (A/B runs)
-    bool no_vhs_upper = false;      // AFQ_VHS_MIRROR=1: always store both triangles of the HS potential (A/B runs)
-    bool no_ring = false;           // AFQ_NO_RING=1: register-prefetch GEMM engine only (A/B runs)
+    bool greens_cache = true;       // a handed-out device pointer turns it off
 
     // afq_propagate -> k_greens: run the step's weight update behind the determinant (greens_small_kernel)
     bool fuse_weight_req = false, fuse_weight_done = false;
@@ -341,20 +338,6 @@ struct afq_handle {
             return AFQ_EHIP;                                                    \
         }                                                                       \
     } while (0)
-
-// tuning / A-B switches read from the environment exist only in builds made with -DAFQ_TUNING
-// (make TUNING=1); the product library has none of them
-// AFQ_KNOB_SET("X"): is switch X set?  AFQ_KNOB_INT("X", d): its integer value, d when unset.  In the product build both
-// are constants (false / d), no environment is read, and every kernel variant a switch selects sits inside an
-// `#ifdef AFQ_TUNING` region, so the product library does not even contain it.
-#ifdef AFQ_TUNING
-inline const char *afq_knob(const char *name) { return getenv(name); }
-#define AFQ_KNOB_SET(name) (afq_knob(name) != nullptr)
-#define AFQ_KNOB_INT(name, dflt) (afq_knob(name) ? atoi(afq_knob(name)) : (dflt))
-#else
-#define AFQ_KNOB_SET(name) false
-#define AFQ_KNOB_INT(name, dflt) (dflt)
-#endif
 
 // every kernel launch goes through AFQ_LAUNCH / AFQ_GEMM + AFQ_POST: the name of the kernel is left in the
 // handle's breadcrumb ring before the launch, and AFQ_POST checks the launch (and, in the debug modes,

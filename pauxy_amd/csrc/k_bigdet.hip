@@ -159,11 +159,10 @@ struct GjArgs {
     int *dete;                       // [2 nw] binary exponent
     const int *only = nullptr;       // when set: only the matrices with a non-zero entry are processed
     unsigned long long *nflagged = nullptr;   // ... and counted here (afq_counters [2])
-    unsigned long long *ts = nullptr;   // tuning builds (AFQ_GJ_TS): s_memtime stamps of work-group 0, [wave][block step][point]
-    int dbg = 0;                     // tuning builds: timing ablations of gj_mfma_kernel (WRONG results): 1 no inversion of the
-                                     // pivot tile, 2 no rank-16 update of the register tiles, 4 none of the diagonal tiles,
-                                     // 8 no block steps at all (loads only); 64 flags every matrix (right results: everything
-                                     // through the step-by-step kernel)
+    // always 0 (nothing sets it): the timing ablations of gj_mfma_kernel it once selected (1 no inversion of the pivot tile,
+    // 2 no rank-16 update, 4 no diagonal tiles, 8 no block steps, 64 flag every matrix).  Its run-time tests stay in the
+    // kernel because they steer the register allocation: without them gj_mfma_kernel spills 334 VGPRs to scratch.
+    int dbg = 0;
 };
 
 // wave-wide maximum of a 32-bit key by DPP row shifts / row broadcasts (no LDS traffic)
@@ -460,18 +459,6 @@ __global__ __launch_bounds__(512) void gj_mfma_kernel(GjArgs a, int *flag) {
         }
         return gj_wave_max_u32(key);
     };
-#ifdef AFQ_TUNING
-    auto stamp = [&](int kb, int pt) {
-        if (a.ts && b == 0) {
-            unsigned long long t;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t));
-            if (lane == 0) a.ts[(wave * 8 + kb) * 8 + pt] = t;
-        }
-    };
-#define GJ_STAMP(kb, pt) stamp(kb, pt)
-#else
-#define GJ_STAMP(kb, pt)
-#endif
     // B-fragments of block column J in step kb: the scaled block row, or P^-1 itself (its home) for the pivot's own column
     // (the update then turns O[i, k] into -O[i, k] P^-1)
     auto bpanel = [&](int J, int kb) { return J == kb ? Dg + kb * 256 : Rp + J * 256; };
@@ -485,7 +472,6 @@ __global__ __launch_bounds__(512) void gj_mfma_kernel(GjArgs a, int *flag) {
         auto invert = [&](const int t, const int nb) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (!(a.dbg & 1)) gj_wave16q_inv(Pl, nb, lane, rowk, piv_all + 16 * t, prow_all + 16 * t);
-            GJ_STAMP(t ? t - 1 : 0, t ? 4 : 7);
             d2_t *pa = Pa + (t & 1) * 256;
             double m = 0.0;
             bool isnan = false;
@@ -610,11 +596,8 @@ __global__ __launch_bounds__(512) void gj_mfma_kernel(GjArgs a, int *flag) {
         for (int kb = 0; kb < nsteps; ++kb) {
             const int nblk = n - 16 * kb < 16 ? n - 16 * kb : 16;
             const int nks = (nblk + 3) >> 2;
-            GJ_STAMP(kb, 0);
             if (kb == nt16 - 1) judge();                               // (every pivot tile is inverted, every guard slot written)
-            GJ_STAMP(kb, 1);
             gj_lds_barrier();                                          // B1
-            GJ_STAMP(kb, 2);
             // the next pivot tile up to date, inverted, published -- while the other waves update everything else
             const int nx = kb + 1;
             if (nx < nt16) {
@@ -626,7 +609,6 @@ __global__ __launch_bounds__(512) void gj_mfma_kernel(GjArgs a, int *flag) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (4 * r + lk < nbx && lr < nbx) Pl[(4 * r + lk) * nbx + lr] = cmake(accr[r], acci[r]);
-                GJ_STAMP(kb, 3);
                 invert(nx, nbx);
             } else {                                                   // last step: this pivot's inverse is final
                 if (a.write_inverse && !*s_bad) {
@@ -639,9 +621,7 @@ __global__ __launch_bounds__(512) void gj_mfma_kernel(GjArgs a, int *flag) {
                 }
                 determinant();
             }
-            GJ_STAMP(kb, 5);
             gj_lds_barrier();                                          // B4
-            GJ_STAMP(kb, 6);
         }
         return;
     }
@@ -700,7 +680,6 @@ __global__ __launch_bounds__(512) void gj_mfma_kernel(GjArgs a, int *flag) {
         const int nblk = n - 16 * kb < 16 ? n - 16 * kb : 16;
         const int nks = (nblk + 3) >> 2;                               // k-steps of 4 that hold anything
         const int Jk = (kb + wave) & 7;                                // this wave's tile of the block row is (kb, Jk)
-        GJ_STAMP(kb, 0);
         // ---- row scaling R' = P^-1 R of this wave's tile of the block row, straight from its registers (the accumulator
         //      layout IS the B-fragment order: register ks = k-step ks) -> Rp and back into the registers
         if (Jk < nt16) {
@@ -733,9 +712,7 @@ __global__ __launch_bounds__(512) void gj_mfma_kernel(GjArgs a, int *flag) {
                 }
             }
         }
-        GJ_STAMP(kb, 1);
         gj_lds_barrier();                                              // B1
-        GJ_STAMP(kb, 2);
         const bool st = kb == nt16 - 1 && a.write_inverse && !*s_bad; // last step: every tile is final after its update
         // ---- rank-16 update of every tile outside the block row: C <- (J == kb ? 0 : C) + (-F) R'
 #pragma unroll
@@ -754,7 +731,6 @@ __global__ __launch_bounds__(512) void gj_mfma_kernel(GjArgs a, int *flag) {
                 }
             } else if (i == kb && J < nt16 && st) store_tile(i, J, Cr[i], Ci[i]);   // (the scaled block row)
         }
-        GJ_STAMP(kb, 3);
         // ... and the diagonal tiles that are neither this pivot nor the next one (that is wave 0's): one each for waves
         // 1, 2, 3, 5, 6, 7 -- not wave 4, the pivot wave's neighbour on its SIMD: the register Gauss-Jordan runs 17 k cycles
         // beside 12 k cycles of fp64 MFMAs and 21.5 k beside 23 k (all six tiles on wave 4), 12.5 k alone
@@ -777,9 +753,7 @@ __global__ __launch_bounds__(512) void gj_mfma_kernel(GjArgs a, int *flag) {
                 for (int r = 0; r < 4; ++r) Dg[(i * 4 + r) * 64 + lane] = (d2_t){accr[r], acci[r]};
             }
         }
-        GJ_STAMP(kb, 5);
         gj_lds_barrier();                                              // B4: panels free for the next block step
-        GJ_STAMP(kb, 6);
     }
 }
 
@@ -813,7 +787,7 @@ int k_greens_big_supported(afq_handle *h) {
     const int nmax = h->na > h->nb ? h->na : h->nb;
     const size_t lds_small = sizeof(cplx) * (2 * ((size_t)nmax * nmax + 2 * nmax) + ((2 * nmax + 3) / 4 + 1) + (size_t)h->M * h->nt);
     const bool small_fits = nmax <= 45 && h->M <= 128 && lds_small <= 160 * 1024;
-    return !small_fits && nmax > 16 && nmax <= GJ_N && h->nb > 0 && !h->no_ring;
+    return !small_fits && nmax > 16 && nmax <= GJ_N && h->nb > 0;
 }
 
 int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const WeightArgs *wa_in) {
@@ -829,13 +803,6 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Weight
         p.batch = nb2; p.rows = nmax; p.cols = nmax; p.kdim = h->M;
         p.nt = h->nt; p.na = h->na; p.nb = h->nb; p.ld = nmax;
         p.phi = h->phi; p.psic = h->psic; p.psi_stride = h->psi_stride; p.O = h->big_ws; p.zero = (const cplx *)h->zero_page;
-#ifdef AFQ_TUNING
-        if (AFQ_KNOB_SET("AFQ_OVLP_CFG")) AFQ_GEMM_AS(h, "k_greens_big: OvlpProb GEMM", (launch_mfma_gemm_wg<4, 2, 1, 4, 4, decltype(p), MAP_COLS_FAST, true, 1, 2>(p, h->stream, h->zero_page)));
-        else if (AFQ_KNOB_SET("AFQ_BIG_LEAN")) AFQ_GEMM_AS(h, "k_greens_big: OvlpProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, decltype(p), MAP_COLS_FAST, true, 1, 5, 4>(p, h->stream, h->zero_page)));
-        else if (AFQ_KNOB_SET("AFQ_BIG_WPE")) AFQ_GEMM_AS(h, "k_greens_big: OvlpProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, decltype(p), MAP_COLS_FAST, true, 1, 3, 4>(p, h->stream, h->zero_page)));
-        else if (AFQ_KNOB_SET("AFQ_BIG_NOLOADER")) AFQ_GEMM_AS(h, "k_greens_big: OvlpProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, decltype(p), MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
-        else
-#endif
         AFQ_GEMM_AS(h, "k_greens_big: OvlpProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, decltype(p), MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
         return AFQ_OK;
     };
@@ -848,40 +815,14 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Weight
         a.na = h->na; a.nb = h->nb; a.ld = nmax; a.write_inverse = ghalf != nullptr || oinv != nullptr;
         a.O = h->big_ws; a.detm = h->detm; a.dete = h->dete;
         // blocked Gauss-Jordan on the matrix pipe for more than one block of 32; the step-by-step kernel for matrices it flags
-        // as poorly conditioned block-wise (none in any test or benchmark so far) and for tuning builds that ask for it
-        const bool blocked = nmax > 32 && !AFQ_KNOB_SET("AFQ_GJ_STEPWISE");     // (up to 32: one leaf would do all the work)
+        // as poorly conditioned block-wise (none in any benchmark so far; tests drive it with ill-conditioned matrices)
+        const bool blocked = nmax > 32;     // (up to 32: one leaf would do all the work)
         if (blocked) {
             static size_t lds_set[AFQ_MAX_DEVICES] = {0};
             AFQ_HIP(h, afq_raise_lds((const void *)gj_mfma_kernel, GjMfmaLds::BYTES, lds_set));
             if (!h->gj_flag) AFQ_HIP(h, hipMalloc(&h->gj_flag, sizeof(int) * nb2));
-            a.dbg = AFQ_KNOB_INT("AFQ_GJ_DBG", 0);
-#ifdef AFQ_TUNING
-            static unsigned long long *ts_dev = nullptr;
-            static int ts_launch = 0;
-            if (AFQ_KNOB_SET("AFQ_GJ_TS")) {
-                if (!ts_dev) { hipMalloc(&ts_dev, 512 * 8); hipMemset(ts_dev, 0, 512 * 8); }
-                a.ts = ts_dev;
-            }
-#endif
             AFQ_LAUNCH(h, gj_mfma_kernel, dim3(nb2), dim3(512), GjMfmaLds::BYTES, h->stream, a, h->gj_flag);
             AFQ_POST(h);
-#ifdef AFQ_TUNING
-            if (a.ts && ++ts_launch == 30) {
-                unsigned long long t[512];
-                hipStreamSynchronize(h->stream);
-                hipMemcpy(t, a.ts, sizeof(t), hipMemcpyDeviceToHost);
-                const unsigned long long t0 = t[0];
-                for (int kb = 0; kb < 8; ++kb)
-                    for (int wv = 0; wv < 8; ++wv) {
-                        const unsigned long long *o = t + (wv * 8 + kb) * 8;
-                        fprintf(stderr, "GJ_TS step %d wave %d: start %+7lld | to B1 %5lld | in B1 %5lld | %s %5lld | %s %5lld | %s %5lld | in B4 %5lld\n", kb, wv,
-                                (long long)(o[0] - t0), (long long)(o[1] - o[0]), (long long)(o[2] - o[1]),
-                                wv ? "tiles" : "upd next", (long long)(o[3] - o[2]),
-                                wv ? "-" : "leaf", wv ? 0ll : (long long)(o[4] - o[3]),
-                                wv ? "diag share" : "conv", (long long)(o[5] - (wv ? o[3] : o[4])), (long long)(o[6] - o[5]));
-                    }
-            }
-#endif
             a.only = h->gj_flag;                                      // (work-groups of unflagged matrices return at once)
             a.nflagged = h->counters ? h->counters + 2 : nullptr;
             afq_note_launch(h, "gj_big_kernel (fallback pass)");      // (its own name in launch traces: priced by the matrices it processes)
@@ -907,13 +848,6 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Weight
             p.psicT = h->psicT; p.gdiag = h->gdiag; p.nparts = h->gdiag_parts;
             p.skip_store = 0;
             if (decltype(p)::COLDOT && h->ghalf_skip_store) { p.skip_store = 1; h->ghalf_skipped = true; }
-#ifdef AFQ_TUNING
-            if (AFQ_KNOB_SET("AFQ_GHALF_CFG")) AFQ_GEMM_AS(h, "k_greens_big: GhalfProb GEMM", (launch_mfma_gemm_wg<4, 2, 1, 4, 4, decltype(p), MAP_COLS_FAST, true, 1, 2>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_BIG_LEAN")) AFQ_GEMM_AS(h, "k_greens_big: GhalfProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, decltype(p), MAP_COLS_FAST, true, 1, 5, 4>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_BIG_WPE")) AFQ_GEMM_AS(h, "k_greens_big: GhalfProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, decltype(p), MAP_COLS_FAST, true, 1, 3, 4>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_BIG_NOLOADER")) AFQ_GEMM_AS(h, "k_greens_big: GhalfProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, decltype(p), MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
-            else
-#endif
             AFQ_GEMM_AS(h, "k_greens_big: GhalfProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, decltype(p), MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
             return AFQ_OK;
         };
@@ -925,7 +859,7 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Weight
             // the last writer used
             const int parts16 = (nmax + 15) / 16;
             if (!h->gdiag) AFQ_HIP(h, hipMalloc(&h->gdiag, sizeof(cplx) * (size_t)nb2 * parts16 * h->M));
-            if (h->ghalf_skip_store && h->psi_real && !AFQ_KNOB_SET("AFQ_NO_GDIAG_REAL")) {
+            if (h->ghalf_skip_store && h->psi_real) {
                 // only diag G is wanted and the trial is real: W = conj(psi) O^-1 (real by complex), rowdot with phi
                 GdiagProbT p;
                 p.batch = nb2; p.rows = h->M; p.cols = nmax; p.kdim = nmax;
@@ -934,26 +868,11 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Weight
                 p.zero = (const cplx *)h->zero_page;
                 h->gdiag_parts = parts16;
                 h->ghalf_skipped = true;
-#ifdef AFQ_TUNING
-                const int gc = AFQ_KNOB_INT("AFQ_GDIAG_CFG", 0);
-                if (gc == 1) AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 4, 4, GdiagProbT, MAP_COLS_FAST, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (gc == 2) AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<4, 2, 2, 4, 4, GdiagProbT, MAP_COLS_FAST, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (gc == 3) AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GdiagProbT, MAP_COLS_FAST, false, 1, 2>(p, h->stream, h->zero_page)));
-                else if (gc == 4) AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 4, 4, GdiagProbT, MAP_COLS_FAST, false, 1, 2>(p, h->stream, h->zero_page)));
-                else if (gc == 5) AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<4, 2, 2, 4, 2, GdiagProbT, MAP_COLS_FAST, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (gc == 6) AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<4, 2, 1, 4, 4, GdiagProbT, MAP_COLS_FAST, false, 1, 2>(p, h->stream, h->zero_page)));
-                else if (gc == 8) AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GdiagProbT, MAP_BATCH_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (gc == 9) AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GdiagProbT, MAP_BATCH_XCD_ROWS, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (gc == 10) AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 2, GdiagProbT, MAP_COLS_FAST, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (gc == 11) AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 8, GdiagProbT, MAP_COLS_FAST, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (gc == 7) AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<4, 2, 2, 4, 4, GdiagProbT, MAP_COLS_FAST, false, 1, 2>(p, h->stream, h->zero_page)));
-                else
-#endif
                 AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GdiagProbT, MAP_COLS_FAST, false, 1, 3>(p, h->stream, h->zero_page)));
                 h->gdiag_version = h->ghalf_version;
                 return AFQ_OK;
             }
-            h->gdiag_parts = AFQ_KNOB_SET("AFQ_GHALF_CFG") ? parts16 : (nmax + 31) / 32;
+            h->gdiag_parts = (nmax + 31) / 32;
             const int rc = run(GhalfProbT<true>());
             if (rc) return rc;
             h->gdiag_version = h->ghalf_version;
@@ -1051,106 +970,6 @@ struct CholArgs {
 // after step k the slots (i > k, k) hold -m_i = column k of the unit-lower inverse factor, so at the
 // end v[i][j] (j < i) = Ltilde^-1[i][j] with S = Ltilde D Ltilde^H, and
 //     T = R^-1 = Ltilde^-H D^-1/2,   Tt[i][j] = T[j][i] = conj(v[i][j]) / sqrt(D_i).
-#ifdef AFQ_TUNING      // (tuning builds only: AFQ_CHOL_STEPWISE; the product runs chol_mfma_kernel)
-__global__ __launch_bounds__(512) void chol_linv_kernel(CholArgs a) {
-    __shared__ cplx colk[2][GJ_N], rowk[2][GJ_N];
-    __shared__ double piv[GJ_N];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = (b & 1) ? a.nb : a.na;
-    const cplx *S = a.S + (long)b * a.ld * a.ld;
-    cplx *Tt = a.Tt + (long)b * a.ld * a.ld;
-    const int tr = tid >> 5, tc = tid & 31;
-    double vr[8][4], vi[8][4];
-#pragma unroll
-    for (int x = 0; x < 8; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) {
-            const int i = tr + 16 * x, j = tc + 32 * y;
-            const cplx t = (i < n && j < n) ? S[(long)i * a.ld + j] : cmake(0.0, 0.0);
-            vr[x][y] = t.x; vi[x][y] = t.y;
-        }
-    if (tid < GJ_N) piv[tid] = 1.0;
-    bool bad = false;
-#pragma unroll
-    for (int y0 = 0; y0 < 4; ++y0) {
-        for (int kk = 0; kk < 32; ++kk) {
-            const int k = 32 * y0 + kk;
-            if (k >= n) break;
-            const int buf = k & 1;
-            if (tc == kk) {
-#pragma unroll
-                for (int x = 0; x < 8; ++x) colk[buf][tr + 16 * x] = cmake(vr[x][y0], vi[x][y0]);
-            }
-            if (wave == ((k & 15) >> 1)) {
-                const int x0 = k >> 4;
-                const bool mine = tr == (k & 15);
-#pragma unroll
-                for (int x = 0; x < 8; ++x) {
-                    if (x0 == x) {
-                        if (mine) {
-#pragma unroll
-                            for (int y = 0; y < 4; ++y) {
-                                const int j = tc + 32 * y;
-                                rowk[buf][j] = (j == k) ? cmake(1.0, 0.0) : cmake(vr[x][y], vi[x][y]);
-                            }
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            const double d = colk[buf][k].x;
-            bad = bad || !(d > 0.0);
-            const double dinv = 1.0 / d;
-            if (tid == 0) piv[k] = d;
-            double rkx[4], rky[4];
-#pragma unroll
-            for (int y = 0; y < 4; ++y) { const cplx t = rowk[buf][tc + 32 * y]; rkx[y] = t.x; rky[y] = t.y; }
-            if (tc == kk) {
-#pragma unroll
-                for (int x = 0; x < 8; ++x) { vr[x][y0] = 0.0; vi[x][y0] = 0.0; }
-            }
-#pragma unroll
-            for (int x = 0; x < 8; ++x) {
-                const int i = tr + 16 * x;
-                const cplx c = colk[buf][i];
-                const double fx = i > k ? c.x * dinv : 0.0, fy = i > k ? c.y * dinv : 0.0;
-#pragma unroll
-                for (int y = 0; y < 4; ++y) {
-                    double ox = vr[x][y], oy = vi[x][y];
-                    ox = fma(-fx, rkx[y], ox); ox = fma(fy, rky[y], ox);
-                    oy = fma(-fx, rky[y], oy); oy = fma(-fy, rkx[y], oy);
-                    vr[x][y] = ox; vi[x][y] = oy;
-                }
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int x = 0; x < 8; ++x) {
-        const int i = tr + 16 * x;
-        if (i >= n) continue;
-        const double rs = 1.0 / sqrt(piv[i]);
-#pragma unroll
-        for (int y = 0; y < 4; ++y) {
-            const int j = tc + 32 * y;
-            if (j >= n) continue;
-            cplx t = cmake(0.0, 0.0);
-            if (j < i) t = cmake(vr[x][y] * rs, -vi[x][y] * rs);
-            else if (j == i) t = cmake(rs, 0.0);
-            Tt[(long)i * a.ld + j] = t;
-        }
-    }
-    if (wave == 0) {
-        double l = log(piv[lane]) + log(piv[lane + 64]);
-        for (int o = 32; o > 0; o >>= 1) l += __shfl_down(l, o);
-        if (lane == 0) {
-            a.logd[b] = 0.5 * l;
-            if (bad) a.fail[b >> 1] = 1;
-        }
-    }
-}
-#endif
 
 // Blocked version of chol_linv_kernel on the matrix pipe (round 4; the structure of gj_mfma_kernel: eight waves per matrix,
 // 16 x 16 tiles in MFMA accumulator layout, wave w > 0 owns the tiles (I, (I + w) mod 8), the pivot wave 0 keeps the
@@ -1420,13 +1239,6 @@ int k_reortho_big(afq_handle *h) {
             p.batch = nb2; p.rows = nmax; p.cols = nmax; p.kdim = h->M;
             p.nt = h->nt; p.na = h->na; p.nb = h->nb; p.ld = nmax;
             p.x = src; p.S = h->big_ws; p.zero = (const cplx *)h->zero_page;
-#ifdef AFQ_TUNING
-            if (AFQ_KNOB_SET("AFQ_BIG_LEAN")) AFQ_GEMM_AS(h, "k_reortho_big: GramProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GramProb, MAP_COLS_FAST, true, 1, 5, 4>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_BIG_WPE")) AFQ_GEMM_AS(h, "k_reortho_big: GramProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GramProb, MAP_COLS_FAST, true, 1, 3, 4>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_BIG_NOLOADER")) AFQ_GEMM_AS(h, "k_reortho_big: GramProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GramProb, MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_BIG_NOLEAN")) AFQ_GEMM_AS(h, "k_reortho_big: GramProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GramProb, MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
-            else
-#endif
             // round 5: the lean loop at two work-groups per CU (mfma_gemm_wg.h, STAG = 5): 238 -> 218 us at C4.  (The overlap
             // and Ghalf GEMMs of the Green's function measured 2-3 % SLOWER that way and keep the pipelined loop.)
             AFQ_GEMM_AS(h, "k_reortho_big: GramProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GramProb, MAP_COLS_FAST, true, 1, 5, 4>(p, h->stream, h->zero_page)));
@@ -1436,9 +1248,6 @@ int k_reortho_big(afq_handle *h) {
             a.na = h->na; a.nb = h->nb; a.ld = nmax;
             a.S = h->big_ws; a.Tt = h->big_ws2; a.logd = h->qr_logd + (size_t)pass * nb2; a.fail = h->qr_fail;
             if (nmax <= 32) AFQ_LAUNCH(h, chol_small_kernel, dim3((nb2 + 3) / 4), dim3(256), 0, h->stream, a, nb2);
-#ifdef AFQ_TUNING
-            else if (AFQ_KNOB_SET("AFQ_CHOL_STEPWISE")) AFQ_LAUNCH(h, chol_linv_kernel, dim3(nb2), dim3(512), 0, h->stream, a);
-#endif
             else {
                 static size_t lds_set[AFQ_MAX_DEVICES] = {0};
                 AFQ_HIP(h, afq_raise_lds((const void *)chol_mfma_kernel, CholMfmaLds::BYTES, lds_set));
@@ -1451,13 +1260,6 @@ int k_reortho_big(afq_handle *h) {
             p.batch = nb2; p.rows = h->M; p.cols = nmax; p.kdim = nmax;
             p.nt = h->nt; p.na = h->na; p.nb = h->nb; p.ld = nmax;
             p.x = src; p.Tt = h->big_ws2; p.out = dst; p.fail = h->qr_fail; p.zero = (const cplx *)h->zero_page;
-#ifdef AFQ_TUNING
-            if (AFQ_KNOB_SET("AFQ_BIG_LEAN")) AFQ_GEMM_AS(h, "k_reortho_big: QProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, QProb, MAP_COLS_FAST, true, 1, 5, 4>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_BIG_WPE")) AFQ_GEMM_AS(h, "k_reortho_big: QProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, QProb, MAP_COLS_FAST, true, 1, 3, 4>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_BIG_NOLOADER")) AFQ_GEMM_AS(h, "k_reortho_big: QProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, QProb, MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_BIG_NOLEAN")) AFQ_GEMM_AS(h, "k_reortho_big: QProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, QProb, MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
-            else
-#endif
             AFQ_GEMM_AS(h, "k_reortho_big: QProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, QProb, MAP_COLS_FAST, true, 1, 5, 4>(p, h->stream, h->zero_page)));   // 253 -> 230 us
         }
     }

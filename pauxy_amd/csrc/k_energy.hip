@@ -580,7 +580,6 @@ static int launch_exx_quadratic(afq_handle *h, int *S_out, bool *two_pass) {
     if (S < 1) S = 1;
     if (S > EXQ_MAX_BATCH / 2) S = EXQ_MAX_BATCH / 2;
     while (S > 1 && nmax / S < 64) --S;
-    S = AFQ_KNOB_INT("AFQ_EXQ_SPLIT", S);
     // Closed-shell population (every walker's Ghalf_b == Ghalf_a, verified on the device by the Green's function launch this
     // Ghalf comes from: closed_checked_version) and one Atil for both spins: the 2 S slices of the FIRST launch all belong to
     // spin alpha (every XCD busy), the second launch holds spin beta's and returns at once on the device when the flag says
@@ -588,7 +587,7 @@ static int launch_exx_quadratic(afq_handle *h, int *S_out, bool *two_pass) {
     // (the small Green's function kernel checks the spin blocks only beside the spin sum of real half-rotated vectors,
     //  k_fb_use_sum: complex ones -- a complex trial, or complex Cholesky vectors -- are checked here, as the large systems are)
     if (h->closed_bad && h->closed_checked_version != h->ghalf_version && (k_greens_big_supported(h) || !h->rchol_real) &&
-        h->ndet == 1 && h->na == h->nb && h->atil[0] == h->atil[1] && !h->exx_open_hint && !AFQ_KNOB_SET("AFQ_NO_CLOSED_EXX")) {
+        h->ndet == 1 && h->na == h->nb && h->atil[0] == h->atil[1] && !h->exx_open_hint) {
         // (an open-shell population is found out by the first evaluation's published verdict, exx_open_hint: no check, and
         //  the two-spin launch, from then on)
         AFQ_LAUNCH(h, ghalf_closed_check_kernel, dim3(h->nw), dim3(256), 0, h->stream, h->ghalf, nma, h->closed_bad, ++h->closed_epoch);
@@ -596,11 +595,10 @@ static int launch_exx_quadratic(afq_handle *h, int *S_out, bool *two_pass) {
         h->closed_checked_version = h->ghalf_version;
     }
     const bool closed_try = h->closed_bad && h->closed_checked_version == h->ghalf_version && h->closed_checked_version != 0 &&
-                            h->ndet == 1 && h->na == h->nb && h->atil[0] == h->atil[1] && !h->exx_open_hint && !AFQ_KNOB_SET("AFQ_NO_CLOSED_EXX");
+                            h->ndet == 1 && h->na == h->nb && h->atil[0] == h->atil[1] && !h->exx_open_hint;
     // (slices of the one-spin launch: 2 S, as many work-groups as the two-spin launch has.  C3, us per evaluation: S = 4
     //  slices 106.6, 5 100.9, 6 96.9, 7 91.4, 8 = 2 S 96.9, 10 139.8, 16 107.3; the two-spin launch 138.9)
     int SL = closed_try ? 2 * S : S;
-    if (closed_try) SL = AFQ_KNOB_INT("AFQ_EXQ_CLOSED_SL", SL);
     if (SL > EXQ_MAX_BATCH) SL = EXQ_MAX_BATCH;
     const int NB = closed_try ? SL : 2 * S;                      // batches of one launch
     ExxQProb<RC> p;
@@ -611,7 +609,7 @@ static int launch_exx_quadratic(afq_handle *h, int *S_out, bool *two_pass) {
     // the alpha slices in every XCD's queue -- work-groups that return at once instead of a launch that returns at once
     // (5.0 us per evaluation in the kernel trace); otherwise (C5 sizes: 2 slices) the beta launch keeps the alpha launch's
     // spread over the XCDs
-    const bool merged = closed_try && NB % 8 == 0 && 2 * NB <= EXQ_MAX_BATCH && !AFQ_KNOB_SET("AFQ_EXQ_TWO_LAUNCHES");
+    const bool merged = closed_try && NB % 8 == 0 && 2 * NB <= EXQ_MAX_BATCH;
     const int npass = closed_try && !merged ? 2 : 1;
     const int nbat = merged ? 2 * NB : NB;
     p.batch = nbat;
@@ -671,28 +669,7 @@ static int launch_exx_quadratic(afq_handle *h, int *S_out, bool *two_pass) {
         // round 5: a complex Atil (3-multiplication products, 144 VGPRs) on the lean loop at two work-groups per CU
         // (k_apply_exponential in k_gemm.hip): 9.95 -> 9.74 ms per determinant at C5; the real one (99 VGPRs) is two per CU anyway
         // (short contractions -- several slices: C3 sizes -- on eight waves with a 1 x 2 tile block each, the ring depths, the
-        //  pipelined loops and the two-work-groups-per-CU variants measured against these are in tuning builds: AFQ_EXQ_CFG)
-#ifdef AFQ_TUNING
-        const int cfg = AFQ_KNOB_INT("AFQ_EXQ_CFG", 1);
-        if (cfg == 16) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC, 1, 3>(p, h->stream, h->zero_page)));
-        else if (cfg == 9) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC>(p, h->stream, h->zero_page)));
-        else if (cfg == 4) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC, 1, 2>(p, h->stream, h->zero_page)));
-        else if (cfg == 5) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 4, 1, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC>(p, h->stream, h->zero_page)));
-        else if (cfg == 6) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 4, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC>(p, h->stream, h->zero_page)));
-        else if (cfg == 7) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC, 1, 3>(p, h->stream, h->zero_page)));
-        else if (cfg == 8) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC, 1, 3>(p, h->stream, h->zero_page)));
-        else if (cfg == 12) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC, 1, 3>(p, h->stream, h->zero_page)));
-        else if (cfg == 13) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC, 1, 2>(p, h->stream, h->zero_page)));
-        else if (cfg == 14) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC, 1, 2>(p, h->stream, h->zero_page)));
-        else if (cfg == 15) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC, 1, 5, 4>(p, h->stream, h->zero_page)));
-        else if (cfg == 10) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC, 1, 3, 4>(p, h->stream, h->zero_page)));
-        else if (cfg == 11) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC, 1, 2, 4>(p, h->stream, h->zero_page)));
-        else if (cfg == 2) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 4, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC>(p, h->stream, h->zero_page)));
-        else if (cfg == 3) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD, RC>(p, h->stream, h->zero_page)));
-        else if (AFQ_KNOB_SET("AFQ_EXQ_PIPE")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC, 1, 2>(p, h->stream, h->zero_page)));
-        else if (cfg != 1) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, ExxQProb<RC>, MAP_BATCH_XCD_ROWS, RC>(p, h->stream, h->zero_page)));
-        else
-#endif
+        //  pipelined loops and the two-work-groups-per-CU variants were measured against these)
         if (pass == 1) {
             ExxQBetaProb<RC> pb;
             static_cast<ExxQProb<RC> &>(pb) = p;

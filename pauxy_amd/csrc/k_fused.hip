@@ -42,36 +42,14 @@
 #endif
 #define PF_FPW (16 / PF_LW)      // operand fragments each refilling wave moves per chunk
 
-// Tuning builds (make TUNING=1 -> libafqmc_hip_tuning.so) carry timing ablations (a.dbg bits: WRONG results, timing only)
-// and s_memtime probes.  They all sit behind this one macro family, which expands to NOTHING in the product build, so the
-// kernel below reads straight through and its barrier / vmcnt invariants can be audited without mentally compiling
-// anything out:
-//   PF_UNLESS(bits) stmt;   the statement is skipped when an ablation bit is set
-//   PF_TUNE(code)           code that exists in tuning builds only
-//   PF_STAGE(i), PF_BND(n, i)   s_memtime stamps of the phases / product boundaries
-#ifdef AFQ_TUNING
-#define PF_UNLESS(bits) if (!(a.dbg & (bits)))
-#define PF_TUNE(...) __VA_ARGS__
-#define PF_STAGE(i) stage_stamp(i)
-#define PF_BND(n, i) bnd_stamp(n, i)
-#else
-#define PF_UNLESS(bits)
-#define PF_TUNE(...)
-#define PF_STAGE(i)
-#define PF_BND(n, i)
-#endif
-
 struct PropFusedArgs {
     int M, na, nb, nt, order;
-    int t4;                     // Taylor products on v_mfma_f64_4x4x4 (see taylor4 below)
-    int dbg;                    // tuning builds: bit 0 = no per-chunk barrier (WRONG results; timing ceiling only)
-    unsigned long long *ts;     // tuning builds (AFQ_PF_TS=1): s_memtime stamps of work-group 0, waves 0 and 4
     int vhs_upper;              // vhs holds only the upper triangle of the (symmetric) HS potential
     int same_b;                 // BH1[0] == BH1[1]: one one-body pass serves both spins
     int b_real;                 // BH1 is real: one-body products take 2 real multiplications instead of 3
     int rem4;                   // M <= 100 in the full 7-row-tile deal: rows 96.. as one 4x4x4 unit (see taylor)
-    int hyb;                    // > 0: a column slot with at most 4 * hyb <= 12 live columns is multiplied as hyb units of
-                                // 16 rows x 4 columns on v_mfma_f64_4x4x4 (see taylor_h)
+    int hyb;                    // with contig: the fourth column slot's at most 4 * hyb <= 8 live columns are multiplied as
+                                // hyb units of 16 rows x 4 columns on v_mfma_f64_4x4x4 (see taylor_h)
     int symcols;                // contig with na == nb (round 5): T holds the walker's columns in the order [a 0..15 | b 0..15 |
                                 // a 16..23, b 16..23 | a 24.., b 24..] so that a column and its twin of the other spin always go
                                 // through the same code and MFMA shape (slots 0, 1: taylor; slot 2: taylor_h's tile; slot 3:
@@ -161,22 +139,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
     cplx *phi = a.phi + (long)w * M * nt;
     const cplx *vhs = a.vhs + (long)w * M * M;
 
-    // (tuning: coarse stage stamps (AFQ_PF_TS=1), work-group 0, wave 0 -> a.ts[128 + i]; product build: nothing)
-    PF_TUNE(auto stage_stamp = [&](int i) {
-        if (a.ts && w == 0 && wave == 0) {
-            unsigned long long t;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t));
-            if (lane == 0) a.ts[128 + i] = t;
-        }
-    };
-    auto bnd_stamp = [&](int n, int i) {
-        if (a.ts && w == 0 && (wave & 3) == 0 && (n == 3 || n == 4)) {
-            unsigned long long t;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t));
-            if (lane == 0) a.ts[144 + (wave >> 2) * 8 + (n == 4 ? 4 : 0) + i] = t;
-        }
-    };)
-    PF_STAGE(0);
     // ---- A stream: global chunk g = phase * NCH + c; phases: B0 B1 V..V B0 B1, or B V..V B when both spins
     // share one propagator matrix (BH1[0] == BH1[1]: every closed-shell-type Hamiltonian) -- the one-body
     // products of the two spins then run as ONE pass over the matrix with four column tiles per wave
@@ -198,7 +160,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
     const int p_kl = 2 * lk + (lw & 1);                          // sub-step f&1 (the same for every t: PF_LW is even)
     auto prepare = [&]() __attribute__((always_inline)) {
         if (!refills) { prepared = true; return; }
-        PF_TUNE(if ((a.dbg & 1024) && gi > 2) { prepared = true; return; })       // stale addresses (timing only)
         const bool in_v = gi_phase >= nob && gi_phase < nob + a.order;
         const int spin = gi_phase < nob ? gi_phase : gi_phase - nob - a.order;      // 0 or 1 on live chunks
         const cplx *A = in_v ? vhs : a.BH1 + (spin == 1 ? MM : 0L);
@@ -228,7 +189,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
         if (!refills) return;
         if (!prepared) prepare();
         unsigned char *dst = ring + (size_t)gi_slot * 16384;
-        PF_TUNE(if (a.dbg & 512) { for (int t = 0; t < PF_FPW; ++t) asm volatile("" ::"v"(nsrc[t]), "s"(dst)); } else)   // addresses computed, DMA not issued
 #pragma unroll
         for (int t = 0; t < PF_FPW; ++t) glds16(nsrc[t], dst + (lw + t * PF_LW) * 1024);
         if (++gi_slot == PF_D) gi_slot = 0;
@@ -255,7 +215,7 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
         if (closed && tid == 0) atomicAdd(a.n_closed, 1ULL);
     }
     // Layout of T for THIS walker: the contiguous-column layout (a.contig) serves open-shell walkers; a closed-shell one takes
-    // the two-slots-per-spin layout [a0 a1 b0 b1], whose alpha half is three tiles per SIMD.  (Measured, C3, tuning build:
+    // the two-slots-per-spin layout [a0 a1 b0 b1], whose alpha half is three tiles per SIMD.  (Measured, C3:
     // 126.7 us; keeping the contiguous layout and leaving out its one wholly redundant slot [b 0..15] 145.3; neither 162.3.)
     const bool relayout = closed && a.contig;
     const int contig = relayout ? 0 : a.contig, hyb = relayout ? 0 : a.hyb;
@@ -278,7 +238,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
     // ((chunk * 4 + slot) * 2 + (p & 1)) * 64 + ((p & 7) >> 1) * 16 + column in the slot, i.e. shifts and masks only), each
     // either a walker element or a zero -- instead of a zero fill, a barrier and a sweep over the walker with a division
     // by the column count per element
-    PF_UNLESS((32 | 128))
     for (int e = tid; e < NCH * 512; e += PF_NT) {
         const int j = e & 15, kk = (e >> 4) & 3, pb = (e >> 6) & 1, slot = (e >> 7) & 3, ch = e >> 9;
         const int p = ch * 8 + 2 * kk + pb, sp = contig ? 0 : slot >> 1, col = (contig ? slot : slot & 1) * 16 + j;
@@ -301,15 +260,11 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
         return base + (unsigned)(((2 * ti * 4 + cs) * 2) * 1024) + (unsigned)((r >> 1) * 8192 + (r & 1) * 512);
     };
 
-    PF_STAGE(1);
     int ring_slot = 0;                                           // slot of the chunk being consumed
     // one k-chunk of a product: wait own DMA, barrier, refill the ring, hand back the slot base
     auto next_chunk = [&]() __attribute__((always_inline)) -> unsigned {
-        PF_UNLESS(18)
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((PF_D - 2) * PF_FPW) : "memory");
-        PF_UNLESS(1)
         __builtin_amdgcn_s_barrier();
-        PF_UNLESS(2)
         issueA();
         const unsigned sl = ring_l + ring_slot * 16384;
         if (++ring_slot == PF_D) ring_slot = 0;
@@ -352,7 +307,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
         };
         auto mfmas = [&](d2_t (&av)[2], d2_t (&bv)[NSL][2]) {
             __builtin_amdgcn_sched_barrier(0);
-            PF_UNLESS(64)
 #pragma unroll
             for (int ss = 0; ss < 2; ++ss)
 #pragma unroll
@@ -468,7 +422,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
                     const double im = BR ? P2[j][r] : P3[j][r] - P1[j][r] - P2[j][r];
                     if (to_global) {
                         const int row = rt * 16 + lk_e + 4 * r, col = (contig ? cs : cs & 1) * 16 + lr_e;
-                        PF_UNLESS(256)
                         if (row < M && col < ns_) phi[(long)row * nt + off_ + wcol(col)] = cmake(re, im);
                     } else if (t_ok(rt, r)) {
                         *(d2_t *)(Tf + t_addr(rt, r, cs)) = (d2_t){re, im};
@@ -602,7 +555,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
 #if PF_NW == 8
         if constexpr (FULL == 7) {
             bool col_deal = a.rem4 && a.same_b;
-            PF_TUNE(if (a.dbg & (to_global ? 16384 : 8192)) col_deal = false;)
             if (col_deal) {
                 if (a.b_real) {
                     if (wave < 4) one_body_col(to_global, std::true_type{}, std::false_type{});
@@ -656,7 +608,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
     //  measured, same chunk time)
     one_body_stage(false);
     lds_barrier();                                               // T = B phi complete
-    PF_STAGE(2);
 
     // ------------------------------------------------------------------ Taylor series
     // Tile deal: the 7 x 4 grid of 16x16 output tiles (M <= 104 rows, two column tiles per spin) is split so that
@@ -707,7 +658,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
         // (second register set) while the MFMAs of chunk c run, so the LDS pipe and the MFMA pipe overlap instead
         // of alternating in lock step behind the per-chunk barrier.
         auto load_frags = [&](unsigned sl, int c, d2_t (&av)[NI][2], d2_t (&bv)[NJ][2]) {
-            PF_TUNE(if (a.dbg & 4) return;)
             const unsigned abase = sl + r0 * 2048 + lane * 16;
             const unsigned bbase = tf_l + (c * 4 + c0) * 2048 + lane * 16;
 #pragma unroll
@@ -730,7 +680,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
                 }
             double Q1 = 0.0, Q2 = 0.0, Q3 = 0.0;                   // remainder unit (REM)
             auto mfma_ss = [&](d2_t (&av)[NI][2], d2_t (&bv)[NJ][2], const int ss) __attribute__((always_inline)) {
-                PF_TUNE(if (a.dbg & 8) return;)
 #pragma unroll
                 for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -779,10 +728,7 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
                         }
                         const int g = REM ? (gt == 0 ? 0 : gt - 1) : gt;
                         const int i = g / NJ, j = g % NJ;
-                        if (!(REM && gt == 0))
-                        // (tuning: timing ablation with the MFMA load a hybrid 16x16x4 / 4x4x4 tiling would leave at most)
-                        PF_TUNE(if (!((a.dbg & 4096) && ((NI == 2 && NJ == 2 && g == 3) || (NI == 3 && i == 2)))))
-                        {
+                        if (!(REM && gt == 0)) {
                         P1[i][j] = mfma16(ax[i][0], bx[j][0], P1[i][j]);
                         P2[i][j] = mfma16(ax[i][1], bx[j][1], P2[i][j]);
                         P3[i][j] = mfma16(ax[i][0] + ax[i][1], bx[j][0] + bx[j][1], P3[i][j]);
@@ -807,7 +753,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
                 };
                 // first chunk of the product: the fragment reads go out first, the ring refill issues under their latency
                 unsigned sl = next_chunk_sync();
-                if (n == 4) PF_BND(4, 0);
                 {
                     const unsigned abase = sl + r0 * 2048 + lane * 16, bbase = tf_l + c0 * 2048 + lane * 16;
 #pragma unroll
@@ -819,27 +764,13 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
                     issueA();
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 }
-                if (n == 4) PF_BND(4, 1);
                 for (int c = 0; c < NCH; ++c) {
                     const bool more = c + 1 < NCH;
-                    // (tuning: s_memtime lands in SGPRs; the values are read behind the lgkmcnt(0) wait that closes a half)
-                    PF_TUNE(unsigned long long t0, t1, t2, t3; asm volatile("s_memtime %0" : "=s"(t0));)
                     // sub-step 0 of chunk c; fetch its sub-step 1 fragments
                     half(a0, b0, q0, a1, b1, q1, sl + r0 * 2048 + lane * 16, tf_l + (c * 4 + c0) * 2048 + lane * 16, sl + rem_a, 1, true, false);
-                    PF_TUNE(asm volatile("s_memtime %0" : "=s"(t1));)
                     if (more) sl = next_chunk_sync();             // chunk c + 1 has landed
-                    PF_TUNE(asm volatile("s_memtime %0" : "=s"(t2));)
                     // sub-step 1 of chunk c; refill the ring, fetch the sub-step 0 fragments of chunk c + 1
                     half(a1, b1, q1, a0, b0, q0, sl + r0 * 2048 + lane * 16, tf_l + ((c + 1) * 4 + c0) * 2048 + lane * 16, sl + rem_a, 0, more, more);
-                    PF_TUNE(asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t3));
-                            if (a.ts && w == 0 && n == 3 && (wave & 3) == 0 && lane == 0) {
-                                unsigned long long *o = a.ts + ((wave >> 2) * 16 + c) * 4;
-                                o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
-                            }
-                            if (a.ts && w == 0 && n == 3 && lane == 0) {
-                                unsigned long long *o = a.ts + 256 + (wave * 16 + c) * 4;
-                                o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
-                            })
                 }
             } else
 #endif
@@ -894,7 +825,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
             }
 #endif
             }
-            if (n == 3) PF_BND(3, 0);
             // Everyone has to be through with T_{n-1} before it is overwritten -- but behind the last chunk barrier of the
             // half-chunk pipeline only the LAST chunk of T is still being read.  A wave whose tiles end below that chunk
             // (every wave of the full M <= 100 deal: the last chunk belongs to the remainder unit) stores first and takes the
@@ -902,7 +832,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
             // while its SIMD partner still multiplies, instead of behind it.
             const bool store_first = PF_NW == 8 && FULL != 0 && 2 * (r0 + NI) <= NCH - 1;
             if (!store_first) __builtin_amdgcn_s_barrier();
-            if (n == 3) PF_BND(3, 1);
             // T_n = product / n goes back to T as the next right-hand operand; after the last term T receives the SUM instead
             // (wave-uniform branch: two straight-line store sequences rather than a select per element)
             const bool last = n == a.order;
@@ -937,12 +866,9 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
                 RR += re; RI += im;
                 *(d2_t *)(Tf + rem_t) = last ? (d2_t){RR, RI} : (d2_t){re, im};
             }
-            if (n == 3) PF_BND(3, 2);
             // T_n visible: the barrier is the one the first chunk of the next product (or of the closing one-body pass)
             // starts with -- only the wave's own LDS writes have to be done before it gets there
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (n == 3) PF_BND(3, 3);
-            PF_STAGE(2 + n);
         }
     };
 
@@ -951,12 +877,8 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
     // 16x16x4 MFMA on it costs 64 cycles whatever it holds; the same rows as NU = ceil((n - 16) / 4) units of 16 rows x 4
     // columns on v_mfma_f64_4x4x4 (blk = 4-row group: the A operand IS the ring fragment of the row tile, lane 16 k + row;
     // the B operand repeats T[k][4 u + j] in every blk; D lane 16 i + 4 blk + j = element (row 4 blk + i, column 4 u + j))
-    // cost 16 NU <= 48.  Deal of the full M <= 100 shape (per k-step, in MFMA cycles, three products per tile / unit):
-    //   waves 0-3   row tiles (0,1) or (2,3) x [full slot | unit slot] of one spin     2 x (192 + 48 NU)
-    //   waves 4, 5  row tiles 4, 5 of the full slot of a spin (the plain taylor() deal)  384
-    //   waves 6, 7  row tiles 4, 5 of the unit slot of a spin + the two remainder units
-    //               (rows 96 .. M-1, see REM in taylor) of BOTH slots of that spin       96 NU + 96
-    // NU = 3: every SIMD (waves w, w + 4) carries 1056 instead of 1200 cycles per k-step.  Same half-chunk pipeline, same
+    // cost 16 NU <= 48.  The contiguous-column deal below multiplies its fourth slot this way; units in the second slot of
+    // each spin of the two-slots-per-spin layout were measured NEGATIVE (see k_prop_fused).  Same half-chunk pipeline, same
     // barriers per chunk and per product as taylor(); the short groups go first so that the long ones cover the reads.
     auto taylor_h = [&](auto hf_tag, auto rem_tag, auto nu_tag, const int r0, const int cf, const int cu, const int cr)
         __attribute__((always_inline)) {
@@ -1077,17 +999,9 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             for (int c = 0; c < NCH; ++c) {
                 const bool more = c + 1 < NCH;
-                PF_TUNE(unsigned long long t0, t1, t2, t3; asm volatile("s_memtime %0" : "=s"(t0));)
                 half(f0, f1, sl, c, 1, true, false);             // sub-step 0 of chunk c; fetch its sub-step 1
-                PF_TUNE(asm volatile("s_memtime %0" : "=s"(t1));)
                 if (more) sl = next_chunk_sync();                 // chunk c + 1 has landed
-                PF_TUNE(asm volatile("s_memtime %0" : "=s"(t2));)
                 half(f1, f0, sl, c + 1, 0, more, more);          // sub-step 1 of chunk c; refill, fetch sub-step 0 of chunk c + 1
-                PF_TUNE(asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t3));
-                        if (a.ts && w == 0 && n == 3 && lane == 0) {
-                            unsigned long long *o = a.ts + 256 + (wave * 16 + c) * 4;
-                            o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
-                        })
             }
             // T_n = product / n back into T (rows below the last chunk: nobody reads them any more behind the last chunk
             // barrier), the barrier, then the remainder rows -- exactly the sequence of taylor() with store_first
@@ -1127,10 +1041,7 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
     // not faster -- 183 us against 177 us: MFMA-busy cycles drop 18 %, wave-parked cycles (s_waitcnt / barrier) rise
     // from 23 % to 35 % of the wave cycles, 1.6 x the instructions, and the broadcast read of a 4-column group of T
     // is a 2-way bank conflict in the spin-padded fragment layout.  The kernel is bound by the per-chunk
-    // synchronisation skeleton, not by MFMA issue.  The variant is compiled only into tuning builds (AFQ_T4=1).
-#ifdef AFQ_TUNING
-#include "k_fused_t4.inc"      // taylor4(): the same products on v_mfma_f64_4x4x4 (tuning builds only)
-#endif
+    // synchronisation skeleton, not by MFMA issue.
     // closed-shell walker in the two-slots-per-spin layout: T(b0, b1) = T(a0, a1) behind the Taylor stage, for the closing
     // one-body pass (which multiplies every slot)
     auto mirror_spin = [&]() __attribute__((always_inline)) {
@@ -1151,7 +1062,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
         else taylor(I2{}, I1{}, std::false_type{}, 2 * g, wave & 3, 2, std::false_type{});
     }
 #else
-    PF_TUNE(if (a.t4) taylor4(); else)
     if (NARROW && FULL) {
         // six row tiles, one column tile per spin: waves 0-3 a pair of the row tiles 0-3, waves 4-7 one of the tiles 4, 5
         using I1 = std::integral_constant<int, 1>;
@@ -1201,21 +1111,6 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
             else deal(I1{});
         }
     }
-    else if (FULL == 7 && hyb) {
-        if constexpr (FULL == 7) {
-            using I1 = std::integral_constant<int, 1>;
-            using I2 = std::integral_constant<int, 2>;
-            using I3 = std::integral_constant<int, 3>;
-            auto deal = [&](auto nu) __attribute__((always_inline)) {
-                if (wave < 4) taylor_h(std::true_type{}, std::false_type{}, nu, 2 * (wave >> 1), 2 * (wave & 1), 2 * (wave & 1) + 1, 0);
-                else if (wave < 6) taylor(I2{}, I1{}, std::true_type{}, 4, 2 * (wave - 4), 2, std::false_type{});
-                else taylor_h(std::false_type{}, std::true_type{}, nu, 4, 0, 2 * (wave - 6) + 1, 2 * (wave - 6));
-            };
-            if (hyb == 3) deal(I3{});
-            else if (hyb == 2) deal(I2{});
-            else deal(I1{});
-        }
-    }
     else if (FULL >= 5 && closed) {
         // Closed-shell walker, two slots per spin: the alpha half only -- waves 0-3 two row tiles of one slot each (rows (0,1) /
         // (2,3) x slot a0 / a1), waves 4-7 one row tile each (row 4 and, where it exists, row 5 x a0 / a1; with seven full row
@@ -1251,49 +1146,32 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
 
     one_body_stage(true);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    PF_STAGE(9);
 }
 
 int k_prop_fused_supported(afq_handle *h) {
-    return !h->no_fused && !h->vhs_diag && h->nv == 1 && h->M <= 104 && h->na <= 32 && h->nb <= 32 && (h->nb > 0 || AFQ_KNOB_SET("AFQ_PF_NB0"));
+    return !h->vhs_diag && h->nv == 1 && h->M <= 104 && h->na <= 32 && h->nb <= 32 && h->nb > 0;
 }
 
 int k_prop_fused(afq_handle *h) {
     PropFusedArgs a;
     a.M = h->M; a.na = h->na; a.nb = h->nb; a.nt = h->nt; a.order = h->exp_order;
     a.vhs_upper = h->vhs_upper ? 1 : 0;
-    // 4x4x4 Taylor products (tuning builds only): M <= 100 (six full row tiles + at most four remainder rows)
-    a.t4 = (h->M <= 100 && AFQ_KNOB_SET("AFQ_T4")) ? 1 : 0;
-    a.dbg = AFQ_KNOB_INT("AFQ_PF_DBG", 0);
-    a.ts = nullptr;
-#ifdef AFQ_TUNING
-    static unsigned long long *ts_dev = nullptr;
-    static int ts_launch = 0;
-    if (AFQ_KNOB_SET("AFQ_PF_TS")) {
-        if (!ts_dev) { hipMalloc(&ts_dev, (256 + 512) * 8); hipMemset(ts_dev, 0, (256 + 512) * 8); }
-        a.ts = ts_dev;
-    }
-#endif
-    a.same_b = (h->bh1_same && !AFQ_KNOB_SET("AFQ_NO_SAME_B")) ? 1 : 0;
-    a.b_real = (h->bh1_real && !AFQ_KNOB_SET("AFQ_NO_REAL_B")) ? 1 : 0;
-    a.rem4 = (h->M > 96 && h->M <= 100 && !AFQ_KNOB_SET("AFQ_PF_NOREM")) ? 1 : 0;
-    // hybrid column tiling: both spins with 17 .. 28 electrons and the same number of 4-column units in their second slot
-    // (measured NEGATIVE at C3, round 4: 148.6 us against 145.5 us -- three 4x4x4 units need 9 MFMA + 3 add instructions where
-    //  the padded 16x16x4 tile needs 3 + 1, and a wave that multiplies mostly units is bound by instruction issue, not by the
-    //  matrix pipe; tuning builds only, AFQ_PF_HYB=1)
+    a.same_b = h->bh1_same ? 1 : 0;
+    a.b_real = h->bh1_real ? 1 : 0;
+    a.rem4 = (h->M > 96 && h->M <= 100) ? 1 : 0;
+    // (hybrid column tiling of the two-slots-per-spin layout -- both spins with 17 .. 28 electrons, their second slots as
+    //  4-column units -- measured NEGATIVE at C3, round 4: 148.6 us against 145.5 us -- three 4x4x4 units need 9 MFMA + 3 add
+    //  instructions where the padded 16x16x4 tile needs 3 + 1, and a wave that multiplies mostly units is bound by
+    //  instruction issue, not by the matrix pipe)
     a.hyb = 0;
-    if (a.rem4 && h->na > 16 && h->nb > 16 && h->na <= 28 && h->nb <= 28 && (h->na - 13) / 4 == (h->nb - 13) / 4 &&
-        PF_NW == 8 && AFQ_KNOB_SET("AFQ_PF_HYB"))
-        a.hyb = (h->na - 13) / 4;
     // contiguous columns: one one-body matrix for both spins (the HS potential never depends on the spin), 48 < na + nb <= 56
     // (a third unit per row tile would unbalance the deal and push wave 7 over 256 registers)
     a.contig = 0; a.symcols = 0;
-    if (a.rem4 && a.same_b && h->na > 16 && h->nb > 16 && h->nt > 48 && h->nt <= 56 && PF_NW == 8 && !a.hyb &&
-        !AFQ_KNOB_SET("AFQ_PF_NOCONTIG")) {
+    if (a.rem4 && a.same_b && h->na > 16 && h->nb > 16 && h->nt > 48 && h->nt <= 56 && PF_NW == 8) {
         a.contig = 1;
         a.hyb = (h->nt - 48 + 3) / 4;
     }
-    a.symcols = (a.contig && h->na == h->nb && !AFQ_KNOB_SET("AFQ_PF_NOSYM")) ? 1 : 0;
+    a.symcols = (a.contig && h->na == h->nb) ? 1 : 0;
     a.closed_try = 0;           // (set below, once the deal is known)
     a.BH1 = h->BH1; a.vhs = h->vhs; a.phi = h->phi; a.alive = h->alive; a.zero16 = h->zero_page;
     a.n_closed = h->counters + 3;
@@ -1307,9 +1185,8 @@ int k_prop_fused(afq_handle *h) {
         const int nrt_ = (h->M + 15) / 16, ct = (h->na + 15) / 16 + (h->nb + 15) / 16;
         const double ksteps = 2.0 * NCH;
         const double per_pass = ksteps * (2048.0 * (a.rem4 ? nrt_ - 1 : nrt_) * ct + 512.0 * (a.rem4 ? ct : 0));
-        // hybrid tiling of the Taylor products: per spin one full slot + hyb units per row tile, four remainder units in all
-        const double taylor_pass = a.contig ? ksteps * (2048.0 * (nrt_ - 1) * 3 + 512.0 * (nrt_ - 1) * a.hyb + 512.0 * 4)
-                                   : a.hyb ? ksteps * (2048.0 * (nrt_ - 1) * 2 + 512.0 * (nrt_ - 1) * 2 * a.hyb + 512.0 * 4) : per_pass;
+        // contiguous columns: three full slots + hyb units per row tile in the Taylor products, four remainder units in all
+        const double taylor_pass = a.contig ? ksteps * (2048.0 * (nrt_ - 1) * 3 + 512.0 * (nrt_ - 1) * a.hyb + 512.0 * 4) : per_pass;
         h->issued_flops[AFQ_K_PROPAGATOR] = (3.0 * h->exp_order * taylor_pass + 2.0 * (a.b_real ? 2.0 : 3.0) * per_pass) * h->nw;
         h->prop_issued_open = h->issued_flops[AFQ_K_PROPAGATOR] / h->nw;
         // a closed-shell walker (afq_counters [3]) issues the alpha slots only in its Taylor products: two column slots x the
@@ -1322,12 +1199,12 @@ int k_prop_fused(afq_handle *h) {
     // every tile of the deal present: wide with 5-7 row tiles (waves 4-7 own the tiles from 4 on) and two column tiles
     // per spin, or narrow with six row tiles
     const int nrt = (h->M + 15) / 16;
-    const bool nofull = PF_NW != 8 || AFQ_KNOB_SET("AFQ_PF_NOFULL");
+    const bool nofull = PF_NW != 8;
     const int full = nofull ? 0 : narrow ? (nrt == 6 ? 6 : 0) : (nrt >= 5 && h->na > 16 && h->nb > 16 ? nrt : 0);
     // closed-shell deals: one matrix for both spins (the chain then acts on the spin blocks alike), as many electrons of
     // either spin, and a deal without holes: the contiguous-column deal with twins in like slots (symcols), or two slots per spin
-    a.closed_try = (a.same_b && h->na == h->nb && h->exp_order > 0 && full != 0 && PF_NW == 8 && !a.t4 &&
-                    (a.contig ? a.symcols != 0 : a.hyb == 0) && !AFQ_KNOB_SET("AFQ_PF_NOCLOSED")) ? 1 : 0;
+    a.closed_try = (a.same_b && h->na == h->nb && h->exp_order > 0 && full != 0 && PF_NW == 8 &&
+                    (!a.contig || a.symcols)) ? 1 : 0;
 #define PF_LAUNCH_(NARROW_, FULL_, SLOT_)                                                                     \
     do {                                                                                                      \
         AFQ_HIP(h, afq_raise_lds((const void *)prop_fused_kernel<NARROW_, FULL_>, lds, lds_set[SLOT_]));      \
@@ -1341,34 +1218,5 @@ int k_prop_fused(afq_handle *h) {
     else PF_LAUNCH_(false, 0, 5);
 #undef PF_LAUNCH_
     AFQ_POST(h);
-#ifdef AFQ_TUNING
-    if (a.ts && ++ts_launch == 30) {
-        unsigned long long t[256 + 512];
-        hipStreamSynchronize(h->stream);
-        hipMemcpy(t, a.ts, sizeof(t), hipMemcpyDeviceToHost);
-        fprintf(stderr, "PF_STAGE ticks: phi->T %lld | one-body %lld | Taylor", (long long)(t[129] - t[128]), (long long)(t[130] - t[129]));
-        for (int n = 1; n <= h->exp_order && n <= 6; ++n) fprintf(stderr, " %lld", (long long)(t[130 + n] - t[129 + n]));
-        for (int wv = 0; wv < 2; ++wv) {
-            const unsigned long long *o = t + 144 + wv * 8;
-            fprintf(stderr, "\nPF_BND wave %d: loop end -> barrier %lld | epilogue + T writes %lld | barrier %lld | next_chunk %lld | fragment reads %lld",
-                    wv * 4, (long long)(o[1] - o[0]), (long long)(o[2] - o[1]), (long long)(o[3] - o[2]), (long long)(o[4] - o[3]), (long long)(o[5] - o[4]));
-        }
-        fprintf(stderr, "\n");
-        fprintf(stderr, " | one-body + store %lld | total %lld\n", (long long)(t[137] - t[130 + h->exp_order]), (long long)(t[137] - t[128]));
-        for (int wv = 0; wv < 8; ++wv) {
-            const unsigned long long *o = t + 256 + (wv * 16 + 5) * 4, *o0 = t + 256 + 5 * 4, *o6 = t + 256 + (wv * 16 + 6) * 4;
-            fprintf(stderr, "PF_ALL wave %d (product 3, chunk 5): start %+5lld  halfA %5lld  sync %5lld (released at %+5lld)  halfB %5lld  | chunk period %lld\n",
-                    wv, (long long)(o[0] - o0[0]), (long long)(o[1] - o[0]), (long long)(o[2] - o[1]), (long long)(o[2] - o0[0]),
-                    (long long)(o[3] - o[2]), (long long)(o6[0] - o[0]));
-        }
-        for (int wv = 0; wv < 2; ++wv)
-            for (int c = 0; c < (h->M + 7) / 8; ++c) {
-                const unsigned long long *o = t + (wv * 16 + c) * 4;
-                fprintf(stderr, "PF_TS wave %d chunk %2d: halfA %5lld  sync %5lld  halfB %5lld  | since chunk start of wave 0: %lld\n",
-                        wv * 4, c, (long long)(o[1] - o[0]), (long long)(o[2] - o[1]), (long long)(o[3] - o[2]),
-                        (long long)(o[0] - t[c * 4]));
-            }
-    }
-#endif
     return AFQ_OK;
 }

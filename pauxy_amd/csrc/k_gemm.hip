@@ -116,10 +116,10 @@ static int onebody_spin(afq_handle *h, int s, const cplx *rowscale) {
     // (only the launch over the columns of both spins can leave the beta tiles of closed-shell walkers out)
     p.closed_w = (h->closed_large && p.off == 0 && ns == h->nt && !rowscale) ? h->closed_w : nullptr;
     p.na_cols = h->na;
-    if (!h->no_ring && M > 64 && M <= 128 && ns > 16 && ns <= 32 && h->nw >= 64) {
+    if (M > 64 && M <= 128 && ns > 16 && ns <= 32 && h->nw >= 64) {
         // one work-group = one walker-spin: BH1 and phi fragments through the LDS ring once
         AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 1, 2, 2, 4, OneBodyProbT<AR>, MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
-    } else if (!h->no_ring && M > 128 && ns > 32 && h->nw >= 64) {
+    } else if (M > 128 && ns > 32 && h->nw >= 64) {
         // large systems: 128 x 64 or 64 x 128 work-group tiles, whichever pads the output less (M = 400, 100 columns:
         // 448 x 128 against 512 x 128), 3M complex products (2 real ones when BH1 is real); the 64 x 128 shape runs the
         // half-chunk pipelined loop (measured at C5 on the Taylor product: 813 -> 683 us)
@@ -127,19 +127,6 @@ static int onebody_spin(afq_handle *h, int s, const cplx *rowscale) {
         // 128 x 128 tiles (two 16-row and four 16-column MFMA tiles per wave, pipelined loop) when they pad no more than the
         // smaller shapes: twice the MFMAs per chunk and barrier (C4, 256 x 256 per walker: 302 -> 272 us, 1.84 -> 1.77 ms per step)
         const long padC = (long)((M + 127) / 128) * 128 * ((ns + 127) / 128) * 128;
-#ifdef AFQ_TUNING
-        const int ocfg = AFQ_KNOB_INT("AFQ_OB_CFG", 0);
-        if (ocfg == 1) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 4, 4, OneBodyProbT<AR>, MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
-        else if (ocfg == 2) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 1, 1, 8, 4, OneBodyProbT<AR>, MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
-        else if (ocfg == 3) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, OneBodyProbT<AR>, MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
-        else if (AFQ_KNOB_SET("AFQ_OB_NOLOADER")) {
-            if (padC <= padA && padC <= padB) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 2, 4, 4, OneBodyProbT<AR>, MAP_COLS_FAST, true, 1, 2>(p, h->stream, h->zero_page)));
-            else if (padB <= padA) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 4, 4, OneBodyProbT<AR>, MAP_COLS_FAST, true, 1, 2>(p, h->stream, h->zero_page)));
-            else AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 2, 2, 4, OneBodyProbT<AR>, MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
-        }
-        else if (AFQ_KNOB_SET("AFQ_OB_NOLEAN")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, OneBodyProbT<AR>, MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
-        else
-#endif
         (void)padA, (void)padB, (void)padC;
         // round 4: 64 x 64 tiles on four compute waves (2 x 2 MFMA tiles each) + four loader waves that do nothing but the
         // ring refill (STAG = 3): C4 (256 x 256 per walker, real BH1) 338 -> 300 us against the 128 x 128 tiles above, C5
@@ -171,7 +158,7 @@ int k_onebody(afq_handle *h, const cplx *rowscale) {
     // tiles once instead of twice (M = 400, 50 + 50 columns: 448 x 128 against 2 x 512 x 64)
     // ... and on small systems (M <= 64: the register engine, launch-latency bound) one launch instead of two
     const bool merged = h->bh1_same && h->na > 0 && h->nb > 0 && (!rowscale || h->nv == 1) &&
-                        ((M > 128 && h->nt > 32 && h->nw >= 64 && !h->no_ring) || M <= 64);
+                        ((M > 128 && h->nt > 32 && h->nw >= 64) || M <= 64);
     for (int s = merged ? 2 : 0; s < (merged ? 3 : 2); ++s) {
         if (s < 2 && (s == 0 ? h->na : h->nb) == 0) continue;
         const int rc = h->bh1_real ? onebody_spin<true>(h, s, rowscale) : onebody_spin<false>(h, s, rowscale);
@@ -268,8 +255,7 @@ __global__ void ghalf_sum_kernel(const cplx *ghalf, cplx *out, long half, long n
 // sum_q R[q,k] Ga[q] + sum_q R[q,k] Gb[q] = sum_q R[q,k] (Ga + Gb)[q] -- half the contraction.  The 2 * nsplit output
 // partials keep their layout (every consumer sums all of them): they become 2 * nsplit slices of the one contraction.
 bool k_fb_use_sum(afq_handle *h) {
-    return h->rchol_same && h->rchol_real && h->ndet == 1 && h->na == h->nb && h->nw > 32 && !h->no_ring &&
-           !AFQ_KNOB_SET("AFQ_FB_NOSUM");
+    return h->rchol_same && h->rchol_real && h->ndet == 1 && h->na == h->nb && h->nw > 32;
 }
 
 static int force_bias_generic_impl(afq_handle *h);
@@ -280,7 +266,7 @@ int k_force_bias_generic(afq_handle *h) {
     // (multi-determinant trial: one set of partials, and one version, per determinant -- the Coulomb vectors of an energy
     //  evaluation serve the force bias of the next step as they do for one determinant)
     unsigned long long &ver = h->ndet == 1 ? h->vbias_version : h->dets[h->cur_det].vbias_version;
-    if (ver == h->ghalf_version && !AFQ_KNOB_SET("AFQ_FB_NOREUSE")) return AFQ_OK;
+    if (ver == h->ghalf_version) return AFQ_OK;
     const int rc = force_bias_generic_impl(h);
     ver = rc == AFQ_OK ? h->ghalf_version : 0;
     return rc;
@@ -288,7 +274,7 @@ int k_force_bias_generic(afq_handle *h) {
 
 // every determinant's partials are current (left behind by the energy evaluation on the same Green's functions)
 bool k_msd_vbias_current(afq_handle *h) {
-    if (h->ndet <= 1 || AFQ_KNOB_SET("AFQ_FB_NOREUSE")) return false;
+    if (h->ndet <= 1) return false;
     for (int d = 0; d < h->ndet; ++d) if (h->dets[d].vbias_version != h->ghalf_version) return false;
     return true;
 }
@@ -318,46 +304,22 @@ static int force_bias_generic_impl(afq_handle *h) {
             p.kdim = kmax; p.ghalf = h->ghalf_sum; p.astride = half;
         }
         const TileChoice tc = pick_tiles(p.batch, p.rows, p.cols, kMixedTiles, 5);
-        if (h->nw > 32 && !h->no_ring) {
+        if (h->nw > 32) {
             // work-group tile 64 walkers x 64 fields (cfg 2), operands shared through the LDS ring.  Measured at C3
             // together with the reduction of the split-K partial sums in fields_kernel (step time, us):
             // 64x128 tile / 16 slices 553.7, 64x64 / 8 slices 545.4, 32x64 / 8 slices 545.3, 64x64 / 4 slices 553.6
-#ifdef AFQ_TUNING
-            static const int cfg = AFQ_KNOB_INT("AFQ_FB_CFG", 2);
-            static const int kc = AFQ_KNOB_INT("AFQ_GEMM_KC", 1);
-            if (cfg == 1) {
-                KernelTrace kt(h, AFQ_K_FORCE_BIAS);
-                if (kc == 2) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 4, 2, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD, false, 2>(p, h->stream, h->zero_page)));
-                else AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 4, 2, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD>(p, h->stream, h->zero_page)));
-            }
-            else if (cfg == 3) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD>(p, h->stream, h->zero_page)));
-            else if (cfg != 2) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD>(p, h->stream, h->zero_page)));
-            else
-#endif
             {
                 KernelTrace kt(h, AFQ_K_FORCE_BIAS);
                 h->issued_flops[AFQ_K_FORCE_BIAS] = mfma_gemm_wg_issued_flops<4, 2, 1, 2, ForceBiasProb<false>>(
                     p, [&](int, int, int) -> long { return p.kdim; });
                 // half-chunk pipelined loop (STAG = 2): 56 us at C3 against 58 (staggered halves) / 61 (plain loop)
-#ifdef AFQ_TUNING
-                if (AFQ_KNOB_SET("AFQ_GEMM_NOSTAG")) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD>(p, h->stream, h->zero_page)));
-                else if (AFQ_KNOB_SET("AFQ_GEMM_STAG1")) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD, false, 1, 1>(p, h->stream, h->zero_page)));
-                else if (AFQ_KNOB_SET("AFQ_FB_LOADER")) {
-                    const int v = AFQ_KNOB_INT("AFQ_FB_LOADER", 0);
-                    if (v == 2) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                    else if (v == 3) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 1, 1, 4, 4, ForceBiasProb<false>, MAP_BATCH_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                    else AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                }
-                else if (AFQ_KNOB_SET("AFQ_FB_NOLOADER")) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD, false, 1, 2>(p, h->stream, h->zero_page)));
-                else
-#endif
                 // round 4: the ring refill on eight loader waves of its own (STAG = 3; see the HS-potential GEMM): 32.9 -> 31.8 us
                 AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 2, 4, ForceBiasProb<false>, MAP_BATCH_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
             }
         } else {
             DISPATCH_TILES(h, p, tc, MAP_BATCH_XCD, 4);
         }
-    } else if (h->nw > 32 && !h->no_ring) {
+    } else if (h->nw > 32) {
         // complex half-rotated Cholesky vectors (complex trial): rchol is stored planar, so the real-B ring
         // engine runs twice, out = A . Re(rchol) then out += i A . Im(rchol)
         ForceBiasProb<false> p;
@@ -478,7 +440,7 @@ static double msd_fb_cost_gbar(const afq_handle *h) {
 }
 
 bool k_msd_gbar_wanted(afq_handle *h) {
-    if (h->ndet <= 1 || h->kind != AFQ_SYS_GENERIC || h->no_ring || !h->msd_psicT) return false;
+    if (h->ndet <= 1 || h->kind != AFQ_SYS_GENERIC || !h->msd_psicT) return false;
     if (!h->hs_sym && !(h->hs_cplx == AFQ_HS_HERMITIAN && h->msd_psicT_neg)) return false;
     if (2 * h->fb_split > FB_MAX_BATCH) return false;
     if (h->msd_fb_mode == 1) return false;
@@ -512,21 +474,6 @@ int k_force_bias_msd_gbar(afq_handle *h) {
         GbarSymProb p;
         p.batch = nw; p.rows = M; p.cols = M; p.kdim = 2 * KK; p.KK = KK; p.M = M; p.ldS = h->ld_hs;
         p.psicT = h->msd_psicT; p.psicT2 = h->msd_psicT; p.gs = h->msd_gs; p.S = h->msd_S;
-#ifdef AFQ_TUNING
-        const int gcfg = AFQ_KNOB_INT("AFQ_GBAR_CFG", 0);
-        if (gcfg == 1) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GbarSymProb, MAP_BATCH_XCD, true, 1, 3>(p, h->stream, h->zero_page)));
-        else if (gcfg == 2) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GbarSymProb, MAP_BATCH_XCD_ROWS, true, 1, 3>(p, h->stream, h->zero_page)));
-        else if (gcfg == 3) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<4, 2, 2, 4, 4, GbarSymProb, MAP_BATCH_XCD, true>(p, h->stream, h->zero_page)));
-        else if (gcfg == 4) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GbarSymProb, MAP_BATCH_XCD, true, 1, 2>(p, h->stream, h->zero_page)));
-        else if (gcfg == 5) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GbarSymProb, MAP_BATCH_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-        else if (gcfg == 6) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GbarSymProb, MAP_COLS_FAST, true, 1, 2>(p, h->stream, h->zero_page)));
-        else if (gcfg == 7) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GbarSymProb, MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
-        else if (gcfg == 11) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GbarSymProb, MAP_COLS_FAST, true, 1, 5, 4>(p, h->stream, h->zero_page)));
-        else if (gcfg == 9) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GbarSymProb, MAP_COLS_FAST, true, 1, 2, 4>(p, h->stream, h->zero_page)));
-        else if (gcfg == 10) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GbarSymProb, MAP_COLS_FAST, true, 1, 3, 4>(p, h->stream, h->zero_page)));
-        else if (gcfg == 8) AFQ_GEMM_AS(h, "msd_gbar_fold GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 8, GbarSymProb, MAP_BATCH_XCD, true, 1, 2>(p, h->stream, h->zero_page)));
-        else
-#endif
         if (M > 64)
             // 64 x 64 tiles, four waves of 2 x 2, 3-multiplication products, the half-chunk pipelined loop with the waves'
             // own refill (STAG = 2).  Measured at C5 sizes (400 x 400, contraction 2 x 400, 256 walkers;
@@ -657,26 +604,6 @@ struct VhsProbT {
 
 typedef VhsProbT<false> VhsProb;
 
-#ifdef AFQ_TUNING
-static void gemm_ts_dump(afq_handle *h, const char *what) {
-    static unsigned long long *buf = nullptr;
-    static int n = 0;
-    if (!AFQ_KNOB_SET("AFQ_GEMM_TS")) return;
-    if (!buf) {
-        hipMalloc(&buf, (64 * 4 + 64) * 8);
-        hipMemset(buf, 0, (64 * 4 + 64) * 8);
-        hipMemcpyToSymbol(HIP_SYMBOL(afq_gemm_ts), &buf, sizeof(buf));
-    }
-    if (++n != 40) return;
-    unsigned long long t[64 * 4 + 64];
-    hipStreamSynchronize(h->stream);
-    hipMemcpy(t, buf, sizeof(t), hipMemcpyDeviceToHost);
-    for (int w = 0; w < 64; w += 9)
-        fprintf(stderr, "GEMM_TS %s wg %2d: loop %llu ticks = %.2f us of the 100 MHz clock (tick %.2f GHz; %llu chunks, %.0f ticks per chunk)  stores %llu\n",
-                what, w, t[4 * w + 1], t[4 * w] * 0.01, t[4 * w] ? t[4 * w + 1] / (t[4 * w] * 10.0) : 0.0, t[4 * w + 3],
-                t[4 * w + 3] ? (double)t[4 * w + 1] / t[4 * w + 3] : 0.0, t[4 * w + 2]);
-}
-#endif
 
 // complex Cholesky vectors L_n = R_n + i I_n:  VHS = i sqrt(dt) (x R + i x I), two real-B products in stream order --
 // the Re panel writes VHS (Hermitian: packed p <= q columns, R symmetric, mirrored store; general: all M*M columns), the
@@ -685,7 +612,7 @@ static void gemm_ts_dump(afq_handle *h, const char *what) {
 // symmetric nor Hermitian: both triangles are stored (vhs_upper is never set: hs_sym is false).
 template <class P>
 static int vhs_cplx_launch(afq_handle *h, P p, bool packed, double *flops) {
-    if (h->nw > 32 && !h->no_ring) {
+    if (h->nw > 32) {
         if (packed) {
             AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, P, MAP_COLPANEL_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
             *flops += mfma_gemm_wg_issued_flops<2, 2, 1, 5, P>(p, [&](int, int, int) -> long { return p.kdim; });
@@ -729,87 +656,16 @@ static int k_vhs_generic_cplx(afq_handle *h) {
 
 int k_vhs_generic(afq_handle *h) {
     if (h->hs_cplx) return k_vhs_generic_cplx(h);
-#ifdef AFQ_TUNING
-    struct Dump { afq_handle *h; ~Dump() { gemm_ts_dump(h, "after VHS"); } } dump_{h};
-    // timing ablations of the ring loop (mfma_gemm_wg.h: afq_gemm_abl), for this GEMM only: set and cleared in stream order
-    static const int vhs_abl = AFQ_KNOB_INT("AFQ_VHS_ABL", 0);
-    static const int abl_zero = 0;
-    struct Abl {
-        afq_handle *h;
-        Abl(afq_handle *h_) : h(h_) { if (vhs_abl) hipMemcpyToSymbolAsync(HIP_SYMBOL(afq_gemm_abl), &vhs_abl, sizeof(int), 0, hipMemcpyHostToDevice, h->stream); }
-        ~Abl() { if (vhs_abl) hipMemcpyToSymbolAsync(HIP_SYMBOL(afq_gemm_abl), &abl_zero, sizeof(int), 0, hipMemcpyHostToDevice, h->stream); }
-    } abl_guard_{h};
-#endif
     VhsProb p;
     p.batch = 1; p.rows = h->nw; p.cols = h->hs_sym ? h->M * (h->M + 1) / 2 : h->M * h->M; p.kdim = h->K;
     p.xs = h->xs; p.hsT = h->hs_pot; p.ldb = h->ld_hs; p.out = h->vhs; p.sqrt_dt = h->sqrt_dt; p.alive = h->alive;
     p.pair = h->hs_sym ? h->hs_pair : nullptr; p.M = h->M; p.mm = (long)h->M * h->M;
     p.mirror = !h->vhs_upper;
-    if (h->nw > 32 && !h->no_ring) {
+    if (h->nw > 32) {
         // work-group tile 64 walkers x 160 (p,q) pairs; hs_pot^T panels shared through the LDS ring
         // measured at C3 (tools/sweep_vhs_cfg.sh): packed symmetric columns 75.8 us with the 32 x 160 tile
         // (cfg 7), 116 us with the 64 x 160 tile that is best for the full M^2 columns (100 us)
-#ifdef AFQ_TUNING
-        static const int cfg_env = AFQ_KNOB_INT("AFQ_VHS_CFG", -1);
-        const int cfg = cfg_env >= 0 ? cfg_env : (h->hs_sym ? 7 : 0);
-        if (cfg == 1) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 4, 2, 2, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-        else if (cfg == 2) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 2, 2, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-        else if (cfg == 3) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 4, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-        else if (cfg == 4) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 4, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-        else if (cfg == 5) AFQ_GEMM(h, (launch_mfma_gemm_wg<1, 2, 2, 5, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-        else if (cfg == 6) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 1, 2, 5, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-        else if (cfg == 7) {
-            static const int kc = AFQ_KNOB_INT("AFQ_GEMM_KC", 1);
-            KernelTrace kt(h, AFQ_K_VHS);
-            static const int xmap = AFQ_KNOB_INT("AFQ_VHS_XCD", 0);   // measured: 77.8 vs 75.8 us
-            if (AFQ_KNOB_SET("AFQ_GEMM_PIPE")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, VhsProb, MAP_ROWS_FAST, false, 1, 2>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_VHS_LOADER")) {
-                const int v = AFQ_KNOB_INT("AFQ_VHS_LOADER", 0);
-                if (v == 2) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, VhsProb, MAP_COLPANEL_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (v == 3) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 8, VhsProb, MAP_ROWS_FAST, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (v == 4) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 8, VhsProb, MAP_COLPANEL_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (v == 5) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 1, 1, 5, 4, VhsProb, MAP_ROWS_FAST, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (v == 6) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 1, 1, 5, 8, VhsProb, MAP_COLPANEL_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (v == 9) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 1, 1, 5, 4, VhsProb, MAP_COLPANEL_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (v == 10) AFQ_GEMM(h, (launch_mfma_gemm_wg<1, 2, 1, 5, 4, VhsProb, MAP_COLPANEL_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (v == 11) AFQ_GEMM(h, (launch_mfma_gemm_wg<1, 1, 1, 5, 4, VhsProb, MAP_COLPANEL_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (v == 12) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 1, 1, 5, 4, VhsProb, MAP_ROWS_FAST, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (v == 13) AFQ_GEMM(h, (launch_mfma_gemm_wg<1, 2, 2, 5, 4, VhsProb, MAP_COLPANEL_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (v == 14) AFQ_GEMM(h, (launch_mfma_gemm_wg<1, 4, 2, 5, 4, VhsProb, MAP_COLPANEL_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-                else if (v == 7) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, VhsProb, MAP_COLPANEL_XCD, false, 1, 5, 4>(p, h->stream, h->zero_page)));
-                else if (v == 8) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, VhsProb, MAP_ROWS_FAST, false, 1, 5, 4>(p, h->stream, h->zero_page)));
-                else AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, VhsProb, MAP_ROWS_FAST, false, 1, 3>(p, h->stream, h->zero_page)));
-            }
-            else if (AFQ_KNOB_SET("AFQ_VHS_D8")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 8, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_VHS_D8P")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 8, VhsProb, MAP_ROWS_FAST, false, 1, 2>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_VHS_RREG")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, VhsProb, MAP_ROWS_FAST, false, 1, 4>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_VHS_RREG8")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 8, VhsProb, MAP_ROWS_FAST, false, 1, 4>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_VHS_D8X")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 8, VhsProb, MAP_COLPANEL_XCD, false, 1, 2>(p, h->stream, h->zero_page)));
-            else
-            if (kc == 2) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, VhsProb, MAP_ROWS_FAST, false, 2>(p, h->stream, h->zero_page)));
-            else if (xmap) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, VhsProb, MAP_COLPANEL_XCD>(p, h->stream, h->zero_page)));
-            else if (AFQ_KNOB_SET("AFQ_VHS_NOLOADER")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-            // Round 4: four LOADER waves beside the four compute waves (STAG = 3) and the column panels pinned to XCDs.
-            // Timing ablations of the plain loop (tools/vhs_ablate.sh, cycles per chunk of 8 contraction indices at C3):
-            // 1938 as it was = 1385 for the 20 MFMAs alone + 790 for refill, fragment reads and barrier alone, of which
-            // only 240 overlapped -- an LDS-DMA instruction holds its wave's instruction issue for 100+ cycles, and a wave
-            // that is alone on its SIMD idles the matrix pipe meanwhile, wherever in the loop the refill sits (the
-            // pipelined loop: 1882).  With the refill on waves of its own: 1611, 59.0 -> 52.2 us.  The XCD map makes the
-            // eight row tiles of a column panel share one L2: HBM-side fetch 160 -> 38 MB per launch
-            // (profiles/r04_vhs_variants.txt), no effect on the time by itself.
-            else AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 1, 5, 4, VhsProb, MAP_COLPANEL_XCD, false, 1, 3>(p, h->stream, h->zero_page)));
-            h->issued_flops[AFQ_K_VHS] = mfma_gemm_wg_issued_flops<2, 2, 1, 5, VhsProb>(p, [&](int, int, int) -> long { return p.kdim; });
-        }
-        else if (cfg == 8) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 1, 1, 5, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-        else if (cfg == 9) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 3, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-        else if (cfg == 10) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 3, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-        else {
-            KernelTrace kt(h, AFQ_K_VHS);
-            h->issued_flops[AFQ_K_VHS] = mfma_gemm_wg_issued_flops<2, 2, 2, 5, VhsProb>(p, [&](int, int, int) -> long { return p.kdim; });
-            AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 5, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
-        }
-#else
-        // (the variants measured against these two are in tuning builds only: NEGATIVES.md, profiles/r04_vhs_variants.txt)
+        // (the variants measured against these two: NEGATIVES.md, profiles/r04_vhs_variants.txt)
         if (h->hs_sym) {
             // packed symmetric columns: 32 walkers x 160 (p,q) pairs, four compute + four loader waves (STAG = 3), column
             // panels pinned to XCDs
@@ -821,7 +677,6 @@ int k_vhs_generic(afq_handle *h) {
             h->issued_flops[AFQ_K_VHS] = mfma_gemm_wg_issued_flops<2, 2, 2, 5, VhsProb>(p, [&](int, int, int) -> long { return p.kdim; });
             AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 5, 4, VhsProb, MAP_ROWS_FAST>(p, h->stream, h->zero_page)));
         }
-#endif
         return AFQ_OK;
     }
     static const TileChoice cand[] = {{2, 4}, {2, 2}, {1, 4}, {1, 2}};       // (2 x 5 does not fit two fragment sets)
@@ -888,51 +743,13 @@ int k_apply_exponential(afq_handle *h, const cplx *vhs) {
             p.tin = tin; p.tout = tout; p.phi = h->phi; p.inv_n = 1.0 / n; p.alive = h->alive;
             p.closed_w = (h->closed_large && h->nv == 1) ? h->closed_w : nullptr;
             p.na_cols = h->na;
-            if (!h->no_ring && M > 64 && M <= 128 && p.cols > 32 && p.cols <= 64 && h->nw >= 64) {
+            if (M > 64 && M <= 128 && p.cols > 32 && p.cols <= 64 && h->nw >= 64) {
                 // one work-group (8 waves, 128 x 64 tile) = one walker: VHS[w] and T[w] pass the LDS ring once
                 AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 2, 2, 4, TaylorProb, MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
                 continue;
             }
-            if (!h->no_ring && M > 128 && p.cols > 32 && h->nw >= 64) {
+            if (M > 128 && p.cols > 32 && h->nw >= 64) {
                 // large systems: 128 x 64 work-group tiles, 3M complex products
-#ifdef AFQ_TUNING
-                const int tcfg = AFQ_KNOB_INT("AFQ_TAYLOR_CFG", 0);
-                bool done = true;
-                if (AFQ_KNOB_SET("AFQ_BIG_PIPE")) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 2, 2, 4, TaylorProb, MAP_COLS_FAST, true, 1, 2>(p, h->stream, h->zero_page)));
-                else if (tcfg == 1) AFQ_GEMM(h, (launch_mfma_gemm_wg<8, 1, 1, 7, 4, TaylorProb, MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
-                else if (tcfg == 2) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 4, 4, TaylorProb, MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
-                else if (tcfg == 3) AFQ_GEMM(h, (launch_mfma_gemm_wg<8, 1, 1, 7, 2, TaylorProb, MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
-                else if (tcfg == 4) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 4, 4, TaylorProb, MAP_COLS_FAST, true, 1, 2>(p, h->stream, h->zero_page)));
-                else if (tcfg == 5) AFQ_GEMM(h, (launch_mfma_gemm_wg<8, 1, 1, 7, 4, TaylorProb, MAP_COLS_FAST, true, 1, 2>(p, h->stream, h->zero_page)));
-                else if (tcfg == 6) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 4, 4, TaylorProb, MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
-                else if (tcfg == 7) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 1, 1, 8, 4, TaylorProb, MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
-                else if (tcfg == 8) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, TaylorProb, MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
-                else {
-                    // 128 x 64 or 64 x 128 tiles, whichever pads the M x ncols output less; the 64 x 128 shape with the
-                    // half-chunk pipelined loop (C5, 400 x 100: 813 -> 683 us per product)
-                    const long padA = (long)((M + 127) / 128) * 128 * ((p.cols + 63) / 64) * 64;
-                    const long padB = (long)((M + 63) / 64) * 64 * ((p.cols + 127) / 128) * 128;
-                    if (AFQ_KNOB_SET("AFQ_TAYLOR_NOLOADER")) {
-                        if (padB <= padA) AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 1, 4, 4, TaylorProb, MAP_COLS_FAST, true, 1, 2>(p, h->stream, h->zero_page)));
-                        else AFQ_GEMM(h, (launch_mfma_gemm_wg<4, 2, 2, 2, 4, TaylorProb, MAP_COLS_FAST, true>(p, h->stream, h->zero_page)));
-                    }
-                    // round 4: 64 x 64 tiles, four compute + four loader waves (STAG = 3; see k_vhs_generic): C5 sizes 689 -> 627 us
-                    else if (AFQ_KNOB_SET("AFQ_TAYLOR_LEAN")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, TaylorProb, MAP_COLS_FAST, true, 1, 5, 4>(p, h->stream, h->zero_page)));
-                    else if (AFQ_KNOB_SET("AFQ_TAYLOR_LEAN1")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, TaylorProb, MAP_COLS_FAST, true, 1, 5, 1>(p, h->stream, h->zero_page)));
-                    else if (AFQ_KNOB_SET("AFQ_TAYLOR_WPE")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, TaylorProb, MAP_COLS_FAST, true, 1, 3, 4>(p, h->stream, h->zero_page)));
-                    else if (AFQ_KNOB_SET("AFQ_TAYLOR_WPE2")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, TaylorProb, MAP_COLS_FAST, true, 1, 2, 4>(p, h->stream, h->zero_page)));
-                    else if (AFQ_KNOB_SET("AFQ_TAYLOR_S2")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, TaylorProb, MAP_BATCH_XCD, true, 1, 2>(p, h->stream, h->zero_page)));
-                    else if (AFQ_KNOB_SET("AFQ_TAYLOR_S2C")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, TaylorProb, MAP_COLS_FAST, true, 1, 2>(p, h->stream, h->zero_page)));
-                    else if (AFQ_KNOB_SET("AFQ_TAYLOR_XCD")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, TaylorProb, MAP_BATCH_XCD, true, 1, 3>(p, h->stream, h->zero_page)));
-                    else if (AFQ_KNOB_SET("AFQ_TAYLOR_LOADER")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, TaylorProb, MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
-                    // round 5: the same 64 x 64 tiles from four waves that refill the ring themselves inside the half-chunk
-                    // pipelined loop (STAG = 2): 627-633 -> 612-616 us (C5 sizes).  Forcing two work-groups per CU
-                    // (128 VGPRs, WPE = 4) spills 65-98 registers into the chunk loop: 2102 us
-                    else if (AFQ_KNOB_SET("AFQ_TAYLOR_S2DEF")) AFQ_GEMM(h, (launch_mfma_gemm_wg<2, 2, 2, 2, 4, TaylorProb, MAP_COLS_FAST, true, 1, 2>(p, h->stream, h->zero_page)));
-                    else done = false;
-                }
-                if (done) continue;
-#endif
                 {
                     // ... and TWO work-groups per CU: the 3-multiplication kernels of this engine hold 142-160 VGPRs, i.e. one
                     // work-group of 4 + 4 waves per CU.  Forcing 128 registers on the pipelined loops spills (2102 us);

@@ -99,8 +99,6 @@ struct GreensArgs {
     int o_in_lds;
     int only_alive;
     const int *alive;
-    int dbg;            // timing experiments only (AFQ_GREENS_DBG, tuning builds; 0 in the product): 1 skip pivot loop,
-                        // 2 skip phase 3, 4 skip phase 1, 8 LDS Gauss-Jordan instead of the register one
     int psi_real;       // every imaginary part of the (single, shared) trial is exactly zero (checked at upload)
     int skip_spin;      // with gsum: do not store the per-spin Ghalf (nobody will read it: afq_propagate_finish)
     int psi_closed;     // the alpha and beta blocks of the (single, shared) trial are bitwise equal, na == nb (checked at upload)
@@ -208,12 +206,6 @@ __global__ void weight_kernel(WeightArgs a) {
 // wa.weight != null: the hybrid / free-projection weight update of this walker (propagation/continuous.py:264-292,
 // :194-200) and the driver's weight cap run right behind its determinant (a.det IS wa.ovlp_new then), which
 // saves the separate weight_kernel launch of the step.
-#ifdef AFQ_TUNING
-__device__ unsigned long long *afq_gs_ts = nullptr;      // [8 waves][12 stamps] of work-group 0 (AFQ_GS_TS)
-#define GS_STAMP(i) do { if (afq_gs_ts && blockIdx.x == 0 && (threadIdx.x & 63) == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)); afq_gs_ts[(threadIdx.x >> 6) * 12 + (i)] = t_; } } while (0)
-#else
-#define GS_STAMP(i)
-#endif
 // WGJ: both spins have n <= 32 and invert by one wave each in registers (gj_wave.h); otherwise the LDS Gauss-Jordan of
 // wave 0.  Two instantiations, so that neither carries the other's registers and scalars.
 template <bool INVERSE, bool WGJ>
@@ -241,7 +233,6 @@ __global__ __launch_bounds__(512) void greens_small_kernel(GreensArgs a, WeightA
     const int lr = lane & 15, lk = lane >> 4;
     const int nt16 = (n + 15) >> 4;
     const int nks = (M + 3) >> 2;
-    GS_STAMP(0);
     // ---- phases 0 and 1: the walker's Slater matrix into LDS, O = phi_s^T conj(psi_s) by MFMA (phi fragments from LDS, trial
     // fragments from memory).  k-steps go in groups of four.  The first sixteen trial fragments of the wave's first tile are
     // requested BEFORE the copy (they do not depend on the walker: their latency runs under phase 0), the rest right behind
@@ -256,7 +247,7 @@ __global__ __launch_bounds__(512) void greens_small_kernel(GreensArgs a, WeightA
     // whole phase (a generic lambda instantiated for both cases): a test inside the loops is a branch per k-step.
     const bool yreal = WGJ && a.psi_real != 0;
     const char *psi_w = (const char *)(a.psi + w * a.psi_stride);
-    const bool has_tile = wave < nt16 * nt16 && !(a.dbg & 4);
+    const bool has_tile = wave < nt16 * nt16;
     bool closed = false;                                     // (set in phase01, uniform over the work-group)
     auto phase01 = [&](auto yr_tag) __attribute__((always_inline)) {
         constexpr bool YR = decltype(yr_tag)::value;
@@ -290,7 +281,6 @@ __global__ __launch_bounds__(512) void greens_small_kernel(GreensArgs a, WeightA
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        GS_STAMP(1);
         __syncthreads();                                         // phi_l complete
         // Closed-shell walker (round 5): the trial's spin blocks are bitwise equal (host-checked) and so are THIS walker's
         // -- an RHF run, where every operator of the step acts on both spins alike.  Checked here, on the copy in LDS, every
@@ -308,7 +298,7 @@ __global__ __launch_bounds__(512) void greens_small_kernel(GreensArgs a, WeightA
             if (!closed && tid == 0 && a.closed_bad) atomicMax(a.closed_bad, a.closed_epoch);
             if (closed && tid == 0 && a.counters) atomicAdd(&a.counters[5], 1ull);
         }
-        for (int t = wave; t < ((a.dbg & 4) || (closed && g == 1) ? 0 : nt16 * nt16); t += 4) {
+        for (int t = wave; t < (closed && g == 1 ? 0 : nt16 * nt16); t += 4) {
             const int ti = t / nt16, tj = t % nt16;
             const int ia = ti * 16 + lr;
             const int iac = ia < n ? ia : n - 1;
@@ -367,15 +357,13 @@ __global__ __launch_bounds__(512) void greens_small_kernel(GreensArgs a, WeightA
     };
     if (yreal) phase01(std::true_type{});
     else phase01(std::false_type{});
-    GS_STAMP(2);
     __syncthreads();
-    GS_STAMP(3);
     // ---- phase 2
     __shared__ cplx gj_row[2][32], gj_piv[2][32];
     __shared__ int gj_prow[2][32];
     // (the two single-wave inversions run on different SIMDs: spin up on wave 0, spin down on wave 1 of its group = wave 5)
     if (WGJ) {
-        if (wave == g && !(a.dbg & 1) && !(closed && g == 1)) {
+        if (wave == g && !(closed && g == 1)) {
             cplx ph;
             int la;
             gj_wave32(O, n, lane, INVERSE, gj_row[g], gj_piv[g], gj_prow[g], ph, la);
@@ -384,7 +372,7 @@ __global__ __launch_bounds__(512) void greens_small_kernel(GreensArgs a, WeightA
                 if (closed) { ph_s[1] = ph; la_s[1] = (double)la; }         // det O_b = det O_a
             }
         }
-    } else if (wave == 0 && !(a.dbg & 1)) {
+    } else if (wave == 0) {
         // det = prod of pivots, kept as (mantissa, binary exponent) so that neither log, exp nor
         // hypot sits on the per-pivot critical path
         cplx ph = cmake(1.0, 0.0);
@@ -503,18 +491,15 @@ __global__ __launch_bounds__(512) void greens_small_kernel(GreensArgs a, WeightA
         }
         if (lane == 0) { ph_s[g] = ph; la_s[g] = (double)la; }
     }
-    GS_STAMP(4);
     __syncthreads();
-    GS_STAMP(5);
     // (the last wave: its phase-3 item is the half-width one, the first wave's is full)
     if (tid == 448) {
-        const cplx p2 = (a.dbg & 1) ? cmake(1.0, 0.0) : cmul(ph_s[0], ph_s[1]);
-        const int e = (a.dbg & 1) ? 0 : (int)(la_s[0] + la_s[1]);
+        const cplx p2 = cmul(ph_s[0], ph_s[1]);
+        const int e = (int)(la_s[0] + la_s[1]);
         a.det[w] = cmake(ldexp(p2.x, e), ldexp(p2.y, e));
         if (a.det_a) a.det_a[w] = cmake(ldexp(ph_s[0].x, (int)la_s[0]), ldexp(ph_s[0].y, (int)la_s[0]));
         if (wa.weight) weight_update_and_cap(wa, w);
     }
-    GS_STAMP(6);
     if (INVERSE && a.oinv) {
         cplx *oo = a.oinv + ((long)w * 2 + g) * nmax * nmax;
         for (int e = tid & 255; e < n * n; e += 256) oo[(e / n) * nmax + (e % n)] = O[e];
@@ -527,7 +512,7 @@ __global__ __launch_bounds__(512) void greens_small_kernel(GreensArgs a, WeightA
     // With a.gsum (na == nb, host-checked) every wave of the work-group takes items of BOTH spins, so that the two Green's
     // functions of an element meet in one lane and their sum (what the force bias contracts when both spins share the
     // Cholesky block) is stored along.
-    if (INVERSE && a.ghalf && !(a.dbg & 2)) {
+    if (INVERSE && a.ghalf) {
         const bool both = a.gsum != nullptr;
         const int mt16 = (M + 15) >> 4, npair = (mt16 + 1) >> 1;
         const int first = both ? __builtin_amdgcn_readfirstlane(tid >> 6) : wave, stride = both ? 8 : 4;
@@ -554,7 +539,6 @@ __global__ __launch_bounds__(512) void greens_small_kernel(GreensArgs a, WeightA
                 }
                 d4_t p1a = {0, 0, 0, 0}, p2a = {0, 0, 0, 0}, p3a = {0, 0, 0, 0};
                 d4_t p1b = {0, 0, 0, 0}, p2b = {0, 0, 0, 0}, p3b = {0, 0, 0, 0};
-                GS_STAMP(7 + 2 * (s & 1));
 #pragma unroll
                 for (int ks = 0; ks < 12; ++ks) {
                     if (ks < nks3) {
@@ -573,7 +557,6 @@ __global__ __launch_bounds__(512) void greens_small_kernel(GreensArgs a, WeightA
                         }
                     }
                 }
-                GS_STAMP(8 + 2 * (s & 1));
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int i = ti * 16 + lk + 4 * r;
@@ -602,7 +585,6 @@ __global__ __launch_bounds__(512) void greens_small_kernel(GreensArgs a, WeightA
             }
         }
     }
-    GS_STAMP(11);
 }
 
 // --------------------------------------------------------------------------
@@ -790,7 +772,7 @@ static int launch_greens(afq_handle *h, cplx *ghalf, cplx *det, int only_alive, 
     a.phi = h->phi; a.psi = h->psi; a.psi_stride = h->psi_stride; a.ghalf = ghalf; a.det = det; a.ws = h->lu_ws;
     a.det_a = h->det_a_out;
     a.psi_real = h->psi_real && h->psi_stride == 0 && h->ndet <= 1;
-    a.psi_closed = h->psi_closed && h->psi_stride == 0 && h->ndet <= 1 && !AFQ_KNOB_SET("AFQ_NO_CLOSED_GREENS");
+    a.psi_closed = h->psi_closed && h->psi_stride == 0 && h->ndet <= 1;
     a.closed_bad = nullptr; a.closed_epoch = 0; a.counters = h->counters;
     if (ghalf == h->ghalf) h->closed_checked_version = 0;       // (set again below when THIS launch checks every walker)
     a.skip_spin = 0;
@@ -818,57 +800,25 @@ static int launch_greens(afq_handle *h, cplx *ghalf, cplx *det, int only_alive, 
             h->fuse_weight_done = true;
         }
         h->fuse_weight_req = false;
-        static const int dbg = AFQ_KNOB_INT("AFQ_GREENS_DBG", 0);
-        a.dbg = dbg;
-#ifdef AFQ_TUNING
-        static bool nopiv_set = false;
-        if (!nopiv_set && AFQ_KNOB_SET("AFQ_GJ_NOPIV")) {
-            const int one = 1;
-            hipMemcpyToSymbol(HIP_SYMBOL(afq_gj_nopiv), &one, sizeof(int));
-            nopiv_set = true;
-        }
-#endif
-#ifdef AFQ_TUNING
-        static unsigned long long *gsts = nullptr;
-        static int gs_launch = 0;
-        if (AFQ_KNOB_SET("AFQ_GS_TS")) {
-            if (!gsts) { hipMalloc(&gsts, 96 * 8); hipMemset(gsts, 0, 96 * 8); hipMemcpyToSymbol(HIP_SYMBOL(afq_gs_ts), &gsts, sizeof(gsts)); }
-            if (++gs_launch == 30) {
-                unsigned long long t[96];
-                hipStreamSynchronize(h->stream);
-                hipMemcpy(t, gsts, sizeof(t), hipMemcpyDeviceToHost);
-                for (int wv = 0; wv < 8; ++wv) {
-                    fprintf(stderr, "gs_ts wave %d:", wv);
-                    for (int i = 1; i < 12; ++i) fprintf(stderr, " %6lld", t[wv * 12 + i] ? (long long)(t[wv * 12 + i] - t[0]) : -1LL);
-                    fprintf(stderr, "\n");
-                }
-            }
-        }
-#endif
         if (h->M > 4 * GS_KSMAX) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "fast Green's kernel supports M <= 128");
         const size_t lds = sizeof(cplx) * (2 * ((size_t)nmax * nmax + 2 * nmax) + ((2 * nmax + 3) / 4 + 1) +
                                            (size_t)h->M * h->nt);
         // raise the dynamic-LDS cap once per kernel and device, not per launch
         static size_t lds_set[4][AFQ_MAX_DEVICES] = {{0}};
         const bool wgj = nmax <= 32;
-#ifdef AFQ_TUNING
-        const bool wgj_on = wgj && !(dbg & 8);
-#else
-        const bool wgj_on = wgj;
-#endif
         // at most 8 electrons per spin, walker + trial in LDS: the vector-ALU kernel above
         const size_t lds_tiny = sizeof(cplx) * 2 * (size_t)h->M * h->nt;
         static size_t lds_set_tiny[2][AFQ_MAX_DEVICES] = {{0}};
-        const bool tiny = nmax <= 8 && h->nt >= 1 && lds_tiny <= 150 * 1024 && !dbg && !AFQ_KNOB_SET("AFQ_NO_GREENS_TINY");
+        const bool tiny = nmax <= 8 && h->nt >= 1 && lds_tiny <= 150 * 1024;
         if (ghalf || oinv) {
             // the spin sum the force bias contracts (every walker written: not on the only_alive path)
             const bool want_sum = ghalf && ghalf == h->ghalf && !only_alive && k_fb_use_sum(h) && h->psi_stride == 0;
             if (want_sum) {
                 if (!h->ghalf_sum) AFQ_HIP(h, hipMalloc(&h->ghalf_sum, sizeof(cplx) * (size_t)h->na * h->M * h->nw));
                 a.gsum = h->ghalf_sum;
-                if (h->ghalf_skip_store && (wgj_on || tiny) && !oinv) { a.skip_spin = 1; h->ghalf_skipped = true; }
+                if (h->ghalf_skip_store && (wgj || tiny) && !oinv) { a.skip_spin = 1; h->ghalf_skipped = true; }
             }
-            if (want_sum && wgj_on && !tiny && a.psi_closed && !oinv) {
+            if (want_sum && wgj && !tiny && a.psi_closed && !oinv) {
                 // this launch compares the spin blocks of EVERY walker: its verdict holds for the Ghalf it leaves behind
                 a.closed_bad = h->closed_bad; a.closed_epoch = ++h->closed_epoch;
                 h->closed_checked_version = h->ghalf_version;
@@ -877,7 +827,7 @@ static int launch_greens(afq_handle *h, cplx *ghalf, cplx *det, int only_alive, 
             if (tiny) {
                 AFQ_HIP(h, afq_raise_lds((const void *)greens_tiny_kernel<true>, lds_tiny, lds_set_tiny[0]));
                 AFQ_LAUNCH(h, (greens_tiny_kernel<true>), dim3(h->nw), dim3(512), lds_tiny, h->stream, a, wa);
-            } else if (wgj_on) {
+            } else if (wgj) {
                 AFQ_HIP(h, afq_raise_lds((const void *)greens_small_kernel<true, true>, lds, lds_set[0]));
                 AFQ_LAUNCH(h, (greens_small_kernel<true, true>), dim3(h->nw), dim3(512), lds, h->stream, a, wa);
             } else {
@@ -888,7 +838,7 @@ static int launch_greens(afq_handle *h, cplx *ghalf, cplx *det, int only_alive, 
         } else if (tiny) {
             AFQ_HIP(h, afq_raise_lds((const void *)greens_tiny_kernel<false>, lds_tiny, lds_set_tiny[1]));
             AFQ_LAUNCH(h, (greens_tiny_kernel<false>), dim3(h->nw), dim3(512), lds_tiny, h->stream, a, wa);
-        } else if (wgj_on) {
+        } else if (wgj) {
             AFQ_HIP(h, afq_raise_lds((const void *)greens_small_kernel<false, true>, lds, lds_set[2]));
             AFQ_LAUNCH(h, (greens_small_kernel<false, true>), dim3(h->nw), dim3(512), lds, h->stream, a, wa);
         } else {
@@ -902,7 +852,6 @@ static int launch_greens(afq_handle *h, cplx *ghalf, cplx *det, int only_alive, 
     const size_t need = sizeof(cplx) * (size_t)nmax * nmax;
     a.o_in_lds = need <= 64 * 1024;
     a.only_alive = only_alive; a.alive = h->alive;
-    a.dbg = 0;
     if (!a.o_in_lds && !h->lu_ws)
         AFQ_HIP(h, hipMalloc(&h->lu_ws, sizeof(cplx) * (size_t)h->nw * nmax * nmax));
     a.ws = h->lu_ws;
@@ -1132,9 +1081,6 @@ __global__ __launch_bounds__(NTHR) void fields_kernel(int K, double sqrt_dt, con
                                                       FieldRng rng) {
     __shared__ double red[NTHR / 64][8];
     const int w = blockIdx.x;
-#ifdef AFQ_TUNING
-    if (rng.dbg & 8) return;
-#endif
     if (rng.on) {
         const bool live = fabs(rng.weight[w]) > 1e-8;
         if (threadIdx.x == 0) rng.alive_out[w] = live ? 1 : 0;
@@ -1149,9 +1095,6 @@ __global__ __launch_bounds__(NTHR) void fields_kernel(int K, double sqrt_dt, con
         if (ab > 1.0) { b.x /= ab; b.y /= ab; acc[6] += 1.0; }
         const double x = rng.on ? xdev : xi[e];
         const cplx sft = cmake(x - b.x, -b.y);
-#ifdef AFQ_TUNING
-        if (!(rng.dbg & 4))
-#endif
         {
         xbar[e] = b;
         xs[e] = sft;
@@ -1238,15 +1181,9 @@ __global__ __launch_bounds__(NTHR) void fields_kernel(int K, double sqrt_dt, con
             for (int m = 0; m < 2; ++m) {
                 const long e = 2 * pr + m;
                 const int n = (int)(e - e0);
-#ifdef AFQ_TUNING
-                if (rng.dbg & 2) { if (n >= 0 && n < K) { bb[m] = cmake(0.01 * n, 0.02); mm[m] = cmake(0.5, 0.1); } continue; }
-#endif
                 if (n >= 0 && n < K) { bb[m] = FUSED ? xbar_value(xa, w, n) : xbar[e]; mm[m] = mf[n]; }
             }
             double xn[2] = {0.0, 0.0};
-#ifdef AFQ_TUNING
-            if (rng.dbg & 1) { xn[0] = 0.3 + 1e-3 * threadIdx.x; xn[1] = -0.2; } else
-#endif
             if (rng.on) philox_normal_pair(pr, rng.seed, rng.stream, rng.counter, xn[0], xn[1]);
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
@@ -1256,9 +1193,6 @@ __global__ __launch_bounds__(NTHR) void fields_kernel(int K, double sqrt_dt, con
             }
         }
     }
-#ifdef AFQ_TUNING
-    if (rng.dbg & 16) { if (threadIdx.x == 0) { cmf[w] = cmake(acc[0], acc[1]); cfb[w] = cmake(acc[2], acc[3] + acc[4] + acc[5] + acc[6]); } return; }
-#endif
     // one reduction for all seven sums: wave shuffles, one barrier
 #pragma unroll
     for (int q = 0; q < 7; ++q)
@@ -1291,9 +1225,6 @@ int k_fields(afq_handle *h) {
 // force bias from the contraction output + clip + shift in one launch (the step's hot path)
 int k_xbar_fields(afq_handle *h, cplx *hubbard_factors) {
     FieldRng rng = FieldRng();
-#ifdef AFQ_TUNING
-    rng.dbg = AFQ_KNOB_INT("AFQ_FIELDS_DBG", 0);
-#endif
     if (h->rng_inline) {
         rng.on = 1; rng.seed = h->rng_seed; rng.stream = h->rng_stream; rng.counter = h->rng_inline_counter;
         rng.weight = h->weight; rng.alive_out = h->alive;
@@ -1563,12 +1494,6 @@ struct RfArgs {
     cplx *keep;          // cached overlap of a Green's function that stays valid across the QR (ovlp /= det R), or null
 };
 
-#ifdef AFQ_TUNING
-__device__ unsigned long long *afq_rf_ts = nullptr;
-#define RF_STAMP(i) do { if (afq_rf_ts && blockIdx.x == 0 && threadIdx.x == 0) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)); afq_rf_ts[i] = t_; } } while (0)
-#else
-#define RF_STAMP(i)
-#endif
 // RJ: registers per lane of the Cholesky wave (ceil(nmax / 2) rounded up to 4 / 8 / 13 / 16; one instantiation each: a kernel that
 // carries all of them spills)
 template <int RJ>
@@ -1586,7 +1511,6 @@ __global__ __launch_bounds__(512) void reortho_fused_kernel(RfArgs a) {
     cplx *phi_l = (cplx *)smem;                              // [M, nt]
     cplx *S = phi_l + (long)M * nt + (long)g * (32 * RF_LD);   // [32, RF_LD] Gram matrix, then T^T, of this spin (row stride 33: no bank conflicts for a lane per row)
     cplx *phi_g = a.phi + (long)w * M * nt;
-    RF_STAMP(0);
     {
         // the walker by LDS-DMA: 1 KB per wave and instruction, all requests of a wave in flight at once
         const unsigned total = (unsigned)(M * nt) * 16u;
@@ -1599,8 +1523,7 @@ __global__ __launch_bounds__(512) void reortho_fused_kernel(RfArgs a) {
     }
     if (tid < 2) { logd_s[tid] = 0.0; bad_s[tid] = 0; }
     __syncthreads();
-    RF_STAMP(1);
-    const int nt16 = (n + 15) >> 4, mt16 = (M + 15) >> 4, nks = (M + 3) >> 2, nks3 = (n + 3) >> 2;
+    const int nt16 = (n + 15) >> 4, mt16 = (M + 15) >> 4, nks = (M + 3) >> 2;
     for (int pass = 0; pass < 2; ++pass) {
         // ---- Gram matrix
         for (int t = wave; t < nt16 * nt16; t += 4) {
@@ -1648,7 +1571,6 @@ __global__ __launch_bounds__(512) void reortho_fused_kernel(RfArgs a) {
                 accI = mfma16(x.y, y.y, accI);
                 acc3 = mfma16(x.x - x.y, y.x + y.y, acc3);
             }
-            RF_STAMP(9 + pass);
             if (nfull < nks) {
                 const int p = nfull * 4 + lk, pc = p < M ? p : M - 1;
                 cplx x = phi_l[pc * nt + off + iac], y = phi_l[pc * nt + off + jbc];
@@ -1668,9 +1590,7 @@ __global__ __launch_bounds__(512) void reortho_fused_kernel(RfArgs a) {
                 if (i < n && j < n) S[i * RF_LD + j] = cmake(accR[r], accI[r]);
             }
         }
-        RF_STAMP(11 + pass);
         __syncthreads();
-        RF_STAMP(2 + 3 * pass);
         // ---- inverse Cholesky factor: T^T[r][c] = conj(Ltilde^-1[r][c]) / sqrt(D_r) (see chol_small_kernel)
         if (wave == g && n > 0) {                            // (spin up on SIMD 0, spin down on SIMD 1: not both on one)
             bool bad = false;
@@ -1687,7 +1607,6 @@ __global__ __launch_bounds__(512) void reortho_fused_kernel(RfArgs a) {
             }
         }
         __syncthreads();
-        RF_STAMP(3 + 3 * pass);
         if (bad_s[0] | bad_s[1]) {                           // leave the walker to the Gram-Schmidt kernel
             if (tid == 0) a.fail[w] = 1;
             return;
@@ -1753,7 +1672,6 @@ __global__ __launch_bounds__(512) void reortho_fused_kernel(RfArgs a) {
             }
         }
         __syncthreads();
-        RF_STAMP(4 + 3 * pass);
     }
     for (int e = tid; e < M * nt; e += 512) phi_g[e] = phi_l[e];
     if (tid == 0) {
@@ -1764,15 +1682,13 @@ __global__ __launch_bounds__(512) void reortho_fused_kernel(RfArgs a) {
         if (a.keep) a.keep[w] = cmake(a.keep[w].x / d, a.keep[w].y / d);
         if (a.fp) a.weight[w] *= d;                          // walkers/handler.py:178-181
     }
-    RF_STAMP(8);
 }
 
 static bool reortho_fused_supported(afq_handle *h, size_t *lds_out) {
     const int nmax = h->na > h->nb ? h->na : h->nb;
     const size_t lds = sizeof(cplx) * ((size_t)h->M * h->nt + 2 * 32 * RF_LD);
     *lds_out = lds;
-    static const bool off = AFQ_KNOB_SET("AFQ_NO_REORTHO_FUSED");
-    return !off && nmax <= 32 && h->nb > 0 && h->M >= 16 && lds <= 150 * 1024;
+    return nmax <= 32 && h->nb > 0 && h->M >= 16 && lds <= 150 * 1024;
 }
 
 static int k_reortho_fused(afq_handle *h, size_t lds, cplx *keep) {
@@ -1787,24 +1703,6 @@ static int k_reortho_fused(afq_handle *h, size_t lds, cplx *keep) {
                           (const void *)reortho_fused_kernel<13>, (const void *)reortho_fused_kernel<16>};
     static size_t lds_set4[4][AFQ_MAX_DEVICES] = {{0}};
     AFQ_HIP(h, afq_raise_lds(kfn[rji], lds, lds_set4[rji]));
-#ifdef AFQ_TUNING
-    static unsigned long long *rfts = nullptr;
-    static int rf_launch = 0;
-    if (AFQ_KNOB_SET("AFQ_RF_TS")) {
-        if (!rfts) { hipMalloc(&rfts, 13 * 8); hipMemset(rfts, 0, 13 * 8); hipMemcpyToSymbol(HIP_SYMBOL(afq_rf_ts), &rfts, sizeof(rfts)); }
-        if (++rf_launch == 20) {
-            unsigned long long t[13];
-            hipStreamSynchronize(h->stream);
-            hipMemcpy(t, rfts, sizeof(t), hipMemcpyDeviceToHost);
-            fprintf(stderr, "RF_TS ticks: load %lld | pass 0: gram %lld chol %lld q %lld | pass 1: gram %lld chol %lld q %lld | store %lld\n",
-                    (long long)(t[1] - t[0]), (long long)(t[2] - t[1]), (long long)(t[3] - t[2]), (long long)(t[4] - t[3]),
-                    (long long)(t[5] - t[4]), (long long)(t[6] - t[5]), (long long)(t[7] - t[6]), (long long)(t[8] - t[7]));
-            fprintf(stderr, "RF_TS gram detail: pass 0 k-loop %lld, to own end %lld, barrier %lld | pass 1 k-loop %lld, to own end %lld, barrier %lld\n",
-                    (long long)(t[9] - t[1]), (long long)(t[11] - t[9]), (long long)(t[2] - t[11]),
-                    (long long)(t[10] - t[4]), (long long)(t[12] - t[10]), (long long)(t[5] - t[12]));
-        }
-    }
-#endif
     if (rji == 0) AFQ_LAUNCH(h, reortho_fused_kernel<4>, dim3(h->nw), dim3(512), lds, h->stream, a);
     else if (rji == 1) AFQ_LAUNCH(h, reortho_fused_kernel<8>, dim3(h->nw), dim3(512), lds, h->stream, a);
     else if (rji == 2) AFQ_LAUNCH(h, reortho_fused_kernel<13>, dim3(h->nw), dim3(512), lds, h->stream, a);
@@ -1822,17 +1720,16 @@ int k_reortho(afq_handle *h, cplx *keep, bool *keep_done) {
     a.only = nullptr; a.keep = nullptr;
     if (keep_done) *keep_done = false;
     const int nmax = h->na > h->nb ? h->na : h->nb;
-    static const bool no_cholqr = AFQ_KNOB_SET("AFQ_NO_CHOLQR");
     // Cholesky-QR2 on the GEMM engines: always for 45 < N <= 128; for smaller N once the population is
     // large enough that seven launches beat the one latency-bound Gram-Schmidt work-group per walker
-    const bool small_ok = nmax <= 45 && h->nb > 0 && !h->no_ring && h->nw >= 64 && h->M >= 32;
+    const bool small_ok = nmax <= 45 && h->nb > 0 && h->nw >= 64 && h->M >= 32;
     size_t lds_fused = 0;
-    if (small_ok && !no_cholqr && reortho_fused_supported(h, &lds_fused)) {
+    if (small_ok && reortho_fused_supported(h, &lds_fused)) {
         int rc = k_reortho_fused(h, lds_fused, keep);
         if (rc) return rc;
         a.only = h->qr_fail; a.keep = keep;
         if (keep_done) *keep_done = keep != nullptr;
-    } else if ((k_greens_big_supported(h) || small_ok) && !no_cholqr) {
+    } else if (k_greens_big_supported(h) || small_ok) {
         int rc = k_reortho_big(h);
         if (rc) return rc;
         a.only = h->qr_fail;

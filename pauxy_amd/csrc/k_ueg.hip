@@ -101,8 +101,6 @@ struct UegFieldArgs {
     // round 5: the walker's Ghalf, the trial rows and the two gather tables go to LDS by LDS-DMA at kernel start
     int nfb;                    // entries of the force-bias lists (fb_off[K])
     int fb_lds, coef_lds;       // the force-bias lists / the coefficient lists are staged in LDS (they fit)
-    int abl;                    // tuning builds, timing ablations (WRONG results): 1 no Philox, 2 no gather + clip, 4 no G rows,
-                                // 8 no coefficients
 };
 
 // copy `bytes` (a multiple of 16, the source allocation padded accordingly) from memory to LDS with every wave's requests
@@ -175,11 +173,11 @@ __device__ __attribute__((always_inline)) inline bool ueg_fields_body(const UegF
         }
     }
     double xn0[2] = {0.0, 0.0};
-    if (rng.on && pr0 <= pr_last && !(a.abl & 1)) philox_normal_pair(pr0, rng.seed, rng.stream, rng.counter, xn0[0], xn0[1]);
+    if (rng.on && pr0 <= pr_last) philox_normal_pair(pr0, rng.seed, rng.stream, rng.counter, xn0[0], xn0[1]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     // rows of G_up + G_dn that are not identically zero: sum over ALL columns of the trial (both spins) of conj(psi[row, c]) Ghalf[c, :]
-    for (int e = tid; e < ((a.abl & 4) ? 0 : a.nrows * a.M); e += UF_NTF) {
+    for (int e = tid; e < a.nrows * a.M; e += UF_NTF) {
         const int rr = e / a.M, j = e - rr * a.M;
         cplx acc = cmake(0.0, 0.0);
         for (int c0 = 0; c0 < a.nt; c0 += 8) {
@@ -200,14 +198,14 @@ __device__ __attribute__((always_inline)) inline bool ueg_fields_body(const UegF
     double acc[7] = {0, 0, 0, 0, 0, 0, 0};
     auto element = [&](const long e, const int n, const double x, const int z0, const int z1, const cplx mm) {
         cplx b = cmake(0.0, 0.0);
-        if (a.force_bias && !(a.abl & 2)) {
+        if (a.force_bias) {
             // propagation/planewave.py:70-76: vbias[n] = (G_up + G_dn) . column n of [iA | iB], xbar = -sqrt(dt) vbias
             cplx v = cmake(0.0, 0.0);
             if (a.fb_lds) { for (int z = z0; z < z1; ++z) cfma(v, fbv[z], gc[fbi[z]]); }
             else { for (int z = z0; z < z1; ++z) cfma(v, a.fb_val[z], gc[a.fb_idx[z]]); }
             b = cmake(-a.sqrt_dt * v.x, -a.sqrt_dt * v.y);
         }
-        const double ab = (a.abl & 2) ? 0.0 : hypot(b.x, b.y);
+        const double ab = hypot(b.x, b.y);
         if (ab > 1.0) { b.x /= ab; b.y /= ab; acc[6] += 1.0; }
         const cplx sft = cmake(x - b.x, -b.y);
         a.xbar[e] = b;
@@ -259,7 +257,7 @@ __device__ __attribute__((always_inline)) inline bool ueg_fields_body(const UegF
     cplx *vc = a.vcoef + (long)w * (a.ncoef + 1);
     for (int id = tid; id <= a.ncoef; id += UF_NTF) {
         cplx c = cmake(0.0, 0.0);
-        if (id < a.ncoef && !(a.abl & 8)) {
+        if (id < a.ncoef) {
             for (int t = 0; t < a.nterms; ++t) {
                 const int n = a.coef_lds ? cql[id * a.nterms + t] : a.coef_q[id * a.nterms + t];
                 if (n >= 0) cfma(c, a.coef_lds ? cvl[id * a.nterms + t] : a.coef_v[id * a.nterms + t], xl[n]);
@@ -335,7 +333,7 @@ __device__ __attribute__((always_inline)) inline void prop_ueg_body(const PropUe
     const int w = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lk = lane >> 4;
-    const int M = a.M, nt = a.nt, Mp = a.Mp, nrt = a.nrt, nks = a.nks;
+    const int M = a.M, nt = a.nt, nrt = a.nrt, nks = a.nks;
     // ---- LDS carve: coefficients | T | partial tiles
     cplx *coef = (cplx *)smem;                                                   // [ncoef + 1]
     unsigned char *Tb = smem + (((size_t)(a.ncoef + 1) * 16 + 15) & ~(size_t)15);   // [nks][1024]
@@ -639,7 +637,7 @@ int k_ueg_fast_propagator(afq_handle *h, const double *BH1) {
 
 int k_ueg_fast_supported(afq_handle *h) {
     UegFast *f = uf_of(h);
-    if (!f || h->kind != AFQ_SYS_UEG || h->no_fused) return 0;
+    if (!f || h->kind != AFQ_SYS_UEG) return 0;
     if (!f->elem_ok || !f->trial_ok || !f->bdiag_ok) return 0;
     if (h->ndet != 1 || h->rdm_on || h->psi_stride != 0 || h->nt > 16 || h->nb <= 0 || h->M > 112) return 0;
     if (!(h->flags & AFQ_PROP_HYBRID) || (h->flags & AFQ_PROP_FREE_PROJECTION)) return 0;
@@ -672,21 +670,13 @@ static int ueg_field_args(afq_handle *h, UegFieldArgs &a, FieldRng &rng, size_t 
     const size_t fb_bytes = (size_t)f->nfb * 16 + (((size_t)f->nfb + 3) & ~(size_t)3) * 4;
     const size_t ncq = (size_t)f->ncoef * f->nterms, cq_bytes = ncq * 16 + ((ncq + 3) & ~(size_t)3) * 4;
     a.nfb = f->nfb;
-    a.abl = AFQ_KNOB_INT("AFQ_UEG_ABL", 0);
     // (the work-group is alone on its CU: everything but 2 KB of the 160 KB for the kernel's static arrays may be used)
     const size_t cap = 158 * 1024;
-    a.fb_lds = lds + fb_bytes <= cap && !AFQ_KNOB_SET("AFQ_UEG_NO_TABLE_LDS");
+    a.fb_lds = lds + fb_bytes <= cap;
     if (a.fb_lds) lds += fb_bytes;
     live_end = lds;                     // what lies beyond is still read while the coefficients are written
-    a.coef_lds = lds + cq_bytes <= cap && !AFQ_KNOB_SET("AFQ_UEG_NO_TABLE_LDS");
+    a.coef_lds = lds + cq_bytes <= cap;
     if (a.coef_lds) lds += cq_bytes;
-#ifdef AFQ_TUNING
-    static bool said = false;
-    if (!said && AFQ_KNOB_SET("AFQ_UEG_SAY")) {
-        said = true;
-        fprintf(stderr, "ueg_fields: nrows %d nfb %d ncoef %d nterms %d lds %zu fb_lds %d coef_lds %d\n", f->nrows, f->nfb, f->ncoef, f->nterms, lds, a.fb_lds, a.coef_lds);
-    }
-#endif
     return AFQ_OK;
 }
 
@@ -748,7 +738,6 @@ int k_ueg_step(afq_handle *h) {
     FieldRng rng;
     PropUegArgs pa;
     size_t lds_f, live_end, lds_p;
-    if (AFQ_KNOB_SET("AFQ_UEG_NO_STEP_FUSION")) { const int rc = k_ueg_fields(h); return rc ? rc : k_prop_ueg(h); }
     const bool was_inline = h->rng_inline;
     int rc = ueg_field_args(h, fa, rng, lds_f, live_end);
     if (rc) return rc;

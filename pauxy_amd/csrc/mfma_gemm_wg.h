@@ -37,16 +37,6 @@ template <class P> struct gemm_conj_a<P, decltype((void)P::A_CONJ)> { static con
 template <class P, class = void> struct gemm_incr { static constexpr bool value = false; };
 template <class P> struct gemm_incr<P, decltype((void)P::INCR)> { static constexpr bool value = P::INCR; };
 
-#ifdef AFQ_TUNING
-// tuning builds: when set (hipMemcpyToSymbol), work-groups 0-63 of every ring GEMM leave their s_memtime phases here
-__device__ unsigned long long *afq_gemm_ts = nullptr;
-// tuning builds: timing ablations of the plain chunk loop (WRONG results): bit 0 no MFMAs, bit 1 no ring refill,
-// bit 2 no fragment reads, bit 3 no chunk barrier, bit 4 no output stores
-__device__ int afq_gemm_abl = 0;
-#define GEMM_UNLESS(bits) if (!(abl & (bits)))
-#else
-#define GEMM_UNLESS(bits)
-#endif
 // optional problem trait: static constexpr bool KCUT = true -- kcut(b, col0, ncols) is the contraction length the work-group
 // tile at columns [col0, col0 + ncols) of batch b needs (<= kdim; B is zero beyond it for these columns: triangular B)
 template <class P, class = void> struct gemm_kcut { static constexpr bool value = false; };
@@ -109,9 +99,6 @@ template <class P> struct gemm_incr_types<P, true> {
 // while the first sits at its chunk barrier or in its epilogue.
 template <int WM, int WN, int TM, int TN, int D, class P, int MAP, bool K3M = false, int KC = 1, int STAG = 0, int WPE = 1>
 __global__ __launch_bounds__(WM *WN * 64 * ((STAG == 3 || STAG == 5) ? 2 : 1), WPE) void mfma_gemm_wg_kernel(P p, const void *zero16) {
-#ifdef AFQ_TUNING
-    const unsigned long long ts0 = __builtin_amdgcn_s_memtime();
-#endif
     static_assert(P::A_CPLX, "A operand must be complex");
     static_assert(D == 2 || D == 4 || D == 8, "ring depth must be 2, 4 or 8");
     extern __shared__ __align__(16) unsigned char smem[];
@@ -355,20 +342,16 @@ __global__ __launch_bounds__(WM *WN * 64 * ((STAG == 3 || STAG == 5) ? 2 : 1), W
         mfma_step(sub, 1);
     };
 
-#ifdef AFQ_TUNING
-    const int abl = afq_gemm_abl;
-    const unsigned long long ts1 = __builtin_amdgcn_s_memtime(), tr1 = __builtin_amdgcn_s_memrealtime();
-#endif
     // STAG == 4: the ring is refilled THROUGH REGISTERS (global_load_dwordx4, ds_write_b128 one chunk later) instead of by
     // LDS-DMA.  A global_load ... lds instruction keeps its wave's instruction issue busy for 150+ cycles and only a few
     // MFMAs queue up ahead of it, so with one wave per SIMD the four refill instructions of a chunk idle the matrix pipe
     // for ~600 of its 1900 cycles (VhsProb at C3: SQ_WAIT_INST_LDS 1.5 % and zero bank conflicts -- it is not the LDS).
     // A plain load and a plain LDS store issue in a few cycles each; the price is 16 bytes of staging registers per
     // fragment and chunk in flight -- and only ONE chunk of latency tolerance (the loads of chunk c + D are waited for one
-    // iteration later, in program order ahead of half the MFMAs).  MEASURED NEGATIVE (round 3, VhsProb at C3, tuning knob
-    // AFQ_VHS_RREG): correct, 67.9 us against 61.5 us with the DMA ring; 63 % of that kernel's L2 accesses miss
+    // iteration later, in program order ahead of half the MFMAs).  MEASURED NEGATIVE (round 3, VhsProb at C3): correct,
+    // 67.9 us against 61.5 us with the DMA ring; 63 % of that kernel's L2 accesses miss
     // (TCC_MISS / (HIT + MISS), profiles/archive/r03_pmc_sq_tcp_bench_kernels.txt), so the three chunks the DMA ring keeps in
-    // flight matter more than the issue slots it costs.  Kept for tuning builds only.
+    // flight matter more than the issue slots it costs.  No launch uses it.
     if constexpr (STAG == 4) {
         static_assert(KC == 1 && gemm_incr<P>::value, "register-staged refill: incremental problems, one sub-chunk per slot");
         d2_t stgA[LPA], stgB[LPB];
@@ -421,10 +404,6 @@ __global__ __launch_bounds__(WM *WN * 64 * ((STAG == 3 || STAG == 5) ? 2 : 1), W
     }
     if constexpr (STAG == 4) {
     } else
-#ifdef AFQ_TUNING
-    if (STAG == 3 && (abl & 32) && !loader) __builtin_amdgcn_s_setprio(3);       // experiment: compute waves first
-    if (STAG == 3 && (abl & 64) && loader) __builtin_amdgcn_s_setprio(3);        // experiment: loader waves first
-#endif
     if (LOADERS && loader) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWAIT) : "memory");
         __builtin_amdgcn_s_barrier();
@@ -590,12 +569,9 @@ __global__ __launch_bounds__(WM *WN * 64 * ((STAG == 3 || STAG == 5) ? 2 : 1), W
     } else
     for (int c = 0; c < nchunks; ++c) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWAIT) : "memory");
-        GEMM_UNLESS(8)
         __builtin_amdgcn_s_barrier();
-        GEMM_UNLESS(2)
         issue(c + D - 1, (c + D - 1) & (D - 1));
         const unsigned sl0 = ring_l + (c & (D - 1)) * CHUNK;
-        GEMM_UNLESS(4)
         read_sub(sl0, 0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -603,7 +579,6 @@ __global__ __launch_bounds__(WM *WN * 64 * ((STAG == 3 || STAG == 5) ? 2 : 1), W
             read_sub(sl0, KC - 1);                         // in flight under the MFMAs of the first half
             __builtin_amdgcn_sched_barrier(0);
         }
-        GEMM_UNLESS(1)
         mfma_sub(0);
         if (KC == 2) {
             __builtin_amdgcn_sched_barrier(0);
@@ -612,9 +587,6 @@ __global__ __launch_bounds__(WM *WN * 64 * ((STAG == 3 || STAG == 5) ? 2 : 1), W
             mfma_sub(KC - 1);
         }
     }
-#ifdef AFQ_TUNING
-    const unsigned long long ts2 = __builtin_amdgcn_s_memtime(), tr2 = __builtin_amdgcn_s_memrealtime();
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (P::B_CPLX && K3M && !gemm_areal<P>::value && !gemm_breal<P>::value) {
 #pragma unroll
@@ -658,7 +630,6 @@ __global__ __launch_bounds__(WM *WN * 64 * ((STAG == 3 || STAG == 5) ? 2 : 1), W
             for (int r = 0; r < 4; ++r) {
                 const int row = wrow0 + i * 16 + lk + 4 * r;
                 const int col = wcol0 + j * 16 + lr;
-                GEMM_UNLESS(16)
                 if (row < p.rows && col < p.cols) p.store(b, row, col, accR[i][j][r], accI[i][j][r]);
             }
     if constexpr (gemm_coldot<P>::value) {
@@ -684,14 +655,6 @@ __global__ __launch_bounds__(WM *WN * 64 * ((STAG == 3 || STAG == 5) ? 2 : 1), W
         }
     }
     }
-#ifdef AFQ_TUNING
-    if (afq_gemm_ts && threadIdx.x == 0 && blockIdx.x < 64) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long ts3 = __builtin_amdgcn_s_memtime();
-        unsigned long long *o = afq_gemm_ts + blockIdx.x * 4;
-        o[0] = tr2 - tr1; o[1] = ts2 - ts1; o[2] = ts3 - ts2; o[3] = (unsigned long long)nchunks;
-    }
-#endif
 }
 
 // Flops the matrix pipe executes for one launch of the engine (what "issued" rooflines are priced on): every work-group

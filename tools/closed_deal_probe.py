@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The step kernels of an RHF run (closed-shell walkers) at M basis functions, N + N electrons, 256 walkers, K = 5 M:
-launch trace of 40 steps.  With the tuning build, AFQ_PF_NOCLOSED=1 / AFQ_NO_CLOSED_EXX=1 switch the closed-shell paths off.
+launch trace of 40 steps.
 Usage: python tools/closed_deal_probe.py M N"""
 import os
 import sys
