@@ -224,6 +224,9 @@ int afq_bp_update_ext(afq_handle *h, const double *phi_bp0, int nstblz, int rest
  *   unstable: Ggr(t+1) = B_t Ggr(t), Gls(t+1) = Gls(t) B_t^-1;
  *   spgf_out c128[nmax+1][2 spin][2: greater, lesser][M][M] = sum_w wfac_w Re G_w(t), denom_out c128 = sum_w wfac_w
  *   (walkers without a complete window count 0).  Then the history restarts and the window start is the walkers now.
+ *   The window is read-only on the walk: walkers, weights, overlaps, the cached Green's function the last step left
+ *   for the next one (Ghalf) and the full G the mixed one_rdm accumulates are what they were (the window's own Green's
+ *   functions live in its scratch), so a run with windows is bitwise the run without them.
  * AFQ_ESTATE before afq_itcf_configure; AFQ_ENOMEM when the stored psi_L
  * (16 nw nmax M (na+nb) bytes) exceed half of the free device memory.                                 */
 int afq_itcf_configure(afq_handle *h, int nmax, int neqlb, int stable, int restore_weights);

@@ -2101,24 +2101,31 @@ static int itcf_scratch(afq_handle *h, size_t n, cplx **out) {
     return AFQ_OK;
 }
 
-static int itcf_greens(afq_handle *h, cplx *psiR, cplx *psiL, cplx *psiLc, cplx *ovlp, cplx *P, cplx *Q) {
+static int itcf_greens(afq_handle *h, cplx *psiR, cplx *psiL, cplx *psiLc, cplx *ovlp, cplx *ghalf, cplx *G, cplx *P, cplx *Q) {
     // P = gab(psi_L, psi_R) per spin: the Green's function of psi_R with psi_L[w] in the role of the trial, as the
-    // back-propagated G of bp_update
+    // back-propagated G of bp_update.  Its Ghalf and G go to the window's own buffers: the handle's Ghalf is the walk's
+    // cached Green's function, which the next step and the next re-orthogonalisation reuse (and with it whatever was
+    // contracted from it: the version counters go back to where they were), and the handle's G is walker state of the
+    // mixed one_rdm (accumulated by every estimator update, carried by comb, copy and pack)
     const size_t per = (size_t)h->M * h->nt;
     int rc = k_conj_copy(h, psiL, psiLc, (long)(per * h->nw));
     if (rc) return rc;
-    cplx *s_phi = h->phi, *s_psi = h->psi, *s_psic = h->psic;
-    h->phi = psiR; h->psi = psiL; h->psic = psiLc; h->psi_stride = (long)per;
+    cplx *s_phi = h->phi, *s_psi = h->psi, *s_psic = h->psic, *s_ghalf = h->ghalf, *s_G = h->G;
+    const unsigned long long s_version = h->ghalf_version, s_checked = h->closed_checked_version;
+    h->phi = psiR; h->psi = psiL; h->psic = psiLc; h->psi_stride = (long)per; h->ghalf = ghalf; h->G = G;
     rc = k_greens(h, ovlp);
-    if (!rc) rc = ensure_G(h);
     if (!rc) rc = k_full_G(h);
-    h->phi = s_phi; h->psi = s_psi; h->psic = s_psic; h->psi_stride = 0;
+    h->phi = s_phi; h->psi = s_psi; h->psic = s_psic; h->psi_stride = 0; h->ghalf = s_ghalf; h->G = s_G;
+    h->ghalf_version = s_version; h->closed_checked_version = s_checked;
     if (rc) return rc;
-    return k_itcf_projectors(h, h->G, P, Q);
+    return k_itcf_projectors(h, G, P, Q);
 }
 
 int afq_itcf_update(afq_handle *h, const double *psi_T, int nstblz, double *spgf_out, double *denom_out) {
     AFQ_API(h, "afq_itcf_update");
+    // the window is read-only on the walk: the Green's function the last step left for the next one stays valid (a window
+    // that fails half way leaves it invalid, which only costs a recomputation)
+    const bool s_valid = h && h->greens_valid, s_gsum = h && h->gsum_only;
     if (h) { h->greens_valid = false; h->gsum_only = false; }
     if (!h || !psi_T || !spgf_out || !denom_out || nstblz < 1) return AFQ_EINVAL;
     int rc = need_ready(h, true);
@@ -2132,11 +2139,11 @@ int afq_itcf_update(afq_handle *h, const double *psi_T, int nstblz, double *spgf
     const int nkeep = stable ? nmax : 1;
     const bool gen = !h->hirsch;
     // scratch in complex units: psi_L, psi_R (x2), conj(psi_L), BT2^-1, B, B^-1, P, Q, Ggr, Gls, T, the Generic Taylor
-    // workspace and fields or the discrete diagonals, wfac, [denom | spgf], determinants (mantissa, exponent), overlaps
-    // and the parked ot / detR of the re-orthogonalisation
+    // workspace and fields or the discrete diagonals, wfac, [denom | spgf], determinants (mantissa, exponent), overlaps,
+    // the parked ot / detR of the re-orthogonalisation, the Ghalf and the G of the window's Green's functions
     const size_t sizes[] = {(size_t)nkeep * nw * per, nw * per, nw * per, nw * per, 2 * mm, g2, g2, g2, g2, g2, g2, g2,
                             gen ? 2 * nw * mm + g2 : 0, gen ? (size_t)nw * h->K : 2 * (size_t)nw * M, (size_t)nw,
-                            1 + nspgf, (size_t)nw + 2, (size_t)nw + 2, (size_t)nw, (size_t)nw, (size_t)nw};
+                            1 + nspgf, (size_t)nw + 2, (size_t)nw + 2, (size_t)nw, (size_t)nw, (size_t)nw, nw * per, g2};
     size_t total = 0;
     for (size_t x : sizes) total += x;
     {
@@ -2159,6 +2166,7 @@ int afq_itcf_update(afq_handle *h, const double *psi_T, int nstblz, double *spgf
     int *dete = (int *)part[17];
     cplx *ovlp = part[18], *tmp_ot = part[19];
     double *tmp_detR = (double *)part[20], *f = (double *)part[13];
+    cplx *wghalf = part[21], *wG = part[22];
     // BT2^-1 per spin
     AFQ_HIP(h, hipMemcpyAsync(BT2inv, h->BH1, sizeof(cplx) * 2 * mm, hipMemcpyDeviceToDevice, h->stream));
     if ((rc = k_gj_inverse(h, BT2inv, M, 2, detm, dete))) return rc;
@@ -2173,7 +2181,7 @@ int afq_itcf_update(afq_handle *h, const double *psi_T, int nstblz, double *spgf
     AFQ_HIP(h, hipMemcpyAsync(psiR, h->phi_old, sizeof(cplx) * nw * per, hipMemcpyDeviceToDevice, h->stream));
     for (int tau = 0; tau < nmax; ++tau) {
         if (stable || tau == 0) {
-            if ((rc = itcf_greens(h, psiR, psiL + (size_t)tau * nw * per, psiLc, ovlp, P, Q))) return rc;
+            if ((rc = itcf_greens(h, psiR, psiL + (size_t)tau * nw * per, psiLc, ovlp, wghalf, wG, P, Q))) return rc;
         }
         if (tau == 0) {
             AFQ_HIP(h, hipMemcpyAsync(Ggr, Q, sizeof(cplx) * g2, hipMemcpyDeviceToDevice, h->stream));
@@ -2219,6 +2227,7 @@ int afq_itcf_update(afq_handle *h, const double *psi_T, int nstblz, double *spgf
     if ((rc = k_bp_reset(h, false))) return rc;
     AFQ_HIP(h, hipMemcpyAsync(h->phi_old, h->phi, sizeof(cplx) * per * nw, hipMemcpyDeviceToDevice, h->stream));
     if ((rc = k_alive(h))) return rc;
+    h->greens_valid = s_valid; h->gsum_only = s_gsum;
     if ((rc = copy_out(h, denom_out, est, sizeof(cplx)))) return rc;
     return copy_out(h, spgf_out, est + 1, sizeof(cplx) * nspgf);
 }

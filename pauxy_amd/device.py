@@ -234,7 +234,8 @@ class AfqDevice(object):
         """One window -> (spgf_sum [nmax+1, 2, 2, M, M], denominator): sum_w wfac_w Re G_w(tau) and sum_w wfac_w."""
         psi = _c128(psi_T, (self.M, self.na + self.nb))
         M = self.M
-        spgf = numpy.zeros((self.itcf_nmax + 1, 2, 2, M, M), dtype=numpy.complex128)
+        # (before itcf_configure the library refuses with AFQ_ESTATE and writes nothing)
+        spgf = numpy.zeros((getattr(self, 'itcf_nmax', 0) + 1, 2, 2, M, M), dtype=numpy.complex128)
         den = numpy.zeros(1, dtype=numpy.complex128)
         self._ck(self.lib.afq_itcf_update(self.h, _p(psi), int(nstblz), _p(spgf), _p(den)))
         return spgf, den[0]

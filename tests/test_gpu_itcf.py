@@ -1,7 +1,9 @@
 """Imaginary-time Green's function on the device (afq_itcf_configure / afq_itcf_update, k_itcf.hip): walkers
-propagated on the device with fields from the test, their recorded histories replayed through the numpy restatement
-(tests/itcf_ref.py) and the device's window sums compared with it; the window's lesser function at tau = 0 against the
-back-propagated one-body RDM of the same history; a full AFQMC run that writes and reads back the estimator."""
+propagated on the device with fields from the test, their recorded histories replayed through the extended-precision
+restatement (tests/itcf_ref_ext.py) and the device's window sums compared with it under the rule of that module (a
+bound per case from the fp64 restatement's own distance to the extended one, per slice; every comparison prints its
+figures); the window's lesser function at tau = 0 against the back-propagated one-body RDM of the same history; a full
+AFQMC run that writes and reads back the estimator.  tests/test_gpu_itcf_shapes.py: the dispatch paths and sequences."""
 import numpy
 import pytest
 
@@ -9,36 +11,18 @@ from pauxy_amd import _lib as L, trial as trial_mod
 from pauxy_amd.qmc.afqmc import AFQMC
 from pauxy_amd.utils.io import extract_itcf
 from tests import itcf_ref
-from tests.itcf_models import generic_model, hirsch_device
+from tests.itcf_models import compare_window, generic_model, hirsch_device, restore_factors
 from tests.helpers import make_device
 from tests.test_gpu_traj import close
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-8
 
 
-def restore_factors(dev, psi, nstblz):
-    """weight_w (phase product / cosine product) per walker: the back-propagation's 'full' denominator of one walker."""
-    w0 = dev.get(L.F_WEIGHT).copy()
-    out = numpy.zeros(dev.nw, dtype=complex)
-    for i in range(dev.nw):
-        if w0[i] == 0:
-            continue
-        one = numpy.zeros(dev.nw)
-        one[i] = 1.0
-        dev.set(L.F_WEIGHT, one)
-        out[i] = w0[i] * dev.bp_update(psi, nstblz, 'full', reset=False)[1]
-    dev.set(L.F_WEIGHT, w0)
-    return out
-
-
-def check_window(dev, Bs_of, phi0, psi_T, na, nmax, nstblz, stable, wfac):
+def check_window(case, dev, kind, model, fields, phi0, psi_T, na, nmax, nstblz, stable, wfac, **kw):
+    """One afq_itcf_update against the extended restatement of the recorded histories, under the rule of
+    tests/itcf_ref_ext.py (a bound from the case's own fp64-against-extended error, per slice): compare_window."""
     spgf, den = dev.itcf_update(psi_T, nstblz)
-    wins = [itcf_ref.window(Bs_of(w), phi0[w], psi_T, na, nmax, nstblz, stable) if wfac[w] != 0 else None
-            for w in range(dev.nw)]
-    want = itcf_ref.accumulate(wins, wfac)
-    close(den, numpy.sum(wfac), 1e-12)
-    close(spgf, want, TOL)
+    compare_window(case, (spgf, den), kind, model, numpy.asarray(fields), phi0, psi_T, na, nmax, nstblz, stable, wfac, **kw)
     return spgf, den
 
 
@@ -62,11 +46,11 @@ def run_generic(M, K, na, nb, nw, nmax, neqlb, nstblz, stable, restore, dead=(),
     wfac = restore_factors(dev, model.psi, nstblz) if restore else dev.get(L.F_WEIGHT).astype(complex)
     for d in dead:
         assert wfac[d] == 0
-    BT2 = numpy.asarray(model.BH1)
-
-    def Bs_of(w):
-        return numpy.array([itcf_ref.b_generic(s.hs_pot, BT2, xs[t, w], model.dt) for t in range(nmax + neqlb)])
-    out = check_window(dev, Bs_of, phi0, model.psi, na, nmax, nstblz, stable, wfac)
+    case = "generic%s M=%d %d+%d nw=%d nmax=%d neqlb=%d nstblz=%d %s%s" % (
+        ' (H)' if hermitian else '', M, na, nb, nw, nmax, neqlb, nstblz, 'stable' if stable else 'unstable',
+        ' restore' if restore else '')
+    out = check_window(case, dev, 'generic', (numpy.asarray(s.hs_pot), numpy.asarray(model.BH1), model.dt), xs, phi0,
+                       model.psi, na, nmax, nstblz, stable, wfac)
     dev.close()
     return out
 
@@ -98,7 +82,8 @@ def test_stable_and_unstable_windows_agree():
     a, da = run_generic(16, 24, 5, 3, 7, 8, 0, 3, True, False)
     b, db = run_generic(16, 24, 5, 3, 7, 8, 0, 3, False, False)
     assert da == db
-    close(a, b, 1e-9)
+    print("ITCF-PAIR | stable vs unstable M=16 nw=7 nmax=8 | %.2e" % (numpy.max(numpy.abs(a - b)) / max(1.0, numpy.max(numpy.abs(b)))))
+    close(a, b, 2e-13)            # each is within bound(err_ref) of the extended restatement (1e-13 here: ITCF-CASE lines)
 
 
 @pytest.mark.parametrize("nx,na,nb,nw,nmax,neqlb,nstblz,stable", [
@@ -122,10 +107,9 @@ def test_hirsch_window_against_restatement(nx, na, nb, nw, nmax, neqlb, nstblz, 
     fields = numpy.array(fields)
     wfac = dev.get(L.F_WEIGHT).astype(complex)
     wfac[(fields < 0).any(axis=(0, 2))] = 0.0          # a walker that died inside the window has no complete history
-
-    def Bs_of(w):
-        return numpy.array([itcf_ref.b_hirsch(BT2, fields[t, w], dt, U) for t in range(nmax + neqlb)])
-    check_window(dev, Bs_of, phi0, psi, na, nmax, nstblz, stable, wfac)
+    case = "hirsch %dx%d %d+%d nw=%d nmax=%d neqlb=%d nstblz=%d %s" % (nx, nx, na, nb, nw, nmax, neqlb, nstblz,
+                                                                      'stable' if stable else 'unstable')
+    check_window(case, dev, 'hirsch', (BT2, dt, U), fields, phi0, psi, na, nmax, nstblz, stable, wfac)
     dev.close()
 
 
@@ -143,7 +127,9 @@ def test_lesser_function_at_zero_is_the_back_propagated_rdm():
     _, den_bp, G_bp = dev.bp_update(model.psi, 3, None, reset=False)
     spgf, den = dev.itcf_update(model.psi, 3)
     close(den, den_bp, 1e-12)
-    close(spgf[0, :, 1], G_bp.transpose(0, 2, 1).real, 1e-10)
+    want = G_bp.transpose(0, 2, 1).real
+    print("ITCF-PAIR | Gls(0) vs back-propagated RDM M=16 nw=9 | %.2e" % (numpy.max(numpy.abs(spgf[0, :, 1] - want)) / max(1.0, numpy.max(numpy.abs(want)))))
+    close(spgf[0, :, 1], want, 1e-13)     # the same kernels on the same history: the order of the rule at this shape
     dev.close()
 
 

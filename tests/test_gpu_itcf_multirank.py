@@ -83,6 +83,14 @@ def test_two_ranks_give_the_itcf_of_one_rank():
     steps = [s for s, _ in one['itcf']]
     assert steps == [4, 8, 12, 16, 20], steps
     assert [s for s, _ in a['itcf']] == steps and b['itcf'] == []
-    for (_, g1), (_, g2) in zip(one['itcf'], a['itcf']):
+    got_phi = numpy.concatenate([a['phi'], b['phi']])
+    print("ITCF-RANKS | walkers bitwise equal: %s (max difference %.2e)" % (numpy.array_equal(got_phi, one['phi']),
+                                                                          numpy.max(numpy.abs(got_phi - one['phi']))))
+    assert numpy.array_equal(got_phi, one['phi'])
+    for (step, g1), (_, g2) in zip(one['itcf'], a['itcf']):
+        print("ITCF-RANKS | window closing at step %d | two ranks vs one: %.2e" % (
+            step, numpy.max(numpy.abs(g2 - g1)) / max(1.0, numpy.max(numpy.abs(g1)))))
         assert g1.shape == g2.shape == (4, 2, 2, 12, 12) and numpy.isfinite(g1).all()
-        assert numpy.max(numpy.abs(g2 - g1)) <= 1e-9 * max(1.0, numpy.max(numpy.abs(g1)))
+        # mr.compare's walkers are bitwise those of one rank (asserted here), so the windows differ by the order of the
+        # sum over walkers alone: MARGIN x 1e-15 of tests/itcf_ref_ext.py
+        assert numpy.max(numpy.abs(g2 - g1)) <= 100 * 1e-15 * max(1.0, numpy.max(numpy.abs(g1)))
