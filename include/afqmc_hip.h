@@ -208,6 +208,30 @@ int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, co
 int afq_bp_ekt_chunks(afq_handle *h, int nc, int ncy);
 int afq_bp_update_ext(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
                       int reset, double *est_out, double *two_rdm_out, double *fock_out);
+/* The window of a multi-determinant trial |psi_T> = sum_d c_d |D_d> (afq_set_trial_multi; generic systems).  On such a
+ * handle afq_bp_configure sizes phi_bp for ndet determinants per walker and the window's scratch, and refuses with
+ * AFQ_ENOMEM (and the byte counts) when they exceed half of the free device memory.  The reference has no such window
+ * (its BackPropagation fails on ndets > 1); what is computed, per walker over its recorded fields x_1 .. x_n:
+ *   1. D_d^bp = B(x_1)^H .. B(x_n)^H D_d for every determinant, the operator and the re-orthogonalisation schedule of
+ *      afq_bp_update; the HS potential of a backward step is built once per walker, not once per determinant, and on
+ *      the GEMM chain the ndet determinants of a walker are one column-stacked operand [M, ndet (na+nb)].
+ *   2. A re-orthogonalisation replaces D by Q with D = Q R, diag R > 0.  With one determinant det R cancels between
+ *      numerator and denominator; with several it does not: log r_d = sum of log det R_alpha + log det R_beta over
+ *      the re-orthogonalisations is kept per (walker, d), and
+ *        w_d = conj(c_d) exp(log r_d - max_d' log r_d') det(Q_d,alpha^H phi_old,alpha) det(Q_d,beta^H phi_old,beta);
+ *      a w_d that is zero or not finite counts as zero, and a walker whose sum_d w_d is zero or not finite does not
+ *      contribute to numerator or denominator.
+ *   3. G_d = gab(Q_d, phi_old)^T per spin, G_bp[w] = sum_d w_d G_d / sum_d w_d.
+ *   4. est_out as afq_bp_update's: [E, E1b, E2b sums, sum_w wt_w, sum_w wt_w G_bp[w]] with the same wt_w; with
+ *      eval_energy E_w = sum_d w_d E[G_d] / sum_d w_d from the full-G Cholesky energy of every G_d (not E[G_bp]: the
+ *      two-body part is quadratic in G).
+ * dets c128[ndet, M, na+nb], coeffs c128[ndet]; ndet must be the handle's.  detw_out (may be NULL) c128[nw, ndet]:
+ * w_d / sum_d w_d per walker, the counterpart of afq_walkers_det_weights.  The window is read-only on the walk like
+ * afq_itcf_update's (its Green's functions live in its own scratch).  afq_bp_update on such a handle is the
+ * single-determinant window of phi_bp0 (init_walker).  AFQ_EUNSUPPORTED with a multi-determinant trial:
+ * afq_bp_observables (two-body RDM, EKT) and afq_itcf_configure.                                       */
+int afq_bp_update_msd(afq_handle *h, int ndet, const double *dets, const double *coeffs, int nstblz, int restore_weights,
+                      int eval_energy, int reset, double *est_out, double *detw_out);
 
 /* Imaginary-time single-particle Green's function (the ITCF estimator, estimators/itcf.py of the reference).
  * afq_itcf_configure: windows of n = nmax + neqlb steps (nmax >= 1, neqlb >= 0); sizes the field history of

@@ -98,6 +98,7 @@ SIGNATURES = {
     "afq_bp_observables": [_h, c_int, c_int, _dp, _dp, c_int],
     "afq_bp_ekt_chunks": [_h, c_int, c_int],
     "afq_bp_update_ext": [_h, _dp, c_int, c_int, c_int, c_int, _dp, _dp, _dp],
+    "afq_bp_update_msd": [_h, c_int, _dp, _dp, c_int, c_int, c_int, c_int, _dp, _dp],
     "afq_itcf_configure": [_h, c_int, c_int, c_int, c_int],
     "afq_itcf_update": [_h, _dp, c_int, _dp, _dp],
     "afq_local_energy_full_g": [_h, _dp, c_int, _dp],

@@ -107,6 +107,7 @@ void free_walkers(afq_handle *h) {
     dev_free(h->hs_fbfac);
     dev_free(h->bp_hist); dev_free(h->bp_n); dev_free(h->bp_flag); dev_free(h->bp_cos); dev_free(h->bp_ph);
     dev_free(h->phi_old); dev_free(h->phi_bp); dev_free(h->BH1dag); dev_free(h->bp_xs); dev_free(h->bp_est);
+    dev_free(h->bpm_ws); h->bpm_ws_len = 0;
     h->nbp = 0; dev_free(h->xbar); dev_free(h->xs);
     dev_free(h->bpo_h1); dev_free(h->bpo_L); dev_free(h->bpo_wt); dev_free(h->bpo_out); dev_free(h->bpo_ws);
     h->bpo_ws_len = 0; h->bpo_two = h->bpo_ekt = 0; h->bpo_nL = 0;
@@ -1875,11 +1876,15 @@ int afq_propagate_hirsch_free(afq_handle *h, const double *u, int32_t *fields_ou
 }
 
 // ---------------------------------------------------------------- back-propagation
+struct BpMsdWs;
+static size_t bp_msd_carve(afq_handle *h, cplx *base, BpMsdWs *ws);
+
 int afq_bp_configure(afq_handle *h, int nbp) {
     if (!h || nbp < 1) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;
-    if (h->ndet > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagation needs a single-determinant trial");
+    if (h->ndet > 1 && h->kind != AFQ_SYS_GENERIC)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagation of a multi-determinant trial: generic systems only");
     if (h->kind == AFQ_SYS_HUBBARD && !h->hirsch)
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagation of a Hubbard system: discrete fields only (the reference's propagation/hubbard.py:568-672 reads the history as 0 / 1 fields)");
     if (h->hirsch && h->K != h->M) AFQ_FAIL(h, AFQ_ESTATE, "discrete fields: one per site expected");
@@ -1887,14 +1892,33 @@ int afq_bp_configure(afq_handle *h, int nbp) {
     // the backward step reuses the forward one with fields -conj(x): B(x)^H only when every L_n^H == L_n
     if (h->hs_cplx == AFQ_HS_GENERAL)
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagation with non-Hermitian complex Cholesky vectors");
-    const size_t per = (size_t)h->M * h->nt, n = h->nw;
+    const size_t per = (size_t)h->M * h->nt, n = h->nw, nd = h->ndet > 1 ? h->ndet : 1;
+    size_t msd_ws = 0;
+    if (nd > 1) {
+        // the determinants' phi_bp (and conjugate) and the window's scratch are sized here, and checked first: a
+        // configuration that does not fit says so with the byte counts instead of failing at an allocation half way
+        msd_ws = bp_msd_carve(h, nullptr, nullptr);
+        size_t fr = 0, tot = 0;
+        hipSetDevice(h->device);
+        AFQ_HIP(h, hipMemGetInfo(&fr, &tot));
+        const double need = 16.0 * ((double)2 * per * n * nd + (double)msd_ws + (double)n * nbp * h->K);
+        if (need > 0.5 * (double)fr)
+            AFQ_FAIL(h, AFQ_ENOMEM, "back-propagation of " + std::to_string(nd) + " determinants: " +
+                                        std::to_string((unsigned long long)need) +
+                                        " bytes, more than half of the free device memory (" +
+                                        std::to_string((unsigned long long)fr) + " bytes)");
+    }
     if ((rc = dev_alloc(h, &h->bp_hist, n * nbp * h->K))) return rc;
     if ((rc = dev_alloc(h, &h->bp_n, n))) return rc;
     if ((rc = dev_alloc(h, &h->bp_flag, n))) return rc;
     if ((rc = dev_alloc(h, &h->bp_cos, n))) return rc;
     if ((rc = dev_alloc(h, &h->bp_ph, n))) return rc;
     if ((rc = dev_alloc(h, &h->phi_old, per * n))) return rc;
-    if ((rc = dev_alloc(h, &h->phi_bp, 2 * per * n))) return rc;        // phi_bp and conj(phi_bp)
+    if ((rc = dev_alloc(h, &h->phi_bp, 2 * per * n * nd))) return rc;   // phi_bp and conj(phi_bp), of every determinant
+    if (nd > 1) {
+        if ((rc = dev_alloc(h, &h->bpm_ws, msd_ws))) return rc;
+        h->bpm_ws_len = msd_ws;
+    }
     if ((rc = dev_alloc(h, &h->BH1dag, (size_t)2 * h->M * h->M))) return rc;
     if ((rc = dev_alloc(h, &h->bp_xs, n * h->K))) return rc;
     if ((rc = dev_alloc(h, &h->bp_est, (size_t)4 + 2 * h->M * h->M))) return rc;
@@ -2027,6 +2051,132 @@ int afq_bp_update_ext(afq_handle *h, const double *phi_bp0, int nstblz, int rest
     return bp_update(h, phi_bp0, nstblz, restore_weights, eval_energy, reset, est_out, two_rdm_out, fock_out);
 }
 
+// ---- multi-determinant windows (k_bp_msd.hip)
+struct BpMsdWs {
+    cplx *dets, *coeffs, *ot, *ovlp, *detw, *S, *fac, *ghalf, *G, *gsum, *E, *esum, *stack;
+    double *logr, *detR;
+};
+
+// the window's scratch of an ndet-determinant handle in complex units; with base, the pointers into it
+static size_t bp_msd_carve(afq_handle *h, cplx *base, BpMsdWs *ws) {
+    const size_t n = h->nw, nd = h->ndet, per = (size_t)h->M * h->nt, g2 = (size_t)2 * h->M * h->M * n;
+    const size_t half = (nd * n + 1) / 2;                  // nd n doubles
+    // the column-stacked products keep one more copy of the determinants (the fused propagator works in place)
+    const size_t stack = k_prop_fused_supported(h) ? 0 : nd * n * per;
+    const size_t sizes[] = {nd * per, nd, n, nd * n, n * nd, n, 2 * n, n * per, g2, g2, 3 * n, 3 * n, stack, half, half};
+    size_t off = 0;
+    cplx *part[sizeof(sizes) / sizeof(sizes[0])];
+    for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); off += sizes[i], ++i) part[i] = base ? base + off : nullptr;
+    if (ws) {
+        ws->dets = part[0]; ws->coeffs = part[1]; ws->ot = part[2]; ws->ovlp = part[3]; ws->detw = part[4]; ws->S = part[5];
+        ws->fac = part[6]; ws->ghalf = part[7]; ws->G = part[8]; ws->gsum = part[9]; ws->E = part[10]; ws->esum = part[11];
+        ws->stack = part[12]; ws->logr = (double *)part[13]; ws->detR = (double *)part[14];
+    }
+    return off;
+}
+
+// phi_bp[d, w] <- B(x_0)^H ... B(x_{n-1})^H phi_bp[d, w] for every determinant d: bp_backward with ONE field set and ONE
+// HS potential per walker and step.  Fused propagator: the determinants' slabs one after the other over that V; GEMM
+// chain: the determinants of a walker as one column-stacked operand (k_bp_msd_onebody / k_bp_msd_taylor).  After a
+// re-orthogonalisation log det R of every (d, w) is added to logr [ndet, nw].
+static int bp_backward_msd(afq_handle *h, int nstblz, const BpMsdWs &ws) {
+    const size_t n = h->nw, per = (size_t)h->M * h->nt, nd = h->ndet, slab = n * per;
+    cplx *s_phi = h->phi, *s_xs = h->xs, *s_BH1 = h->BH1, *s_ot = h->ot;
+    double *s_detR = h->detR;
+    const int s_flags = h->flags;
+    h->xs = h->bp_xs; h->BH1 = h->BH1dag; h->ot = ws.ot;
+    h->flags &= ~AFQ_PROP_FREE_PROJECTION;
+    const bool fused = k_prop_fused_supported(h);
+    cplx *A = h->phi_bp, *B = ws.stack, *C = h->phi_bp + nd * slab;     // (the conjugates' half is free until the end)
+    int rc = AFQ_OK;
+    for (int i = 0; i < h->nbp && !rc; ++i) {
+        if ((rc = k_bp_fields(h, i))) break;
+        h->vhs_upper = fused && h->hs_sym;
+        rc = build_vhs(h);
+        if (!rc && fused)
+            for (size_t d = 0; d < nd && !rc; ++d) { h->phi = A + d * slab; rc = k_prop_fused(h); }
+        h->vhs_upper = false;
+        if (rc) break;
+        if (!fused) {
+            if ((rc = k_bp_msd_onebody(h, (int)nd, A, B))) break;
+            if ((rc = k_bp_msd_taylor(h, (int)nd, h->vhs, B, C, A))) break;
+            if ((rc = k_bp_msd_onebody(h, (int)nd, B, A))) break;
+        }
+        if (i != 0 && i % nstblz == 0) {
+            for (size_t d = 0; d < nd && !rc; ++d) {
+                h->phi = A + d * slab; h->detR = ws.detR + d * n;
+                rc = k_reortho(h);
+            }
+            if (!rc) rc = k_bp_msd_logr(h, ws.detR, ws.logr, (long)(nd * n));
+        }
+    }
+    h->phi = s_phi; h->xs = s_xs; h->BH1 = s_BH1; h->ot = s_ot; h->detR = s_detR; h->flags = s_flags;
+    return rc;
+}
+
+int afq_bp_update_msd(afq_handle *h, int ndet, const double *dets, const double *coeffs, int nstblz, int restore_weights,
+                      int eval_energy, int reset, double *est_out, double *detw_out) {
+    AFQ_API(h, "afq_bp_update_msd");
+    // read-only on the walk, as afq_itcf_update: the Green's function the last step left for the next one stays valid
+    const bool s_valid = h && h->greens_valid, s_gsum = h && h->gsum_only;
+    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (!h || !dets || !coeffs || !est_out || ndet < 1 || nstblz < 1 || restore_weights < 0 || restore_weights > 2)
+        return AFQ_EINVAL;
+    int rc = need_ready(h, true);
+    if (rc) return rc;
+    if (!h->nbp) AFQ_FAIL(h, AFQ_ESTATE, "back-propagation is not configured");
+    if (h->ndet <= 1 || !h->bpm_ws)
+        AFQ_FAIL(h, AFQ_ESTATE, "afq_bp_update_msd: the handle holds a single-determinant trial (afq_bp_update)");
+    if (ndet != h->ndet)
+        AFQ_FAIL(h, AFQ_EINVAL, "afq_bp_update_msd: " + std::to_string(ndet) + " determinants, the history was configured for " +
+                                    std::to_string(h->ndet));
+    const size_t per = (size_t)h->M * h->nt, n = h->nw, nd = ndet, slab = n * per, gsz = (size_t)2 * h->M * h->M;
+    BpMsdWs ws;
+    bp_msd_carve(h, h->bpm_ws, &ws);
+    AFQ_HIP(h, hipMemcpyAsync(ws.dets, dets, sizeof(cplx) * nd * per, hipMemcpyHostToDevice, h->stream));
+    AFQ_HIP(h, hipMemcpyAsync(ws.coeffs, coeffs, sizeof(cplx) * nd, hipMemcpyHostToDevice, h->stream));
+    AFQ_HIP(h, hipMemsetAsync(ws.logr, 0, sizeof(double) * nd * n, h->stream));
+    {   // every walker starts from D_d in slab d (k_bp_init fills the nw walkers phi_bp points at)
+        cplx *s_bp = h->phi_bp;
+        for (size_t d = 0; d < nd && !rc; ++d) { h->phi_bp = s_bp + d * slab; rc = k_bp_init(h, ws.dets + d * per); }
+        h->phi_bp = s_bp;
+        if (rc) return rc;
+    }
+    if ((rc = bp_backward_msd(h, nstblz, ws))) return rc;
+    // G_d[w] = gab(Q_d, phi_old)^T and <Q_d|phi_old> with Q_d[w] in the role of the trial, determinant by determinant
+    // into the window's own Ghalf / G; every handle field that is lent goes back, version counters included
+    cplx *conj_bp = h->phi_bp + nd * slab;
+    if ((rc = k_conj_copy(h, h->phi_bp, conj_bp, (long)(nd * slab)))) return rc;
+    if (eval_energy && h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagated energies: generic systems only");
+    {
+        cplx *s_phi = h->phi, *s_psi = h->psi, *s_psic = h->psic, *s_ghalf = h->ghalf, *s_G = h->G;
+        const unsigned long long s_version = h->ghalf_version, s_checked = h->closed_checked_version;
+        h->phi = h->phi_old; h->psi_stride = (long)per; h->ghalf = ws.ghalf; h->G = ws.G;
+        for (size_t d = 0; d < nd && !rc; ++d) {
+            h->psi = h->phi_bp + d * slab; h->psic = conj_bp + d * slab;
+            rc = k_greens(h, ws.ovlp + d * n);
+            if (!rc) rc = k_full_G(h);
+            if (!rc && eval_energy) rc = k_energy_full_g(h, ws.G, h->nw, ws.E);     // E[G_d], not E[G_bp]: quadratic in G
+            if (!rc) rc = k_bp_msd_detw(h, ndet, (int)d, ws.coeffs, ws.logr, ws.ovlp, ws.detw, ws.S);
+            if (!rc) rc = k_bp_msd_gsum(h, ndet, (int)d, ws.detw, ws.G, ws.gsum, eval_energy ? ws.E : nullptr, ws.esum);
+        }
+        h->phi = s_phi; h->psi = s_psi; h->psic = s_psic; h->psi_stride = 0; h->ghalf = s_ghalf; h->G = s_G;
+        h->ghalf_version = s_version; h->closed_checked_version = s_checked;
+        if (rc) return rc;
+    }
+    AFQ_HIP(h, hipMemsetAsync(h->bp_est, 0, sizeof(cplx) * (4 + gsz), h->stream));
+    if ((rc = k_bp_msd_finish(h, ndet, restore_weights, ws.detw, ws.S, ws.fac))) return rc;
+    if ((rc = k_bp_msd_accumulate(h, ws.gsum, ws.fac, eval_energy ? ws.esum : nullptr, h->bp_est))) return rc;
+    if (reset) {
+        if ((rc = k_bp_reset(h, false))) return rc;
+        AFQ_HIP(h, hipMemcpyAsync(h->phi_old, h->phi, sizeof(cplx) * per * n, hipMemcpyDeviceToDevice, h->stream));
+    }
+    if ((rc = k_alive(h))) return rc;
+    h->greens_valid = s_valid; h->gsum_only = s_gsum;
+    if ((rc = copy_out(h, detw_out, ws.detw, sizeof(cplx) * n * nd))) return rc;
+    return copy_out(h, est_out, h->bp_est, sizeof(cplx) * (4 + gsz));
+}
+
 int afq_bp_ekt_chunks(afq_handle *h, int nc, int ncy) {
     if (!h || nc < 0 || ncy < 0) return AFQ_EINVAL;
     h->bpo_nc = nc; h->bpo_ncy = ncy;
@@ -2040,6 +2190,8 @@ int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, co
     if (!h || (ekt && (!h1 || nL < 1 || (L == nullptr && nL != h->K)))) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;
+    if (h->ndet > 1 && (two_rdm || ekt))
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagated two-body RDM / EKT with a multi-determinant trial (sum_d w_d f[G_d] of quartic / cubic forms)");
     if (!h->nbp) AFQ_FAIL(h, AFQ_ESTATE, "back-propagation is not configured: afq_bp_configure first");
     if (ekt && h->kind == AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "EKT: the Hubbard model has no Cholesky vectors");
     if (ekt && !L && h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EINVAL, "EKT: pass the vectors L_x of this system");
@@ -2078,12 +2230,12 @@ int afq_itcf_configure(afq_handle *h, int nmax, int neqlb, int stable, int resto
     if (h->kind == AFQ_SYS_UEG) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "ITCF: no propagator matrix for the UEG (itcf.py:114-122)");
     if (h->hirsch && restore_weights)
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "restore_weights with discrete fields: FieldConfig.push records no weight factors (walkers/stack.py:35-49)");
+    if (h->ndet > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "ITCF: multi-determinant trials");
     const int n = nmax + neqlb;
     if (h->nbp && h->nbp != n)
         AFQ_FAIL(h, AFQ_ESTATE, "ITCF: a field history of " + std::to_string(h->nbp) + " steps is configured, the window needs " +
                                     std::to_string(n));
-    // (afq_bp_configure refuses multi-determinant trials, continuous Hubbard fields, free projection and general
-    //  complex Cholesky vectors)
+    // (afq_bp_configure refuses continuous Hubbard fields, free projection and general complex Cholesky vectors)
     if (!h->nbp && (rc = afq_bp_configure(h, n))) return rc;
     h->it_nmax = nmax; h->it_neqlb = neqlb; h->it_stable = stable ? 1 : 0; h->it_restore = restore_weights ? 1 : 0;
     return AFQ_OK;

@@ -172,6 +172,10 @@ struct afq_handle {
     cplx *BH1dag = nullptr;         // [2, M, M] BH1^H
     cplx *bp_xs = nullptr;          // [nw, K]
     cplx *bp_est = nullptr;         // [4 + 2 M M]
+    // multi-determinant windows (afq_bp_update_msd, k_bp_msd.hip): with ndet > 1 phi_bp holds [ndet, nw, M, nt] and its
+    // conjugate behind it, and bpm_ws the window's own scratch (carved by afq_bp_update_msd), bpm_ws_len complex elements
+    cplx *bpm_ws = nullptr;
+    size_t bpm_ws_len = 0;
     // back-propagated two-body RDM / EKT Fock matrices (afq_bp_observables, k_bp_obs.hip)
     int bpo_two = 0, bpo_ekt = 0;   // what afq_bp_update_ext may be asked for
     int bpo_nL = 0;                 // EKT vectors L_x, x < nL
@@ -478,6 +482,16 @@ int k_conj_transpose(afq_handle *h, const cplx *A, cplx *At);
 int k_bp_accumulate(afq_handle *h, int restore, int with_energy);
 int k_bp_reset(afq_handle *h, bool first);
 int k_bp_hirsch_step(afq_handle *h, int i);                 // B(x)^H of the i-th most recent discrete configuration
+// k_bp_msd.hip: the backward pass and the determinant-weighted sums of a multi-determinant window (afq_bp_update_msd).
+// The column-stacked products take phi as [ndet, nw, M, nt] and every walker's BH1^H / V once for its ndet nt columns.
+int k_bp_msd_onebody(afq_handle *h, int ndet, const cplx *src, cplx *dst);              // dst[d, w] = BH1[s] src[d, w]
+int k_bp_msd_taylor(afq_handle *h, int ndet, const cplx *vhs, cplx *phi, cplx *t0, cplx *t1);   // phi <- sum_n V^n / n! phi
+int k_bp_msd_logr(afq_handle *h, const double *detR, double *logr, long n);            // logr += log det R
+int k_bp_msd_detw(afq_handle *h, int ndet, int d, const cplx *coeffs, const double *logr, const cplx *ovlp, cplx *detw,
+                  cplx *S);                                                            // w_d and S (+)= w_d
+int k_bp_msd_gsum(afq_handle *h, int ndet, int d, const cplx *detw, const cplx *G, cplx *gsum, const cplx *E, cplx *esum);
+int k_bp_msd_finish(afq_handle *h, int ndet, int restore, cplx *detw, const cplx *S, cplx *fac);
+int k_bp_msd_accumulate(afq_handle *h, const cplx *gsum, const cplx *fac, const cplx *esum, cplx *est);
 int k_xbar_fields(afq_handle *h, cplx *hubbard_factors = nullptr);   // + the Hubbard row-scaling factors (continuous fields)
 int k_msd_combine(afq_handle *h, cplx *det_out, bool skip_small);          // detd -> detw, det_out = sum_d detw
 int k_msd_energy_combine(afq_handle *h);                   // energy_all, detw -> energy                                  // vbias / G -> xbar (unclipped), system dispatch

@@ -223,6 +223,21 @@ class AfqDevice(object):
             extra['fock_1p'], extra['fock_1h'] = fock[0], fock[1]
         return out[:3], out[3], out[4:].reshape(2, M, M), extra
 
+    def bp_update_msd(self, dets, coeffs, nstblz, restore_weights=None, eval_energy=False, reset=True):
+        """The window of a multi-determinant trial (afq_bp_update_msd): dets [ndet, M, na+nb], coeffs [ndet] ->
+        (energies_sum[3], denominator, G_bp_sum[2, M, M], detw[nw, ndet]) with detw = w_d / sum_d w_d per walker."""
+        mode = {None: 0, 'partial': 1, 'full': 2}.get(restore_weights, 1)
+        dets = _c128(dets)
+        ndet = dets.shape[0]
+        dets = _c128(dets, (ndet, self.M, self.na + self.nb))
+        coeffs = _c128(coeffs, (ndet,))
+        M = self.M
+        out = numpy.zeros(4 + 2 * M * M, dtype=numpy.complex128)
+        detw = numpy.zeros((self.nw, ndet), dtype=numpy.complex128)
+        self._ck(self.lib.afq_bp_update_msd(self.h, int(ndet), _p(dets), _p(coeffs), int(nstblz), mode,
+                                            int(bool(eval_energy)), int(bool(reset)), _p(out), _p(detw)))
+        return out[:3], out[3], out[4:].reshape(2, M, M), detw
+
     # ---- imaginary-time Green's function
     def itcf_configure(self, nmax, neqlb=0, stable=True, restore_weights=False):
         """afq_itcf_configure: windows of nmax + neqlb steps on the field history (sized here when none is set)."""

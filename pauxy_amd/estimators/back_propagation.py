@@ -1,7 +1,10 @@
 """Back-propagated estimator on the device, behind PAUXY's ``BackPropagation`` surface.
 
 Mirrors pauxy/estimators/back_propagation.py:63-326 for RHF/UHF-type single-determinant
-trials on a Generic, UEG or (discrete-field) Hubbard system: same constructor signature and attributes (``tau_bp``,
+trials on a Generic, UEG or (discrete-field) Hubbard system, and for multi-determinant (NOMSD) trials on a Generic
+system (``afq_bp_update_msd``: every determinant back-propagated, weighted by conj(c_d), its overlap with the walker at
+the window's start and the norms its re-orthogonalisations took out; the reference itself fails on ``ndets > 1``, and
+``two_rdm`` / ``evaluate_ekt`` are refused with it): same constructor signature and attributes (``tau_bp``,
 ``nmax``, ``splits``, ``calc_one_rdm``, ``restore_weights``, ``init_walker``), same
 ``update`` / ``print_step`` / ``zero`` methods.  The field history (walkers/stack.py
 FieldConfig), ``phi_old`` and the back-propagation itself live on the device
@@ -38,8 +41,13 @@ class BackPropagation(object):
         self.eval_energy = bp.get('evaluate_energy', False)
         self.eval_ekt = bp.get('evaluate_ekt', False)
         self.restore_weights = bp.get('restore_weights', None)
-        if system.name not in ("Generic", "UEG", "Hubbard") or getattr(trial, 'ndets', 1) != 1:
-            raise NotImplementedError("device back-propagation: Generic, UEG or Hubbard system, single-determinant trial")
+        ndets = int(getattr(trial, 'ndets', 1))           # (not kept: the attributes are the reference's)
+        if system.name not in ("Generic", "UEG", "Hubbard") or (ndets != 1 and system.name != "Generic"):
+            raise NotImplementedError("device back-propagation: Generic, UEG or Hubbard system; multi-determinant "
+                                      "trials on Generic systems")
+        if ndets != 1 and (self.calc_two_rdm is not None or self.eval_ekt):
+            # sum_d w_d f[G_d] of forms quartic / cubic in G_d: not the one-body sums of afq_bp_update_msd
+            raise NotImplementedError("back-propagated two_rdm / evaluate_ekt with a multi-determinant trial")
         if system.name == "Hubbard" and self.restore_weights is not None:
             # back_propagation.py:117-125: the Hubbard variant back-propagates the DISCRETE fields, which are recorded
             # without weight factors (hubbard.py:215-216, walkers/stack.py:35-49); afq_bp_configure refuses the
@@ -102,6 +110,19 @@ class BackPropagation(object):
         dev = psi.dev
         buff_ix = int(dev.bp_steps()[0])
         if buff_ix not in self.splits:
+            return
+        if getattr(trial, 'ndets', 1) != 1 and not self.init_walker:
+            # |psi_T> = sum_d c_d |D_d>: every determinant is back-propagated, weighted by conj(c_d) and its overlap
+            # with the walker at the window's start, norms of the re-orthogonalisations included (afq_bp_update_msd)
+            energies, denom, G, _ = dev.bp_update_msd(numpy.asarray(trial.psi), numpy.asarray(trial.coeffs), self.nstblz,
+                                                      self.restore_weights, self.eval_energy,
+                                                      reset=bool(buff_ix == self.splits[-1]))
+            self.estimates[:self.nreg] += energies
+            self.estimates[self.nreg] += denom
+            self.estimates[self.nreg + 1:self.nreg + 1 + G.size] += G.ravel()
+            psi._greens_version = -1
+            self.accumulated = True
+            self.buff_ix = buff_ix
             return
         phi0 = numpy.asarray(trial.init if self.init_walker else trial.psi, dtype=numpy.complex128)
         if phi0.ndim == 3:
