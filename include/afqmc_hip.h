@@ -158,6 +158,17 @@ int afq_hirsch_finish(afq_handle *h, double eshift);
  * dispatches to when no half-rotated Ghalf is given): G c128[n, 2, M, M] -> E c128[n, 3] = (E, E1b, E2b).
  * O(M^3 K) per Green's function; not on the per-step path.                                       */
 int afq_local_energy_full_g(afq_handle *h, const double *G, int n, double *E_out);
+/* The UEG energy's pair sums on FULL, general Green's functions, kept per momentum transfer (estimators/ueg.py:27-88,
+ * local_energy_ueg(system, G, two_rdm=...)): G c128[n, 2, M, M] -> E c128[n, 3] = (E, E1b, E2b) without ecore (as
+ * afq_local_energy on a UEG handle) and two_rdm c128[n, 2, 2, nq],
+ *   two_rdm[s,s,q] = Gkpq[s,q] Gpmq[s,q] - Gprod[s,q],  two_rdm[s,t,q] = Gkpq[s,q] Gpmq[t,q] (s != t),
+ * with the index lists the handle was given (any rows, any lengths, empty lists included); E2b = 1 / (2 vol) sum_q
+ * vqvec[q] sum_st two_rdm[s,t,q].  Nothing is assumed about G (no zero rows).  Same input, same bits.  UEG handles
+ * only (AFQ_EUNSUPPORTED); M < 65536.
+ * afq_hubbard_energy_full_g: estimators/hubbard.py:93-114 on full Green's functions, ke = sum_s sum_ij T_s[i,j] G_s[i,j],
+ * pe = U sum_i G_a[i,i] G_b[i,i]; Hubbard handles only.                                                        */
+int afq_ueg_pair_sums(afq_handle *h, const double *G, int n, double *E_out, double *two_rdm_out);
+int afq_hubbard_energy_full_g(afq_handle *h, const double *G, int n, double *E_out);
 
 /* ---- back-propagated estimator --------------------------------
  * estimators/back_propagation.py:63-226, walkers/stack.py:5-127 (FieldConfig),
@@ -184,7 +195,8 @@ int afq_bp_steps(afq_handle *h, int32_t *steps_out);
  * then, when `reset` is set (the last of the nsplit path lengths, back_propagation.py:68-69,219-222), resets the
  * histories and copies phi -> phi_old.  Generic systems (propagation/generic.py:253-290) and the UEG
  * (propagation/planewave.py:114-178; B(x)^H = B(-conj x) for both).  With eval_energy the entries 0-2 are
- * sum_w wt_w (E, E1b, E2b)[G_bp[w]] from the full-G Cholesky energy (generic systems).          */
+ * sum_w wt_w (E, E1b, E2b)[G_bp[w]]: the full-G Cholesky energy (generic systems), local_energy_hubbard on G_bp
+ * (Hubbard, discrete fields), the pair sums of afq_ueg_pair_sums on G_bp (UEG; ecore not included).            */
 int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
                   int reset, double *est_out);
 /* Back-propagated two-body RDM and extended Koopmans' theorem (EKT) Fock matrices (estimators/back_propagation.py:
@@ -198,7 +210,11 @@ int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_
  *            L = NULL with complex vectors (afq_set_system_generic_c128).
  * The hot path is k_bp_obs.hip: the EKT quadratic terms in rank-N form from the factors of G_bp (phi_bp and the
  * half-rotated G_bp), the terms linear in G once per window on sum_w wt_w G_bp[w]; the two-body RDM as one MFMA GEMM
- * per (p, q) over the stacked walker contraction.                                                   */
+ * per (p, q) over the stacked walker contraction.
+ *   two_rdm = 2  (UEG handles only, AFQ_EUNSUPPORTED elsewhere) the structure factor instead: afq_bp_update_ext's
+ *            two_rdm_out then is c128[2, 2, nq] = sum_w wt_w two_rdm[G_bp[w]] of afq_ueg_pair_sums, walkers summed in
+ *            index order (no atomics: the same bits on every run); walkers of weight zero contribute nothing.
+ *            Evaluated with or without eval_energy.                                                    */
 int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, const double *L, int nL);
 /* afq_bp_update plus, where the pointers are not NULL, two_rdm_out c128[M^4] = sum_w wt_w two_rdm[G_bp[w]] and
  * fock_out c128[2, M, M] = sum_w wt_w (F1p, F1h)[G_bp[w]] with the weights of est_out (complex with restore_weights).
@@ -462,6 +478,14 @@ int afq_estimates_update(afq_handle *h, int eval_energy);
  * walker.G travels with a walker cloned to another rank (exchange slot, afq_walker_pack) and afq_estimates_allreduce
  * reduces the accumulator along with the ten estimators (the reference keeps them in one vector, mixed.py:261).  */
 int afq_estimates_rdm(afq_handle *h, int on);
+/* Mixed estimator with two_rdm: 'structure_factor' (estimators/mixed.py:103-108,230-233): after afq_estimates_sf(h, 1)
+ * every afq_estimates_update that evaluates the energy also adds sum_w weight_w Re two_rdm[G_w] (afq_ueg_pair_sums on
+ * the walkers' mixed Green's functions) to a device accumulator f64[2, 2, nq]: weight_w is the factor that multiplies the
+ * walker's energy in ENumer in that same update, so that accumulator / EDenom is the energy's own estimator per
+ * momentum transfer.  UEG, single determinant, importance sampling (AFQ_EUNSUPPORTED otherwise).
+ * afq_estimates_sf_get returns (and optionally zeroes) the accumulator.                                        */
+int afq_estimates_sf(afq_handle *h, int on);
+int afq_estimates_sf_get(afq_handle *h, double *sf_out /* f64[2, 2, nq] */, int zero);
 int afq_estimates_rdm_get(afq_handle *h, double *rdm_out /* f64[2, M, M] */, int zero);
 /* Synchronises the stream; also the place where a population that collapsed in an asynchronous comb is
  * reported (AFQ_EWEIGHT, walkers/handler.py:236-241) and an exchange overflow (AFQ_EOVERFLOW).           */

@@ -76,6 +76,8 @@ SIGNATURES = {
     "afq_estimates_get_end": [_h, _dp],
     "afq_estimates_rdm": [_h, c_int],
     "afq_estimates_rdm_get": [_h, _dp, c_int],
+    "afq_estimates_sf": [_h, c_int],
+    "afq_estimates_sf_get": [_h, _dp, c_int],
     "afq_rng_seed": [_h, c_uint64, c_uint64],
     "afq_counters": [_h, c_void_p, c_int],
     "afq_counters_ext": [_h, c_void_p, c_int, c_int],
@@ -102,6 +104,8 @@ SIGNATURES = {
     "afq_itcf_configure": [_h, c_int, c_int, c_int, c_int],
     "afq_itcf_update": [_h, _dp, c_int, _dp, _dp],
     "afq_local_energy_full_g": [_h, _dp, c_int, _dp],
+    "afq_ueg_pair_sums": [_h, _dp, c_int, _dp, _dp],
+    "afq_hubbard_energy_full_g": [_h, _dp, c_int, _dp],
     "afq_set_trial_multi": [_h, c_int, _dp, _dp, _dp],
     "afq_walkers_det_weights": [_h, _dp],
     "afq_rng_normal": [_h, _dp, c_int64],

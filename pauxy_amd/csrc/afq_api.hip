@@ -84,6 +84,8 @@ void free_system(afq_handle *h) {
     dev_free(h->H1); dev_free(h->rH1);
     dev_free(h->iA_colptr); dev_free(h->iA_row); dev_free(h->iA_val); dev_free(h->ell_row); dev_free(h->ell_val); dev_free(h->ueg_rmap); dev_free(h->ueg_rows);
     dev_free(h->ueg_kp); dev_free(h->ueg_pm); dev_free(h->ueg_koff); dev_free(h->ueg_poff);
+    dev_free(h->sf_kp); dev_free(h->sf_pm); dev_free(h->sf_order); h->sf_nlong = 0;
+    dev_free(h->sf_ws); dev_free(h->sf_two); h->sf_ws_len = h->sf_two_len = 0;
     dev_free(h->iB_colptr); dev_free(h->iB_row); dev_free(h->iB_val);
     dev_free(h->iA_rowptr); dev_free(h->iA_col); dev_free(h->iA_rval);
     dev_free(h->iB_rowptr); dev_free(h->iB_col); dev_free(h->iB_rval);
@@ -110,12 +112,13 @@ void free_walkers(afq_handle *h) {
     dev_free(h->bpm_ws); h->bpm_ws_len = 0;
     h->nbp = 0; dev_free(h->xbar); dev_free(h->xs);
     dev_free(h->bpo_h1); dev_free(h->bpo_L); dev_free(h->bpo_wt); dev_free(h->bpo_out); dev_free(h->bpo_ws);
-    h->bpo_ws_len = 0; h->bpo_two = h->bpo_ekt = 0; h->bpo_nL = 0;
+    h->bpo_ws_len = 0; h->bpo_two = h->bpo_ekt = h->bpo_sf = 0; h->bpo_nL = 0;
     dev_free(h->it_ws); h->it_ws_len = 0; h->it_nmax = 0;
     dev_free(h->cmf); dev_free(h->cfb); dev_free(h->vhs); dev_free(h->lu_ws);
     dev_free(h->gj_flag); dev_free(h->big_ws); dev_free(h->big_ws2); dev_free(h->detm); dev_free(h->dete); dev_free(h->qr_logd); dev_free(h->qr_fail);
     dev_free(h->energy); dev_free(h->exx_part); dev_free(h->gfrag); dev_free(h->exq_y); h->exq_y_len = 0;
     dev_free(h->alive); dev_free(h->parent_ix); dev_free(h->rdm_acc); h->rdm_on = false;
+    dev_free(h->sf_acc); h->sf_on = false;
     dev_free(h->closed_w); h->closed_w_n = 0;
     if (h->pack_tmp) { hipFree(h->pack_tmp); h->pack_tmp = nullptr; }
     h->exx_part_len = 0; h->gfrag_bytes = 0; h->nw = 0;
@@ -542,6 +545,7 @@ int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64
         if ((rc = dev_upload(h, &h->ueg_rows, rows.data(), rows.size()))) return rc;
         // packed copies for energy_ueg_q_kernel (M and the staged row count fit 16 bits, the list lengths 31)
         dev_free(h->ueg_kp); dev_free(h->ueg_pm); dev_free(h->ueg_koff); dev_free(h->ueg_poff);
+        dev_free(h->sf_kp); dev_free(h->sf_pm); dev_free(h->sf_order); h->sf_nlong = 0;
         if (M < 65536 && kpq_off[nq] < (1LL << 31) && pmq_off[nq] < (1LL << 31)) {
             std::vector<int> kp((size_t)kpq_off[nq]), pm((size_t)pmq_off[nq]), ko((size_t)nq + 1), po((size_t)nq + 1);
             for (int64_t z = 0; z < kpq_off[nq]; ++z) kp[z] = (rmap[kpq_i[z]] << 16) | (int)kpq_kpq[z];
@@ -551,6 +555,19 @@ int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64
             if ((rc = dev_upload(h, &h->ueg_pm, pm.data(), pm.size() ? pm.size() : 1))) return rc;
             if ((rc = dev_upload(h, &h->ueg_koff, ko.data(), ko.size()))) return rc;
             if ((rc = dev_upload(h, &h->ueg_poff, po.data(), po.size()))) return rc;
+            // the same lists for gathers from G itself, and the deal of the pair sums on general Green's functions
+            // (k_ueg_sf.hip): momentum transfers by decreasing nk * np, ties by q; those above 64 pairs take a wave each
+            for (int64_t z = 0; z < kpq_off[nq]; ++z) kp[z] = ((int)kpq_i[z] << 16) | (int)kpq_kpq[z];
+            for (int64_t z = 0; z < pmq_off[nq]; ++z) pm[z] = ((int)pmq_i[z] << 16) | (int)pmq_pmq[z];
+            std::vector<int> order((size_t)nq);
+            std::vector<long> cost((size_t)nq);
+            for (int q = 0; q < nq; ++q) { order[q] = q; cost[q] = (long)(ko[q + 1] - ko[q]) * (po[q + 1] - po[q]); }
+            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
+            h->sf_nlong = 0;
+            while (h->sf_nlong < nq && cost[order[h->sf_nlong]] > 64) ++h->sf_nlong;
+            if ((rc = dev_upload(h, &h->sf_kp, kp.data(), kp.size() ? kp.size() : 1))) return rc;
+            if ((rc = dev_upload(h, &h->sf_pm, pm.data(), pm.size() ? pm.size() : 1))) return rc;
+            if ((rc = dev_upload(h, &h->sf_order, order.data(), order.size() ? order.size() : 1))) return rc;
         }
     }
     if ((rc = dev_upload(h, &h->vqvec, vqvec, (size_t)nq))) return rc;
@@ -1496,6 +1513,14 @@ static int estimates_update_impl(afq_handle *h, int eval_energy, int publish_zer
         if ((rc = k_estimates(h, eval_energy, false, &pub))) return rc;
         h->est_pending = true;
     } else if ((rc = k_estimates(h, eval_energy))) return rc;
+    if (eval_energy && h->sf_on) {
+        // sf_acc += sum_w weight_w Re two_rdm[G_w]: weight_w is what multiplies the energy in enumer (estimates_kernel)
+        if (h->flags & AFQ_PROP_FREE_PROJECTION) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "mixed structure factor: importance sampling only");
+        cplx *two = nullptr, *E = nullptr;                             // (the walkers' own energies stay as they are)
+        if ((rc = k_ueg_sf_two(h, h->nw, &two, &E))) return rc;
+        if ((rc = k_ueg_pair_sums(h, h->G, h->nw, E, two))) return rc;
+        if ((rc = k_ueg_sf_wsum(h, two, h->nw, nullptr, h->weight, nullptr, h->sf_acc))) return rc;
+    }
     if (h->rdm_on && !(h->flags & AFQ_PROP_FREE_PROJECTION)) {   // the free-projection branch has no RDM (mixed.py:151-175)
         if (!h->G) AFQ_FAIL(h, AFQ_ESTATE, "one_rdm: no Green's function evaluated yet");
         return k_rdm_accumulate(h);
@@ -1526,6 +1551,33 @@ int afq_estimates_rdm(afq_handle *h, int on) {
         if ((rc = dev_alloc(h, &h->rdm_acc, n))) return rc;
         AFQ_HIP(h, hipMemsetAsync(h->rdm_acc, 0, sizeof(double) * n, h->stream));
     }
+    return AFQ_OK;
+}
+
+int afq_estimates_sf(afq_handle *h, int on) {
+    if (!h) return AFQ_EINVAL;
+    int rc = need_ready(h, false);
+    if (rc) return rc;
+    if (h->kind != AFQ_SYS_UEG) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "mixed structure factor: UEG systems only");
+    if (h->ndet > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "mixed structure factor: single-determinant trial");
+    if (on && (h->flags & AFQ_PROP_FREE_PROJECTION)) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "mixed structure factor: importance sampling only");
+    h->sf_on = on != 0;
+    if (h->sf_on && !h->sf_acc) {
+        const size_t n = (size_t)4 * h->nq;
+        if ((rc = dev_alloc(h, &h->sf_acc, n))) return rc;
+        AFQ_HIP(h, hipMemsetAsync(h->sf_acc, 0, sizeof(double) * n, h->stream));
+    }
+    return AFQ_OK;
+}
+
+int afq_estimates_sf_get(afq_handle *h, double *sf_out, int zero) {
+    if (!h || !sf_out) return AFQ_EINVAL;
+    if (!h->sf_acc) AFQ_FAIL(h, AFQ_ESTATE, "mixed structure factor accumulation is not switched on");
+    hipSetDevice(h->device);
+    const size_t n = (size_t)4 * h->nq;
+    int rc = copy_out(h, sf_out, h->sf_acc, sizeof(double) * n);
+    if (rc) return rc;
+    if (zero) AFQ_HIP(h, hipMemsetAsync(h->sf_acc, 0, sizeof(double) * n, h->stream));
     return AFQ_OK;
 }
 
@@ -2016,15 +2068,25 @@ static int bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int resto
     AFQ_HIP(h, hipMemsetAsync(h->bp_est, 0, sizeof(cplx) * ((size_t)4 + 2 * h->M * h->M), h->stream));
     if (eval_energy) {
         // local_energy(system, G_bp, opt=False) (back_propagation.py:159-163): the full-G Cholesky energy
-        if (h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagated energies: generic systems only");
-        if ((rc = k_energy_full_g(h, h->G, h->nw, h->energy))) return rc;
+        // Hubbard: estimators/hubbard.py:93-114 on G_bp; UEG: estimators/ueg.py:27-88 on G_bp (k_ueg_sf.hip), below
+        if (h->kind == AFQ_SYS_GENERIC) { if ((rc = k_energy_full_g(h, h->G, h->nw, h->energy))) return rc; }
+        else if (h->kind == AFQ_SYS_HUBBARD) { if ((rc = k_energy_hubbard_full_g(h, h->G, h->nw, h->energy))) return rc; }
+    }
+    const bool sf = two_rdm_out && h->bpo_sf;
+    cplx *sf_two = nullptr, *sf_E = nullptr;
+    if (h->kind == AFQ_SYS_UEG && (eval_energy || sf)) {
+        // one evaluation serves both: the energies fold the per-q sums the structure factor keeps
+        if ((rc = k_ueg_sf_two(h, h->nw, &sf_two, &sf_E))) return rc;
+        if ((rc = k_ueg_pair_sums(h, h->G, h->nw, eval_energy ? h->energy : sf_E, sf_two))) return rc;
     }
     if ((rc = k_bp_accumulate(h, restore_weights, eval_energy))) return rc;
-    const size_t m4 = (size_t)h->M * h->M * h->M * h->M, m2 = (size_t)h->M * h->M;
+    const size_t m2 = (size_t)h->M * h->M, m4 = h->bpo_sf ? (size_t)4 * h->nq : m2 * m2;    // length of the two_rdm output
     if (two_rdm_out || fock_out) {
         // sum_w wt_w two_rdm[G_bp[w]] and (F1p, F1h)[G_bp[w]] (k_bp_obs.hip), before the reset clears the weight factors
-        if ((rc = k_bp_observables(h, restore_weights, two_rdm_out ? h->bpo_out : nullptr,
+        if ((rc = k_bp_observables(h, restore_weights, two_rdm_out && !sf ? h->bpo_out : nullptr,
                                    fock_out ? h->bpo_out + (h->bpo_two ? m4 : 0) : nullptr))) return rc;
+        // the structure factor with the same weights (bpo_wt), walkers in index order
+        if (sf && (rc = k_ueg_sf_wsum(h, sf_two, h->nw, h->bpo_wt, nullptr, h->bpo_out, nullptr))) return rc;
     }
     if (reset) {
         // FieldConfig.reset + Walkers.copy_historic_wfn (walkers/stack.py:124-127, handler.py:200-203)
@@ -2046,7 +2108,7 @@ int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_
 int afq_bp_update_ext(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
                       int reset, double *est_out, double *two_rdm_out, double *fock_out) {
     AFQ_API(h, "afq_bp_update_ext");
-    if (h && two_rdm_out && !h->bpo_two) AFQ_FAIL(h, AFQ_ESTATE, "two-body RDM: afq_bp_observables(h, 1, ...) first");
+    if (h && two_rdm_out && !h->bpo_two) AFQ_FAIL(h, AFQ_ESTATE, "two-body RDM: afq_bp_observables(h, 1 or 2, ...) first");
     if (h && fock_out && !h->bpo_ekt) AFQ_FAIL(h, AFQ_ESTATE, "EKT Fock matrices: afq_bp_observables(h, ., 1, ...) first");
     return bp_update(h, phi_bp0, nstblz, restore_weights, eval_energy, reset, est_out, two_rdm_out, fock_out);
 }
@@ -2194,13 +2256,17 @@ int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, co
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagated two-body RDM / EKT with a multi-determinant trial (sum_d w_d f[G_d] of quartic / cubic forms)");
     if (!h->nbp) AFQ_FAIL(h, AFQ_ESTATE, "back-propagation is not configured: afq_bp_configure first");
     if (ekt && h->kind == AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "EKT: the Hubbard model has no Cholesky vectors");
+    if (two_rdm == 2 && h->kind != AFQ_SYS_UEG)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "structure factor: UEG systems only (no momentum transfers elsewhere)");
+    if (two_rdm < 0 || two_rdm > 2) AFQ_FAIL(h, AFQ_EINVAL, "afq_bp_observables: two_rdm is 0, 1 (two-body RDM) or 2 (structure factor)");
+    const bool sf = two_rdm == 2;
     if (ekt && !L && h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EINVAL, "EKT: pass the vectors L_x of this system");
     if (ekt && !L && h->hs_cplx)
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "EKT with complex Cholesky vectors: the reference's 4-fold-symmetry form pins nothing");
-    const size_t M = (size_t)h->M, m4 = M * M * M * M;
+    const size_t M = (size_t)h->M, m4 = sf ? (size_t)4 * h->nq : M * M * M * M;
     hipSetDevice(h->device);
     dev_free(h->bpo_out);              // a buffer of an earlier call does not count against the budget
-    if (two_rdm) {
+    if (two_rdm && !sf) {
         size_t fr = 0, tot = 0;
         AFQ_HIP(h, hipMemGetInfo(&fr, &tot));
         const double need = 16.0 * (double)m4;
@@ -2210,14 +2276,14 @@ int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, co
                                         std::to_string((unsigned long long)fr) + " bytes)");
     }
     dev_free(h->bpo_h1); dev_free(h->bpo_L);
-    h->bpo_two = h->bpo_ekt = 0; h->bpo_nL = 0;
+    h->bpo_two = h->bpo_ekt = h->bpo_sf = 0; h->bpo_nL = 0;
     if (ekt) {
         if ((rc = dev_upload(h, &h->bpo_h1, h1, M * M))) return rc;
         if (L && (rc = dev_upload(h, &h->bpo_L, L, (size_t)nL * M * M))) return rc;
         h->bpo_nL = nL;
     }
     if ((two_rdm || ekt) && (rc = dev_alloc(h, &h->bpo_out, (two_rdm ? m4 : 0) + (ekt ? 2 * M * M : 0)))) return rc;
-    h->bpo_two = two_rdm ? 1 : 0; h->bpo_ekt = ekt ? 1 : 0;
+    h->bpo_two = two_rdm ? 1 : 0; h->bpo_ekt = ekt ? 1 : 0; h->bpo_sf = sf ? 1 : 0;
     return AFQ_OK;
 }
 
@@ -2394,6 +2460,36 @@ int afq_local_energy_full_g(afq_handle *h, const double *G, int n, double *E_out
     if ((rc = dev_upload(h, &Gd, G, gsz))) return rc;
     if ((rc = dev_alloc(h, &Ed, (size_t)3 * n))) { dev_free(Gd); return rc; }
     rc = k_energy_full_g(h, Gd, n, Ed);
+    if (!rc) rc = copy_out(h, E_out, Ed, sizeof(cplx) * 3 * n);
+    dev_free(Gd); dev_free(Ed);
+    return rc;
+}
+
+int afq_ueg_pair_sums(afq_handle *h, const double *G, int n, double *E_out, double *two_rdm_out) {
+    if (!h || !G || !E_out || !two_rdm_out || n < 1) return AFQ_EINVAL;
+    if (h->kind != AFQ_SYS_UEG) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "UEG pair sums: UEG systems only");
+    hipSetDevice(h->device);
+    const size_t gsz = (size_t)2 * h->M * h->M * n, tsz = (size_t)4 * h->nq * n;
+    cplx *Gd = nullptr, *Ed = nullptr, *Td = nullptr;
+    int rc;
+    if ((rc = dev_upload(h, &Gd, G, gsz))) return rc;
+    if ((rc = dev_alloc(h, &Ed, (size_t)3 * n)) || (rc = dev_alloc(h, &Td, tsz))) { dev_free(Gd); dev_free(Ed); return rc; }
+    rc = k_ueg_pair_sums(h, Gd, n, Ed, Td);
+    if (!rc) rc = copy_out(h, E_out, Ed, sizeof(cplx) * 3 * n);
+    if (!rc) rc = copy_out(h, two_rdm_out, Td, sizeof(cplx) * tsz);
+    dev_free(Gd); dev_free(Ed); dev_free(Td);
+    return rc;
+}
+
+int afq_hubbard_energy_full_g(afq_handle *h, const double *G, int n, double *E_out) {
+    if (!h || !G || !E_out || n < 1) return AFQ_EINVAL;
+    if (h->kind != AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "full-G Hubbard energy: Hubbard systems only");
+    hipSetDevice(h->device);
+    cplx *Gd = nullptr, *Ed = nullptr;
+    int rc;
+    if ((rc = dev_upload(h, &Gd, G, (size_t)2 * h->M * h->M * n))) return rc;
+    if ((rc = dev_alloc(h, &Ed, (size_t)3 * n))) { dev_free(Gd); return rc; }
+    rc = k_energy_hubbard_full_g(h, Gd, n, Ed);
     if (!rc) rc = copy_out(h, E_out, Ed, sizeof(cplx) * 3 * n);
     dev_free(Gd); dev_free(Ed);
     return rc;

@@ -98,6 +98,12 @@ struct afq_handle {
     int64_t *pmq_off = nullptr, *pmq_i = nullptr, *pmq_pmq = nullptr;
     double *vqvec = nullptr; double vol = 1.0; double *H1diag = nullptr;
     void *ueg_fast = nullptr;       // k_ueg.hip: tables of the plane-wave step that needs no M x M intermediate
+    // pair sums on general Green's functions (k_ueg_sf.hip): the lists packed with the rows of G itself (ueg_kp / ueg_pm
+    // carry rows of the staged copy), the momentum transfers by decreasing nk * np (the first sf_nlong: a wave each)
+    int *sf_kp = nullptr, *sf_pm = nullptr, *sf_order = nullptr;
+    int sf_nlong = 0;
+    cplx *sf_ws = nullptr, *sf_two = nullptr;      // [n, 2, nq, 3] Gkpq, Gpmq, Gprod; [n, 2, 2, nq] two_rdm; grown on demand
+    size_t sf_ws_len = 0, sf_two_len = 0;
 
     // ---- trial
     bool have_trial = false;
@@ -178,6 +184,7 @@ struct afq_handle {
     size_t bpm_ws_len = 0;
     // back-propagated two-body RDM / EKT Fock matrices (afq_bp_observables, k_bp_obs.hip)
     int bpo_two = 0, bpo_ekt = 0;   // what afq_bp_update_ext may be asked for
+    int bpo_sf = 0;                 // two_rdm is the UEG structure factor [2, 2, nq] (afq_bp_observables(h, 2, ...))
     int bpo_nL = 0;                 // EKT vectors L_x, x < nL
     cplx *bpo_h1 = nullptr;         // [M, M] h1 of the EKT
     cplx *bpo_L = nullptr;          // [nL, M, M] the caller's vectors (null: the handle's own real L_full)
@@ -287,6 +294,10 @@ struct afq_handle {
     // cloned by the comb, and rdm_acc += sum_w weight_w Re G_w with every afq_estimates_update
     bool rdm_on = false;
     double *rdm_acc = nullptr;      // [2, M, M]
+    // Mixed estimator with two_rdm: 'structure_factor' (afq_estimates_sf): sf_acc += sum_w weight_w Re two_rdm[G_w] with
+    // every afq_estimates_update that evaluates the energy
+    bool sf_on = false;
+    double *sf_acc = nullptr;       // [2, 2, nq]
     unsigned long long *counters = nullptr;   // [AFQ_NCOUNTERS]
     int *alive = nullptr;           // [nw]
     int *parent_ix = nullptr;       // [nw]
@@ -550,3 +561,11 @@ int k_energy_hubbard(afq_handle *h);
 int k_vbias_ueg(afq_handle *h);
 int k_vhs_ueg(afq_handle *h);
 int k_energy_ueg(afq_handle *h);
+// k_ueg_sf.hip: the UEG pair sums per momentum transfer on general Green's functions G_dev [n, 2, M, M] ->
+// E_dev [n, 3] (no ecore), two_dev [n, 2, 2, nq]; their weighted sum over n in index order; the Hubbard energy of full G
+int k_ueg_pair_mode(afq_handle *h);                          // 0 spin block in LDS, 1 the lists' rows in LDS, 2 global
+int k_ueg_pair_sums(afq_handle *h, const cplx *G_dev, int n, cplx *E_dev, cplx *two_dev);
+int k_ueg_sf_two(afq_handle *h, int n, cplx **two_dev, cplx **E_dev);   // the handle's [n, 2, 2, nq] + [n, 3] scratch
+int k_ueg_sf_wsum(afq_handle *h, const cplx *two_dev, int n, const cplx *wt_c, const double *wt_r, cplx *out_c,
+                  double *acc_r);                            // out_c = sum_g wt[g] two[g]; acc_r += Re of it
+int k_energy_hubbard_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *E_dev);   // estimators/hubbard.py:93-114

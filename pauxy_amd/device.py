@@ -109,6 +109,7 @@ class AfqDevice(object):
         self._ck(self.lib.afq_set_system_ueg(self.h, M, nq, na, nb, *[_p(a) for a in arrs], float(vol),
                                              _p(H1diag), float(ecore)))
         self.kind, self.M, self.K, self.na, self.nb = 'ueg', M, 2 * nq, na, nb
+        self.nq = nq
 
     def set_trial(self, psi):
         self.ndet = 1
@@ -178,9 +179,33 @@ class AfqDevice(object):
         self._ck(self.lib.afq_local_energy_full_g(self.h, _p(G), n, _p(out)))
         return out
 
+    def ueg_pair_sums(self, G):
+        """(E [n, 3], two_rdm [n, 2, 2, nq]) of general Green's functions G[n, 2, M, M] on a UEG handle: the pair sums
+        of local_energy_ueg(system, G, two_rdm=...) per momentum transfer (afq_ueg_pair_sums; E without ecore)."""
+        G = _c128(G)
+        n = G.shape[0]
+        G = _c128(G, (n, 2, self.M, self.M))
+        E = numpy.zeros((n, 3), dtype=numpy.complex128)
+        two = numpy.zeros((n, 2, 2, getattr(self, 'nq', 0)), dtype=numpy.complex128)
+        self._ck(self.lib.afq_ueg_pair_sums(self.h, _p(G), n, _p(E), _p(two)))
+        return E, two
+
+    def hubbard_energy_full_g(self, G):
+        """(E, E1b, E2b) of Green's functions G[n, 2, M, M] by local_energy_hubbard (afq_hubbard_energy_full_g)."""
+        G = _c128(G)
+        n = G.shape[0]
+        G = _c128(G, (n, 2, self.M, self.M))
+        out = numpy.zeros((n, 3), dtype=numpy.complex128)
+        self._ck(self.lib.afq_hubbard_energy_full_g(self.h, _p(G), n, _p(out)))
+        return out
+
     def bp_observables(self, two_rdm=False, ekt=False, h1=None, L=None):
         """afq_bp_observables: what bp_update may be asked for.  EKT: h1 [M, M] and L [nL, M, M] (None: a generic
-        system's own vectors)."""
+        system's own vectors).  two_rdm='structure_factor' (UEG): bp_update's 'two_rdm' then is [2, 2, nq]."""
+        self._bp_sf = isinstance(two_rdm, str) and two_rdm == 'structure_factor'
+        if isinstance(two_rdm, str) and not self._bp_sf:
+            raise ValueError("two_rdm: True or 'structure_factor'")
+        two_rdm = 2 if self._bp_sf else int(bool(two_rdm))
         M = self.M
         h1p = Lp = None
         nL = 0
@@ -194,7 +219,7 @@ class AfqDevice(object):
                 nL = L.shape[0]
                 L = _c128(L, (nL, M, M))
                 Lp = _p(L)
-        self._ck(self.lib.afq_bp_observables(self.h, int(bool(two_rdm)), int(bool(ekt)), h1p, Lp, int(nL)))
+        self._ck(self.lib.afq_bp_observables(self.h, two_rdm, int(bool(ekt)), h1p, Lp, int(nL)))
 
     def bp_ekt_chunks(self, nc=0, ncy=0):
         """afq_bp_ekt_chunks: Cholesky vectors per EKT chunk (0: automatic)."""
@@ -204,7 +229,8 @@ class AfqDevice(object):
                   ekt=False):
         """-> (energies_sum[3], denominator, G_bp_sum[2, M, M]); restore_weights in (None, 'partial', 'full').
         With two_rdm / ekt (after bp_observables) a fourth item {'two_rdm': [M]*4, 'fock_1p': [M, M], 'fock_1h':
-        [M, M]} holds the weighted sums of what was asked for."""
+        [M, M]} holds the weighted sums of what was asked for ('two_rdm': [2, 2, nq] after
+        bp_observables(two_rdm='structure_factor'))."""
         mode = {None: 0, 'partial': 1, 'full': 2}.get(restore_weights, 1)
         phi0 = _c128(phi_bp0, (self.M, self.na + self.nb))
         M = self.M
@@ -213,7 +239,10 @@ class AfqDevice(object):
             self._ck(self.lib.afq_bp_update(self.h, _p(phi0), int(nstblz), mode, int(bool(eval_energy)),
                                             int(bool(reset)), _p(out)))
             return out[:3], out[3], out[4:].reshape(2, M, M)
-        two = numpy.zeros((M, M, M, M), dtype=numpy.complex128) if two_rdm else None
+        two = None
+        if two_rdm:
+            shape = (2, 2, self.nq) if getattr(self, '_bp_sf', False) else (M, M, M, M)
+            two = numpy.zeros(shape, dtype=numpy.complex128)
         fock = numpy.zeros((2, M, M), dtype=numpy.complex128) if ekt else None
         self._ck(self.lib.afq_bp_update_ext(self.h, _p(phi0), int(nstblz), mode, int(bool(eval_energy)),
                                             int(bool(reset)), _p(out), None if two is None else _p(two),
@@ -437,6 +466,15 @@ class AfqDevice(object):
     def estimates_rdm_get(self, zero=False):
         out = numpy.empty((2, self.M, self.M), dtype=numpy.float64)
         self._ck(self.lib.afq_estimates_rdm_get(self.h, _p(out), int(bool(zero))))
+        return out
+
+    def estimates_sf(self, on=True):
+        """Mixed structure factor: energy updates also add sum_w weight_w Re two_rdm[G_w] (afq_estimates_sf)."""
+        self._ck(self.lib.afq_estimates_sf(self.h, int(bool(on))))
+
+    def estimates_sf_get(self, zero=False):
+        out = numpy.empty((2, 2, self.nq), dtype=numpy.float64)
+        self._ck(self.lib.afq_estimates_sf_get(self.h, _p(out), int(bool(zero))))
         return out
 
     def estimates_get(self, zero=False):

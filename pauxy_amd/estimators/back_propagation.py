@@ -21,12 +21,24 @@ Fock matrices of estimators/ekt.py) add the lists ``self.two_rdm`` / ``self.fock
 including the Fock matrices' offset with ``one_rdm: False``.  These attributes exist only when the option is set.
 EKT on a Generic system uses L_x[i, k] = hs_pot[i*M + k, x] (the reference's ekt.py asserts a 3-D array and fails on
 the [M*M, K] vectors of a Generic system); it is refused for the Hubbard model and for complex Generic vectors.
-``two_rdm: 'structure_factor'`` is refused (it needs back-propagated UEG energies).
+
+``evaluate_energy: True`` works on all three systems: the full-G Cholesky energy (Generic), local_energy_hubbard
+(Hubbard) and local_energy_ueg (UEG) of every walker's G_bp.  (The reference's own call passes the dispatcher an
+``opt`` keyword it does not have and raises TypeError; the numbers are those of the call without it.)
+``two_rdm: 'structure_factor'`` (UEG only; NotImplementedError for systems without momentum transfers) accumulates
+sum_w weight_w two_rdm[G_bp[w]] with the [2, 2, nq] array local_energy_ueg(system, G, two_rdm=...) fills, in the
+reference's flat layout (``two_rdm_shape = (2, 2, nq)``), complex and not normalised: ``self.two_rdm`` and the group
+``two_rdm_<n>``.  The sums run over the system's index lists: ``UEG(..., full_lists=True)`` gives the complete pair
+sums of a back-propagated Green's function, the default lists (the reference's: first nup plane waves) truncated ones.
+One deliberate difference: the structure factor is evaluated whenever it is asked for, also with ``evaluate_energy:
+False``; the reference fills the array only inside its energy call and would accumulate zeros there.
 """
 import numpy
 
 
 class BackPropagation(object):
+    structure_factor = False
+
     def __init__(self, bp, root, filename, qmc, system, trial, dtype, BT2):
         self.tau_bp = bp.get('tau_bp', 0)
         self.nmax = int(self.tau_bp / qmc.dt)
@@ -53,16 +65,18 @@ class BackPropagation(object):
             # without weight factors (hubbard.py:215-216, walkers/stack.py:35-49); afq_bp_configure refuses the
             # continuous Hubbard propagator
             raise NotImplementedError("restore_weights with the discrete Hubbard fields")
-        if self.calc_two_rdm is not None and isinstance(self.calc_two_rdm, str) and self.calc_two_rdm == "structure_factor":
-            # the structure factor needs back-propagated UEG energies, which are refused below (DESIGN row 8f-2)
-            raise NotImplementedError("back-propagated two_rdm: 'structure_factor'")
+        if isinstance(self.calc_two_rdm, str):
+            if self.calc_two_rdm != "structure_factor":
+                raise ValueError("two_rdm: True or 'structure_factor'")
+            self.structure_factor = True            # (an instance attribute only with the option, like two_rdm)
+        if self.structure_factor and system.name != "UEG":
+            # S(q) is a sum over momentum transfers: back_propagation.py:88-89 reads system.qvecs
+            raise NotImplementedError("back-propagated two_rdm: 'structure_factor' needs a UEG system")
         if self.eval_ekt and system.name == "Hubbard":
             raise NotImplementedError("EKT: the Hubbard model has no Cholesky vectors")
         if (self.eval_ekt and system.name == "Generic" and numpy.iscomplexobj(system.hs_pot)
                 and numpy.any(numpy.asarray(system.hs_pot).imag != 0)):
             raise NotImplementedError("EKT with complex Cholesky vectors (ekt.py's 4-fold-symmetry formula)")
-        if self.eval_energy and system.name != "Generic":
-            raise NotImplementedError("back-propagated energies: Generic systems")
         if (system.name == "Generic" and numpy.iscomplexobj(system.hs_pot)
                 and numpy.any(numpy.asarray(system.hs_pot).imag != 0)):
             # the backward step applies B(-conj(x)) with the same L_n: B(x)^H only when every L_n is Hermitian
@@ -80,8 +94,10 @@ class BackPropagation(object):
         dms_size = self.G.size
         if self.calc_two_rdm is not None:         # back_propagation.py:86-99,100-104: the flat layout of the reference
             self.two_rdm = []
-            self.two_rdm_size = M ** 4
-            dms_size += M ** 4
+            # back_propagation.py:88-94
+            self.two_rdm_shape = (2, 2, len(system.qvecs)) if self.structure_factor else (M,) * 4
+            self.two_rdm_size = int(numpy.prod(self.two_rdm_shape))
+            dms_size += self.two_rdm_size
         if self.eval_ekt:
             self.fock_1p = []
             self.fock_1h = []
@@ -173,8 +189,8 @@ class BackPropagation(object):
                     out.push(self.one_rdm[-1], 'one_rdm_%d' % self.buff_ix)
             if self.calc_two_rdm:                      # back_propagation.py:304-308
                 start = self.nreg + 1 + self.G.size
-                M = self.G.shape[-1]
-                self.two_rdm.append(self.global_estimates[start:start + self.two_rdm_size].reshape((M,) * 4).copy())
+                self.two_rdm.append(self.global_estimates[start:start + self.two_rdm_size]
+                                    .reshape(self.two_rdm_shape).copy())
                 if out is not None:
                     out.push(self.two_rdm[-1], 'two_rdm_%d' % self.buff_ix)
             if self.eval_ekt:
@@ -206,7 +222,8 @@ class BackPropagation(object):
                 cv = system.chol_vecs
                 cv = cv.toarray() if hasattr(cv, 'toarray') else numpy.asarray(cv)
                 L = 2.0 * cv.T.reshape((system.nchol, system.nbasis, system.nbasis))
-        dev.bp_observables(two_rdm=self.calc_two_rdm is not None, ekt=bool(self.eval_ekt), h1=h1, L=L)
+        two = 'structure_factor' if self.structure_factor else self.calc_two_rdm is not None
+        dev.bp_observables(two_rdm=two, ekt=bool(self.eval_ekt), h1=h1, L=L)
         self._obs_dev = dev
 
     def rdm(self):

@@ -10,6 +10,13 @@ Output: the per-block rows are kept in ``self.blocks`` (and printed when
 ``verbose``); when the container was given a file name the root rank also pushes
 them to ``basic/energies/<block>`` with ``basic/headers`` (mixed.py:278,368-371;
 layout in pauxy_amd/estimators/utils.py).
+
+``two_rdm: 'structure_factor'`` (UEG, importance sampling): every update that evaluates the energy also accumulates
+sum_w weight_w Re two_rdm[G_w] on the device, two_rdm[2, 2, nq] being what local_energy_ueg(system, G, two_rdm=...)
+fills.  Per block the root pushes ``basic/two_rdm/<block>`` = (the accumulator summed over ranks) / (the block's global
+EDenom) and keeps it in ``self.two_rdm``: the energy's own estimator per momentum transfer, so that
+1 / (2 vol) * vqvec . two_rdm.sum((0, 1)) of a block is that block's E2Body.  (The reference's non-thermal branch never
+hands its two_rdm array to the energy call, mixed.py:214, and writes zeros; this normalisation is this package's.)
 """
 import time
 
@@ -26,11 +33,22 @@ def get_estimator_enum(thermal=False):
 
 
 class Mixed(object):
+    calc_two_rdm = None
+    structure_factor = False
+    _sf_armed = False
+
     def __init__(self, mixed, system, root, filename, qmc, trial, dtype=complex):
         self.eval_energy = mixed.get('evaluate_energy', True)
         self.calc_one_rdm = mixed.get('one_rdm', False)
-        if mixed.get('two_rdm', None) is not None:
-            raise NotImplementedError("two_rdm accumulation is outside the device hot path")
+        two = mixed.get('two_rdm', None)
+        if two is not None:
+            if not (isinstance(two, str) and two == 'structure_factor' and system.name == "UEG"):
+                raise NotImplementedError("mixed two_rdm: only 'structure_factor' on a UEG system")
+            # (set only with the option: without it the instance holds what it held before)
+            self.calc_two_rdm = two
+            self.structure_factor = True
+            self.sf_acc = numpy.zeros((2, 2, len(system.qvecs)))
+            self.two_rdm = []                                           # per block, as pushed to 'two_rdm'
         self.G = numpy.zeros((2, system.nbasis, system.nbasis))          # mixed.py:99
         self.rdm_acc = numpy.zeros_like(self.G)
         self.one_rdm = []                                               # per block, as pushed to 'one_rdm'
@@ -74,6 +92,8 @@ class Mixed(object):
         """mixed.py:133-233: importance-sampling branch (:210-225) or, when the propagator was
         built with free_projection, the complex wfac = weight*ot*phase accumulation of :151-175
         (the device handle knows which from afq_set_propagator)."""
+        if self.structure_factor and free_projection:
+            raise NotImplementedError("mixed two_rdm: 'structure_factor' with free projection")
         psi._end_sweep()
         psi._flush()
         dev = psi.dev
@@ -90,6 +110,8 @@ class Mixed(object):
         self.estimates[:self.names.time] += est[:self.names.time]
         if self.calc_one_rdm:
             self.rdm_acc += dev.estimates_rdm_get(zero=True)            # mixed.py:226-229
+        if self.structure_factor and do_energy and self.eval_energy:
+            self.sf_acc += dev.estimates_sf_get(zero=True)
         if do_energy:
             psi._greens_version = psi.phi_version           # the launch refreshed Ghalf
 
@@ -98,6 +120,9 @@ class Mixed(object):
         if self.calc_one_rdm and not self._rdm_armed:
             dev.estimates_rdm(True)
             self._rdm_armed = True
+        if self.structure_factor and not self._sf_armed:
+            dev.estimates_sf(True)          # (the library refuses a free-projection propagator)
+            self._sf_armed = True
 
     def print_step(self, comm, nprocs, step, nsteps=None, free_projection=False):
         """mixed.py:235-289."""
@@ -135,9 +160,17 @@ class Mixed(object):
             red = numpy.zeros_like(self.rdm_acc)
             comm.Reduce(self.rdm_acc, red, op=None, root=0)
             self.rdm_acc[...] = red
+        if self.structure_factor and comm.size > 1 and not getattr(comm, 'already_reduced', False):
+            red = numpy.zeros_like(self.sf_acc)
+            comm.Reduce(self.sf_acc, red, op=None, root=0)
+            self.sf_acc[...] = red
         if comm.rank == 0:
             row = [step] + list(gs[:ns.time + 1])
             self.blocks.append(numpy.array(row))
+            if self.structure_factor:
+                # the energy's estimator per momentum transfer: the block's sums over its (global) energy denominator
+                with numpy.errstate(divide='ignore', invalid='ignore'):
+                    self.two_rdm.append(self.sf_acc / gs[ns.edenom].real)
             if self.calc_one_rdm:                               # mixed.py:279-283
                 rdm = self.rdm_acc / nsteps / gs[ns.weight].real
                 self.one_rdm.append(rdm)
@@ -145,6 +178,8 @@ class Mixed(object):
                 self.output.push(row, 'energies')               # mixed.py:278
                 if self.calc_one_rdm:
                     self.output.push(self.one_rdm[-1], 'one_rdm')
+                if self.structure_factor:
+                    self.output.push(self.two_rdm[-1], 'two_rdm')
                 self.output.increment()
             if self.verbose:
                 print(" ".join("{: .10e}".format(x) for x in numpy.array(row).real))
@@ -159,6 +194,8 @@ class Mixed(object):
 
     def zero(self):
         self.rdm_acc[:] = 0
+        if self.structure_factor:
+            self.sf_acc[:] = 0
         self.estimates[:] = 0
         self.global_estimates[:] = 0
         self.estimates[self.names.time] = time.time()
@@ -187,7 +224,9 @@ def local_energy(system, G, Ghalf=None, two_rdm=None, rchol=None, eri=None, C0=N
                  exxa0=None, exxb0=None, UVT=None, device=None):
     """pauxy.estimators.mixed.local_energy (mixed.py:383-437) for ONE Green's
     function, evaluated by the device energy kernels: ``Ghalf`` (half-rotated form) or, without it, the
-    full ``G`` is used for Generic; ``G`` for Hubbard and the UEG.  Call-compatible with the reference:
+    full ``G`` is used for Generic; ``G`` for Hubbard and the UEG.  ``two_rdm`` (UEG only, ignored elsewhere as in the
+    reference): an array [2, 2, nq] that receives the pair sums per momentum transfer (estimators/ueg.py:71-80), with the
+    system's index lists and for any ``G``.  Call-compatible with the reference:
     the device is the handle ``pauxy_amd.context`` already holds for ``system`` (the one the propagator,
     walkers and estimators of that system share); ``device=`` names another one.  The evaluation uses a
     scratch handle when the shared one carries a population (its walkers are not disturbed)."""
@@ -197,6 +236,11 @@ def local_energy(system, G, Ghalf=None, two_rdm=None, rchol=None, eri=None, C0=N
         device = context.scratch_device(system)
     if device.nw < 1:
         device.walkers_alloc(1)
+    if device.kind == 'ueg' and two_rdm is not None:
+        # estimators/ueg.py:71-80: the per-q pair sums of this G go to the caller's two_rdm[2, 2, nq]
+        E, two = device.ueg_pair_sums(numpy.asarray(G, dtype=numpy.complex128)[None])
+        two_rdm[...] = two[0]
+        return (complex(E[0, 0]), complex(E[0, 1]), complex(E[0, 2]))
     if device.kind == 'ueg':
         device.set(L.F_G, numpy.asarray(G, dtype=numpy.complex128), 0)
     else:

@@ -222,7 +222,7 @@ class AFQMC(object):
         hirsch = getattr(self.propagators, 'hs_type', '') == 'discrete'
         overlap = (overlap_blocks and not others and (dcomm or self.comm.size == 1) and not hirsch and on_step is None
                    and getattr(self.propagators, 'device_rng', False) and mixed.eval_energy and not mixed.calc_one_rdm
-                   and not self.psi.write_restart)
+                   and not mixed.structure_factor and not self.psi.write_restart)
         begun = False
         try:
             for step in range(first_step, first_step + n):
@@ -250,6 +250,13 @@ class AFQMC(object):
                     mixed.estimates[:ns.time] += est[:ns.time]
                     if mixed.calc_one_rdm:
                         mixed.rdm_acc += dev.estimates_rdm_get(zero=True)
+                    if mixed.structure_factor:
+                        sf = dev.estimates_sf_get(zero=True)
+                        if dcomm:               # (the one-body RDM sums are reduced by estimates_allreduce itself)
+                            red = numpy.zeros_like(sf)
+                            other_comm.Allreduce(sf, red)
+                            sf = red
+                        mixed.sf_acc += sf
                     mixed.print_step(block_comm, self.comm.size, step)
                     self.psi.tune_exchange_capacity()
                 for est in others:

@@ -108,9 +108,15 @@ class Hubbard(object):
 
 
 class UEG(object):
-    """Uniform electron gas in a plane-wave basis, systems/ueg.py:43-191,336-428."""
+    """Uniform electron gas in a plane-wave basis, systems/ueg.py:43-191,336-428.
 
-    def __init__(self, rs, nup, ndown, ecut):
+    The energy's index lists (ikpq_* / ipmq_*) run over the first ``nup`` plane waves, as the reference's do
+    (systems/ueg.py:139): complete for a Green's function whose rows beyond the trial's occupied plane waves vanish (the
+    mixed one of the Hartree-Fock trial), truncated sums for one with dense rows (a back-propagated one).
+    ``full_lists=True`` builds them over all ``nbasis`` plane waves (the reference's ``thermal: True`` lists and nothing
+    else of that option): the complete pair sums for any Green's function."""
+
+    def __init__(self, rs, nup, ndown, ecut, full_lists=False):
         self.name = "UEG"
         self.nup, self.ndown = nup, ndown
         self.nelec = (nup, ndown)
@@ -145,7 +151,8 @@ class UEG(object):
         self.H1 = numpy.array([T, T])
         h1e_mod = self._mod_one_body(T)
         self.h1e_mod = numpy.array([h1e_mod, h1e_mod])
-        nlimit = self.nup
+        self.full_lists = bool(full_lists)
+        nlimit = self.nbasis if self.full_lists else self.nup
         (self.ikpq_i, self.ikpq_kpq) = self._index_lists(+1, nlimit)
         (self.ipmq_i, self.ipmq_pmq) = self._index_lists(-1, nlimit)
         (self.chol_vecs, self.iA, self.iB) = self._two_body_potentials()
@@ -274,5 +281,6 @@ def get_system(sys_opts):
         return Hubbard(sys_opts['nx'], sys_opts['ny'], sys_opts['nup'], sys_opts['ndown'], sys_opts['U'],
                        t=sys_opts.get('t', 1.0))
     if name == 'UEG':
-        return UEG(sys_opts['rs'], sys_opts['nup'], sys_opts['ndown'], sys_opts['ecut'])
+        return UEG(sys_opts['rs'], sys_opts['nup'], sys_opts['ndown'], sys_opts['ecut'],
+                   full_lists=sys_opts.get('full_lists', False))
     raise ValueError("unrecognized system name {}".format(name))
