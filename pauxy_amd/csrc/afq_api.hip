@@ -7,26 +7,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include "afq_internal.h"
+#include "afq_host.h"
 
 namespace {
-
-template <class T> int dev_alloc(afq_handle *h, T **p, size_t n) {
-    if (*p) { hipFree(*p); *p = nullptr; }
-    if (n == 0) return AFQ_OK;
-    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
-    if (e != hipSuccess) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return AFQ_ENOMEM; }
-    return AFQ_OK;
-}
-
-template <class T> int dev_upload(afq_handle *h, T **p, const void *src, size_t n) {
-    int rc = dev_alloc(h, p, n);
-    if (rc) return rc;
-    if (n) AFQ_HIP(h, hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return AFQ_OK;
-}
-
-template <class T> void dev_free(T *&p) { if (p) { hipFree(p); p = nullptr; } }
 
 // ---- multi-determinant operand sets: psi / psic / rH1 / rchol_* of the handle are views of dets[cur_det]
 void stash_det(afq_handle *h) {
@@ -109,6 +92,7 @@ void free_walkers(afq_handle *h) {
     dev_free(h->hs_fbfac);
     dev_free(h->bp_hist); dev_free(h->bp_n); dev_free(h->bp_flag); dev_free(h->bp_cos); dev_free(h->bp_ph);
     dev_free(h->phi_old); dev_free(h->phi_bp); dev_free(h->BH1dag); dev_free(h->bp_xs); dev_free(h->bp_est);
+    dev_free(h->bp_ot); dev_free(h->bp_detR);
     dev_free(h->bpm_ws); h->bpm_ws_len = 0;
     h->nbp = 0; dev_free(h->xbar); dev_free(h->xs);
     dev_free(h->bpo_h1); dev_free(h->bpo_L); dev_free(h->bpo_wt); dev_free(h->bpo_out); dev_free(h->bpo_ws);
@@ -223,8 +207,6 @@ hipError_t afq_post_launch(afq_handle *h) {
     if (h->debug_sync) e = hipStreamSynchronize(h->stream);
     return e;
 }
-
-#define AFQ_API(h, name) do { if (h) (h)->crumb_api = name; } while (0)
 
 extern "C" {
 
@@ -819,14 +801,6 @@ int afq_walkers_device_ptr(afq_handle *h, int field, void **dev_ptr, int64_t *by
 // ----------------------------------------------------------------- hot path
 static int greens_any(afq_handle *h, cplx *det_out, bool with_ghalf);
 
-static int need_ready(afq_handle *h, bool prop) {
-    if (!h->kind || !h->have_trial || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, "system, trial and walkers must be set");
-    if (prop && !h->have_prop) AFQ_FAIL(h, AFQ_ESTATE, "propagator not set");
-    if (h->prop_pending) AFQ_FAIL(h, AFQ_ESTATE, "a step is half done: afq_propagate_finish first");
-    hipSetDevice(h->device);
-    return AFQ_OK;
-}
-
 // The last step left its Green's function behind as overlap + spin sum of Ghalf only (afq_propagate_finish on a step the
 // driver announced with afq_estimates_fuse_next): somebody wants the per-spin Ghalf after all -- evaluate it.
 static int ensure_spin_ghalf(afq_handle *h) {
@@ -835,21 +809,6 @@ static int ensure_spin_ghalf(afq_handle *h) {
     const int rc = greens_any(h, h->ovlp_new, true);
     h->greens_valid = rc == AFQ_OK;
     return rc;
-}
-
-static int ensure_G(afq_handle *h) {
-    if (!h->G) {
-        int rc = dev_alloc(h, &h->G, (size_t)2 * h->M * h->M * h->nw);
-        if (rc) return rc;
-    }
-    return AFQ_OK;
-}
-
-static int copy_out(afq_handle *h, void *host, const void *dev, size_t bytes) {
-    if (!host) return AFQ_OK;
-    AFQ_HIP(h, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream));
-    AFQ_HIP(h, hipStreamSynchronize(h->stream));
-    return AFQ_OK;
 }
 
 int afq_greens(afq_handle *h, int want_G, double *ovlp_out) {
@@ -947,19 +906,8 @@ static int force_bias(afq_handle *h, bool with_xbar = true) {
     return with_xbar ? k_xbar(h) : AFQ_OK;
 }
 
-static int build_vhs(afq_handle *h) {
-    if (h->kind == AFQ_SYS_GENERIC) return k_vhs_generic(h);
-    if (h->kind == AFQ_SYS_HUBBARD) return k_vhs_hubbard(h);
-    return k_vhs_ueg(h);
-}
-
 static int local_energy(afq_handle *h);
 static int local_energy_dets(afq_handle *h);
-
-static int apply_exp(afq_handle *h, const cplx *vhs) {
-    if (h->vhs_diag) return k_apply_exponential_diag(h, vhs);
-    return k_apply_exponential(h, vhs);
-}
 
 int afq_propagate(afq_handle *h, const double *xi, double eshift_re, double eshift_im) {
     const int rc = afq_propagate_begin(h, xi);
@@ -1925,574 +1873,6 @@ int afq_propagate_hirsch_free(afq_handle *h, const double *u, int32_t *fields_ou
     if ((rc = k_hirsch_free(h, eshift))) return rc;
     if (fields_out && (rc = copy_out(h, fields_out, h->hs_fields, sizeof(int) * (size_t)h->nw * h->M))) return rc;
     return k_alive(h);
-}
-
-// ---------------------------------------------------------------- back-propagation
-struct BpMsdWs;
-static size_t bp_msd_carve(afq_handle *h, cplx *base, BpMsdWs *ws);
-
-int afq_bp_configure(afq_handle *h, int nbp) {
-    if (!h || nbp < 1) return AFQ_EINVAL;
-    int rc = need_ready(h, true);
-    if (rc) return rc;
-    if (h->ndet > 1 && h->kind != AFQ_SYS_GENERIC)
-        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagation of a multi-determinant trial: generic systems only");
-    if (h->kind == AFQ_SYS_HUBBARD && !h->hirsch)
-        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagation of a Hubbard system: discrete fields only (the reference's propagation/hubbard.py:568-672 reads the history as 0 / 1 fields)");
-    if (h->hirsch && h->K != h->M) AFQ_FAIL(h, AFQ_ESTATE, "discrete fields: one per site expected");
-    if (h->flags & AFQ_PROP_FREE_PROJECTION) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "no field history in free projection");
-    // the backward step reuses the forward one with fields -conj(x): B(x)^H only when every L_n^H == L_n
-    if (h->hs_cplx == AFQ_HS_GENERAL)
-        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagation with non-Hermitian complex Cholesky vectors");
-    const size_t per = (size_t)h->M * h->nt, n = h->nw, nd = h->ndet > 1 ? h->ndet : 1;
-    size_t msd_ws = 0;
-    if (nd > 1) {
-        // the determinants' phi_bp (and conjugate) and the window's scratch are sized here, and checked first: a
-        // configuration that does not fit says so with the byte counts instead of failing at an allocation half way
-        msd_ws = bp_msd_carve(h, nullptr, nullptr);
-        size_t fr = 0, tot = 0;
-        hipSetDevice(h->device);
-        AFQ_HIP(h, hipMemGetInfo(&fr, &tot));
-        const double need = 16.0 * ((double)2 * per * n * nd + (double)msd_ws + (double)n * nbp * h->K);
-        if (need > 0.5 * (double)fr)
-            AFQ_FAIL(h, AFQ_ENOMEM, "back-propagation of " + std::to_string(nd) + " determinants: " +
-                                        std::to_string((unsigned long long)need) +
-                                        " bytes, more than half of the free device memory (" +
-                                        std::to_string((unsigned long long)fr) + " bytes)");
-    }
-    if ((rc = dev_alloc(h, &h->bp_hist, n * nbp * h->K))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_n, n))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_flag, n))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_cos, n))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_ph, n))) return rc;
-    if ((rc = dev_alloc(h, &h->phi_old, per * n))) return rc;
-    if ((rc = dev_alloc(h, &h->phi_bp, 2 * per * n * nd))) return rc;   // phi_bp and conj(phi_bp), of every determinant
-    if (nd > 1) {
-        if ((rc = dev_alloc(h, &h->bpm_ws, msd_ws))) return rc;
-        h->bpm_ws_len = msd_ws;
-    }
-    if ((rc = dev_alloc(h, &h->BH1dag, (size_t)2 * h->M * h->M))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_xs, n * h->K))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_est, (size_t)4 + 2 * h->M * h->M))) return rc;
-    h->nbp = nbp;
-    AFQ_HIP(h, hipMemsetAsync(h->bp_hist, 0, sizeof(cplx) * n * nbp * h->K, h->stream));
-    AFQ_HIP(h, hipMemsetAsync(h->bp_flag, 0, sizeof(int) * n, h->stream));
-    if ((rc = k_bp_reset(h, true))) return rc;
-    if ((rc = k_conj_transpose(h, h->BH1, h->BH1dag))) return rc;
-    // walkers/walker.py:43: phi_old starts as the walker itself
-    AFQ_HIP(h, hipMemcpyAsync(h->phi_old, h->phi, sizeof(cplx) * per * n, hipMemcpyDeviceToDevice, h->stream));
-    return AFQ_OK;
-}
-
-int afq_bp_steps(afq_handle *h, int32_t *steps_out) {
-    if (!h || !steps_out) return AFQ_EINVAL;
-    if (!h->nbp) AFQ_FAIL(h, AFQ_ESTATE, "back-propagation is not configured");
-    hipSetDevice(h->device);
-    int rc = copy_out(h, steps_out, h->bp_n, sizeof(int) * h->nw);
-    // discrete fields are recorded one at a time: FieldConfig.step counts completed configurations
-    if (!rc && h->hirsch) for (int i = 0; i < h->nw; ++i) steps_out[i] /= h->M;
-    return rc;
-}
-
-// phi_bp <- B(x_0)^H ... B(x_{n-1})^H phi_bp over the recorded history, re-orthogonalised after the i-th step from the end
-// when i != 0 and i % nstblz == 0 (propagation/generic.py:279-288, hubbard.py:661-671).  With keep, phi_bp after the
-// step of window slice t (= nbp - 1 - i) is copied to keep + t nw M nt for t < nkeep (the ITCF's psi_L(t)).
-static int bp_backward(afq_handle *h, int nstblz, cplx *keep, int nkeep) {
-    const size_t n = h->nw, per = (size_t)h->M * h->nt;
-    // borrow the step machinery: phi <- phi_bp, BH1 <- BH1^H, fields <- -conj(x), every walker "alive"
-    // while it still has recorded steps; the walkers' own overlaps / detR / weights are parked
-    cplx *s_phi = h->phi, *s_xs = h->xs, *s_BH1 = h->BH1, *s_ot = h->ot;
-    double *s_detR = h->detR;
-    const int s_flags = h->flags;
-    cplx *tmp_ot = nullptr; double *tmp_detR = nullptr;
-    int rc;
-    if ((rc = dev_alloc(h, &tmp_ot, n))) return rc;
-    if ((rc = dev_alloc(h, &tmp_detR, n))) { dev_free(tmp_ot); return rc; }
-    h->phi = h->phi_bp; h->xs = h->bp_xs; h->BH1 = h->BH1dag; h->ot = tmp_ot; h->detR = tmp_detR;
-    h->flags &= ~AFQ_PROP_FREE_PROJECTION;
-    const bool fused = k_prop_fused_supported(h);
-    rc = AFQ_OK;
-    for (int i = 0; i < h->nbp && !rc; ++i) {                       // propagation/generic.py:279-288
-        if (h->hirsch) {                                            // propagation/hubbard.py:661-671
-            rc = k_bp_hirsch_step(h, i);
-        } else {
-            if ((rc = k_bp_fields(h, i))) break;
-            h->vhs_upper = fused && h->hs_sym;
-            rc = build_vhs(h);
-            if (!rc && fused) rc = k_prop_fused(h);
-            h->vhs_upper = false;
-            if (rc) break;
-            if (!fused) {
-                if ((rc = k_onebody(h))) break;
-                if ((rc = apply_exp(h, h->vhs))) break;
-                rc = k_onebody(h);
-            }
-        }
-        if (!rc && i != 0 && i % nstblz == 0) rc = k_reortho(h);    // utils/linalg.py:82-105 on both spins
-        const int t = h->nbp - 1 - i;
-        if (!rc && keep && t < nkeep) {
-            const hipError_t e = hipMemcpyAsync(keep + (size_t)t * n * per, h->phi_bp, sizeof(cplx) * n * per,
-                                                hipMemcpyDeviceToDevice, h->stream);
-            if (e != hipSuccess) { h->err = hipGetErrorString(e); rc = AFQ_EHIP; }
-        }
-    }
-    h->phi = s_phi; h->xs = s_xs; h->BH1 = s_BH1; h->ot = s_ot; h->detR = s_detR; h->flags = s_flags;
-    dev_free(tmp_ot); dev_free(tmp_detR);
-    return rc;
-}
-
-static int bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
-                     int reset, double *est_out, double *two_rdm_out, double *fock_out) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
-    if (!h || !phi_bp0 || !est_out || nstblz < 1 || restore_weights < 0 || restore_weights > 2) return AFQ_EINVAL;
-    int rc = need_ready(h, true);
-    if (rc) return rc;
-    if (!h->nbp) AFQ_FAIL(h, AFQ_ESTATE, "back-propagation is not configured");
-    if (h->hirsch && restore_weights)
-        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "restore_weights with discrete fields: FieldConfig.push records no weight factors (walkers/stack.py:35-49)");
-    const size_t per = (size_t)h->M * h->nt, n = h->nw;
-    // trial (or initial) determinant for every walker; the second half of phi_bp is upload scratch first
-    AFQ_HIP(h, hipMemcpyAsync(h->phi_bp + per * n, phi_bp0, sizeof(cplx) * per, hipMemcpyHostToDevice, h->stream));
-    if ((rc = k_bp_init(h, h->phi_bp + per * n))) return rc;
-    if ((rc = bp_backward(h, nstblz, nullptr, 0))) return rc;
-    // G_bp[w] = gab(phi_bp, phi_old)^T (back_propagation.py:156-157) = the Green's function of phi_old with
-    // phi_bp[w] in the role of the trial
-    if ((rc = k_conj_copy(h, h->phi_bp, h->phi_bp + per * n, (long)(per * n)))) return rc;
-    cplx *s_phi = h->phi, *s_psi = h->psi, *s_psic = h->psic;
-    h->phi = h->phi_old; h->psi = h->phi_bp; h->psic = h->phi_bp + per * n; h->psi_stride = (long)per;
-    rc = k_greens(h, h->ovlp_old);
-    if (!rc) rc = ensure_G(h);
-    if (!rc) rc = k_full_G(h);
-    h->phi = s_phi; h->psi = s_psi; h->psic = s_psic; h->psi_stride = 0;
-    if (rc) return rc;
-    AFQ_HIP(h, hipMemsetAsync(h->bp_est, 0, sizeof(cplx) * ((size_t)4 + 2 * h->M * h->M), h->stream));
-    if (eval_energy) {
-        // local_energy(system, G_bp, opt=False) (back_propagation.py:159-163): the full-G Cholesky energy
-        // Hubbard: estimators/hubbard.py:93-114 on G_bp; UEG: estimators/ueg.py:27-88 on G_bp (k_ueg_sf.hip), below
-        if (h->kind == AFQ_SYS_GENERIC) { if ((rc = k_energy_full_g(h, h->G, h->nw, h->energy))) return rc; }
-        else if (h->kind == AFQ_SYS_HUBBARD) { if ((rc = k_energy_hubbard_full_g(h, h->G, h->nw, h->energy))) return rc; }
-    }
-    const bool sf = two_rdm_out && h->bpo_sf;
-    cplx *sf_two = nullptr, *sf_E = nullptr;
-    if (h->kind == AFQ_SYS_UEG && (eval_energy || sf)) {
-        // one evaluation serves both: the energies fold the per-q sums the structure factor keeps
-        if ((rc = k_ueg_sf_two(h, h->nw, &sf_two, &sf_E))) return rc;
-        if ((rc = k_ueg_pair_sums(h, h->G, h->nw, eval_energy ? h->energy : sf_E, sf_two))) return rc;
-    }
-    if ((rc = k_bp_accumulate(h, restore_weights, eval_energy))) return rc;
-    const size_t m2 = (size_t)h->M * h->M, m4 = h->bpo_sf ? (size_t)4 * h->nq : m2 * m2;    // length of the two_rdm output
-    if (two_rdm_out || fock_out) {
-        // sum_w wt_w two_rdm[G_bp[w]] and (F1p, F1h)[G_bp[w]] (k_bp_obs.hip), before the reset clears the weight factors
-        if ((rc = k_bp_observables(h, restore_weights, two_rdm_out && !sf ? h->bpo_out : nullptr,
-                                   fock_out ? h->bpo_out + (h->bpo_two ? m4 : 0) : nullptr))) return rc;
-        // the structure factor with the same weights (bpo_wt), walkers in index order
-        if (sf && (rc = k_ueg_sf_wsum(h, sf_two, h->nw, h->bpo_wt, nullptr, h->bpo_out, nullptr))) return rc;
-    }
-    if (reset) {
-        // FieldConfig.reset + Walkers.copy_historic_wfn (walkers/stack.py:124-127, handler.py:200-203)
-        if ((rc = k_bp_reset(h, false))) return rc;
-        AFQ_HIP(h, hipMemcpyAsync(h->phi_old, h->phi, sizeof(cplx) * per * n, hipMemcpyDeviceToDevice, h->stream));
-    }
-    if ((rc = k_alive(h))) return rc;
-    if (two_rdm_out && (rc = copy_out(h, two_rdm_out, h->bpo_out, sizeof(cplx) * m4))) return rc;
-    if (fock_out && (rc = copy_out(h, fock_out, h->bpo_out + (h->bpo_two ? m4 : 0), sizeof(cplx) * 2 * m2))) return rc;
-    return copy_out(h, est_out, h->bp_est, sizeof(cplx) * ((size_t)4 + 2 * h->M * h->M));
-}
-
-int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
-                  int reset, double *est_out) {
-    AFQ_API(h, "afq_bp_update");
-    return bp_update(h, phi_bp0, nstblz, restore_weights, eval_energy, reset, est_out, nullptr, nullptr);
-}
-
-int afq_bp_update_ext(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
-                      int reset, double *est_out, double *two_rdm_out, double *fock_out) {
-    AFQ_API(h, "afq_bp_update_ext");
-    if (h && two_rdm_out && !h->bpo_two) AFQ_FAIL(h, AFQ_ESTATE, "two-body RDM: afq_bp_observables(h, 1 or 2, ...) first");
-    if (h && fock_out && !h->bpo_ekt) AFQ_FAIL(h, AFQ_ESTATE, "EKT Fock matrices: afq_bp_observables(h, ., 1, ...) first");
-    return bp_update(h, phi_bp0, nstblz, restore_weights, eval_energy, reset, est_out, two_rdm_out, fock_out);
-}
-
-// ---- multi-determinant windows (k_bp_msd.hip)
-struct BpMsdWs {
-    cplx *dets, *coeffs, *ot, *ovlp, *detw, *S, *fac, *ghalf, *G, *gsum, *E, *esum, *stack;
-    double *logr, *detR;
-};
-
-// the window's scratch of an ndet-determinant handle in complex units; with base, the pointers into it
-static size_t bp_msd_carve(afq_handle *h, cplx *base, BpMsdWs *ws) {
-    const size_t n = h->nw, nd = h->ndet, per = (size_t)h->M * h->nt, g2 = (size_t)2 * h->M * h->M * n;
-    const size_t half = (nd * n + 1) / 2;                  // nd n doubles
-    // the column-stacked products keep one more copy of the determinants (the fused propagator works in place)
-    const size_t stack = k_prop_fused_supported(h) ? 0 : nd * n * per;
-    const size_t sizes[] = {nd * per, nd, n, nd * n, n * nd, n, 2 * n, n * per, g2, g2, 3 * n, 3 * n, stack, half, half};
-    size_t off = 0;
-    cplx *part[sizeof(sizes) / sizeof(sizes[0])];
-    for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); off += sizes[i], ++i) part[i] = base ? base + off : nullptr;
-    if (ws) {
-        ws->dets = part[0]; ws->coeffs = part[1]; ws->ot = part[2]; ws->ovlp = part[3]; ws->detw = part[4]; ws->S = part[5];
-        ws->fac = part[6]; ws->ghalf = part[7]; ws->G = part[8]; ws->gsum = part[9]; ws->E = part[10]; ws->esum = part[11];
-        ws->stack = part[12]; ws->logr = (double *)part[13]; ws->detR = (double *)part[14];
-    }
-    return off;
-}
-
-// phi_bp[d, w] <- B(x_0)^H ... B(x_{n-1})^H phi_bp[d, w] for every determinant d: bp_backward with ONE field set and ONE
-// HS potential per walker and step.  Fused propagator: the determinants' slabs one after the other over that V; GEMM
-// chain: the determinants of a walker as one column-stacked operand (k_bp_msd_onebody / k_bp_msd_taylor).  After a
-// re-orthogonalisation log det R of every (d, w) is added to logr [ndet, nw].
-static int bp_backward_msd(afq_handle *h, int nstblz, const BpMsdWs &ws) {
-    const size_t n = h->nw, per = (size_t)h->M * h->nt, nd = h->ndet, slab = n * per;
-    cplx *s_phi = h->phi, *s_xs = h->xs, *s_BH1 = h->BH1, *s_ot = h->ot;
-    double *s_detR = h->detR;
-    const int s_flags = h->flags;
-    h->xs = h->bp_xs; h->BH1 = h->BH1dag; h->ot = ws.ot;
-    h->flags &= ~AFQ_PROP_FREE_PROJECTION;
-    const bool fused = k_prop_fused_supported(h);
-    cplx *A = h->phi_bp, *B = ws.stack, *C = h->phi_bp + nd * slab;     // (the conjugates' half is free until the end)
-    int rc = AFQ_OK;
-    for (int i = 0; i < h->nbp && !rc; ++i) {
-        if ((rc = k_bp_fields(h, i))) break;
-        h->vhs_upper = fused && h->hs_sym;
-        rc = build_vhs(h);
-        if (!rc && fused)
-            for (size_t d = 0; d < nd && !rc; ++d) { h->phi = A + d * slab; rc = k_prop_fused(h); }
-        h->vhs_upper = false;
-        if (rc) break;
-        if (!fused) {
-            if ((rc = k_bp_msd_onebody(h, (int)nd, A, B))) break;
-            if ((rc = k_bp_msd_taylor(h, (int)nd, h->vhs, B, C, A))) break;
-            if ((rc = k_bp_msd_onebody(h, (int)nd, B, A))) break;
-        }
-        if (i != 0 && i % nstblz == 0) {
-            for (size_t d = 0; d < nd && !rc; ++d) {
-                h->phi = A + d * slab; h->detR = ws.detR + d * n;
-                rc = k_reortho(h);
-            }
-            if (!rc) rc = k_bp_msd_logr(h, ws.detR, ws.logr, (long)(nd * n));
-        }
-    }
-    h->phi = s_phi; h->xs = s_xs; h->BH1 = s_BH1; h->ot = s_ot; h->detR = s_detR; h->flags = s_flags;
-    return rc;
-}
-
-int afq_bp_update_msd(afq_handle *h, int ndet, const double *dets, const double *coeffs, int nstblz, int restore_weights,
-                      int eval_energy, int reset, double *est_out, double *detw_out) {
-    AFQ_API(h, "afq_bp_update_msd");
-    // read-only on the walk, as afq_itcf_update: the Green's function the last step left for the next one stays valid
-    const bool s_valid = h && h->greens_valid, s_gsum = h && h->gsum_only;
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
-    if (!h || !dets || !coeffs || !est_out || ndet < 1 || nstblz < 1 || restore_weights < 0 || restore_weights > 2)
-        return AFQ_EINVAL;
-    int rc = need_ready(h, true);
-    if (rc) return rc;
-    if (!h->nbp) AFQ_FAIL(h, AFQ_ESTATE, "back-propagation is not configured");
-    if (h->ndet <= 1 || !h->bpm_ws)
-        AFQ_FAIL(h, AFQ_ESTATE, "afq_bp_update_msd: the handle holds a single-determinant trial (afq_bp_update)");
-    if (ndet != h->ndet)
-        AFQ_FAIL(h, AFQ_EINVAL, "afq_bp_update_msd: " + std::to_string(ndet) + " determinants, the history was configured for " +
-                                    std::to_string(h->ndet));
-    const size_t per = (size_t)h->M * h->nt, n = h->nw, nd = ndet, slab = n * per, gsz = (size_t)2 * h->M * h->M;
-    BpMsdWs ws;
-    bp_msd_carve(h, h->bpm_ws, &ws);
-    AFQ_HIP(h, hipMemcpyAsync(ws.dets, dets, sizeof(cplx) * nd * per, hipMemcpyHostToDevice, h->stream));
-    AFQ_HIP(h, hipMemcpyAsync(ws.coeffs, coeffs, sizeof(cplx) * nd, hipMemcpyHostToDevice, h->stream));
-    AFQ_HIP(h, hipMemsetAsync(ws.logr, 0, sizeof(double) * nd * n, h->stream));
-    {   // every walker starts from D_d in slab d (k_bp_init fills the nw walkers phi_bp points at)
-        cplx *s_bp = h->phi_bp;
-        for (size_t d = 0; d < nd && !rc; ++d) { h->phi_bp = s_bp + d * slab; rc = k_bp_init(h, ws.dets + d * per); }
-        h->phi_bp = s_bp;
-        if (rc) return rc;
-    }
-    if ((rc = bp_backward_msd(h, nstblz, ws))) return rc;
-    // G_d[w] = gab(Q_d, phi_old)^T and <Q_d|phi_old> with Q_d[w] in the role of the trial, determinant by determinant
-    // into the window's own Ghalf / G; every handle field that is lent goes back, version counters included
-    cplx *conj_bp = h->phi_bp + nd * slab;
-    if ((rc = k_conj_copy(h, h->phi_bp, conj_bp, (long)(nd * slab)))) return rc;
-    if (eval_energy && h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagated energies: generic systems only");
-    {
-        cplx *s_phi = h->phi, *s_psi = h->psi, *s_psic = h->psic, *s_ghalf = h->ghalf, *s_G = h->G;
-        const unsigned long long s_version = h->ghalf_version, s_checked = h->closed_checked_version;
-        h->phi = h->phi_old; h->psi_stride = (long)per; h->ghalf = ws.ghalf; h->G = ws.G;
-        for (size_t d = 0; d < nd && !rc; ++d) {
-            h->psi = h->phi_bp + d * slab; h->psic = conj_bp + d * slab;
-            rc = k_greens(h, ws.ovlp + d * n);
-            if (!rc) rc = k_full_G(h);
-            if (!rc && eval_energy) rc = k_energy_full_g(h, ws.G, h->nw, ws.E);     // E[G_d], not E[G_bp]: quadratic in G
-            if (!rc) rc = k_bp_msd_detw(h, ndet, (int)d, ws.coeffs, ws.logr, ws.ovlp, ws.detw, ws.S);
-            if (!rc) rc = k_bp_msd_gsum(h, ndet, (int)d, ws.detw, ws.G, ws.gsum, eval_energy ? ws.E : nullptr, ws.esum);
-        }
-        h->phi = s_phi; h->psi = s_psi; h->psic = s_psic; h->psi_stride = 0; h->ghalf = s_ghalf; h->G = s_G;
-        h->ghalf_version = s_version; h->closed_checked_version = s_checked;
-        if (rc) return rc;
-    }
-    AFQ_HIP(h, hipMemsetAsync(h->bp_est, 0, sizeof(cplx) * (4 + gsz), h->stream));
-    if ((rc = k_bp_msd_finish(h, ndet, restore_weights, ws.detw, ws.S, ws.fac))) return rc;
-    if ((rc = k_bp_msd_accumulate(h, ws.gsum, ws.fac, eval_energy ? ws.esum : nullptr, h->bp_est))) return rc;
-    if (reset) {
-        if ((rc = k_bp_reset(h, false))) return rc;
-        AFQ_HIP(h, hipMemcpyAsync(h->phi_old, h->phi, sizeof(cplx) * per * n, hipMemcpyDeviceToDevice, h->stream));
-    }
-    if ((rc = k_alive(h))) return rc;
-    h->greens_valid = s_valid; h->gsum_only = s_gsum;
-    if ((rc = copy_out(h, detw_out, ws.detw, sizeof(cplx) * n * nd))) return rc;
-    return copy_out(h, est_out, h->bp_est, sizeof(cplx) * (4 + gsz));
-}
-
-int afq_bp_ekt_chunks(afq_handle *h, int nc, int ncy) {
-    if (!h || nc < 0 || ncy < 0) return AFQ_EINVAL;
-    h->bpo_nc = nc; h->bpo_ncy = ncy;
-    return AFQ_OK;
-}
-
-// share of the free device memory the M^4 two-body RDM (one copy on the device) may take
-#define AFQ_BPO_MEM_SHARE 0.5
-
-int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, const double *L, int nL) {
-    if (!h || (ekt && (!h1 || nL < 1 || (L == nullptr && nL != h->K)))) return AFQ_EINVAL;
-    int rc = need_ready(h, true);
-    if (rc) return rc;
-    if (h->ndet > 1 && (two_rdm || ekt))
-        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagated two-body RDM / EKT with a multi-determinant trial (sum_d w_d f[G_d] of quartic / cubic forms)");
-    if (!h->nbp) AFQ_FAIL(h, AFQ_ESTATE, "back-propagation is not configured: afq_bp_configure first");
-    if (ekt && h->kind == AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "EKT: the Hubbard model has no Cholesky vectors");
-    if (two_rdm == 2 && h->kind != AFQ_SYS_UEG)
-        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "structure factor: UEG systems only (no momentum transfers elsewhere)");
-    if (two_rdm < 0 || two_rdm > 2) AFQ_FAIL(h, AFQ_EINVAL, "afq_bp_observables: two_rdm is 0, 1 (two-body RDM) or 2 (structure factor)");
-    const bool sf = two_rdm == 2;
-    if (ekt && !L && h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EINVAL, "EKT: pass the vectors L_x of this system");
-    if (ekt && !L && h->hs_cplx)
-        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "EKT with complex Cholesky vectors: the reference's 4-fold-symmetry form pins nothing");
-    const size_t M = (size_t)h->M, m4 = sf ? (size_t)4 * h->nq : M * M * M * M;
-    hipSetDevice(h->device);
-    dev_free(h->bpo_out);              // a buffer of an earlier call does not count against the budget
-    if (two_rdm && !sf) {
-        size_t fr = 0, tot = 0;
-        AFQ_HIP(h, hipMemGetInfo(&fr, &tot));
-        const double need = 16.0 * (double)m4;
-        if (need > AFQ_BPO_MEM_SHARE * (double)fr)
-            AFQ_FAIL(h, AFQ_ENOMEM, "two-body RDM: " + std::to_string((unsigned long long)need) +
-                                        " bytes (16 M^4) exceed half of the free device memory (" +
-                                        std::to_string((unsigned long long)fr) + " bytes)");
-    }
-    dev_free(h->bpo_h1); dev_free(h->bpo_L);
-    h->bpo_two = h->bpo_ekt = h->bpo_sf = 0; h->bpo_nL = 0;
-    if (ekt) {
-        if ((rc = dev_upload(h, &h->bpo_h1, h1, M * M))) return rc;
-        if (L && (rc = dev_upload(h, &h->bpo_L, L, (size_t)nL * M * M))) return rc;
-        h->bpo_nL = nL;
-    }
-    if ((two_rdm || ekt) && (rc = dev_alloc(h, &h->bpo_out, (two_rdm ? m4 : 0) + (ekt ? 2 * M * M : 0)))) return rc;
-    h->bpo_two = two_rdm ? 1 : 0; h->bpo_ekt = ekt ? 1 : 0; h->bpo_sf = sf ? 1 : 0;
-    return AFQ_OK;
-}
-
-// ---------------------------------------------------------------- imaginary-time Green's function (k_itcf.hip)
-int afq_itcf_configure(afq_handle *h, int nmax, int neqlb, int stable, int restore_weights) {
-    if (!h || nmax < 1 || neqlb < 0) return AFQ_EINVAL;
-    int rc = need_ready(h, true);
-    if (rc) return rc;
-    if (h->M > 128) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "ITCF: M > 128 (the batched Gauss-Jordan inverse)");
-    if (h->kind == AFQ_SYS_UEG) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "ITCF: no propagator matrix for the UEG (itcf.py:114-122)");
-    if (h->hirsch && restore_weights)
-        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "restore_weights with discrete fields: FieldConfig.push records no weight factors (walkers/stack.py:35-49)");
-    if (h->ndet > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "ITCF: multi-determinant trials");
-    const int n = nmax + neqlb;
-    if (h->nbp && h->nbp != n)
-        AFQ_FAIL(h, AFQ_ESTATE, "ITCF: a field history of " + std::to_string(h->nbp) + " steps is configured, the window needs " +
-                                    std::to_string(n));
-    // (afq_bp_configure refuses continuous Hubbard fields, free projection and general complex Cholesky vectors)
-    if (!h->nbp && (rc = afq_bp_configure(h, n))) return rc;
-    h->it_nmax = nmax; h->it_neqlb = neqlb; h->it_stable = stable ? 1 : 0; h->it_restore = restore_weights ? 1 : 0;
-    return AFQ_OK;
-}
-
-// the window's device scratch, kept on the handle and grown on demand (a larger window frees the old buffer first)
-static int itcf_scratch(afq_handle *h, size_t n, cplx **out) {
-    if (n > h->it_ws_len) {
-        if (h->it_ws) { hipStreamSynchronize(h->stream); dev_free(h->it_ws); h->it_ws_len = 0; }
-        const int rc = dev_alloc(h, &h->it_ws, n);
-        if (rc) return rc;
-        h->it_ws_len = n;
-    }
-    *out = h->it_ws;
-    return AFQ_OK;
-}
-
-static int itcf_greens(afq_handle *h, cplx *psiR, cplx *psiL, cplx *psiLc, cplx *ovlp, cplx *ghalf, cplx *G, cplx *P, cplx *Q) {
-    // P = gab(psi_L, psi_R) per spin: the Green's function of psi_R with psi_L[w] in the role of the trial, as the
-    // back-propagated G of bp_update.  Its Ghalf and G go to the window's own buffers: the handle's Ghalf is the walk's
-    // cached Green's function, which the next step and the next re-orthogonalisation reuse (and with it whatever was
-    // contracted from it: the version counters go back to where they were), and the handle's G is walker state of the
-    // mixed one_rdm (accumulated by every estimator update, carried by comb, copy and pack)
-    const size_t per = (size_t)h->M * h->nt;
-    int rc = k_conj_copy(h, psiL, psiLc, (long)(per * h->nw));
-    if (rc) return rc;
-    cplx *s_phi = h->phi, *s_psi = h->psi, *s_psic = h->psic, *s_ghalf = h->ghalf, *s_G = h->G;
-    const unsigned long long s_version = h->ghalf_version, s_checked = h->closed_checked_version;
-    h->phi = psiR; h->psi = psiL; h->psic = psiLc; h->psi_stride = (long)per; h->ghalf = ghalf; h->G = G;
-    rc = k_greens(h, ovlp);
-    if (!rc) rc = k_full_G(h);
-    h->phi = s_phi; h->psi = s_psi; h->psic = s_psic; h->psi_stride = 0; h->ghalf = s_ghalf; h->G = s_G;
-    h->ghalf_version = s_version; h->closed_checked_version = s_checked;
-    if (rc) return rc;
-    return k_itcf_projectors(h, G, P, Q);
-}
-
-int afq_itcf_update(afq_handle *h, const double *psi_T, int nstblz, double *spgf_out, double *denom_out) {
-    AFQ_API(h, "afq_itcf_update");
-    // the window is read-only on the walk: the Green's function the last step left for the next one stays valid (a window
-    // that fails half way leaves it invalid, which only costs a recomputation)
-    const bool s_valid = h && h->greens_valid, s_gsum = h && h->gsum_only;
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
-    if (!h || !psi_T || !spgf_out || !denom_out || nstblz < 1) return AFQ_EINVAL;
-    int rc = need_ready(h, true);
-    if (rc) return rc;
-    if (!h->it_nmax) AFQ_FAIL(h, AFQ_ESTATE, "ITCF is not configured: afq_itcf_configure first");
-    if (h->nbp != h->it_nmax + h->it_neqlb) AFQ_FAIL(h, AFQ_ESTATE, "ITCF: the field history changed length");
-    const int M = h->M, nw = h->nw, nmax = h->it_nmax;
-    const size_t per = (size_t)M * h->nt, mm = (size_t)M * M, g2 = 2 * mm * nw, nspgf = (size_t)(nmax + 1) * 4 * mm;
-    // psi_L(t) is read for every slice by the stable chain, for t = 0 only by the unstable one
-    const bool stable = h->it_stable != 0;
-    const int nkeep = stable ? nmax : 1;
-    const bool gen = !h->hirsch;
-    // scratch in complex units: psi_L, psi_R (x2), conj(psi_L), BT2^-1, B, B^-1, P, Q, Ggr, Gls, T, the Generic Taylor
-    // workspace and fields or the discrete diagonals, wfac, [denom | spgf], determinants (mantissa, exponent), overlaps,
-    // the parked ot / detR of the re-orthogonalisation, the Ghalf and the G of the window's Green's functions
-    const size_t sizes[] = {(size_t)nkeep * nw * per, nw * per, nw * per, nw * per, 2 * mm, g2, g2, g2, g2, g2, g2, g2,
-                            gen ? 2 * nw * mm + g2 : 0, gen ? (size_t)nw * h->K : 2 * (size_t)nw * M, (size_t)nw,
-                            1 + nspgf, (size_t)nw + 2, (size_t)nw + 2, (size_t)nw, (size_t)nw, (size_t)nw, nw * per, g2};
-    size_t total = 0;
-    for (size_t x : sizes) total += x;
-    {
-        size_t fr = 0, tot = 0;
-        AFQ_HIP(h, hipMemGetInfo(&fr, &tot));
-        const double need = 16.0 * (double)nw * nkeep * per;
-        const double avail = (double)fr + 16.0 * (double)h->it_ws_len;   // (a buffer that has to grow is freed first)
-        if (need > 0.5 * avail)
-            AFQ_FAIL(h, AFQ_ENOMEM, "ITCF: the stored psi_L take " + std::to_string((unsigned long long)need) +
-                                        " bytes, more than half of the free device memory (" +
-                                        std::to_string((unsigned long long)avail) + " bytes)");
-    }
-    cplx *base;
-    if ((rc = itcf_scratch(h, total, &base))) return rc;
-    cplx *part[sizeof(sizes) / sizeof(sizes[0])];
-    for (size_t i = 0, off = 0; i < sizeof(sizes) / sizeof(sizes[0]); off += sizes[i], ++i) part[i] = base + off;
-    cplx *psiL = part[0], *psiR = part[1], *psiR2 = part[2], *psiLc = part[3], *BT2inv = part[4], *B = part[5];
-    cplx *Binv = part[6], *P = part[7], *Q = part[8], *Ggr = part[9], *Gls = part[10], *T = part[11];
-    cplx *ws = part[12], *xs = part[13], *wfac = part[14], *est = part[15], *detm = part[16];
-    int *dete = (int *)part[17];
-    cplx *ovlp = part[18], *tmp_ot = part[19];
-    double *tmp_detR = (double *)part[20], *f = (double *)part[13];
-    cplx *wghalf = part[21], *wG = part[22];
-    // BT2^-1 per spin
-    AFQ_HIP(h, hipMemcpyAsync(BT2inv, h->BH1, sizeof(cplx) * 2 * mm, hipMemcpyDeviceToDevice, h->stream));
-    if ((rc = k_gj_inverse(h, BT2inv, M, 2, detm, dete))) return rc;
-    // 1. psi_L(t) = B_t^H psi_L(t+1) from psi_L(n) = psi_T: the back-propagation of bp_update, psi_L(t < nkeep) kept
-    AFQ_HIP(h, hipMemcpyAsync(h->phi_bp + per * nw, psi_T, sizeof(cplx) * per, hipMemcpyHostToDevice, h->stream));
-    if ((rc = k_bp_init(h, h->phi_bp + per * nw))) return rc;
-    if ((rc = bp_backward(h, nstblz, psiL, nkeep))) return rc;
-    // 2. weights of the window (the alive flags of the last backward step mark the walkers with a complete window)
-    AFQ_HIP(h, hipMemsetAsync(est, 0, sizeof(cplx) * (1 + nspgf), h->stream));
-    if ((rc = k_itcf_weights(h, h->it_restore, wfac, est))) return rc;
-    // 3. forward: psi_R, P(t), the B matrices and the chains
-    AFQ_HIP(h, hipMemcpyAsync(psiR, h->phi_old, sizeof(cplx) * nw * per, hipMemcpyDeviceToDevice, h->stream));
-    for (int tau = 0; tau < nmax; ++tau) {
-        if (stable || tau == 0) {
-            if ((rc = itcf_greens(h, psiR, psiL + (size_t)tau * nw * per, psiLc, ovlp, wghalf, wG, P, Q))) return rc;
-        }
-        if (tau == 0) {
-            AFQ_HIP(h, hipMemcpyAsync(Ggr, Q, sizeof(cplx) * g2, hipMemcpyDeviceToDevice, h->stream));
-            AFQ_HIP(h, hipMemcpyAsync(Gls, P, sizeof(cplx) * g2, hipMemcpyDeviceToDevice, h->stream));
-            if ((rc = k_itcf_accumulate(h, Ggr, Gls, wfac, est + 1))) return rc;
-        }
-        if (gen) {
-            cplx *s_xs = h->xs;
-            h->xs = xs;
-            rc = k_itcf_fields(h, xs, tau);
-            if (!rc) rc = build_vhs(h);
-            h->xs = s_xs;
-            if (!rc) rc = k_itcf_generic_b(h, h->vhs, h->BH1, BT2inv, B, Binv, ws, detm, dete);
-        } else {
-            rc = k_itcf_hirsch_b(h, tau, h->BH1, BT2inv, B, Binv, f);
-        }
-        if (rc) return rc;
-        if (stable) {                                   // Ggr <- B (I - P) Ggr, Gls <- Gls P B^-1
-            if ((rc = k_itcf_mul(h, Q, Ggr, T)) || (rc = k_itcf_mul(h, B, T, Ggr))) return rc;
-            if ((rc = k_itcf_mul(h, Gls, P, T)) || (rc = k_itcf_mul(h, T, Binv, Gls))) return rc;
-        } else {                                        // Ggr <- B Ggr, Gls <- Gls B^-1
-            if ((rc = k_itcf_mul(h, B, Ggr, T))) return rc;
-            std::swap(Ggr, T);
-            if ((rc = k_itcf_mul(h, Gls, Binv, T))) return rc;
-            std::swap(Gls, T);
-        }
-        if ((rc = k_itcf_accumulate(h, Ggr, Gls, wfac, est + 1 + (size_t)(tau + 1) * 4 * mm))) return rc;
-        if (stable && tau + 1 < nmax) {
-            if ((rc = k_itcf_propagate(h, B, psiR, psiR2))) return rc;
-            std::swap(psiR, psiR2);
-            if (tau != 0 && tau % nstblz == 0) {
-                cplx *s_phi = h->phi, *s_ot = h->ot;
-                double *s_detR = h->detR;
-                const int s_flags = h->flags;
-                h->phi = psiR; h->ot = tmp_ot; h->detR = tmp_detR; h->flags &= ~AFQ_PROP_FREE_PROJECTION;
-                rc = k_reortho(h);
-                h->phi = s_phi; h->ot = s_ot; h->detR = s_detR; h->flags = s_flags;
-                if (rc) return rc;
-            }
-        }
-    }
-    // 4. FieldConfig.reset + copy_init_wfn: the next window starts from the walkers now
-    if ((rc = k_bp_reset(h, false))) return rc;
-    AFQ_HIP(h, hipMemcpyAsync(h->phi_old, h->phi, sizeof(cplx) * per * nw, hipMemcpyDeviceToDevice, h->stream));
-    if ((rc = k_alive(h))) return rc;
-    h->greens_valid = s_valid; h->gsum_only = s_gsum;
-    if ((rc = copy_out(h, denom_out, est, sizeof(cplx)))) return rc;
-    return copy_out(h, spgf_out, est + 1, sizeof(cplx) * nspgf);
-}
-
-int afq_local_energy_full_g(afq_handle *h, const double *G, int n, double *E_out) {
-    if (!h || !G || !E_out || n < 1) return AFQ_EINVAL;
-    if (h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "full-G Cholesky energy: generic systems only");
-    hipSetDevice(h->device);
-    const size_t gsz = (size_t)2 * h->M * h->M * n;
-    cplx *Gd = nullptr, *Ed = nullptr;
-    int rc;
-    if ((rc = dev_upload(h, &Gd, G, gsz))) return rc;
-    if ((rc = dev_alloc(h, &Ed, (size_t)3 * n))) { dev_free(Gd); return rc; }
-    rc = k_energy_full_g(h, Gd, n, Ed);
-    if (!rc) rc = copy_out(h, E_out, Ed, sizeof(cplx) * 3 * n);
-    dev_free(Gd); dev_free(Ed);
-    return rc;
-}
-
-int afq_ueg_pair_sums(afq_handle *h, const double *G, int n, double *E_out, double *two_rdm_out) {
-    if (!h || !G || !E_out || !two_rdm_out || n < 1) return AFQ_EINVAL;
-    if (h->kind != AFQ_SYS_UEG) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "UEG pair sums: UEG systems only");
-    hipSetDevice(h->device);
-    const size_t gsz = (size_t)2 * h->M * h->M * n, tsz = (size_t)4 * h->nq * n;
-    cplx *Gd = nullptr, *Ed = nullptr, *Td = nullptr;
-    int rc;
-    if ((rc = dev_upload(h, &Gd, G, gsz))) return rc;
-    if ((rc = dev_alloc(h, &Ed, (size_t)3 * n)) || (rc = dev_alloc(h, &Td, tsz))) { dev_free(Gd); dev_free(Ed); return rc; }
-    rc = k_ueg_pair_sums(h, Gd, n, Ed, Td);
-    if (!rc) rc = copy_out(h, E_out, Ed, sizeof(cplx) * 3 * n);
-    if (!rc) rc = copy_out(h, two_rdm_out, Td, sizeof(cplx) * tsz);
-    dev_free(Gd); dev_free(Ed); dev_free(Td);
-    return rc;
-}
-
-int afq_hubbard_energy_full_g(afq_handle *h, const double *G, int n, double *E_out) {
-    if (!h || !G || !E_out || n < 1) return AFQ_EINVAL;
-    if (h->kind != AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "full-G Hubbard energy: Hubbard systems only");
-    hipSetDevice(h->device);
-    cplx *Gd = nullptr, *Ed = nullptr;
-    int rc;
-    if ((rc = dev_upload(h, &Gd, G, (size_t)2 * h->M * h->M * n))) return rc;
-    if ((rc = dev_alloc(h, &Ed, (size_t)3 * n))) { dev_free(Gd); return rc; }
-    rc = k_energy_hubbard_full_g(h, Gd, n, Ed);
-    if (!rc) rc = copy_out(h, E_out, Ed, sizeof(cplx) * 3 * n);
-    dev_free(Gd); dev_free(Ed);
-    return rc;
 }
 
 int afq_walkers_det_weights(afq_handle *h, double *weights_out) {

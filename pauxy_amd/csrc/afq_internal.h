@@ -178,6 +178,8 @@ struct afq_handle {
     cplx *BH1dag = nullptr;         // [2, M, M] BH1^H
     cplx *bp_xs = nullptr;          // [nw, K]
     cplx *bp_est = nullptr;         // [4 + 2 M M]
+    cplx *bp_ot = nullptr;          // [nw] where a re-orthogonalisation of phi_bp leaves ot and detR while the walkers'
+    double *bp_detR = nullptr;      // own are parked (single-determinant windows)
     // multi-determinant windows (afq_bp_update_msd, k_bp_msd.hip): with ndet > 1 phi_bp holds [ndet, nw, M, nt] and its
     // conjugate behind it, and bpm_ws the window's own scratch (carved by afq_bp_update_msd), bpm_ws_len complex elements
     cplx *bpm_ws = nullptr;
@@ -412,6 +414,16 @@ struct PhaseTimer {
             h->t_ms[slot] += ms;
         }
     }
+};
+
+// Lends a handle field for a scope: the k_* launchers read their operands from the handle, so code that has them work
+// on something else overwrites the field here, and every way out of the scope puts the old value back.
+template <class T> struct Lent {
+    T &slot; T saved;
+    Lent(T &s, T v) : slot(s), saved(s) { slot = v; }
+    ~Lent() { slot = saved; }
+    Lent(const Lent &) = delete;
+    Lent &operator=(const Lent &) = delete;
 };
 
 // Brackets ONE kernel launch with a start/stop event pair on the handle's stream when
