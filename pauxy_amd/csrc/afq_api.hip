@@ -84,8 +84,8 @@ void free_walkers(afq_handle *h) {
     dev_free(h->weight); dev_free(h->unscaled); dev_free(h->detR); dev_free(h->log_detR);
     dev_free(h->ot); dev_free(h->ehyb); dev_free(h->phase); dev_free(h->eloc);
     dev_free(h->ghalf_all); h->ghalf = nullptr; dev_free(h->G); dev_free(h->ovlp_old); dev_free(h->ovlp_new);
-    dev_free(h->xi); dev_free(h->vbias_all); h->vbias = nullptr; dev_free(h->ghalf_sum); h->gsum_version = 0; h->vbias_version = 0;
-    dev_free(h->gdiag); h->gdiag_version = 0; h->gdiag_parts = 0;
+    dev_free(h->xi); dev_free(h->vbias_all); h->vbias = nullptr; dev_free(h->ghalf_sum); h->gf.gsum.clear(); h->gf.vbias.clear();
+    dev_free(h->gdiag); h->gf.gdiag.clear(); h->gdiag_parts = 0;
     dev_free(h->detd); dev_free(h->detd_a); dev_free(h->detw); dev_free(h->energy_all);
     dev_free(h->msd_gs); dev_free(h->msd_S); dev_free(h->msd_D); h->msd_fb_gbar = false;
     dev_free(h->hs_oinv); dev_free(h->hs_u); dev_free(h->hs_fields); dev_free(h->hs_used); dev_free(h->hs_alive0);
@@ -307,7 +307,7 @@ static int upload_rchol(afq_handle *h, const double *rchol, bool real) {
     for (size_t q = 0; q < nq; ++q)
         for (int n = 0; n < K; ++n) re[q * h->ld_rc + n] = rchol[2 * (q * K + n)];
     h->rchol_real = real;
-    ++h->ghalf_version;                 // force-bias partials contracted with the old vectors are stale
+    h->gf.rewritten();                  // force-bias partials contracted with the old vectors are stale
     h->rchol_same = h->na == h->nb && memcmp(rchol, rchol + 2 * (size_t)h->na * h->M * K, sizeof(double) * 2 * (size_t)h->na * h->M * K) == 0;
     k_free_atil(h->atil);                  // the quadratic-form operand belongs to the old vectors
     h->atil_unavailable = false;
@@ -327,7 +327,7 @@ static int upload_rchol(afq_handle *h, const double *rchol, bool real) {
 
 int afq_set_system_generic(afq_handle *h, int M, int K, int na, int nb, const double *hs_pot,
                            const double *rchol, const double *H1, double ecore) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !hs_pot || !rchol || !H1) return AFQ_EINVAL;
     int rc = set_dims(h, AFQ_SYS_GENERIC, M, K, na, nb);
     if (rc) return rc;
@@ -375,7 +375,7 @@ int afq_set_system_generic(afq_handle *h, int M, int K, int na, int nb, const do
 // complex Cholesky vectors: Re and Im parts as two transposed real panels (afq_internal.h: hs_cplx)
 int afq_set_system_generic_c128(afq_handle *h, int M, int K, int na, int nb, const double *hs_pot,
                                 const double *rchol, const double *H1, double ecore) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !hs_pot || !rchol || !H1) return AFQ_EINVAL;
     if (M <= 0 || K <= 0) AFQ_FAIL(h, AFQ_EINVAL, "bad dimensions");
     const size_t mm = (size_t)M * M, nq = (size_t)(na + nb) * M;
@@ -437,7 +437,7 @@ int afq_set_system_generic_c128(afq_handle *h, int M, int K, int na, int nb, con
 }
 
 int afq_set_system_hubbard(afq_handle *h, int M, int na, int nb, double U, const double *T) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !T) return AFQ_EINVAL;
     int rc = set_dims(h, AFQ_SYS_HUBBARD, M, M, na, nb);
     if (rc) return rc;
@@ -473,7 +473,7 @@ int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64
                        const int64_t *kpq_i, const int64_t *kpq_kpq, const int64_t *pmq_off,
                        const int64_t *pmq_i, const int64_t *pmq_pmq, const double *vqvec, double vol,
                        const double *H1diag, double ecore) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !iA_colptr || !iB_colptr || !kpq_off || !pmq_off || !vqvec || !H1diag) return AFQ_EINVAL;
     int rc = set_dims(h, AFQ_SYS_UEG, M, 2 * nq, na, nb);
     if (rc) return rc;
@@ -559,7 +559,7 @@ int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64
 }
 
 int afq_set_trial(afq_handle *h, const double *psi) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !psi) return AFQ_EINVAL;
     if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "set the system before the trial");
     if (h->ndet > 1) AFQ_FAIL(h, AFQ_ESTATE, "a multi-determinant trial is set; set the system again first");
@@ -572,7 +572,7 @@ int afq_set_trial(afq_handle *h, const double *psi) {
 }
 
 int afq_set_trial_multi(afq_handle *h, int ndet, const double *psi, const double *coeffs, const double *rchol) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !psi || !coeffs || !rchol || ndet < 1) return AFQ_EINVAL;
     if (h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "multi-determinant trials need a generic system");
     if (h->nw) AFQ_FAIL(h, AFQ_ESTATE, "set the trial before allocating walkers");
@@ -628,7 +628,7 @@ int afq_set_trial_multi(afq_handle *h, int ndet, const double *psi, const double
 
 int afq_set_propagator(afq_handle *h, const double *BH1, const double *mf_shift, double dt, int exp_order,
                        int flags) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !BH1 || !mf_shift || dt <= 0 || exp_order < 0) return AFQ_EINVAL;
     if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "set the system before the propagator");
     hipSetDevice(h->device);
@@ -656,7 +656,7 @@ int afq_set_propagator(afq_handle *h, const double *BH1, const double *mf_shift,
 
 // ------------------------------------------------------------------ walkers
 int afq_walkers_alloc(afq_handle *h, int nw) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || nw <= 0) return AFQ_EINVAL;
     if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "set the system before allocating walkers");
     hipSetDevice(h->device);
@@ -754,7 +754,7 @@ static int field_info(afq_handle *h, int field, void **base, size_t *bytes) {
 static int ensure_spin_ghalf(afq_handle *h);
 
 int afq_walkers_set(afq_handle *h, int field, const void *host, int first, int count) {
-    if (h && (field == AFQ_F_PHI || field == AFQ_F_GHALF)) { h->greens_valid = false; h->gsum_only = false; ++h->ghalf_version; }
+    if (h && (field == AFQ_F_PHI || field == AFQ_F_GHALF)) { h->gf.drop(); h->gf.rewritten(); }
     if (!h || !host) return AFQ_EINVAL;
     if (!h->nw) AFQ_FAIL(h, AFQ_ESTATE, "no walkers allocated");
     if (first < 0 || count < 0 || first + count > h->nw) AFQ_FAIL(h, AFQ_EINVAL, "walker range out of bounds");
@@ -788,32 +788,33 @@ int afq_walkers_device_ptr(afq_handle *h, int field, void **dev_ptr, int64_t *by
     if (rc) return rc;
     // a reader of the per-spin Ghalf must find the CURRENT walkers' there: a step announced with afq_estimates_fuse_next
     // leaves only overlap + spin sum behind
-    if (field == AFQ_F_GHALF && h->gsum_only) {
+    if (field == AFQ_F_GHALF && h->gf.kept == GreensCache::SUM_ONLY) {
         hipSetDevice(h->device);
         if ((rc = ensure_spin_ghalf(h))) return rc;
     }
-    h->greens_valid = false; h->gsum_only = false; h->greens_cache = false;             // the caller may write through the pointer
+    h->gf.drop(); h->gf.enabled = false;                 // the caller may write through the pointer
     *dev_ptr = base;
     if (bytes_per_walker) *bytes_per_walker = (int64_t)bytes;
     return AFQ_OK;
 }
 
 // ----------------------------------------------------------------- hot path
-static int greens_any(afq_handle *h, cplx *det_out, bool with_ghalf);
+static int greens_any(afq_handle *h, cplx *det_out, bool with_ghalf, GreensRequest req = GreensRequest(),
+                      GreensResult *res = nullptr);
 
 // The last step left its Green's function behind as overlap + spin sum of Ghalf only (afq_propagate_finish on a step the
 // driver announced with afq_estimates_fuse_next): somebody wants the per-spin Ghalf after all -- evaluate it.
 static int ensure_spin_ghalf(afq_handle *h) {
-    if (!h->gsum_only) return AFQ_OK;
-    h->gsum_only = false;
+    if (h->gf.kept != GreensCache::SUM_ONLY) return AFQ_OK;
+    h->gf.drop();
     const int rc = greens_any(h, h->ovlp_new, true);
-    h->greens_valid = rc == AFQ_OK;
+    if (rc == AFQ_OK) h->gf.keep(GreensCache::FULL);
     return rc;
 }
 
 int afq_greens(afq_handle *h, int want_G, double *ovlp_out) {
     AFQ_API(h, "afq_greens");
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h) return AFQ_EINVAL;
     int rc = need_ready(h, false);
     if (rc) return rc;
@@ -829,7 +830,7 @@ int afq_greens(afq_handle *h, int want_G, double *ovlp_out) {
 }
 
 int afq_inverse_overlap(afq_handle *h, double *oinv_out, double *ovlp_out) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !oinv_out) return AFQ_EINVAL;
     int rc = need_ready(h, false);
     if (rc) return rc;
@@ -852,7 +853,7 @@ int afq_inverse_overlap(afq_handle *h, double *oinv_out, double *ovlp_out) {
 
 int afq_calc_overlap(afq_handle *h, double *ovlp_out) {
     AFQ_API(h, "afq_calc_overlap");
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h) return AFQ_EINVAL;
     int rc = need_ready(h, false);
     if (rc) return rc;
@@ -867,15 +868,14 @@ int afq_calc_overlap(afq_handle *h, double *ovlp_out) {
 // Green's function (with_ghalf) or overlap only, for every determinant of the trial.  Multi-determinant:
 // per-determinant Ghalf_d / <D_d|phi> into the slices, then weights conj(c_d) <D_d|phi> and their sum
 // (walkers/multi_det.py:194-229 and :135-162).
-static int greens_any(afq_handle *h, cplx *det_out, bool with_ghalf) {
+static int greens_any(afq_handle *h, cplx *det_out, bool with_ghalf, GreensRequest req, GreensResult *res) {
     int rc;
-    if (h->ndet <= 1) return with_ghalf ? k_greens(h, det_out) : k_overlap(h, det_out);
+    if (h->ndet <= 1) return with_ghalf ? k_greens(h, det_out, req, res) : k_overlap(h, det_out, req, res);
     for (int d = 0; d < h->ndet; ++d) {
         select_det(h, d);
         cplx *dd = h->detd + (size_t)d * h->nw;
-        h->det_a_out = with_ghalf ? h->detd_a + (size_t)d * h->nw : nullptr;
-        rc = with_ghalf ? k_greens(h, dd) : k_overlap(h, dd);
-        h->det_a_out = nullptr;
+        req.det_a = with_ghalf ? h->detd_a + (size_t)d * h->nw : nullptr;
+        rc = with_ghalf ? k_greens(h, dd, req, res) : k_overlap(h, dd, req, res);
         if (rc) { select_det(h, 0); return rc; }
     }
     select_det(h, 0);
@@ -940,13 +940,14 @@ int afq_propagate_begin(afq_handle *h, const double *xi) {
     if (!fp || (h->flags & AFQ_PROP_FORCE_BIAS)) {
         PhaseTimer t(h, T_GREENS);                         // continuous.py:245
         // (the spin sum alone will not do when this step needs more than the force bias: local-energy weights, one_rdm)
-        const bool sum_ok = h->gsum_only && (h->flags & AFQ_PROP_HYBRID) && !h->rdm_on &&
+        const GreensCache::Kept kept = h->gf.kept;
+        const bool sum_ok = kept == GreensCache::SUM_ONLY && (h->flags & AFQ_PROP_HYBRID) && !h->rdm_on &&
                             (h->kind == AFQ_SYS_GENERIC ||
-                             (h->kind == AFQ_SYS_HUBBARD && h->gdiag && h->gdiag_version == h->ghalf_version));
-        if (h->greens_valid || sum_ok) std::swap(h->ovlp_old, h->ovlp_new);   // computed at the end of the last step
-                                                                   // (gsum_only: as overlap + spin sum of Ghalf, all the force bias reads)
+                             (h->kind == AFQ_SYS_HUBBARD && h->gdiag && h->gf.gdiag.current(h->gf)));
+        if (kept == GreensCache::FULL || sum_ok) std::swap(h->ovlp_old, h->ovlp_new);   // computed at the end of the last step
+                                                     // (SUM_ONLY: as overlap + spin sum of Ghalf, all the force bias reads)
         else if ((rc = greens_any(h, h->ovlp_old, true))) return rc;
-        h->greens_valid = false; h->gsum_only = false;
+        h->gf.drop();                                      // (the step rewrites phi)
         const bool le = !fp && !(h->flags & AFQ_PROP_HYBRID);
         // (the plane-wave fast step gathers the force bias from the occupied rows of G built from Ghalf: no full G)
         if ((h->kind == AFQ_SYS_UEG && ((h->flags & AFQ_PROP_FORCE_BIAS) || le) && !k_ueg_fast_supported(h)) ||
@@ -1047,10 +1048,11 @@ int afq_propagate_finish(afq_handle *h, double eshift_re, double eshift_im) {
         // step's Green's function needs (continuous.py:245 of step n+1), so factorise once: this call
         // leaves Ghalf of the NEW phi behind and the next afq_propagate / afq_estimates_update reuses it.
         const bool le_msd = h->ndet > 1 && !fp && !(h->flags & AFQ_PROP_HYBRID);
-        h->fuse_weight_done = false;
-        h->fuse_weight_req = h->ndet == 1 && !le_msd;       // single determinant: k_greens may take the weight update along
-        h->fuse_eshift = cmake(eshift_re, eshift_im);
-        if (h->greens_cache && !fp) {
+        GreensRequest req;
+        GreensResult res;
+        req.ride_weight = h->ndet == 1 && !le_msd;          // single determinant: k_greens may take the weight update along
+        req.eshift = cmake(eshift_re, eshift_im);
+        if (h->gf.enabled && !fp) {
             // afq_estimates_fuse_next told us that nothing but the next step's force bias will read this Green's function
             // (no comb, no energy, no block end behind this step): when that force bias contracts the spin sum
             // Ghalf_a + Ghalf_b (k_fb_use_sum), the per-spin Ghalf -- 2/3 of the kernel's stores, 20 MB per step at C3 --
@@ -1059,25 +1061,16 @@ int afq_propagate_finish(afq_handle *h, double eshift_re, double eshift_im) {
             //  268 MB of Ghalf per step at C4 that nobody reads)
             const bool fb_sum = h->kind == AFQ_SYS_GENERIC && k_fb_use_sum(h);
             const bool fb_diag = h->kind == AFQ_SYS_HUBBARD && !h->hirsch && h->psicT && k_greens_big_supported(h);
-            h->ghalf_skip_store = h->fuse_est_req && h->ndet == 1 && (fb_sum || fb_diag) &&
-                                  (h->flags & AFQ_PROP_HYBRID) && (h->flags & AFQ_PROP_FORCE_BIAS) && !h->rdm_on &&
-                                  h->nbp == 0 && h->psi_stride == 0;
-            h->ghalf_skipped = false;
-            rc = greens_any(h, h->ovlp_new, true);
-            h->fuse_weight_req = false;
-            h->ghalf_skip_store = false;
-            if (rc) return rc;
-            h->greens_valid = !h->ghalf_skipped;
-            h->gsum_only = h->ghalf_skipped;
-        } else {
-            rc = greens_any(h, h->ovlp_new, false);
-            h->fuse_weight_req = false;
-            if (rc) return rc;
-        }
+            req.may_skip_store = h->fuse_est_req && h->ndet == 1 && (fb_sum || fb_diag) &&
+                                 (h->flags & AFQ_PROP_HYBRID) && (h->flags & AFQ_PROP_FORCE_BIAS) && !h->rdm_on &&
+                                 h->nbp == 0 && h->psi_stride == 0;
+            if ((rc = greens_any(h, h->ovlp_new, true, req, &res))) return rc;
+            h->gf.keep(res.store_skipped ? GreensCache::SUM_ONLY : GreensCache::FULL);
+        } else if ((rc = greens_any(h, h->ovlp_new, false, req, &res))) return rc;
         if (h->ndet > 1 && !fp && !(h->flags & AFQ_PROP_HYBRID)) {
             if ((rc = k_msd_energy_combine(h))) return rc;
         }
-        if ((rc = k_update_weight(h, cmake(eshift_re, eshift_im)))) return rc;
+        if (!res.weight_rode && (rc = k_update_weight(h, req.eshift))) return rc;
         if (h->nbp > 0 && !fp && (rc = k_bp_push(h))) return rc;     // FieldConfig.update (continuous.py:288-289)
     }
     if (h->fuse_est_req) {                                // afq_estimates_fuse_next: the weight update took the terms along
@@ -1126,17 +1119,17 @@ int afq_reortho(afq_handle *h, double *detR_out) {
     AFQ_API(h, "afq_reortho");
     if (!h) return AFQ_EINVAL;
     int rc = need_ready(h, false);
-    if (rc) { h->greens_valid = false; h->gsum_only = false; return rc; }
+    if (rc) { h->gf.drop(); return rc; }
     // Ghalf = (phi^T psi*)^-1 phi^T does not change when phi -> phi R^-1, so a Green's function kept from
     // the end of the last step stays valid across the QR; only the cached overlap picks up 1 / det R.
-    const bool keep = (h->greens_valid || h->gsum_only) && h->ndet == 1;
-    const bool sum_only = h->gsum_only;                  // (the spin sum of Ghalf is as invariant as Ghalf itself)
-    h->greens_valid = false; h->gsum_only = false;
+    // (the spin sum of Ghalf is as invariant as Ghalf itself: either kept state stays)
+    const GreensCache::Kept kept = h->gf.take();
+    const bool keep = kept != GreensCache::NOTHING && h->ndet == 1;
     bool scaled = false;
     { PhaseTimer t(h, T_QR); if ((rc = k_reortho(h, keep ? h->ovlp_new : nullptr, &scaled))) return rc; }
     if (keep) {
         if (!scaled && (rc = k_scale_by_inverse(h, h->ovlp_new, h->detR))) return rc;
-        h->greens_valid = !sum_only; h->gsum_only = sum_only;
+        h->gf.keep(kept);
     }
     // the cached overlap above needs det R itself; walker.detR / walker.ot / log_detR take the shifted one
     if (h->log_shift_on && (rc = k_log_shift_reortho(h))) return rc;
@@ -1258,7 +1251,7 @@ int afq_vhs(afq_handle *h, const double *xs, double *vhs_out) {
 }
 
 int afq_apply_exponential(afq_handle *h, const double *vhs) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !vhs) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;
@@ -1280,7 +1273,7 @@ int afq_apply_exponential(afq_handle *h, const double *vhs) {
 }
 
 int afq_kinetic(afq_handle *h) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;
@@ -1310,14 +1303,14 @@ int afq_popcontrol_comb(afq_handle *h, double r, double target_weight, int32_t *
     AFQ_API(h, "afq_popcontrol_comb");
     if (!h) return AFQ_EINVAL;
     int rc = need_ready(h, false);
-    if (rc) { h->greens_valid = false; h->gsum_only = false; return rc; }
+    if (rc) { h->gf.drop(); return rc; }
     const int nranks = k_comm_size(h);
     if (h->nw * nranks == 1) return AFQ_OK;              // handler.py:226-227
     // a kept Green's function travels with the cloned walkers (the clone / pack kernels copy Ghalf and the cached overlap)
-    const bool keep = h->greens_valid && h->ndet == 1;
-    h->greens_valid = false; h->gsum_only = false;
+    // (never the spin sum alone: the clones copy Ghalf)
+    const bool keep = h->gf.take() == GreensCache::FULL && h->ndet == 1;
     if ((rc = k_comb(h, r, target_weight, keep))) return rc;
-    h->greens_valid = keep; h->gsum_only = false;
+    if (keep) h->gf.keep(GreensCache::FULL);
     if (!parent_ix && !total_weight_out) return AFQ_OK;  // asynchronous: nothing read back, no host sync
     double sc[8];
     if ((rc = copy_out(h, sc, h->scal, sizeof(sc)))) return rc;
@@ -1399,7 +1392,7 @@ int afq_walker_pack(afq_handle *h, int iw, void *dev_buf) {
 }
 
 int afq_walker_unpack(afq_handle *h, int iw, const void *dev_buf) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !dev_buf) return AFQ_EINVAL;
     int rc = need_ready(h, false);
     if (rc) return rc;
@@ -1408,7 +1401,7 @@ int afq_walker_unpack(afq_handle *h, int iw, const void *dev_buf) {
 }
 
 int afq_walkers_copy(afq_handle *h, int src, int dst) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h) return AFQ_EINVAL;
     int rc = need_ready(h, false);
     if (rc) return rc;
@@ -1437,13 +1430,13 @@ static int estimates_update_impl(afq_handle *h, int eval_energy, int publish_zer
     if (eval_energy) {
         {
             PhaseTimer t(h, T_GREENS);
-            if (!h->greens_valid) {
+            if (h->gf.kept != GreensCache::FULL) {
                 // (e.g. behind a comb that did not carry the Green's functions along: multi-determinant trials.)  It is
                 // the Green's function of the CURRENT walkers, so it also is what the next step starts from: the overlaps go
                 // where the end-of-step evaluation leaves them and the evaluation is kept -- with it the Coulomb vectors the
                 // energy contracts below, which are the next step's force bias
                 if ((rc = greens_any(h, h->ovlp_new, true))) return rc;
-                if (h->greens_cache && !(h->flags & AFQ_PROP_FREE_PROJECTION) && h->psi_stride == 0) { h->greens_valid = true; h->gsum_only = false; }
+                if (h->gf.enabled && !(h->flags & AFQ_PROP_FREE_PROJECTION) && h->psi_stride == 0) h->gf.keep(GreensCache::FULL);
             }
             if (h->kind == AFQ_SYS_UEG || h->rdm_on) {       // (one_rdm: w.greens_function(trial) refreshes walker.G, mixed.py:212)
                 if ((rc = ensure_G(h))) return rc;
@@ -1746,7 +1739,7 @@ static int hirsch_ready(afq_handle *h) {
 }
 
 int afq_set_propagator_hirsch(afq_handle *h, const double *bt2, double dt, int charge_decomposition) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !bt2 || dt <= 0) return AFQ_EINVAL;
     if (h->kind != AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_ESTATE, "the Hirsch transformation needs a Hubbard system");
     if (h->ndet > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "Hirsch propagator: single-determinant trials");
@@ -1794,7 +1787,7 @@ int afq_set_propagator_hirsch(afq_handle *h, const double *bt2, double dt, int c
 }
 
 int afq_hirsch_kinetic(afq_handle *h) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1803,7 +1796,7 @@ int afq_hirsch_kinetic(afq_handle *h) {
 }
 
 int afq_hirsch_two_body(afq_handle *h, const double *u, int32_t *fields_out, int32_t *used_out) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !u) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1816,7 +1809,7 @@ int afq_hirsch_two_body(afq_handle *h, const double *u, int32_t *fields_out, int
 }
 
 int afq_hirsch_finish(afq_handle *h, double eshift) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1828,7 +1821,7 @@ int afq_hirsch_finish(afq_handle *h, double eshift) {
 
 int afq_propagate_hirsch(afq_handle *h, double eshift) {
     AFQ_API(h, "afq_propagate_hirsch");
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1862,7 +1855,7 @@ int afq_hirsch_free_projection(afq_handle *h, int on) {
 
 int afq_propagate_hirsch_free(afq_handle *h, const double *u, int32_t *fields_out, double eshift) {
     AFQ_API(h, "afq_propagate_hirsch_free");
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;

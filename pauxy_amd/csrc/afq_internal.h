@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "../../include/afqmc_hip.h"
+#include "greens_cache.h"
 
 typedef double2 cplx;   // (x = re, y = im), same bytes as numpy complex128
 
@@ -114,12 +115,10 @@ struct afq_handle {
     bool psi_real = false;          // every imaginary part of the uploaded trial is exactly zero
     bool psi_closed = false;        // na == nb and the alpha and beta blocks of the (single, shared) trial are bitwise equal
     // Closed-shell populations (round 5).  The Green's function kernel checks every walker's spin blocks for bitwise equality
-    // (greens_small_kernel); a walker that fails raises closed_bad to the epoch of that launch.  closed_checked_version is
-    // the ghalf_version whose Ghalf comes from such a checked launch (carried through the comb's clones, which copy whole
-    // walkers): while it equals ghalf_version, "*closed_bad < closed_epoch" ON THE DEVICE means Ghalf_b == Ghalf_a for every
-    // walker, and the exchange energy evaluates one spin (k_energy.hip).  The host never reads the flag.
+    // (greens_small_kernel); a walker that fails raises closed_bad to the epoch of that launch (gf.closed says which Ghalf
+    // the verdict is about).  The host never reads the flag.
     unsigned long long *closed_bad = nullptr;
-    unsigned long long closed_epoch = 0, closed_checked_version = 0;
+    unsigned long long closed_epoch = 0;
     // host-side HINT read with every block's sums (est_publish_kernel): the population held an open-shell walker at the last
     // block end.  launch_exx_quadratic then skips the one-spin-first form (two launches when the population is open: 181
     // against 135 us at C3) for the one-launch two-spin form; results are the same either way, a stale hint costs time only
@@ -141,14 +140,13 @@ struct afq_handle {
         double *rchol_frag[2] = {nullptr, nullptr}, *rchol_frag_im[2] = {nullptr, nullptr};
         void *atil[2] = {nullptr, nullptr};
         bool rchol_same = false;
-        unsigned long long vbias_version = 0;   // ghalf_version this determinant's force-bias partials were contracted from
+        GreensCache::Stamp vbias_stamp;         // this determinant's force-bias partials (as gf.vbias for one determinant)
     };
     int ndet = 1, cur_det = 0;
     std::vector<DetOps> dets;       // size ndet when ndet > 1
     cplx *coeffs = nullptr;         // [ndet] device copy of the CI coefficients
     cplx *detd = nullptr;           // [ndet, nw] per-determinant overlaps <D_d|phi_w>
     cplx *detd_a = nullptr;         // [ndet, nw] their alpha factors det(phi_a^T conj(D_d,a)) (multi_det.py:209 tests it first)
-    cplx *det_a_out = nullptr;      // where the Green's function launch in flight leaves the alpha determinants (or null)
     cplx *detw = nullptr;           // [nw, ndet] weights conj(c_d) <D_d|phi_w> of the last evaluation
     cplx *ghalf_all = nullptr;      // owning pointers of the per-determinant slices
     cplx *vbias_all = nullptr;
@@ -248,15 +246,9 @@ struct afq_handle {
     int fb_split = 1;               // contraction slices of the force-bias GEMM
     cplx *vbias = nullptr;          // [fb_split*2, nw, K] partial per-spin Coulomb vectors X_a, X_b
     cplx *ghalf_sum = nullptr;      // [nw, na*M] Ghalf_a + Ghalf_b when both spins share rchol (force bias on half the contraction)
-    // every writer of ghalf bumps ghalf_version; ghalf_sum is current when gsum_version equals it (the small Green's
-    // function kernel writes the sum itself, otherwise k_force_bias_generic runs ghalf_sum_kernel first)
-    unsigned long long ghalf_version = 1, gsum_version = 0;
-    unsigned long long vbias_version = 0;       // ghalf_version the force-bias partials in vbias were contracted from
-    // Hubbard: diag(G_s) as partial sums over row blocks of Ghalf, written by the Ghalf GEMM itself (k_bigdet.hip);
-    // current when gdiag_version == ghalf_version, cloned along by the comb
-    cplx *gdiag = nullptr;          // [2 nw, gdiag_parts, M]
+    cplx *gdiag = nullptr;          // Hubbard: diag(G_s) as partial sums over row blocks of Ghalf, [2 nw, gdiag_parts, M]
     int gdiag_parts = 0;
-    unsigned long long gdiag_version = 0;
+    GreensCache gf;                 // what ghalf / ghalf_sum / gdiag / vbias / ovlp_new hold for the current walkers
     cplx *xbar = nullptr, *xs = nullptr;              // [nw, K]
     cplx *cmf = nullptr, *cfb = nullptr;              // [nw]
     cplx *vhs = nullptr;            // [nw, nv, M, M] or [nw, nv, M] when vhs_diag
@@ -309,20 +301,10 @@ struct afq_handle {
     double *scal = nullptr;
     void *pack_tmp = nullptr;
     void *zero_page = nullptr;      // 256 zero bytes: source of out-of-range LDS-DMA loads
-    // Ghalf / ovlp_new describe the CURRENT phi of every walker (set by the end-of-step Green's
-    // function of afq_propagate, cleared by everything that writes phi, psi or Ghalf)
-    bool greens_valid = false;
-    bool greens_cache = true;       // a handed-out device pointer turns it off
-
-    // afq_propagate -> k_greens: run the step's weight update behind the determinant (greens_small_kernel)
-    bool fuse_weight_req = false, fuse_weight_done = false;
     // afq_estimates_fuse_next: the weight update of the next step adds every walker's estimator terms to est_acc[w][6]
     // (per walker: no cross-walker sum, no atomics); the next estimates_kernel launch, or the next fetch, folds them in
     double *est_acc = nullptr;
     bool fuse_est_req = false, est_acc_pending = false;
-    // the Green's function cached at the end of a step as overlap + spin sum of Ghalf only (afq_propagate_finish)
-    bool gsum_only = false, ghalf_skip_store = false, ghalf_skipped = false;
-    cplx fuse_eshift;
 
     // rng
     uint64_t rng_seed = 0, rng_stream = 0, rng_counter = 0;
@@ -449,7 +431,7 @@ struct KernelTrace {
 // k_gemm.hip
 int k_onebody(afq_handle *h, const cplx *rowscale = nullptr);   // phi <- [diag(rowscale_w)] BH1 phi (all live walkers)
 int k_force_bias_generic(afq_handle *h);                    // ghalf -> vbias[2,nw,K]
-bool k_msd_vbias_current(afq_handle *h);                    // every determinant's force-bias partials match ghalf_version
+bool k_msd_vbias_current(afq_handle *h);                    // every determinant's force-bias partials are current
 bool k_msd_gbar_wanted(afq_handle *h);                      // multi-determinant force bias through the averaged G
 int k_force_bias_msd_gbar(afq_handle *h);                   // ghalf_all, detw -> averaged partials in vbias_all
 bool k_fb_use_sum(afq_handle *h);                           // force bias runs once over Ghalf_a + Ghalf_b
@@ -484,19 +466,18 @@ int k_itcf_weights(afq_handle *h, int restore, cplx *wfac, cplx *denom);
 int k_itcf_accumulate(afq_handle *h, const cplx *Ggr, const cplx *Gls, const cplx *wfac, cplx *spgf_tau);
 // k_bigdet.hip
 int k_greens_big_supported(afq_handle *h);
-struct WeightArgs;
-int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv = nullptr, const WeightArgs *wa = nullptr);   // ghalf may be null
-                                // (overlap only); wa: the step's weight update rides on the determinant kernel
+// ghalf may be null (overlap only); req as launch_greens (k_small.hip) has narrowed it: ride_weight is taken as decided
+int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const GreensRequest &req, GreensResult *res);
 int k_reortho_big(afq_handle *h);                           // Cholesky-QR2; sets qr_fail for breakdowns
 int k_gj_inverse(afq_handle *h, cplx *O, int n, int batch, cplx *detm, int *dete);   // in place, n <= 128
 // k_small.hip
 int k_alive(afq_handle *h);
-int k_greens(afq_handle *h, cplx *det_out);                 // ghalf + det
-int k_overlap(afq_handle *h, cplx *det_out);                // det(psi^H phi)
+int k_greens(afq_handle *h, cplx *det_out, const GreensRequest &req = GreensRequest(), GreensResult *res = nullptr);   // ghalf + det
+int k_overlap(afq_handle *h, cplx *det_out, const GreensRequest &req = GreensRequest(), GreensResult *res = nullptr);  // det(psi^H phi)
 int k_inverse_overlap(afq_handle *h, cplx *oinv, cplx *det_out);   // O^-1 [nw,2,nmax,nmax] + det, live walkers
 int k_fields(afq_handle *h);                                // vbias -> xbar(clipped), xs, cmf, cfb
 int k_fields_explicit(afq_handle *h, const double *xi_d, const cplx *xbar_d, cplx *xs_d, cplx *cmf_d, cplx *cfb_d);
-int k_xbar(afq_handle *h);
+int k_xbar(afq_handle *h);                                 // vbias / G -> xbar (unclipped), system dispatch
 int k_bp_push(afq_handle *h);
 int k_bp_fields(afq_handle *h, int i);
 int k_bp_init(afq_handle *h, const cplx *phi0_dev);
@@ -517,8 +498,10 @@ int k_bp_msd_finish(afq_handle *h, int ndet, int restore, cplx *detw, const cplx
 int k_bp_msd_accumulate(afq_handle *h, const cplx *gsum, const cplx *fac, const cplx *esum, cplx *est);
 int k_xbar_fields(afq_handle *h, cplx *hubbard_factors = nullptr);   // + the Hubbard row-scaling factors (continuous fields)
 int k_msd_combine(afq_handle *h, cplx *det_out, bool skip_small);          // detd -> detw, det_out = sum_d detw
-int k_msd_energy_combine(afq_handle *h);                   // energy_all, detw -> energy                                  // vbias / G -> xbar (unclipped), system dispatch
+int k_msd_energy_combine(afq_handle *h);                   // energy_all, detw -> energy
 int k_update_weight(afq_handle *h, cplx eshift);
+struct WeightArgs;
+WeightArgs k_weight_args(afq_handle *h, cplx eshift);       // the weight update's operands, for the kernels it rides on
 int k_reortho(afq_handle *h, cplx *keep = nullptr, bool *keep_done = nullptr);
 int k_cap_weights(afq_handle *h, double frac, double total_weight);
 int k_comb(afq_handle *h, double r, double target, bool with_greens = false);

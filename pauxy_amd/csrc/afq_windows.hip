@@ -115,21 +115,18 @@ int reortho_foreign(afq_handle *h, cplx *phi, cplx *ot, double *detR) {
 
 // gab(L, R)^T per walker: the Green's function of R with L[w] (Lc its conjugate) in the role of the trial; overlaps to
 // ovlp, Ghalf and G to the given destinations.  window_owned says whose they are:
-//   false  the handle's own ghalf / G (the caller has run ensure_G): the bumped ghalf_version stays, for what the walk
-//          had cached is overwritten, and the caller leaves greens_valid false
+//   false  the handle's own ghalf / G (the caller has run ensure_G): the bumped version stays, for what the walk had
+//          cached is overwritten, and the caller leaves nothing kept
 //   true   buffers of the window.  The handle's Ghalf is the walk's cached Green's function, which the next step and the
-//          next re-orthogonalisation reuse (and with it whatever was contracted from it: the version counters go back
-//          to where they were), and the handle's G is walker state of the mixed one_rdm (accumulated by every
-//          estimator update, carried by comb, copy and pack).  The caller restores greens_valid / gsum_only once the
-//          whole window has succeeded.
+//          next re-orthogonalisation reuse (and with it whatever was contracted from it: GreensCache::Foreign),
+//          and the handle's G is walker state of the mixed one_rdm (accumulated by every
+//          estimator update, carried by comb, copy and pack).  The caller puts back what was kept once the
+//          whole window has succeeded (GreensCache::ReadOnly).
 int greens_with_trial(afq_handle *h, cplx *R, cplx *L, cplx *Lc, cplx *ovlp, cplx *ghalf, cplx *G, bool window_owned) {
     Lent<cplx *> l_phi(h->phi, R), l_psi(h->psi, L), l_psic(h->psic, Lc), l_ghalf(h->ghalf, ghalf), l_G(h->G, G);
     Lent<long> l_stride(h->psi_stride, (long)h->M * h->nt);
-    std::optional<Lent<unsigned long long>> l_version, l_checked;
-    if (window_owned) {
-        l_version.emplace(h->ghalf_version, h->ghalf_version);
-        l_checked.emplace(h->closed_checked_version, h->closed_checked_version);
-    }
+    std::optional<GreensCache::Foreign> foreign;
+    if (window_owned) foreign.emplace(h->gf);
     int rc;
     if ((rc = k_greens(h, ovlp))) return rc;
     return k_full_G(h);
@@ -190,7 +187,7 @@ int bp_backward(afq_handle *h, int nd, int nstblz, cplx *stack, cplx *ot, double
 
 int bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
               int reset, double *est_out, double *two_rdm_out, double *fock_out) {
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    if (h) h->gf.drop();
     if (!h || !phi_bp0 || !est_out || nstblz < 1 || restore_weights < 0 || restore_weights > 2) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;
@@ -348,8 +345,7 @@ int afq_bp_update_msd(afq_handle *h, int ndet, const double *dets, const double 
                       int eval_energy, int reset, double *est_out, double *detw_out) {
     AFQ_API(h, "afq_bp_update_msd");
     // read-only on the walk, as afq_itcf_update: the Green's function the last step left for the next one stays valid
-    const bool was_valid = h && h->greens_valid, was_gsum = h && h->gsum_only;
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    GreensCache::ReadOnly read_only(h ? &h->gf : nullptr);
     if (!h || !dets || !coeffs || !est_out || ndet < 1 || nstblz < 1 || restore_weights < 0 || restore_weights > 2)
         return AFQ_EINVAL;
     int rc = need_ready(h, true);
@@ -386,7 +382,7 @@ int afq_bp_update_msd(afq_handle *h, int ndet, const double *dets, const double 
     if ((rc = k_bp_msd_finish(h, ndet, restore_weights, ws.detw, ws.S, ws.fac))) return rc;
     if ((rc = k_bp_msd_accumulate(h, ws.gsum, ws.fac, eval_energy ? ws.esum : nullptr, h->bp_est))) return rc;
     if ((rc = window_end(h, reset != 0))) return rc;
-    h->greens_valid = was_valid; h->gsum_only = was_gsum;
+    read_only.succeeded();
     if ((rc = copy_out(h, detw_out, ws.detw, sizeof(cplx) * n * nd))) return rc;
     return copy_out(h, est_out, h->bp_est, sizeof(cplx) * (4 + gsz));
 }
@@ -463,8 +459,7 @@ int afq_itcf_update(afq_handle *h, const double *psi_T, int nstblz, double *spgf
     AFQ_API(h, "afq_itcf_update");
     // the window is read-only on the walk: the Green's function the last step left for the next one stays valid (a window
     // that fails half way leaves it invalid, which only costs a recomputation)
-    const bool was_valid = h && h->greens_valid, was_gsum = h && h->gsum_only;
-    if (h) { h->greens_valid = false; h->gsum_only = false; }
+    GreensCache::ReadOnly read_only(h ? &h->gf : nullptr);
     if (!h || !psi_T || !spgf_out || !denom_out || nstblz < 1) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;
@@ -538,7 +533,7 @@ int afq_itcf_update(afq_handle *h, const double *psi_T, int nstblz, double *spgf
     }
     // 4. FieldConfig.reset + copy_init_wfn: the next window starts from the walkers now
     if ((rc = window_end(h, true))) return rc;
-    h->greens_valid = was_valid; h->gsum_only = was_gsum;
+    read_only.succeeded();
     if ((rc = copy_out(h, denom_out, w.est, sizeof(cplx)))) return rc;
     return copy_out(h, spgf_out, w.est + 1, sizeof(cplx) * nspgf);
 }

@@ -790,7 +790,7 @@ int k_greens_big_supported(afq_handle *h) {
     return !small_fits && nmax > 16 && nmax <= GJ_N && h->nb > 0;
 }
 
-int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const WeightArgs *wa_in) {
+int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const GreensRequest &req, GreensResult *res) {
     const int nmax = h->na > h->nb ? h->na : h->nb;
     const int nb2 = 2 * h->nw;
     const size_t wsn = (size_t)nb2 * nmax * nmax;
@@ -832,11 +832,12 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Weight
         }
         AFQ_POST(h);
         WeightArgs wa;
-        if (wa_in) wa = *wa_in;
+        if (req.ride_weight) wa = k_weight_args(h, req.eshift);
         else std::memset(&wa, 0, sizeof(wa));
         AFQ_LAUNCH(h, det_combine_kernel, dim3((h->nw + 127) / 128), dim3(128), 0, h->stream, h->detm,
-                           h->dete, det, h->det_a_out, h->nw, wa);
+                           h->dete, det, req.det_a, h->nw, wa);
         AFQ_POST(h);
+        if (res && req.ride_weight) res->weight_rode = true;
     }
     if (oinv)    // [nw, 2, nmax, nmax]: the layout of the workspace (batch = 2 w + spin)
         AFQ_HIP(h, hipMemcpyAsync(oinv, h->big_ws, sizeof(cplx) * wsn, hipMemcpyDeviceToDevice, h->stream));
@@ -847,7 +848,7 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Weight
             p.Oinv = h->big_ws; p.phi = h->phi; p.ghalf = ghalf; p.zero = (const cplx *)h->zero_page;
             p.psicT = h->psicT; p.gdiag = h->gdiag; p.nparts = h->gdiag_parts;
             p.skip_store = 0;
-            if (decltype(p)::COLDOT && h->ghalf_skip_store) { p.skip_store = 1; h->ghalf_skipped = true; }
+            if (decltype(p)::COLDOT && req.may_skip_store) { p.skip_store = 1; if (res) res->store_skipped = true; }
             AFQ_GEMM_AS(h, "k_greens_big: GhalfProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, decltype(p), MAP_COLS_FAST, true, 1, 3>(p, h->stream, h->zero_page)));
             return AFQ_OK;
         };
@@ -859,7 +860,7 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Weight
             // the last writer used
             const int parts16 = (nmax + 15) / 16;
             if (!h->gdiag) AFQ_HIP(h, hipMalloc(&h->gdiag, sizeof(cplx) * (size_t)nb2 * parts16 * h->M));
-            if (h->ghalf_skip_store && h->psi_real) {
+            if (req.may_skip_store && h->psi_real) {
                 // only diag G is wanted and the trial is real: W = conj(psi) O^-1 (real by complex), rowdot with phi
                 GdiagProbT p;
                 p.batch = nb2; p.rows = h->M; p.cols = nmax; p.kdim = nmax;
@@ -867,15 +868,15 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Weight
                 p.psic = h->psic; p.Oinv = h->big_ws; p.phi = h->phi; p.gdiag = h->gdiag; p.nparts = parts16;
                 p.zero = (const cplx *)h->zero_page;
                 h->gdiag_parts = parts16;
-                h->ghalf_skipped = true;
+                if (res) res->store_skipped = true;
                 AFQ_GEMM_AS(h, "k_greens_big: GdiagProb GEMM", (launch_mfma_gemm_wg<2, 2, 2, 2, 4, GdiagProbT, MAP_COLS_FAST, false, 1, 3>(p, h->stream, h->zero_page)));
-                h->gdiag_version = h->ghalf_version;
+                h->gf.gdiag.mark(h->gf);
                 return AFQ_OK;
             }
             h->gdiag_parts = (nmax + 31) / 32;
             const int rc = run(GhalfProbT<true>());
             if (rc) return rc;
-            h->gdiag_version = h->ghalf_version;
+            h->gf.gdiag.mark(h->gf);
         } else {
             const int rc = run(GhalfProbT<false>());
             if (rc) return rc;

@@ -706,10 +706,10 @@ int stage_plan_pack(afq_handle *h, double target, bool with_greens, bool fused_p
 }
 
 int stage_unpack(afq_handle *h, bool with_greens, bool pack_too = false) {
-    // (the closed-shell verdict of this rank's population carries over when the walkers that arrive are checked too)
-    const bool closed_too = with_greens && h->closed_bad && h->closed_checked_version == h->ghalf_version && h->na == h->nb;
-    ++h->ghalf_version;                 // cloned / received walkers bring their Ghalf along
-    if (closed_too) h->closed_checked_version = h->ghalf_version;
+    // received walkers bring their Ghalf and overlap along, not the spin sum or the diagonal sums; the closed-shell verdict
+    // of this rank's population carries over because the unpack kernel checks the walkers that arrive (closed_half)
+    const bool closed_too = with_greens && h->closed_bad && h->gf.closed.current(h->gf) && h->na == h->nb;
+    h->gf.cloned(closed_too ? GreensCache::CLOSED : 0);
     afq_comm_state *c = cs_of(h);
     if (c->nranks > 1) {
         PackArgs p;
@@ -1139,8 +1139,7 @@ int afq_popcontrol_comb_local(afq_handle **hs, int n, double r, double target, i
         afq_handle *h = hs[i];
         hipSetDevice(h->device);
         h->scal_cache_valid = false;
-        keep[i] = h->greens_valid && h->ndet == 1;
-        h->greens_valid = false; h->gsum_only = false;
+        keep[i] = h->gf.take() == GreensCache::FULL && h->ndet == 1;       // (never the spin sum alone: the pairs ship Ghalf)
     }
     // a cached Green's function travels only if every rank has one (the slots of a pair must agree)
     bool with_greens = true;
@@ -1166,7 +1165,7 @@ int afq_popcontrol_comb_local(afq_handle **hs, int n, double r, double target, i
         hipSetDevice(h->device);
         for (int j = 0; j < n; ++j) if (j != i) AFQ_HIP(h, hipStreamWaitEvent(h->stream, cs_of(hs[j])->ev2, 0));
         if ((rc = stage_unpack(h, with_greens))) return rc;
-        h->greens_valid = with_greens; h->gsum_only = false;
+        h->gf.keep(with_greens ? GreensCache::FULL : GreensCache::NOTHING);
         // a rank's next prep overwrites rows of the OTHER ranks' gw of the other parity only; its next pack writes into
         // their windows only after their next prep (all-gather), which follows their unpack in stream order
     }

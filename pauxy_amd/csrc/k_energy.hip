@@ -581,21 +581,21 @@ static int launch_exx_quadratic(afq_handle *h, int *S_out, bool *two_pass) {
     if (S > EXQ_MAX_BATCH / 2) S = EXQ_MAX_BATCH / 2;
     while (S > 1 && nmax / S < 64) --S;
     // Closed-shell population (every walker's Ghalf_b == Ghalf_a, verified on the device by the Green's function launch this
-    // Ghalf comes from: closed_checked_version) and one Atil for both spins: the 2 S slices of the FIRST launch all belong to
+    // Ghalf comes from: gf.closed) and one Atil for both spins: the 2 S slices of the FIRST launch all belong to
     // spin alpha (every XCD busy), the second launch holds spin beta's and returns at once on the device when the flag says
     // closed; energy_finish_kernel then counts the alpha sums twice.  Nothing is decided on the host.
     // (the small Green's function kernel checks the spin blocks only beside the spin sum of real half-rotated vectors,
     //  k_fb_use_sum: complex ones -- a complex trial, or complex Cholesky vectors -- are checked here, as the large systems are)
-    if (h->closed_bad && h->closed_checked_version != h->ghalf_version && (k_greens_big_supported(h) || !h->rchol_real) &&
+    if (h->closed_bad && !h->gf.closed.current(h->gf) && (k_greens_big_supported(h) || !h->rchol_real) &&
         h->ndet == 1 && h->na == h->nb && h->atil[0] == h->atil[1] && !h->exx_open_hint) {
         // (an open-shell population is found out by the first evaluation's published verdict, exx_open_hint: no check, and
         //  the two-spin launch, from then on)
         AFQ_LAUNCH(h, ghalf_closed_check_kernel, dim3(h->nw), dim3(256), 0, h->stream, h->ghalf, nma, h->closed_bad, ++h->closed_epoch);
         AFQ_POST(h);
-        h->closed_checked_version = h->ghalf_version;
+        h->gf.closed.mark(h->gf);
     }
-    const bool closed_try = h->closed_bad && h->closed_checked_version == h->ghalf_version && h->closed_checked_version != 0 &&
-                            h->ndet == 1 && h->na == h->nb && h->atil[0] == h->atil[1] && !h->exx_open_hint;
+    const bool closed_try = h->closed_bad && h->gf.closed.current(h->gf) && h->ndet == 1 && h->na == h->nb &&
+                            h->atil[0] == h->atil[1] && !h->exx_open_hint;
     // (slices of the one-spin launch: 2 S, as many work-groups as the two-spin launch has.  C3, us per evaluation: S = 4
     //  slices 106.6, 5 100.9, 6 96.9, 7 91.4, 8 = 2 S 96.9, 10 139.8, 16 107.3; the two-spin launch 138.9)
     int SL = closed_try ? 2 * S : S;

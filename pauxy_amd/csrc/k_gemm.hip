@@ -261,21 +261,22 @@ bool k_fb_use_sum(afq_handle *h) {
 static int force_bias_generic_impl(afq_handle *h);
 
 // The Coulomb vectors of the energy evaluation at the end of step n and the force bias at the start of step n + 1 are
-// the same contraction of the same (cached) Ghalf: the second call is skipped while ghalf_version has not moved.
+// the same contraction of the same (cached) Ghalf: the second call is skipped while the partials' stamp is current.
 int k_force_bias_generic(afq_handle *h) {
     // (multi-determinant trial: one set of partials, and one version, per determinant -- the Coulomb vectors of an energy
     //  evaluation serve the force bias of the next step as they do for one determinant)
-    unsigned long long &ver = h->ndet == 1 ? h->vbias_version : h->dets[h->cur_det].vbias_version;
-    if (ver == h->ghalf_version) return AFQ_OK;
+    GreensCache::Stamp &made = h->ndet == 1 ? h->gf.vbias : h->dets[h->cur_det].vbias_stamp;
+    if (made.current(h->gf)) return AFQ_OK;
     const int rc = force_bias_generic_impl(h);
-    ver = rc == AFQ_OK ? h->ghalf_version : 0;
+    if (rc == AFQ_OK) made.mark(h->gf);
+    else made.clear();
     return rc;
 }
 
 // every determinant's partials are current (left behind by the energy evaluation on the same Green's functions)
 bool k_msd_vbias_current(afq_handle *h) {
     if (h->ndet <= 1) return false;
-    for (int d = 0; d < h->ndet; ++d) if (h->dets[d].vbias_version != h->ghalf_version) return false;
+    for (int d = 0; d < h->ndet; ++d) if (!h->dets[d].vbias_stamp.current(h->gf)) return false;
     return true;
 }
 
@@ -286,12 +287,12 @@ static int force_bias_generic_impl(afq_handle *h) {
         fill_force_bias(p, h);
         if (k_fb_use_sum(h)) {
             const long half = (long)h->na * h->M, n = half * h->nw;
-            if (!h->ghalf_sum) { AFQ_HIP(h, hipMalloc(&h->ghalf_sum, sizeof(cplx) * (size_t)n)); h->gsum_version = 0; }
-            if (h->gsum_version != h->ghalf_version) {      // not written by the Green's function kernel itself
+            if (!h->ghalf_sum) { AFQ_HIP(h, hipMalloc(&h->ghalf_sum, sizeof(cplx) * (size_t)n)); h->gf.gsum.clear(); }
+            if (!h->gf.gsum.current(h->gf)) {               // not written by the Green's function kernel itself
                 AFQ_LAUNCH(h, ghalf_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ghalf,
                            h->ghalf_sum, half, n);
                 AFQ_POST(h);
-                h->gsum_version = h->ghalf_version;
+                h->gf.gsum.mark(h->gf);
             }
             const int ns2 = 2 * h->fb_split;
             const long per = (half + ns2 - 1) / ns2;
@@ -451,7 +452,7 @@ bool k_msd_gbar_wanted(afq_handle *h) {
 int k_force_bias_msd_gbar(afq_handle *h) {
     const int M = h->M, KK = (h->ndet * h->nt + 7) & ~7, nw = h->nw;     // (stacks zero-padded to whole chunks of 8)
     const long P = (long)M * (M + 1) / 2, per = (long)h->nt * M;
-    h->dets[0].vbias_version = 0;                  // the averaged partials go where determinant 0 keeps its own
+    h->dets[0].vbias_stamp.clear();                // the averaged partials go where determinant 0 keeps its own
     if (!h->hs_pk) {
         AFQ_HIP(h, hipMalloc(&h->hs_pk, sizeof(double) * (size_t)P * h->ld_rc));
         AFQ_HIP(h, hipMemsetAsync(h->hs_pk, 0, sizeof(double) * (size_t)P * h->ld_rc, h->stream));

@@ -5,6 +5,7 @@
 // LDS when they fit and in a global workspace otherwise.
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <type_traits>
 #include "mfma_gemm.h"
 #include "gj_wave.h"
@@ -180,7 +181,6 @@ __global__ __launch_bounds__(NTHR) void greens_kernel(GreensArgs a) {
 #include "weight_update.h"
 
 
-static WeightArgs weight_args(afq_handle *h, cplx eshift);
 static WeightArgs no_weight_args() {
     WeightArgs a;
     memset(&a, 0, sizeof(a));
@@ -764,87 +764,74 @@ __global__ __launch_bounds__(512) void greens_tiny_kernel(GreensArgs a, WeightAr
     }
 }
 
-static int launch_greens(afq_handle *h, cplx *ghalf, cplx *det, int only_alive, cplx *oinv = nullptr) {
+// the one-work-group kernels: [with Ghalf or O^-1 | determinant only][tiny, wave Gauss-Jordan (N <= 32), blocked]; the
+// dynamic-LDS cap of each is raised once per kernel and device, not per launch
+typedef void (*GreensKernel)(GreensArgs, WeightArgs);
+struct GreensVariant { GreensKernel kern; const char *name; size_t lds_set[AFQ_MAX_DEVICES]; };
+#define GREENS_VARIANT(kern) {kern, #kern, {0}}
+static GreensVariant greens_variants[2][3] = {
+    {GREENS_VARIANT((greens_tiny_kernel<true>)), GREENS_VARIANT((greens_small_kernel<true, true>)),
+     GREENS_VARIANT((greens_small_kernel<true, false>))},
+    {GREENS_VARIANT((greens_tiny_kernel<false>)), GREENS_VARIANT((greens_small_kernel<false, true>)),
+     GREENS_VARIANT((greens_small_kernel<false, false>))}};
+#undef GREENS_VARIANT
+
+static int launch_greens(afq_handle *h, cplx *ghalf, cplx *det, int only_alive, cplx *oinv = nullptr,
+                         const GreensRequest &req = GreensRequest(), GreensResult *res = nullptr) {
     GreensArgs a;
     a.oinv = oinv; a.gsum = nullptr;
-    if (ghalf) ++h->ghalf_version;
+    if (ghalf) h->gf.rewritten();
     a.M = h->M; a.na = h->na; a.nb = h->nb; a.nt = h->nt; a.nw = h->nw;
     a.phi = h->phi; a.psi = h->psi; a.psi_stride = h->psi_stride; a.ghalf = ghalf; a.det = det; a.ws = h->lu_ws;
-    a.det_a = h->det_a_out;
+    a.det_a = req.det_a;
     a.psi_real = h->psi_real && h->psi_stride == 0 && h->ndet <= 1;
     a.psi_closed = h->psi_closed && h->psi_stride == 0 && h->ndet <= 1;
     a.closed_bad = nullptr; a.closed_epoch = 0; a.counters = h->counters;
-    if (ghalf == h->ghalf) h->closed_checked_version = 0;       // (set again below when THIS launch checks every walker)
+    if (ghalf == h->ghalf) h->gf.closed.clear();                // (set again below when THIS launch checks every walker)
     a.skip_spin = 0;
     const int nmax = h->na > h->nb ? h->na : h->nb;
     if (nmax > 256) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "more than 256 electrons per spin");
+    // the step's weight update rides on the determinant kernel when the caller asked for it and this IS the overlap of the
+    // propagated walkers
+    const bool ride = req.ride_weight && res && det == h->ovlp_new && !only_alive && !oinv;
     if (k_greens_big_supported(h)) {
-        // the step's weight update rides on the determinant kernel of the large path as well (conditions as below)
-        if (h->fuse_weight_req && det == h->ovlp_new && !only_alive && !oinv && h->ndet <= 1) {
-            const WeightArgs wa = weight_args(h, h->fuse_eshift);
-            h->fuse_weight_done = true;
-            h->fuse_weight_req = false;
-            return k_greens_big(h, ghalf, det, oinv, &wa);
-        }
-        return k_greens_big(h, ghalf, det, oinv);
+        GreensRequest big = req;
+        big.ride_weight = ride && h->ndet <= 1;
+        return k_greens_big(h, ghalf, det, oinv, big, res);
     }
     // (the fast kernel keeps the walker, both overlap matrices and their inverses in LDS: 160 KB per work-group)
-    const size_t lds_small = sizeof(cplx) * (2 * ((size_t)nmax * nmax + 2 * nmax) + ((2 * nmax + 3) / 4 + 1) + (size_t)h->M * h->nt);
-    if (nmax <= 45 && h->M <= 4 * GS_KSMAX && lds_small <= 160 * 1024) {
+    const size_t lds = sizeof(cplx) * (2 * ((size_t)nmax * nmax + 2 * nmax) + ((2 * nmax + 3) / 4 + 1) + (size_t)h->M * h->nt);
+    if (nmax <= 45 && h->M <= 4 * GS_KSMAX && lds <= 160 * 1024) {
         a.o_in_lds = 1; a.only_alive = only_alive; a.alive = h->alive;
-        // the step's weight update rides on this launch when afq_propagate asked for it and this IS the
-        // overlap of the propagated walkers
-        WeightArgs wa = no_weight_args();
-        if (h->fuse_weight_req && det == h->ovlp_new && !only_alive && !oinv) {
-            wa = weight_args(h, h->fuse_eshift);
-            h->fuse_weight_done = true;
-        }
-        h->fuse_weight_req = false;
-        if (h->M > 4 * GS_KSMAX) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "fast Green's kernel supports M <= 128");
-        const size_t lds = sizeof(cplx) * (2 * ((size_t)nmax * nmax + 2 * nmax) + ((2 * nmax + 3) / 4 + 1) +
-                                           (size_t)h->M * h->nt);
-        // raise the dynamic-LDS cap once per kernel and device, not per launch
-        static size_t lds_set[4][AFQ_MAX_DEVICES] = {{0}};
+        const WeightArgs wa = ride ? k_weight_args(h, req.eshift) : no_weight_args();
+        if (ride) res->weight_rode = true;
         const bool wgj = nmax <= 32;
         // at most 8 electrons per spin, walker + trial in LDS: the vector-ALU kernel above
         const size_t lds_tiny = sizeof(cplx) * 2 * (size_t)h->M * h->nt;
-        static size_t lds_set_tiny[2][AFQ_MAX_DEVICES] = {{0}};
         const bool tiny = nmax <= 8 && h->nt >= 1 && lds_tiny <= 150 * 1024;
-        if (ghalf || oinv) {
-            // the spin sum the force bias contracts (every walker written: not on the only_alive path)
-            const bool want_sum = ghalf && ghalf == h->ghalf && !only_alive && k_fb_use_sum(h) && h->psi_stride == 0;
-            if (want_sum) {
-                if (!h->ghalf_sum) AFQ_HIP(h, hipMalloc(&h->ghalf_sum, sizeof(cplx) * (size_t)h->na * h->M * h->nw));
-                a.gsum = h->ghalf_sum;
-                if (h->ghalf_skip_store && (wgj || tiny) && !oinv) { a.skip_spin = 1; h->ghalf_skipped = true; }
-            }
-            if (want_sum && wgj && !tiny && a.psi_closed && !oinv) {
-                // this launch compares the spin blocks of EVERY walker: its verdict holds for the Ghalf it leaves behind
-                a.closed_bad = h->closed_bad; a.closed_epoch = ++h->closed_epoch;
-                h->closed_checked_version = h->ghalf_version;
-            }
-            KernelTrace kt(h, AFQ_K_GREENS);
-            if (tiny) {
-                AFQ_HIP(h, afq_raise_lds((const void *)greens_tiny_kernel<true>, lds_tiny, lds_set_tiny[0]));
-                AFQ_LAUNCH(h, (greens_tiny_kernel<true>), dim3(h->nw), dim3(512), lds_tiny, h->stream, a, wa);
-            } else if (wgj) {
-                AFQ_HIP(h, afq_raise_lds((const void *)greens_small_kernel<true, true>, lds, lds_set[0]));
-                AFQ_LAUNCH(h, (greens_small_kernel<true, true>), dim3(h->nw), dim3(512), lds, h->stream, a, wa);
-            } else {
-                AFQ_HIP(h, afq_raise_lds((const void *)greens_small_kernel<true, false>, lds, lds_set[1]));
-                AFQ_LAUNCH(h, (greens_small_kernel<true, false>), dim3(h->nw), dim3(512), lds, h->stream, a, wa);
-            }
-            if (want_sum) h->gsum_version = h->ghalf_version;
-        } else if (tiny) {
-            AFQ_HIP(h, afq_raise_lds((const void *)greens_tiny_kernel<false>, lds_tiny, lds_set_tiny[1]));
-            AFQ_LAUNCH(h, (greens_tiny_kernel<false>), dim3(h->nw), dim3(512), lds_tiny, h->stream, a, wa);
-        } else if (wgj) {
-            AFQ_HIP(h, afq_raise_lds((const void *)greens_small_kernel<false, true>, lds, lds_set[2]));
-            AFQ_LAUNCH(h, (greens_small_kernel<false, true>), dim3(h->nw), dim3(512), lds, h->stream, a, wa);
-        } else {
-            AFQ_HIP(h, afq_raise_lds((const void *)greens_small_kernel<false, false>, lds, lds_set[3]));
-            AFQ_LAUNCH(h, (greens_small_kernel<false, false>), dim3(h->nw), dim3(512), lds, h->stream, a, wa);
+        const bool inverse = ghalf || oinv;
+        // the spin sum the force bias contracts (every walker written: not on the only_alive path)
+        const bool want_sum = ghalf && ghalf == h->ghalf && !only_alive && k_fb_use_sum(h) && h->psi_stride == 0;
+        if (want_sum) {
+            if (!h->ghalf_sum) AFQ_HIP(h, hipMalloc(&h->ghalf_sum, sizeof(cplx) * (size_t)h->na * h->M * h->nw));
+            a.gsum = h->ghalf_sum;
+            if (req.may_skip_store && (wgj || tiny) && !oinv) { a.skip_spin = 1; if (res) res->store_skipped = true; }
         }
+        if (want_sum && wgj && !tiny && a.psi_closed && !oinv) {
+            // this launch compares the spin blocks of EVERY walker: its verdict holds for the Ghalf it leaves behind
+            a.closed_bad = h->closed_bad; a.closed_epoch = ++h->closed_epoch;
+            h->gf.closed.mark(h->gf);
+        }
+        GreensVariant &v = greens_variants[inverse ? 0 : 1][tiny ? 0 : wgj ? 1 : 2];
+        const size_t v_lds = tiny ? lds_tiny : lds;
+        {
+            std::optional<KernelTrace> kt;
+            if (inverse) kt.emplace(h, AFQ_K_GREENS);
+            AFQ_HIP(h, afq_raise_lds((const void *)v.kern, v_lds, v.lds_set));
+            afq_note_launch(h, v.name);
+            hipLaunchKernelGGL(v.kern, dim3(h->nw), dim3(512), v_lds, h->stream, a, wa);
+        }
+        if (want_sum) h->gf.gsum.mark(h->gf);
         AFQ_POST(h);
         return AFQ_OK;
     }
@@ -860,10 +847,14 @@ static int launch_greens(afq_handle *h, cplx *ghalf, cplx *det, int only_alive, 
     return AFQ_OK;
 }
 
-int k_greens(afq_handle *h, cplx *det_out) { return launch_greens(h, h->ghalf, det_out, 0); }
+int k_greens(afq_handle *h, cplx *det_out, const GreensRequest &req, GreensResult *res) {
+    return launch_greens(h, h->ghalf, det_out, 0, nullptr, req, res);
+}
 // det(psi^H phi) == det(phi^T conj(psi)) (transpose), so the same factorisation serves
 // walkers/single_det.py:170-199
-int k_overlap(afq_handle *h, cplx *det_out) { return launch_greens(h, nullptr, det_out, 0); }
+int k_overlap(afq_handle *h, cplx *det_out, const GreensRequest &req, GreensResult *res) {
+    return launch_greens(h, nullptr, det_out, 0, nullptr, req, res);
+}
 // O^-1 of every walker and spin (+ determinant), no Ghalf: the discrete Hirsch propagator's inverse overlap
 int k_inverse_overlap(afq_handle *h, cplx *oinv, cplx *det_out) {
     const int nmax = h->na > h->nb ? h->na : h->nb;
@@ -975,7 +966,7 @@ static XbarArgs xbar_args(afq_handle *h) {
     a.sqrt_dt = h->sqrt_dt; a.U = h->U;
     a.vbias = h->vbias; a.mf = h->mf_shift; a.ghalf = h->ghalf; a.psi = h->psi; a.xbar = h->xbar;
     a.psicT = (h->ndet <= 1 && h->psi_stride == 0) ? h->psicT : nullptr;
-    a.gdiag = (h->kind == AFQ_SYS_HUBBARD && h->gdiag && h->gdiag_version == h->ghalf_version) ? h->gdiag : nullptr;
+    a.gdiag = (h->kind == AFQ_SYS_HUBBARD && h->gdiag && h->gf.gdiag.current(h->gf)) ? h->gdiag : nullptr;
     a.gparts = h->gdiag_parts;
     a.ndet = h->ndet; a.detw = h->detw; a.det_stride = (long)2 * h->fb_split * h->nw * h->K;
     if (h->ndet > 1) a.vbias = h->vbias_all;
@@ -1371,14 +1362,13 @@ int k_bp_reset(afq_handle *h, bool first) {
 
 
 int k_update_weight(afq_handle *h, cplx eshift) {
-    if (h->fuse_weight_done) { h->fuse_weight_done = false; return AFQ_OK; }   // rode on the Green's function kernel
-    const WeightArgs a = weight_args(h, eshift);
+    const WeightArgs a = k_weight_args(h, eshift);
     AFQ_LAUNCH(h, weight_kernel, dim3((h->nw + 127) / 128), dim3(128), 0, h->stream, a);
     AFQ_POST(h);
     return AFQ_OK;
 }
 
-static WeightArgs weight_args(afq_handle *h, cplx eshift) {
+WeightArgs k_weight_args(afq_handle *h, cplx eshift) {
     WeightArgs a;
     a.nw = h->nw; a.flags = h->flags; a.dt = h->dt; a.eshift = eshift; a.alive = h->alive;
     a.ovlp_old = h->ovlp_old; a.ovlp_new = h->ovlp_new; a.cmf = h->cmf; a.cfb = h->cfb;
@@ -1986,13 +1976,10 @@ int k_scale_by_inverse(afq_handle *h, cplx *x, const double *d) {
 // clone_kernel over the (src, dst) pairs in h->pack_tmp, count in scal[1]; at most nw / 2 pairs
 int k_clone_pairs(afq_handle *h, bool with_greens, bool reset_weights) {
     // cloned walkers bring their Ghalf along, and its spin sum when that is current (it then stays current)
-    const bool sum_too = with_greens && h->ghalf_sum && h->gsum_version == h->ghalf_version;
-    const bool diag_too = with_greens && h->gdiag && h->gdiag_version == h->ghalf_version;
-    const bool closed_too = with_greens && h->closed_checked_version == h->ghalf_version;   // clones are whole walkers
-    ++h->ghalf_version;
-    if (closed_too) h->closed_checked_version = h->ghalf_version;
-    if (sum_too) h->gsum_version = h->ghalf_version;
-    if (diag_too) h->gdiag_version = h->ghalf_version;
+    // the clone kernel copies whole walkers with Ghalf, its spin sum and the diagonal sums, and a copy of a closed-shell
+    // walker is one: everything derived stays current
+    const bool sum_too = with_greens && h->gf.gsum.current(h->gf), diag_too = with_greens && h->gf.gdiag.current(h->gf);
+    h->gf.cloned(with_greens ? GreensCache::SUM | GreensCache::DIAG | GreensCache::CLOSED : 0);
     CloneArgs a;
     a.gdiag = diag_too ? h->gdiag : nullptr; a.gdiag_per = 2L * h->gdiag_parts * h->M;
     a.gsum = sum_too ? h->ghalf_sum : nullptr; a.gsum_per = (long)h->na * h->M;
