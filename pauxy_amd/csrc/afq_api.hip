@@ -11,101 +11,31 @@
 
 namespace {
 
-// ---- multi-determinant operand sets: psi / psic / rH1 / rchol_* of the handle are views of dets[cur_det]
-void stash_det(afq_handle *h) {
-    if (h->ndet <= 1) return;
-    afq_handle::DetOps &o = h->dets[h->cur_det];
-    o.psi = h->psi; o.psic = h->psic; o.rH1 = h->rH1; o.rchol_re = h->rchol_re; o.rchol_im = h->rchol_im;
-    for (int s = 0; s < 2; ++s) { o.rchol_frag[s] = h->rchol_frag[s]; o.rchol_frag_im[s] = h->rchol_frag_im[s]; o.atil[s] = h->atil[s]; }
-    o.rchol_same = h->rchol_same;
-}
-
-void select_det(afq_handle *h, int d) {
-    if (h->ndet <= 1 || d == h->cur_det) return;
-    stash_det(h);
-    const afq_handle::DetOps &o = h->dets[d];
-    h->psi = o.psi; h->psic = o.psic; h->rH1 = o.rH1; h->rchol_re = o.rchol_re; h->rchol_im = o.rchol_im;
-    for (int s = 0; s < 2; ++s) { h->rchol_frag[s] = o.rchol_frag[s]; h->rchol_frag_im[s] = o.rchol_frag_im[s]; h->atil[s] = o.atil[s]; }
-    h->rchol_same = o.rchol_same;
-    h->cur_det = d;
-    if (h->nw) {
-        h->ghalf = h->ghalf_all + (size_t)d * h->nw * h->M * h->nt;
-        if (h->vbias_all) h->vbias = h->vbias_all + (size_t)d * 2 * h->fb_split * h->nw * h->K;
-    }
-}
-
+// ---- the three releases below free by lifetime (dev_mem.h); what stays next to them are the resets that are not memory
 void free_dets(afq_handle *h) {
-    if (h->ndet > 1) {
-        stash_det(h);
-        for (afq_handle::DetOps &o : h->dets) {
-            if (o.psi) hipFree(o.psi);
-            if (o.psic) hipFree(o.psic);
-            if (o.rH1) hipFree(o.rH1);
-            if (o.rchol_re) hipFree(o.rchol_re);
-            if (o.rchol_im) hipFree(o.rchol_im);
-            for (int s = 0; s < 2; ++s) {
-                if (o.rchol_frag[s]) hipFree(o.rchol_frag[s]);
-                if (o.rchol_frag_im[s]) hipFree(o.rchol_frag_im[s]);
-            }
-            k_free_atil(o.atil);
-        }
-        h->psi = nullptr; h->psic = nullptr; h->rH1 = nullptr; h->rchol_re = nullptr; h->rchol_im = nullptr;
-        for (int s = 0; s < 2; ++s) { h->rchol_frag[s] = nullptr; h->rchol_frag_im[s] = nullptr; h->atil[s] = nullptr; }
-    }
-    h->dets.clear();
-    h->ndet = 1; h->cur_det = 0;
-    if (h->coeffs) { hipFree(h->coeffs); h->coeffs = nullptr; }
-    dev_free(h->msd_psicT); dev_free(h->msd_psicT_neg); h->msd_fb_gbar = false;
+    h->mem.release(LT_TRIAL);
+    h->dets.assign(1, afq_handle::DetOps());
+    h->ndet = 1;
+    select_det(h, 0, true);
+    h->msd_fb_gbar = false;
 }
 
 void free_system(afq_handle *h) {
     free_dets(h);
-    dev_free(h->hs_pot); dev_free(h->hs_pair); dev_free(h->hs_pk); dev_free(h->L_full);
-    dev_free(h->hs_pot_im); dev_free(h->hs_pair_im); dev_free(h->hs_pk_im); dev_free(h->L_full_c); h->hs_cplx = 0; dev_free(h->rchol_re); dev_free(h->rchol_im);
-    for (int s = 0; s < 2; ++s) { dev_free(h->rchol_frag[s]); dev_free(h->rchol_frag_im[s]); }
-    k_free_atil(h->atil);
-    dev_free(h->H1); dev_free(h->rH1);
-    dev_free(h->iA_colptr); dev_free(h->iA_row); dev_free(h->iA_val); dev_free(h->ell_row); dev_free(h->ell_val); dev_free(h->ueg_rmap); dev_free(h->ueg_rows);
-    dev_free(h->ueg_kp); dev_free(h->ueg_pm); dev_free(h->ueg_koff); dev_free(h->ueg_poff);
-    dev_free(h->sf_kp); dev_free(h->sf_pm); dev_free(h->sf_order); h->sf_nlong = 0;
-    dev_free(h->sf_ws); dev_free(h->sf_two); h->sf_ws_len = h->sf_two_len = 0;
-    dev_free(h->iB_colptr); dev_free(h->iB_row); dev_free(h->iB_val);
-    dev_free(h->iA_rowptr); dev_free(h->iA_col); dev_free(h->iA_rval);
-    dev_free(h->iB_rowptr); dev_free(h->iB_col); dev_free(h->iB_rval);
-    dev_free(h->kpq_off); dev_free(h->kpq_i); dev_free(h->kpq_kpq);
-    dev_free(h->pmq_off); dev_free(h->pmq_i); dev_free(h->pmq_pmq);
-    dev_free(h->vqvec); dev_free(h->H1diag);
-    h->kind = 0;
+    h->mem.release(LT_SYSTEM);
+    h->hs_cplx = 0; h->sf_nlong = 0; h->kind = 0;
+    h->hirsch = false;              // the discrete propagator belongs to the system it was set for
 }
 
 void free_walkers(afq_handle *h) {
-    dev_free(h->est_acc); h->est_acc_pending = false; h->fuse_est_req = false;
-    dev_free(h->phi); dev_free(h->phi_t); dev_free(h->phi_t2);
-    dev_free(h->weight); dev_free(h->unscaled); dev_free(h->detR); dev_free(h->log_detR);
-    dev_free(h->ot); dev_free(h->ehyb); dev_free(h->phase); dev_free(h->eloc);
-    dev_free(h->ghalf_all); h->ghalf = nullptr; dev_free(h->G); dev_free(h->ovlp_old); dev_free(h->ovlp_new);
-    dev_free(h->xi); dev_free(h->vbias_all); h->vbias = nullptr; dev_free(h->ghalf_sum); h->gf.gsum.clear(); h->gf.vbias.clear();
-    dev_free(h->gdiag); h->gf.gdiag.clear(); h->gdiag_parts = 0;
-    dev_free(h->detd); dev_free(h->detd_a); dev_free(h->detw); dev_free(h->energy_all);
-    dev_free(h->msd_gs); dev_free(h->msd_S); dev_free(h->msd_D); h->msd_fb_gbar = false;
-    dev_free(h->hs_oinv); dev_free(h->hs_u); dev_free(h->hs_fields); dev_free(h->hs_used); dev_free(h->hs_alive0);
-    dev_free(h->hs_fbfac);
-    dev_free(h->bp_hist); dev_free(h->bp_n); dev_free(h->bp_flag); dev_free(h->bp_cos); dev_free(h->bp_ph);
-    dev_free(h->phi_old); dev_free(h->phi_bp); dev_free(h->BH1dag); dev_free(h->bp_xs); dev_free(h->bp_est);
-    dev_free(h->bp_ot); dev_free(h->bp_detR);
-    dev_free(h->bpm_ws); h->bpm_ws_len = 0;
-    h->nbp = 0; dev_free(h->xbar); dev_free(h->xs);
-    dev_free(h->bpo_h1); dev_free(h->bpo_L); dev_free(h->bpo_wt); dev_free(h->bpo_out); dev_free(h->bpo_ws);
-    h->bpo_ws_len = 0; h->bpo_two = h->bpo_ekt = h->bpo_sf = 0; h->bpo_nL = 0;
-    dev_free(h->it_ws); h->it_ws_len = 0; h->it_nmax = 0;
-    dev_free(h->cmf); dev_free(h->cfb); dev_free(h->vhs); dev_free(h->lu_ws);
-    dev_free(h->gj_flag); dev_free(h->big_ws); dev_free(h->big_ws2); dev_free(h->detm); dev_free(h->dete); dev_free(h->qr_logd); dev_free(h->qr_fail);
-    dev_free(h->energy); dev_free(h->exx_part); dev_free(h->gfrag); dev_free(h->exq_y); h->exq_y_len = 0;
-    dev_free(h->alive); dev_free(h->parent_ix); dev_free(h->rdm_acc); h->rdm_on = false;
-    dev_free(h->sf_acc); h->sf_on = false;
-    dev_free(h->closed_w); h->closed_w_n = 0;
-    if (h->pack_tmp) { hipFree(h->pack_tmp); h->pack_tmp = nullptr; }
-    h->exx_part_len = 0; h->gfrag_bytes = 0; h->nw = 0;
+    h->mem.release(LT_WALKERS);
+    h->ghalf = nullptr; h->vbias = nullptr;         // views of ghalf_all / vbias_all
+    h->est_acc_pending = false; h->fuse_est_req = false;
+    h->gf.gsum.clear(); h->gf.vbias.clear(); h->gf.gdiag.clear(); h->gdiag_parts = 0;
+    h->msd_fb_gbar = false;
+    h->nbp = 0; h->bpo_two = h->bpo_ekt = h->bpo_sf = 0; h->bpo_nL = 0; h->it_nmax = 0;
+    h->rdm_on = false; h->sf_on = false;
+    h->nw = 0;
 }
 
 // rH1[i, q] = sum_p conj(psi[p, i]) H1_s[p, q]  (s = spin of orbital i)
@@ -126,7 +56,9 @@ int build_rH1(afq_handle *h, const std::vector<double> &H1, const std::vector<do
             }
         }
     }
-    return dev_upload(h, &h->rH1, r.data(), (size_t)nt * M);
+    int rc = dev_upload(h, LT_TRIAL, &h->dets[h->cur_det].rH1, r.data(), (size_t)nt * M);
+    select_det(h, h->cur_det, true);
+    return rc;
 }
 
 }  // namespace
@@ -144,7 +76,8 @@ static afq_host_cache *cache_of(afq_handle *h) { return &static_cast<afq_handle_
 
 static int upload_psi(afq_handle *h, const double *psi) {
     const size_t n = (size_t)h->M * h->nt;
-    int rc = dev_upload(h, &h->psi, psi, n);
+    afq_handle::DetOps &o = h->dets[h->cur_det];
+    int rc = dev_upload(h, LT_TRIAL, &o.psi, psi, n);
     if (rc) return rc;
     cache_of(h)->psi.assign(psi, psi + 2 * n);
     h->psi_real = true;
@@ -161,10 +94,11 @@ static int upload_psi(afq_handle *h, const double *psi) {
                 pt[2 * ((size_t)i * h->M + p_)] = pc[2 * ((size_t)p_ * h->nt + i)];
                 pt[2 * ((size_t)i * h->M + p_) + 1] = pc[2 * ((size_t)p_ * h->nt + i) + 1];
             }
-        int rc2 = dev_upload(h, &h->psicT, pt.data(), n);
-        if (rc2) return rc2;
+        if ((rc = dev_upload(h, LT_TRIAL, &h->psicT, pt.data(), n))) return rc;
     }
-    return dev_upload(h, &h->psic, pc.data(), n);
+    rc = dev_upload(h, LT_TRIAL, &o.psic, pc.data(), n);
+    select_det(h, h->cur_det, true);
+    return rc;
 }
 
 static int maybe_build_rH1(afq_handle *h) {
@@ -223,15 +157,13 @@ int afq_create(int device_id, afq_handle **out) {
     h->device = device_id;
     if (hipStreamCreate(&h->stream) != hipSuccess) { delete h; return AFQ_EHIP; }
     hipEventCreate(&h->ev0); hipEventCreate(&h->ev1);
-    if (hipMalloc(&h->estimates, sizeof(cplx) * AFQ_EST_COUNT_) != hipSuccess ||
-        hipMalloc(&h->counters, sizeof(unsigned long long) * AFQ_NCOUNTERS) != hipSuccess ||
-        hipMalloc(&h->closed_bad, sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc(&h->scal, sizeof(double) * AFQ_NSCAL) != hipSuccess) { delete h; return AFQ_ENOMEM; }
+    if (dev_alloc(h, LT_HANDLE, &h->estimates, AFQ_EST_COUNT_) || dev_alloc(h, LT_HANDLE, &h->counters, AFQ_NCOUNTERS) ||
+        dev_alloc(h, LT_HANDLE, &h->closed_bad, 1) || dev_alloc(h, LT_HANDLE, &h->scal, AFQ_NSCAL) ||
+        dev_alloc(h, LT_HANDLE, (char **)&h->zero_page, 256)) { h->mem.release(LT_HANDLE); delete h; return AFQ_ENOMEM; }
     hipMemset(h->estimates, 0, sizeof(cplx) * AFQ_EST_COUNT_);
     hipMemset(h->counters, 0, sizeof(unsigned long long) * AFQ_NCOUNTERS);
     hipMemset(h->closed_bad, 0, sizeof(unsigned long long));
     hipMemset(h->scal, 0, sizeof(double) * AFQ_NSCAL);
-    if (hipMalloc(&h->zero_page, 256) != hipSuccess) { delete h; return AFQ_ENOMEM; }
     hipMemset(h->zero_page, 0, 256);
     // diagnostics (not tuning): AFQ_DEBUG_SYNC=1 synchronises and checks after every launch (a failing kernel is
     // named in afq_last_error), AFQ_DEBUG_MARKERS=1 queues a marker behind every launch so that afq_last_launch
@@ -254,9 +186,7 @@ int afq_destroy(afq_handle *h) {
     k_ueg_fast_free(h);
     free_walkers(h);
     free_system(h);
-    dev_free(h->psi); dev_free(h->psic); dev_free(h->psicT); dev_free(h->BH1); dev_free(h->mf_shift);
-    dev_free(h->estimates); dev_free(h->counters); dev_free(h->closed_bad); dev_free(h->scal);
-    if (h->zero_page) hipFree(h->zero_page);
+    h->mem.release(LT_HANDLE);
     if (h->retired) hipHostFree((void *)h->retired);
     hipEventDestroy(h->ev0); hipEventDestroy(h->ev1);
     if (h->est_stage) hipHostFree(h->est_stage);
@@ -308,20 +238,17 @@ static int upload_rchol(afq_handle *h, const double *rchol, bool real) {
         for (int n = 0; n < K; ++n) re[q * h->ld_rc + n] = rchol[2 * (q * K + n)];
     h->rchol_real = real;
     h->gf.rewritten();                  // force-bias partials contracted with the old vectors are stale
-    h->rchol_same = h->na == h->nb && memcmp(rchol, rchol + 2 * (size_t)h->na * h->M * K, sizeof(double) * 2 * (size_t)h->na * h->M * K) == 0;
-    k_free_atil(h->atil);                  // the quadratic-form operand belongs to the old vectors
+    afq_handle::DetOps &o = h->dets[h->cur_det];
+    o.rchol_same = h->na == h->nb && memcmp(rchol, rchol + 2 * (size_t)h->na * h->M * K, sizeof(double) * 2 * (size_t)h->na * h->M * K) == 0;
     h->atil_unavailable = false;
-    if ((rc = dev_upload(h, &h->rchol_re, re.data(), re.size()))) return rc;
+    if ((rc = dev_upload(h, LT_TRIAL, &o.rchol_re, re.data(), re.size()))) return rc;
     if (!real) {
         std::vector<double> im(nq * h->ld_rc, 0.0);
         for (size_t q = 0; q < nq; ++q)
             for (int n = 0; n < K; ++n) im[q * h->ld_rc + n] = rchol[2 * (q * K + n) + 1];
-        if ((rc = dev_upload(h, &h->rchol_im, im.data(), im.size()))) return rc;
+        if ((rc = dev_upload(h, LT_TRIAL, &o.rchol_im, im.data(), im.size()))) return rc;
     }
-    for (int s = 0; s < 2; ++s) {
-        if (h->rchol_frag[s]) { hipFree(h->rchol_frag[s]); h->rchol_frag[s] = nullptr; }
-        if (h->rchol_frag_im[s]) { hipFree(h->rchol_frag_im[s]); h->rchol_frag_im[s] = nullptr; }
-    }
+    select_det(h, h->cur_det, true);
     return k_prepare_energy_operands(h, rchol);
 }
 
@@ -355,19 +282,19 @@ int afq_set_system_generic(afq_handle *h, int M, int K, int na, int nb, const do
                     const double *a = hs_pot + ((size_t)p * M + q) * K;
                     for (int n = 0; n < K; ++n) t[(size_t)n * h->ld_hs + c] = a[n];
                 }
-            if ((rc = dev_upload(h, &h->hs_pot, t.data(), t.size()))) return rc;
-            if ((rc = dev_upload(h, &h->hs_pair, pq.data(), np))) return rc;
+            if ((rc = dev_upload(h, LT_SYSTEM, &h->hs_pot, t.data(), t.size()))) return rc;
+            if ((rc = dev_upload(h, LT_SYSTEM, &h->hs_pair, pq.data(), np))) return rc;
         } else {
             h->ld_hs = (long)((mm + 1) & ~(size_t)1);
             std::vector<double> t((size_t)K * h->ld_hs, 0.0);
             for (size_t r = 0; r < mm; ++r)
                 for (int n = 0; n < K; ++n) t[(size_t)n * h->ld_hs + r] = hs_pot[r * K + n];
-            if ((rc = dev_upload(h, &h->hs_pot, t.data(), t.size()))) return rc;
+            if ((rc = dev_upload(h, LT_SYSTEM, &h->hs_pot, t.data(), t.size()))) return rc;
         }
     }
     h->ld_rc = (long)((K + 1) & ~1);
     if ((rc = upload_rchol(h, rchol, rchol_is_real(rchol, nq * K)))) return rc;
-    if ((rc = dev_upload(h, &h->H1, H1, 2 * mm))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->H1, H1, 2 * mm))) return rc;
     cache_of(h)->H1.assign(H1, H1 + 4 * mm);
     return AFQ_OK;
 }
@@ -414,10 +341,10 @@ int afq_set_system_generic_c128(afq_handle *h, int M, int K, int na, int nb, con
                 for (int n = 0; n < K; ++n) ti[(size_t)n * h->ld_hs_im + ci] = at(p, q, n, 1);
                 ++ci;
             }
-        if ((rc = dev_upload(h, &h->hs_pot, tr.data(), tr.size()))) return rc;
-        if ((rc = dev_upload(h, &h->hs_pot_im, ti.data(), ti.size()))) return rc;
-        if ((rc = dev_upload(h, &h->hs_pair, pq.data(), np))) return rc;
-        if (nu && (rc = dev_upload(h, &h->hs_pair_im, pqi.data(), nu))) return rc;
+        if ((rc = dev_upload(h, LT_SYSTEM, &h->hs_pot, tr.data(), tr.size()))) return rc;
+        if ((rc = dev_upload(h, LT_SYSTEM, &h->hs_pot_im, ti.data(), ti.size()))) return rc;
+        if ((rc = dev_upload(h, LT_SYSTEM, &h->hs_pair, pq.data(), np))) return rc;
+        if (nu && (rc = dev_upload(h, LT_SYSTEM, &h->hs_pair_im, pqi.data(), nu))) return rc;
     } else {
         h->ld_hs = h->ld_hs_im = (long)((mm + 1) & ~(size_t)1);
         std::vector<double> tr((size_t)K * h->ld_hs, 0.0), ti((size_t)K * h->ld_hs, 0.0);
@@ -426,12 +353,12 @@ int afq_set_system_generic_c128(afq_handle *h, int M, int K, int na, int nb, con
                 tr[(size_t)n * h->ld_hs + r] = hs_pot[2 * (r * K + n)];
                 ti[(size_t)n * h->ld_hs + r] = hs_pot[2 * (r * K + n) + 1];
             }
-        if ((rc = dev_upload(h, &h->hs_pot, tr.data(), tr.size()))) return rc;
-        if ((rc = dev_upload(h, &h->hs_pot_im, ti.data(), ti.size()))) return rc;
+        if ((rc = dev_upload(h, LT_SYSTEM, &h->hs_pot, tr.data(), tr.size()))) return rc;
+        if ((rc = dev_upload(h, LT_SYSTEM, &h->hs_pot_im, ti.data(), ti.size()))) return rc;
     }
     h->ld_rc = (long)((K + 1) & ~1);
     if ((rc = upload_rchol(h, rchol, rchol_is_real(rchol, nq * K)))) return rc;
-    if ((rc = dev_upload(h, &h->H1, H1, 2 * mm))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->H1, H1, 2 * mm))) return rc;
     cache_of(h)->H1.assign(H1, H1 + 4 * mm);
     return AFQ_OK;
 }
@@ -443,7 +370,7 @@ int afq_set_system_hubbard(afq_handle *h, int M, int na, int nb, double U, const
     if (rc) return rc;
     h->U = U; h->ecore = 0.0;
     const size_t mm = (size_t)M * M;
-    if ((rc = dev_upload(h, &h->H1, T, 2 * mm))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->H1, T, 2 * mm))) return rc;
     cache_of(h)->H1.assign(T, T + 4 * mm);
     return AFQ_OK;
 }
@@ -462,9 +389,9 @@ static int csc_to_csr(afq_handle *h, int nrow, int ncol, const int64_t *cp, cons
             col[d] = c; v[2 * d] = val[2 * z]; v[2 * d + 1] = val[2 * z + 1];
         }
     int rc;
-    if ((rc = dev_upload(h, rp_d, rp.data(), rp.size()))) return rc;
-    if ((rc = dev_upload(h, col_d, col.data(), col.size()))) return rc;
-    return dev_upload(h, val_d, v.data(), (size_t)nnz);
+    if ((rc = dev_upload(h, LT_SYSTEM, rp_d, rp.data(), rp.size()))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, col_d, col.data(), col.size()))) return rc;
+    return dev_upload(h, LT_SYSTEM, val_d, v.data(), (size_t)nnz);
 }
 
 int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64_t *iA_colptr,
@@ -479,12 +406,12 @@ int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64
     if (rc) return rc;
     h->nq = nq; h->vol = vol; h->ecore = ecore;
     h->nnzA = iA_colptr[nq]; h->nnzB = iB_colptr[nq];
-    if ((rc = dev_upload(h, &h->iA_colptr, iA_colptr, (size_t)nq + 1))) return rc;
-    if ((rc = dev_upload(h, &h->iA_row, iA_row, (size_t)h->nnzA))) return rc;
-    if ((rc = dev_upload(h, &h->iA_val, iA_val, (size_t)h->nnzA))) return rc;
-    if ((rc = dev_upload(h, &h->iB_colptr, iB_colptr, (size_t)nq + 1))) return rc;
-    if ((rc = dev_upload(h, &h->iB_row, iB_row, (size_t)h->nnzB))) return rc;
-    if ((rc = dev_upload(h, &h->iB_val, iB_val, (size_t)h->nnzB))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->iA_colptr, iA_colptr, (size_t)nq + 1))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->iA_row, iA_row, (size_t)h->nnzA))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->iA_val, iA_val, (size_t)h->nnzA))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->iB_colptr, iB_colptr, (size_t)nq + 1))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->iB_row, iB_row, (size_t)h->nnzB))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->iB_val, iB_val, (size_t)h->nnzB))) return rc;
     if ((rc = csc_to_csr(h, M * M, nq, iA_colptr, iA_row, iA_val, &h->iA_rowptr, &h->iA_col, &h->iA_rval))) return rc;
     if ((rc = csc_to_csr(h, M * M, nq, iB_colptr, iB_row, iB_val, &h->iB_rowptr, &h->iB_col, &h->iB_rval))) return rc;
     {   // column-ELL layout of [iA | iB]: adjacent columns (= adjacent threads) read adjacent entries
@@ -508,35 +435,33 @@ int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64
             }
         }
         h->ell_len = L;
-        if ((rc = dev_upload(h, &h->ell_row, er.data(), nc * L))) return rc;
-        if ((rc = dev_upload(h, &h->ell_val, ev.data(), nc * L))) return rc;
+        if ((rc = dev_upload(h, LT_SYSTEM, &h->ell_row, er.data(), nc * L))) return rc;
+        if ((rc = dev_upload(h, LT_SYSTEM, &h->ell_val, ev.data(), nc * L))) return rc;
     }
-    if ((rc = dev_upload(h, &h->kpq_off, kpq_off, (size_t)nq + 1))) return rc;
-    if ((rc = dev_upload(h, &h->kpq_i, kpq_i, (size_t)kpq_off[nq]))) return rc;
-    if ((rc = dev_upload(h, &h->kpq_kpq, kpq_kpq, (size_t)kpq_off[nq]))) return rc;
-    if ((rc = dev_upload(h, &h->pmq_off, pmq_off, (size_t)nq + 1))) return rc;
-    if ((rc = dev_upload(h, &h->pmq_i, pmq_i, (size_t)pmq_off[nq]))) return rc;
-    if ((rc = dev_upload(h, &h->pmq_pmq, pmq_pmq, (size_t)pmq_off[nq]))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->kpq_off, kpq_off, (size_t)nq + 1))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->kpq_i, kpq_i, (size_t)kpq_off[nq]))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->kpq_kpq, kpq_kpq, (size_t)kpq_off[nq]))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->pmq_off, pmq_off, (size_t)nq + 1))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->pmq_i, pmq_i, (size_t)pmq_off[nq]))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->pmq_pmq, pmq_pmq, (size_t)pmq_off[nq]))) return rc;
     {   // rows of G referenced by the energy's index lists (estimators/ueg.py:27-88)
         std::vector<int> rmap(M, -1), rows;
         for (int64_t z = 0; z < kpq_off[nq]; ++z) if (rmap[kpq_i[z]] < 0) { rmap[kpq_i[z]] = 1; }
         for (int64_t z = 0; z < pmq_off[nq]; ++z) if (rmap[pmq_i[z]] < 0) { rmap[pmq_i[z]] = 1; }
         for (int i = 0; i < M; ++i) if (rmap[i] > 0) { rmap[i] = (int)rows.size(); rows.push_back(i); }
         h->ueg_nrows = (int)rows.size();
-        if ((rc = dev_upload(h, &h->ueg_rmap, rmap.data(), (size_t)M))) return rc;
-        if ((rc = dev_upload(h, &h->ueg_rows, rows.data(), rows.size()))) return rc;
+        if ((rc = dev_upload(h, LT_SYSTEM, &h->ueg_rmap, rmap.data(), (size_t)M))) return rc;
+        if ((rc = dev_upload(h, LT_SYSTEM, &h->ueg_rows, rows.data(), rows.size()))) return rc;
         // packed copies for energy_ueg_q_kernel (M and the staged row count fit 16 bits, the list lengths 31)
-        dev_free(h->ueg_kp); dev_free(h->ueg_pm); dev_free(h->ueg_koff); dev_free(h->ueg_poff);
-        dev_free(h->sf_kp); dev_free(h->sf_pm); dev_free(h->sf_order); h->sf_nlong = 0;
         if (M < 65536 && kpq_off[nq] < (1LL << 31) && pmq_off[nq] < (1LL << 31)) {
             std::vector<int> kp((size_t)kpq_off[nq]), pm((size_t)pmq_off[nq]), ko((size_t)nq + 1), po((size_t)nq + 1);
             for (int64_t z = 0; z < kpq_off[nq]; ++z) kp[z] = (rmap[kpq_i[z]] << 16) | (int)kpq_kpq[z];
             for (int64_t z = 0; z < pmq_off[nq]; ++z) pm[z] = (rmap[pmq_i[z]] << 16) | (int)pmq_pmq[z];
             for (int q = 0; q <= nq; ++q) { ko[q] = (int)kpq_off[q]; po[q] = (int)pmq_off[q]; }
-            if ((rc = dev_upload(h, &h->ueg_kp, kp.data(), kp.size() ? kp.size() : 1))) return rc;
-            if ((rc = dev_upload(h, &h->ueg_pm, pm.data(), pm.size() ? pm.size() : 1))) return rc;
-            if ((rc = dev_upload(h, &h->ueg_koff, ko.data(), ko.size()))) return rc;
-            if ((rc = dev_upload(h, &h->ueg_poff, po.data(), po.size()))) return rc;
+            if ((rc = dev_upload(h, LT_SYSTEM, &h->ueg_kp, kp.data(), kp.size() ? kp.size() : 1))) return rc;
+            if ((rc = dev_upload(h, LT_SYSTEM, &h->ueg_pm, pm.data(), pm.size() ? pm.size() : 1))) return rc;
+            if ((rc = dev_upload(h, LT_SYSTEM, &h->ueg_koff, ko.data(), ko.size()))) return rc;
+            if ((rc = dev_upload(h, LT_SYSTEM, &h->ueg_poff, po.data(), po.size()))) return rc;
             // the same lists for gathers from G itself, and the deal of the pair sums on general Green's functions
             // (k_ueg_sf.hip): momentum transfers by decreasing nk * np, ties by q; those above 64 pairs take a wave each
             for (int64_t z = 0; z < kpq_off[nq]; ++z) kp[z] = ((int)kpq_i[z] << 16) | (int)kpq_kpq[z];
@@ -547,13 +472,13 @@ int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64
             std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
             h->sf_nlong = 0;
             while (h->sf_nlong < nq && cost[order[h->sf_nlong]] > 64) ++h->sf_nlong;
-            if ((rc = dev_upload(h, &h->sf_kp, kp.data(), kp.size() ? kp.size() : 1))) return rc;
-            if ((rc = dev_upload(h, &h->sf_pm, pm.data(), pm.size() ? pm.size() : 1))) return rc;
-            if ((rc = dev_upload(h, &h->sf_order, order.data(), order.size() ? order.size() : 1))) return rc;
+            if ((rc = dev_upload(h, LT_SYSTEM, &h->sf_kp, kp.data(), kp.size() ? kp.size() : 1))) return rc;
+            if ((rc = dev_upload(h, LT_SYSTEM, &h->sf_pm, pm.data(), pm.size() ? pm.size() : 1))) return rc;
+            if ((rc = dev_upload(h, LT_SYSTEM, &h->sf_order, order.data(), order.size() ? order.size() : 1))) return rc;
         }
     }
-    if ((rc = dev_upload(h, &h->vqvec, vqvec, (size_t)nq))) return rc;
-    if ((rc = dev_upload(h, &h->H1diag, H1diag, (size_t)2 * M))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->vqvec, vqvec, (size_t)nq))) return rc;
+    if ((rc = dev_upload(h, LT_SYSTEM, &h->H1diag, H1diag, (size_t)2 * M))) return rc;
     cache_of(h)->H1.clear();
     return k_ueg_fast_system(h, M, nq, iA_colptr, iA_row, iA_val, iB_colptr, iB_row, iB_val);
 }
@@ -577,33 +502,21 @@ int afq_set_trial_multi(afq_handle *h, int ndet, const double *psi, const double
     if (h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "multi-determinant trials need a generic system");
     if (h->nw) AFQ_FAIL(h, AFQ_ESTATE, "set the trial before allocating walkers");
     hipSetDevice(h->device);
-    // drop the operands afq_set_system_generic uploaded for a single determinant
-    free_dets(h);
-    dev_free(h->psi); dev_free(h->psic); dev_free(h->rH1); dev_free(h->rchol_re); dev_free(h->rchol_im);
-    for (int s = 0; s < 2; ++s) { dev_free(h->rchol_frag[s]); dev_free(h->rchol_frag_im[s]); }
-    k_free_atil(h->atil);
+    free_dets(h);           // the operands afq_set_system_generic uploaded for a single determinant included
     const size_t npsi = (size_t)h->M * h->nt, nrc = npsi * h->K;
     const bool real = rchol_is_real(rchol, nrc * ndet);
-    h->ndet = ndet; h->cur_det = 0;
-    h->dets.assign(ndet > 1 ? ndet : 0, afq_handle::DetOps());
+    h->ndet = ndet;
+    h->dets.assign(ndet, afq_handle::DetOps());
     int rc;
     for (int d = 0; d < ndet; ++d) {
-        if (ndet > 1) {
-            // fresh (null) slots for determinant d; stash_det records what the uploads allocate
-            if (d > 0) {
-                stash_det(h);
-                h->psi = nullptr; h->psic = nullptr; h->rH1 = nullptr; h->rchol_re = nullptr; h->rchol_im = nullptr;
-                for (int s = 0; s < 2; ++s) { h->rchol_frag[s] = nullptr; h->rchol_frag_im[s] = nullptr; h->atil[s] = nullptr; }
-                h->cur_det = d;
-            }
-        }
+        select_det(h, d, true);
         if ((rc = upload_psi(h, psi + 2 * npsi * d))) return rc;
         if ((rc = upload_rchol(h, rchol + 2 * nrc * d, real))) return rc;
         h->have_trial = true;
         if ((rc = maybe_build_rH1(h))) return rc;
     }
     select_det(h, 0);
-    if ((rc = dev_upload(h, &h->coeffs, coeffs, (size_t)ndet))) return rc;
+    if ((rc = dev_upload(h, LT_TRIAL, &h->coeffs, coeffs, (size_t)ndet))) return rc;
     if (ndet > 1) {
         // conj(psi_d)^T of every determinant stacked, [ndet nt, M]: both operands of the averaged Green's function
         // (k_force_bias_msd_gbar) read it along the orbital index
@@ -617,10 +530,10 @@ int afq_set_trial_multi(afq_handle *h, int ndet, const double *psi, const double
                     double *dst = &pt[2 * (((size_t)d * nt + i) * M + p_)];
                     dst[0] = src[0]; dst[1] = -src[1];
                 }
-        if ((rc = dev_upload(h, &h->msd_psicT, pt.data(), kkp * M))) return rc;
+        if ((rc = dev_upload(h, LT_TRIAL, &h->msd_psicT, pt.data(), kkp * M))) return rc;
         if (h->hs_cplx == AFQ_HS_HERMITIAN) {
             for (double &v : pt) v = -v;
-            if ((rc = dev_upload(h, &h->msd_psicT_neg, pt.data(), kkp * M))) return rc;
+            if ((rc = dev_upload(h, LT_TRIAL, &h->msd_psicT_neg, pt.data(), kkp * M))) return rc;
         }
     }
     return AFQ_OK;
@@ -633,11 +546,11 @@ int afq_set_propagator(afq_handle *h, const double *BH1, const double *mf_shift,
     if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "set the system before the propagator");
     hipSetDevice(h->device);
     int rc;
-    if ((rc = dev_upload(h, &h->BH1, BH1, (size_t)2 * h->M * h->M))) return rc;
+    if ((rc = dev_upload(h, LT_HANDLE, &h->BH1, BH1, (size_t)2 * h->M * h->M))) return rc;
     h->bh1_real = true;
     h->bh1_same = memcmp(BH1, BH1 + (size_t)2 * h->M * h->M, sizeof(double) * 2 * h->M * h->M) == 0;
     for (size_t i = 0, n = (size_t)2 * h->M * h->M; i < n && h->bh1_real; ++i) h->bh1_real = BH1[2 * i + 1] == 0.0;
-    if ((rc = dev_upload(h, &h->mf_shift, mf_shift, (size_t)h->K))) return rc;
+    if ((rc = dev_upload(h, LT_HANDLE, &h->mf_shift, mf_shift, (size_t)h->K))) return rc;
     if (h->kind == AFQ_SYS_UEG && (rc = k_ueg_fast_propagator(h, BH1))) return rc;
     h->dt = dt; h->sqrt_dt = std::pow(dt, 0.5); h->exp_order = exp_order;
     if (flags & AFQ_PROP_FREE_PROJECTION) flags &= ~AFQ_PROP_FORCE_BIAS;   // continuous.py:30-33
@@ -649,7 +562,7 @@ int afq_set_propagator(afq_handle *h, const double *BH1, const double *mf_shift,
     if (h->nw && (old_nv != h->nv || old_diag != h->vhs_diag || !h->vhs)) {
         // (diagonal potential: a second block of the same size holds its Taylor factors)
         const size_t per = h->vhs_diag ? (size_t)2 * h->nv * h->M : (size_t)h->nv * h->M * h->M;
-        if ((rc = dev_alloc(h, &h->vhs, per * h->nw))) return rc;
+        if ((rc = dev_alloc(h, LT_WALKERS, &h->vhs, per * h->nw))) return rc;
     }
     return AFQ_OK;
 }
@@ -662,16 +575,16 @@ int afq_walkers_alloc(afq_handle *h, int nw) {
     hipSetDevice(h->device);
     free_walkers(h);
     const size_t per = (size_t)h->M * h->nt, K = h->K, n = nw;
-    int rc;
-#define A_(ptr, cnt) if ((rc = dev_alloc(h, &(ptr), (cnt)))) return rc;
-    A_(h->phi, per * n) A_(h->phi_t, per * n) A_(h->phi_t2, per * n)
-    A_(h->weight, n) A_(h->unscaled, n) A_(h->detR, n) A_(h->log_detR, n)
-    A_(h->ot, n) A_(h->ehyb, n) A_(h->phase, n) A_(h->eloc, n)
-    A_(h->ghalf_all, per * n * h->ndet) A_(h->ovlp_old, n) A_(h->ovlp_new, n)
-    h->ghalf = h->ghalf_all + (size_t)h->cur_det * n * per;
-    if (h->ndet > 1) { A_(h->detd, n * h->ndet) A_(h->detd_a, n * h->ndet) A_(h->detw, n * h->ndet) A_(h->energy_all, 3 * n * h->ndet) }
-    A_(h->xi, K * n) A_(h->xbar, K * n) A_(h->xs, K * n) A_(h->cmf, n) A_(h->cfb, n)
-    A_(h->energy, 3 * n) A_(h->alive, n) A_(h->parent_ix, n)
+    int rc = 0;
+    auto walk = [&](auto &slot, size_t cnt) { return rc = dev_alloc(h, LT_WALKERS, &slot, cnt); };
+    if (walk(h->phi, per * n) || walk(h->phi_t, per * n) || walk(h->phi_t2, per * n) ||
+        walk(h->weight, n) || walk(h->unscaled, n) || walk(h->detR, n) || walk(h->log_detR, n) ||
+        walk(h->ot, n) || walk(h->ehyb, n) || walk(h->phase, n) || walk(h->eloc, n) ||
+        walk(h->ghalf_all, per * n * h->ndet) || walk(h->ovlp_old, n) || walk(h->ovlp_new, n)) return rc;
+    if (h->ndet > 1 && (walk(h->detd, n * h->ndet) || walk(h->detd_a, n * h->ndet) || walk(h->detw, n * h->ndet) ||
+                        walk(h->energy_all, 3 * n * h->ndet))) return rc;
+    if (walk(h->xi, K * n) || walk(h->xbar, K * n) || walk(h->xs, K * n) || walk(h->cmf, n) || walk(h->cfb, n) ||
+        walk(h->energy, 3 * n) || walk(h->alive, n) || walk(h->parent_ix, n)) return rc;
     // force-bias contraction slices: enough wave-tasks to fill 1024 SIMDs
     h->fb_split = 1;
     if (h->kind == AFQ_SYS_GENERIC) {
@@ -688,21 +601,18 @@ int afq_walkers_alloc(afq_handle *h, int nw) {
         const int nmax = std::max(h->na, h->nb) * h->M;
         while (sp > 1 && nmax / sp < 64) --sp;
         h->fb_split = sp;
-        A_(h->vbias_all, (size_t)2 * sp * n * K * h->ndet)
-        h->vbias = h->vbias_all + (size_t)h->cur_det * 2 * sp * n * K;
+        if (walk(h->vbias_all, (size_t)2 * sp * n * K * h->ndet)) return rc;
     } else if (h->kind == AFQ_SYS_UEG) {
-        A_(h->vbias_all, n * K)
-        h->vbias = h->vbias_all;
+        if (walk(h->vbias_all, n * K) || walk(h->G, (size_t)2 * h->M * h->M * n)) return rc;
     }
-    if (h->kind == AFQ_SYS_UEG) A_(h->G, (size_t)2 * h->M * h->M * n)
     {
         // Hubbard: diagonals of up to two HS matrices, and their Taylor factors behind them
         const size_t pv = h->kind == AFQ_SYS_HUBBARD ? (size_t)4 * h->M : (size_t)h->M * h->M;
-        A_(h->vhs, pv * n)
+        if (walk(h->vhs, pv * n)) return rc;
     }
-#undef A_
-    AFQ_HIP(h, hipMalloc(&h->pack_tmp, std::max((size_t)nw * 2 * sizeof(int), (size_t)4096)));
+    if ((rc = dev_alloc(h, LT_WALKERS, (char **)&h->pack_tmp, std::max((size_t)nw * 2 * sizeof(int), (size_t)4096)))) return rc;
     h->nw = nw;
+    select_det(h, h->cur_det, true);              // ghalf / vbias: the selected determinant's slices
     h->cap_frac = 0.0; h->cap_total = -1.0;       // a cap armed for an earlier population does not carry over
     {   // walker.total_weight starts as the population size (walkers/handler.py:164); with a communicator
         // the population is nw walkers on every rank
@@ -836,17 +746,16 @@ int afq_inverse_overlap(afq_handle *h, double *oinv_out, double *ovlp_out) {
     if (rc) return rc;
     if (h->ndet > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "inverse overlaps: single-determinant trials");
     const size_t nmax = h->na > h->nb ? h->na : h->nb, n = (size_t)h->nw * 2 * nmax * nmax;
-    cplx *tmp = nullptr;
-    if ((rc = dev_alloc(h, &tmp, n))) return rc;
+    DevTemp<cplx> tmp;
+    if ((rc = dev_temp(h, tmp, n))) return rc;
     AFQ_HIP(h, hipMemsetAsync(tmp, 0, sizeof(cplx) * n, h->stream));
-    if ((rc = k_alive(h))) { dev_free(tmp); return rc; }
+    if ((rc = k_alive(h))) return rc;
     // every walker, dead or alive: flag them all for this call
     std::vector<int> ones(h->nw, 1);
     AFQ_HIP(h, hipMemcpyAsync(h->alive, ones.data(), sizeof(int) * h->nw, hipMemcpyHostToDevice, h->stream));
     rc = k_inverse_overlap(h, tmp, h->ovlp_new);
     if (!rc) rc = copy_out(h, oinv_out, tmp, sizeof(cplx) * n);
     if (!rc && ovlp_out) rc = copy_out(h, ovlp_out, h->ovlp_new, sizeof(cplx) * h->nw);
-    dev_free(tmp);
     if (!rc) rc = k_alive(h);
     return rc;
 }
@@ -1087,7 +996,7 @@ int afq_estimates_fuse_next(afq_handle *h) {
     if (h->hirsch) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "afq_estimates_fuse_next: continuous propagator only");
     hipSetDevice(h->device);
     if (!h->est_acc) {
-        int rc = dev_alloc(h, &h->est_acc, (size_t)6 * h->nw);
+        int rc = dev_alloc(h, LT_WALKERS, &h->est_acc, (size_t)6 * h->nw);
         if (rc) return rc;
         AFQ_HIP(h, hipMemsetAsync(h->est_acc, 0, sizeof(double) * 6 * h->nw, h->stream));
     }
@@ -1489,7 +1398,7 @@ int afq_estimates_rdm(afq_handle *h, int on) {
     h->rdm_on = on != 0;
     if (h->rdm_on && !h->rdm_acc) {
         const size_t n = (size_t)2 * h->M * h->M;
-        if ((rc = dev_alloc(h, &h->rdm_acc, n))) return rc;
+        if ((rc = dev_alloc(h, LT_WALKERS, &h->rdm_acc, n))) return rc;
         AFQ_HIP(h, hipMemsetAsync(h->rdm_acc, 0, sizeof(double) * n, h->stream));
     }
     return AFQ_OK;
@@ -1505,7 +1414,7 @@ int afq_estimates_sf(afq_handle *h, int on) {
     h->sf_on = on != 0;
     if (h->sf_on && !h->sf_acc) {
         const size_t n = (size_t)4 * h->nq;
-        if ((rc = dev_alloc(h, &h->sf_acc, n))) return rc;
+        if ((rc = dev_alloc(h, LT_WALKERS, &h->sf_acc, n))) return rc;
         AFQ_HIP(h, hipMemsetAsync(h->sf_acc, 0, sizeof(double) * n, h->stream));
     }
     return AFQ_OK;
@@ -1645,24 +1554,21 @@ int afq_rng_seed(afq_handle *h, uint64_t seed, uint64_t stream) {
 int afq_rng_normal(afq_handle *h, double *out, int64_t n) {
     if (!h || !out || n < 1) return AFQ_EINVAL;
     hipSetDevice(h->device);
-    double *tmp = nullptr;
-    int rc = dev_alloc(h, &tmp, (size_t)n);
-    if (rc) return rc;
-    rc = k_rng_normal_into(h, tmp, (long)n);
+    DevTemp<double> tmp;
+    int rc = dev_temp(h, tmp, (size_t)n);
+    if (!rc) rc = k_rng_normal_into(h, tmp, (long)n);
     if (!rc) rc = copy_out(h, out, tmp, sizeof(double) * (size_t)n);
-    dev_free(tmp);
     return rc;
 }
 
 int afq_rng_philox4x32(afq_handle *h, const uint32_t *ctr_key, uint32_t *out, int n) {
     if (!h || !ctr_key || !out || n < 1) return AFQ_EINVAL;
     hipSetDevice(h->device);
-    uint32_t *in_d = nullptr, *out_d = nullptr;
-    int rc = dev_upload(h, &in_d, ctr_key, (size_t)6 * n);
-    if (!rc) rc = dev_alloc(h, &out_d, (size_t)4 * n);
+    DevTemp<uint32_t> in_d, out_d;
+    int rc = dev_temp(h, in_d, (size_t)6 * n, ctr_key);
+    if (!rc) rc = dev_temp(h, out_d, (size_t)4 * n);
     if (!rc) rc = k_philox_raw(h, in_d, out_d, n);
     if (!rc) rc = copy_out(h, out, out_d, sizeof(uint32_t) * 4 * (size_t)n);
-    dev_free(in_d); dev_free(out_d);
     return rc;
 }
 
@@ -1722,11 +1628,11 @@ static int hirsch_buffers(afq_handle *h) {
     if (h->hs_oinv) return AFQ_OK;
     const size_t n = h->nw, nmax = h->na > h->nb ? h->na : h->nb;
     int rc;
-    if ((rc = dev_alloc(h, &h->hs_oinv, n * 2 * nmax * nmax))) return rc;
-    if ((rc = dev_alloc(h, &h->hs_u, n * h->M))) return rc;
-    if ((rc = dev_alloc(h, &h->hs_fields, n * h->M))) return rc;
-    if ((rc = dev_alloc(h, &h->hs_used, n))) return rc;
-    if ((rc = dev_alloc(h, &h->hs_alive0, n))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->hs_oinv, n * 2 * nmax * nmax))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->hs_u, n * h->M))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->hs_fields, n * h->M))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->hs_used, n))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->hs_alive0, n))) return rc;
     AFQ_HIP(h, hipMemsetAsync(h->hs_alive0, 0, sizeof(int) * n, h->stream));
     return AFQ_OK;
 }
@@ -1745,7 +1651,7 @@ int afq_set_propagator_hirsch(afq_handle *h, const double *bt2, double dt, int c
     if (h->ndet > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "Hirsch propagator: single-determinant trials");
     hipSetDevice(h->device);
     int rc;
-    if ((rc = dev_upload(h, &h->BH1, bt2, (size_t)2 * h->M * h->M))) return rc;
+    if ((rc = dev_upload(h, LT_HANDLE, &h->BH1, bt2, (size_t)2 * h->M * h->M))) return rc;
     h->bh1_real = true;         // (expm of a real hopping matrix: the one-body GEMM then needs two real products per pair)
     for (size_t i = 0, n = (size_t)2 * h->M * h->M; i < n && h->bh1_real; ++i) h->bh1_real = bt2[2 * i + 1] == 0.0;
     h->bh1_same = false;
@@ -1778,7 +1684,7 @@ int afq_set_propagator_hirsch(afq_handle *h, const double *bt2, double dt, int c
     h->hs_direct = false;
     if (!h->mf_shift) {
         std::vector<double> z(2 * (size_t)h->K, 0.0);
-        if ((rc = dev_upload(h, &h->mf_shift, z.data(), (size_t)h->K))) return rc;
+        if ((rc = dev_upload(h, LT_HANDLE, &h->mf_shift, z.data(), (size_t)h->K))) return rc;
     }
     h->dt = dt; h->sqrt_dt = std::sqrt(dt);
     h->flags = 0; h->nv = 1; h->vhs_diag = true;

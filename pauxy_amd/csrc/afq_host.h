@@ -2,23 +2,6 @@
 #pragma once
 #include "afq_internal.h"
 
-template <class T> static int dev_alloc(afq_handle *h, T **p, size_t n) {
-    if (*p) { hipFree(*p); *p = nullptr; }
-    if (n == 0) return AFQ_OK;
-    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
-    if (e != hipSuccess) { h->err = std::string("hipMalloc: ") + hipGetErrorString(e); return AFQ_ENOMEM; }
-    return AFQ_OK;
-}
-
-template <class T> static int dev_upload(afq_handle *h, T **p, const void *src, size_t n) {
-    int rc = dev_alloc(h, p, n);
-    if (rc) return rc;
-    if (n) AFQ_HIP(h, hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return AFQ_OK;
-}
-
-template <class T> static void dev_free(T *&p) { if (p) { hipFree(p); p = nullptr; } }
-
 #define AFQ_API(h, name) do { if (h) (h)->crumb_api = name; } while (0)
 
 static inline int need_ready(afq_handle *h, bool prop) {
@@ -30,11 +13,7 @@ static inline int need_ready(afq_handle *h, bool prop) {
 }
 
 static inline int ensure_G(afq_handle *h) {
-    if (!h->G) {
-        int rc = dev_alloc(h, &h->G, (size_t)2 * h->M * h->M * h->nw);
-        if (rc) return rc;
-    }
-    return AFQ_OK;
+    return dev_ensure(h, LT_WALKERS, &h->G, (size_t)2 * h->M * h->M * h->nw);
 }
 
 static inline int copy_out(afq_handle *h, void *host, const void *dev, size_t bytes) {

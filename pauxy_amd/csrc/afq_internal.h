@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/afqmc_hip.h"
 #include "greens_cache.h"
+#include "dev_mem.h"
 
 typedef double2 cplx;   // (x = re, y = im), same bytes as numpy complex128
 
@@ -45,6 +46,7 @@ struct afq_handle {
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
+    DevMem mem;                     // the owning slots of every device block below, by lifetime (dev_mem.h)
 
     // ---- system
     int kind = 0;
@@ -69,8 +71,7 @@ struct afq_handle {
     double *rchol_im = nullptr;     // f64 [nt*M, ld_rc] or null when real
     double *rchol_frag[2] = {nullptr, nullptr};   // energy-kernel A operand, fragment order, per spin
     double *rchol_frag_im[2] = {nullptr, nullptr};
-    // quadratic-form exchange (k_energy.hip): Atil_s [(N_s M), ldq] f64 (c128 when rchol is complex), built on first
-    // use; atil[1] == atil[0] when both spins have the same half-rotated vectors (closed-shell trial)
+    // quadratic-form exchange (k_energy.hip): Atil_s [(N_s M), ldq] f64 (c128 when rchol is complex), built on first use
     void *atil[2] = {nullptr, nullptr};
     bool atil_unavailable = false;  // automatic mode: Atil did not fit when it was to be built -> T-intermediate kernel
     bool rchol_same = false;        // alpha and beta blocks of rchol are bitwise equal
@@ -129,11 +130,11 @@ struct afq_handle {
     // While closed_large is set the one-body and Taylor GEMMs leave out the work-group tiles that lie wholly in the beta columns
     // of such a walker; closed_copy_beta_kernel copies the propagated alpha block over the beta block at the end of the step.
     int *closed_w = nullptr;
-    int closed_w_n = 0;
+    size_t closed_w_n = 0;
     bool closed_large = false;
 
-    // multi-determinant trial: the trial-dependent operands of every determinant;
-    // psi / psic / rchol_* / rchol_frag* / rH1 above and ghalf / vbias below are VIEWS of the selected one
+    // the trial-dependent operands of every determinant (multi-determinant trial: SURVEY 8a row 15), owned here;
+    // psi / psic / rchol_* / rchol_frag* / atil / rH1 above and ghalf / vbias below are VIEWS of the selected one
     struct DetOps {
         cplx *psi = nullptr, *psic = nullptr, *rH1 = nullptr;
         double *rchol_re = nullptr, *rchol_im = nullptr;
@@ -143,12 +144,12 @@ struct afq_handle {
         GreensCache::Stamp vbias_stamp;         // this determinant's force-bias partials (as gf.vbias for one determinant)
     };
     int ndet = 1, cur_det = 0;
-    std::vector<DetOps> dets;       // size ndet when ndet > 1
+    std::vector<DetOps> dets = std::vector<DetOps>(1);   // size ndet
     cplx *coeffs = nullptr;         // [ndet] device copy of the CI coefficients
     cplx *detd = nullptr;           // [ndet, nw] per-determinant overlaps <D_d|phi_w>
     cplx *detd_a = nullptr;         // [ndet, nw] their alpha factors det(phi_a^T conj(D_d,a)) (multi_det.py:209 tests it first)
     cplx *detw = nullptr;           // [nw, ndet] weights conj(c_d) <D_d|phi_w> of the last evaluation
-    cplx *ghalf_all = nullptr;      // owning pointers of the per-determinant slices
+    cplx *ghalf_all = nullptr;      // [ndet] slices: what ghalf / vbias point into
     cplx *vbias_all = nullptr;
     cplx *energy_all = nullptr;     // [ndet, nw, 3] per-determinant local energies
     // force bias of a multi-determinant trial through the determinant-averaged Green's function (the reference's own
@@ -261,9 +262,9 @@ struct afq_handle {
     int *qr_fail = nullptr;         // [nw] Cholesky breakdown -> Gram-Schmidt fallback
     cplx *energy = nullptr;         // [nw, 3]
     cplx *exx_part = nullptr;       // exchange partial sums
-    int64_t exx_part_len = 0;
+    size_t exx_part_len = 0;
     double *gfrag = nullptr;        // Ghalf in MFMA fragment order (energy kernel B operand)
-    size_t gfrag_bytes = 0;
+    size_t gfrag_len = 0;
     bool prop_pending = false;                      // afq_propagate_begin done, afq_propagate_finish outstanding
     double *est_stage = nullptr;                    // mapped host memory: estimator sums + scal[4] + sequence number
     unsigned long long est_seq = 0;
@@ -382,6 +383,60 @@ inline hipError_t afq_raise_lds(const void *kern, size_t lds, size_t (&set)[AFQ_
 }
 
 #define AFQ_FAIL(h, code, msg) do { (h)->err = (msg); return (code); } while (0)
+#define AFQ_TRY(call) do { if (int rc_ = (call)) return rc_; } while (0)     // (the callee has set err)
+
+// ---- the three ways a handle field comes to own device memory (dev_mem.h); what names the failing buffer in the error
+// allocate or replace: n elements (0: the slot stays null)
+inline int dev_nomem(afq_handle *h, const char *what, size_t bytes, hipError_t e) {
+    (void)hipGetLastError();
+    h->err = std::string(what) + ": hipMalloc of " + std::to_string(bytes) + " bytes failed (" + hipGetErrorString(e) + ")";
+    return AFQ_ENOMEM;
+}
+template <class T> static int dev_alloc(afq_handle *h, Lifetime lt, T **p, size_t n, const char *what = "device buffer",
+                                        size_t *len = nullptr) {
+    const hipError_t e = h->mem.replace(lt, (void **)p, n * sizeof(T), len);
+    return e == hipSuccess ? AFQ_OK : dev_nomem(h, what, n * sizeof(T), e);
+}
+template <class T> static int dev_upload(afq_handle *h, Lifetime lt, T **p, const void *src, size_t n) {
+    int rc = dev_alloc(h, lt, p, n);
+    if (rc) return rc;
+    if (n) AFQ_HIP(h, hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return AFQ_OK;
+}
+// ensure: allocate if the slot is null (a block of this lifetime is never of another size)
+template <class T> static int dev_ensure(afq_handle *h, Lifetime lt, T **p, size_t n) {
+    return *p ? AFQ_OK : dev_alloc(h, lt, p, n);
+}
+// grow: at least n elements; queued work may still read the block that is freed.  Failure leaves null and *len == 0.
+template <class T> static int dev_grow(afq_handle *h, Lifetime lt, T **p, size_t *len, size_t n, const char *what) {
+    if (n <= *len) return AFQ_OK;
+    if (*p) hipStreamSynchronize(h->stream);
+    const int rc = dev_alloc(h, lt, p, n, what, len);
+    if (!rc) *len = n;
+    return rc;
+}
+
+// a per-call buffer (freed when its DevTemp leaves scope), filled from the host when src is given
+template <class T> static int dev_temp(afq_handle *h, DevTemp<T> &t, size_t n, const void *src = nullptr) {
+    const hipError_t e = t.alloc(n);
+    if (e != hipSuccess) return dev_nomem(h, "per-call buffer", n * sizeof(T), e);
+    if (src) AFQ_HIP(h, hipMemcpy(t.p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return AFQ_OK;
+}
+
+// the handle's trial operands become views of dets[d] (and ghalf / vbias its slices)
+inline void select_det(afq_handle *h, int d, bool refresh = false) {
+    if (d == h->cur_det && !refresh) return;
+    const afq_handle::DetOps &o = h->dets[d];
+    h->psi = o.psi; h->psic = o.psic; h->rH1 = o.rH1; h->rchol_re = o.rchol_re; h->rchol_im = o.rchol_im;
+    for (int s = 0; s < 2; ++s) { h->rchol_frag[s] = o.rchol_frag[s]; h->rchol_frag_im[s] = o.rchol_frag_im[s]; h->atil[s] = o.atil[s]; }
+    h->rchol_same = o.rchol_same;
+    h->cur_det = d;
+    if (h->nw) {
+        h->ghalf = h->ghalf_all + (size_t)d * h->nw * h->M * h->nt;
+        if (h->vbias_all) h->vbias = h->vbias_all + (size_t)d * 2 * h->fb_split * h->nw * h->K;
+    }
+}
 
 struct PhaseTimer {
     afq_handle *h; int slot;
@@ -547,7 +602,6 @@ int k_comm_popcontrol(afq_handle *h, double r, double target, bool with_greens);
 int k_energy_generic(afq_handle *h);
 int k_prepare_energy_operands(afq_handle *h, const double *rchol_host);
 int k_exchange_uses_quadratic(afq_handle *h);            // which algorithm k_energy_generic takes for the current trial
-void k_free_atil(void *(&atil)[2]);
 // k_models.hip (Hubbard / UEG)
 int k_vhs_hubbard(afq_handle *h);
 int k_apply_exponential_diag(afq_handle *h, const cplx *vhs_diag);

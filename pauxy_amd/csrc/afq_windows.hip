@@ -75,14 +75,9 @@ ItcfWs itcf_carve(afq_handle *h, cplx *base, int nkeep) {
 
 // the window's device scratch, kept on the handle and grown on demand (a larger window frees the old buffer first)
 int itcf_scratch(afq_handle *h, size_t n, cplx **out) {
-    if (n > h->it_ws_len) {
-        if (h->it_ws) { hipStreamSynchronize(h->stream); dev_free(h->it_ws); h->it_ws_len = 0; }
-        const int rc = dev_alloc(h, &h->it_ws, n);
-        if (rc) return rc;
-        h->it_ws_len = n;
-    }
+    const int rc = dev_grow(h, LT_WALKERS, &h->it_ws, &h->it_ws_len, n, "imaginary-time window");
     *out = h->it_ws;
-    return AFQ_OK;
+    return rc;
 }
 
 // ---- the pieces every window is made of
@@ -246,14 +241,13 @@ int itcf_greens(afq_handle *h, const ItcfWs &w, cplx *psiR, cplx *psiL) {
 // tsz, the launch's second result T [tsz]
 template <class F> int full_g_call(afq_handle *h, const double *G, int n, double *E_out, size_t tsz, double *T_out, F launch) {
     hipSetDevice(h->device);
-    cplx *Gd = nullptr, *Ed = nullptr, *Td = nullptr;
-    int rc = dev_upload(h, &Gd, G, (size_t)2 * h->M * h->M * n);
-    if (!rc) rc = dev_alloc(h, &Ed, (size_t)3 * n);
-    if (!rc) rc = dev_alloc(h, &Td, tsz);
+    DevTemp<cplx> Gd, Ed, Td;
+    int rc = dev_temp(h, Gd, (size_t)2 * h->M * h->M * n, G);
+    if (!rc) rc = dev_temp(h, Ed, (size_t)3 * n);
+    if (!rc) rc = dev_temp(h, Td, tsz);
     if (!rc) rc = launch(Gd, Ed, Td);
     if (!rc) rc = copy_out(h, E_out, Ed, sizeof(cplx) * 3 * n);
     if (!rc && tsz) rc = copy_out(h, T_out, Td, sizeof(cplx) * tsz);
-    dev_free(Gd); dev_free(Ed); dev_free(Td);
     return rc;
 }
 
@@ -291,22 +285,22 @@ int afq_bp_configure(afq_handle *h, int nbp) {
                                         " bytes, more than half of the free device memory (" +
                                         std::to_string((unsigned long long)fr) + " bytes)");
     }
-    if ((rc = dev_alloc(h, &h->bp_hist, n * nbp * h->K))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_n, n))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_flag, n))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_cos, n))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_ph, n))) return rc;
-    if ((rc = dev_alloc(h, &h->phi_old, per * n))) return rc;
-    if ((rc = dev_alloc(h, &h->phi_bp, 2 * per * n * nd))) return rc;   // phi_bp and conj(phi_bp), of every determinant
-    if ((rc = dev_alloc(h, &h->bp_ot, n))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_detR, n))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->bp_hist, n * nbp * h->K))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->bp_n, n))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->bp_flag, n))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->bp_cos, n))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->bp_ph, n))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->phi_old, per * n))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->phi_bp, 2 * per * n * nd))) return rc;   // phi_bp and conj(phi_bp), of every determinant
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->bp_ot, n))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->bp_detR, n))) return rc;
     if (nd > 1) {
-        if ((rc = dev_alloc(h, &h->bpm_ws, msd_ws))) return rc;
+        if ((rc = dev_alloc(h, LT_WALKERS, &h->bpm_ws, msd_ws, "multi-determinant window", &h->bpm_ws_len))) return rc;
         h->bpm_ws_len = msd_ws;
     }
-    if ((rc = dev_alloc(h, &h->BH1dag, (size_t)2 * h->M * h->M))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_xs, n * h->K))) return rc;
-    if ((rc = dev_alloc(h, &h->bp_est, (size_t)4 + 2 * h->M * h->M))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->BH1dag, (size_t)2 * h->M * h->M))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->bp_xs, n * h->K))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->bp_est, (size_t)4 + 2 * h->M * h->M))) return rc;
     h->nbp = nbp;
     AFQ_HIP(h, hipMemsetAsync(h->bp_hist, 0, sizeof(cplx) * n * nbp * h->K, h->stream));
     AFQ_HIP(h, hipMemsetAsync(h->bp_flag, 0, sizeof(int) * n, h->stream));
@@ -413,7 +407,7 @@ int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, co
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "EKT with complex Cholesky vectors: the reference's 4-fold-symmetry form pins nothing");
     const size_t M = (size_t)h->M, m4 = sf ? (size_t)4 * h->nq : M * M * M * M;
     hipSetDevice(h->device);
-    dev_free(h->bpo_out);              // a buffer of an earlier call does not count against the budget
+    dev_alloc(h, LT_WALKERS, &h->bpo_out, 0);      // a buffer of an earlier call does not count against the budget
     if (two_rdm && !sf) {
         size_t fr = 0, tot = 0;
         AFQ_HIP(h, hipMemGetInfo(&fr, &tot));
@@ -423,14 +417,14 @@ int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, co
                                         " bytes (16 M^4) exceed half of the free device memory (" +
                                         std::to_string((unsigned long long)fr) + " bytes)");
     }
-    dev_free(h->bpo_h1); dev_free(h->bpo_L);
+    dev_alloc(h, LT_WALKERS, &h->bpo_h1, 0); dev_alloc(h, LT_WALKERS, &h->bpo_L, 0);
     h->bpo_two = h->bpo_ekt = h->bpo_sf = 0; h->bpo_nL = 0;
     if (ekt) {
-        if ((rc = dev_upload(h, &h->bpo_h1, h1, M * M))) return rc;
-        if (L && (rc = dev_upload(h, &h->bpo_L, L, (size_t)nL * M * M))) return rc;
+        if ((rc = dev_upload(h, LT_WALKERS, &h->bpo_h1, h1, M * M))) return rc;
+        if (L && (rc = dev_upload(h, LT_WALKERS, &h->bpo_L, L, (size_t)nL * M * M))) return rc;
         h->bpo_nL = nL;
     }
-    if ((two_rdm || ekt) && (rc = dev_alloc(h, &h->bpo_out, (two_rdm ? m4 : 0) + (ekt ? 2 * M * M : 0)))) return rc;
+    if ((two_rdm || ekt) && (rc = dev_alloc(h, LT_WALKERS, &h->bpo_out, (two_rdm ? m4 : 0) + (ekt ? 2 * M * M : 0)))) return rc;
     h->bpo_two = two_rdm ? 1 : 0; h->bpo_ekt = ekt ? 1 : 0; h->bpo_sf = sf ? 1 : 0;
     return AFQ_OK;
 }

@@ -1,0 +1,65 @@
+// Device memory of the handle, owned by lifetime.
+//
+// Every device block has exactly ONE owning slot: a pointer field of the handle (or of an afq_handle::DetOps), entered in
+// the registry under the lifetime that ends it when it is allocated -- by dev_alloc / dev_upload (allocate or replace),
+// dev_ensure (allocate if null) or dev_grow (at least n elements, with a length field).  Nothing else allocates into a
+// handle field, and nothing frees one but these three and DevMem::release:
+//   LT_HANDLE   afq_destroy              estimates, counters, closed_bad, scal, zero_page, BH1, mf_shift
+//   LT_SYSTEM   a new afq_set_system_*   the Hamiltonian's operands and what is derived from them alone
+//   LT_TRIAL    a new system or trial    dets[d].* (below), psicT, coeffs, msd_psicT*
+//   LT_WALKERS  afq_walkers_alloc        everything sized by nw, the windows configured after the walkers included
+// release(lifetime) frees every block of that lifetime, nulls its slot and zeroes the length that goes with it, so an
+// "ensure" or "grow" of a later configuration never meets a block sized for an earlier one.
+//
+// Views are never registered and never allocated through:
+//   ghalf, vbias                 offsets into ghalf_all / vbias_all (the selected determinant's slice)
+//   psi, psic, rH1, rchol_re/im, rchol_frag*, atil, rchol_same
+//                                copies of dets[cur_det], refreshed by select_det and by nothing else; dets[] is the
+//                                only owner of the trial's operands (one element for a single determinant).  An upload
+//                                writes to dets[cur_det] and then refreshes the view.
+//   dets[d].atil[1]              equals atil[0] when both spins share the half-rotated vectors: owned by atil[0] alone
+//   Lent<>                       points a VIEW field (or phi / G / BH1 / xs / ot / detR, which no release runs under)
+//                                at foreign memory for a scope; it is never handed a slot that release would free
+// The communicator (afq_comm_state) and the plane-wave tables (ueg_fast) own their memory in their own structs.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <vector>
+
+enum Lifetime { LT_HANDLE = 0, LT_SYSTEM, LT_TRIAL, LT_WALKERS, LT_COUNT };
+
+struct DevMem {
+    struct Slot { void **p; size_t *len; };
+    std::vector<Slot> owned[LT_COUNT];
+
+    // frees what the slot holds, allocates bytes (0: leaves it null) and enters the slot under lt; *len is zeroed
+    hipError_t replace(Lifetime lt, void **p, size_t bytes, size_t *len) {
+        std::vector<Slot> &v = owned[lt];
+        size_t i = 0;
+        while (i < v.size() && v[i].p != p) ++i;
+        if (i == v.size()) v.push_back({p, len});
+        if (*p) { hipFree(*p); *p = nullptr; }
+        if (len) *len = 0;
+        if (!bytes) return hipSuccess;
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess) *p = nullptr;
+        return e;
+    }
+    void release(Lifetime lt) {
+        for (const Slot &s : owned[lt]) {
+            if (*s.p) { hipFree(*s.p); *s.p = nullptr; }
+            if (s.len) *s.len = 0;
+        }
+        owned[lt].clear();
+    }
+};
+
+// A per-call device buffer: every way out of the scope frees it.
+template <class T> struct DevTemp {
+    T *p = nullptr;
+    DevTemp() = default;
+    DevTemp(const DevTemp &) = delete;
+    DevTemp &operator=(const DevTemp &) = delete;
+    ~DevTemp() { if (p) hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, n * sizeof(T)); }
+    operator T *() const { return p; }
+};

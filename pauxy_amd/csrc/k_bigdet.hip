@@ -794,10 +794,10 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Greens
     const int nmax = h->na > h->nb ? h->na : h->nb;
     const int nb2 = 2 * h->nw;
     const size_t wsn = (size_t)nb2 * nmax * nmax;
-    if (!h->big_ws) AFQ_HIP(h, hipMalloc(&h->big_ws, sizeof(cplx) * wsn));
+    AFQ_TRY(dev_ensure(h, LT_WALKERS, &h->big_ws, wsn));
     if (!h->detm) {
-        AFQ_HIP(h, hipMalloc(&h->detm, sizeof(cplx) * nb2));
-        AFQ_HIP(h, hipMalloc(&h->dete, sizeof(int) * nb2));
+        AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->detm, nb2));
+        AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->dete, nb2));
     }
     auto overlap = [&](auto p) -> int {
         p.batch = nb2; p.rows = nmax; p.cols = nmax; p.kdim = h->M;
@@ -820,7 +820,7 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Greens
         if (blocked) {
             static size_t lds_set[AFQ_MAX_DEVICES] = {0};
             AFQ_HIP(h, afq_raise_lds((const void *)gj_mfma_kernel, GjMfmaLds::BYTES, lds_set));
-            if (!h->gj_flag) AFQ_HIP(h, hipMalloc(&h->gj_flag, sizeof(int) * nb2));
+            AFQ_TRY(dev_ensure(h, LT_WALKERS, &h->gj_flag, nb2));
             AFQ_LAUNCH(h, gj_mfma_kernel, dim3(nb2), dim3(512), GjMfmaLds::BYTES, h->stream, a, h->gj_flag);
             AFQ_POST(h);
             a.only = h->gj_flag;                                      // (work-groups of unflagged matrices return at once)
@@ -859,7 +859,7 @@ int k_greens_big(afq_handle *h, cplx *ghalf, cplx *det, cplx *oinv, const Greens
             // from the real-trial product below, per 16 columns of W: the buffer holds the larger count, gdiag_parts is what
             // the last writer used
             const int parts16 = (nmax + 15) / 16;
-            if (!h->gdiag) AFQ_HIP(h, hipMalloc(&h->gdiag, sizeof(cplx) * (size_t)nb2 * parts16 * h->M));
+            AFQ_TRY(dev_ensure(h, LT_WALKERS, &h->gdiag, (size_t)nb2 * parts16 * h->M));
             if (req.may_skip_store && h->psi_real) {
                 // only diag G is wanted and the trial is real: W = conj(psi) O^-1 (real by complex), rowdot with phi
                 GdiagProbT p;
@@ -1225,11 +1225,11 @@ int k_reortho_big(afq_handle *h) {
     const int nmax = h->na > h->nb ? h->na : h->nb;
     const int nb2 = 2 * h->nw;
     const size_t wsn = (size_t)nb2 * nmax * nmax;
-    if (!h->big_ws) AFQ_HIP(h, hipMalloc(&h->big_ws, sizeof(cplx) * wsn));
-    if (!h->big_ws2) AFQ_HIP(h, hipMalloc(&h->big_ws2, sizeof(cplx) * wsn));
+    AFQ_TRY(dev_ensure(h, LT_WALKERS, &h->big_ws, wsn));
+    AFQ_TRY(dev_ensure(h, LT_WALKERS, &h->big_ws2, wsn));
     if (!h->qr_logd) {
-        AFQ_HIP(h, hipMalloc(&h->qr_logd, sizeof(double) * 2 * nb2));
-        AFQ_HIP(h, hipMalloc(&h->qr_fail, sizeof(int) * h->nw));
+        AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->qr_logd, 2 * nb2));
+        AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->qr_fail, h->nw));
     }
     AFQ_HIP(h, hipMemsetAsync(h->qr_fail, 0, sizeof(int) * h->nw, h->stream));
     for (int pass = 0; pass < 2; ++pass) {

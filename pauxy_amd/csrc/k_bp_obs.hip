@@ -194,15 +194,7 @@ struct Rdm2Prob {
 
 // workspace of the handle, grown on demand
 cplx *bo_ws(afq_handle *h, size_t n, int *rc) {
-    if (n > h->bpo_ws_len) {
-        if (h->bpo_ws) { hipStreamSynchronize(h->stream); hipFree(h->bpo_ws); h->bpo_ws = nullptr; h->bpo_ws_len = 0; }
-        if (hipMalloc((void **)&h->bpo_ws, n * sizeof(cplx)) != hipSuccess) {
-            h->err = "back-propagated observables: hipMalloc of " + std::to_string(n * sizeof(cplx)) + " bytes failed";
-            *rc = AFQ_ENOMEM;
-            return nullptr;
-        }
-        h->bpo_ws_len = n;
-    }
+    *rc = dev_grow(h, LT_WALKERS, &h->bpo_ws, &h->bpo_ws_len, n, "back-propagated observables");
     return h->bpo_ws;
 }
 
@@ -405,7 +397,7 @@ int bo_two_rdm(afq_handle *h, const cplx *wt, cplx *out) {
 
 int k_bp_observables(afq_handle *h, int restore, cplx *two_out, cplx *fock_out) {
     int rc = AFQ_OK;
-    if (!h->bpo_wt) AFQ_HIP(h, hipMalloc((void **)&h->bpo_wt, sizeof(cplx) * (size_t)h->nw));
+    BO_CK(dev_ensure(h, LT_WALKERS, &h->bpo_wt, (size_t)h->nw));
     BO_LAUNCH(bo_weights_kernel, dim3((h->nw + 127) / 128), dim3(128), 0, h->stream, h->weight, h->bp_cos, h->bp_ph,
               restore, h->nw, h->bpo_wt);
     if (two_out) BO_CK(bo_two_rdm(h, h->bpo_wt, two_out));

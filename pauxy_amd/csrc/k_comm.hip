@@ -551,15 +551,14 @@ int host_allgather(afq_handle *h, const void *send, void *recv, int bytes) {
     }
     RcclApi *api = rccl_api();
     if (!api) AFQ_FAIL(h, AFQ_ESTATE, "RCCL is not loaded");
-    char *d = nullptr;
-    AFQ_HIP(h, hipMalloc(&d, (size_t)bytes * (c->nranks + 1)));
+    DevTemp<char> d;
+    AFQ_HIP(h, d.alloc((size_t)bytes * (c->nranks + 1)));
     hipError_t e = hipMemcpyAsync(d, send, bytes, hipMemcpyHostToDevice, h->stream);
     ncclResult_t r = ncclSuccess;
     if (e == hipSuccess) r = api->AllGather(d, d + bytes, (size_t)bytes, ncclChar, c->nccl, h->stream);
     if (e == hipSuccess && r == ncclSuccess)
         e = hipMemcpyAsync(recv, d + bytes, (size_t)bytes * c->nranks, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d);
     if (r != ncclSuccess) { h->err = std::string("ncclAllGather(bootstrap): ") + api->GetErrorString(r); return AFQ_EHIP; }
     AFQ_HIP(h, e);
     return AFQ_OK;
@@ -1216,8 +1215,8 @@ int afq_estimates_allreduce(afq_handle *h, double *buf, int nest) {
             AFQ_NCCL(h, api, api->AllReduce(h->rdm_acc, h->rdm_acc, (size_t)2 * h->M * h->M, ncclDouble, ncclSum, c->nccl, h->stream));
         return AFQ_OK;
     }
-    double *tmp = nullptr;
-    AFQ_HIP(h, hipMalloc(&tmp, sizeof(double) * 2 * (size_t)nest));
+    DevTemp<double> tmp;
+    AFQ_HIP(h, tmp.alloc(2 * (size_t)nest));
     hipError_t e = hipMemcpyAsync(tmp, buf, sizeof(double) * 2 * (size_t)nest, hipMemcpyHostToDevice, h->stream);
     ncclResult_t r = ncclSuccess;
     int rcw = AFQ_OK;
@@ -1228,7 +1227,6 @@ int afq_estimates_allreduce(afq_handle *h, double *buf, int nest) {
     if (e == hipSuccess && r == ncclSuccess && rcw == AFQ_OK)
         e = hipMemcpyAsync(buf, tmp, sizeof(double) * 2 * (size_t)nest, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(tmp);
     if (rcw) return rcw;
     if (r != ncclSuccess) { h->err = std::string("ncclAllReduce: ") + api->GetErrorString(r); return AFQ_EHIP; }
     AFQ_HIP(h, e);
@@ -1308,8 +1306,8 @@ int afq_comm_probe(afq_handle *h, int64_t *mismatch_out) {
     // ---- all-gather: rank s contributes [1000 s + i] and r = 0.5 + s
     std::vector<double> wts(nw), gathered((size_t)R * (nw + 1));
     for (int i = 0; i < nw; ++i) wts[i] = 1000.0 * c->rank + i;
-    double *wdev = nullptr;
-    AFQ_HIP(h, hipMalloc(&wdev, sizeof(double) * nw));
+    DevTemp<double> wdev;
+    AFQ_HIP(h, wdev.alloc(nw));
     AFQ_HIP(h, hipMemcpyAsync(wdev, wts.data(), sizeof(double) * nw, hipMemcpyHostToDevice, h->stream));
     ++c->seq_g;
     const double *gsrc = nullptr;
@@ -1325,8 +1323,8 @@ int afq_comm_probe(afq_handle *h, int64_t *mismatch_out) {
     }
     // ---- one slot to and from every peer
     ++c->seq_x;
-    unsigned long long *badd = nullptr;
-    AFQ_HIP(h, hipMalloc(&badd, 16));
+    DevTemp<unsigned long long> badd;
+    AFQ_HIP(h, badd.alloc(2));
     AFQ_HIP(h, hipMemsetAsync(badd, 0, 16, h->stream));
     if (c->win_collectives) {
         AFQ_LAUNCH(h, probe_wait_kernel, dim3(1), dim3(64), 0, h->stream, c->wl.flag_g(c->win), R, c->seq_g, badd);
@@ -1342,7 +1340,7 @@ int afq_comm_probe(afq_handle *h, int64_t *mismatch_out) {
         } else {
             AFQ_LAUNCH(h, probe_fill_kernel, dim3(R), dim3(256), 0, h->stream, c->sbuf, (long)c->slot, (long)c->cap, c->rank, R);
             AFQ_POST(h);
-            if ((rc = sendrecv_slots(h, api))) { hipFree(wdev); hipFree(badd); return rc; }
+            if ((rc = sendrecv_slots(h, api))) return rc;
             AFQ_LAUNCH(h, probe_check_kernel, dim3(R), dim3(256), 0, h->stream, c->rbuf, (long)c->slot, (long)c->cap, c->rank, R,
                        (const unsigned long long *)nullptr, c->seq_x, badd);
             AFQ_POST(h);
@@ -1351,7 +1349,7 @@ int afq_comm_probe(afq_handle *h, int64_t *mismatch_out) {
     // ---- all-reduce of [rank + 1, 2 (rank + 1), ...] (host-buffer variant: the device variant is the same call underneath)
     double red[8];
     for (int i = 0; i < 8; ++i) red[i] = (i + 1.0) * (c->rank + 1);
-    if ((rc = afq_estimates_allreduce(h, red, 4))) { hipFree(wdev); hipFree(badd); return rc; }
+    if ((rc = afq_estimates_allreduce(h, red, 4))) return rc;
     AFQ_HIP(h, hipMemcpy(gathered.data(), gsrc, sizeof(double) * gathered.size(), hipMemcpyDeviceToHost));
     for (int s = 0; s < R; ++s) {
         for (int i = 0; i < nw; ++i) if (gathered[(size_t)s * (nw + 1) + i] != 1000.0 * s + i) ++bad[0];
@@ -1361,7 +1359,6 @@ int afq_comm_probe(afq_handle *h, int64_t *mismatch_out) {
     unsigned long long bh[2] = {0, 0};
     AFQ_HIP(h, hipMemcpy(bh, badd, 16, hipMemcpyDeviceToHost));
     bad[1] = (int64_t)bh[0]; bad[2] += (int64_t)bh[1];
-    hipFree(wdev); hipFree(badd);
     if (mismatch_out) { mismatch_out[0] = bad[0]; mismatch_out[1] = bad[1]; mismatch_out[2] = bad[2]; }
     if (bad[0] || bad[1] || bad[2]) {
         char msg[256];

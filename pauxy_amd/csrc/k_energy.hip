@@ -488,20 +488,13 @@ int k_prepare_energy_operands(afq_handle *h, const double *rchol_host) {
                         fr[dst] = rchol_host[src];
                         if (!h->rchol_real) fi[dst] = rchol_host[src + 1];
                     }
-        AFQ_HIP(h, hipMalloc(&h->rchol_frag[s], n * sizeof(double)));
-        AFQ_HIP(h, hipMemcpy(h->rchol_frag[s], fr.data(), n * sizeof(double), hipMemcpyHostToDevice));
-        if (!h->rchol_real) {
-            AFQ_HIP(h, hipMalloc(&h->rchol_frag_im[s], n * sizeof(double)));
-            AFQ_HIP(h, hipMemcpy(h->rchol_frag_im[s], fi.data(), n * sizeof(double), hipMemcpyHostToDevice));
-        }
+        afq_handle::DetOps &o = h->dets[h->cur_det];
+        int rc = dev_upload(h, LT_TRIAL, &o.rchol_frag[s], fr.data(), n);
+        if (!rc && !h->rchol_real) rc = dev_upload(h, LT_TRIAL, &o.rchol_frag_im[s], fi.data(), n);
+        if (rc) return rc;
     }
+    select_det(h, h->cur_det, true);
     return AFQ_OK;
-}
-
-void k_free_atil(void *(&atil)[2]) {
-    if (atil[0]) hipFree(atil[0]);
-    if (atil[1] && atil[1] != atil[0]) hipFree(atil[1]);
-    atil[0] = atil[1] = nullptr;
 }
 
 // bytes of the quadratic-form operands of ONE determinant
@@ -529,18 +522,17 @@ int k_exchange_uses_quadratic(afq_handle *h) {
 static int ensure_atil(afq_handle *h) {
     if (h->atil[0]) return AFQ_OK;
     const int M = h->M;
+    afq_handle::DetOps &o = h->dets[h->cur_det];      // the owner: a shared atil[1] is a view of atil[0], not registered
     for (int s = 0; s < 2; ++s) {
         const int ns = s == 0 ? h->na : h->nb;
         if (ns == 0) continue;
-        if (s == 1 && h->rchol_same) { h->atil[1] = h->atil[0]; break; }
+        if (s == 1 && h->rchol_same) { h->atil[1] = o.atil[1] = o.atil[0]; break; }
         const long NM = (long)ns * M, ldq = (NM + 1) & ~1L;
         const size_t bytes = (size_t)NM * ldq * (h->rchol_real ? sizeof(double) : sizeof(cplx));
-        if (hipMalloc(&h->atil[s], bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            h->atil[s] = nullptr;
-            k_free_atil(h->atil);                 // the other spin's operand, if it was made
-            AFQ_FAIL(h, AFQ_ENOMEM, "quadratic-form exchange operand does not fit");
-        }
+        const int rc = dev_alloc(h, LT_TRIAL, (char **)&o.atil[s], bytes);
+        if (rc) dev_alloc(h, LT_TRIAL, (char **)&o.atil[0], 0);      // the other spin's operand, if it was made
+        select_det(h, h->cur_det, true);
+        if (rc) AFQ_FAIL(h, AFQ_ENOMEM, "quadratic-form exchange operand does not fit");
         AFQ_HIP(h, hipMemsetAsync(h->atil[s], 0, bytes, h->stream));
         const dim3 grid((unsigned)((NM + 63) / 64), (unsigned)((NM + 63) / 64));
         const long row0 = s == 0 ? 0 : (long)h->na * M;
@@ -643,11 +635,7 @@ static int launch_exx_quadratic(afq_handle *h, int *S_out, bool *two_pass) {
     p.kdim = kmax;
     p.ncb = (int)((nmax + 15) / 16);
     const size_t per_pass = (size_t)NB * h->nw * p.ncb, need = per_pass * (closed_try ? 2 : 1);
-    if (h->exq_y_len < need) {
-        if (h->exq_y) hipFree(h->exq_y);
-        AFQ_HIP(h, hipMalloc(&h->exq_y, sizeof(cplx) * need));
-        h->exq_y_len = need;
-    }
+    if (int rc = dev_grow(h, LT_WALKERS, &h->exq_y, &h->exq_y_len, need, "quadratic-form partial sums")) return rc;
     p.E = h->exq_y + per_pass * pass;
     if (pass == 1 || merged) { p.skip_flag = h->closed_bad; p.skip_epoch = h->closed_epoch; p.skip_from = merged ? NB : 0; }
     // short contractions (several slices: C3 sizes) run better on eight waves with a 1 x 2 tile block each (146 vs 165 us),
@@ -714,12 +702,7 @@ int k_energy_generic(afq_handle *h) {
         AFQ_POST(h);
         return AFQ_OK;
     }
-    const size_t gbytes = sizeof(double) * (size_t)h->nt * 2 * nwt * nks * 64;
-    if (!h->gfrag || h->gfrag_bytes < gbytes) {
-        if (h->gfrag) hipFree(h->gfrag);
-        AFQ_HIP(h, hipMalloc(&h->gfrag, gbytes));
-        h->gfrag_bytes = gbytes;
-    }
+    if ((rc = dev_grow(h, LT_WALKERS, &h->gfrag, &h->gfrag_len, (size_t)h->nt * 2 * nwt * nks * 64, "Ghalf fragments"))) return rc;
     {
         const long nf = (long)h->nt * nwt * nks;
         AFQ_LAUNCH(h, gfrag_kernel, dim3((unsigned)((nf + 3) / 4)), dim3(256), 0, h->stream, h->ghalf,
@@ -727,11 +710,7 @@ int k_energy_generic(afq_handle *h) {
         AFQ_POST(h);
     }
     const long ntask = 2L * nxt * nwt * EXX_CHUNKS;
-    if (h->exx_part_len < ntask * 16) {
-        if (h->exx_part) hipFree(h->exx_part);
-        AFQ_HIP(h, hipMalloc(&h->exx_part, sizeof(cplx) * ntask * 16));
-        h->exx_part_len = ntask * 16;
-    }
+    if ((rc = dev_grow(h, LT_WALKERS, &h->exx_part, &h->exx_part_len, (size_t)ntask * 16, "exchange partial sums"))) return rc;
     ExxArgs a;
     a.M = M; a.K = K; a.nw = h->nw; a.nt = h->nt; a.nks = nks; a.nxt = nxt; a.nwt = nwt;
     a.ns[0] = h->na; a.ns[1] = h->nb; a.goff[0] = 0; a.goff[1] = h->na;

@@ -171,15 +171,6 @@ __global__ __launch_bounds__(256) void fullg_finish_kernel(const cplx *G, const 
     }
 }
 
-namespace {
-// scratch device buffer released on every exit path
-template <class T> struct Scratch {
-    T *p = nullptr;
-    ~Scratch() { if (p) hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, n * sizeof(T)); }
-};
-}  // namespace
-
 // G_dev [ng, 2, M, M] -> E_dev [ng, 3]
 template <class LT>
 static int energy_full_g(afq_handle *h, const LT *Lf, const cplx *G_dev, int ng, cplx *E_dev) {
@@ -188,7 +179,7 @@ static int energy_full_g(afq_handle *h, const LT *Lf, const cplx *G_dev, int ng,
     // chunk of Cholesky vectors: T workspace <= ~1.5 GB
     const size_t per_n = (size_t)ng2 * M * M * sizeof(cplx);
     int nc = (int)std::max<size_t>(1, std::min<size_t>((size_t)K, ((size_t)3 << 29) / per_n));
-    Scratch<cplx> sT, spart, sX, sexx;
+    DevTemp<cplx> sT, spart, sX, sexx;
     AFQ_HIP(h, sT.alloc(per_n / sizeof(cplx) * nc));
     AFQ_HIP(h, spart.alloc((size_t)ng2 * nc));
     AFQ_HIP(h, sX.alloc((size_t)ng2 * K));
@@ -229,7 +220,7 @@ int k_energy_full_g(afq_handle *h, const cplx *G_dev, int ng, cplx *E_dev) {
     const long n = (long)K * M * Mp;
     if (h->hs_cplx) {
         if (!h->L_full_c) {
-            AFQ_HIP(h, hipMalloc(&h->L_full_c, sizeof(cplx) * (size_t)n));
+            if (int rc = dev_alloc(h, LT_SYSTEM, &h->L_full_c, (size_t)n)) return rc;
             AFQ_LAUNCH(h, fullg_expand_cplx_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
                        h->hs_pot, h->ld_hs, h->hs_pot_im, h->ld_hs_im, h->hs_cplx == AFQ_HS_HERMITIAN ? 1 : 0, M, Mp,
                        K, h->L_full_c);
@@ -246,7 +237,7 @@ int k_fullg_expand(afq_handle *h) {
     const int M = h->M, K = h->K, Mp = (M + 1) & ~1;
     const long n = (long)K * M * Mp;
     if (!h->L_full) {
-        AFQ_HIP(h, hipMalloc(&h->L_full, sizeof(double) * (size_t)n));
+        if (int rc = dev_alloc(h, LT_SYSTEM, &h->L_full, (size_t)n)) return rc;
         AFQ_LAUNCH(h, fullg_expand_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->hs_pot,
                            h->ld_hs, h->hs_sym ? 1 : 0, M, Mp, K, h->L_full);
         AFQ_POST(h);

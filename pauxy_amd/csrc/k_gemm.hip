@@ -287,7 +287,7 @@ static int force_bias_generic_impl(afq_handle *h) {
         fill_force_bias(p, h);
         if (k_fb_use_sum(h)) {
             const long half = (long)h->na * h->M, n = half * h->nw;
-            if (!h->ghalf_sum) { AFQ_HIP(h, hipMalloc(&h->ghalf_sum, sizeof(cplx) * (size_t)n)); h->gf.gsum.clear(); }
+            if (!h->ghalf_sum) { AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->ghalf_sum, (size_t)n)); h->gf.gsum.clear(); }
             if (!h->gf.gsum.current(h->gf)) {               // not written by the Green's function kernel itself
                 AFQ_LAUNCH(h, ghalf_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->ghalf,
                            h->ghalf_sum, half, n);
@@ -454,18 +454,18 @@ int k_force_bias_msd_gbar(afq_handle *h) {
     const long P = (long)M * (M + 1) / 2, per = (long)h->nt * M;
     h->dets[0].vbias_stamp.clear();                // the averaged partials go where determinant 0 keeps its own
     if (!h->hs_pk) {
-        AFQ_HIP(h, hipMalloc(&h->hs_pk, sizeof(double) * (size_t)P * h->ld_rc));
+        AFQ_TRY(dev_alloc(h, LT_SYSTEM, &h->hs_pk, (size_t)P * h->ld_rc));
         AFQ_HIP(h, hipMemsetAsync(h->hs_pk, 0, sizeof(double) * (size_t)P * h->ld_rc, h->stream));
         AFQ_LAUNCH(h, transpose_f64_kernel, dim3((unsigned)((P + 31) / 32), (unsigned)((h->K + 31) / 32)), dim3(32, 8), 0,
                    h->stream, h->hs_pot, h->hs_pk, h->K, P, h->ld_hs, h->ld_rc);
         AFQ_POST(h);
     }
     if (!h->msd_gs) {
-        AFQ_HIP(h, hipMalloc(&h->msd_gs, sizeof(cplx) * (size_t)nw * KK * M));
+        AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->msd_gs, (size_t)nw * KK * M));
         AFQ_HIP(h, hipMemsetAsync(h->msd_gs, 0, sizeof(cplx) * (size_t)nw * KK * M, h->stream));             // (the pad rows)
     }
     if (!h->msd_S) {
-        AFQ_HIP(h, hipMalloc(&h->msd_S, sizeof(cplx) * (size_t)nw * h->ld_hs));
+        AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->msd_S, (size_t)nw * h->ld_hs));
         AFQ_HIP(h, hipMemsetAsync(h->msd_S, 0, sizeof(cplx) * (size_t)nw * h->ld_hs, h->stream));   // (the pad column)
     }
     AFQ_LAUNCH(h, msd_scale_ghalf_kernel, dim3((unsigned)((per + 255) / 256), nw, h->ndet), dim3(256), 0, h->stream,
@@ -490,14 +490,14 @@ int k_force_bias_msd_gbar(afq_handle *h) {
     const long PI = (long)M * (M - 1) / 2;
     if (herm && PI > 0) {
         if (!h->hs_pk_im) {
-            AFQ_HIP(h, hipMalloc(&h->hs_pk_im, sizeof(double) * (size_t)PI * h->ld_rc));
+            AFQ_TRY(dev_alloc(h, LT_SYSTEM, &h->hs_pk_im, (size_t)PI * h->ld_rc));
             AFQ_HIP(h, hipMemsetAsync(h->hs_pk_im, 0, sizeof(double) * (size_t)PI * h->ld_rc, h->stream));
             AFQ_LAUNCH(h, transpose_f64_kernel, dim3((unsigned)((PI + 31) / 32), (unsigned)((h->K + 31) / 32)), dim3(32, 8), 0,
                        h->stream, h->hs_pot_im, h->hs_pk_im, h->K, PI, h->ld_hs_im, h->ld_rc);
             AFQ_POST(h);
         }
         if (!h->msd_D) {
-            AFQ_HIP(h, hipMalloc(&h->msd_D, sizeof(cplx) * (size_t)nw * h->ld_hs_im));
+            AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->msd_D, (size_t)nw * h->ld_hs_im));
             AFQ_HIP(h, hipMemsetAsync(h->msd_D, 0, sizeof(cplx) * (size_t)nw * h->ld_hs_im, h->stream));
         }
         GbarProbT<true> p;

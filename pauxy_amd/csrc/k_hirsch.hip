@@ -277,7 +277,7 @@ __global__ void hirsch_direct_weight_kernel(double *weight, cplx *ot, const cplx
 static int k_hirsch_two_body_direct(afq_handle *h) {
     const int nmax = h->na > h->nb ? h->na : h->nb;
     if (h->nbp > 0) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "the direct Hirsch update records no field history (hubbard.py:222-275)");
-    if (!h->hs_fbfac) AFQ_HIP(h, hipMalloc(&h->hs_fbfac, sizeof(double) * h->nw));
+    AFQ_TRY(dev_ensure(h, LT_WALKERS, &h->hs_fbfac, h->nw));
     {
         const long n = (long)h->nw * h->M;
         AFQ_LAUNCH(h, hirsch_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->hs_fields, n);

@@ -813,7 +813,7 @@ static int launch_greens(afq_handle *h, cplx *ghalf, cplx *det, int only_alive, 
         // the spin sum the force bias contracts (every walker written: not on the only_alive path)
         const bool want_sum = ghalf && ghalf == h->ghalf && !only_alive && k_fb_use_sum(h) && h->psi_stride == 0;
         if (want_sum) {
-            if (!h->ghalf_sum) AFQ_HIP(h, hipMalloc(&h->ghalf_sum, sizeof(cplx) * (size_t)h->na * h->M * h->nw));
+            AFQ_TRY(dev_ensure(h, LT_WALKERS, &h->ghalf_sum, (size_t)h->na * h->M * h->nw));
             a.gsum = h->ghalf_sum;
             if (req.may_skip_store && (wgj || tiny) && !oinv) { a.skip_spin = 1; if (res) res->store_skipped = true; }
         }
@@ -840,7 +840,7 @@ static int launch_greens(afq_handle *h, cplx *ghalf, cplx *det, int only_alive, 
     a.o_in_lds = need <= 64 * 1024;
     a.only_alive = only_alive; a.alive = h->alive;
     if (!a.o_in_lds && !h->lu_ws)
-        AFQ_HIP(h, hipMalloc(&h->lu_ws, sizeof(cplx) * (size_t)h->nw * nmax * nmax));
+        AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->lu_ws, (size_t)h->nw * nmax * nmax));
     a.ws = h->lu_ws;
     AFQ_LAUNCH(h, greens_kernel, dim3(h->nw), dim3(NTHR), a.o_in_lds ? need : 0, h->stream, a);
     AFQ_POST(h);
@@ -1682,7 +1682,7 @@ static bool reortho_fused_supported(afq_handle *h, size_t *lds_out) {
 }
 
 static int k_reortho_fused(afq_handle *h, size_t lds, cplx *keep) {
-    if (!h->qr_fail) AFQ_HIP(h, hipMalloc(&h->qr_fail, sizeof(int) * h->nw));
+    AFQ_TRY(dev_ensure(h, LT_WALKERS, &h->qr_fail, h->nw));
     RfArgs a;
     a.M = h->M; a.na = h->na; a.nb = h->nb; a.nt = h->nt; a.nw = h->nw;
     a.fp = (h->flags & AFQ_PROP_FREE_PROJECTION) ? 1 : 0;
@@ -2028,12 +2028,7 @@ __global__ __launch_bounds__(256) void closed_copy_beta_kernel(cplx *phi, int M,
 }
 
 int k_closed_flags(afq_handle *h) {
-    if (!h->closed_w || h->closed_w_n < h->nw) {
-        if (h->closed_w) hipFree(h->closed_w);
-        h->closed_w = nullptr;
-        AFQ_HIP(h, hipMalloc(&h->closed_w, sizeof(int) * (size_t)h->nw));
-        h->closed_w_n = h->nw;
-    }
+    AFQ_TRY(dev_grow(h, LT_WALKERS, &h->closed_w, &h->closed_w_n, (size_t)h->nw, "closed-shell flags"));
     AFQ_LAUNCH(h, closed_flags_kernel, dim3(h->nw), dim3(256), 0, h->stream, h->phi, h->M, h->na, h->nt, h->alive, h->closed_w, h->counters);
     AFQ_POST(h);
     return AFQ_OK;

@@ -197,17 +197,6 @@ __global__ __launch_bounds__(256) void hubbard_energy_full_g_kernel(const cplx *
     }
 }
 
-int sf_grow(afq_handle *h, cplx **p, size_t *have, size_t n) {
-    if (n <= *have) return AFQ_OK;
-    if (*p) { hipStreamSynchronize(h->stream); hipFree(*p); *p = nullptr; *have = 0; }
-    if (hipMalloc((void **)p, n * sizeof(cplx)) != hipSuccess) {
-        h->err = "UEG pair sums: hipMalloc of " + std::to_string(n * sizeof(cplx)) + " bytes failed";
-        return AFQ_ENOMEM;
-    }
-    *have = n;
-    return AFQ_OK;
-}
-
 }  // namespace
 
 int k_ueg_pair_mode(afq_handle *h) {
@@ -220,7 +209,7 @@ int k_ueg_pair_mode(afq_handle *h) {
 int k_ueg_pair_sums(afq_handle *h, const cplx *G, int n, cplx *E, cplx *two) {
     if (!h->sf_kp) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "UEG pair sums: the packed index lists need M < 65536");
     const int M = h->M, nq = h->nq, mode = k_ueg_pair_mode(h);
-    int rc = sf_grow(h, &h->sf_ws, &h->sf_ws_len, (size_t)n * 2 * nq * 3);
+    int rc = dev_grow(h, LT_SYSTEM, &h->sf_ws, &h->sf_ws_len, (size_t)n * 2 * nq * 3, "UEG pair sums");
     if (rc) return rc;
     const int P = mode == 2 ? M : (M | 1);
     const size_t lds = mode == 0 ? sizeof(cplx) * M * P : mode == 1 ? sizeof(cplx) * h->ueg_nrows * P : 0;
@@ -248,7 +237,7 @@ int k_ueg_pair_sums(afq_handle *h, const cplx *G, int n, cplx *E, cplx *two) {
 
 int k_ueg_sf_two(afq_handle *h, int n, cplx **two, cplx **E) {
     const size_t nt = (size_t)n * 4 * h->nq;
-    int rc = sf_grow(h, &h->sf_two, &h->sf_two_len, nt + (size_t)3 * n);
+    int rc = dev_grow(h, LT_SYSTEM, &h->sf_two, &h->sf_two_len, nt + (size_t)3 * n, "UEG pair sums");
     *two = h->sf_two;
     *E = h->sf_two ? h->sf_two + nt : nullptr;
     return rc;
