@@ -208,7 +208,11 @@ def update_weight_hybrid(w, ovlp, ovlp_new, cfb, cmf, eshift, dt):
     ovlp_ratio = ovlp_new / ovlp
     ehyb = -(cmath.log(ovlp_ratio) + cfb + cmf) / dt
     ehyb, trig = apply_bound_hybrid(ehyb, eshift, ebound)
-    imp = cmath.exp(-dt * (0.5 * (ehyb + w['hybrid_energy']) - eshift))
+    try:
+        imp = cmath.exp(-dt * (0.5 * (ehyb + w['hybrid_energy']) - eshift))
+    except OverflowError:
+        # cmath raises where the C library's exp returns inf: the infinite magnitude is what :275 tests for
+        imp = complex(numpy.inf, 0.0)
     (magn, phase) = cmath.polar(imp)
     w['hybrid_energy'] = ehyb
     if not math.isinf(magn):
