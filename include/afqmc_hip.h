@@ -349,6 +349,16 @@ int afq_local_energy(afq_handle *h, double *E_out);
 int afq_set_exchange_algorithm(afq_handle *h, int mode);
 int afq_exchange_algorithm(afq_handle *h, int *mode_out);
 
+/* A closed-shell walker (spin blocks bitwise equal, found by the fused propagator on the walker itself at every launch)
+ * has two forms of its propagation with the same result to rounding:
+ *   1  streamed deal: the Taylor products of the alpha half, V streamed through the LDS operand ring for every product
+ *   2  resident body: V loaded once per walker and step into registers as MFMA A fragments, no ring in the products;
+ *      exists for one real one-body matrix for both spins, na == nb in 17 .. 32, 96 < M <= 104, exp_order > 0
+ * mode 0 (default) picks 2 where it exists; mode 2 on any other shape runs 1.  The getter reports the form closed
+ * walkers take with the handle's present shape and setting.                                                        */
+int afq_set_propagator_closed_form(afq_handle *h, int mode);
+int afq_propagator_closed_form(afq_handle *h, int *mode_out);
+
 /* Force bias of a multi-determinant trial (propagation/generic.py:154-157, walkers/multi_det.py:283-290) has two
  * device algorithms with the same result:
  *   1  one half-rotated contraction per determinant, rchol_d^T vec(Ghalf_d), averaged with the weights

@@ -131,6 +131,8 @@ SIGNATURES = {
     "afq_estimates_allreduce_local": [POINTER(_h), c_int],
     "afq_set_exchange_algorithm": [_h, c_int],
     "afq_exchange_algorithm": [_h, POINTER(c_int)],
+    "afq_set_propagator_closed_form": [_h, c_int],
+    "afq_propagator_closed_form": [_h, POINTER(c_int)],
     "afq_set_msd_force_bias": [_h, c_int],
     "afq_msd_force_bias": [_h, POINTER(c_int)],
     "afq_kernel_trace": [_h, c_int],

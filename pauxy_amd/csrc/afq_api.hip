@@ -1089,6 +1089,18 @@ int afq_set_exchange_algorithm(afq_handle *h, int mode) {
     return AFQ_OK;
 }
 
+int afq_set_propagator_closed_form(afq_handle *h, int mode) {
+    if (!h || mode < 0 || mode > 2) return AFQ_EINVAL;
+    h->prop_closed_mode = mode;
+    return AFQ_OK;
+}
+
+int afq_propagator_closed_form(afq_handle *h, int *mode) {
+    if (!h || !mode) return AFQ_EINVAL;
+    *mode = k_prop_closed_resident(h) ? 2 : 1;
+    return AFQ_OK;
+}
+
 int afq_set_msd_force_bias(afq_handle *h, int mode) {
     if (!h || mode < 0 || mode > 2) return AFQ_EINVAL;
     h->msd_fb_mode = mode;

@@ -76,6 +76,7 @@ struct afq_handle {
     bool atil_unavailable = false;  // automatic mode: Atil did not fit when it was to be built -> T-intermediate kernel
     bool rchol_same = false;        // alpha and beta blocks of rchol are bitwise equal
     int exx_mode = 0;               // afq_set_exchange_algorithm: 0 auto, 1 T-intermediate (exx_kernel), 2 quadratic form
+    int prop_closed_mode = 0;       // afq_set_propagator_closed_form: 0 auto, 1 streamed deal, 2 V resident in registers (where eligible)
     cplx *exq_y = nullptr;          // [2 * slices, nw, ceil(N M / 16)] per-tile partial sums of the quadratic form
     size_t exq_y_len = 0;
     cplx *H1 = nullptr;             // [2, M, M]
@@ -495,6 +496,7 @@ int k_apply_exponential(afq_handle *h, const cplx *vhs);    // phi <- sum_n vhs^
 int k_full_G(afq_handle *h);                                // G = conj(psi) ghalf
 // k_fused.hip
 int k_prop_fused_supported(afq_handle *h);
+int k_prop_closed_resident(afq_handle *h);
 int k_prop_fused(afq_handle *h);                           // phi <- B exp(V) B phi for live walkers, in place
 // k_hirsch.hip
 int k_hirsch_alive(afq_handle *h, int mode);

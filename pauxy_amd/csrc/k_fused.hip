@@ -16,6 +16,8 @@
 //   * shapes whose tile deal has no holes (template FULL) run a half-chunk pipeline in which every non-MFMA
 //     instruction -- ring refill, fragment reads, address arithmetic -- sits between two MFMA groups of the
 //     same wave; the other shapes run a generic loop with per-tile validity tests
+//   * a closed-shell walker of the headline's shape class leaves this body right behind the closedness check for the one of
+//     k_fused_closed.h: V loaded once into registers, no ring in the Taylor products
 // One raw s_barrier per k-chunk; two more per product to hand the result back into T.
 // Replaces 2 x 2 one-body launches + order Taylor launches + 3 copy kernels + the
 // phi ping-pong buffers of the unfused path; dead walkers (qmc/afqmc.py:232) are skipped
@@ -64,6 +66,7 @@ struct PropFusedArgs {
     const int *alive;
     const void *zero16;
     unsigned long long *n_closed;   // afq_counters [3]: walkers that took the closed-shell deal
+    int resident;               // a walker found closed takes the body with V resident in registers (k_fused_closed.h)
 };
 
 __device__ inline d2_t lds_read_c(unsigned addr) { return lds_read_b128(addr); }
@@ -116,6 +119,8 @@ __device__ inline void lds_barrier() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
+
+#include "k_fused_closed.h"
 
 // NARROW: at most one column tile per spin (na, nb <= 16); a separate instantiation so that each carries only the
 // Taylor tile deals it uses (register allocation and code size of one variant do not tax the other)
@@ -213,6 +218,15 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
         }
         closed = __builtin_amdgcn_readfirstlane(__syncthreads_and(same ? 1 : 0)) != 0;
         if (closed && tid == 0) atomicAdd(a.n_closed, 1ULL);
+    }
+    // The resident body (host-checked shape class: a.resident) takes the closed walker from here.  The two ring chunks
+    // issued above have landed (the barrier of the check waits for them) in LDS the body does not use.
+    if constexpr (!NARROW && FULL == 7 && PF_NW == 8) {
+        if (closed && a.resident) {
+            if (M <= 100) prop_closed_resident<25>(a, smem, phi, vhs);
+            else prop_closed_resident<26>(a, smem, phi, vhs);
+            return;
+        }
     }
     // Layout of T for THIS walker: the contiguous-column layout (a.contig) serves open-shell walkers; a closed-shell one takes
     // the two-slots-per-spin layout [a0 a1 b0 b1], whose alpha half is three tiles per SIMD.  (Measured, C3:
@@ -1152,6 +1166,13 @@ int k_prop_fused_supported(afq_handle *h) {
     return !h->vhs_diag && h->nv == 1 && h->M <= 104 && h->na <= 32 && h->nb <= 32 && h->nb > 0;
 }
 
+// Shape class of the closed-shell body with V resident in registers (k_fused_closed.h), and the form the handle asks for
+// (afq_set_propagator_closed_form): closed walkers of any other shape, and all of them in mode 1, take the streamed deal.
+int k_prop_closed_resident(afq_handle *h) {
+    return PF_NW == 8 && k_prop_fused_supported(h) && h->prop_closed_mode != 1 && h->bh1_same && h->bh1_real &&
+           h->na == h->nb && h->na > 16 && h->na <= 32 && h->M > 96 && h->M <= 104 && h->exp_order > 0;
+}
+
 int k_prop_fused(afq_handle *h) {
     PropFusedArgs a;
     a.M = h->M; a.na = h->na; a.nb = h->nb; a.nt = h->nt; a.order = h->exp_order;
@@ -1195,6 +1216,10 @@ int k_prop_fused(afq_handle *h) {
         const int cta = (h->na + 15) / 16;
         const double closed_pass = ksteps * (2048.0 * (a.rem4 ? nrt_ - 1 : nrt_) * cta + 512.0 * (a.rem4 ? cta : 0));
         h->prop_issued_closed = 3.0 * h->exp_order * closed_pass + 2.0 * (a.b_real ? 2.0 : 3.0) * per_pass;
+        // ... through the resident body: seven padded row tiles x the two alpha slots x ceil(M / 4) k-steps in every product
+        // (4-multiplication Taylor products, two real products in each of the two one-body passes)
+        if (k_prop_closed_resident(h))
+            h->prop_issued_closed = (4.0 * h->exp_order + 2.0 * 2.0) * ((h->M + 3) / 4) * 2048.0 * 7 * 2;
     }
     // every tile of the deal present: wide with 5-7 row tiles (waves 4-7 own the tiles from 4 on) and two column tiles
     // per spin, or narrow with six row tiles
@@ -1205,6 +1230,7 @@ int k_prop_fused(afq_handle *h) {
     // either spin, and a deal without holes: the contiguous-column deal with twins in like slots (symcols), or two slots per spin
     a.closed_try = (a.same_b && h->na == h->nb && h->exp_order > 0 && full != 0 && PF_NW == 8 &&
                     (!a.contig || a.symcols)) ? 1 : 0;
+    a.resident = (a.closed_try && full == 7 && k_prop_closed_resident(h)) ? 1 : 0;
 #define PF_LAUNCH_(NARROW_, FULL_, SLOT_)                                                                     \
     do {                                                                                                      \
         AFQ_HIP(h, afq_raise_lds((const void *)prop_fused_kernel<NARROW_, FULL_>, lds, lds_set[SLOT_]));      \

@@ -1,0 +1,172 @@
+// Closed-shell body of the fused propagator with the walker's HS potential V resident in registers
+// (included by k_fused.hip behind PropFusedArgs; entered from prop_fused_kernel<false, 7> for a walker it has found closed).
+//
+//   phi <- B . [ sum_{n<=order} V^n / n! ] . B . phi      on the alpha half; the result is stored to both spin blocks
+//
+// Shape class (host-checked, see k_prop_closed_resident): one real one-body matrix for both spins, na == nb in 17 .. 32,
+// M in 97 .. 104, order > 0.  KS = ceil(M / 4) k-steps of one v_mfma_f64_16x16x4 (25 or 26): the k loop of every product is
+// fully unrolled over KS so that each A fragment of V has a register of its own.
+//   * wave r (0 .. 6) owns row tile r and both alpha column slots.  Its A fragments of V -- lane (lr, lk) holds
+//     V[16 r + lr][4 s + lk] for k-step s, one 16-byte global load each -- are loaded ONCE per walker and step, under the
+//     opening one-body pass, and serve all `order` Taylor products: no operand ring, no chunk barrier, no DMA.
+//     Wave 7 takes part in the fill of T and in the barriers only.
+//   * T (the right-hand operand, alpha half: M x 32 complex) lives in LDS in B-fragment order [k-step][slot][64 lanes x 16 B]
+//     (lane (lr, lk) of k-step s, slot j: T[4 s + lk][16 j + lr]), 2 KB per k-step, KS * 2 KB <= 52 KB per image.  Two
+//     images: a product reads one and writes the other, so a hand-over is ONE barrier.  The accumulator of row tile r
+//     (register q, lane (lr, lk) = row 16 r + 4 q + lk) is exactly the lane image of k-step 4 r + q: the write-back is a
+//     lane-linear ds_write_b128.  Both images lie below the operand ring of the streamed body (2 * KS * 2 KB <= NCH * 8 KB).
+//   * the one-body passes stream the real parts of BH1 (8 bytes per lane and k-step, L2 resident, shared by all walkers)
+//     into registers ahead of their k loop: two real products per slot.
+//   * the Taylor products are plain 4-multiplication complex products (re = P1 - P2 at the end, im accumulated in one
+//     register set): k ascending in steps of 4, T_n = product / n, sum += T_n as in taylor().  Four MFMAs per k-step and slot
+//     where taylor()'s 3-multiplication form has three: see DESIGN section 4 for why this body pays them.
+// Rows and k >= M read a zero page: the padding of T stays zero through every product.
+#pragma once
+
+#define PCR_LDS(p) ((__attribute__((address_space(3))) unsigned char *)(p))
+
+template <int KS>
+__device__ __attribute__((always_inline)) inline void prop_closed_resident(const PropFusedArgs &a, unsigned char *smem_,
+                                                                           cplx *phi, const cplx *vhs) {
+    auto *smem = PCR_LDS(smem_);
+    typedef __attribute__((address_space(3))) d2_t lds_d2;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int M = a.M, nt = a.nt, na = a.na;
+    constexpr unsigned TB = KS * 2048;                          // one image of T
+    const bool mul = wave < 7;                                  // wave-uniform
+    // The lane's coordinates are derived afresh from the thread index wherever a stage needs them (laundered through an
+    // empty asm): addresses and indices of a later stage then hold no registers across the unrolled products.
+    auto lane_id = [&]() __attribute__((always_inline)) -> int {
+        int t = tid;
+        asm volatile("" : "+v"(t));
+        return t & 63;
+    };
+
+    // ---- phi[w], alpha half -> image 0 (B-fragment order), padding zeroed
+    for (int e = tid; e < KS * 128; e += PF_NT) {
+        const int k = 4 * (e >> 7) + ((e >> 4) & 3), col = 16 * ((e >> 6) & 1) + (e & 15);
+        const bool ok = k < M && col < na;
+        const cplx v = phi[ok ? k * nt + col : 0];
+        ((lds_d2 *)smem)[e] = ok ? (d2_t){v.x, v.y} : (d2_t){0.0, 0.0};
+    }
+    __syncthreads();
+
+    // A fragments of Re(BH1), this wave's row tile
+    auto load_b = [&](double (&bh)[KS]) __attribute__((always_inline)) {
+        const int lane = lane_id(), lk = lane >> 4, row = wave * 16 + (lane & 15);
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const int k = 4 * s + lk;
+            const double *p = (row < M && k < M) ? &a.BH1[row * M + k].x : (const double *)a.zero16;
+            bh[s] = *p;
+        }
+    };
+    // one-body product of image `src`: P1 + i P2 = Re(BH1)[row tile] . T
+    auto one_body = [&](const unsigned src, const double (&bh)[KS], d4_t (&P1)[2], d4_t (&P2)[2]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { P1[j] = (d4_t){0, 0, 0, 0}; P2[j] = (d4_t){0, 0, 0, 0}; }
+        const auto *tb = smem + src + lane_id() * 16;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const d2_t b = *(const lds_d2 *)(tb + (s * 2 + j) * 1024);
+                P1[j] = mfma16(bh[s], b[0], P1[j]);
+                P2[j] = mfma16(bh[s], b[1], P2[j]);
+            }
+        }
+    };
+    // accumulator layout -> image `dst`: register q of row tile `wave` is k-step 4 wave + q (k-steps past KS do not exist)
+    auto put = [&](const unsigned dst, const d4_t (&re)[2], const d4_t (&im)[2]) __attribute__((always_inline)) {
+        auto *tb = smem + dst + lane_id() * 16;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (4 * wave + q < KS) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) *(lds_d2 *)(tb + ((4 * wave + q) * 2 + j) * 1024) = (d2_t){re[j][q], im[j][q]};
+            }
+    };
+
+    d2_t av[KS];                                                // V, this wave's row tile: resident for the whole step
+    d4_t SR[2], SI[2];                                          // running Taylor sum
+    if (mul) {
+        // ---- V fragments: issued here, behind the operands of the opening pass, and consumed from the first Taylor product
+        // on -- the loads travel under that pass
+        double bh[KS];
+        load_b(bh);
+        const int lane = lane_id(), lk = lane >> 4, row = wave * 16 + (lane & 15);   // this lane's row and k of the A operands
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const int k = 4 * s + lk;
+            // upper-triangle storage of V: element (row, k < row) lives at (k, row)
+            const int off = (a.vhs_upper && k < row) ? k * M + row : row * M + k;
+            const d2_t *p = (row < M && k < M) ? (const d2_t *)(vhs + off) : (const d2_t *)a.zero16;
+            av[s] = *p;
+        }
+        // ---- T_0 = B phi: image 0 -> image 1, and the first term of the sum
+        one_body(0, bh, SR, SI);
+        put(TB, SR, SI);
+    }
+    lds_barrier();
+
+    // ---- Taylor products from the resident fragments: image cur -> image cur ^ TB, one barrier each
+    unsigned cur = TB;
+    for (int n = 1; n <= a.order; ++n) {
+        if (mul) {
+            double inv_n = 1.0 / n;
+            asm volatile("" : "+v"(inv_n));
+            d4_t P1[2], P2[2], P3[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) { P1[j] = (d4_t){0, 0, 0, 0}; P2[j] = (d4_t){0, 0, 0, 0}; P3[j] = (d4_t){0, 0, 0, 0}; }
+            const auto *tb = smem + cur + lane_id() * 16;
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                // (laundered at the k-step itself, so that the first product waits for the loads of V one fragment at a time)
+                asm volatile("" : "+v"(av[s]));
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    // (both halves of the imaginary part go into one accumulator, two independent MFMAs apart)
+                    const d2_t b = *(const lds_d2 *)(tb + (s * 2 + j) * 1024);
+                    P3[j] = mfma16(av[s][0], b[1], P3[j]);
+                    P1[j] = mfma16(av[s][0], b[0], P1[j]);
+                    P2[j] = mfma16(av[s][1], b[1], P2[j]);
+                    P3[j] = mfma16(av[s][1], b[0], P3[j]);
+                }
+            }
+            // T_n = product / n is the next right-hand operand; after the last term the image receives the SUM instead
+            d4_t re[2], im[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    re[j][q] = (P1[j][q] - P2[j][q]) * inv_n;
+                    im[j][q] = P3[j][q] * inv_n;
+                    SR[j][q] += re[j][q]; SI[j][q] += im[j][q];
+                }
+            if (n == a.order) put(cur ^ TB, SR, SI);
+            else put(cur ^ TB, re, im);
+        }
+        lds_barrier();
+        cur ^= TB;
+    }
+
+    // ---- closing one-body pass on the alpha half, stored to both spin blocks: beta is the stored copy of alpha
+    if (mul) {
+        d4_t P1[2], P2[2];
+        double bh[KS];
+        load_b(bh);
+        one_body(cur, bh, P1, P2);
+        const int lane = lane_id(), lr = lane & 15, lk = lane >> 4;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int orow = wave * 16 + lk + 4 * q, col = 16 * j + lr;
+                if (orow < M && col < na) {
+                    const cplx v = cmake(P1[j][q], P2[j][q]);
+                    phi[(long)orow * nt + col] = v;
+                    phi[(long)orow * nt + na + col] = v;
+                }
+            }
+    }
+}

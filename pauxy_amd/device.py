@@ -670,6 +670,16 @@ class AfqDevice(object):
         self._ck(self.lib.afq_exchange_algorithm(self.h, ctypes.byref(m)))
         return m.value
 
+    def set_propagator_closed_form(self, mode):
+        """0 automatic, 1 streamed closed-shell deal, 2 V resident in registers where eligible (see
+        afq_set_propagator_closed_form)."""
+        self._ck(self.lib.afq_set_propagator_closed_form(self.h, int(mode)))
+
+    def propagator_closed_form(self):
+        m = ctypes.c_int()
+        self._ck(self.lib.afq_propagator_closed_form(self.h, ctypes.byref(m)))
+        return m.value
+
     def set_msd_force_bias(self, mode):
         """0 automatic, 1 one contraction per determinant, 2 determinant-averaged G (see afq_set_msd_force_bias)."""
         self._ck(self.lib.afq_set_msd_force_bias(self.h, int(mode)))
