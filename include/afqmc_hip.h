@@ -169,6 +169,14 @@ int afq_local_energy_full_g(afq_handle *h, const double *G, int n, double *E_out
  * pe = U sum_i G_a[i,i] G_b[i,i]; Hubbard handles only.                                                        */
 int afq_ueg_pair_sums(afq_handle *h, const double *G, int n, double *E_out, double *two_rdm_out);
 int afq_hubbard_energy_full_g(afq_handle *h, const double *G, int n, double *E_out);
+/* Density and spin correlation functions of FULL Green's functions by Wick's theorem for one pair of determinants
+ * (k_corr.hip): G c128[n, 2, M, M] (spin 0 = up, 1 = down) -> corr c128[n, 5, M, M],
+ *   corr[2s+t][i,j] = G_s[i,i] G_t[j,j]                                   (s != t)   <n_is n_jt>
+ *   corr[2s+s][i,j] = G_s[i,i] G_s[j,j] + G_s[i,j] (d_ij - G_s[j,i])                 <n_is n_js>
+ *   corr[4][i,j]    = G_0[i,j] (d_ij - G_1[j,i])                                     <S+_i S-_j> for G[i,j] = <c+_i c_j>
+ * Slices 0-3 are the same for G and for its transpose per spin; slice 4 is transposed with G.  Nothing is assumed
+ * about G.  Any handle whose system is set (AFQ_ESTATE before that): only M is used.  Same input, same bits.       */
+int afq_correlations_full_g(afq_handle *h, const double *G, int n, double *corr_out);
 
 /* ---- back-propagated estimator --------------------------------
  * estimators/back_propagation.py:63-226, walkers/stack.py:5-127 (FieldConfig),
@@ -214,9 +222,15 @@ int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_
  *   two_rdm = 2  (UEG handles only, AFQ_EUNSUPPORTED elsewhere) the structure factor instead: afq_bp_update_ext's
  *            two_rdm_out then is c128[2, 2, nq] = sum_w wt_w two_rdm[G_bp[w]] of afq_ueg_pair_sums, walkers summed in
  *            index order (no atomics: the same bits on every run); walkers of weight zero contribute nothing.
- *            Evaluated with or without eval_energy.                                                    */
+ *            Evaluated with or without eval_energy.
+ *   two_rdm = 3  (every system, also together with ekt) the correlation functions instead: two_rdm_out then is
+ *            c128[5, M, M] = sum_w wt_w corr[G_bp[w]] of afq_correlations_full_g, O(M^2) where the two-body RDM is
+ *            O(M^4): no memory check.  Walkers are summed in index order in chunks of a fixed length, the chunks in
+ *            chunk order (no atomics: the same bits on every run and every device); walkers of weight zero contribute
+ *            nothing.  Evaluated with or without eval_energy.                                          */
 int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, const double *L, int nL);
-/* afq_bp_update plus, where the pointers are not NULL, two_rdm_out c128[M^4] = sum_w wt_w two_rdm[G_bp[w]] and
+/* afq_bp_update plus, where the pointers are not NULL, two_rdm_out c128[M^4] (c128[2, 2, nq] / c128[5, M, M] in the
+ * modes 2 / 3 of afq_bp_observables) = sum_w wt_w two_rdm[G_bp[w]] and
  * fock_out c128[2, M, M] = sum_w wt_w (F1p, F1h)[G_bp[w]] with the weights of est_out (complex with restore_weights).
  * With both NULL it is afq_bp_update, bitwise.                                                       */
 /* Cholesky vectors per chunk of the EKT: nc for the rank-N panels, ncy for the term linear in G (0 = automatic: as

@@ -33,7 +33,7 @@ void free_walkers(afq_handle *h) {
     h->est_acc_pending = false; h->fuse_est_req = false;
     h->gf.gsum.clear(); h->gf.vbias.clear(); h->gf.gdiag.clear(); h->gdiag_parts = 0;
     h->msd_fb_gbar = false;
-    h->nbp = 0; h->bpo_two = h->bpo_ekt = h->bpo_sf = 0; h->bpo_nL = 0; h->it_nmax = 0;
+    h->nbp = 0; h->bpo_two = h->bpo_ekt = h->bpo_sf = h->bpo_corr = 0; h->bpo_nL = 0; h->it_nmax = 0;
     h->rdm_on = false; h->sf_on = false;
     h->nw = 0;
 }

@@ -107,6 +107,9 @@ struct afq_handle {
     int sf_nlong = 0;
     cplx *sf_ws = nullptr, *sf_two = nullptr;      // [n, 2, nq, 3] Gkpq, Gpmq, Gprod; [n, 2, 2, nq] two_rdm; grown on demand
     size_t sf_ws_len = 0, sf_two_len = 0;
+    // correlation functions (k_corr.hip): [n, 2, M] diagonals, then [nchunk, 5, M, M] partial sums; grown on demand
+    cplx *corr_ws = nullptr;
+    size_t corr_ws_len = 0;
 
     // ---- trial
     bool have_trial = false;
@@ -187,11 +190,12 @@ struct afq_handle {
     // back-propagated two-body RDM / EKT Fock matrices (afq_bp_observables, k_bp_obs.hip)
     int bpo_two = 0, bpo_ekt = 0;   // what afq_bp_update_ext may be asked for
     int bpo_sf = 0;                 // two_rdm is the UEG structure factor [2, 2, nq] (afq_bp_observables(h, 2, ...))
+    int bpo_corr = 0;               // two_rdm is the correlation functions [5, M, M] (afq_bp_observables(h, 3, ...), k_corr.hip)
     int bpo_nL = 0;                 // EKT vectors L_x, x < nL
     cplx *bpo_h1 = nullptr;         // [M, M] h1 of the EKT
     cplx *bpo_L = nullptr;          // [nL, M, M] the caller's vectors (null: the handle's own real L_full)
     cplx *bpo_wt = nullptr;         // [nw] accumulation weights of the window
-    cplx *bpo_out = nullptr;        // [M^4 (two_rdm) + 2 M M (fock)] results of the window
+    cplx *bpo_out = nullptr;        // [M^4, 4 nq or 5 M M (two_rdm) + 2 M M (fock)] results of the window
     cplx *bpo_ws = nullptr;         // scratch, grown on demand
     size_t bpo_ws_len = 0;
     int bpo_nc = 0, bpo_ncy = 0;    // afq_bp_ekt_chunks: x per chunk of the panels / of the linear term (0: automatic)
@@ -620,3 +624,7 @@ int k_ueg_sf_two(afq_handle *h, int n, cplx **two_dev, cplx **E_dev);   // the h
 int k_ueg_sf_wsum(afq_handle *h, const cplx *two_dev, int n, const cplx *wt_c, const double *wt_r, cplx *out_c,
                   double *acc_r);                            // out_c = sum_g wt[g] two[g]; acc_r += Re of it
 int k_energy_hubbard_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *E_dev);   // estimators/hubbard.py:93-114
+// k_corr.hip: <n_is n_jt> and <S+_i S-_j> of full Green's functions G_dev [n, 2, M, M] -> out_dev [n, 5, M, M], and
+// their weighted sum over n -> out_dev [5, M, M] (Green's functions of weight zero left out), in index order
+int k_corr_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *out_dev);
+int k_corr_wsum(afq_handle *h, const cplx *G_dev, int n, const cplx *wt_c, cplx *out_dev);

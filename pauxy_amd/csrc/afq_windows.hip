@@ -180,6 +180,13 @@ int bp_backward(afq_handle *h, int nd, int nstblz, cplx *stack, cplx *ot, double
     return AFQ_OK;
 }
 
+// length of the two_rdm part of bpo_out in the mode afq_bp_observables set: the structure factor [2, 2, nq], the
+// correlation functions [5, M, M] or the two-body RDM [M]^4
+size_t bpo_two_len(const afq_handle *h) {
+    const size_t m2 = (size_t)h->M * h->M;
+    return h->bpo_sf ? (size_t)4 * h->nq : h->bpo_corr ? 5 * m2 : m2 * m2;
+}
+
 int bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
               int reset, double *est_out, double *two_rdm_out, double *fock_out) {
     if (h) h->gf.drop();
@@ -214,13 +221,16 @@ int bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weig
         if ((rc = k_ueg_pair_sums(h, h->G, h->nw, eval_energy ? h->energy : sf_E, sf_two))) return rc;
     }
     if ((rc = k_bp_accumulate(h, restore_weights, eval_energy))) return rc;
-    const size_t m2 = (size_t)h->M * h->M, m4 = h->bpo_sf ? (size_t)4 * h->nq : m2 * m2;    // length of the two_rdm output
+    const bool corr = two_rdm_out && h->bpo_corr;
+    const size_t m2 = (size_t)h->M * h->M, m4 = bpo_two_len(h);
     if (two_rdm_out || fock_out) {
         // sum_w wt_w two_rdm[G_bp[w]] and (F1p, F1h)[G_bp[w]] (k_bp_obs.hip), before the reset clears the weight factors
-        if ((rc = k_bp_observables(h, restore_weights, two_rdm_out && !sf ? h->bpo_out : nullptr,
+        if ((rc = k_bp_observables(h, restore_weights, two_rdm_out && !sf && !corr ? h->bpo_out : nullptr,
                                    fock_out ? h->bpo_out + (h->bpo_two ? m4 : 0) : nullptr))) return rc;
         // the structure factor with the same weights (bpo_wt), walkers in index order
         if (sf && (rc = k_ueg_sf_wsum(h, sf_two, h->nw, h->bpo_wt, nullptr, h->bpo_out, nullptr))) return rc;
+        // the correlation functions of every G_bp[w], summed with the same weights (k_corr.hip)
+        if (corr && (rc = k_corr_wsum(h, h->G, h->nw, h->bpo_wt, h->bpo_out))) return rc;
     }
     if ((rc = window_end(h, reset != 0))) return rc;
     if (two_rdm_out && (rc = copy_out(h, two_rdm_out, h->bpo_out, sizeof(cplx) * m4))) return rc;
@@ -330,7 +340,7 @@ int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_
 int afq_bp_update_ext(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
                       int reset, double *est_out, double *two_rdm_out, double *fock_out) {
     AFQ_API(h, "afq_bp_update_ext");
-    if (h && two_rdm_out && !h->bpo_two) AFQ_FAIL(h, AFQ_ESTATE, "two-body RDM: afq_bp_observables(h, 1 or 2, ...) first");
+    if (h && two_rdm_out && !h->bpo_two) AFQ_FAIL(h, AFQ_ESTATE, "two-body RDM: afq_bp_observables(h, 1, 2 or 3, ...) first");
     if (h && fock_out && !h->bpo_ekt) AFQ_FAIL(h, AFQ_ESTATE, "EKT Fock matrices: afq_bp_observables(h, ., 1, ...) first");
     return bp_update(h, phi_bp0, nstblz, restore_weights, eval_energy, reset, est_out, two_rdm_out, fock_out);
 }
@@ -400,15 +410,16 @@ int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, co
     if (ekt && h->kind == AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "EKT: the Hubbard model has no Cholesky vectors");
     if (two_rdm == 2 && h->kind != AFQ_SYS_UEG)
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "structure factor: UEG systems only (no momentum transfers elsewhere)");
-    if (two_rdm < 0 || two_rdm > 2) AFQ_FAIL(h, AFQ_EINVAL, "afq_bp_observables: two_rdm is 0, 1 (two-body RDM) or 2 (structure factor)");
-    const bool sf = two_rdm == 2;
+    if (two_rdm < 0 || two_rdm > 3)
+        AFQ_FAIL(h, AFQ_EINVAL, "afq_bp_observables: two_rdm is 0, 1 (two-body RDM), 2 (structure factor) or 3 (correlation functions)");
+    const bool sf = two_rdm == 2, corr = two_rdm == 3;
     if (ekt && !L && h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EINVAL, "EKT: pass the vectors L_x of this system");
     if (ekt && !L && h->hs_cplx)
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "EKT with complex Cholesky vectors: the reference's 4-fold-symmetry form pins nothing");
-    const size_t M = (size_t)h->M, m4 = sf ? (size_t)4 * h->nq : M * M * M * M;
+    const size_t M = (size_t)h->M, m4 = sf ? (size_t)4 * h->nq : corr ? 5 * M * M : M * M * M * M;
     hipSetDevice(h->device);
     dev_alloc(h, LT_WALKERS, &h->bpo_out, 0);      // a buffer of an earlier call does not count against the budget
-    if (two_rdm && !sf) {
+    if (two_rdm && !sf && !corr) {
         size_t fr = 0, tot = 0;
         AFQ_HIP(h, hipMemGetInfo(&fr, &tot));
         const double need = 16.0 * (double)m4;
@@ -418,14 +429,14 @@ int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, co
                                         std::to_string((unsigned long long)fr) + " bytes)");
     }
     dev_alloc(h, LT_WALKERS, &h->bpo_h1, 0); dev_alloc(h, LT_WALKERS, &h->bpo_L, 0);
-    h->bpo_two = h->bpo_ekt = h->bpo_sf = 0; h->bpo_nL = 0;
+    h->bpo_two = h->bpo_ekt = h->bpo_sf = h->bpo_corr = 0; h->bpo_nL = 0;
     if (ekt) {
         if ((rc = dev_upload(h, LT_WALKERS, &h->bpo_h1, h1, M * M))) return rc;
         if (L && (rc = dev_upload(h, LT_WALKERS, &h->bpo_L, L, (size_t)nL * M * M))) return rc;
         h->bpo_nL = nL;
     }
     if ((two_rdm || ekt) && (rc = dev_alloc(h, LT_WALKERS, &h->bpo_out, (two_rdm ? m4 : 0) + (ekt ? 2 * M * M : 0)))) return rc;
-    h->bpo_two = two_rdm ? 1 : 0; h->bpo_ekt = ekt ? 1 : 0; h->bpo_sf = sf ? 1 : 0;
+    h->bpo_two = two_rdm ? 1 : 0; h->bpo_ekt = ekt ? 1 : 0; h->bpo_sf = sf ? 1 : 0; h->bpo_corr = corr ? 1 : 0;
     return AFQ_OK;
 }
 
@@ -544,6 +555,13 @@ int afq_ueg_pair_sums(afq_handle *h, const double *G, int n, double *E_out, doub
     if (h->kind != AFQ_SYS_UEG) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "UEG pair sums: UEG systems only");
     return full_g_call(h, G, n, E_out, (size_t)4 * h->nq * n, two_rdm_out,
                        [&](cplx *Gd, cplx *Ed, cplx *Td) { return k_ueg_pair_sums(h, Gd, n, Ed, Td); });
+}
+
+int afq_correlations_full_g(afq_handle *h, const double *G, int n, double *corr_out) {
+    if (!h || !G || !corr_out || n < 1) return AFQ_EINVAL;
+    if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "correlation functions: the system must be set (they are sized by its M)");
+    return full_g_call(h, G, n, nullptr, (size_t)5 * h->M * h->M * n, corr_out,
+                       [&](cplx *Gd, cplx *, cplx *Td) { return k_corr_full_g(h, Gd, n, Td); });
 }
 
 int afq_hubbard_energy_full_g(afq_handle *h, const double *G, int n, double *E_out) {

@@ -199,13 +199,25 @@ class AfqDevice(object):
         self._ck(self.lib.afq_hubbard_energy_full_g(self.h, _p(G), n, _p(out)))
         return out
 
+    def correlations_full_g(self, G):
+        """corr [n, 5, M, M] of general Green's functions G[n, 2, M, M] (afq_correlations_full_g): <n_is n_jt> in the
+        slices 2s+t, <S+_i S-_j> in slice 4.  Any handle whose system is set."""
+        G = _c128(G)
+        n = G.shape[0]
+        G = _c128(G, (n, 2, self.M, self.M))
+        out = numpy.zeros((n, 5, self.M, self.M), dtype=numpy.complex128)
+        self._ck(self.lib.afq_correlations_full_g(self.h, _p(G), n, _p(out)))
+        return out
+
     def bp_observables(self, two_rdm=False, ekt=False, h1=None, L=None):
         """afq_bp_observables: what bp_update may be asked for.  EKT: h1 [M, M] and L [nL, M, M] (None: a generic
-        system's own vectors).  two_rdm='structure_factor' (UEG): bp_update's 'two_rdm' then is [2, 2, nq]."""
+        system's own vectors).  two_rdm='structure_factor' (UEG): bp_update's 'two_rdm' then is [2, 2, nq];
+        two_rdm='correlation' (any system): [5, M, M], the weighted sum of correlations_full_g over the walkers."""
+        if isinstance(two_rdm, str) and two_rdm not in ('structure_factor', 'correlation'):
+            raise ValueError("two_rdm: True, 'structure_factor' or 'correlation'")
         self._bp_sf = isinstance(two_rdm, str) and two_rdm == 'structure_factor'
-        if isinstance(two_rdm, str) and not self._bp_sf:
-            raise ValueError("two_rdm: True or 'structure_factor'")
-        two_rdm = 2 if self._bp_sf else int(bool(two_rdm))
+        self._bp_corr = isinstance(two_rdm, str) and two_rdm == 'correlation'
+        two_rdm = 2 if self._bp_sf else 3 if self._bp_corr else int(bool(two_rdm))
         M = self.M
         h1p = Lp = None
         nL = 0
@@ -230,7 +242,7 @@ class AfqDevice(object):
         """-> (energies_sum[3], denominator, G_bp_sum[2, M, M]); restore_weights in (None, 'partial', 'full').
         With two_rdm / ekt (after bp_observables) a fourth item {'two_rdm': [M]*4, 'fock_1p': [M, M], 'fock_1h':
         [M, M]} holds the weighted sums of what was asked for ('two_rdm': [2, 2, nq] after
-        bp_observables(two_rdm='structure_factor'))."""
+        bp_observables(two_rdm='structure_factor'), [5, M, M] after bp_observables(two_rdm='correlation'))."""
         mode = {None: 0, 'partial': 1, 'full': 2}.get(restore_weights, 1)
         phi0 = _c128(phi_bp0, (self.M, self.na + self.nb))
         M = self.M
@@ -241,7 +253,8 @@ class AfqDevice(object):
             return out[:3], out[3], out[4:].reshape(2, M, M)
         two = None
         if two_rdm:
-            shape = (2, 2, self.nq) if getattr(self, '_bp_sf', False) else (M, M, M, M)
+            shape = ((2, 2, self.nq) if getattr(self, '_bp_sf', False)
+                     else (5, M, M) if getattr(self, '_bp_corr', False) else (M, M, M, M))
             two = numpy.zeros(shape, dtype=numpy.complex128)
         fock = numpy.zeros((2, M, M), dtype=numpy.complex128) if ekt else None
         self._ck(self.lib.afq_bp_update_ext(self.h, _p(phi0), int(nstblz), mode, int(bool(eval_energy)),

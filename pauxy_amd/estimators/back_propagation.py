@@ -32,12 +32,20 @@ reference's flat layout (``two_rdm_shape = (2, 2, nq)``), complex and not normal
 sums of a back-propagated Green's function, the default lists (the reference's: first nup plane waves) truncated ones.
 One deliberate difference: the structure factor is evaluated whenever it is asked for, also with ``evaluate_energy:
 False``; the reference fills the array only inside its energy call and would accumulate zeros there.
+
+``two_rdm: 'correlation'`` (Generic, UEG and Hubbard systems, single-determinant trials; not in the reference's
+estimator, whose analysis/correlation.py still reads such a dataset) accumulates sum_w weight_w corr[G_bp[w]] with the
+[5, M, M] array of ``afq_correlations_full_g``: <n_is n_jt> in the slices 2s+t and <S+_i S-_j> in slice 4
+(``two_rdm_shape = (5, M, M)``), complex and not normalised like the structure factor, in the same slot of the flat
+vector, ``self.two_rdm`` and the group ``two_rdm_<n>``.  It is evaluated with or without ``evaluate_energy`` and
+together with ``evaluate_ekt``.  estimators/correlation.py turns the normalised array into charge and spin correlations.
 """
 import numpy
 
 
 class BackPropagation(object):
     structure_factor = False
+    correlation = False
 
     def __init__(self, bp, root, filename, qmc, system, trial, dtype, BT2):
         self.tau_bp = bp.get('tau_bp', 0)
@@ -66,9 +74,13 @@ class BackPropagation(object):
             # continuous Hubbard propagator
             raise NotImplementedError("restore_weights with the discrete Hubbard fields")
         if isinstance(self.calc_two_rdm, str):
-            if self.calc_two_rdm != "structure_factor":
-                raise ValueError("two_rdm: True or 'structure_factor'")
-            self.structure_factor = True            # (an instance attribute only with the option, like two_rdm)
+            if self.calc_two_rdm not in ("structure_factor", "correlation"):
+                raise ValueError("two_rdm: True, 'structure_factor' or 'correlation'")
+            # (instance attributes only with the option, like two_rdm)
+            if self.calc_two_rdm == "structure_factor":
+                self.structure_factor = True
+            else:
+                self.correlation = True
         if self.structure_factor and system.name != "UEG":
             # S(q) is a sum over momentum transfers: back_propagation.py:88-89 reads system.qvecs
             raise NotImplementedError("back-propagated two_rdm: 'structure_factor' needs a UEG system")
@@ -95,7 +107,8 @@ class BackPropagation(object):
         if self.calc_two_rdm is not None:         # back_propagation.py:86-99,100-104: the flat layout of the reference
             self.two_rdm = []
             # back_propagation.py:88-94
-            self.two_rdm_shape = (2, 2, len(system.qvecs)) if self.structure_factor else (M,) * 4
+            self.two_rdm_shape = ((2, 2, len(system.qvecs)) if self.structure_factor
+                                  else (5, M, M) if self.correlation else (M,) * 4)
             self.two_rdm_size = int(numpy.prod(self.two_rdm_shape))
             dms_size += self.two_rdm_size
         if self.eval_ekt:
@@ -222,7 +235,8 @@ class BackPropagation(object):
                 cv = system.chol_vecs
                 cv = cv.toarray() if hasattr(cv, 'toarray') else numpy.asarray(cv)
                 L = 2.0 * cv.T.reshape((system.nchol, system.nbasis, system.nbasis))
-        two = 'structure_factor' if self.structure_factor else self.calc_two_rdm is not None
+        two = ('structure_factor' if self.structure_factor else 'correlation' if self.correlation
+               else self.calc_two_rdm is not None)
         dev.bp_observables(two_rdm=two, ekt=bool(self.eval_ekt), h1=h1, L=L)
         self._obs_dev = dev
 
