@@ -410,6 +410,25 @@ int afq_set_weight_cap(afq_handle *h, double frac, double total_weight);
  * work (no host synchronisation, no AFQ_EWEIGHT check).                         */
 int afq_popcontrol_comb(afq_handle *h, double r, double target_weight,
                         int32_t *parent_ix, double *total_weight_out);
+/* walkers/handler.py:225-251,340-412 for a single rank (population_control: pair_branch): rescale as the comb does;
+ * order the walkers by |weight| (stable); pair the p-th lightest with the p-th heaviest and act on the pair while its
+ * light walker is below min_weight or its heavy one above max_weight (the first pair that is neither ends it); pair p
+ * uses u[p]: with probability a_heavy / (a_light + a_heavy) the heavy walker is cloned, else the light one, and both
+ * copies carry half the pair's weight.  The j-th clone by index overwrites the j-th kill by index.  Walkers outside a
+ * pair keep their scaled, signed weight; nothing is reset to 1 and the total weight is conserved.
+ *   u       nu >= nw / 2 uniforms on the host (AFQ_EINVAL below that); staged by the call, the caller may free them
+ *   mult    int32[nw] out (may be NULL): 0 kill, 1 keep, 2 clone
+ *   ndraws_out (may be NULL) how many uniforms were consumed: u[0 .. ndraws)
+ *   total_weight_out (may be NULL) the total weight before scaling, what afq_cap_weights(.., -1) then uses
+ * With all three outputs NULL the call only enqueues work (no host synchronisation, no AFQ_EWEIGHT check); a collapsed
+ * population (total < 1e-8) changes nothing and is reported by the next synchronising call, as for the comb.
+ * One work-group plans in LDS: at most AFQ_PAIR_BRANCH_MAX_WALKERS walkers (AFQ_EUNSUPPORTED above).  With a
+ * library-owned communicator of more than one rank attached: AFQ_EUNSUPPORTED (that communicator does the comb only;
+ * with a one-rank communicator the call is the single-rank event).                                                   */
+#define AFQ_PAIR_BRANCH_MAX_WALKERS 8192
+int afq_popcontrol_pair_branch(afq_handle *h, const double *u, int nu, double target_weight,
+                               double min_weight, double max_weight, int32_t *mult,
+                               int32_t *ndraws_out, double *total_weight_out);
 
 /* ---- library-owned communicator ----------------------------------------------------
  * walkers/handler.py:225-338 across ranks -- the Allgather of the weights (:232), rank 0's comb uniform

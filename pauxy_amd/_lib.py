@@ -62,6 +62,8 @@ SIGNATURES = {
     "afq_cap_weights": [_h, c_double, c_double],
     "afq_set_weight_cap": [_h, c_double, c_double],
     "afq_popcontrol_comb": [_h, c_double, c_double, c_void_p, POINTER(c_double)],
+    "afq_popcontrol_pair_branch": [_h, _dp, c_int, c_double, c_double, c_double, c_void_p, POINTER(c_int32),
+                                   POINTER(c_double)],
     "afq_walkers_scale_weights": [_h, c_double],
     "afq_walkers_copy": [_h, c_int, c_int],
     "afq_walker_pack_bytes": [_h, POINTER(c_int64)],

@@ -1244,6 +1244,38 @@ int afq_popcontrol_comb(afq_handle *h, double r, double target_weight, int32_t *
     return copy_out(h, parent_ix, h->parent_ix, sizeof(int) * h->nw);
 }
 
+int afq_popcontrol_pair_branch(afq_handle *h, const double *u, int nu, double target_weight, double min_weight,
+                               double max_weight, int32_t *mult, int32_t *ndraws_out, double *total_weight_out) {
+    if (h) h->scal_cache_valid = false;
+    AFQ_API(h, "afq_popcontrol_pair_branch");
+    if (!h) return AFQ_EINVAL;
+    int rc = need_ready(h, false);
+    if (rc) { h->gf.drop(); return rc; }
+    if (k_comm_size(h) > 1) {
+        h->gf.drop();
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "pair branching over the library-owned communicator: it does the comb only");
+    }
+    if (h->nw == 1) return AFQ_OK;                       // handler.py:226-227
+    if (!u || nu < h->nw / 2 || !(target_weight > 0.0)) {
+        h->gf.drop();
+        AFQ_FAIL(h, AFQ_EINVAL, "afq_popcontrol_pair_branch: nw / 2 uniforms and a positive target weight are needed");
+    }
+    if ((rc = dev_grow(h, LT_WALKERS, &h->pb_u, &h->pb_u_n, (size_t)(h->nw / 2), "pair-branch uniforms"))) { h->gf.drop(); return rc; }
+    AFQ_HIP(h, hipMemcpyAsync(h->pb_u, u, sizeof(double) * (size_t)(h->nw / 2), hipMemcpyHostToDevice, h->stream));
+    // a kept Green's function travels with the cloned walkers, as for the comb
+    const bool keep = h->gf.take() == GreensCache::FULL && h->ndet == 1;
+    if ((rc = k_pair_branch(h, h->pb_u, target_weight, min_weight, max_weight, keep))) return rc;
+    if (keep) h->gf.keep(GreensCache::FULL);
+    if (!mult && !ndraws_out && !total_weight_out) return AFQ_OK;  // asynchronous: nothing read back, no host sync
+    double sc[AFQ_NSCAL];
+    if ((rc = copy_out(h, sc, h->scal, sizeof(sc)))) return rc;
+    if (total_weight_out) *total_weight_out = sc[0];
+    if (sc[1] < 0) AFQ_FAIL(h, AFQ_EWEIGHT, "total walker weight below 1e-8");
+    if (ndraws_out) *ndraws_out = (int32_t)sc[9];
+    if (!mult) return AFQ_OK;
+    return copy_out(h, mult, h->parent_ix, sizeof(int) * h->nw);
+}
+
 int afq_walkers_scale_weights(afq_handle *h, double scale) {
     if (!h || scale == 0.0) return AFQ_EINVAL;
     int rc = need_ready(h, false);

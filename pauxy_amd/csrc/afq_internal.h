@@ -304,8 +304,11 @@ struct afq_handle {
     // [AFQ_NSCAL] device scalars: 0 total weight of the last comb, 1 local pairs (< 0: collapsed), 2 collapse flag (sticky),
     // 3 exchange overflow (sticky), 4 largest transfer between two ranks, 5 comb events, 6 communication error (sticky:
     // a peer's flag never arrived), 7 walkers this rank has sent, 8 bytes this rank has sent (window transport)
+    // 9 uniforms the last pair-branch event consumed
     double *scal = nullptr;
     void *pack_tmp = nullptr;
+    double *pb_u = nullptr;         // [pb_u_n] the uniforms of afq_popcontrol_pair_branch, staged for its plan kernel
+    size_t pb_u_n = 0;
     void *zero_page = nullptr;      // 256 zero bytes: source of out-of-range LDS-DMA loads
     // afq_estimates_fuse_next: the weight update of the next step adds every walker's estimator terms to est_acc[w][6]
     // (per walker: no cross-walker sum, no atomics); the next estimates_kernel launch, or the next fetch, folds them in
@@ -566,6 +569,9 @@ WeightArgs k_weight_args(afq_handle *h, cplx eshift);       // the weight update
 int k_reortho(afq_handle *h, cplx *keep = nullptr, bool *keep_done = nullptr);
 int k_cap_weights(afq_handle *h, double frac, double total_weight);
 int k_comb(afq_handle *h, double r, double target, bool with_greens = false);
+// single-rank pair branching: plan from the uniforms u_dev[nw / 2] (device), then the clones; weights are not reset
+int k_pair_branch(afq_handle *h, const double *u_dev, double target, double min_weight, double max_weight,
+                  bool with_greens = false);
 int k_clone_pairs(afq_handle *h, bool with_greens, bool reset_weights = false);
 int k_closed_flags(afq_handle *h);          // closed_w[w] for every walker
 int k_closed_copy_beta(afq_handle *h);      // phi[w][:, na:] = phi[w][:, :na] where closed_w[w]

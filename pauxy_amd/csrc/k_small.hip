@@ -2050,6 +2050,119 @@ int k_comb(afq_handle *h, double r, double target, bool with_greens) {
     return k_clone_pairs(h, with_greens, true);       // the weights go back to 1 in the same launch
 }
 
+// Pair-branch population control, walkers/handler.py:225-251,340-412, decided by one work-group.
+//   total, scaling   as comb_plan_kernel (the same chunked sums), scal[0] = total, collapsed population: same exit
+//   sort             a_i = |weight_i / scale| ascending and stable (argsort(kind='mergesort'), :348): a bitonic network
+//                    in LDS on the composite key (a_i, i), padded to a power of two with (+inf, index >= nw) keys --
+//                    data independent, so it terminates whatever the weights are
+//   pairs            pair p = (sorted[p], sorted[nw-1-p]) is acted on while every earlier pair was and
+//                    a_s < min_weight or a_e > max_weight (:356, :385-386); it reads u[p], its one uniform (:359), and
+//                    the walker it clones gets 0.5 * (a_s + a_e) (:362, :373).  "Every earlier pair was" is the index
+//                    of the first pair that fails the test: a minimum over the pairs (atomicMin on one LDS word, the
+//                    same value in whatever order the threads arrive), not a prefix scan of flags
+//   placement        clones and kills compacted by index, the j-th clone overwrites the j-th kill (all of :396-410's
+//                    messages carry the same tag on one rank); the killed slot gets the weight of the clone that lands
+//                    there, which clone_kernel does not copy
+// Out: parent_ix[i] = 0 kill / 1 keep / 2 clone, pairs for clone_kernel, scal[1] = pairs, scal[9] = uniforms consumed.
+// LDS: P * 12 + nw * 4 bytes for P = nw rounded up to a power of two; the clone / kill lists reuse the sort keys.
+__global__ __launch_bounds__(256) void pair_branch_plan_kernel(double *weight, double *unscaled, int nw, int P,
+                                                                const double *u, double target, double min_weight,
+                                                                double max_weight, int *parent_ix, int *pairs,
+                                                                double *scal) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    double *key = (double *)smem;             // [P] a_i, sorted
+    int *idx = (int *)(key + P);              // [P] walker of each sorted position
+    int *mult = idx + P;                      // [nw]
+    __shared__ double wtot_d[4];
+    __shared__ int wtot_i[4];
+    __shared__ int s_first;                   // first pair that is not acted on
+    const int tid = threadIdx.x;
+    const int per = (nw + 255) / 256;
+    const int i0 = tid * per < nw ? tid * per : nw, i1 = (tid + 1) * per < nw ? (tid + 1) * per : nw;
+    double loc = 0.0;
+    for (int i = i0; i < i1; ++i) loc += fabs(weight[i]);
+    double total;
+    (void)block_excl_scan256(loc, wtot_d, &total);            // sum(global_weights), handler.py:233
+    if (tid == 0) scal[0] = total;
+    if (total < 1e-8) { if (tid == 0) { scal[1] = -1.0; scal[2] = 1.0; } return; }      // handler.py:236-241
+    const double scale = total / target;
+    for (int i = i0; i < i1; ++i) {
+        unscaled[i] = weight[i];                              // handler.py:245
+        const double w = weight[i] / scale;
+        weight[i] = w;
+        key[i] = fabs(w);                                     // handler.py:341
+        idx[i] = i;
+        mult[i] = 1;
+    }
+    for (int i = nw + tid; i < P; i += 256) { key[i] = INFINITY; idx[i] = i; }
+    if (tid == 0) s_first = nw / 2;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += 256) {
+                const int lo = 2 * t - (t & (j - 1)), hi = lo + j;        // the two positions that differ in bit j
+                const double ka = key[lo], kb = key[hi];
+                const int ia = idx[lo], ib = idx[hi];
+                const bool a_after_b = ka > kb || (ka == kb && ia > ib);
+                if (a_after_b == ((lo & k) == 0)) { key[lo] = kb; key[hi] = ka; idx[lo] = ib; idx[hi] = ia; }
+            }
+            __syncthreads();
+        }
+    }
+    const int npairs = nw / 2;
+    for (int p = tid; p < npairs; p += 256) {
+        const int is = idx[p], ie = idx[nw - 1 - p];
+        // (a padding key among the first nw positions can only follow from NaN weights: never index with it)
+        if (!(key[p] < min_weight || key[nw - 1 - p] > max_weight) || is >= nw || ie >= nw) { atomicMin(&s_first, p); break; }
+    }
+    __syncthreads();
+    const int nact = s_first;
+    for (int p = tid; p < nact; p += 256) {
+        const int is = idx[p], ie = idx[nw - 1 - p];
+        const double a_s = key[p], a_e = key[nw - 1 - p];
+        const double wab = a_s + a_e;                         // handler.py:358
+        const bool big = u[p] < a_e / wab;                    // handler.py:360
+        const int clone = big ? ie : is, kill = big ? is : ie;
+        weight[clone] = 0.5 * wab;                            // handler.py:362,373
+        mult[clone] = 2; mult[kill] = 0;
+    }
+    __syncthreads();                                          // (the keys are dead from here: their LDS holds the lists)
+    int *clone_l = (int *)key, *kill_l = clone_l + nw;
+    int nc = 0, nk = 0;
+    for (int i = i0; i < i1; ++i) { nc += mult[i] == 2; nk += mult[i] == 0; }
+    int totc, totk;
+    int bc = block_excl_scan256(nc, wtot_i, &totc);
+    int bk = block_excl_scan256(nk, wtot_i, &totk);
+    for (int i = i0; i < i1; ++i) {
+        if (mult[i] == 2) clone_l[bc++] = i;
+        if (mult[i] == 0) kill_l[bk++] = i;
+        parent_ix[i] = mult[i];
+    }
+    __syncthreads();
+    const int np = totc < totk ? totc : totk;                 // (both equal nact)
+    for (int j = tid; j < np; j += 256) {
+        pairs[2 * j] = clone_l[j]; pairs[2 * j + 1] = kill_l[j];
+        weight[kill_l[j]] = weight[clone_l[j]];               // the buffer that travels holds the new weight, handler.py:399-410
+    }
+    if (tid == 0) { scal[1] = (double)np; scal[9] = (double)nact; }
+}
+
+int k_pair_branch(afq_handle *h, const double *u_dev, double target, double min_weight, double max_weight,
+                  bool with_greens) {
+    if (h->nw > AFQ_PAIR_BRANCH_MAX_WALKERS)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "pair branching on the device serves at most AFQ_PAIR_BRANCH_MAX_WALKERS (8192) walkers per handle");
+    int P = 2;
+    while (P < h->nw) P <<= 1;
+    const size_t lds = (sizeof(double) + sizeof(int)) * (size_t)P + sizeof(int) * (size_t)h->nw;
+    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
+    // (the default limit of 64 KiB covers the kernel's few static words too: 4096 walkers are already above it)
+    if (lds + 256 > 64 * 1024) AFQ_HIP(h, afq_raise_lds((const void *)pair_branch_plan_kernel, lds, lds_set));
+    AFQ_LAUNCH(h, pair_branch_plan_kernel, dim3(1), dim3(256), lds, h->stream, h->weight, h->unscaled, h->nw, P, u_dev,
+               target, min_weight, max_weight, h->parent_ix, (int *)h->pack_tmp, h->scal);
+    AFQ_POST(h);
+    return k_clone_pairs(h, with_greens, false);      // nothing is reset: the plan has written both weights
+}
+
 // --------------------------------------------------------------------------
 // estimators/mixed.py:211-225: one workgroup, deterministic tree sums.
 // estimators/mixed.py:151-175, 211-225: one workgroup, deterministic tree sums.

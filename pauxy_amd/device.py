@@ -450,6 +450,19 @@ class AfqDevice(object):
         self._ck(self.lib.afq_popcontrol_comb(self.h, float(r), float(target), _p(pix), ctypes.byref(tw)))
         return pix, tw.value
 
+    def popcontrol_pair_branch(self, u, target, min_weight, max_weight, fetch=True):
+        """Single-rank pair branching from the uniforms u (at least nw // 2) -> (mult, ndraws, total weight);
+        ``fetch=False`` only enqueues the event and returns (None, None, None)."""
+        u = numpy.ascontiguousarray(u, dtype=numpy.float64).reshape(-1)
+        args = (self.h, _p(u) if u.size else None, int(u.size), float(target), float(min_weight), float(max_weight))
+        if not fetch:        # asynchronous: the total weight stays on the device (cap_weights(frac, -1))
+            self._ck(self.lib.afq_popcontrol_pair_branch(*args, None, None, None))
+            return None, None, None
+        mult = numpy.ones(self.nw, dtype=numpy.int32)
+        nd, tw = ctypes.c_int32(0), ctypes.c_double(0.0)
+        self._ck(self.lib.afq_popcontrol_pair_branch(*args, _p(mult), ctypes.byref(nd), ctypes.byref(tw)))
+        return mult, nd.value, tw.value
+
     def scale_weights(self, scale):
         self._ck(self.lib.afq_walkers_scale_weights(self.h, float(scale)))
 

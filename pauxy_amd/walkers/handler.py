@@ -59,6 +59,63 @@ def comb_pairs(parent_ix):
     return list(zip(clone.tolist(), kill.tolist()))
 
 
+def pair_branch_plan(weights, min_weight, max_weight, draws, nw_per_rank=None):
+    """Pair branching (walkers/handler.py:340-412) as a plan over the scaled, signed weights of the whole population.
+
+    The walkers are ordered by |weight| with the stable sort of :348; pair p joins the p-th lightest with the p-th
+    heaviest walker and is acted on while its light walker is below ``min_weight`` or its heavy one above
+    ``max_weight`` -- the first pair that is neither ends the loop (:385-386).  Every pair acted on consumes one
+    uniform, in pair order (``draws``: a sequence, or a callable asked once per such pair): with probability
+    a_e / (a_s + a_e) the heavy walker is cloned over the light one, else the light over the heavy (:360-381), and
+    the clone carries half the pair's weight.  Walkers outside a pair keep their weight and its sign.
+
+    Placement is what the messages of :396-410 amount to (every message between two ranks has the same tag, so they
+    match in posting order): the k-th clone, by local index, on rank A whose partner lives on rank B overwrites the
+    k-th kill, by local index, on B whose partner lives on A.  On one rank that is zip(clone, kill) by index -- not
+    the walker's own partner.  ``nw_per_rank`` None: one rank.
+
+    Returns (new_weights, mult, pairs, ndraws): the weight of every slot afterwards (a killed slot holds the weight
+    of the clone that lands there), mult int32 (0 kill, 1 keep, 2 clone), pairs [(src_global, dst_global)] by source
+    index, and the number of uniforms consumed."""
+    w = numpy.array(weights, dtype=numpy.float64)
+    n = len(w)
+    per = n if nw_per_rank is None else int(nw_per_rank)
+    a = numpy.abs(w)
+    order = numpy.argsort(a, kind='mergesort')
+    mult = numpy.ones(n, dtype=numpy.int32)
+    partner = numpy.full(n, -1, dtype=numpy.int64)
+    take = draws if callable(draws) else iter(draws).__next__
+    s, e, ndraws = 0, n - 1, 0
+    with numpy.errstate(invalid='ignore'):
+        while s < e:
+            i_s, i_e = order[s], order[e]
+            a_s, a_e = a[i_s], a[i_e]
+            if not (a_s < min_weight or a_e > max_weight):
+                break
+            wab = a_s + a_e
+            r = take()
+            ndraws += 1
+            clone, kill = (i_e, i_s) if r < a_e / wab else (i_s, i_e)
+            w[clone] = 0.5 * wab
+            mult[clone], mult[kill] = 2, 0
+            partner[clone], partner[kill] = kill, clone
+            s += 1
+            e -= 1
+    kills = {}                                    # (rank of the kill, rank of its partner) -> kills by index
+    for k in numpy.where(mult == 0)[0]:
+        kills.setdefault((k // per, partner[k] // per), []).append(int(k))
+    taken = {}
+    pairs = []
+    for c in numpy.where(mult == 2)[0]:
+        key = (partner[c] // per, c // per)
+        j = taken.get(key, 0)
+        taken[key] = j + 1
+        k = kills[key][j]
+        pairs.append((int(c), k))
+        w[k] = w[c]
+    return w, mult, pairs, ndraws
+
+
 class WalkerView(object):
     """Proxy for walker ``i`` of a device-resident population (the attribute
     and method surface of pauxy/walkers/single_det.py:11-364 that the hot path,
@@ -212,8 +269,9 @@ class Walkers(object):
                 and numpy.asarray(trial.psi).ndim == 3):
             trial.psi = trial.psi[0]                       # walkers/handler.py:61
         self.pcont_method = walker_opts.get('population_control', 'comb')
-        if self.pcont_method != 'comb':
-            raise NotImplementedError("only the comb population control is implemented")
+        if self.pcont_method not in ('comb', 'pair_branch'):
+            raise NotImplementedError("population control '%s': only comb and pair_branch are implemented"
+                                      % self.pcont_method)
         self.min_weight = walker_opts.get('min_weight', 0.1)
         self.max_weight = walker_opts.get('max_weight', 4.0)
         self.ctx = get_context(system, trial, device_id)
@@ -234,6 +292,14 @@ class Walkers(object):
         opt = walker_opts.get('device_comm', None)
         want = opt if opt is not None else os.environ.get('AFQ_DEVICE_COMM', '1') != '0'
         forced = opt is not None and opt is not False        # tried whatever the driver's communicator sits on
+        if self.pcont_method == 'pair_branch' and comm is not None and comm.size > 1:
+            # the library-owned communicator does the comb only: pair branching across ranks goes through the host
+            if forced:
+                raise NotImplementedError("walkers: {device_comm: %r} with population_control 'pair_branch' on %d "
+                                          "ranks: the device communicator does the comb only; leave device_comm "
+                                          "unset and pair branching runs over the driver's communicator"
+                                          % (opt, comm.size))
+            want = False
         if (comm is not None and comm.size > 1 and want and
                 (forced or (getattr(comm, 'device', None) is not None and comm.device.type == 'cuda'))):
             self.device_comm, self.device_comm_error = self._init_device_comm(comm, want)
@@ -434,7 +500,13 @@ class Walkers(object):
         launch.  Several ranks: all-gather of |weights|, identical comb on every
         rank from rank 0's uniform, point-to-point copies of the cloned walkers.
         ``fetch=False`` (single rank, batched loop): nothing is read back, the total
-        weight stays on the device for the next weight cap."""
+        weight stays on the device for the next weight cap.
+
+        ``population_control: pair_branch`` (walkers/handler.py:340-412): one device launch on a single rank, the plan
+        of ``pair_branch_plan`` on rank 0 and packed walkers between ranks otherwise.  The reference draws one uniform
+        per pair it acts on; with ``fetch=True`` the host stream is left exactly there (nw // 2 uniforms are handed to
+        the device, the state is put back and the number the device consumed is drawn again).  With ``fetch=False``
+        nothing comes back, so the host stream advances by nw // 2 per event instead of by the number consumed."""
         self._end_sweep()
         if self.ntot_walkers == 1:
             return
@@ -442,6 +514,36 @@ class Walkers(object):
         if self.use_log_shift:
             self.update_log_ovlp(comm)
         size = 1 if comm is None else comm.size
+        if self.pcont_method == 'pair_branch':
+            if size == 1:
+                if not fetch:
+                    self.dev.popcontrol_pair_branch(numpy.random.rand(self.nw // 2), self.target_weight,
+                                                    self.min_weight, self.max_weight, fetch=False)
+                    self.phi_version += 1
+                    self._invalidate()
+                    return
+                state = numpy.random.get_state()
+                u = numpy.random.rand(self.nw // 2)
+                ndraws = 0
+                try:
+                    mult, ndraws, total = self.dev.popcontrol_pair_branch(u, self.target_weight, self.min_weight,
+                                                                          self.max_weight)
+                except L.AfqError as e:
+                    if e.code == -6:
+                        print("# Warning: total weight is below 1e-8.  Something is seriously wrong.")
+                        sys.exit()
+                    raise
+                finally:                                   # on every way out: the stream is ndraws past where it was
+                    numpy.random.set_state(state)
+                    numpy.random.rand(ndraws)              # one draw per pair acted on, handler.py:359
+                self.last_parent_ix = mult
+            else:
+                total, self.last_parent_ix = pair_branch_distributed(self.dev, comm, self.nw, self.target_weight,
+                                                                     self.min_weight, self.max_weight)
+            self.set_total_weight(total)
+            self.phi_version += 1
+            self._invalidate()
+            return
         if size == 1 or self.device_comm:
             # single rank, or the collective of afq_comm_init: only rank 0 draws the comb uniform (handler.py:276)
             r = numpy.random.random() if (size == 1 or comm.rank == 0) else 0.0
@@ -673,6 +775,52 @@ def pop_control_distributed(dev, comm, nw, target_weight):
     WalkerTransport(dev, comm).exchange(outgoing, incoming)
     dev.reset_weights()                                    # handler.py:337-338
     return total_weight, parent_ix
+
+
+def pair_branch_distributed(dev, comm, nw, target_weight, min_weight, max_weight):
+    """walkers/handler.py:225-251,340-412 across ranks (``dev`` as for pop_control_distributed, plus set for the weights).
+
+    One all-gather of |weights| (:232), the scaling of :244-246 on every rank, then rank 0 alone plans with
+    ``pair_branch_plan`` and draws -- exactly the uniforms the plan consumes, from its global stream (:359) -- and hands
+    the plan to every rank in one broadcast (the reference's scatter :392).  Clones get their new weight before they
+    travel (:399), walkers move in the plan's order (the packed walker carries its weight), nothing is reset.
+
+    Returns (total weight, mult) with mult the GLOBAL int32[nw * size] of the plan (0 kill, 1 keep, 2 clone), which is
+    what ``Walkers.last_parent_ix`` then holds; on one rank it holds the device's mult[nw]."""
+    weights = numpy.abs(dev.get(L.F_WEIGHT))
+    global_weights = numpy.empty(nw * comm.size)
+    comm.Allgather(weights, global_weights)                # handler.py:232
+    total_weight = float(numpy.cumsum(global_weights)[-1])  # sum(global_weights), sequential
+    if total_weight < 1e-8:
+        if comm.rank == 0:
+            print("# Warning: total weight is {:13.8e}.  Something is seriously wrong.".format(total_weight))
+        sys.exit()
+    scale = total_weight / target_weight
+    dev.scale_weights(scale)                               # handler.py:244-246
+    plan = None
+    if comm.rank == 0:
+        new_w, mult, pairs, _ = pair_branch_plan(global_weights / scale, min_weight, max_weight, numpy.random.rand, nw)
+        plan = {'w': new_w, 'mult': mult, 'pairs': pairs}
+    plan = comm.bcast(plan, root=0)
+    mult, pairs = plan['mult'], plan['pairs']
+    lo = comm.rank * nw
+    clones = [c - lo for c, _ in pairs if lo <= c < lo + nw]
+    if clones:                                             # handler.py:399, before the walker is packed
+        mine = dev.get(L.F_WEIGHT)
+        mine[clones] = plan['w'][[c + lo for c in clones]]
+        dev.set(L.F_WEIGHT, mine)
+    outgoing, incoming = {}, {}                            # peer rank -> local walker indices, in pair order
+    for c, k in pairs:
+        src_rank, dst_rank = c // nw, k // nw
+        if src_rank == dst_rank:
+            if src_rank == comm.rank:
+                dev.copy_walker(c % nw, k % nw)            # (afq_walkers_copy: the weight goes along)
+        elif src_rank == comm.rank:
+            outgoing.setdefault(dst_rank, []).append(c % nw)
+        elif dst_rank == comm.rank:
+            incoming.setdefault(src_rank, []).append(k % nw)
+    WalkerTransport(dev, comm).exchange(outgoing, incoming)
+    return total_weight, mult
 
 
 class WalkerTransport(object):
