@@ -56,7 +56,8 @@ typedef struct afq_handle afq_handle;
 /* walker fields for afq_walkers_set / afq_walkers_get.
  * per-walker shapes: PHI c128[M, na+nb]; WEIGHT, UNSCALED_WEIGHT, DETR f64;
  * OT, HYBRID_ENERGY, PHASE, ELOC c128; GHALF c128[na+nb, M] (alpha rows first);
- * G c128[2, M, M]; XBAR, XSHIFTED c128[K]; ENERGY c128[3]; LOG_DETR f64         */
+ * G c128[2, M, M]; XBAR, XSHIFTED c128[K]; ENERGY c128[3]; LOG_DETR f64;
+ * THERMAL_G f64[2, M, M], THERMAL_STACK f64[nbins, 2, M, M] (afq_thermal_configure) */
 enum afq_field {
     AFQ_F_PHI = 0,
     AFQ_F_WEIGHT = 1,
@@ -72,6 +73,8 @@ enum afq_field {
     AFQ_F_XSHIFTED = 11,
     AFQ_F_ENERGY = 12,
     AFQ_F_LOG_DETR = 13,
+    AFQ_F_THERMAL_G = 14,       /* f64[2, M, M], thermal walkers (afq_thermal_configure); get and set      */
+    AFQ_F_THERMAL_STACK = 15,   /* f64[nbins, 2, M, M], thermal walkers; get, and set for unit tests        */
     AFQ_F_COUNT_
 };
 
@@ -552,6 +555,52 @@ int afq_estimates_get_begin(afq_handle *h, int zero);
  * that ends a block) -- one launch less at every block boundary; afq_estimates_get_end collects them as after _get_begin. */
 int afq_estimates_update_publish(afq_handle *h, int eval_energy, int zero);
 int afq_estimates_get_end(afq_handle *h, double *est_out /* c128[10] */);
+
+/* ---- finite-temperature AFQMC: thermal walkers of the Hubbard model, discrete Hirsch fields -----------------
+ * qmc/thermal_afqmc.py, walkers/thermal.py, walkers/stack.py, thermal_propagation/hubbard.py of the reference:
+ * ThermalDiscrete with the spin decomposition (every matrix real), OneBody trial density matrix, constrained
+ * path, low_rank off.  A thermal walker has no determinant: it carries G_s = [I + B_L .. B_1]^-1 per spin
+ * (AFQ_F_THERMAL_G) and a stack of nbins = ntime_slices / stack_size propagator products (AFQ_F_THERMAL_STACK); the
+ * time slice, block and in-bin counter are the same for every walker and belong to the handle.  No trial determinant
+ * and no afq_set_propagator are needed.  M <= 64 sites (a walker's working set stays in LDS).
+ *   afq_thermal_configure  after afq_set_system_hubbard and afq_walkers_alloc.  BT, BT_inv (the trial's dmat and its
+ *                          inverse), BH1 = expm(-dt (H1 - mu I)): f64[2, M, M]; auxf f64[2, 2] = [field][spin] with the
+ *                          chemical-potential shift folded in; nstblz the period of the stable rebuild of G;
+ *                          stack_size must divide ntime_slices.  options: AFQ_THERMAL_* bits of what the caller
+ *                          was asked for -- each of them is refused by name.  Ends with afq_thermal_reset.
+ *                          AFQ_EUNSUPPORTED: the option bits, M > 64, a system that is not Hubbard, a communicator
+ *                          of more than one rank, a handle with back-propagation, ITCF or the mixed RDM switched on
+ *                          (and afq_bp_configure, afq_itcf_configure, afq_estimates_rdm, afq_popcontrol_pair_branch
+ *                          on a thermal handle afterwards).
+ *   afq_thermal_reset      handler.py:424-430: every bin = BT^stack_size, G = the trial's stratified G (computed once,
+ *                          broadcast), weight = 1, counters zeroed.
+ *   afq_thermal_propagate  one time slice of every walker (thermal_propagation/hubbard.py:117-142): for the sites in
+ *                          order probs = 1/2 prod_s (1 + (1 - G_s[i,i]) (auxf[x,s] - 1)), p = max(probs, 0),
+ *                          norm = p_0 + p_1; u[w, i] is consumed whatever norm is; norm > 0: weight *= norm exp(eshift),
+ *                          x = u < p_0 / norm ? 0 : 1, rank-1 update of both G_s; else weight = 0 and G is left alone.
+ *                          Then B_s = diag(auxf[x, s]) BH1_s goes onto the current bin (stack.py:287-297), every
+ *                          nstblz slices G is rebuilt from the stack (afq_thermal_greens at the slice just done), and
+ *                          before the last slice G_s <- BT_s G_s BT_s^-1.  u f64[nw, M]; fields_out int32[nw, M] (may
+ *                          be NULL; -1 where norm <= 0).  AFQ_ESTATE once ntime_slices slices are done.
+ *   afq_thermal_greens     walkers/thermal.py:472-543 for every walker at slice_ix: the stratified decomposition of
+ *                          the chain of bins starting behind bin slice_ix / stack_size, graded by column-pivoted
+ *                          Householder QR (k_thermal.hip).
+ *   afq_thermal_energy     P_s = I - G_s^T into the full-G Hubbard energy: E_out f64[nw, 3] = (E, T, V),
+ *                          nav_out f64[nw] = tr P_up + tr P_down (either may be NULL).
+ *   afq_thermal_state      int32[4] = time slice, block, in-bin counter, nbins.
+ * afq_popcontrol_comb on a thermal handle copies G and the bins of parent to child (single rank);
+ * afq_cap_weights, afq_walkers_get / _set of WEIGHT and UNSCALED_WEIGHT work as for ground-state walkers.         */
+#define AFQ_THERMAL_CHARGE          1   /* charge_decomposition                */
+#define AFQ_THERMAL_FREE_PROJECTION 2
+#define AFQ_THERMAL_LOW_RANK        4
+#define AFQ_THERMAL_AVERAGE_GF      8
+int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int nstblz, const double *BT,
+                          const double *BT_inv, const double *BH1, const double *auxf, int options);
+int afq_thermal_reset(afq_handle *h);
+int afq_thermal_propagate(afq_handle *h, const double *u, int32_t *fields_out, double eshift);
+int afq_thermal_greens(afq_handle *h, int slice_ix);
+int afq_thermal_energy(afq_handle *h, double *E_out, double *nav_out);
+int afq_thermal_state(afq_handle *h, int32_t *out4);
 
 /* ---- misc ------------------------------------------------------------------ */
 /* Device stream of auxiliary fields (used by afq_propagate with xi == NULL; replaces numpy.random.normal of

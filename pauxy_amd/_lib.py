@@ -20,7 +20,9 @@ ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, 
 AFQ_SYS_GENERIC, AFQ_SYS_HUBBARD, AFQ_SYS_UEG = 1, 2, 3
 AFQ_PROP_HYBRID, AFQ_PROP_FORCE_BIAS, AFQ_PROP_FREE_PROJECTION, AFQ_PROP_HUBBARD_SPIN = 1, 2, 4, 8
 (F_PHI, F_WEIGHT, F_UNSCALED_WEIGHT, F_OT, F_HYBRID_ENERGY, F_PHASE, F_DETR, F_ELOC, F_GHALF, F_G,
- F_XBAR, F_XSHIFTED, F_ENERGY, F_LOG_DETR) = range(14)
+ F_XBAR, F_XSHIFTED, F_ENERGY, F_LOG_DETR, F_THERMAL_G, F_THERMAL_STACK) = range(16)
+THERMAL_CHARGE, THERMAL_FREE_PROJECTION, THERMAL_LOW_RANK, THERMAL_AVERAGE_GF = 1, 2, 4, 8
+AFQ_EINVAL, AFQ_ESTATE, AFQ_EUNSUPPORTED = -1, -2, -5
 
 _h = c_void_p
 _dp = c_void_p        # const double* / void* passed as raw addresses
@@ -142,6 +144,12 @@ SIGNATURES = {
     "afq_kernel_trace_stride": [_h, c_int, c_int],
     "afq_kernel_trace_get": [_h, c_int, _dp, c_int, POINTER(c_int)],
     "afq_kernel_issued_flops": [_h, c_int, POINTER(c_double)],
+    "afq_thermal_configure": [_h, c_int, c_int, c_int, _dp, _dp, _dp, _dp, c_int],
+    "afq_thermal_reset": [_h],
+    "afq_thermal_propagate": [_h, _dp, c_void_p, c_double],
+    "afq_thermal_greens": [_h, c_int],
+    "afq_thermal_energy": [_h, _dp, _dp],
+    "afq_thermal_state": [_h, c_void_p],
 }
 
 

@@ -70,6 +70,9 @@ class Context(object):
         self.trial = trial
         self.dev = AfqDevice(local_device_id() if device_id is None else device_id)
         self._upload_system()
+        self.propagator_set = False
+        if getattr(trial, 'name', '') == 'thermal':
+            return                  # a trial density matrix: no determinant to upload (afq_thermal_configure takes it)
         psi = trial_psi(trial)
         if psi.ndim == 3:
             # multi-determinant expansion: per-determinant half-rotated Cholesky vectors, stacked as in

@@ -35,6 +35,7 @@ void free_walkers(afq_handle *h) {
     h->msd_fb_gbar = false;
     h->nbp = 0; h->bpo_two = h->bpo_ekt = h->bpo_sf = h->bpo_corr = 0; h->bpo_nL = 0; h->it_nmax = 0;
     h->rdm_on = false; h->sf_on = false;
+    h->th_on = false;
     h->nw = 0;
 }
 
@@ -655,6 +656,8 @@ static int field_info(afq_handle *h, int field, void **base, size_t *bytes) {
     case AFQ_F_XSHIFTED: *base = h->xs; *bytes = (size_t)h->K * sizeof(cplx); break;
     case AFQ_F_ENERGY: *base = h->energy; *bytes = 3 * sizeof(cplx); break;
     case AFQ_F_LOG_DETR: *base = h->log_detR; *bytes = sizeof(double); break;
+    case AFQ_F_THERMAL_G: *base = h->th_G; *bytes = (size_t)2 * h->M * h->M * sizeof(double); break;
+    case AFQ_F_THERMAL_STACK: *base = h->th_stack; *bytes = (size_t)2 * h->M * h->M * h->th_nbins * sizeof(double); break;
     default: AFQ_FAIL(h, AFQ_EINVAL, "unknown walker field");
     }
     if (!*base) AFQ_FAIL(h, AFQ_ESTATE, "walker field not allocated (afq_walkers_alloc / afq_greens first)");
@@ -1213,6 +1216,7 @@ int afq_set_weight_cap(afq_handle *h, double frac, double total_weight) {
 
 int afq_cap_weights(afq_handle *h, double frac, double total_weight) {
     if (!h) return AFQ_EINVAL;
+    if (h->th_on && h->nw) { hipSetDevice(h->device); return k_cap_weights(h, frac, total_weight); }   // (no trial determinant)
     int rc = need_ready(h, false);
     if (rc) return rc;
     return k_cap_weights(h, frac, total_weight);
@@ -1223,14 +1227,20 @@ int afq_popcontrol_comb(afq_handle *h, double r, double target_weight, int32_t *
     if (h) h->scal_cache_valid = false;
     AFQ_API(h, "afq_popcontrol_comb");
     if (!h) return AFQ_EINVAL;
-    int rc = need_ready(h, false);
-    if (rc) { h->gf.drop(); return rc; }
+    const bool thermal = h->th_on && h->nw;              // thermal walkers: no trial determinant, G and the bins travel
+    int rc = AFQ_OK;
+    if (thermal) {
+        h->gf.drop();
+        hipSetDevice(h->device);
+        if (k_comm_size(h) > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: one rank only");
+    } else if ((rc = need_ready(h, false))) { h->gf.drop(); return rc; }
     const int nranks = k_comm_size(h);
     if (h->nw * nranks == 1) return AFQ_OK;              // handler.py:226-227
     // a kept Green's function travels with the cloned walkers (the clone / pack kernels copy Ghalf and the cached overlap)
     // (never the spin sum alone: the clones copy Ghalf)
     const bool keep = h->gf.take() == GreensCache::FULL && h->ndet == 1;
     if ((rc = k_comb(h, r, target_weight, keep))) return rc;
+    if (thermal && (rc = k_thermal_clone(h))) return rc;
     if (keep) h->gf.keep(GreensCache::FULL);
     if (!parent_ix && !total_weight_out) return AFQ_OK;  // asynchronous: nothing read back, no host sync
     double sc[8];
@@ -1249,6 +1259,7 @@ int afq_popcontrol_pair_branch(afq_handle *h, const double *u, int nu, double ta
     if (h) h->scal_cache_valid = false;
     AFQ_API(h, "afq_popcontrol_pair_branch");
     if (!h) return AFQ_EINVAL;
+    if (h->th_on) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: pair_branch population control is not supported (comb only)");
     int rc = need_ready(h, false);
     if (rc) { h->gf.drop(); return rc; }
     if (k_comm_size(h) > 1) {
@@ -1436,6 +1447,7 @@ int afq_estimates_update_publish(afq_handle *h, int eval_energy, int zero) {
 
 int afq_estimates_rdm(afq_handle *h, int on) {
     if (!h) return AFQ_EINVAL;
+    if (h->th_on) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no mixed one_rdm / two_rdm");
     int rc = need_ready(h, false);
     if (rc) return rc;
     if (h->ndet > 1 || h->hirsch) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "mixed one_rdm: single-determinant trial, continuous propagator");

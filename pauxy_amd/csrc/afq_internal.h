@@ -220,6 +220,20 @@ struct afq_handle {
     int *hs_used = nullptr;         // [nw] uniforms consumed
     int *hs_alive0 = nullptr;       // [nw] walkers the driver propagates this step (|w| > 1e-8)
 
+    // ---- finite-temperature walkers (k_thermal.hip; walkers/thermal.py, walkers/stack.py, thermal_propagation/hubbard.py)
+    bool th_on = false;             // afq_thermal_configure done: the walkers are thermal walkers
+    int th_L = 0, th_ss = 0, th_nbins = 0, th_nstblz = 0;   // time slices, stack_size, bins, stabilisation period
+    int th_slice = 0, th_block = 0, th_counter = 0;          // PropagatorStack.time_slice / block / counter (every walker's)
+    double th_auxf[2][2];           // [field][spin], the chemical-potential shift folded in
+    double *th_BT = nullptr, *th_BTinv = nullptr, *th_BH1 = nullptr;   // [2, M, M] each
+    double *th_BTpow = nullptr;     // [2, M, M] BT^stack_size: every bin of a fresh path
+    double *th_G = nullptr;         // [nw, 2, M, M]
+    double *th_G0 = nullptr;        // [2, M, M] the trial's G (afq_thermal_reset)
+    double *th_stack = nullptr;     // [nw, nbins, 2, M, M]
+    double *th_u = nullptr;         // [nw, M] uniforms of the slice
+    int *th_fields = nullptr;       // [nw, M] chosen fields (-1: both probabilities vanished)
+    double *th_nav = nullptr;       // [nw]
+
     // ---- propagator
     bool have_prop = false;
     cplx *BH1 = nullptr;            // [2, M, M]
@@ -630,6 +644,9 @@ int k_ueg_sf_two(afq_handle *h, int n, cplx **two_dev, cplx **E_dev);   // the h
 int k_ueg_sf_wsum(afq_handle *h, const cplx *two_dev, int n, const cplx *wt_c, const double *wt_r, cplx *out_c,
                   double *acc_r);                            // out_c = sum_g wt[g] two[g]; acc_r += Re of it
 int k_energy_hubbard_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *E_dev);   // estimators/hubbard.py:93-114
+// k_thermal.hip
+int k_thermal_greens(afq_handle *h, int slice_ix);          // th_G of every walker from its stack
+int k_thermal_clone(afq_handle *h);                         // G and bins of the comb's (src, dst) pairs in pack_tmp
 // k_corr.hip: <n_is n_jt> and <S+_i S-_j> of full Green's functions G_dev [n, 2, M, M] -> out_dev [n, 5, M, M], and
 // their weighted sum over n -> out_dev [5, M, M] (Green's functions of weight zero left out), in index order
 int k_corr_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *out_dev);

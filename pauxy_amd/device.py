@@ -341,6 +341,8 @@ class AfqDevice(object):
             L.F_GHALF: ((nt, M), numpy.complex128), L.F_G: ((2, M, M), numpy.complex128),
             L.F_XBAR: ((K,), numpy.complex128), L.F_XSHIFTED: ((K,), numpy.complex128),
             L.F_ENERGY: ((3,), numpy.complex128), L.F_LOG_DETR: ((), numpy.float64),
+            L.F_THERMAL_G: ((2, M, M), numpy.float64),
+            L.F_THERMAL_STACK: ((getattr(self, 'thermal_nbins', 0), 2, M, M), numpy.float64),
         }[field]
 
     def set(self, field, values, first=0):
@@ -357,6 +359,40 @@ class AfqDevice(object):
         out = numpy.empty((count,) + shape, dtype=dt)
         self._ck(self.lib.afq_walkers_get(self.h, field, _p(out), int(first), int(count)))
         return out
+
+    # -- thermal walkers (finite temperature) ------------------------------
+    def thermal_configure(self, ntime_slices, stack_size, nstblz, BT, BT_inv, BH1, auxf, options=0):
+        M = self.M
+        BT, BT_inv, BH1 = _f64(BT, (2, M, M)), _f64(BT_inv, (2, M, M)), _f64(BH1, (2, M, M))
+        auxf = _f64(auxf, (2, 2))
+        self._ck(self.lib.afq_thermal_configure(self.h, int(ntime_slices), int(stack_size), int(nstblz), _p(BT),
+                                                _p(BT_inv), _p(BH1), _p(auxf), int(options)))
+        self.thermal_nbins = int(ntime_slices) // int(stack_size)
+
+    def thermal_reset(self):
+        self._ck(self.lib.afq_thermal_reset(self.h))
+
+    def thermal_propagate(self, u, eshift=0.0, fetch_fields=False):
+        u = _f64(u, (self.nw, self.M))
+        fields = numpy.empty((self.nw, self.M), dtype=numpy.int32) if fetch_fields else None
+        self._ck(self.lib.afq_thermal_propagate(self.h, _p(u), _p(fields), float(eshift)))
+        return fields
+
+    def thermal_greens(self, slice_ix):
+        self._ck(self.lib.afq_thermal_greens(self.h, int(slice_ix)))
+
+    def thermal_energy(self):
+        """(E [nw, 3] = (E, T, V), nav [nw]) of the walkers' current G."""
+        E = numpy.empty((self.nw, 3), dtype=numpy.float64)
+        nav = numpy.empty(self.nw, dtype=numpy.float64)
+        self._ck(self.lib.afq_thermal_energy(self.h, _p(E), _p(nav)))
+        return E, nav
+
+    def thermal_state(self):
+        """(time slice, block, in-bin counter, nbins)."""
+        out = numpy.zeros(4, dtype=numpy.int32)
+        self._ck(self.lib.afq_thermal_state(self.h, _p(out)))
+        return tuple(int(x) for x in out)
 
     # -- hot path ---------------------------------------------------------
     def greens(self, want_G=False, fetch=True):

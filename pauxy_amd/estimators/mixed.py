@@ -28,7 +28,10 @@ class _Enum(dict):
 
 
 def get_estimator_enum(thermal=False):
-    keys = ['uweight', 'weight', 'enumer', 'edenom', 'eproj', 'e1b', 'e2b', 'ehyb', 'ovlp', 'time']
+    keys = ['uweight', 'weight', 'enumer', 'edenom', 'eproj', 'e1b', 'e2b', 'ehyb', 'ovlp']
+    if thermal:
+        keys.append('nav')                                              # mixed.py:463-464
+    keys.append('time')
     return _Enum((k, v) for v, k in enumerate(keys))
 
 
@@ -36,8 +39,15 @@ class Mixed(object):
     calc_two_rdm = None
     structure_factor = False
     _sf_armed = False
+    thermal = False             # set with a finite-temperature run (qmc.beta, mixed.py:87-92): the Nav column
 
     def __init__(self, mixed, system, root, filename, qmc, trial, dtype=complex):
+        if getattr(qmc, 'beta', None) is not None:
+            self.thermal = True
+            if mixed.get('average_gf', False):
+                raise NotImplementedError("mixed estimator: average_gf is not supported with a thermal trial")
+            if mixed.get('one_rdm', False) or mixed.get('two_rdm', None) is not None:
+                raise NotImplementedError("mixed estimator: one_rdm / two_rdm are not supported with a thermal trial")
         self.eval_energy = mixed.get('evaluate_energy', True)
         self.calc_one_rdm = mixed.get('one_rdm', False)
         two = mixed.get('two_rdm', None)
@@ -60,9 +70,11 @@ class Mixed(object):
         self.nsteps = qmc.nsteps
         self.header = ['Iteration', 'WeightFactor', 'Weight', 'ENumer', 'EDenom', 'ETotal', 'E1Body',
                        'E2Body', 'EHybrid', 'Overlap', 'Time']
+        if self.thermal:
+            self.header.insert(len(self.header) - 1, 'Nav')
         self.nreg = len(self.header[1:])
         self.dtype = dtype
-        self.names = get_estimator_enum()
+        self.names = get_estimator_enum(self.thermal)
         self.estimates = numpy.zeros(self.nreg, dtype=dtype)
         self.estimates[self.names.time] = time.time()
         self.global_estimates = numpy.zeros(self.nreg, dtype=dtype)
@@ -92,6 +104,8 @@ class Mixed(object):
         """mixed.py:133-233: importance-sampling branch (:210-225) or, when the propagator was
         built with free_projection, the complex wfac = weight*ot*phase accumulation of :151-175
         (the device handle knows which from afq_set_propagator)."""
+        if self.thermal:
+            return self.update_thermal(psi)
         if self.structure_factor and free_projection:
             raise NotImplementedError("mixed two_rdm: 'structure_factor' with free projection")
         psi._end_sweep()
@@ -114,6 +128,26 @@ class Mixed(object):
             self.sf_acc += dev.estimates_sf_get(zero=True)
         if do_energy:
             psi._greens_version = psi.phi_version           # the launch refreshed Ghalf
+
+    def update_thermal(self, psi):
+        """mixed.py:200-209,222-225 for a population of thermal walkers: G rebuilt from every walker's stack at its
+        current time slice (the end of the path), the energies and particle numbers from the device, the weighted
+        sums -- once per path -- here."""
+        ns, es = self.names, self.estimates
+        psi.recompute_greens_function(None)
+        E, nav = psi.dev.thermal_energy()
+        from pauxy_amd import _lib as L
+        w = psi.dev.get(L.F_WEIGHT)
+        uw = psi.dev.get(L.F_UNSCALED_WEIGHT)
+        for i in range(len(w)):                                         # (walker order, as the reference sums)
+            es[ns.nav] += w[i] * nav[i]
+            es[ns.enumer] += w[i] * E[i, 0]
+            es[ns.e1b:ns.e2b + 1] += w[i] * E[i, 1:3]
+            es[ns.edenom] += w[i]
+            es[ns.uweight] += uw[i]
+            es[ns.weight] += w[i]
+            es[ns.ovlp] += w[i] * 1.0                                   # walker.ot stays 1 (walkers/walker.py)
+            es[ns.ehyb] += w[i] * 0.0                                   # walker.hybrid_energy stays 0
 
     def arm_rdm(self, dev):
         """one_rdm: True -> the device accumulates weight * walker.G.real with every estimator update."""
@@ -150,6 +184,8 @@ class Mixed(object):
             gs[ns.ehyb] /= gs[ns.weight]
             gs[ns.ovlp] /= gs[ns.weight]
             eshift = numpy.array([gs[ns.ehyb], gs[ns.eproj]])
+            if self.thermal:
+                gs[ns.nav] = gs[ns.nav] / gs[ns.weight]                 # mixed.py:271-272
         else:
             eshift = numpy.array([0, 0])
         if not everywhere:

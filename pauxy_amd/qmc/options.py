@@ -21,6 +21,6 @@ class QMCOpts(object):
         self.npop_control = _get(inputs, 'pop_control_freq', 1, ['npop_control', 'pop_control'])
         self.eqlb_time = _get(inputs, 'equilibration_time', 2.0, ['tau_eqlb'])
         self.neqlb = int(self.eqlb_time / self.dt)
-        self.beta = None
+        self.beta = _get(inputs, 'beta', None)
         self.rng_seed = _get(inputs, 'rng_seed', None, ['random_seed', 'seed'])
         self.ntot_walkers = self.nwalkers

@@ -1,0 +1,116 @@
+"""Finite-temperature driver over the device objects, restated from pauxy/qmc/thermal_afqmc.py:77-235
+(``ThermalAFQMC``): OneBody trial density matrix, thermal walkers, ThermalDiscrete, the mixed estimator with its Nav
+column; one path of ``ntime_slices`` slices per block, estimators at the end of every path, then a reset.
+
+    for every path:  for every time slice ts:
+        propagate every walker; cap |w| at 0.1 total_weight when ts > 0; comb when ts % npop_control == 0 and ts != 0
+    estimators from the end-of-path G, one row printed, walkers reset to the trial
+"""
+import time
+
+import numpy
+
+from pauxy_amd.comm import FakeComm
+from pauxy_amd.estimators.handler import Estimators
+from pauxy_amd.propagation.thermal_hubbard import ThermalDiscrete
+from pauxy_amd.qmc.options import QMCOpts
+from pauxy_amd.systems import get_system
+from pauxy_amd.trial_density import OneBody
+from pauxy_amd.walkers.handler import Walkers
+
+
+def _opt(options, key, aliases, default=None):
+    for k in (key,) + tuple(aliases):
+        if k in options:
+            return options[k]
+    return {} if default is None else default
+
+
+def get_trial_density_matrix(system, beta, dt, options={}, verbose=False):
+    """trial_density_matrices/utils.py: only the one-body density matrix has a device path."""
+    name = options.get('name', 'one_body')
+    if name == 'one_body_mod':
+        return OneBody(system, beta, dt, options=options, H1=system.h1e_mod, verbose=verbose)
+    if name == 'one_body':
+        return OneBody(system, beta, dt, options=options, verbose=verbose)
+    raise NotImplementedError("trial density matrix '%s' is not supported (MeanField included): one_body only" % name)
+
+
+class ThermalAFQMC(object):
+    def __init__(self, comm=None, options=None, system=None, trial=None, parallel=False, verbose=None):
+        self.comm = comm if comm is not None else FakeComm()
+        if self.comm.size > 1:
+            raise NotImplementedError("ThermalAFQMC: more than one rank is not supported")
+        options = options or {}
+        self.verbosity = verbose or 0
+        qmc_opts = _opt(options, 'qmc', ['qmc_options'])
+        if qmc_opts.get('beta') is None:
+            raise ValueError("ThermalAFQMC needs qmc: {beta: ...}")
+        self.root = self.comm.rank == 0
+        self.nprocs = self.comm.size
+        self.rank = self.comm.rank
+        self._init_time = time.time()
+        if system is None:
+            sys_opts = dict(_opt(options, 'system', ['model']), thermal=True)
+            system = get_system(sys_opts)
+        if system.name != "Hubbard":
+            raise NotImplementedError("ThermalAFQMC: Hubbard systems only (no Generic / UEG)")
+        self.system = system
+        self.qmc = QMCOpts(qmc_opts, system)
+        if self.qmc.rng_seed is not None:
+            numpy.random.seed(self.qmc.rng_seed + self.comm.rank)           # qmc/utils.py:3-16
+        self.qmc.ntime_slices = int(round(self.qmc.beta / self.qmc.dt))
+        self.qmc.nsteps = 1                                                 # thermal_afqmc.py:123-125
+        self.qmc.total_steps = self.qmc.nblocks
+        if trial is None:
+            trial = get_trial_density_matrix(system, self.qmc.beta, self.qmc.dt,
+                                             options=_opt(options, 'trial', ['trial_density']))
+        self.trial = trial
+        self.qmc.nwalkers = max(1, int(self.qmc.nwalkers / self.comm.size))
+        self.qmc.ntot_walkers = self.qmc.nwalkers * self.nprocs
+        self.walk = Walkers(system, trial, self.qmc, walker_opts=_opt(options, 'walkers', ['walker', 'walker_opts']),
+                            comm=self.comm)
+        prop_opts = _opt(options, 'propagator', ['prop', 'propagation'])
+        self.propagators = ThermalDiscrete(system, trial, self.qmc, options=prop_opts,
+                                           lowrank=self.walk.walkers[0].lowrank)
+        est_opts = _opt(options, 'estimators', ['estimates'])
+        if est_opts.get('back_propagation', est_opts.get('back_propagated')) is not None or est_opts.get('itcf') is not None:
+            raise NotImplementedError("ThermalAFQMC: back-propagation and ITCF are not supported with a thermal trial")
+        self.estimators = Estimators(est_opts, self.root, self.qmc, system, trial, self.propagators.BT_BP, verbose)
+        if self.qmc.nstblz != self.propagators.nstblz:                      # thermal_afqmc.py:179-181
+            self.propagators.nstblz = self.qmc.nstblz
+        self.setup_timers()
+
+    def setup_timers(self):
+        self.tpath = self.tprop = self.testim = self.tpopc = 0.0
+
+    def run(self, walk=None, comm=None, verbose=None):
+        """thermal_afqmc.py:190-235."""
+        comm = comm or self.comm
+        if walk is not None:
+            self.walk = walk
+        self.setup_timers()
+        mixed = self.estimators.estimators['mixed']
+        mixed.update(self.system, self.qmc, self.trial, self.walk, 0, False)
+        mixed.print_step(comm, self.nprocs, 0, 1)
+        for step in range(1, self.qmc.total_steps + 1):
+            start_path = time.time()
+            for ts in range(0, self.qmc.ntime_slices):
+                start = time.time()
+                self.propagators.propagate_walkers(self.walk, 0)
+                if ts > 0:
+                    self.walk.cap_weights(0.10)
+                self.tprop += time.time() - start
+                start = time.time()
+                if ts % self.qmc.npop_control == 0 and ts != 0:
+                    self.walk.pop_control(comm)
+                self.tpopc += time.time() - start
+            self.tpath += time.time() - start_path
+            start = time.time()
+            self.estimators.update(self.system, self.qmc, self.trial, self.walk, step, False)
+            self.testim += time.time() - start
+            self.estimators.print_step(comm, self.nprocs, step, free_projection=False)
+            self.walk.reset(self.trial)
+
+    def finalise(self, verbose=False):
+        self.estimators.flush()

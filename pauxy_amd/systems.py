@@ -84,7 +84,7 @@ def hubbard_kinetic(t, nx, ny, xpbc=True, ypbc=True):
 class Hubbard(object):
     """2-D (or 1-D) Hubbard model, systems/hubbard.py:46-104."""
 
-    def __init__(self, nx, ny, nup, ndown, U, t=1.0):
+    def __init__(self, nx, ny, nup, ndown, U, t=1.0, mu=None):
         self.name = "Hubbard"
         self.nx, self.ny = nx, ny
         self.nup, self.ndown = nup, ndown
@@ -98,10 +98,11 @@ class Hubbard(object):
         self.ecore = 0.0
         self.nfields = self.nbasis
         self.symmetric = False
+        self._alt_convention = False
         self.control_variate = False
         self.ktwist = numpy.array(None)
         self.vol = nx * ny
-        self.mu = None
+        self.mu = mu
         # systems/hubbard.py:148-155
         v0 = 0.5 * U * numpy.eye(self.nbasis)
         self.h1e_mod = numpy.array([self.H1[0] - v0, self.H1[1] - v0])
@@ -279,7 +280,7 @@ def get_system(sys_opts):
         return Generic((nup, ndown), h1e, chol, ecore, h1e_mod=h1e_mod)
     if name == 'Hubbard':
         return Hubbard(sys_opts['nx'], sys_opts['ny'], sys_opts['nup'], sys_opts['ndown'], sys_opts['U'],
-                       t=sys_opts.get('t', 1.0))
+                       t=sys_opts.get('t', 1.0), mu=sys_opts.get('mu', None))
     if name == 'UEG':
         return UEG(sys_opts['rs'], sys_opts['nup'], sys_opts['ndown'], sys_opts['ecut'],
                    full_lists=sys_opts.get('full_lists', False))

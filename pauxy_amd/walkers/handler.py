@@ -248,6 +248,13 @@ class Walkers(object):
     trial = hidden()
     _device_comm_fault = hidden()       # (test hook of the communicator bring-up, see _init_device_comm)
 
+    def __new__(cls, system=None, trial=None, *args, **kwargs):
+        # walkers/handler.py:77-100: a thermal trial (density matrix) gets a population of thermal walkers
+        if cls is Walkers and getattr(trial, 'name', '') == 'thermal':
+            from pauxy_amd.walkers.thermal import ThermalWalkers
+            return ThermalWalkers(system, trial, *args, **kwargs)
+        return object.__new__(cls)
+
     def __init__(self, system, trial, qmc, walker_opts={}, verbose=False, comm=None, nprop_tot=None,
                  nbp=None, device_id=None):
         self.nwalkers = qmc.nwalkers

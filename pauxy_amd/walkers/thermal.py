@@ -1,0 +1,168 @@
+"""Population of thermal walkers on the device (the ``trial.name == 'thermal'`` branch of walkers/handler.py:77-100
+and walkers/thermal.py, walkers/stack.py of the reference).
+
+A thermal walker is its Green's function G [2, M, M] and a stack of propagator products; both live in the library
+(k_thermal.hip).  ``walkers[i]`` are light views with the members the reference's driver and estimators read
+(``weight``, ``G``, ``stack_size``, ``stack_length``, ``local_energy``, ``greens_function``)."""
+import numpy
+
+from pauxy_amd import _lib as L
+from pauxy_amd.context import get_context, hidden
+from pauxy_amd.propagation.thermal_hubbard import thermal_constants
+from pauxy_amd.trial_density import update_stack
+
+
+class ThermalWalkerView(object):
+    _h = hidden()
+
+    def __init__(self, handler, i):
+        self._h = handler
+        self.index = i
+        self.stack_size = handler.stack_size
+        self.stack_length = handler.stack_length
+        self.num_slices = handler.num_slices
+        self.lowrank = False
+        self.ot = 1.0
+        self.hybrid_energy = 0.0
+
+    @property
+    def weight(self):
+        return float(self._h.dev.get(L.F_WEIGHT, self.index, 1)[0])
+
+    @weight.setter
+    def weight(self, value):
+        self._h.dev.set(L.F_WEIGHT, numpy.array([float(numpy.real(value))]), self.index)
+
+    @property
+    def unscaled_weight(self):
+        return float(self._h.dev.get(L.F_UNSCALED_WEIGHT, self.index, 1)[0])
+
+    @property
+    def total_weight(self):
+        return self._h.total_weight
+
+    @property
+    def G(self):
+        self._h.ensure_configured()
+        return self._h.dev.get(L.F_THERMAL_G, self.index, 1)[0]
+
+    def greens_function(self, trial, slice_ix=None, inplace=True):
+        """walkers/thermal.py:90-95 -- for the whole population (the library moves every walker together)."""
+        if not inplace:
+            raise NotImplementedError("ThermalWalker.greens_function(inplace=False)")
+        self._h.recompute_greens_function(trial, slice_ix)
+
+    def local_energy(self, system, two_rdm=None):
+        if two_rdm is not None:
+            raise NotImplementedError("thermal walkers: no two_rdm")
+        self._h.ensure_configured()
+        E, _ = self._h.dev.thermal_energy()
+        return tuple(E[self.index])
+
+
+class ThermalWalkers(object):
+    ctx = hidden()
+    dev = hidden()
+    system = hidden()
+    trial = hidden()
+    _prop = hidden()
+
+    def __init__(self, system, trial, qmc, walker_opts={}, verbose=False, comm=None, nprop_tot=None, nbp=None,
+                 device_id=None):
+        if comm is not None and comm.size > 1:
+            raise NotImplementedError("thermal walkers: more than one rank is not supported")
+        if nbp is not None or nprop_tot is not None:
+            raise NotImplementedError("thermal walkers: no back-propagation or ITCF with a thermal trial")
+        if system.name != "Hubbard":
+            raise NotImplementedError("thermal walkers: Hubbard systems only (no Generic / UEG)")
+        if not hasattr(trial, 'dmat_inv'):
+            raise NotImplementedError("thermal walkers: a OneBody trial density matrix is needed (no MeanField)")
+        if walker_opts.get('low_rank', False):
+            raise NotImplementedError("thermal walkers: low_rank: True is not supported")
+        self.pcont_method = walker_opts.get('population_control', 'comb')
+        if self.pcont_method != 'comb':
+            raise NotImplementedError("thermal walkers: population control '%s' is not supported (pair_branch "
+                                      "included): comb only" % self.pcont_method)
+        if system.nbasis > 64:
+            raise NotImplementedError("thermal walkers: M = %d > 64 sites is not supported" % system.nbasis)
+        self.nwalkers = qmc.nwalkers
+        self.ntot_walkers = qmc.ntot_walkers
+        self.walker_type = 'thermal'
+        self.write_freq = 0
+        self.write_restart = False
+        self.use_log_shift = False
+        self.num_slices = trial.num_slices
+        # walkers/thermal.py:31-43
+        self.stack_size = walker_opts.get('stack_size', None)
+        if self.stack_size is None:
+            self.stack_size = trial.stack_size
+        if (self.num_slices // self.stack_size) * self.stack_size != self.num_slices:
+            self.stack_size = update_stack(self.stack_size, self.num_slices)
+        self.stack_length = self.num_slices // self.stack_size
+        # walkers/handler.py:86-100: the stabilisation period against the stack size
+        if self.stack_size % qmc.nstblz != 0 or qmc.nstblz < self.stack_size:
+            if qmc.nstblz < self.stack_size:
+                qmc.nstblz = self.stack_size
+            else:
+                qmc.nstblz = update_stack(qmc.nstblz, self.stack_size)
+        self.nstblz = qmc.nstblz
+        self.dt = qmc.dt
+        self.ctx = get_context(system, trial, device_id)
+        self.dev = self.ctx.dev
+        self.system, self.trial = system, trial
+        self.dev.walkers_alloc(self.nwalkers)
+        self.nw = self.nwalkers
+        self.target_weight = qmc.ntot_walkers
+        self.total_weight = float(qmc.ntot_walkers)
+        self.time_slice = 0
+        self.path_index = 0
+        self.configured_nstblz = None
+        self._prop = None
+        self.last_parent_ix = None
+        self.walkers = [ThermalWalkerView(self, i) for i in range(self.nw)]
+
+    def ensure_configured(self, prop=None):
+        """The library is configured on first use: the propagator's stabilisation period decides when it is known."""
+        nstblz = self.nstblz if prop is None else prop.nstblz
+        if self.configured_nstblz == nstblz:
+            return
+        if self.configured_nstblz is not None and self.time_slice != 0:
+            raise RuntimeError("thermal walkers: the stabilisation period changed in the middle of a path")
+        _, auxf, _, _, BH1 = thermal_constants(self.system, self.trial, self.dt)
+        self.dev.thermal_configure(self.num_slices, self.stack_size, nstblz, self.trial.dmat, self.trial.dmat_inv,
+                                   BH1, auxf)
+        self.configured_nstblz = nstblz
+        self.nstblz = nstblz
+
+    def set_total_weight(self, total_weight):
+        self.total_weight = total_weight
+
+    def recompute_greens_function(self, trial, time_slice=None):
+        self.ensure_configured()
+        self.dev.thermal_greens(self.time_slice if time_slice is None else time_slice)
+
+    def pop_control(self, comm=None):
+        """walkers/handler.py:225-338 on one rank: the comb, G and the stack travel with the clones."""
+        if self.ntot_walkers == 1:
+            return
+        self.ensure_configured()
+        r = numpy.random.random()
+        try:
+            pix, total = self.dev.popcontrol_comb(r, self.target_weight)
+        except L.AfqError as e:
+            if e.code == L.AFQ_EWEIGHT:
+                raise SystemExit("# Warning: total weight is below 1e-8.  Something is seriously wrong.")
+            raise
+        self.last_parent_ix = pix
+        self.set_total_weight(total)
+
+    def cap_weights(self, frac=0.10):
+        """qmc/thermal_afqmc.py:220-221 for every walker: |w| > frac total_weight -> frac total_weight."""
+        self.dev.cap_weights(frac, self.total_weight)
+
+    def reset(self, trial):
+        """walkers/handler.py:424-430."""
+        self.ensure_configured()
+        self.dev.thermal_reset()
+        self.time_slice = 0
+        self.path_index += 1
