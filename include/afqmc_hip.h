@@ -505,8 +505,14 @@ int afq_popcontrol_comb_local(afq_handle **handles, int n, double r, double targ
 int afq_estimates_allreduce_local(afq_handle **handles, int n);
 /* multi-rank building blocks: scale weights by 1/scale saving unscaled_weight
  * (handler.py:244-246); copy walker src -> dst inside this GPU; pack / unpack
- * the minimal walker state (phi + scalars) to a device buffer for transport;
- * reset all weights to 1 (handler.py:337-338).                                 */
+ * one walker to a device buffer of afq_walker_pack_bytes bytes for transport;
+ * reset all weights to 1 (handler.py:337-338).
+ * What a walker carries is listed ONCE, in csrc/walker_fields.h; the copy, the pack, the clones of the population
+ * control and the exchange slots of the communicator all loop over that list.  The packed walker starts
+ * phi c128[M, na + nb] | ot, hybrid energy, phase, eloc (c128) | unscaled weight, detR, weight, log detR (f64);
+ * the back-propagation state and walker.G follow when they are on, every entry at a multiple of the unit it is
+ * copied in (16, 8 or 4 bytes) and the whole rounded up to 16 bytes:
+ * 16 (per + 4) + 32 [+ 16 (per + nbp K + 1) + 16] [+ 32 M^2] bytes, per = M (na + nb).                            */
 int afq_walkers_scale_weights(afq_handle *h, double scale);
 int afq_walkers_copy(afq_handle *h, int src, int dst);
 int afq_walker_pack_bytes(afq_handle *h, int64_t *bytes);

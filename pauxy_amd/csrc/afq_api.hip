@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "afq_host.h"
+#include "walker_fields.h"
 
 namespace {
 
@@ -1240,7 +1241,6 @@ int afq_popcontrol_comb(afq_handle *h, double r, double target_weight, int32_t *
     // (never the spin sum alone: the clones copy Ghalf)
     const bool keep = h->gf.take() == GreensCache::FULL && h->ndet == 1;
     if ((rc = k_comb(h, r, target_weight, keep))) return rc;
-    if (thermal && (rc = k_thermal_clone(h))) return rc;
     if (keep) h->gf.keep(GreensCache::FULL);
     if (!parent_ix && !total_weight_out) return AFQ_OK;  // asynchronous: nothing read back, no host sync
     double sc[8];
@@ -1301,48 +1301,23 @@ int afq_walkers_reset_weights(afq_handle *h) {
     return k_reset_weights(h);
 }
 
-// packed walker: phi | ot, ehyb, phase, eloc (c128) | unscaled_weight, detR, weight, log_detR (f64)
+// packed walker: the entries of walker_fields (the weight included) as WalkerFields::packed_bytes lays them out, which
+// starts phi | ot, ehyb, phase, eloc (c128) | unscaled_weight, detR, weight, log_detR (f64)
 int afq_walker_pack_bytes(afq_handle *h, int64_t *bytes) {
     if (!h || !bytes) return AFQ_EINVAL;
-    size_t b = sizeof(cplx) * ((size_t)h->M * h->nt + 4) + sizeof(double) * 4;
-    if (h->nbp > 0)   // phi_old + field history + FieldConfig.step + the two running weight factors
-        b += sizeof(cplx) * ((size_t)h->M * h->nt + (size_t)h->nbp * h->K + 1) + sizeof(double) * 2;
-    if (h->rdm_on && h->G) b += sizeof(cplx) * (size_t)2 * h->M * h->M;     // walker.G (mixed one_rdm)
-    *bytes = (int64_t)b;
+    *bytes = (int64_t)walker_fields(h, WF_WEIGHT).packed_bytes();
     return AFQ_OK;
 }
 
 static int pack_io(afq_handle *h, int iw, char *buf, bool pack) {
-    const size_t per = (size_t)h->M * h->nt;
-    struct Item { void *p; size_t b; };
-    const Item items[] = {{h->phi + per * iw, per * sizeof(cplx)}, {h->ot + iw, sizeof(cplx)},
-                          {h->ehyb + iw, sizeof(cplx)}, {h->phase + iw, sizeof(cplx)},
-                          {h->eloc + iw, sizeof(cplx)}, {h->unscaled + iw, sizeof(double)},
-                          {h->detR + iw, sizeof(double)}, {h->weight + iw, sizeof(double)},
-                          {h->log_detR + iw, sizeof(double)}};
-    size_t off = 0;
-    for (const Item &it : items) {
-        if (pack) AFQ_HIP(h, hipMemcpyAsync(buf + off, it.p, it.b, hipMemcpyDeviceToDevice, h->stream));
-        else AFQ_HIP(h, hipMemcpyAsync(it.p, buf + off, it.b, hipMemcpyDeviceToDevice, h->stream));
-        off += it.b;
-    }
-    if (h->nbp > 0) {
-        const size_t hk = (size_t)h->nbp * h->K;
-        const Item bp[] = {{h->phi_old + per * iw, per * sizeof(cplx)}, {h->bp_hist + hk * iw, hk * sizeof(cplx)},
-                           {h->bp_ph + iw, sizeof(cplx)}, {h->bp_cos + iw, sizeof(double)},
-                           {h->bp_n + iw, sizeof(int)}};
-        for (const Item &it : bp) {
-            if (pack) AFQ_HIP(h, hipMemcpyAsync(buf + off, it.p, it.b, hipMemcpyDeviceToDevice, h->stream));
-            else AFQ_HIP(h, hipMemcpyAsync(it.p, buf + off, it.b, hipMemcpyDeviceToDevice, h->stream));
-            off += it.b;
-        }
-    }
-    if (h->rdm_on && h->G) {
-        const size_t gb = sizeof(cplx) * (size_t)2 * h->M * h->M;
-        cplx *g = h->G + (size_t)iw * 2 * h->M * h->M;
-        if (pack) AFQ_HIP(h, hipMemcpyAsync(buf + off, g, gb, hipMemcpyDeviceToDevice, h->stream));
-        else AFQ_HIP(h, hipMemcpyAsync(g, buf + off, gb, hipMemcpyDeviceToDevice, h->stream));
-        off += gb;
+    const WalkerFields f = walker_fields(h, WF_WEIGHT);
+    long off = 0;
+    for (int k = 0; k < f.n; ++k) {
+        const WalkerFields::Entry &e = f.e[k];
+        off = WalkerFields::packed_at(off, e.bytes);
+        if (pack) AFQ_HIP(h, hipMemcpyAsync(buf + off, e.base + iw * e.bytes, e.bytes, hipMemcpyDeviceToDevice, h->stream));
+        else AFQ_HIP(h, hipMemcpyAsync(e.base + iw * e.bytes, buf + off, e.bytes, hipMemcpyDeviceToDevice, h->stream));
+        off += e.bytes;
     }
     return AFQ_OK;
 }
@@ -1371,15 +1346,9 @@ int afq_walkers_copy(afq_handle *h, int src, int dst) {
     if (rc) return rc;
     if (src < 0 || dst < 0 || src >= h->nw || dst >= h->nw) AFQ_FAIL(h, AFQ_EINVAL, "walker index out of range");
     if (src == dst) return AFQ_OK;
-    const size_t per = (size_t)h->M * h->nt;
-#define C_(ptr, n) AFQ_HIP(h, hipMemcpyAsync((ptr) + (size_t)dst * (n), (ptr) + (size_t)src * (n), sizeof(*(ptr)) * (n), hipMemcpyDeviceToDevice, h->stream));
-    C_(h->phi, per) C_(h->ot, 1) C_(h->ehyb, 1) C_(h->phase, 1) C_(h->eloc, 1)
-    C_(h->unscaled, 1) C_(h->detR, 1) C_(h->weight, 1) C_(h->log_detR, 1)
-    if (h->nbp > 0) {
-        C_(h->phi_old, per) C_(h->bp_hist, (size_t)h->nbp * h->K) C_(h->bp_ph, 1) C_(h->bp_cos, 1) C_(h->bp_n, 1)
-    }
-    if (h->rdm_on && h->G) { C_(h->G, (size_t)2 * h->M * h->M) }      // walker.G is walker state for the mixed one_rdm
-#undef C_
+    const WalkerFields f = walker_fields(h, WF_WEIGHT);
+    for (int k = 0; k < f.n; ++k)
+        AFQ_HIP(h, hipMemcpyAsync(f.e[k].base + dst * f.e[k].bytes, f.e[k].base + src * f.e[k].bytes, f.e[k].bytes, hipMemcpyDeviceToDevice, h->stream));
     return AFQ_OK;
 }
 

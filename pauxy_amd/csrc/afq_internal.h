@@ -646,7 +646,6 @@ int k_ueg_sf_wsum(afq_handle *h, const cplx *two_dev, int n, const cplx *wt_c, c
 int k_energy_hubbard_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *E_dev);   // estimators/hubbard.py:93-114
 // k_thermal.hip
 int k_thermal_greens(afq_handle *h, int slice_ix);          // th_G of every walker from its stack
-int k_thermal_clone(afq_handle *h);                         // G and bins of the comb's (src, dst) pairs in pack_tmp
 // k_corr.hip: <n_is n_jt> and <S+_i S-_j> of full Green's functions G_dev [n, 2, M, M] -> out_dev [n, 5, M, M], and
 // their weighted sum over n -> out_dev [5, M, M] (Green's functions of weight zero left out), in index order
 int k_corr_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *out_dev);

@@ -13,8 +13,8 @@
 //                            form one contiguous run and the position inside the run is the exchange slot.
 //                            Out: pairs inside this rank, send / receive slot lists per peer, global parent_ix.
 //   4. clone_kernel          copies inside the rank
-//   5. comm_pack_kernel      walker state (phi, scalars, cached Green's function, back-propagation history)
-//                            of the outgoing walkers
+//   5. comm_pack_kernel      the outgoing walkers, entry by entry of the walker table (walker_fields.h: phi, scalars,
+//                            back-propagation history, walker.G, cached Green's function)
 //   6. exchange              WINDOW transport (default): every rank maps every peer's receive window once
 //                            (hipIpcGetMemHandle / hipIpcOpenMemHandle; xGMI peer access) and the pack kernel
 //                            writes ONLY THE LIVE SLOTS straight into the destination rank's window, then raises
@@ -51,6 +51,7 @@
 #include <vector>
 
 #include "block_scan.h"
+#include "walker_fields.h"
 
 namespace {
 
@@ -190,28 +191,17 @@ __device__ inline bool flag_wait(const unsigned long long *flag, unsigned long l
     return true;
 }
 
-// ---- slot layout: the walker state that has to travel, in 16-byte units ------------------------------------
-// phi | [ghalf] | [phi_old | hist] | [G] | ot ehyb phase eloc | (unscaled, detR) (log_detR, 0) | [ovlp_new] | [bp_ph | (bp_cos, bp_n)]
-struct SlotLayout {
-    long per, hist_per, gsz;
-    int with_greens, with_bp, with_rdm;     // with_rdm: walker.G travels (mixed estimator with one_rdm: the accumulated
-                                            // G is whatever the walker carries, estimators/mixed.py:226-229)
-    __host__ __device__ long size() const {
-        long n = per + 6;
-        if (with_greens) n += per + 1;
-        if (with_bp) n += per + hist_per + 2;
-        if (with_rdm) n += gsz;
-        return n;
-    }
-};
+// ---- exchange slot: one walker in the packed form of its table (walker_fields.h: WalkerFields::packed_bytes), without
+// the weight and without the caches derived from Ghalf.  The buffers are sized for the table with a cached Green's function.
+long max_slot(afq_handle *h) { return walker_fields(h, WF_GREENS).packed_bytes() / (long)sizeof(cplx); }
 
 struct PackArgs {
-    SlotLayout L;
+    WalkerFields f;          // what travels in this event
     int cap, nranks, rank;
     const int *count;        // nsend / nrecv [R]
     const int *idx;          // send_idx / recv_idx [R][cap]
     cplx *buf;               // SENDRECV: sbuf / rbuf [R][cap][slot]; WINDOW unpack: this rank's rbuf
-    long slot;               // elements per slot (>= L.size(), fixed for the buffers)
+    long slot;               // elements per slot (>= f.packed_bytes(), fixed for the buffers)
     // WINDOW transport
     int window;
     PeerWindows pw;          // pack: where peer p's window is mapped
@@ -219,9 +209,6 @@ struct PackArgs {
     unsigned long long seq;  // number of this event
     int *tickets;            // pack: blocks done per peer
     double *scal;            // scal[6]: sticky communication error; scal[7], scal[8]: walkers / bytes sent
-    cplx *phi, *ot, *ehyb, *phase, *eloc, *ghalf, *ovlp_new, *phi_old, *bp_hist, *bp_ph, *G;
-    double *unscaled, *detR, *log_detR, *bp_cos;
-    int *bp_n;
     // unpack: a walker that arrives with a cached Ghalf whose spin blocks differ raises closed_bad to this rank's current
     // epoch (afq_internal.h: the closed-shell verdict of the population must cover what other ranks send); closed_half =
     // na * M elements per spin block, 0 = no check
@@ -246,57 +233,34 @@ __device__ __forceinline__ void comm_pack_body(const PackArgs &a, const int peer
         __syncthreads();
         if (!ok) { if (threadIdx.x == 0 && blockIdx.x == 0) a.scal[6] = 1.0; return; }
     }
-    const long per = a.L.per;
     const long stride = (long)gridDim.x * blockDim.x, t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
     for (int sl = blockIdx.y; sl < count; sl += gridDim.y) {
-        const int w = a.idx[peer * a.cap + sl];
-        cplx *s;
+        const long w = a.idx[peer * a.cap + sl];
+        char *s;
         // window pack: straight into the window of the destination rank, row of this rank; window unpack: this rank's window,
         // row of the source; send / receive buffers otherwise
-        if (a.window && PACK) s = a.wl.rbuf(a.pw.base[peer]) + ((long)a.rank * a.cap + sl) * a.slot;
-        else s = a.buf + ((long)peer * a.cap + sl) * a.slot;
-        auto mv = [&](cplx *field, long n, long off) {
-            for (long i = t0; i < n; i += stride) {
-                if (PACK) s[off + i] = field[(long)w * n + i];
-                else field[(long)w * n + i] = s[off + i];
-            }
-        };
+        if (a.window && PACK) s = (char *)(a.wl.rbuf(a.pw.base[peer]) + ((long)a.rank * a.cap + sl) * a.slot);
+        else s = (char *)(a.buf + ((long)peer * a.cap + sl) * a.slot);
         long off = 0;
-        mv(a.phi, per, off); off += per;
-        if (a.L.with_greens) {
-            mv(a.ghalf, per, off);
-            if (!PACK && a.closed_half) {
+        for (int k = 0; k < a.f.n; ++k) {
+            const WalkerFields::Entry e = a.f.e[k];
+            off = WalkerFields::packed_at(off, e.bytes);
+            if (PACK) walker_field_copy(s + off, e.base + w * e.bytes, e.bytes, t0, stride);
+            else walker_field_copy(e.base + w * e.bytes, s + off, e.bytes, t0, stride);
+            if (!PACK && a.closed_half && k == a.f.ghalf) {
+                const cplx *g = (const cplx *)(s + off);
                 bool differ = false;
                 for (long i = t0; i < a.closed_half; i += stride) {
-                    const cplx x = s[off + i], y = s[off + a.closed_half + i];
+                    const cplx x = g[i], y = g[a.closed_half + i];
                     differ |= __double_as_longlong(x.x) != __double_as_longlong(y.x) || __double_as_longlong(x.y) != __double_as_longlong(y.y);
                 }
                 if (differ) atomicMax(a.closed_bad, a.closed_epoch);
             }
-            off += per;
+            off += e.bytes;
         }
-        if (a.L.with_bp) { mv(a.phi_old, per, off); off += per; mv(a.bp_hist, a.L.hist_per, off); off += a.L.hist_per; }
-        if (a.L.with_rdm) { mv(a.G, a.L.gsz, off); off += a.L.gsz; }
-        if (t0 == 0) {
-            if (PACK) {
-                s[off] = a.ot[w]; s[off + 1] = a.ehyb[w]; s[off + 2] = a.phase[w]; s[off + 3] = a.eloc[w];
-                s[off + 4] = cmake(a.unscaled[w], a.detR[w]);
-                s[off + 5] = cmake(a.log_detR[w], 0.0);
-                long o = off + 6;
-                if (a.L.with_greens) s[o++] = a.ovlp_new[w];
-                if (a.L.with_bp) { s[o++] = a.bp_ph[w]; s[o++] = cmake(a.bp_cos[w], (double)a.bp_n[w]); }
-                if (a.window) {     // traffic statistics: walkers / bytes this rank has written into peer windows
-                    atomicAdd(a.scal + 7, 1.0);
-                    atomicAdd(a.scal + 8, (double)(a.L.size() * (long)sizeof(cplx)));
-                }
-            } else {
-                a.ot[w] = s[off]; a.ehyb[w] = s[off + 1]; a.phase[w] = s[off + 2]; a.eloc[w] = s[off + 3];
-                a.unscaled[w] = s[off + 4].x; a.detR[w] = s[off + 4].y;
-                a.log_detR[w] = s[off + 5].x;
-                long o = off + 6;
-                if (a.L.with_greens) a.ovlp_new[w] = s[o++];
-                if (a.L.with_bp) { a.bp_ph[w] = s[o++]; a.bp_cos[w] = s[o].x; a.bp_n[w] = (int)s[o].y; ++o; }
-            }
+        if (PACK && a.window && t0 == 0) {     // traffic statistics: walkers / bytes this rank has written into peer windows
+            atomicAdd(a.scal + 7, 1.0);
+            atomicAdd(a.scal + 8, (double)((off + 15) & ~15L));
         }
     }
     if (PACK && a.window) {
@@ -505,13 +469,6 @@ void free_buffers(afq_comm_state *c) {
     c->nw = 0;
 }
 
-SlotLayout max_layout(afq_handle *h) {
-    SlotLayout L;
-    L.per = (long)h->M * h->nt; L.hist_per = (long)h->nbp * h->K; L.gsz = 2L * h->M * h->M;
-    L.with_greens = 1; L.with_bp = h->nbp > 0; L.with_rdm = (h->rdm_on && h->G) ? 1 : 0;
-    return L;
-}
-
 bool uses_windows(const afq_comm_state *c) { return c->window || c->win_collectives; }
 
 // Window memory must be coherent between GPUs while kernels run: uncached (what RCCL itself allocates for its peer
@@ -618,7 +575,7 @@ long est_window_doubles(afq_handle *h) { return 2L * AFQ_EST_COUNT_ + 2L * h->M 
 int ensure_buffers(afq_handle *h) {
     afq_comm_state *c = cs_of(h);
     if (c->cap <= 0) c->cap = default_cap(h->nw);
-    const size_t slot = (size_t)max_layout(h).size();
+    const size_t slot = (size_t)max_slot(h);
     if (c->nw == h->nw && c->nbp == h->nbp && c->slot == slot && c->lists) return AFQ_OK;
     AFQ_HIP(h, hipStreamSynchronize(h->stream));
     free_buffers(c);
@@ -661,7 +618,7 @@ int stage_prep(afq_handle *h, double r) {
 
 void fill_pack(afq_handle *h, PackArgs &p, bool with_greens, bool send) {
     afq_comm_state *c = cs_of(h);
-    p.L = max_layout(h); p.L.with_greens = with_greens ? 1 : 0;
+    p.f = walker_fields(h, with_greens ? WF_GREENS : 0);
     p.cap = c->cap; p.nranks = c->nranks; p.rank = c->rank;
     p.count = c->lists + (send ? 0 : c->nranks);
     p.idx = c->lists + 2 * c->nranks + (send ? 0 : c->nranks * c->cap);
@@ -669,9 +626,6 @@ void fill_pack(afq_handle *h, PackArgs &p, bool with_greens, bool send) {
     p.window = c->window ? 1 : 0; p.pw = c->pw; p.wl = c->wl; p.seq = c->seq_x; p.tickets = c->tickets;
     p.scal = h->scal;
     p.buf = c->window ? (send ? nullptr : c->wl.rbuf(c->win)) : (send ? c->sbuf : c->rbuf);
-    p.phi = h->phi; p.ot = h->ot; p.ehyb = h->ehyb; p.phase = h->phase; p.eloc = h->eloc; p.ghalf = h->ghalf;
-    p.ovlp_new = h->ovlp_new; p.phi_old = h->phi_old; p.bp_hist = h->bp_hist; p.bp_ph = h->bp_ph; p.G = h->G;
-    p.unscaled = h->unscaled; p.detR = h->detR; p.log_detR = h->log_detR; p.bp_cos = h->bp_cos; p.bp_n = h->bp_n;
     p.closed_bad = h->closed_bad; p.closed_epoch = h->closed_epoch; p.closed_half = 0;
 }
 
@@ -747,7 +701,7 @@ int ensure_group(afq_handle **hs, int n) {
     for (int i = 0; i < n; ++i) {
         afq_comm_state *c = cs_of(hs[i]);
         hipSetDevice(hs[i]->device);
-        const bool had = c->lists && c->nw == hs[i]->nw && c->nbp == hs[i]->nbp && c->slot == (size_t)max_layout(hs[i]).size();
+        const bool had = c->lists && c->nw == hs[i]->nw && c->nbp == hs[i]->nbp && c->slot == (size_t)max_slot(hs[i]);
         const int rc = ensure_buffers(hs[i]);
         if (rc) return rc;
         fresh = fresh || !had;

@@ -12,6 +12,7 @@
 #include "lds_dma.h"
 
 #include "block_scan.h"
+#include "walker_fields.h"
 #define NTHR 256
 
 // --------------------------------------------------------------------------
@@ -1854,24 +1855,9 @@ __global__ __launch_bounds__(256) void comb_plan_kernel(double *weight, double *
 }
 
 struct CloneArgs {
-    long per;
-    cplx *phi, *ot, *ehyb, *phase, *eloc;
-    double *unscaled, *detR, *log_detR;
+    WalkerFields f;      // what travels with a walker (walker_fields.h), never the weight
     const int *pairs;
     const double *scal;
-    // back-propagation state travels with the walker (walkers/walker.py:89-90); null when off
-    cplx *phi_old, *bp_hist, *bp_ph;
-    double *bp_cos;
-    int *bp_n;
-    long hist_per;
-    // a cached Green's function travels too; null when there is none
-    cplx *ghalf, *ovlp_new;
-    cplx *G;             // walker.G as walker state (mixed one_rdm); null otherwise
-    long gsz;
-    cplx *gsum;          // Ghalf_a + Ghalf_b of the force bias, kept in step with ghalf; null when it is not current
-    long gsum_per;
-    cplx *gdiag;         // Hubbard: diag(G) partial sums, kept in step with ghalf; null when they are not current
-    long gdiag_per;
     double *weight;      // single-rank comb: every weight back to 1 (handler.py:337-338) in this launch; null otherwise
     int nw;
 };
@@ -1883,34 +1869,11 @@ __global__ void clone_kernel(CloneArgs a) {
         if (wr < a.nw) a.weight[wr] = 1.0;
     }
     if (pr >= (int)a.scal[1]) return;
-    const int src = a.pairs[2 * pr], dst = a.pairs[2 * pr + 1];
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < a.per; i += (long)gridDim.x * blockDim.x)
-        a.phi[dst * a.per + i] = a.phi[src * a.per + i];
-    if (a.ghalf) {
-        for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < a.per; i += (long)gridDim.x * blockDim.x)
-            a.ghalf[dst * a.per + i] = a.ghalf[src * a.per + i];
-        if (blockIdx.x == 0 && threadIdx.x == 0) a.ovlp_new[dst] = a.ovlp_new[src];
-    }
-    if (a.gsum)
-        for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < a.gsum_per; i += (long)gridDim.x * blockDim.x)
-            a.gsum[dst * a.gsum_per + i] = a.gsum[src * a.gsum_per + i];
-    if (a.gdiag)
-        for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < a.gdiag_per; i += (long)gridDim.x * blockDim.x)
-            a.gdiag[dst * a.gdiag_per + i] = a.gdiag[src * a.gdiag_per + i];
-    if (a.G)
-        for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < a.gsz; i += (long)gridDim.x * blockDim.x)
-            a.G[dst * a.gsz + i] = a.G[src * a.gsz + i];
-    if (a.phi_old) {
-        for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < a.per; i += (long)gridDim.x * blockDim.x)
-            a.phi_old[dst * a.per + i] = a.phi_old[src * a.per + i];
-        for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < a.hist_per; i += (long)gridDim.x * blockDim.x)
-            a.bp_hist[dst * a.hist_per + i] = a.bp_hist[src * a.hist_per + i];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        a.ot[dst] = a.ot[src]; a.ehyb[dst] = a.ehyb[src]; a.phase[dst] = a.phase[src];
-        a.eloc[dst] = a.eloc[src]; a.unscaled[dst] = a.unscaled[src]; a.detR[dst] = a.detR[src];
-        a.log_detR[dst] = a.log_detR[src];
-        if (a.phi_old) { a.bp_ph[dst] = a.bp_ph[src]; a.bp_cos[dst] = a.bp_cos[src]; a.bp_n[dst] = a.bp_n[src]; }
+    const long src = a.pairs[2 * pr], dst = a.pairs[2 * pr + 1];
+    const long t0 = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+    for (int k = 0; k < a.f.n; ++k) {
+        const WalkerFields::Entry e = a.f.e[k];
+        walker_field_copy(e.base + dst * e.bytes, e.base + src * e.bytes, e.bytes, t0, stride);
     }
 }
 
@@ -1981,16 +1944,9 @@ int k_clone_pairs(afq_handle *h, bool with_greens, bool reset_weights) {
     const bool sum_too = with_greens && h->gf.gsum.current(h->gf), diag_too = with_greens && h->gf.gdiag.current(h->gf);
     h->gf.cloned(with_greens ? GreensCache::SUM | GreensCache::DIAG | GreensCache::CLOSED : 0);
     CloneArgs a;
-    a.gdiag = diag_too ? h->gdiag : nullptr; a.gdiag_per = 2L * h->gdiag_parts * h->M;
-    a.gsum = sum_too ? h->ghalf_sum : nullptr; a.gsum_per = (long)h->na * h->M;
-    a.weight = reset_weights ? h->weight : nullptr; a.nw = h->nw;
-    a.per = (long)h->M * h->nt; a.phi = h->phi; a.ot = h->ot; a.ehyb = h->ehyb; a.phase = h->phase;
-    a.eloc = h->eloc; a.unscaled = h->unscaled; a.detR = h->detR; a.log_detR = h->log_detR;
+    a.f = walker_fields(h, (with_greens ? WF_GREENS : 0) | (sum_too ? WF_GSUM : 0) | (diag_too ? WF_GDIAG : 0));
     a.pairs = (const int *)h->pack_tmp; a.scal = h->scal;
-    a.phi_old = h->nbp > 0 ? h->phi_old : nullptr; a.bp_hist = h->bp_hist; a.bp_ph = h->bp_ph; a.bp_cos = h->bp_cos;
-    a.bp_n = h->bp_n; a.hist_per = (long)h->nbp * h->K;
-    a.ghalf = with_greens ? h->ghalf : nullptr; a.ovlp_new = h->ovlp_new;
-    a.G = (h->rdm_on && h->G) ? h->G : nullptr; a.gsz = 2L * h->M * h->M;
+    a.weight = reset_weights ? h->weight : nullptr; a.nw = h->nw;
     // (grid.y * 256 threads of the x == 0 blocks cover every walker for the weight reset)
     AFQ_LAUNCH(h, clone_kernel, dim3(4, (h->nw + 1) / 2), dim3(256), 0, h->stream, a);
     AFQ_POST(h);

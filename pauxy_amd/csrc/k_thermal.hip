@@ -352,17 +352,6 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_rdm_kernel(const double *G
     if (tid == 0) nav[w] = red[0];
 }
 
-// the comb's clones bring G and their bins along: (src, dst) pairs of comb_plan_kernel, count in scal[1]
-__global__ void thermal_clone_kernel(double *G, double *stack, long gper, long sper, const int *pairs, const double *scal) {
-    const int pr = blockIdx.y;
-    if (pr >= (int)scal[1]) return;
-    const int src = pairs[2 * pr], dst = pairs[2 * pr + 1];
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < gper; i += (long)gridDim.x * blockDim.x)
-        G[dst * gper + i] = G[src * gper + i];
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < sper; i += (long)gridDim.x * blockDim.x)
-        stack[dst * sper + i] = stack[src * sper + i];
-}
-
 int th_need(afq_handle *h) {
     if (!h->th_on || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, "thermal walkers: afq_thermal_configure first");
     if (h->prop_pending) AFQ_FAIL(h, AFQ_ESTATE, "a step is half done: afq_propagate_finish first");
@@ -391,14 +380,6 @@ int th_launch_greens(afq_handle *h, const double *stack, double *G, int first, i
 
 int k_thermal_greens(afq_handle *h, int slice_ix) {
     return th_launch_greens(h, h->th_stack, h->th_G, th_first_bin(h, slice_ix), -1, 2 * h->nw);
-}
-
-int k_thermal_clone(afq_handle *h) {
-    const long gper = 2L * h->M * h->M;
-    AFQ_LAUNCH(h, thermal_clone_kernel, dim3(8, (h->nw + 1) / 2), dim3(256), 0, h->stream, h->th_G, h->th_stack, gper,
-               gper * h->th_nbins, (const int *)h->pack_tmp, h->scal);
-    AFQ_POST(h);
-    return AFQ_OK;
 }
 
 extern "C" {
