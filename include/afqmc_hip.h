@@ -376,6 +376,15 @@ int afq_exchange_algorithm(afq_handle *h, int *mode_out);
 int afq_set_propagator_closed_form(afq_handle *h, int mode);
 int afq_propagator_closed_form(afq_handle *h, int *mode_out);
 
+/* A step announced with afq_estimates_fuse_next and run by afq_propagate (begin and finish in one call) ends in a Green's
+ * function of which only the overlaps and the spin sum of Ghalf are kept.  In the shape class of the resident closed-shell
+ * propagator (above; single determinant, hybrid weights with force bias, no back-propagation window, no RDM) that evaluation,
+ * with the weight update, runs as the tail of the propagator's own launch:
+ *   0  never: two launches, as every other step
+ *   1  tail behind the propagator as it is (4-multiplication Taylor products): the same bits as mode 0
+ *   2  (default) tail behind the resident body with 3-multiplication Taylor products: the same result to rounding      */
+int afq_set_step_fusion(afq_handle *h, int mode);
+
 /* Force bias of a multi-determinant trial (propagation/generic.py:154-157, walkers/multi_det.py:283-290) has two
  * device algorithms with the same result:
  *   1  one half-rotated contraction per determinant, rchol_d^T vec(Ghalf_d), averaged with the weights

@@ -822,8 +822,23 @@ static int force_bias(afq_handle *h, bool with_xbar = true) {
 static int local_energy(afq_handle *h);
 static int local_energy_dets(afq_handle *h);
 
+// Whether THIS step runs its closing Green's function (with the overlap and the weight update) as the tail of the fused
+// propagator's launch: begin and finish in one call (the weight update needs the energy shift), announced with
+// afq_estimates_fuse_next, of the resident closed-shell shape class, and of the kind whose closing evaluation may skip the
+// per-spin store (afq_propagate_finish, GreensRequest::may_skip_store) -- the tail leaves overlap + spin sum behind, nothing
+// else.  Every other step runs the two launches.
+static bool step_fuses(afq_handle *h) {
+    return h->step_one_call && h->step_fusion_mode != 0 && h->fuse_est_req && h->gf.enabled && h->ndet == 1 &&
+           h->kind == AFQ_SYS_GENERIC && (h->flags & AFQ_PROP_HYBRID) && (h->flags & AFQ_PROP_FORCE_BIAS) &&
+           !(h->flags & AFQ_PROP_FREE_PROJECTION) && !h->rdm_on && h->nbp == 0 && h->psi_stride == 0 && !h->hirsch &&
+           !k_greens_big_supported(h) && k_fb_use_sum(h) && k_step_fusion_shape(h);
+}
+
 int afq_propagate(afq_handle *h, const double *xi, double eshift_re, double eshift_im) {
+    if (h) { h->step_one_call = true; h->step_eshift = cmake(eshift_re, eshift_im); }
     const int rc = afq_propagate_begin(h, xi);
+    if (h) h->step_one_call = false;
+    if (rc && h) h->step_tail_done = false;
     return rc ? rc : afq_propagate_finish(h, eshift_re, eshift_im);
 }
 
@@ -933,7 +948,19 @@ int afq_propagate_begin(afq_handle *h, const double *xi) {
     h->vhs_upper = fused && h->hs_sym;
     { PhaseTimer t(h, T_VHS); rc = build_vhs(h); }                                  // :161
     if (rc) { h->vhs_upper = false; return rc; }
-    if (fused) {
+    if (fused && step_fuses(h)) {
+        PhaseTimer t(h, T_EXP);                                                     // :251, :162-171, :258, :261-292
+        // the closing evaluation of afq_propagate_finish, asked for here with the same request and run by the propagator's launch
+        GreensRequest req;
+        req.ride_weight = true;
+        req.eshift = h->step_eshift;
+        req.may_skip_store = true;
+        h->step_tail_res = GreensResult();
+        rc = k_prop_fused_greens(h, req, &h->step_tail_res, h->step_fusion_mode == 2);
+        h->vhs_upper = false;
+        if (rc) return rc;
+        h->step_tail_done = true;
+    } else if (fused) {
         PhaseTimer t(h, T_EXP);                                                     // :251, :162-171, :258
         rc = k_prop_fused(h);
         h->vhs_upper = false;
@@ -965,7 +992,12 @@ int afq_propagate_finish(afq_handle *h, double eshift_re, double eshift_im) {
         GreensResult res;
         req.ride_weight = h->ndet == 1 && !le_msd;          // single determinant: k_greens may take the weight update along
         req.eshift = cmake(eshift_re, eshift_im);
-        if (h->gf.enabled && !fp) {
+        if (h->step_tail_done) {
+            // (the propagator's launch has evaluated it: overlap, spin sum and weight update, per-spin store skipped)
+            h->step_tail_done = false;
+            res = h->step_tail_res;
+            h->gf.keep(res.store_skipped ? GreensCache::SUM_ONLY : GreensCache::FULL);
+        } else if (h->gf.enabled && !fp) {
             // afq_estimates_fuse_next told us that nothing but the next step's force bias will read this Green's function
             // (no comb, no energy, no block end behind this step): when that force bias contracts the spin sum
             // Ghalf_a + Ghalf_b (k_fb_use_sum), the per-spin Ghalf -- 2/3 of the kernel's stores, 20 MB per step at C3 --
@@ -1096,6 +1128,12 @@ int afq_set_exchange_algorithm(afq_handle *h, int mode) {
 int afq_set_propagator_closed_form(afq_handle *h, int mode) {
     if (!h || mode < 0 || mode > 2) return AFQ_EINVAL;
     h->prop_closed_mode = mode;
+    return AFQ_OK;
+}
+
+int afq_set_step_fusion(afq_handle *h, int mode) {
+    if (!h || mode < 0 || mode > 2) return AFQ_EINVAL;
+    h->step_fusion_mode = mode;
     return AFQ_OK;
 }
 

@@ -76,6 +76,7 @@ struct afq_handle {
     bool atil_unavailable = false;  // automatic mode: Atil did not fit when it was to be built -> T-intermediate kernel
     bool rchol_same = false;        // alpha and beta blocks of rchol are bitwise equal
     int exx_mode = 0;               // afq_set_exchange_algorithm: 0 auto, 1 T-intermediate (exx_kernel), 2 quadratic form
+    int step_fusion_mode = 2;       // afq_set_step_fusion: 0 never, 1 tail behind the 4-multiplication body, 2 behind the 3-multiplication one
     int prop_closed_mode = 0;       // afq_set_propagator_closed_form: 0 auto, 1 streamed deal, 2 V resident in registers (where eligible)
     cplx *exq_y = nullptr;          // [2 * slices, nw, ceil(N M / 16)] per-tile partial sums of the quadratic form
     size_t exq_y_len = 0;
@@ -285,6 +286,11 @@ struct afq_handle {
     double *gfrag = nullptr;        // Ghalf in MFMA fragment order (energy kernel B operand)
     size_t gfrag_len = 0;
     bool prop_pending = false;                      // afq_propagate_begin done, afq_propagate_finish outstanding
+    // afq_propagate (begin and finish in one call): the energy shift is known while the propagator is launched, which may then
+    // take the step's closing Green's function along as its tail; step_tail_done tells the finish half that it has, with what result
+    bool step_one_call = false, step_tail_done = false;
+    cplx step_eshift = {0.0, 0.0};
+    GreensResult step_tail_res;
     double *est_stage = nullptr;                    // mapped host memory: estimator sums + scal[4] + sequence number
     unsigned long long est_seq = 0;
     double scal_cache[AFQ_NSCAL] = {0};   // scal[] as of the last afq_estimates_get_end; stale after a population control
@@ -518,7 +524,12 @@ int k_full_G(afq_handle *h);                                // G = conj(psi) gha
 // k_fused.hip
 int k_prop_fused_supported(afq_handle *h);
 int k_prop_closed_resident(afq_handle *h);
-int k_prop_fused(afq_handle *h);                           // phi <- B exp(V) B phi for live walkers, in place
+struct GreensLaunch;
+// phi <- B exp(V) B phi for live walkers, in place; with `tail` (k_prop_fused_greens, k_small.hip) the Green's function, overlap and weight
+// update of EVERY walker's new phi behind it in the same launch, the resident closed-shell body with 3-multiplication Taylor
+// products when mul3
+int k_prop_fused(afq_handle *h, const GreensLaunch *tail = nullptr, bool mul3 = false);
+int k_step_fusion_shape(afq_handle *h);                    // the shape class whose announced steps run the tail
 // k_hirsch.hip
 int k_hirsch_alive(afq_handle *h, int mode);
 int k_hirsch_kinetic(afq_handle *h);
@@ -580,6 +591,8 @@ int k_msd_energy_combine(afq_handle *h);                   // energy_all, detw -
 int k_update_weight(afq_handle *h, cplx eshift);
 struct WeightArgs;
 WeightArgs k_weight_args(afq_handle *h, cplx eshift);       // the weight update's operands, for the kernels it rides on
+// the fused propagator with the step's closing Green's function (k_greens into ovlp_new, as req asks) as the tail of its launch
+int k_prop_fused_greens(afq_handle *h, const GreensRequest &req, GreensResult *res, bool mul3);
 int k_reortho(afq_handle *h, cplx *keep = nullptr, bool *keep_done = nullptr);
 int k_cap_weights(afq_handle *h, double frac, double total_weight);
 int k_comb(afq_handle *h, double r, double target, bool with_greens = false);

@@ -17,7 +17,8 @@
 //     lane-linear ds_write_b128.  Both images lie below the operand ring of the streamed body (2 * KS * 2 KB <= NCH * 8 KB).
 //   * the one-body passes stream the real parts of BH1 (8 bytes per lane and k-step, L2 resident, shared by all walkers)
 //     into registers ahead of their k loop: two real products per slot.
-//   * the Taylor products are plain 4-multiplication complex products (re = P1 - P2 at the end, im accumulated in one
+//   * the Taylor products are plain 4-multiplication complex products (MUL3, launches with the Green's function tail: the
+//     3-multiplication form of taylor(), im = P3 - P1 - P2) (re = P1 - P2 at the end, im accumulated in one
 //     register set): k ascending in steps of 4, T_n = product / n, sum += T_n as in taylor().  Four MFMAs per k-step and slot
 //     where taylor()'s 3-multiplication form has three: see DESIGN section 4 for why this body pays them.
 // Rows and k >= M read a zero page: the padding of T stays zero through every product.
@@ -25,7 +26,7 @@
 
 #define PCR_LDS(p) ((__attribute__((address_space(3))) unsigned char *)(p))
 
-template <int KS>
+template <int KS, bool MUL3>
 __device__ __attribute__((always_inline)) inline void prop_closed_resident(const PropFusedArgs &a, unsigned char *smem_,
                                                                            cplx *phi, const cplx *vhs) {
     auto *smem = PCR_LDS(smem_);
@@ -127,10 +128,18 @@ __device__ __attribute__((always_inline)) inline void prop_closed_resident(const
                 for (int j = 0; j < 2; ++j) {
                     // (both halves of the imaginary part go into one accumulator, two independent MFMAs apart)
                     const d2_t b = *(const lds_d2 *)(tb + (s * 2 + j) * 1024);
-                    P3[j] = mfma16(av[s][0], b[1], P3[j]);
-                    P1[j] = mfma16(av[s][0], b[0], P1[j]);
-                    P2[j] = mfma16(av[s][1], b[1], P2[j]);
-                    P3[j] = mfma16(av[s][1], b[0], P3[j]);
+                    if constexpr (MUL3) {
+                        // taylor()'s form: P1 = ar br, P2 = ai bi, P3 = (ar + ai)(br + bi); the sums are made here, per k-step,
+                        // so that no fragment of V needs a third resident register
+                        P1[j] = mfma16(av[s][0], b[0], P1[j]);
+                        P2[j] = mfma16(av[s][1], b[1], P2[j]);
+                        P3[j] = mfma16(av[s][0] + av[s][1], b[0] + b[1], P3[j]);
+                    } else {
+                        P3[j] = mfma16(av[s][0], b[1], P3[j]);
+                        P1[j] = mfma16(av[s][0], b[0], P1[j]);
+                        P2[j] = mfma16(av[s][1], b[1], P2[j]);
+                        P3[j] = mfma16(av[s][1], b[0], P3[j]);
+                    }
                 }
             }
             // T_n = product / n is the next right-hand operand; after the last term the image receives the SUM instead
@@ -140,7 +149,7 @@ __device__ __attribute__((always_inline)) inline void prop_closed_resident(const
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     re[j][q] = (P1[j][q] - P2[j][q]) * inv_n;
-                    im[j][q] = P3[j][q] * inv_n;
+                    im[j][q] = (MUL3 ? P3[j][q] - P1[j][q] - P2[j][q] : P3[j][q]) * inv_n;
                     SR[j][q] += re[j][q]; SI[j][q] += im[j][q];
                 }
             if (n == a.order) put(cur ^ TB, SR, SI);

@@ -737,6 +737,11 @@ class AfqDevice(object):
         afq_set_propagator_closed_form)."""
         self._ck(self.lib.afq_set_propagator_closed_form(self.h, int(mode)))
 
+    def set_step_fusion(self, mode):
+        """An announced step's closing Green's function as the tail of the propagator's launch: 0 never, 1 behind the
+        4-multiplication body (the bits of 0), 2 behind the 3-multiplication resident body (default; see afq_set_step_fusion)."""
+        self._ck(self.lib.afq_set_step_fusion(self.h, int(mode)))
+
     def propagator_closed_form(self):
         m = ctypes.c_int()
         self._ck(self.lib.afq_propagator_closed_form(self.h, ctypes.byref(m)))
