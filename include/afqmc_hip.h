@@ -75,6 +75,12 @@ enum afq_field {
     AFQ_F_LOG_DETR = 13,
     AFQ_F_THERMAL_G = 14,       /* f64[2, M, M], thermal walkers (afq_thermal_configure); get and set      */
     AFQ_F_THERMAL_STACK = 15,   /* f64[nbins, 2, M, M], thermal walkers; get, and set for unit tests        */
+    /* after afq_thermal_configure_continuous THERMAL_G and THERMAL_STACK are c128 of the same shapes, and there are: */
+    AFQ_F_THERMAL_RIGHT = 16,   /* c128[2, M, M] product of the slices of the current bin                  */
+    AFQ_F_THERMAL_M0 = 17,      /* c128[2] det G_s the next weight update divides by                        */
+    AFQ_F_THERMAL_DET = 18,     /* c128[2] det G_s of the last Green's function evaluation (get only: a set is refused) */
+    AFQ_F_CMF = 19,             /* c128: the mean-field and ...                                              */
+    AFQ_F_CFB = 20,             /* ... force-bias factors of the last field kernel (get only: a set is refused) */
     AFQ_F_COUNT_
 };
 
@@ -616,6 +622,45 @@ int afq_thermal_propagate(afq_handle *h, const double *u, int32_t *fields_out, d
 int afq_thermal_greens(afq_handle *h, int slice_ix);
 int afq_thermal_energy(afq_handle *h, double *E_out, double *nav_out);
 int afq_thermal_state(afq_handle *h, int32_t *out4);
+
+/* ---- finite-temperature AFQMC with continuous fields: thermal walkers of the uniform electron gas -----------
+ * thermal_propagation/planewave.py:219-276,445-517, walkers/stack.py:299-324, walkers/thermal.py of the reference:
+ * PlaneWave with the phaseless constraint and the force bias, OneBody trial density matrix (diagonal for plane
+ * waves), full-rank walkers.  The walker's matrices are complex: AFQ_F_THERMAL_G c128[2, M, M], AFQ_F_THERMAL_STACK
+ * c128[nbins, 2, M, M], AFQ_F_THERMAL_RIGHT, AFQ_F_THERMAL_M0; the comb, afq_walkers_copy and the pack carry all four.
+ * M <= 47 plane waves: the complex Green's function keeps 4 matrices of 16 M (M | 1) bytes in the 160 KiB of LDS of
+ * a work-group (the shells 7, 19, 27, 33 fit, 57 does not).
+ *   afq_thermal_configure_continuous  after afq_set_system_ueg (index lists over ALL plane waves, for the energy) and
+ *                          afq_walkers_alloc; no trial determinant, no afq_set_propagator.  BT, BT_inv, BH1
+ *                          f64[2, M, M]: the trial's dmat and its inverse (diagonal) and
+ *                          expm(-dt/2 h1e_mod + dt/2 mu) of which the diagonal is read, as the reference reads it;
+ *                          mf_shift c128[K]; dt becomes the handle's time step; a component of the force bias with
+ *                          |xbar| > fb_bound (the reference's default: 1.0) is scaled to unit modulus (counted in
+ *                          afq_counters [0]).  The exponential is the degree-6 polynomial.  options:
+ *                          AFQ_THERMAL_* bits of what the caller was asked for, refused by name.  Ends with
+ *                          afq_thermal_reset.  AFQ_EUNSUPPORTED: the option bits, a system that is not the UEG,
+ *                          M > 47 (the message carries M and the bytes), a trial that is not diagonal, more than
+ *                          one rank, back-propagation / ITCF / mixed RDM on the handle.
+ *   afq_thermal_propagate_continuous  one time slice of every walker, dead ones included: P = I - G^T,
+ *                          xbar = -sqrt(dt) P.[iA | iB] (|xbar_i| > fb_bound: unit modulus), xs = xi - xbar, cmf = -sqrt(dt) xs.mf_shift,
+ *                          cfb = xi.xbar - xbar.xbar / 2, VHS = sqrt(dt) (iA xs[:nq] + iB xs[nq:]),
+ *                          B_s = diag(BH1_s) (sum_{n <= 6} VHS^n / n!) diag(BH1_s); right_s <- B_s right_s (right = I
+ *                          at the first slice of a bin), bin[block]_s = left_k right_s with
+ *                          left_k = BT^stack_size BT_inv^k after the k-th slice of the bin;
+ *                          G_s = [I + bin[nbins - 1] .. bin[0]]^-1, Mnew_s = det G_s;
+ *                          oratio = M0_up M0_dn / (Mnew_up Mnew_dn), hyb = log(oratio) + cfb + cmf,
+ *                          magn = |exp(hyb)|; a zero denominator or a magn that is not finite (NaN included): weight = 0, M0 kept; else
+ *                          weight *= magn max(0, cos Im(hyb - cfb)) and M0 = Mnew.  xi f64[nw, K], or NULL for the
+ *                          device's Philox stream; xi_out f64[nw, K] (may be NULL): the fields used.
+ *   afq_thermal_reset / _greens / _energy / _state serve this kind of handle too.  reset also sets right = I; it leaves
+ *   M0 alone, as the reference's Walkers.reset does (the first slice of the next path divides by the determinant the
+ *   last path ended with); only afq_thermal_configure_continuous sets M0 = det of the trial's G.  greens leaves
+ *   det G_s in AFQ_F_THERMAL_DET; energy is the UEG energy of P_s = I - G_s^T (real parts) and
+ *   nav = Re(tr P_up + tr P_down).                                                                             */
+int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_size, double dt, const double *BT,
+                                     const double *BT_inv, const double *BH1, const double *mf_shift, double fb_bound,
+                                     int options);
+int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi_out);
 
 /* ---- misc ------------------------------------------------------------------ */
 /* Device stream of auxiliary fields (used by afq_propagate with xi == NULL; replaces numpy.random.normal of

@@ -20,7 +20,8 @@ ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, 
 AFQ_SYS_GENERIC, AFQ_SYS_HUBBARD, AFQ_SYS_UEG = 1, 2, 3
 AFQ_PROP_HYBRID, AFQ_PROP_FORCE_BIAS, AFQ_PROP_FREE_PROJECTION, AFQ_PROP_HUBBARD_SPIN = 1, 2, 4, 8
 (F_PHI, F_WEIGHT, F_UNSCALED_WEIGHT, F_OT, F_HYBRID_ENERGY, F_PHASE, F_DETR, F_ELOC, F_GHALF, F_G,
- F_XBAR, F_XSHIFTED, F_ENERGY, F_LOG_DETR, F_THERMAL_G, F_THERMAL_STACK) = range(16)
+ F_XBAR, F_XSHIFTED, F_ENERGY, F_LOG_DETR, F_THERMAL_G, F_THERMAL_STACK, F_THERMAL_RIGHT, F_THERMAL_M0,
+ F_THERMAL_DET, F_CMF, F_CFB) = range(21)
 THERMAL_CHARGE, THERMAL_FREE_PROJECTION, THERMAL_LOW_RANK, THERMAL_AVERAGE_GF = 1, 2, 4, 8
 AFQ_EINVAL, AFQ_ESTATE, AFQ_EUNSUPPORTED = -1, -2, -5
 
@@ -151,6 +152,8 @@ SIGNATURES = {
     "afq_thermal_greens": [_h, c_int],
     "afq_thermal_energy": [_h, _dp, _dp],
     "afq_thermal_state": [_h, c_void_p],
+    "afq_thermal_configure_continuous": [_h, c_int, c_int, c_double, _dp, _dp, _dp, _dp, c_double, c_int],
+    "afq_thermal_propagate_continuous": [_h, _dp, _dp],
 }
 
 

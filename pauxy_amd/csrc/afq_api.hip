@@ -657,8 +657,17 @@ static int field_info(afq_handle *h, int field, void **base, size_t *bytes) {
     case AFQ_F_XSHIFTED: *base = h->xs; *bytes = (size_t)h->K * sizeof(cplx); break;
     case AFQ_F_ENERGY: *base = h->energy; *bytes = 3 * sizeof(cplx); break;
     case AFQ_F_LOG_DETR: *base = h->log_detR; *bytes = sizeof(double); break;
-    case AFQ_F_THERMAL_G: *base = h->th_G; *bytes = (size_t)2 * h->M * h->M * sizeof(double); break;
-    case AFQ_F_THERMAL_STACK: *base = h->th_stack; *bytes = (size_t)2 * h->M * h->M * h->th_nbins * sizeof(double); break;
+    case AFQ_F_THERMAL_G:
+        if (h->th_on && h->th_cplx) { *base = h->thc_G; *bytes = (size_t)2 * h->M * h->M * sizeof(cplx); break; }
+        *base = h->th_G; *bytes = (size_t)2 * h->M * h->M * sizeof(double); break;
+    case AFQ_F_THERMAL_STACK:
+        if (h->th_on && h->th_cplx) { *base = h->thc_stack; *bytes = (size_t)2 * h->M * h->M * h->th_nbins * sizeof(cplx); break; }
+        *base = h->th_stack; *bytes = (size_t)2 * h->M * h->M * h->th_nbins * sizeof(double); break;
+    case AFQ_F_THERMAL_RIGHT: *base = h->th_on && h->th_cplx ? h->thc_right : nullptr; *bytes = (size_t)2 * h->M * h->M * sizeof(cplx); break;
+    case AFQ_F_THERMAL_M0: *base = h->th_on && h->th_cplx ? h->thc_M0 : nullptr; *bytes = 2 * sizeof(cplx); break;
+    case AFQ_F_THERMAL_DET: *base = h->th_on && h->th_cplx ? h->thc_det : nullptr; *bytes = 2 * sizeof(cplx); break;
+    case AFQ_F_CMF: *base = h->cmf; *bytes = sizeof(cplx); break;
+    case AFQ_F_CFB: *base = h->cfb; *bytes = sizeof(cplx); break;
     default: AFQ_FAIL(h, AFQ_EINVAL, "unknown walker field");
     }
     if (!*base) AFQ_FAIL(h, AFQ_ESTATE, "walker field not allocated (afq_walkers_alloc / afq_greens first)");
@@ -672,6 +681,8 @@ int afq_walkers_set(afq_handle *h, int field, const void *host, int first, int c
     if (!h || !host) return AFQ_EINVAL;
     if (!h->nw) AFQ_FAIL(h, AFQ_ESTATE, "no walkers allocated");
     if (first < 0 || count < 0 || first + count > h->nw) AFQ_FAIL(h, AFQ_EINVAL, "walker range out of bounds");
+    if (field == AFQ_F_THERMAL_DET || field == AFQ_F_CMF || field == AFQ_F_CFB)
+        AFQ_FAIL(h, AFQ_EINVAL, "afq_walkers_set: a result of the last kernel, not walker state (get only)");
     hipSetDevice(h->device);
     void *base; size_t bytes;
     int rc = field_info(h, field, &base, &bytes);

@@ -234,6 +234,20 @@ struct afq_handle {
     double *th_u = nullptr;         // [nw, M] uniforms of the slice
     int *th_fields = nullptr;       // [nw, M] chosen fields (-1: both probabilities vanished)
     double *th_nav = nullptr;       // [nw]
+    // continuous fields, UEG (k_thermal_cplx.hip; thermal_propagation/planewave.py): the walker's matrices are complex
+    bool th_cplx = false;           // afq_thermal_configure_continuous done (th_on too): thc_* are the walkers' state
+    cplx *thc_G = nullptr;          // [nw, 2, M, M]
+    cplx *thc_G0 = nullptr;         // [2, M, M] the trial's G
+    cplx *thc_stack = nullptr;      // [nw, nbins, 2, M, M]
+    cplx *thc_right = nullptr;      // [nw, 2, M, M] product of the slices of the current bin
+    cplx *thc_M0 = nullptr;         // [nw, 2] det G_s the weight update divides by
+    cplx *thc_M00 = nullptr;        // [2] the trial's
+    cplx *thc_det = nullptr;        // [nw, 2] det G_s of the last evaluation
+    cplx *thc_mf = nullptr;         // [K] mean-field shift
+    double thc_fb_bound = 1.0;      // |xbar_i| above it is scaled to unit modulus
+    double *thc_BTpow = nullptr;    // [2, M] diagonal of BT^stack_size
+    double *thc_left = nullptr;     // [stack_size, 2, M] diagonal of left_k = BT^stack_size BT_inv^(k + 1)
+    double *thc_bh1 = nullptr;      // [2, M] diagonal of BH1
 
     // ---- propagator
     bool have_prop = false;
@@ -659,6 +673,10 @@ int k_ueg_sf_wsum(afq_handle *h, const cplx *two_dev, int n, const cplx *wt_c, c
 int k_energy_hubbard_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *E_dev);   // estimators/hubbard.py:93-114
 // k_thermal.hip
 int k_thermal_greens(afq_handle *h, int slice_ix);          // th_G of every walker from its stack
+// k_thermal_cplx.hip
+int k_thermal_c_greens(afq_handle *h, int slice_ix);        // thc_G and thc_det of every walker from its stack
+int k_thermal_c_reset(afq_handle *h, bool with_m0);         // with_m0: M0 <- the trial's (a fresh population)
+int k_thermal_c_energy(afq_handle *h, double *E_out, double *nav_out);
 // k_corr.hip: <n_is n_jt> and <S+_i S-_j> of full Green's functions G_dev [n, 2, M, M] -> out_dev [n, 5, M, M], and
 // their weighted sum over n -> out_dev [5, M, M] (Green's functions of weight zero left out), in index order
 int k_corr_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *out_dev);

@@ -353,7 +353,7 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_rdm_kernel(const double *G
 }
 
 int th_need(afq_handle *h) {
-    if (!h->th_on || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, "thermal walkers: afq_thermal_configure first");
+    if (!h->th_on || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, "thermal walkers: afq_thermal_configure or afq_thermal_configure_continuous first");
     if (h->prop_pending) AFQ_FAIL(h, AFQ_ESTATE, "a step is half done: afq_propagate_finish first");
     hipSetDevice(h->device);
     return AFQ_OK;
@@ -388,7 +388,7 @@ int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int n
                           const double *BT_inv, const double *BH1, const double *auxf, int options) {
     AFQ_API(h, "afq_thermal_configure");
     if (!h) return AFQ_EINVAL;
-    h->th_on = false;
+    h->th_on = false; h->th_cplx = false;
     if (!BT || !BT_inv || !BH1 || !auxf) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure: null operand");
     if (options & AFQ_THERMAL_CHARGE) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: charge_decomposition is not supported (spin decomposition only)");
     if (options & AFQ_THERMAL_FREE_PROJECTION) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: free_projection is not supported (constrained path only)");
@@ -440,6 +440,7 @@ int afq_thermal_reset(afq_handle *h) {
     AFQ_API(h, "afq_thermal_reset");
     if (!h) return AFQ_EINVAL;
     AFQ_TRY(th_need(h));
+    if (h->th_cplx) return k_thermal_c_reset(h, false);
     const int M = h->M, nbins = h->th_nbins;
     const long per = 2L * M * M;
     // the trial's G once, from walker 0's fresh bins (every bin is BT^stack_size), then broadcast
@@ -458,13 +459,14 @@ int afq_thermal_greens(afq_handle *h, int slice_ix) {
     if (!h) return AFQ_EINVAL;
     AFQ_TRY(th_need(h));
     if (slice_ix < 0 || slice_ix > h->th_L) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_greens: slice_ix outside 0 .. ntime_slices");
-    return k_thermal_greens(h, slice_ix);
+    return h->th_cplx ? k_thermal_c_greens(h, slice_ix) : k_thermal_greens(h, slice_ix);
 }
 
 int afq_thermal_propagate(afq_handle *h, const double *u, int32_t *fields_out, double eshift) {
     AFQ_API(h, "afq_thermal_propagate");
     if (!h) return AFQ_EINVAL;
     AFQ_TRY(th_need(h));
+    if (h->th_cplx) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_propagate: continuous fields are configured (afq_thermal_propagate_continuous)");
     if (!u) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_propagate: the uniforms f64[nw, M] are needed");
     if (h->th_slice >= h->th_L) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_propagate: the path is complete (afq_thermal_reset starts the next)");
     const int M = h->M;
@@ -500,6 +502,7 @@ int afq_thermal_energy(afq_handle *h, double *E_out, double *nav_out) {
     if (!h) return AFQ_EINVAL;
     AFQ_TRY(th_need(h));
     if (!E_out && !nav_out) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_energy: nothing asked for");
+    if (h->th_cplx) return k_thermal_c_energy(h, E_out, nav_out);
     AFQ_LAUNCH(h, thermal_rdm_kernel, dim3(h->nw), dim3(TH_THREADS), 0, h->stream, h->th_G, h->G, h->th_nav, h->M);
     AFQ_POST(h);
     AFQ_TRY(k_energy_hubbard_full_g(h, h->G, h->nw, h->energy));

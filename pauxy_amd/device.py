@@ -341,8 +341,12 @@ class AfqDevice(object):
             L.F_GHALF: ((nt, M), numpy.complex128), L.F_G: ((2, M, M), numpy.complex128),
             L.F_XBAR: ((K,), numpy.complex128), L.F_XSHIFTED: ((K,), numpy.complex128),
             L.F_ENERGY: ((3,), numpy.complex128), L.F_LOG_DETR: ((), numpy.float64),
-            L.F_THERMAL_G: ((2, M, M), numpy.float64),
-            L.F_THERMAL_STACK: ((getattr(self, 'thermal_nbins', 0), 2, M, M), numpy.float64),
+            L.F_THERMAL_G: ((2, M, M), getattr(self, 'thermal_dtype', numpy.float64)),
+            L.F_THERMAL_STACK: ((getattr(self, 'thermal_nbins', 0), 2, M, M), getattr(self, 'thermal_dtype', numpy.float64)),
+            L.F_THERMAL_RIGHT: ((2, M, M), numpy.complex128),
+            L.F_THERMAL_M0: ((2,), numpy.complex128),
+            L.F_THERMAL_DET: ((2,), numpy.complex128),
+            L.F_CMF: ((), numpy.complex128), L.F_CFB: ((), numpy.complex128),
         }[field]
 
     def set(self, field, values, first=0):
@@ -368,6 +372,27 @@ class AfqDevice(object):
         self._ck(self.lib.afq_thermal_configure(self.h, int(ntime_slices), int(stack_size), int(nstblz), _p(BT),
                                                 _p(BT_inv), _p(BH1), _p(auxf), int(options)))
         self.thermal_nbins = int(ntime_slices) // int(stack_size)
+        self.thermal_dtype = numpy.float64
+
+    def thermal_configure_continuous(self, ntime_slices, stack_size, dt, BT, BT_inv, BH1, mf_shift, fb_bound=1.0,
+                                     options=0):
+        """UEG with continuous fields: the walkers' G and bins are complex from here on."""
+        M = self.M
+        BT, BT_inv, BH1 = _f64(BT, (2, M, M)), _f64(BT_inv, (2, M, M)), _f64(BH1, (2, M, M))
+        mf_shift = _c128(mf_shift, (self.K,))
+        self._ck(self.lib.afq_thermal_configure_continuous(self.h, int(ntime_slices), int(stack_size), float(dt), _p(BT),
+                                                           _p(BT_inv), _p(BH1), _p(mf_shift), float(fb_bound),
+                                                           int(options)))
+        self.thermal_nbins = int(ntime_slices) // int(stack_size)
+        self.thermal_dtype = numpy.complex128
+
+    def thermal_propagate_continuous(self, xi=None, fetch_fields=False):
+        """One slice of every walker; xi [nw, K] or None for the device's stream.  -> the fields used, when asked for."""
+        if xi is not None:
+            xi = _f64(xi, (self.nw, self.K))
+        out = numpy.empty((self.nw, self.K), dtype=numpy.float64) if fetch_fields else None
+        self._ck(self.lib.afq_thermal_propagate_continuous(self.h, _p(xi), _p(out)))
+        return out
 
     def thermal_reset(self):
         self._ck(self.lib.afq_thermal_reset(self.h))

@@ -117,7 +117,7 @@ class UEG(object):
     ``full_lists=True`` builds them over all ``nbasis`` plane waves (the reference's ``thermal: True`` lists and nothing
     else of that option): the complete pair sums for any Green's function."""
 
-    def __init__(self, rs, nup, ndown, ecut, full_lists=False):
+    def __init__(self, rs, nup, ndown, ecut, full_lists=False, mu=None):
         self.name = "UEG"
         self.nup, self.ndown = nup, ndown
         self.nelec = (nup, ndown)
@@ -125,7 +125,7 @@ class UEG(object):
         self.ecut = ecut
         self.ktwist = numpy.zeros(3)
         self.control_variate = False
-        self.mu = None
+        self.mu = mu                    # chemical potential of a finite-temperature run (systems/ueg.py:54)
         self.thermal = False
         self.sparse = True
         self.diagH1 = True
@@ -283,5 +283,5 @@ def get_system(sys_opts):
                        t=sys_opts.get('t', 1.0), mu=sys_opts.get('mu', None))
     if name == 'UEG':
         return UEG(sys_opts['rs'], sys_opts['nup'], sys_opts['ndown'], sys_opts['ecut'],
-                   full_lists=sys_opts.get('full_lists', False))
+                   full_lists=sys_opts.get('full_lists', sys_opts.get('thermal', False)), mu=sys_opts.get('mu', None))
     raise ValueError("unrecognized system name {}".format(name))

@@ -2,13 +2,16 @@
 and walkers/thermal.py, walkers/stack.py of the reference).
 
 A thermal walker is its Green's function G [2, M, M] and a stack of propagator products; both live in the library
-(k_thermal.hip).  ``walkers[i]`` are light views with the members the reference's driver and estimators read
-(``weight``, ``G``, ``stack_size``, ``stack_length``, ``local_energy``, ``greens_function``)."""
+(k_thermal.hip: Hubbard, discrete fields, real matrices; k_thermal_cplx.hip: UEG, continuous fields, complex matrices,
+and with them the running product of the current bin and M0 = det G).  ``walkers[i]`` are light views with the members
+the reference's driver and estimators read (``weight``, ``G``, ``M0``, ``stack``, ``stack_size``, ``stack_length``,
+``local_energy``, ``greens_function``)."""
 import numpy
 
 from pauxy_amd import _lib as L
 from pauxy_amd.context import get_context, hidden
 from pauxy_amd.propagation.thermal_hubbard import thermal_constants
+from pauxy_amd.propagation.thermal_planewave import MAX_BASIS, planewave_constants
 from pauxy_amd.trial_density import update_stack
 
 
@@ -46,6 +49,18 @@ class ThermalWalkerView(object):
         self._h.ensure_configured()
         return self._h.dev.get(L.F_THERMAL_G, self.index, 1)[0]
 
+    @property
+    def M0(self):
+        """det G_s the next weight update divides by (UEG, continuous fields)."""
+        self._h.ensure_configured()
+        return self._h.dev.get(L.F_THERMAL_M0, self.index, 1)[0]
+
+    @property
+    def stack(self):
+        """The walker's bins [nbins, 2, M, M]."""
+        self._h.ensure_configured()
+        return self._h.dev.get(L.F_THERMAL_STACK, self.index, 1)[0]
+
     def greens_function(self, trial, slice_ix=None, inplace=True):
         """walkers/thermal.py:90-95 -- for the whole population (the library moves every walker together)."""
         if not inplace:
@@ -73,8 +88,10 @@ class ThermalWalkers(object):
             raise NotImplementedError("thermal walkers: more than one rank is not supported")
         if nbp is not None or nprop_tot is not None:
             raise NotImplementedError("thermal walkers: no back-propagation or ITCF with a thermal trial")
-        if system.name != "Hubbard":
-            raise NotImplementedError("thermal walkers: Hubbard systems only (no Generic / UEG)")
+        if system.name not in ("Hubbard", "UEG"):
+            raise NotImplementedError("thermal walkers: Hubbard systems only (no Generic / UEG) with discrete fields, and "
+                                      "the UEG with continuous fields; %s has no thermal path" % system.name)
+        self.continuous = system.name == "UEG"
         if not hasattr(trial, 'dmat_inv'):
             raise NotImplementedError("thermal walkers: a OneBody trial density matrix is needed (no MeanField)")
         if walker_opts.get('low_rank', False):
@@ -83,6 +100,9 @@ class ThermalWalkers(object):
         if self.pcont_method != 'comb':
             raise NotImplementedError("thermal walkers: population control '%s' is not supported (pair_branch "
                                       "included): comb only" % self.pcont_method)
+        if self.continuous and system.nbasis > MAX_BASIS:
+            raise NotImplementedError("thermal walkers: M = %d > %d plane waves is not supported (the complex Green's "
+                                      "function keeps a walker's working set in LDS)" % (system.nbasis, MAX_BASIS))
         if system.nbasis > 64:
             raise NotImplementedError("thermal walkers: M = %d > 64 sites is not supported" % system.nbasis)
         self.nwalkers = qmc.nwalkers
@@ -117,12 +137,15 @@ class ThermalWalkers(object):
         self.time_slice = 0
         self.path_index = 0
         self.configured_nstblz = None
+        self.configured_fb_bound = None         # (continuous fields: what the library's configuration is keyed on)
         self._prop = None
         self.last_parent_ix = None
         self.walkers = [ThermalWalkerView(self, i) for i in range(self.nw)]
 
     def ensure_configured(self, prop=None):
         """The library is configured on first use: the propagator's stabilisation period decides when it is known."""
+        if self.continuous:
+            return self._ensure_configured_continuous(prop)
         nstblz = self.nstblz if prop is None else prop.nstblz
         if self.configured_nstblz == nstblz:
             return
@@ -133,6 +156,23 @@ class ThermalWalkers(object):
                                    BH1, auxf)
         self.configured_nstblz = nstblz
         self.nstblz = nstblz
+
+    def _ensure_configured_continuous(self, prop):
+        """UEG: the propagator's constants (BH1, mf_shift, fb_bound) go to the library with the trial's; without a
+        propagator yet (a walker's G read first) they are the defaults the propagator would compute.  A propagator
+        whose fb_bound differs from what was configured configures the library again: allowed only at time slice 0, and
+        it starts the population afresh (bins, G, right, weights, and M0 = the trial's; anything set on the walkers
+        before is lost)."""
+        fb_bound = 1.0 if prop is None else prop.fb_bound
+        if self.configured_fb_bound is not None and (prop is None or self.configured_fb_bound == fb_bound):
+            return
+        if self.configured_fb_bound is not None and self.time_slice != 0:
+            raise RuntimeError("thermal walkers: the propagator's fb_bound changed in the middle of a path")
+        BH1, mf_shift = (prop.BH1, prop.mf_shift) if prop is not None else planewave_constants(self.system, self.trial,
+                                                                                                self.dt)
+        self.dev.thermal_configure_continuous(self.num_slices, self.stack_size, self.dt, self.trial.dmat,
+                                              self.trial.dmat_inv, BH1, mf_shift, fb_bound)
+        self.configured_fb_bound = fb_bound
 
     def set_total_weight(self, total_weight):
         self.total_weight = total_weight

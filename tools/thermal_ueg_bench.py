@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Cost of the finite-temperature UEG path with continuous fields (k_thermal_cplx.hip) per time slice: rs = 1, ecut = 2
+(M = 33 plane waves, 512 fields), 2 + 2 electrons, mu = 0.245, beta = 1 in 20 slices of dt = 0.05, OneBody trial, stack_size
+5 (4 bins), 256 walkers.  Prints one JSON line (and writes it to --out).
+
+The kernels are timed with event pairs around every launch (afq_launch_trace) over `--paths` whole paths after
+`--warmup` paths; the fields come from the host (numpy), as in a run.  Per kernel: launches, total and mean ms.
+  thermal_crdm_kernel      P = I - G^T of every walker
+  vbias_ueg_lds_kernel     the plane-wave force bias of P (k_models.hip)
+  thermal_cfields_kernel   clip, shifted fields, cmf, cfb
+  vhs_ueg_kernel           the plane-wave HS potential (k_models.hip)
+  thermal_cslice_kernel    BV by five Horner products, B, right <- B right, the bin
+  thermal_cgreens_kernel   the complex stratified G of all bins and det G (every slice, and once per reset)
+  thermal_cweight_kernel   the phaseless weight update
+`slice_ms` = all of them over the slices run; `path_wall_ms` the host's wall time of a path, fields and copies included
+(median and spread over the paths), taken in a separate pass without the event pairs.
+
+  python tools/thermal_ueg_bench.py [--paths 5] [--warmup 2] [--ecut 2.0] [--stack-size 5] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from pauxy_amd import _lib as L                                                 # noqa: E402
+from pauxy_amd.device import AfqDevice                                          # noqa: E402
+from pauxy_amd.propagation.thermal_planewave import planewave_constants        # noqa: E402
+from pauxy_amd.systems import UEG                                               # noqa: E402
+from pauxy_amd.trial_density import OneBody                                     # noqa: E402
+
+KERNELS = ('thermal_crdm_kernel', 'vbias_ueg_lds_kernel', 'thermal_cfields_kernel', 'vhs_ueg_kernel',
+           'thermal_cslice_kernel', 'thermal_cgreens_kernel', 'thermal_cweight_kernel')
+
+
+def one_path(dev, rng, nslices, M00):
+    dev.thermal_reset()
+    dev.set(L.F_THERMAL_M0, M00)
+    for _ in range(nslices):
+        dev.thermal_propagate_continuous(rng.normal(size=(dev.nw, dev.K)))
+    dev.sync()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--ecut', type=float, default=2.0)
+    ap.add_argument('--walkers', type=int, default=256)
+    ap.add_argument('--beta', type=float, default=1.0)
+    ap.add_argument('--dt', type=float, default=0.05)
+    ap.add_argument('--stack-size', type=int, default=5)
+    ap.add_argument('--paths', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    s = UEG(1.0, 2, 2, a.ecut, full_lists=True, mu=0.245)
+    trial = OneBody(s, a.beta, a.dt)
+    nslices = trial.num_slices
+    BH1, mf_shift = planewave_constants(s, trial, a.dt)
+    dev = AfqDevice(0)
+    dev.set_system_ueg(s.iA, s.iB, s.ikpq_i, s.ikpq_kpq, s.ipmq_i, s.ipmq_pmq, s.vqvec, s.vol,
+                       numpy.array([s.H1[0].diagonal(), s.H1[1].diagonal()]), s.ecore, s.nup, s.ndown)
+    dev.walkers_alloc(a.walkers)
+    dev.thermal_configure_continuous(nslices, a.stack_size, a.dt, trial.dmat, trial.dmat_inv, BH1, mf_shift)
+    M00 = dev.get(L.F_THERMAL_M0)
+    rng = numpy.random.RandomState(5)
+    for _ in range(a.warmup):
+        one_path(dev, rng, nslices, M00)
+    wall = []
+    for _ in range(a.paths):
+        t0 = time.perf_counter()
+        one_path(dev, rng, nslices, M00)
+        wall.append((time.perf_counter() - t0) * 1e3)
+    dev.launch_trace(True)
+    for _ in range(a.paths):
+        one_path(dev, rng, nslices, M00)
+    trace = dev.launch_trace_get()
+    dev.launch_trace(False)
+    res = {'system': 'UEG rs=1 ecut=%g 2+2 mu=0.245' % a.ecut, 'M': s.nbasis, 'fields': s.nfields, 'walkers': a.walkers,
+           'beta': a.beta, 'dt': a.dt, 'slices': nslices, 'stack_size': a.stack_size, 'nbins': nslices // a.stack_size,
+           'trial_mu': trial.mu, 'paths': a.paths, 'kernels': {}}
+    total = 0.0
+    for k in KERNELS:
+        n, ms = trace.get(k, (0, 0.0))
+        res['kernels'][k] = {'launches': n, 'total_ms': ms, 'mean_ms': ms / n if n else 0.0}
+        total += ms
+    res['slice_ms'] = total / (a.paths * nslices)
+    res['path_wall_ms'] = {'median': float(numpy.median(wall)), 'min': float(min(wall)), 'max': float(max(wall))}
+    E, nav = dev.thermal_energy()
+    res['finite'] = bool(numpy.all(numpy.isfinite(E)) and numpy.all(numpy.isfinite(nav)))
+    dev.close()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == '__main__':
+    main()
