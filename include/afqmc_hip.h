@@ -390,6 +390,13 @@ int afq_propagator_closed_form(afq_handle *h, int *mode_out);
  *   1  tail behind the propagator as it is (4-multiplication Taylor products): the same bits as mode 0
  *   2  (default) tail behind the resident body with 3-multiplication Taylor products: the same result to rounding      */
 int afq_set_step_fusion(afq_handle *h, int mode);
+/* Which steps of that shape class run the tail (modes 1 and 2 keep their meaning: the body behind which it runs):
+ *   0  (default) announced steps run by afq_propagate only
+ *   1  every afq_propagate and afq_propagate_begin.  An unannounced step's tail stores the per-spin Ghalf as well; the
+ *      tail of afq_propagate_begin, which does not know the energy shift, leaves the weight update to
+ *      afq_propagate_finish (one weight_kernel launch).
+ * AFQ_EINVAL for any other value.                                                                                   */
+int afq_set_step_fusion_scope(afq_handle *h, int scope);
 
 /* Force bias of a multi-determinant trial (propagation/generic.py:154-157, walkers/multi_det.py:283-290) has two
  * device algorithms with the same result:

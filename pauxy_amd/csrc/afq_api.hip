@@ -838,8 +838,12 @@ static int local_energy_dets(afq_handle *h);
 // afq_estimates_fuse_next, of the resident closed-shell shape class, and of the kind whose closing evaluation may skip the
 // per-spin store (afq_propagate_finish, GreensRequest::may_skip_store) -- the tail leaves overlap + spin sum behind, nothing
 // else.  Every other step runs the two launches.
+// afq_set_step_fusion_scope(1) drops the first two conditions: an unannounced step's tail stores the per-spin Ghalf too (the
+// request afq_propagate_finish would have made), and the tail of a begin without a finish in the same call evaluates Green's
+// function and overlap only -- the shift is not known yet -- and leaves the weight update to afq_propagate_finish.
 static bool step_fuses(afq_handle *h) {
-    return h->step_one_call && h->step_fusion_mode != 0 && h->fuse_est_req && h->gf.enabled && h->ndet == 1 &&
+    const bool in_scope = h->step_fusion_scope == 1 || (h->step_one_call && h->fuse_est_req);
+    return in_scope && h->step_fusion_mode != 0 && h->gf.enabled && h->ndet == 1 &&
            h->kind == AFQ_SYS_GENERIC && (h->flags & AFQ_PROP_HYBRID) && (h->flags & AFQ_PROP_FORCE_BIAS) &&
            !(h->flags & AFQ_PROP_FREE_PROJECTION) && !h->rdm_on && h->nbp == 0 && h->psi_stride == 0 && !h->hirsch &&
            !k_greens_big_supported(h) && k_fb_use_sum(h) && k_step_fusion_shape(h);
@@ -962,10 +966,12 @@ int afq_propagate_begin(afq_handle *h, const double *xi) {
     if (fused && step_fuses(h)) {
         PhaseTimer t(h, T_EXP);                                                     // :251, :162-171, :258, :261-292
         // the closing evaluation of afq_propagate_finish, asked for here with the same request and run by the propagator's launch
+        // (scope 1: without the shift -- begin alone -- the weight update stays with finish; unannounced, somebody may read
+        //  the per-spin Ghalf)
         GreensRequest req;
-        req.ride_weight = true;
-        req.eshift = h->step_eshift;
-        req.may_skip_store = true;
+        req.ride_weight = h->step_one_call;
+        if (h->step_one_call) req.eshift = h->step_eshift;
+        req.may_skip_store = h->fuse_est_req;
         h->step_tail_res = GreensResult();
         rc = k_prop_fused_greens(h, req, &h->step_tail_res, h->step_fusion_mode == 2);
         h->vhs_upper = false;
@@ -1004,7 +1010,8 @@ int afq_propagate_finish(afq_handle *h, double eshift_re, double eshift_im) {
         req.ride_weight = h->ndet == 1 && !le_msd;          // single determinant: k_greens may take the weight update along
         req.eshift = cmake(eshift_re, eshift_im);
         if (h->step_tail_done) {
-            // (the propagator's launch has evaluated it: overlap, spin sum and weight update, per-spin store skipped)
+            // (the propagator's launch has evaluated it: overlap and spin sum; the per-spin store unless the step was announced
+            //  ahead of it; the weight update unless begin ran without the shift -- weight_rode is false then and it runs below)
             h->step_tail_done = false;
             res = h->step_tail_res;
             h->gf.keep(res.store_skipped ? GreensCache::SUM_ONLY : GreensCache::FULL);
@@ -1145,6 +1152,12 @@ int afq_set_propagator_closed_form(afq_handle *h, int mode) {
 int afq_set_step_fusion(afq_handle *h, int mode) {
     if (!h || mode < 0 || mode > 2) return AFQ_EINVAL;
     h->step_fusion_mode = mode;
+    return AFQ_OK;
+}
+
+int afq_set_step_fusion_scope(afq_handle *h, int scope) {
+    if (!h || scope < 0 || scope > 1) return AFQ_EINVAL;
+    h->step_fusion_scope = scope;
     return AFQ_OK;
 }
 

@@ -77,6 +77,7 @@ struct afq_handle {
     bool rchol_same = false;        // alpha and beta blocks of rchol are bitwise equal
     int exx_mode = 0;               // afq_set_exchange_algorithm: 0 auto, 1 T-intermediate (exx_kernel), 2 quadratic form
     int step_fusion_mode = 2;       // afq_set_step_fusion: 0 never, 1 tail behind the 4-multiplication body, 2 behind the 3-multiplication one
+    int step_fusion_scope = 0;      // afq_set_step_fusion_scope: 0 announced one-call steps, 1 every step of the shape class
     int prop_closed_mode = 0;       // afq_set_propagator_closed_form: 0 auto, 1 streamed deal, 2 V resident in registers (where eligible)
     cplx *exq_y = nullptr;          // [2 * slices, nw, ceil(N M / 16)] per-tile partial sums of the quadratic form
     size_t exq_y_len = 0;

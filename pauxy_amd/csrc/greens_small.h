@@ -1,6 +1,6 @@
 // Green's function / overlap of one walker with at most 45 electrons per spin, as device code: the body of
-// greens_small_kernel (k_small.hip), which the fused propagator (k_fused.hip) also runs as the tail of its own launch on an
-// announced step -- one work-group of 512 threads per walker in both, the same code and the same bits.
+// greens_small_kernel (k_small.hip), which the fused propagator (k_fused.hip) also runs as the tail of its own launch on the
+// steps afq_set_step_fusion_scope names -- one work-group of 512 threads per walker in both, the same code and the same bits.
 #pragma once
 #include <type_traits>
 #include "mfma_gemm.h"

@@ -138,13 +138,13 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
 #undef PF_LEAVE
 }
 
-// The same with the step's closing Green's function as its tail (an announced step of the resident shape class, see
-// afq_propagate): behind whichever body the walker took -- or none, a dead walker's overlap is evaluated like any other -- every
+// The same with the step's closing Green's function as its tail (a step of the resident shape class, see step_fuses in
+// afq_api.hip): behind whichever body the walker took -- or none, a dead walker's overlap is evaluated like any other -- every
 // wave waits for its stores of phi, one barrier makes them the work-group's, and greens_small_body runs on the same dynamic
-// LDS: the walker's new phi, both overlap matrices, their inverses, the spin sum of Ghalf and the weight update, as
-// greens_small_kernel<true, true> with the same arguments would leave them.  A walker of the resident body is closed by
-// construction (one result stored to both spin blocks) and skips the tail's compare.  A separate overload, not a flag of the
-// kernel above: that one keeps its signature, its code and its registers.
+// LDS: the walker's new phi, both overlap matrices, their inverses, Ghalf (its spin sum alone on an announced step) and the
+// weight update where the shift is known, as greens_small_kernel<true, true> with the same arguments would leave them.  A
+// walker of the resident body is closed by construction (one result stored to both spin blocks) and skips the tail's compare.
+// A separate overload, not a flag of the kernel above: that one keeps its signature, its code and its registers.
 template <bool NARROW, int FULL, bool TAIL, bool MUL3>
 __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a, GreensArgs ga, WeightArgs wa) {
     static_assert(TAIL && !NARROW && FULL == 7, "the tail rides on the full wide deal only");
@@ -233,7 +233,9 @@ int k_prop_fused(afq_handle *h, const GreensLaunch *tail, bool mul3) {
         if (tail) {
             // ... and the tail's (greens_small_body, n <= 32): the overlap matrix as (n / 16)^2 tiles per spin over the k-steps of M
             // in whole groups of four, two multiplications per k-step against a real trial, else three; O^-1 phi^T as (n / 16) x
-            // (M / 16) tiles per spin over ceil(n / 4) k-steps of three.  A closed walker evaluates one spin.
+            // (M / 16) tiles per spin over ceil(n / 4) k-steps of three.  A closed walker evaluates one spin.  (The same count
+            // whether the tail stores the per-spin Ghalf or not and whether the weight update rides: those are stores and
+            // one thread's scalar arithmetic, no MFMA.)
             const double t16 = (h->na + 15) / 16, m16 = (h->M + 15) / 16;
             const double ks1 = 4.0 * (((h->M + 3) / 4 + 3) / 4), ks3 = (h->na + 3) / 4;
             const double spin = 2048.0 * (t16 * t16 * ks1 * (tail->a.psi_real ? 2.0 : 3.0) + t16 * m16 * ks3 * 3.0);

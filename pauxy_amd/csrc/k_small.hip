@@ -462,11 +462,12 @@ static int launch_greens(afq_handle *h, cplx *ghalf, cplx *det, int only_alive, 
 
 // The end-of-step evaluation (Ghalf of the propagated walkers, their overlaps into ovlp_new) filled here and run by the fused
 // propagator as the tail of its launch; the caller (afq_api.hip) has checked that the step is one the tail serves, and this
-// confirms what the fill granted.
+// confirms what the fill granted: the kernel the tail is (greens_small_body<true, true>) and the spin sum the next force bias
+// contracts.  The per-spin store and the weight update ride or not, as requested (run-time fields of the arguments).
 int k_prop_fused_greens(afq_handle *h, const GreensRequest &req, GreensResult *res, bool mul3) {
     GreensLaunch gl;
     AFQ_TRY(greens_fill(h, h->ghalf, h->ovlp_new, 0, nullptr, req, res, gl));
-    if (gl.path != GreensLaunch::SMALL || !gl.wgj || gl.tiny || !gl.inverse || !gl.a.skip_spin || !gl.a.gsum || !res->weight_rode)
+    if (gl.path != GreensLaunch::SMALL || !gl.wgj || gl.tiny || !gl.inverse || !gl.a.gsum || res->weight_rode != req.ride_weight)
         AFQ_FAIL(h, AFQ_ESTATE, "internal: the fused step's Green's function is not the one the propagator's tail evaluates");
     return k_prop_fused(h, &gl, mul3);
 }

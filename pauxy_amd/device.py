@@ -767,6 +767,11 @@ class AfqDevice(object):
         4-multiplication body (the bits of 0), 2 behind the 3-multiplication resident body (default; see afq_set_step_fusion)."""
         self._ck(self.lib.afq_set_step_fusion(self.h, int(mode)))
 
+    def set_step_fusion_scope(self, scope):
+        """Which steps of the shape class run that tail: 0 announced propagate() calls only (default), 1 every propagate()
+        and propagate_begin() (see afq_set_step_fusion_scope)."""
+        self._ck(self.lib.afq_set_step_fusion_scope(self.h, int(scope)))
+
     def propagator_closed_form(self):
         m = ctypes.c_int()
         self._ck(self.lib.afq_propagator_closed_form(self.h, ctypes.byref(m)))

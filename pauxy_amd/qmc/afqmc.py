@@ -225,6 +225,10 @@ class AFQMC(object):
                    and not mixed.structure_factor and not self.psi.write_restart)
         begun = False
         try:
+            # every step of this loop, announced or not, split or not, may end in the propagator's own launch -- unless the
+            # loop was told to announce nothing (ride_estimates off): it then queues the kernels of run(), bit for bit
+            if getattr(self, 'ride_estimates', True):
+                dev.set_step_fusion_scope(1)
             for step in range(first_step, first_step + n):
                 # one rank, a block ends here and the next step's head is enqueued before the host waits: the update's summation
                 # launch hands the sums over itself (afq_estimates_update_publish)
@@ -274,6 +278,7 @@ class AFQMC(object):
             raise
         finally:
             dev.set_weight_cap(0.0)                     # the cap must not stay armed on the shared handle
+            dev.set_step_fusion_scope(0)                # (nor the scope widened)
         return eshift
 
     def finalise(self, verbose=False):
