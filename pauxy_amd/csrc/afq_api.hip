@@ -637,6 +637,13 @@ int afq_walkers_alloc(afq_handle *h, int nw) {
     AFQ_HIP(h, hipMemset(h->ghalf, 0, sizeof(cplx) * per * n));
     AFQ_HIP(h, hipMemset(h->energy, 0, sizeof(cplx) * 3 * n));
     AFQ_HIP(h, hipMemset(h->xi, 0, sizeof(double) * K * n));
+    // fields_kernel writes the force bias, the shifted fields and their constant factors of the walkers it propagates only: a
+    // walker that is dead from the start reads back zeros (AFQ_F_XBAR, AFQ_F_XSHIFTED), and the HS potential of its slot is
+    // built from zeros, not from whatever the allocation held
+    AFQ_HIP(h, hipMemset(h->xbar, 0, sizeof(cplx) * K * n));
+    AFQ_HIP(h, hipMemset(h->xs, 0, sizeof(cplx) * K * n));
+    AFQ_HIP(h, hipMemset(h->cmf, 0, sizeof(cplx) * n));
+    AFQ_HIP(h, hipMemset(h->cfb, 0, sizeof(cplx) * n));
     return AFQ_OK;
 }
 

@@ -170,11 +170,13 @@ def summary(verdicts):
 # ---------------------------------------------------------------------------------------------------------------------
 # populations
 # ---------------------------------------------------------------------------------------------------------------------
-def population(model, nw, amax, xi_big, seed, closed=False, philox=None):
+def population(model, nw, amax, xi_big, seed, closed=False, philox=None, mixed=False):
     """nw walkers psi + a_w * noise (complex normal, the same for both spins when ``closed``) with a_w graded from 0 to
     amax over the live walkers; every fifth walker starts dead (weight 0) and one more sits at 5e-9, below the 1e-8 the
     driver propagates.  Fields of two steps: standard normals, scaled by 0.05 / 1 / ``xi_big`` in turn over the live
-    walkers; with ``philox`` = (seed, stream) the numbers the device draws itself at counters 0 and 1 (no scaling then)."""
+    walkers; with ``philox`` = (seed, stream) the numbers the device draws itself at counters 0 and 1 (no scaling then).
+    ``mixed``: every third walker from index 1 is opened -- 0.05 * complex normal noise on its beta block, from a stream
+    of its own behind every other draw, so that no other case sees it."""
     rng = numpy.random.RandomState(seed)
     M, na, nt, K = model.M, model.na, model.na + model.nb, model.nfields
     centre = getattr(model, 'centre', model.psi)
@@ -202,6 +204,10 @@ def population(model, nw, amax, xi_big, seed, closed=False, philox=None):
     else:
         xi = [device_normals_fast(nw * K, philox[0], philox[1], c).reshape(nw, K) for c in range(2)]
     ehyb0 = rng.normal(size=nw) + 0.1j * rng.normal(size=nw)
+    if mixed:
+        own = numpy.random.RandomState(seed + 1000)
+        for i in range(1, nw, 3):
+            phis[i, :, na:] += 0.05 * (own.normal(size=(M, nt - na)) + 1j * own.normal(size=(M, nt - na)))
     return phis, weights, xi, ehyb0
 
 
@@ -215,7 +221,7 @@ CASES = {}
 def _case(name, **kw):
     spec = dict(seed=11, closed=False, hybrid=True, philox=None, cap=None, overflow=False, bp=None, checks=ALL,
                 kernels=(), absent=(), msd_fb_mode=0, eshift=0.0,
-                closed_deal=False)
+                closed_deal=False, mixed=False)
     spec.update(kw)
     CASES[name] = spec
 
@@ -247,7 +253,7 @@ def build(name):
     spec = CASES[name]
     model = _model(spec)
     phis, weights, xi, ehyb0 = population(model, spec['nw'], spec['amax'], spec['xi_big'], spec['seed'],
-                                          spec['closed'], spec['philox'])
+                                          spec['closed'], spec['philox'], spec['mixed'])
     ehyb0 = ehyb0 + spec['eshift']
     if spec['overflow']:
         # exp(-dt (0.5 (e + e_old) - eshift)): e_old = -1e6 -> inf (weight 0 by the isinf branch), +1e6 -> 0 (weight 0,
@@ -363,7 +369,7 @@ HUB_SPIN = _hubbard(4, 2, 3, 1, True)
 UEG = dict(kind='ueg', rs=8.0, na=7, nb=7, ecut=1.0, dt=128.0)
 P = dict(amax=0.5, xi_big=2.0)
 H = dict(amax=3.0, xi_big=3.0)
-# generic Hamiltonians, one determinant: the four kernels the weight update is inlined into
+# generic Hamiltonians, one determinant: four of the five kernels the weight update is inlined into (the fifth: ``tail-*``)
 _case('tiny-open', model=TINY, nw=20, eshift=-100.0, kernels=('greens_tiny_kernel', 'prop_fused_kernel'), **P)
 _case('tiny-open-noshift', model=TINY, nw=20, eshift=0.0, checks=('fb', 'kill'), kernels=('greens_tiny_kernel',), **P)
 _case('wgj-closed', model=WGJ, nw=33, eshift=-85.0, closed=True, bp=2,
@@ -405,3 +411,25 @@ _case('c3-closed', model=_generic(100, 12, 25, 25, closed=True, dt=0.01, top=0.0
       closed_deal=True, kernels=('greens_small_kernel<true, true>', 'prop_fused_kernel'), **C3)
 _case('c3-open', model=_generic(100, 12, 25, 25, dt=0.01, top=0.0), nw=16, eshift=-52.0,
       kernels=('greens_small_kernel<true, true>', 'prop_fused_kernel'), **C3)
+# the shape class whose steps close as the tail of the fused propagator's launch (k_step_fusion_shape: real RHF trial, one
+# real BH1, na == nb in 17..32, M in 97..104) with more than 32 walkers (the spin-sum force bias): its corners -- 25 and 26
+# k-steps, the emptiest and the fullest second column slot, row tile 6 with 4, 1 and 8 live rows.  Unannounced steps in the
+# default scope run the two launches (tests/test_gpu_constraint_edges.py); tests/test_gpu_constraint_tail.py takes the same
+# populations through the tail on every route to it.  ``mixed``: open walkers beside resident ones in the same launch;
+# ``tail-bp``: a back-propagation window, with which no step may fuse.
+def _tail(M, N):
+    return _generic(M, 12, N, N, closed=True)
+
+
+TAIL = dict(closed=True, kernels=('greens_small_kernel<true, true>', 'prop_fused_kernel'),
+            absent=('prop_fused_kernel<false, 7, true',), **P)
+_case('tail-100-25', model=_tail(100, 25), nw=33, eshift=-224.6, closed_deal=True, **TAIL)
+_case('tail-97-17', model=_tail(97, 17), nw=33, eshift=-158.2, closed_deal=True, **TAIL)
+_case('tail-104-32', model=_tail(104, 32), nw=33, eshift=-261.9, closed_deal=True, **TAIL)
+_case('tail-cap', model=_tail(100, 25), nw=65, eshift=-212.2, cap=(0.02, 60.0), closed_deal=True, **TAIL)
+_case('tail-philox', model=_tail(100, 25), nw=33, eshift=-183.5, philox=(2024, 3), closed_deal=True, **TAIL)
+_case('tail-overflow', model=_tail(100, 25), nw=33, eshift=0.0, overflow=True, checks=('fb',), closed_deal=True, **TAIL)
+_case('tail-mixed', model=_tail(100, 25), nw=33, eshift=-202.3, mixed=True, **TAIL)
+_case('tail-bp', model=_tail(100, 25), nw=33, eshift=-224.6, bp=2, closed_deal=True, **TAIL)
+# the cases of the shape class whose steps fuse (everything but the back-propagation window)
+TAIL_FUSING = ('tail-100-25', 'tail-97-17', 'tail-104-32', 'tail-cap', 'tail-philox', 'tail-overflow', 'tail-mixed')

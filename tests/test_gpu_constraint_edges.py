@@ -1,7 +1,11 @@
 """The decision branches of the phaseless constraint on every path of the step: the force-bias bound (both copies of the
 clipping, host fields, device Philox fields, the Hubbard variant that builds its site factors from the clipped field), both
 sides of the hybrid / local-energy bound and the no-bound rule for eshift = 0, the phase kill, infinite and vanishing
-importance functions, the weight cap behind a kill -- in each of the kernels the weight update is inlined into.
+importance functions, the weight cap behind a kill -- in each of the kernels the weight update is inlined into:
+greens_tiny_kernel, greens_small_kernel, weight_kernel, det_combine_kernel here; the fifth, the fused propagator with the
+Green's function as its tail (prop_fused_kernel<false, 7, true, MUL3>), never launches on the unannounced default-scope
+steps taken here (the ``tail-*`` cases assert that, and run the two launches with the spin-sum force bias instead): the
+routes to it are tests/test_gpu_constraint_tail.py's.
 
 Two steps through the C ABI on the populations of tests/constraint_cases.py (checked on the reference alone in
 tests/test_constraint_cases_cpu.py: no decision is closer than 1e-6 to its threshold), EVERY walker against the oracle
@@ -56,27 +60,52 @@ def check_step(dev, model, eshift, extra, verdicts, before):
     return got, counters
 
 
-def run_case(name):
+def load_case(dev, run):
+    """A fresh handle made ready for the first step of a case: walkers, weights, overlaps and energies as the oracle starts
+    from them, the cap, the back-propagation window, the Philox seed; counters at zero."""
+    model, phis, weights, xi, eshift, extra = run['case']
+    if extra['msd_fb_mode']:
+        dev.set_msd_force_bias(extra['msd_fb_mode'])
+    dev.set(L.F_PHI, phis)
+    dev.set(L.F_WEIGHT, weights)
+    dev.set(L.F_UNSCALED_WEIGHT, weights)
+    dev.set(L.F_OT, run['ot0'])
+    dev.set(L.F_HYBRID_ENERGY, extra['ehyb0'])
+    dev.set(L.F_ELOC, extra['ehyb0'])
+    if extra['cap'] is not None:
+        dev.set_weight_cap(*extra['cap'])
+    if extra['bp']:
+        dev.bp_configure(extra['bp'])
+    if extra['philox'] is not None:
+        dev.rng_seed(*extra['philox'])
+    dev.counters(reset=True)
+
+
+def check_bp_window(dev, run):
+    """The back-propagation window the second step closed: the steps each walker recorded, then denominator and Green's
+    function with the weights restored partially, against the oracle's."""
+    model, weights = run['case'][0], run['case'][2]
+    assert numpy.array_equal(dev.bp_steps(), run['bp_steps'])
+    energies, denom, G = dev.bp_update(model.psi, 10, 'partial')
+    want = run['bp_est']
+    assert numpy.all(numpy.isfinite(G)) and numpy.isfinite(denom) and numpy.all(numpy.isfinite(energies))
+    close(denom, want[3], TOL)
+    close(G, want[4:].reshape(2, model.M, model.M), TOL)
+    assert numpy.all(energies == 0)
+    assert list(dev.bp_steps()) == [0] * len(weights)
+
+
+def run_case(name, fusion=None):
+    """``fusion``: (mode, scope) of afq_set_step_fusion / afq_set_step_fusion_scope, the handle's defaults when None."""
     run = cc.run_oracle(name)
     model, phis, weights, xi, eshift, extra = run['case']
     nw = len(weights)
     dev = make_device(model, nw, hybrid=extra['hybrid'])
     try:
-        if extra['msd_fb_mode']:
-            dev.set_msd_force_bias(extra['msd_fb_mode'])
-        dev.set(L.F_PHI, phis)
-        dev.set(L.F_WEIGHT, weights)
-        dev.set(L.F_UNSCALED_WEIGHT, weights)
-        dev.set(L.F_OT, run['ot0'])
-        dev.set(L.F_HYBRID_ENERGY, extra['ehyb0'])
-        dev.set(L.F_ELOC, extra['ehyb0'])
-        if extra['cap'] is not None:
-            dev.set_weight_cap(*extra['cap'])
-        if extra['bp']:
-            dev.bp_configure(extra['bp'])
-        if extra['philox'] is not None:
-            dev.rng_seed(*extra['philox'])
-        dev.counters(reset=True)
+        load_case(dev, run)
+        if fusion is not None:
+            dev.set_step_fusion(fusion[0])
+            dev.set_step_fusion_scope(fusion[1])
         dev.launch_trace(True)
         state = {f: dev.get(f) for f in (L.F_PHI, L.F_WEIGHT, L.F_OT, L.F_HYBRID_ENERGY, L.F_ELOC, L.F_PHASE)}
         closed_steps = 0
@@ -98,14 +127,7 @@ def run_case(name):
         est = dev.estimates_get(zero=True)
         close(est[EST], run['estimates'][EST], TOL)
         if extra['bp']:
-            assert numpy.array_equal(dev.bp_steps(), run['bp_steps'])
-            energies, denom, G = dev.bp_update(model.psi, 10, 'partial')
-            want = run['bp_est']
-            assert numpy.all(numpy.isfinite(G)) and numpy.isfinite(denom) and numpy.all(numpy.isfinite(energies))
-            close(denom, want[3], TOL)
-            close(G, want[4:].reshape(2, model.M, model.M), TOL)
-            assert numpy.all(energies == 0)
-            assert list(dev.bp_steps()) == [0] * nw
+            check_bp_window(dev, run)
     finally:
         dev.close()
 
