@@ -186,6 +186,21 @@ int afq_hubbard_energy_full_g(afq_handle *h, const double *G, int n, double *E_o
  * Slices 0-3 are the same for G and for its transpose per spin; slice 4 is transposed with G.  Nothing is assumed
  * about G.  Any handle whose system is set (AFQ_ESTATE before that): only M is used.  Same input, same bits.       */
 int afq_correlations_full_g(afq_handle *h, const double *G, int n, double *corr_out);
+/* Pair-field correlation functions of FULL Green's functions over a table of bonds (k_pair.hip).
+ * afq_set_pairing_bonds: nbr int32[nb, M], nbr[b][i] = the partner site of i along bond b, or -1 where i has no such
+ * partner (open boundaries, Generic systems); any table, repeated partners included.  Needs a system (AFQ_ESTATE before
+ * that; a new system drops the table); nb <= 16 (AFQ_EINVAL above, with the number) and every entry in [-1, M)
+ * (AFQ_EINVAL naming the entry; the table held before stays).  nb = 0 clears the table (nbr may be NULL then).  A window
+ * in the mode of afq_bp_pairing leaves that mode: call afq_bp_pairing again after a new table.
+ * afq_pairing_full_g: G c128[n, 2, M, M] (spin 0 = up, 1 = down) -> pair c128[n, nb, nb, M, M].  With
+ * D+(k, l) = c+_k,up c+_l,down and G[i,j] = <c+_i c_j>,
+ *   pair[b, b', i, j] = <D+(i, nbr[b][i]) D(j, nbr[b'][j])> = G_0[i, j] G_1[nbr[b][i], nbr[b'][j]],
+ * Wick's theorem for one pair of determinants (opposite spins: no exchange term), and 0 where either partner is -1
+ * whatever G holds.  For the transposed convention (the back-propagated G is the transpose) the array comes out with
+ * both index pairs exchanged: its element [b, b', i, j] is pair[b', b, j, i] of the definition above.  Nothing is
+ * assumed about G.  Any handle with a system and a bond table (AFQ_ESTATE without either).  Same input, same bits.  */
+int afq_set_pairing_bonds(afq_handle *h, int nb, const int32_t *nbr);
+int afq_pairing_full_g(afq_handle *h, const double *G, int n, double *pair_out);
 
 /* ---- back-propagated estimator --------------------------------
  * estimators/back_propagation.py:63-226, walkers/stack.py:5-127 (FieldConfig),
@@ -238,8 +253,17 @@ int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_
  *            chunk order (no atomics: the same bits on every run and every device); walkers of weight zero contribute
  *            nothing.  Evaluated with or without eval_energy.                                          */
 int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, const double *L, int nL);
+/* Puts the window's two-body slot into pairing mode (on != 0) or takes it out of it (on = 0; a slot in another mode is
+ * left as it is).  Call after afq_bp_configure (AFQ_ESTATE before) and afq_set_pairing_bonds (AFQ_ESTATE without a
+ * table).  afq_bp_update_ext's two_rdm_out then is c128[nb, nb, M, M] = sum_w wt_w pair[G_bp[w]] of afq_pairing_full_g
+ * (G_bp is the transposed convention: see there), with the wt_w of the one-body sum; walkers are summed in index order
+ * in chunks of a fixed length, the chunks in chunk order (no atomics: the same bits on every run and every device),
+ * walkers of weight zero contribute nothing.  Evaluated with or without eval_energy; what afq_bp_observables set for
+ * the EKT stays and works alongside.  A later afq_bp_observables replaces the mode with its own.  Every system;
+ * AFQ_EUNSUPPORTED with a multi-determinant trial.                                                    */
+int afq_bp_pairing(afq_handle *h, int on);
 /* afq_bp_update plus, where the pointers are not NULL, two_rdm_out c128[M^4] (c128[2, 2, nq] / c128[5, M, M] in the
- * modes 2 / 3 of afq_bp_observables) = sum_w wt_w two_rdm[G_bp[w]] and
+ * modes 2 / 3 of afq_bp_observables, c128[nb, nb, M, M] after afq_bp_pairing) = sum_w wt_w two_rdm[G_bp[w]] and
  * fock_out c128[2, M, M] = sum_w wt_w (F1p, F1h)[G_bp[w]] with the weights of est_out (complex with restore_weights).
  * With both NULL it is afq_bp_update, bitwise.                                                       */
 /* Cholesky vectors per chunk of the EKT: nc for the rank-N panels, ncy for the term linear in G (0 = automatic: as

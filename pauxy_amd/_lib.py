@@ -111,6 +111,9 @@ SIGNATURES = {
     "afq_local_energy_full_g": [_h, _dp, c_int, _dp],
     "afq_ueg_pair_sums": [_h, _dp, c_int, _dp, _dp],
     "afq_correlations_full_g": [_h, _dp, c_int, _dp],
+    "afq_set_pairing_bonds": [_h, c_int, _ip],
+    "afq_pairing_full_g": [_h, _dp, c_int, _dp],
+    "afq_bp_pairing": [_h, c_int],
     "afq_hubbard_energy_full_g": [_h, _dp, c_int, _dp],
     "afq_set_trial_multi": [_h, c_int, _dp, _dp, _dp],
     "afq_walkers_det_weights": [_h, _dp],

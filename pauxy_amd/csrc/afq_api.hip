@@ -24,7 +24,7 @@ void free_dets(afq_handle *h) {
 void free_system(afq_handle *h) {
     free_dets(h);
     h->mem.release(LT_SYSTEM);
-    h->hs_cplx = 0; h->sf_nlong = 0; h->kind = 0;
+    h->hs_cplx = 0; h->sf_nlong = 0; h->kind = 0; h->pair_nb = 0;
     h->hirsch = false;              // the discrete propagator belongs to the system it was set for
 }
 
@@ -34,7 +34,7 @@ void free_walkers(afq_handle *h) {
     h->est_acc_pending = false; h->fuse_est_req = false;
     h->gf.gsum.clear(); h->gf.vbias.clear(); h->gf.gdiag.clear(); h->gdiag_parts = 0;
     h->msd_fb_gbar = false;
-    h->nbp = 0; h->bpo_two = h->bpo_ekt = h->bpo_sf = h->bpo_corr = 0; h->bpo_nL = 0; h->it_nmax = 0;
+    h->nbp = 0; h->bpo_two = h->bpo_ekt = h->bpo_sf = h->bpo_corr = h->bpo_pair = 0; h->bpo_nL = 0; h->it_nmax = 0;
     h->rdm_on = false; h->sf_on = false;
     h->th_on = false;
     h->nw = 0;

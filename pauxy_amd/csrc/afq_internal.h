@@ -112,6 +112,12 @@ struct afq_handle {
     // correlation functions (k_corr.hip): [n, 2, M] diagonals, then [nchunk, 5, M, M] partial sums; grown on demand
     cplx *corr_ws = nullptr;
     size_t corr_ws_len = 0;
+    // pairing correlations (afq_set_pairing_bonds, k_pair.hip): the bond table [pair_nb, M] (partner sites, -1 = none) and
+    // the partial sums [nchunk, nb, nb, M, M] of more than one chunk, grown on demand
+    int *pair_nbr = nullptr;
+    int pair_nb = 0;
+    cplx *pair_ws = nullptr;
+    size_t pair_ws_len = 0;
 
     // ---- trial
     bool have_trial = false;
@@ -193,11 +199,12 @@ struct afq_handle {
     int bpo_two = 0, bpo_ekt = 0;   // what afq_bp_update_ext may be asked for
     int bpo_sf = 0;                 // two_rdm is the UEG structure factor [2, 2, nq] (afq_bp_observables(h, 2, ...))
     int bpo_corr = 0;               // two_rdm is the correlation functions [5, M, M] (afq_bp_observables(h, 3, ...), k_corr.hip)
+    int bpo_pair = 0;               // two_rdm is the pairing correlations [nb, nb, M, M] (afq_bp_pairing, k_pair.hip)
     int bpo_nL = 0;                 // EKT vectors L_x, x < nL
     cplx *bpo_h1 = nullptr;         // [M, M] h1 of the EKT
     cplx *bpo_L = nullptr;          // [nL, M, M] the caller's vectors (null: the handle's own real L_full)
     cplx *bpo_wt = nullptr;         // [nw] accumulation weights of the window
-    cplx *bpo_out = nullptr;        // [M^4, 4 nq or 5 M M (two_rdm) + 2 M M (fock)] results of the window
+    cplx *bpo_out = nullptr;        // [M^4, 4 nq, 5 M M or nb nb M M (two_rdm) + 2 M M (fock)] results of the window
     cplx *bpo_ws = nullptr;         // scratch, grown on demand
     size_t bpo_ws_len = 0;
     int bpo_nc = 0, bpo_ncy = 0;    // afq_bp_ekt_chunks: x per chunk of the panels / of the linear term (0: automatic)
@@ -682,3 +689,9 @@ int k_thermal_c_energy(afq_handle *h, double *E_out, double *nav_out);
 // their weighted sum over n -> out_dev [5, M, M] (Green's functions of weight zero left out), in index order
 int k_corr_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *out_dev);
 int k_corr_wsum(afq_handle *h, const cplx *G_dev, int n, const cplx *wt_c, cplx *out_dev);
+int k_sum_chunks(afq_handle *h, const cplx *part, int nchunk, size_t len, cplx *out_dev);   // out[e] = sum_c part[c][e], in chunk order
+// k_pair.hip: <D+(i, nbr[b][i]) D(j, nbr[b'][j])> over the handle's bond table (pair_nbr, pair_nb >= 1) of full Green's
+// functions G_dev [n, 2, M, M] -> out_dev [n, nb, nb, M, M], and their weighted sum over n -> out_dev [nb, nb, M, M]
+// (Green's functions of weight zero left out), in index order
+int k_pair_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *out_dev);
+int k_pair_wsum(afq_handle *h, const cplx *G_dev, int n, const cplx *wt_c, cplx *out_dev);

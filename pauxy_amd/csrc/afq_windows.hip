@@ -181,10 +181,11 @@ int bp_backward(afq_handle *h, int nd, int nstblz, cplx *stack, cplx *ot, double
 }
 
 // length of the two_rdm part of bpo_out in the mode afq_bp_observables set: the structure factor [2, 2, nq], the
-// correlation functions [5, M, M] or the two-body RDM [M]^4
+// correlation functions [5, M, M] or the two-body RDM [M]^4; or, in the mode afq_bp_pairing set, the pairing correlations
+// [nb, nb, M, M]
 size_t bpo_two_len(const afq_handle *h) {
     const size_t m2 = (size_t)h->M * h->M;
-    return h->bpo_sf ? (size_t)4 * h->nq : h->bpo_corr ? 5 * m2 : m2 * m2;
+    return h->bpo_sf ? (size_t)4 * h->nq : h->bpo_corr ? 5 * m2 : h->bpo_pair ? (size_t)h->pair_nb * h->pair_nb * m2 : m2 * m2;
 }
 
 int bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
@@ -221,16 +222,18 @@ int bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weig
         if ((rc = k_ueg_pair_sums(h, h->G, h->nw, eval_energy ? h->energy : sf_E, sf_two))) return rc;
     }
     if ((rc = k_bp_accumulate(h, restore_weights, eval_energy))) return rc;
-    const bool corr = two_rdm_out && h->bpo_corr;
+    const bool corr = two_rdm_out && h->bpo_corr, pair = two_rdm_out && h->bpo_pair;
     const size_t m2 = (size_t)h->M * h->M, m4 = bpo_two_len(h);
     if (two_rdm_out || fock_out) {
         // sum_w wt_w two_rdm[G_bp[w]] and (F1p, F1h)[G_bp[w]] (k_bp_obs.hip), before the reset clears the weight factors
-        if ((rc = k_bp_observables(h, restore_weights, two_rdm_out && !sf && !corr ? h->bpo_out : nullptr,
+        if ((rc = k_bp_observables(h, restore_weights, two_rdm_out && !sf && !corr && !pair ? h->bpo_out : nullptr,
                                    fock_out ? h->bpo_out + (h->bpo_two ? m4 : 0) : nullptr))) return rc;
         // the structure factor with the same weights (bpo_wt), walkers in index order
         if (sf && (rc = k_ueg_sf_wsum(h, sf_two, h->nw, h->bpo_wt, nullptr, h->bpo_out, nullptr))) return rc;
         // the correlation functions of every G_bp[w], summed with the same weights (k_corr.hip)
         if (corr && (rc = k_corr_wsum(h, h->G, h->nw, h->bpo_wt, h->bpo_out))) return rc;
+        // the pairing correlations of every G_bp[w] over the handle's bond table, the same way (k_pair.hip)
+        if (pair && (rc = k_pair_wsum(h, h->G, h->nw, h->bpo_wt, h->bpo_out))) return rc;
     }
     if ((rc = window_end(h, reset != 0))) return rc;
     if (two_rdm_out && (rc = copy_out(h, two_rdm_out, h->bpo_out, sizeof(cplx) * m4))) return rc;
@@ -341,7 +344,7 @@ int afq_bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_
 int afq_bp_update_ext(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
                       int reset, double *est_out, double *two_rdm_out, double *fock_out) {
     AFQ_API(h, "afq_bp_update_ext");
-    if (h && two_rdm_out && !h->bpo_two) AFQ_FAIL(h, AFQ_ESTATE, "two-body RDM: afq_bp_observables(h, 1, 2 or 3, ...) first");
+    if (h && two_rdm_out && !h->bpo_two) AFQ_FAIL(h, AFQ_ESTATE, "two-body RDM: afq_bp_observables(h, 1, 2 or 3, ...) or afq_bp_pairing(h, 1) first");
     if (h && fock_out && !h->bpo_ekt) AFQ_FAIL(h, AFQ_ESTATE, "EKT Fock matrices: afq_bp_observables(h, ., 1, ...) first");
     return bp_update(h, phi_bp0, nstblz, restore_weights, eval_energy, reset, est_out, two_rdm_out, fock_out);
 }
@@ -430,7 +433,7 @@ int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, co
                                         std::to_string((unsigned long long)fr) + " bytes)");
     }
     dev_alloc(h, LT_WALKERS, &h->bpo_h1, 0); dev_alloc(h, LT_WALKERS, &h->bpo_L, 0);
-    h->bpo_two = h->bpo_ekt = h->bpo_sf = h->bpo_corr = 0; h->bpo_nL = 0;
+    h->bpo_two = h->bpo_ekt = h->bpo_sf = h->bpo_corr = h->bpo_pair = 0; h->bpo_nL = 0;
     if (ekt) {
         if ((rc = dev_upload(h, LT_WALKERS, &h->bpo_h1, h1, M * M))) return rc;
         if (L && (rc = dev_upload(h, LT_WALKERS, &h->bpo_L, L, (size_t)nL * M * M))) return rc;
@@ -438,6 +441,53 @@ int afq_bp_observables(afq_handle *h, int two_rdm, int ekt, const double *h1, co
     }
     if ((two_rdm || ekt) && (rc = dev_alloc(h, LT_WALKERS, &h->bpo_out, (two_rdm ? m4 : 0) + (ekt ? 2 * M * M : 0)))) return rc;
     h->bpo_two = two_rdm ? 1 : 0; h->bpo_ekt = ekt ? 1 : 0; h->bpo_sf = sf ? 1 : 0; h->bpo_corr = corr ? 1 : 0;
+    return AFQ_OK;
+}
+
+// ---------------------------------------------------------------- pairing correlations (k_pair.hip)
+int afq_set_pairing_bonds(afq_handle *h, int nb, const int32_t *nbr) {
+    if (!h || nb < 0 || (nb && !nbr)) return AFQ_EINVAL;
+    if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "pairing bonds: the system must be set (the table is [nb, M])");
+    if (nb > 16) AFQ_FAIL(h, AFQ_EINVAL, "pairing bonds: " + std::to_string(nb) + " bonds, at most 16");
+    const size_t M = (size_t)h->M;
+    for (size_t e = 0; e < nb * M; ++e)
+        if (nbr[e] < -1 || nbr[e] >= h->M)
+            AFQ_FAIL(h, AFQ_EINVAL, "pairing bonds: nbr[" + std::to_string(e / M) + "][" + std::to_string(e % M) + "] = " +
+                                        std::to_string(nbr[e]) + " is outside [-1, " + std::to_string(h->M) + ")");
+    hipSetDevice(h->device);
+    AFQ_HIP(h, hipStreamSynchronize(h->stream));   // queued work may still read the table that is replaced
+    // a window in pairing mode was sized for the old table: the mode ends with it, the other modes stay
+    if (h->bpo_pair) {
+        h->bpo_pair = h->bpo_two = 0;
+        int rc = dev_alloc(h, LT_WALKERS, &h->bpo_out, h->bpo_ekt ? 2 * M * M : 0);
+        if (rc) return rc;
+    }
+    h->pair_nb = 0;
+    int rc = dev_upload(h, LT_SYSTEM, &h->pair_nbr, nbr, nb * M);
+    if (rc) return rc;
+    h->pair_nb = nb;
+    return AFQ_OK;
+}
+
+int afq_bp_pairing(afq_handle *h, int on) {
+    if (!h) return AFQ_EINVAL;
+    int rc = need_ready(h, true);
+    if (rc) return rc;
+    if (h->ndet > 1 && on)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "back-propagated pairing correlations with a multi-determinant trial (sum_d w_d f[G_d] of a quadratic form)");
+    if (!h->nbp) AFQ_FAIL(h, AFQ_ESTATE, "back-propagation is not configured: afq_bp_configure first");
+    if (on && !h->pair_nb) AFQ_FAIL(h, AFQ_ESTATE, "pairing correlations: no bond table (afq_set_pairing_bonds first)");
+    if (!on && !h->bpo_pair) return AFQ_OK;        // the two-body slot is in another mode or in none: left as it is
+    // the two-body slot of the window changes its meaning; the EKT's operands and its slot behind it stay
+    const size_t m2 = (size_t)h->M * h->M, m4 = on ? (size_t)h->pair_nb * h->pair_nb * m2 : 0;
+    hipSetDevice(h->device);
+    AFQ_HIP(h, hipStreamSynchronize(h->stream));
+    h->bpo_two = h->bpo_sf = h->bpo_corr = h->bpo_pair = 0;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->bpo_out, m4 + (h->bpo_ekt ? 2 * m2 : 0), "pairing correlations"))) {
+        h->bpo_ekt = 0;
+        return rc;
+    }
+    h->bpo_two = h->bpo_pair = on ? 1 : 0;
     return AFQ_OK;
 }
 
@@ -564,6 +614,14 @@ int afq_correlations_full_g(afq_handle *h, const double *G, int n, double *corr_
     if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "correlation functions: the system must be set (they are sized by its M)");
     return full_g_call(h, G, n, nullptr, (size_t)5 * h->M * h->M * n, corr_out,
                        [&](cplx *Gd, cplx *, cplx *Td) { return k_corr_full_g(h, Gd, n, Td); });
+}
+
+int afq_pairing_full_g(afq_handle *h, const double *G, int n, double *pair_out) {
+    if (!h || !G || !pair_out || n < 1) return AFQ_EINVAL;
+    if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "pairing correlations: the system must be set (they are sized by its M)");
+    if (!h->pair_nb) AFQ_FAIL(h, AFQ_ESTATE, "pairing correlations: no bond table (afq_set_pairing_bonds first)");
+    return full_g_call(h, G, n, nullptr, (size_t)h->pair_nb * h->pair_nb * h->M * h->M * n, pair_out,
+                       [&](cplx *Gd, cplx *, cplx *Td) { return k_pair_full_g(h, Gd, n, Td); });
 }
 
 int afq_hubbard_energy_full_g(afq_handle *h, const double *G, int n, double *E_out) {

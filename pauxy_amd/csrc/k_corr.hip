@@ -161,6 +161,12 @@ int corr_prepare(afq_handle *h, const cplx *G, int n, size_t extra, cplx **diag,
 
 }  // namespace
 
+int k_sum_chunks(afq_handle *h, const cplx *part, int nchunk, size_t len, cplx *out) {
+    AFQ_LAUNCH(h, corr_combine_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, h->stream, part, nchunk, len, out);
+    AFQ_POST(h);
+    return AFQ_OK;
+}
+
 int k_corr_full_g(afq_handle *h, const cplx *G, int n, cplx *out) {
     const int M = h->M, nt = (M + CT - 1) / CT;
     if ((size_t)nt * nt * n > 0x7fffffffu) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "correlation functions: more than 2^31 tiles in one call");
@@ -183,9 +189,5 @@ int k_corr_wsum(afq_handle *h, const cplx *G, int n, const cplx *wt_c, cplx *out
     AFQ_LAUNCH(h, corr_tile_kernel<true>, dim3((unsigned)(nt * nt * nchunk)), dim3(CTHREADS), 0, h->stream, G,
                diag, wt_c, n, M, nt, nchunk > 1 ? part : out);
     AFQ_POST(h);
-    if (nchunk > 1) {
-        AFQ_LAUNCH(h, corr_combine_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, h->stream, part, nchunk, len, out);
-        AFQ_POST(h);
-    }
-    return AFQ_OK;
+    return nchunk > 1 ? k_sum_chunks(h, part, nchunk, len, out) : AFQ_OK;
 }

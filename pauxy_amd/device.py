@@ -209,15 +209,45 @@ class AfqDevice(object):
         self._ck(self.lib.afq_correlations_full_g(self.h, _p(G), n, _p(out)))
         return out
 
+    def set_pairing_bonds(self, nbr):
+        """afq_set_pairing_bonds: the bond table nbr int [nb, M] of the pairing correlations, nbr[b][i] = the partner
+        site of i along bond b or -1 (estimators.pairing.lattice_bonds builds a lattice's); None or an empty table
+        clears it.  A window in pairing mode leaves it: bp_observables(two_rdm='pairing') again afterwards."""
+        if nbr is None or numpy.size(nbr) == 0:
+            self._ck(self.lib.afq_set_pairing_bonds(self.h, 0, None))
+            self._pair_nb = 0
+            return
+        if numpy.ndim(nbr) != 2 or numpy.shape(nbr)[1] != self.M:
+            raise ValueError("pairing bonds: an integer array [nb, M]")
+        nbr = numpy.ascontiguousarray(nbr, dtype=numpy.int32)
+        self._ck(self.lib.afq_set_pairing_bonds(self.h, nbr.shape[0], _p(nbr)))
+        self._pair_nb = nbr.shape[0]
+
+    def pairing_full_g(self, G):
+        """pair [n, nb, nb, M, M] of general Green's functions G[n, 2, M, M] (afq_pairing_full_g) over the table of
+        set_pairing_bonds: pair[b, b', i, j] = G_0[i, j] G_1[nbr[b][i], nbr[b'][j]] = <D+(i, i_b) D(j, j_b')> with
+        D+(k, l) = c+_k,up c+_l,down for G[i,j] = <c+_i c_j>, 0 where a partner is -1; for the transposed convention
+        the element [b, b', i, j] is pair[b', b, j, i].  Any handle with a system and a bond table."""
+        G = _c128(G)
+        n = G.shape[0]
+        G = _c128(G, (n, 2, self.M, self.M))
+        nb = getattr(self, '_pair_nb', 0)
+        out = numpy.zeros((n, nb, nb, self.M, self.M), dtype=numpy.complex128)
+        self._ck(self.lib.afq_pairing_full_g(self.h, _p(G), n, _p(out)))
+        return out
+
     def bp_observables(self, two_rdm=False, ekt=False, h1=None, L=None):
         """afq_bp_observables: what bp_update may be asked for.  EKT: h1 [M, M] and L [nL, M, M] (None: a generic
         system's own vectors).  two_rdm='structure_factor' (UEG): bp_update's 'two_rdm' then is [2, 2, nq];
-        two_rdm='correlation' (any system): [5, M, M], the weighted sum of correlations_full_g over the walkers."""
-        if isinstance(two_rdm, str) and two_rdm not in ('structure_factor', 'correlation'):
-            raise ValueError("two_rdm: True, 'structure_factor' or 'correlation'")
+        two_rdm='correlation' (any system): [5, M, M], the weighted sum of correlations_full_g over the walkers;
+        two_rdm='pairing' (any system, after set_pairing_bonds; afq_bp_pairing): [nb, nb, M, M], the weighted sum of
+        pairing_full_g over the walkers."""
+        if isinstance(two_rdm, str) and two_rdm not in ('structure_factor', 'correlation', 'pairing'):
+            raise ValueError("two_rdm: True, 'structure_factor', 'correlation' or 'pairing'")
         self._bp_sf = isinstance(two_rdm, str) and two_rdm == 'structure_factor'
         self._bp_corr = isinstance(two_rdm, str) and two_rdm == 'correlation'
-        two_rdm = 2 if self._bp_sf else 3 if self._bp_corr else int(bool(two_rdm))
+        self._bp_pair = isinstance(two_rdm, str) and two_rdm == 'pairing'
+        two_rdm = 2 if self._bp_sf else 3 if self._bp_corr else 0 if self._bp_pair else int(bool(two_rdm))
         M = self.M
         h1p = Lp = None
         nL = 0
@@ -232,6 +262,8 @@ class AfqDevice(object):
                 L = _c128(L, (nL, M, M))
                 Lp = _p(L)
         self._ck(self.lib.afq_bp_observables(self.h, two_rdm, int(bool(ekt)), h1p, Lp, int(nL)))
+        if self._bp_pair:
+            self._ck(self.lib.afq_bp_pairing(self.h, 1))
 
     def bp_ekt_chunks(self, nc=0, ncy=0):
         """afq_bp_ekt_chunks: Cholesky vectors per EKT chunk (0: automatic)."""
@@ -242,7 +274,8 @@ class AfqDevice(object):
         """-> (energies_sum[3], denominator, G_bp_sum[2, M, M]); restore_weights in (None, 'partial', 'full').
         With two_rdm / ekt (after bp_observables) a fourth item {'two_rdm': [M]*4, 'fock_1p': [M, M], 'fock_1h':
         [M, M]} holds the weighted sums of what was asked for ('two_rdm': [2, 2, nq] after
-        bp_observables(two_rdm='structure_factor'), [5, M, M] after bp_observables(two_rdm='correlation'))."""
+        bp_observables(two_rdm='structure_factor'), [5, M, M] after bp_observables(two_rdm='correlation'),
+        [nb, nb, M, M] after bp_observables(two_rdm='pairing'))."""
         mode = {None: 0, 'partial': 1, 'full': 2}.get(restore_weights, 1)
         phi0 = _c128(phi_bp0, (self.M, self.na + self.nb))
         M = self.M
@@ -254,7 +287,8 @@ class AfqDevice(object):
         two = None
         if two_rdm:
             shape = ((2, 2, self.nq) if getattr(self, '_bp_sf', False)
-                     else (5, M, M) if getattr(self, '_bp_corr', False) else (M, M, M, M))
+                     else (5, M, M) if getattr(self, '_bp_corr', False)
+                     else (self._pair_nb, self._pair_nb, M, M) if getattr(self, '_bp_pair', False) else (M, M, M, M))
             two = numpy.zeros(shape, dtype=numpy.complex128)
         fock = numpy.zeros((2, M, M), dtype=numpy.complex128) if ekt else None
         self._ck(self.lib.afq_bp_update_ext(self.h, _p(phi0), int(nstblz), mode, int(bool(eval_energy)),

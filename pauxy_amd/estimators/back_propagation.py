@@ -39,6 +39,16 @@ estimator, whose analysis/correlation.py still reads such a dataset) accumulates
 (``two_rdm_shape = (5, M, M)``), complex and not normalised like the structure factor, in the same slot of the flat
 vector, ``self.two_rdm`` and the group ``two_rdm_<n>``.  It is evaluated with or without ``evaluate_energy`` and
 together with ``evaluate_ekt``.  estimators/correlation.py turns the normalised array into charge and spin correlations.
+
+``two_rdm: 'pairing'`` (the same systems and trials; not in the reference either) accumulates sum_w weight_w
+pair[G_bp[w]] with the [nb, nb, M, M] array of ``afq_pairing_full_g`` over the bond table ``pairing_bonds`` (an integer
+array [nb, M]: the partner site of every site along every bond, -1 where there is none; nb <= 16).  A Hubbard system
+takes ``estimators.pairing.lattice_bonds(nx, ny)`` (on-site, +x, -x, +y, -y) when none is given; any other system
+without ``pairing_bonds`` is a ValueError.  ``two_rdm_shape = (nb, nb, M, M)``, complex and not normalised, in the same
+slot of the flat vector, ``self.two_rdm`` and the group ``two_rdm_<n>``; evaluated with or without ``evaluate_energy``
+and together with ``evaluate_ekt``.  The back-propagated Green's function is the transpose of <c+_i c_j>, so the stored
+element [b, b', i, j] is <D+(j, j_b') D(i, i_b)> with D+(k, l) = c+_k,up c+_l,down (pair[b', b, j, i] of the header's
+definition).  estimators/pairing.py forms the singlet pair fields and the s, extended-s and d-wave channels from it.
 """
 import numpy
 
@@ -46,6 +56,7 @@ import numpy
 class BackPropagation(object):
     structure_factor = False
     correlation = False
+    pairing = False
 
     def __init__(self, bp, root, filename, qmc, system, trial, dtype, BT2):
         self.tau_bp = bp.get('tau_bp', 0)
@@ -74,13 +85,27 @@ class BackPropagation(object):
             # continuous Hubbard propagator
             raise NotImplementedError("restore_weights with the discrete Hubbard fields")
         if isinstance(self.calc_two_rdm, str):
-            if self.calc_two_rdm not in ("structure_factor", "correlation"):
-                raise ValueError("two_rdm: True, 'structure_factor' or 'correlation'")
+            if self.calc_two_rdm not in ("structure_factor", "correlation", "pairing"):
+                raise ValueError("two_rdm: True, 'structure_factor', 'correlation' or 'pairing'")
             # (instance attributes only with the option, like two_rdm)
             if self.calc_two_rdm == "structure_factor":
                 self.structure_factor = True
-            else:
+            elif self.calc_two_rdm == "correlation":
                 self.correlation = True
+            else:
+                self.pairing = True
+        if self.pairing:
+            bonds = bp.get('pairing_bonds', None)
+            if bonds is None:
+                if system.name != "Hubbard":
+                    raise ValueError("two_rdm: 'pairing' needs pairing_bonds [nb, M] on a %s system" % system.name)
+                from pauxy_amd.estimators.pairing import lattice_bonds
+                bonds = lattice_bonds(system.nx, system.ny)[0]
+            bonds = numpy.asarray(bonds)
+            if (bonds.ndim != 2 or bonds.shape[1] != system.nbasis or not 1 <= bonds.shape[0] <= 16
+                    or bonds.dtype.kind not in 'iu' or bonds.min() < -1 or bonds.max() >= system.nbasis):
+                raise ValueError("pairing_bonds: an integer array [nb, M], 1 <= nb <= 16, entries in [-1, M)")
+            self.pairing_bonds = bonds.astype(numpy.int32)
         if self.structure_factor and system.name != "UEG":
             # S(q) is a sum over momentum transfers: back_propagation.py:88-89 reads system.qvecs
             raise NotImplementedError("back-propagated two_rdm: 'structure_factor' needs a UEG system")
@@ -108,7 +133,8 @@ class BackPropagation(object):
             self.two_rdm = []
             # back_propagation.py:88-94
             self.two_rdm_shape = ((2, 2, len(system.qvecs)) if self.structure_factor
-                                  else (5, M, M) if self.correlation else (M,) * 4)
+                                  else (5, M, M) if self.correlation
+                                  else (len(self.pairing_bonds),) * 2 + (M, M) if self.pairing else (M,) * 4)
             self.two_rdm_size = int(numpy.prod(self.two_rdm_shape))
             dms_size += self.two_rdm_size
         if self.eval_ekt:
@@ -236,7 +262,9 @@ class BackPropagation(object):
                 cv = cv.toarray() if hasattr(cv, 'toarray') else numpy.asarray(cv)
                 L = 2.0 * cv.T.reshape((system.nchol, system.nbasis, system.nbasis))
         two = ('structure_factor' if self.structure_factor else 'correlation' if self.correlation
-               else self.calc_two_rdm is not None)
+               else 'pairing' if self.pairing else self.calc_two_rdm is not None)
+        if self.pairing:
+            dev.set_pairing_bonds(self.pairing_bonds)
         dev.bp_observables(two_rdm=two, ekt=bool(self.eval_ekt), h1=h1, L=L)
         self._obs_dev = dev
 
