@@ -6,218 +6,19 @@
 // counter are the same for every walker and live on the handle; the driver moves the population through the slices
 // together.  M <= 64: a walker's working set stays in LDS.
 //
-//   thermal_greens_kernel   one work-group per (walker, spin): G from the stack by the stratified (graded)
-//                           decomposition.  Q D T = B_first by column-pivoted Householder QR; for every further bin
-//                           C = (B Q) D, Q D t = C, T <- t T; then with D = D_b^-1 D_s split at |D| = 1
-//                             G^-1 = I + Q D T = Q D_b^-1 (D_b Q^T + D_s T)   =>   (D_b Q^T + D_s T) G = D_b Q^T,
-//                           one pivoted solve (the same G as T^-1 (D_b Q^T T^-1 + D_s)^-1 D_b Q^T without forming T^-1).
-//                           The products B Q and t T are fp64 MFMA (v_mfma_f64_16x16x4, tiles padded by zero
-//                           operands); the Householder panels and the pivot search are plain wave code.
+//   thermal_greens_kernel   G of every (walker, spin) from the stack: thermal_strat.h's engine with T = double.
 //   thermal_slice_kernel    one work-group per walker, both spins' G in LDS: the M single-site updates of
 //                           propagate_walker_constrained, then B_s = diag(BV_s) BH1_s onto the walker's current bin.
 //   thermal_wrap_kernel     G_s <- BT_s G_s BT_s^-1 (two MFMA products) per (walker, spin).
-#include "afq_internal.h"
-#include "afq_host.h"
-#include "mfma_gemm.h"
-#include <cmath>
+#include "thermal_strat.h"
 #include <cstring>
 
 #define TH_MAXM 64
-#define TH_THREADS 256
 
 namespace {
 
-// C = A B for M x M operands given as element loaders, by the 4 waves of the work-group: 16 x 16 tiles, k in steps of
-// 4; rows, columns and k beyond M enter as zeros and are not stored.  The caller synchronises before and after.
-template <class LA, class LB, class ST>
-__device__ inline void th_gemm(int M, LA la, LB lb, ST st) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const int nt = (M + 15) >> 4, lr = lane & 15, lk = lane >> 4;
-    for (int tile = wave; tile < nt * nt; tile += nwave) {
-        const int row0 = (tile / nt) << 4, col0 = (tile % nt) << 4;
-        const int arow = row0 + lr, bcol = col0 + lr;
-        d4_t acc = (d4_t){0, 0, 0, 0};
-        for (int k0 = 0; k0 < M; k0 += 4) {
-            const int k = k0 + lk;
-            const double a = (arow < M && k < M) ? la(arow, k) : 0.0;
-            const double b = (bcol < M && k < M) ? lb(k, bcol) : 0.0;
-            acc = mfma16(a, b, acc);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = row0 + lk + 4 * r;
-            if (row < M && bcol < M) st(row, bcol, acc[r]);
-        }
-    }
-}
-
-// (value, index) of the largest val over the 64 lanes of a wave; ties go to the lower index; every lane gets the result
-__device__ inline void th_wave_argmax(double &val, int &idx) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(val, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
-    }
-}
-
-// Column-pivoted Householder QR of W [M, M] (LDS, row-major, leading dimension LD), in place: W P = Q R.  On return
-// the upper triangle of W holds R (zeros below), perm[j] the original column now at position j, Qt = Q^T.
-// The pivot of step j is the remaining column of the largest norm over the rows j.., recomputed every step (no
-// downdating).  part: 8 * 64 doubles, v: 64 doubles.  Every wave runs the pivot search on its own: no shared scalars.
-__device__ void th_qrcp(double *W, double *Qt, int M, int LD, int *perm, double *v, double *part) {
-    const int tid = threadIdx.x, c = tid & 63, q = tid >> 6;
-    for (int e = tid; e < M * M; e += TH_THREADS) { const int r = e / M, cc = e % M; Qt[r * LD + cc] = r == cc ? 1.0 : 0.0; }
-    if (tid < M) perm[tid] = tid;
-    __syncthreads();
-    for (int j = 0; j < M; ++j) {
-        if (c >= j && c < M) {
-            double s = 0.0;
-            for (int i = j + q; i < M; i += 4) { const double x = W[i * LD + c]; s = fma(x, x, s); }
-            part[q * 64 + c] = s;
-        }
-        __syncthreads();
-        double nrm2 = (c >= j && c < M) ? (part[c] + part[64 + c]) + (part[128 + c] + part[192 + c]) : -1.0;
-        int piv = c;
-        th_wave_argmax(nrm2, piv);
-        if (piv != j) {
-            if (tid < M) { const double t = W[tid * LD + j]; W[tid * LD + j] = W[tid * LD + piv]; W[tid * LD + piv] = t; }
-            if (tid == TH_THREADS - 1) { const int t = perm[j]; perm[j] = perm[piv]; perm[piv] = t; }
-        }
-        __syncthreads();
-        const double x0 = W[j * LD + j], nrm = sqrt(nrm2);
-        const double alpha = x0 >= 0.0 ? -nrm : nrm;                 // H x = alpha e_0, no cancellation in x0 - alpha
-        const double tau = nrm > 0.0 ? (alpha - x0) / alpha : 0.0;
-        if (tid < M - j) v[j + tid] = (tid == 0 || !(nrm > 0.0)) ? (tid == 0 ? 1.0 : 0.0) : W[(j + tid) * LD + j] / (x0 - alpha);
-        __syncthreads();
-        // v^T W[:, c] for the trailing columns and v^T Qt[:, c] for every column, four row classes per column
-        if (c < M) {
-            double sw = 0.0, sq = 0.0;
-            for (int i = j + q; i < M; i += 4) {
-                const double vi = v[i];
-                if (c > j) sw = fma(vi, W[i * LD + c], sw);
-                sq = fma(vi, Qt[i * LD + c], sq);
-            }
-            part[q * 64 + c] = sw; part[256 + q * 64 + c] = sq;
-        }
-        __syncthreads();
-        if (c < M) {
-            const double sw = tau * ((part[c] + part[64 + c]) + (part[128 + c] + part[192 + c]));
-            const double sq = tau * ((part[256 + c] + part[320 + c]) + (part[384 + c] + part[448 + c]));
-            for (int i = j + q; i < M; i += 4) {
-                const double vi = v[i];
-                if (c > j) W[i * LD + c] = fma(-sw, vi, W[i * LD + c]);
-                Qt[i * LD + c] = fma(-sq, vi, Qt[i * LD + c]);
-            }
-            if (c == j && nrm > 0.0) for (int i = j + q; i < M; i += 4) W[i * LD + j] = i == j ? alpha : 0.0;
-        }
-        __syncthreads();
-    }
-}
-
-// X G = R for X, R [M, M] in LDS by Gauss-Jordan elimination with partial (row) pivoting; G overwrites R, X is
-// destroyed.  colv, rowx, rowr: 64 doubles each.
-__device__ void th_solve(double *X, double *R, int M, int LD, double *colv, double *rowx, double *rowr) {
-    const int tid = threadIdx.x, c = tid & 63;
-    for (int k = 0; k < M; ++k) {
-        double a = (c >= k && c < M) ? fabs(X[c * LD + k]) : -1.0;
-        int p = c;
-        th_wave_argmax(a, p);
-        __syncthreads();                                  // (every wave has read column k before rows move)
-        if (p != k) {
-            if (tid < M) { const double t = X[k * LD + tid]; X[k * LD + tid] = X[p * LD + tid]; X[p * LD + tid] = t; }
-            else if (tid >= 64 && tid < 64 + M) { const double t = R[k * LD + c]; R[k * LD + c] = R[p * LD + c]; R[p * LD + c] = t; }
-        }
-        __syncthreads();
-        const double piv = X[k * LD + k];
-        __syncthreads();
-        if (tid < M) { colv[tid] = X[tid * LD + k]; rowx[tid] = X[k * LD + tid] / piv; }
-        else if (tid >= 64 && tid < 64 + M) rowr[c] = R[k * LD + c] / piv;
-        __syncthreads();
-        for (int e = tid; e < M * M; e += TH_THREADS) {
-            const int i = e / M, cc = e % M;
-            if (i == k) { X[e / M * LD + cc] = rowx[cc]; R[i * LD + cc] = rowr[cc]; }
-            else {
-                const double f = colv[i];
-                X[i * LD + cc] = fma(-f, rowx[cc], X[i * LD + cc]);
-                R[i * LD + cc] = fma(-f, rowr[cc], R[i * LD + cc]);
-            }
-        }
-        __syncthreads();
-    }
-}
-
-struct ThLds {
-    double *m[4];
-    double *D, *v, *part, *aux;
-    int *perm;
-};
-__host__ __device__ inline size_t th_mat(int M) { return (size_t)M * (M | 1); }
-// LDS of the Green's kernel: 4 matrices, D[64], v[64], part[512], aux[192], perm[64]
-inline size_t th_greens_lds(int M) { return sizeof(double) * (4 * th_mat(M) + 64 + 64 + 512 + 192) + sizeof(int) * 64; }
-inline size_t th_slice_lds(int M) { return sizeof(double) * (3 * th_mat(M) + 6 * 64); }
-inline size_t th_wrap_lds(int M) { return sizeof(double) * th_mat(M); }
-
-// G[w, s] from the bins of walker w in the order first, first + 1, .. (mod nbins).  stack [nw, nbins, 2, M, M];
-// src_w < 0: block b works on walker b / 2, otherwise every block works on walker src_w (grid of 2 blocks).
-__global__ __launch_bounds__(TH_THREADS) void thermal_greens_kernel(const double *stack, double *G, int M, int nbins,
-                                                                     int first, int src_w) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int LD = M | 1, tid = threadIdx.x;
-    const size_t mat = th_mat(M);
-    double *W = (double *)smem, *Qt = W + mat, *T = Qt + mat, *X = T + mat;
-    double *D = X + mat, *v = D + 64, *part = v + 64, *aux = part + 512;
-    int *perm = (int *)(aux + 192);
-    const int w = src_w < 0 ? blockIdx.x >> 1 : src_w, s = blockIdx.x & 1;
-    const long mm = (long)M * M;
-    const double *Bw = stack + ((long)w * nbins * 2 + s) * mm;       // bin b at Bw + b * 2 * mm
-
-    {
-        const double *B = Bw + (long)first * 2 * mm;
-        for (int e = tid; e < M * M; e += TH_THREADS) W[(e / M) * LD + e % M] = B[e];
-    }
-    __syncthreads();
-    th_qrcp(W, Qt, M, LD, perm, v, part);
-    // T = D^-1 R P^T
-    for (int e = tid; e < M * M; e += TH_THREADS) {
-        const int i = e / M, j = e % M;
-        T[i * LD + perm[j]] = j >= i ? W[i * LD + j] / W[i * LD + i] : 0.0;
-    }
-    if (tid < M) D[tid] = W[tid * LD + tid];
-    __syncthreads();
-    for (int n = 1; n < nbins; ++n) {
-        const double *B = Bw + (long)((first + n) % nbins) * 2 * mm;
-        // W = (B Q) D, Q[k][c] = Qt[c][k]
-        th_gemm(M, [&](int r, int k) { return B[r * M + k]; }, [&](int k, int c) { return Qt[c * LD + k]; },
-                [&](int r, int c, double x) { W[r * LD + c] = x * D[c]; });
-        __syncthreads();
-        th_qrcp(W, Qt, M, LD, perm, v, part);
-        for (int e = tid; e < M * M; e += TH_THREADS) {
-            const int i = e / M, j = e % M;
-            X[i * LD + perm[j]] = j >= i ? W[i * LD + j] / W[i * LD + i] : 0.0;
-        }
-        if (tid < M) D[tid] = W[tid * LD + tid];
-        __syncthreads();
-        // T <- t T (into W, whose R is used up; then the two change names)
-        th_gemm(M, [&](int r, int k) { return X[r * LD + k]; }, [&](int k, int c) { return T[k * LD + c]; },
-                [&](int r, int c, double x) { W[r * LD + c] = x; });
-        __syncthreads();
-        double *t = T; T = W; W = t;
-    }
-    // (D_b Q^T + D_s T) G = D_b Q^T, D_b = 1 / |D| and D_s = sign(D) where |D| > 1, else D_b = 1 and D_s = D
-    for (int e = tid; e < M * M; e += TH_THREADS) {
-        const int i = e / M, j = e % M;
-        const double d = D[i], ad = fabs(d);
-        const double db = ad > 1.0 ? 1.0 / ad : 1.0, ds = ad > 1.0 ? (d > 0.0 ? 1.0 : -1.0) : d;
-        const double r = db * Qt[i * LD + j];
-        X[i * LD + j] = fma(ds, T[i * LD + j], r);
-        W[i * LD + j] = r;
-    }
-    __syncthreads();
-    th_solve(X, W, M, LD, aux, aux + 64, aux + 128);
-    double *Gd = G + ((long)(src_w < 0 ? w : 0) * 2 + s) * mm;
-    for (int e = tid; e < M * M; e += TH_THREADS) Gd[e] = W[(e / M) * LD + e % M];
-}
+inline size_t th_slice_lds(int M) { return sizeof(double) * (3 * ts_mat(M) + 6 * 64); }
+inline size_t th_wrap_lds(int M) { return sizeof(double) * ts_mat(M); }
 
 struct ThSliceArgs {
     double *G, *stack, *weight;
@@ -230,7 +31,7 @@ struct ThSliceArgs {
 __global__ __launch_bounds__(TH_THREADS) void thermal_slice_kernel(ThSliceArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int M = a.M, LD = M | 1, tid = threadIdx.x, w = blockIdx.x;
-    const size_t mat = th_mat(M);
+    const size_t mat = ts_mat(M);
     double *Gs = (double *)smem;                       // [2][mat]
     double *X = Gs + 2 * mat;
     double *colv = X + mat, *rowv = colv + 128, *bv = rowv + 128;    // [2][64] each
@@ -293,7 +94,7 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_slice_kernel(ThSliceArgs a
         if (a.counter == 0) {
             for (int e = tid; e < M * M; e += TH_THREADS) S[e] = b[e / M] * BH[e];
         } else {
-            th_gemm(M, [&](int r, int k) { return b[r] * BH[r * M + k]; }, [&](int k, int c) { return S[k * M + c]; },
+            ts_gemm<double>(M, [&](int r, int k) { return b[r] * BH[r * M + k]; }, [&](int k, int c) { return S[k * M + c]; },
                     [&](int r, int c, double x) { X[r * LD + c] = x; });
             __syncthreads();
             for (int e = tid; e < M * M; e += TH_THREADS) S[e] = X[(e / M) * LD + e % M];
@@ -310,10 +111,10 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_wrap_kernel(double *G, con
     const long mm = (long)M * M;
     double *Gd = G + (long)blockIdx.x * mm;
     const double *A = BT + s * mm, *Ai = BTinv + s * mm;
-    th_gemm(M, [&](int r, int k) { return A[r * M + k]; }, [&](int k, int c) { return Gd[k * M + c]; },
+    ts_gemm<double>(M, [&](int r, int k) { return A[r * M + k]; }, [&](int k, int c) { return Gd[k * M + c]; },
             [&](int r, int c, double x) { X[r * LD + c] = x; });
     __syncthreads();
-    th_gemm(M, [&](int r, int k) { return X[r * LD + k]; }, [&](int k, int c) { return Ai[k * M + c]; },
+    ts_gemm<double>(M, [&](int r, int k) { return X[r * LD + k]; }, [&](int k, int c) { return Ai[k * M + c]; },
             [&](int r, int c, double x) { Gd[r * M + c] = x; });
 }
 
@@ -330,56 +131,10 @@ __global__ void thermal_reset_kernel(double *stack, double *G, double *weight, c
     if (i == 0) weight[w] = 1.0;
 }
 
-// P_s = I - G_s^T as c128 [nw, 2, M, M] for the full-G Hubbard energy, nav = tr P_up + tr P_down
-__global__ __launch_bounds__(TH_THREADS) void thermal_rdm_kernel(const double *G, cplx *P, double *nav, int M) {
-    __shared__ double red[TH_THREADS];
-    const int w = blockIdx.x, tid = threadIdx.x;
-    const long mm = (long)M * M;
-    const double *Gw = G + (long)w * 2 * mm;
-    cplx *Pw = P + (long)w * 2 * mm;
-    for (int e = tid; e < 2 * M * M; e += TH_THREADS) {
-        const int s = e / (M * M), r = (e / M) % M, c = e % M;
-        Pw[e] = cmake((r == c ? 1.0 : 0.0) - Gw[s * mm + c * M + r], 0.0);
-    }
-    double t = 0.0;
-    for (int e = tid; e < 2 * M; e += TH_THREADS) t += 1.0 - Gw[(e / M) * mm + (long)(e % M) * M + e % M];
-    red[tid] = t;
-    __syncthreads();
-    for (int o = TH_THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) nav[w] = red[0];
-}
-
-int th_need(afq_handle *h) {
-    if (!h->th_on || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, "thermal walkers: afq_thermal_configure or afq_thermal_configure_continuous first");
-    if (h->prop_pending) AFQ_FAIL(h, AFQ_ESTATE, "a step is half done: afq_propagate_finish first");
-    hipSetDevice(h->device);
-    return AFQ_OK;
-}
-
-// first bin of the chain for the Green's function at slice_ix (walkers/thermal.py:477-492)
-int th_first_bin(const afq_handle *h, int slice_ix) {
-    int bin_ix = slice_ix / h->th_ss;
-    if (bin_ix == h->th_nbins) bin_ix = -1;
-    return (bin_ix + 1) % h->th_nbins;
-}
-
-int th_launch_greens(afq_handle *h, const double *stack, double *G, int first, int src_w, int nblocks) {
-    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-    const size_t lds = th_greens_lds(h->M);
-    AFQ_HIP(h, afq_raise_lds((const void *)thermal_greens_kernel, lds, lds_set));
-    AFQ_LAUNCH(h, thermal_greens_kernel, dim3(nblocks), dim3(TH_THREADS), lds, h->stream, stack, G, h->M, h->th_nbins,
-               first, src_w);
-    AFQ_POST(h);
-    return AFQ_OK;
-}
-
 }  // namespace
 
 int k_thermal_greens(afq_handle *h, int slice_ix) {
-    return th_launch_greens(h, h->th_stack, h->th_G, th_first_bin(h, slice_ix), -1, 2 * h->nw);
+    return ts_launch_greens<double>(h, h->th_stack, h->th_G, nullptr, ts_first_bin(h, slice_ix), -1, 2 * h->nw);
 }
 
 extern "C" {
@@ -439,14 +194,14 @@ int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int n
 int afq_thermal_reset(afq_handle *h) {
     AFQ_API(h, "afq_thermal_reset");
     if (!h) return AFQ_EINVAL;
-    AFQ_TRY(th_need(h));
+    AFQ_TRY(th_need(h, false));
     if (h->th_cplx) return k_thermal_c_reset(h, false);
     const int M = h->M, nbins = h->th_nbins;
     const long per = 2L * M * M;
     // the trial's G once, from walker 0's fresh bins (every bin is BT^stack_size), then broadcast
     for (int n = 0; n < nbins; ++n)
         AFQ_HIP(h, hipMemcpyAsync(h->th_stack + (long)n * per, h->th_BTpow, sizeof(double) * per, hipMemcpyDeviceToDevice, h->stream));
-    AFQ_TRY(th_launch_greens(h, h->th_stack, h->th_G0, th_first_bin(h, 0), 0, 2));
+    AFQ_TRY(ts_launch_greens<double>(h, h->th_stack, h->th_G0, nullptr, ts_first_bin(h, 0), 0, 2));
     AFQ_LAUNCH(h, thermal_reset_kernel, dim3((unsigned)((per + 255) / 256), h->nw), dim3(256), 0, h->stream, h->th_stack,
                h->th_G, h->weight, h->th_BTpow, h->th_G0, nbins, per, h->nw);
     AFQ_POST(h);
@@ -457,7 +212,7 @@ int afq_thermal_reset(afq_handle *h) {
 int afq_thermal_greens(afq_handle *h, int slice_ix) {
     AFQ_API(h, "afq_thermal_greens");
     if (!h) return AFQ_EINVAL;
-    AFQ_TRY(th_need(h));
+    AFQ_TRY(th_need(h, false));
     if (slice_ix < 0 || slice_ix > h->th_L) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_greens: slice_ix outside 0 .. ntime_slices");
     return h->th_cplx ? k_thermal_c_greens(h, slice_ix) : k_thermal_greens(h, slice_ix);
 }
@@ -465,7 +220,7 @@ int afq_thermal_greens(afq_handle *h, int slice_ix) {
 int afq_thermal_propagate(afq_handle *h, const double *u, int32_t *fields_out, double eshift) {
     AFQ_API(h, "afq_thermal_propagate");
     if (!h) return AFQ_EINVAL;
-    AFQ_TRY(th_need(h));
+    AFQ_TRY(th_need(h, false));
     if (h->th_cplx) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_propagate: continuous fields are configured (afq_thermal_propagate_continuous)");
     if (!u) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_propagate: the uniforms f64[nw, M] are needed");
     if (h->th_slice >= h->th_L) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_propagate: the path is complete (afq_thermal_reset starts the next)");
@@ -500,23 +255,17 @@ int afq_thermal_propagate(afq_handle *h, const double *u, int32_t *fields_out, d
 int afq_thermal_energy(afq_handle *h, double *E_out, double *nav_out) {
     AFQ_API(h, "afq_thermal_energy");
     if (!h) return AFQ_EINVAL;
-    AFQ_TRY(th_need(h));
+    AFQ_TRY(th_need(h, false));
     if (!E_out && !nav_out) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_energy: nothing asked for");
     if (h->th_cplx) return k_thermal_c_energy(h, E_out, nav_out);
-    AFQ_LAUNCH(h, thermal_rdm_kernel, dim3(h->nw), dim3(TH_THREADS), 0, h->stream, h->th_G, h->G, h->th_nav, h->M);
-    AFQ_POST(h);
+    AFQ_TRY(ts_launch_rdm<double>(h, h->th_G, h->th_nav));
     AFQ_TRY(k_energy_hubbard_full_g(h, h->G, h->nw, h->energy));
-    if (E_out) {
-        std::vector<double> e(6 * (size_t)h->nw);
-        AFQ_TRY(copy_out(h, e.data(), h->energy, sizeof(cplx) * 3 * (size_t)h->nw));
-        for (size_t i = 0; i < 3 * (size_t)h->nw; ++i) E_out[i] = e[2 * i];
-    }
-    return copy_out(h, nav_out, h->th_nav, sizeof(double) * (size_t)h->nw);
+    return th_energy_out(h, E_out, nav_out);
 }
 
 int afq_thermal_state(afq_handle *h, int32_t *out4) {
     if (!h || !out4) return AFQ_EINVAL;
-    AFQ_TRY(th_need(h));
+    AFQ_TRY(th_need(h, false));
     out4[0] = h->th_slice; out4[1] = h->th_block; out4[2] = h->th_counter; out4[3] = h->th_nbins;
     return AFQ_OK;
 }

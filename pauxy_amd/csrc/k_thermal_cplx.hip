@@ -6,274 +6,22 @@
 // handle's, as for the real walkers of k_thermal.hip.  A walker's working set stays in LDS: 4 complex matrices of pitch
 // M | 1, which the 160 KiB of a compute unit hold up to M = 47 (the plane-wave shells: 7, 19, 27, 33; 57 does not fit).
 //
-//   thermal_cgreens_kernel  one work-group per (walker, spin): k_thermal.hip's stratified decomposition in complex
-//                           arithmetic.  Q D T = B_first by column-pivoted QR with complex Householder reflectors
-//                           H = I - tau v v^H (alpha = -x_0 / |x_0| ||x||, tau = (||x|| + |x_0|) / ||x|| real); per
-//                           further bin C = (B Q) D, Q D t = C, T <- t T; D = D_b^-1 D_s split at |D| = 1
-//                           (D_b = 1 / |D|, D_s = D / |D| where |D| > 1), (D_b Q^H + D_s T) G = D_b Q^H by one
-//                           pivoted solve.  det G is the product of the pivots of an LU with partial pivoting of a
-//                           copy of G in the matrix the solve has used up.  The products B Q and t T are complex
-//                           products on v_mfma_f64_16x16x4f64, four real products each, edge tiles padded by zeros.
+//   thermal_cgreens_kernel  G and det G of every (walker, spin) from the stack: thermal_strat.h's engine with T = cplx.
 //   thermal_cslice_kernel   one work-group per walker: BV = sum_{n <= 6} VHS^n / n! by five Horner products in LDS,
 //                           once for both spins; per spin B = diag(BH1) BV diag(BH1), right <- B right (right = I at
 //                           in-bin counter 0), bin[block] = diag(left_k) right.
 //   thermal_cweight_kernel  the phaseless weight update from the determinant ratio, per walker.
-//   thermal_crdm_kernel     P_s = I - G_s^T for the force bias and the energy, nav = Re(tr P_up + tr P_down).
+//   thermal_crdm_kernel     P_s = I - G_s^T for the force bias and the energy (thermal_strat.h).
 //   thermal_cfields_kernel  clip, shifted fields, cmf and cfb of every walker, dead ones included.
 // The force bias and the HS potential are the plane-wave kernels of k_models.hip on P.
-#include "afq_internal.h"
-#include "afq_host.h"
-#include "mfma_gemm.h"
-#include <cmath>
+#include "thermal_strat.h"
 #include <cstring>
 
-#define THC_THREADS 256
 #define THC_LDS_MAX (160 * 1024)
 
 namespace {
 
-// C = A B for complex M x M operands given as element loaders, by the 4 waves of the work-group: 16 x 16 tiles, k in
-// steps of 4, four real MFMA products per step; rows, columns and k beyond M enter as zeros and are not stored.  The
-// caller synchronises before and after.
-template <class LA, class LB, class ST>
-__device__ inline void thc_gemm(int M, LA la, LB lb, ST st) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const int nt = (M + 15) >> 4, lr = lane & 15, lk = lane >> 4;
-    for (int tile = wave; tile < nt * nt; tile += nwave) {
-        const int row0 = (tile / nt) << 4, col0 = (tile % nt) << 4;
-        const int arow = row0 + lr, bcol = col0 + lr;
-        d4_t re = (d4_t){0, 0, 0, 0}, im = (d4_t){0, 0, 0, 0};
-        for (int k0 = 0; k0 < M; k0 += 4) {
-            const int k = k0 + lk;
-            const cplx a = (arow < M && k < M) ? la(arow, k) : cmake(0.0, 0.0);
-            const cplx b = (bcol < M && k < M) ? lb(k, bcol) : cmake(0.0, 0.0);
-            re = mfma16(a.x, b.x, re);
-            re = mfma16(-a.y, b.y, re);
-            im = mfma16(a.x, b.y, im);
-            im = mfma16(a.y, b.x, im);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = row0 + lk + 4 * r;
-            if (row < M && bcol < M) st(row, bcol, cmake(re[r], im[r]));
-        }
-    }
-}
-
-// (value, index) of the largest val over the 64 lanes of a wave; ties go to the lower index; every lane gets the result
-__device__ inline void thc_wave_argmax(double &val, int &idx) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(val, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        if (ov > val || (ov == val && oi < idx)) { val = ov; idx = oi; }
-    }
-}
-
-__device__ inline cplx thc_sum4(const cplx *p) {
-    return cadd(cadd(p[0], p[64]), cadd(p[128], p[192]));
-}
-
-// Column-pivoted Householder QR of the complex W [M, M] (LDS, row-major, leading dimension LD), in place: W P = Q R.
-// On return the upper triangle of W holds R (zeros below), perm[j] the original column now at position j, Qt = Q^H.
-// The pivot of step j is the remaining column of the largest norm over the rows j.., recomputed every step.
-// part: 8 * 64 complex, v: 64 complex.  Every wave runs the pivot search on its own: no shared scalars.
-__device__ void thc_qrcp(cplx *W, cplx *Qt, int M, int LD, int *perm, cplx *v, cplx *part) {
-    const int tid = threadIdx.x, c = tid & 63, q = tid >> 6;
-    for (int e = tid; e < M * M; e += THC_THREADS) { const int r = e / M, cc = e % M; Qt[r * LD + cc] = cmake(r == cc ? 1.0 : 0.0, 0.0); }
-    if (tid < M) perm[tid] = tid;
-    __syncthreads();
-    for (int j = 0; j < M; ++j) {
-        if (c >= j && c < M) {
-            double s = 0.0;
-            for (int i = j + q; i < M; i += 4) { const cplx x = W[i * LD + c]; s = fma(x.x, x.x, s); s = fma(x.y, x.y, s); }
-            part[q * 64 + c].x = s;
-        }
-        __syncthreads();
-        double nrm2 = (c >= j && c < M) ? (part[c].x + part[64 + c].x) + (part[128 + c].x + part[192 + c].x) : -1.0;
-        int piv = c;
-        thc_wave_argmax(nrm2, piv);
-        if (piv != j) {
-            if (tid < M) { const cplx t = W[tid * LD + j]; W[tid * LD + j] = W[tid * LD + piv]; W[tid * LD + piv] = t; }
-            if (tid == THC_THREADS - 1) { const int t = perm[j]; perm[j] = perm[piv]; perm[piv] = t; }
-        }
-        __syncthreads();
-        const cplx x0 = W[j * LD + j];
-        const double nrm = sqrt(nrm2), ax0 = hypot(x0.x, x0.y);
-        const cplx ph = ax0 > 0.0 ? cmake(x0.x / ax0, x0.y / ax0) : cmake(1.0, 0.0);
-        const cplx alpha = cmake(-ph.x * nrm, -ph.y * nrm);          // H x = alpha e_0, |x_0 - alpha| = |x_0| + ||x||
-        const double tau = nrm > 0.0 ? (nrm + ax0) / nrm : 0.0;
-        const cplx den = cmake(ph.x * (ax0 + nrm), ph.y * (ax0 + nrm));   // x_0 - alpha
-        if (tid < M - j)
-            v[j + tid] = (tid == 0 || !(nrm > 0.0)) ? cmake(tid == 0 ? 1.0 : 0.0, 0.0) : cdiv(W[(j + tid) * LD + j], den);
-        __syncthreads();
-        // v^H W[:, c] for the trailing columns and v^H Qt[:, c] for every column, four row classes per column
-        if (c < M) {
-            cplx sw = cmake(0.0, 0.0), sq = cmake(0.0, 0.0);
-            for (int i = j + q; i < M; i += 4) {
-                const cplx vc = cconj(v[i]);
-                if (c > j) cfma(sw, vc, W[i * LD + c]);
-                cfma(sq, vc, Qt[i * LD + c]);
-            }
-            part[q * 64 + c] = sw; part[256 + q * 64 + c] = sq;
-        }
-        __syncthreads();
-        if (c < M) {
-            const cplx sw = cscale(thc_sum4(part + c), -tau), sq = cscale(thc_sum4(part + 256 + c), -tau);
-            for (int i = j + q; i < M; i += 4) {
-                const cplx vi = v[i];
-                if (c > j) cfma(W[i * LD + c], sw, vi);
-                cfma(Qt[i * LD + c], sq, vi);
-            }
-            if (c == j && nrm > 0.0) for (int i = j + q; i < M; i += 4) W[i * LD + j] = i == j ? alpha : cmake(0.0, 0.0);
-        }
-        __syncthreads();
-    }
-}
-
-// X G = R for complex X, R [M, M] in LDS by Gauss-Jordan elimination with partial (row) pivoting; G overwrites R, X is
-// destroyed.  colv, rowx, rowr: 64 complex each.
-__device__ void thc_solve(cplx *X, cplx *R, int M, int LD, cplx *colv, cplx *rowx, cplx *rowr) {
-    const int tid = threadIdx.x, c = tid & 63;
-    for (int k = 0; k < M; ++k) {
-        double a = -1.0;
-        if (c >= k && c < M) { const cplx x = X[c * LD + k]; a = hypot(x.x, x.y); }
-        int p = c;
-        thc_wave_argmax(a, p);
-        __syncthreads();                                  // (every wave has read column k before rows move)
-        if (p != k) {
-            if (tid < M) { const cplx t = X[k * LD + tid]; X[k * LD + tid] = X[p * LD + tid]; X[p * LD + tid] = t; }
-            else if (tid >= 64 && tid < 64 + M) { const cplx t = R[k * LD + c]; R[k * LD + c] = R[p * LD + c]; R[p * LD + c] = t; }
-        }
-        __syncthreads();
-        const cplx piv = X[k * LD + k];
-        __syncthreads();
-        if (tid < M) { colv[tid] = X[tid * LD + k]; rowx[tid] = cdiv(X[k * LD + tid], piv); }
-        else if (tid >= 64 && tid < 64 + M) rowr[c] = cdiv(R[k * LD + c], piv);
-        __syncthreads();
-        for (int e = tid; e < M * M; e += THC_THREADS) {
-            const int i = e / M, cc = e % M;
-            if (i == k) { X[i * LD + cc] = rowx[cc]; R[i * LD + cc] = rowr[cc]; }
-            else {
-                const cplx f = cmake(-colv[i].x, -colv[i].y);
-                cfma(X[i * LD + cc], f, rowx[cc]);
-                cfma(R[i * LD + cc], f, rowr[cc]);
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// det X of the complex X [M, M] in LDS: the product of the pivots of an LU with partial (row) pivoting, the sign of every
-// row exchange included; X is destroyed.  Every thread returns the same value.  colv: 64 complex.
-__device__ cplx thc_det(cplx *X, int M, int LD, cplx *colv) {
-    const int tid = threadIdx.x, c = tid & 63;
-    cplx det = cmake(1.0, 0.0);
-    for (int k = 0; k < M; ++k) {
-        double a = -1.0;
-        if (c >= k && c < M) { const cplx x = X[c * LD + k]; a = hypot(x.x, x.y); }
-        int p = c;
-        thc_wave_argmax(a, p);
-        __syncthreads();
-        if (p != k) {
-            if (tid < M) { const cplx t = X[k * LD + tid]; X[k * LD + tid] = X[p * LD + tid]; X[p * LD + tid] = t; }
-            det = cmake(-det.x, -det.y);
-        }
-        __syncthreads();
-        const cplx piv = X[k * LD + k];                   // (the same value in every thread: uniform branches below)
-        det = cmul(det, piv);
-        if (piv.x == 0.0 && piv.y == 0.0) return cmake(0.0, 0.0);
-        if (tid > k && tid < M) colv[tid] = cdiv(X[tid * LD + k], piv);
-        __syncthreads();
-        const int n = M - k - 1;
-        for (int e = tid; e < n * n; e += THC_THREADS) {
-            const int i = k + 1 + e / n, cc = k + 1 + e % n;
-            cfma(X[i * LD + cc], cmake(-colv[i].x, -colv[i].y), X[k * LD + cc]);
-        }
-        __syncthreads();
-    }
-    return det;
-}
-
-__host__ __device__ inline size_t thc_mat(int M) { return (size_t)M * (M | 1); }
-// LDS of the Green's kernel: 4 matrices, D[64], v[64], part[512], aux[192] complex, perm[64]
-inline size_t thc_greens_lds(int M) { return sizeof(cplx) * (4 * thc_mat(M) + 64 + 64 + 512 + 192) + sizeof(int) * 64; }
-inline size_t thc_slice_lds(int M) { return sizeof(cplx) * 3 * thc_mat(M); }
-
-// G[w, s] and det G[w, s] from the bins of walker w in the order first, first + 1, .. (mod nbins).
-// stack [nw, nbins, 2, M, M]; src_w < 0: block b works on walker b / 2, otherwise every block works on walker src_w and
-// writes walker 0's place (grid of 2 blocks).  det may be null.
-__global__ __launch_bounds__(THC_THREADS) void thermal_cgreens_kernel(const cplx *stack, cplx *G, cplx *det, int M, int nbins,
-                                                                       int first, int src_w) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int LD = M | 1, tid = threadIdx.x;
-    const size_t mat = thc_mat(M);
-    cplx *W = (cplx *)smem, *Qt = W + mat, *T = Qt + mat, *X = T + mat;
-    cplx *D = X + mat, *v = D + 64, *part = v + 64, *aux = part + 512;
-    int *perm = (int *)(aux + 192);
-    const int w = src_w < 0 ? blockIdx.x >> 1 : src_w, s = blockIdx.x & 1;
-    const long mm = (long)M * M;
-    const cplx *Bw = stack + ((long)w * nbins * 2 + s) * mm;         // bin b at Bw + b * 2 * mm
-
-    {
-        const cplx *B = Bw + (long)first * 2 * mm;
-        for (int e = tid; e < M * M; e += THC_THREADS) W[(e / M) * LD + e % M] = B[e];
-    }
-    __syncthreads();
-    thc_qrcp(W, Qt, M, LD, perm, v, part);
-    // T = D^-1 R P^T
-    for (int e = tid; e < M * M; e += THC_THREADS) {
-        const int i = e / M, j = e % M;
-        T[i * LD + perm[j]] = j >= i ? cdiv(W[i * LD + j], W[i * LD + i]) : cmake(0.0, 0.0);
-    }
-    if (tid < M) D[tid] = W[tid * LD + tid];
-    __syncthreads();
-    for (int n = 1; n < nbins; ++n) {
-        const cplx *B = Bw + (long)((first + n) % nbins) * 2 * mm;
-        // W = (B Q) D, Q[k][c] = conj(Qt[c][k])
-        thc_gemm(M, [&](int r, int k) { return B[r * M + k]; }, [&](int k, int c) { return cconj(Qt[c * LD + k]); },
-                 [&](int r, int c, cplx x) { W[r * LD + c] = cmul(x, D[c]); });
-        __syncthreads();
-        thc_qrcp(W, Qt, M, LD, perm, v, part);
-        for (int e = tid; e < M * M; e += THC_THREADS) {
-            const int i = e / M, j = e % M;
-            X[i * LD + perm[j]] = j >= i ? cdiv(W[i * LD + j], W[i * LD + i]) : cmake(0.0, 0.0);
-        }
-        if (tid < M) D[tid] = W[tid * LD + tid];
-        __syncthreads();
-        // T <- t T (into W, whose R is used up; then the two change names)
-        thc_gemm(M, [&](int r, int k) { return X[r * LD + k]; }, [&](int k, int c) { return T[k * LD + c]; },
-                 [&](int r, int c, cplx x) { W[r * LD + c] = x; });
-        __syncthreads();
-        cplx *t = T; T = W; W = t;
-    }
-    // (D_b Q^H + D_s T) G = D_b Q^H, D_b = 1 / |D| and D_s = D / |D| where |D| > 1, else D_b = 1 and D_s = D
-    for (int e = tid; e < M * M; e += THC_THREADS) {
-        const int i = e / M, j = e % M;
-        const cplx d = D[i];
-        const double ad = hypot(d.x, d.y);
-        const double db = ad > 1.0 ? 1.0 / ad : 1.0;
-        const cplx ds = ad > 1.0 ? cmake(d.x / ad, d.y / ad) : d;
-        const cplx r = cscale(Qt[i * LD + j], db);
-        cplx x = r;
-        cfma(x, ds, T[i * LD + j]);
-        X[i * LD + j] = x;
-        W[i * LD + j] = r;
-    }
-    __syncthreads();
-    thc_solve(X, W, M, LD, aux, aux + 64, aux + 128);
-    const long slot = (long)(src_w < 0 ? w : 0) * 2 + s;
-    cplx *Gd = G + slot * mm;
-    for (int e = tid; e < M * M; e += THC_THREADS) {
-        const cplx g = W[(e / M) * LD + e % M];
-        Gd[e] = g;
-        X[(e / M) * LD + e % M] = g;
-    }
-    if (!det) return;
-    __syncthreads();
-    const cplx dg = thc_det(X, M, LD, aux);
-    if (tid == 0) det[slot] = dg;
-}
+inline size_t thc_slice_lds(int M) { return sizeof(cplx) * 3 * ts_mat(M); }
 
 struct ThcSliceArgs {
     const cplx *vhs;            // [nw, M, M]
@@ -282,15 +30,15 @@ struct ThcSliceArgs {
     int M, nbins, block, counter;
 };
 
-__global__ __launch_bounds__(THC_THREADS) void thermal_cslice_kernel(ThcSliceArgs a) {
+__global__ __launch_bounds__(TH_THREADS) void thermal_cslice_kernel(ThcSliceArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int M = a.M, LD = M | 1, tid = threadIdx.x, w = blockIdx.x;
-    const size_t mat = thc_mat(M);
+    const size_t mat = ts_mat(M);
     cplx *V = (cplx *)smem, *T1 = V + mat, *T2 = T1 + mat;
     const long mm = (long)M * M;
     const cplx *Vw = a.vhs + (long)w * mm;
     // Horner: T_6 = I + V / 6, T_n = I + V T_{n + 1} / n, BV = T_1
-    for (int e = tid; e < M * M; e += THC_THREADS) {
+    for (int e = tid; e < M * M; e += TH_THREADS) {
         const int r = e / M, c = e % M;
         const cplx x = Vw[e];
         V[r * LD + c] = x;
@@ -299,7 +47,7 @@ __global__ __launch_bounds__(THC_THREADS) void thermal_cslice_kernel(ThcSliceArg
     __syncthreads();
     for (int n = 5; n >= 1; --n) {
         const double dn = (double)n;
-        thc_gemm(M, [&](int r, int k) { return V[r * LD + k]; }, [&](int k, int c) { return T1[k * LD + c]; },
+        ts_gemm<cplx>(M, [&](int r, int k) { return V[r * LD + k]; }, [&](int k, int c) { return T1[k * LD + c]; },
                  [&](int r, int c, cplx x) { T2[r * LD + c] = cmake(x.x / dn + (r == c ? 1.0 : 0.0), x.y / dn); });
         __syncthreads();
         cplx *t = T1; T1 = T2; T2 = t;
@@ -311,16 +59,16 @@ __global__ __launch_bounds__(THC_THREADS) void thermal_cslice_kernel(ThcSliceArg
         cplx *S = a.stack + (((long)w * a.nbins + a.block) * 2 + s) * mm;
         // B = diag(d) (BV diag(d)) as the reference forms it; right <- B right, right = I at the start of a bin
         if (a.counter == 0) {
-            for (int e = tid; e < M * M; e += THC_THREADS) {
+            for (int e = tid; e < M * M; e += TH_THREADS) {
                 const int r = e / M, c = e % M;
                 T2[r * LD + c] = cscale(cscale(BV[r * LD + c], d[c]), d[r]);
             }
         } else {
-            thc_gemm(M, [&](int r, int k) { return cscale(cscale(BV[r * LD + k], d[k]), d[r]); },
+            ts_gemm<cplx>(M, [&](int r, int k) { return cscale(cscale(BV[r * LD + k], d[k]), d[r]); },
                      [&](int k, int c) { return R[k * M + c]; }, [&](int r, int c, cplx x) { T2[r * LD + c] = x; });
         }
         __syncthreads();
-        for (int e = tid; e < M * M; e += THC_THREADS) {
+        for (int e = tid; e < M * M; e += TH_THREADS) {
             const int r = e / M, c = e % M;
             const cplx x = T2[r * LD + c];
             R[e] = x;
@@ -334,14 +82,14 @@ __global__ __launch_bounds__(THC_THREADS) void thermal_cslice_kernel(ThcSliceArg
 // |xbar| > fb_bound scaled to unit modulus (counted in counters[0], as the ground-state field kernel counts its own),
 // xs = xi - xbar, cmf = -sqrt(dt) xs . mf, cfb = xi . xbar - xbar . xbar / 2 (unconjugated).  Every thread sums its
 // fields in order and the 256 partial sums are added in a fixed tree: the same bits on every run.
-__global__ __launch_bounds__(THC_THREADS) void thermal_cfields_kernel(const cplx *vbias, const double *xi, const cplx *mf,
+__global__ __launch_bounds__(TH_THREADS) void thermal_cfields_kernel(const cplx *vbias, const double *xi, const cplx *mf,
                                                                        cplx *xbar, cplx *xs, cplx *cmf, cplx *cfb, int K,
                                                                        double sqrt_dt, double fb_bound,
                                                                        unsigned long long *counters) {
-    __shared__ double red[7][THC_THREADS];
+    __shared__ double red[7][TH_THREADS];
     const int w = blockIdx.x, tid = threadIdx.x;
     double acc[7] = {0, 0, 0, 0, 0, 0, 0};      // xs . mf (re, im), xi . xbar (re, im), xbar . xbar (re, im), clipped
-    for (int n = tid; n < K; n += THC_THREADS) {
+    for (int n = tid; n < K; n += TH_THREADS) {
         const long e = (long)w * K + n;
         const cplx v = vbias[e], m = mf[n];
         cplx b = cmake(-sqrt_dt * v.x, -sqrt_dt * v.y);
@@ -360,7 +108,7 @@ __global__ __launch_bounds__(THC_THREADS) void thermal_cfields_kernel(const cplx
 #pragma unroll
     for (int q = 0; q < 7; ++q) red[q][tid] = acc[q];
     __syncthreads();
-    for (int o = THC_THREADS / 2; o > 0; o >>= 1) {
+    for (int o = TH_THREADS / 2; o > 0; o >>= 1) {
         if (tid < o)
 #pragma unroll
             for (int q = 0; q < 7; ++q) red[q][tid] += red[q][tid + o];
@@ -393,30 +141,6 @@ __global__ void thermal_cweight_kernel(double *weight, cplx *M0, const cplx *Mne
     M0[2 * w + 1] = Mnew[2 * w + 1];
 }
 
-// P_s = I - G_s^T [nw, 2, M, M] for the force bias and the energy, nav = Re(tr P_up + tr P_down) (nav may be null)
-__global__ __launch_bounds__(THC_THREADS) void thermal_crdm_kernel(const cplx *G, cplx *P, double *nav, int M) {
-    __shared__ double red[THC_THREADS];
-    const int w = blockIdx.x, tid = threadIdx.x;
-    const long mm = (long)M * M;
-    const cplx *Gw = G + (long)w * 2 * mm;
-    cplx *Pw = P + (long)w * 2 * mm;
-    for (int e = tid; e < 2 * M * M; e += THC_THREADS) {
-        const int s = e / (M * M), r = (e / M) % M, c = e % M;
-        const cplx g = Gw[s * mm + (long)c * M + r];
-        Pw[e] = cmake((r == c ? 1.0 : 0.0) - g.x, -g.y);
-    }
-    if (!nav) return;
-    double t = 0.0;
-    for (int e = tid; e < 2 * M; e += THC_THREADS) t += 1.0 - Gw[(e / M) * mm + (long)(e % M) * M + e % M].x;
-    red[tid] = t;
-    __syncthreads();
-    for (int o = THC_THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) nav[w] = red[0];
-}
-
 // walker blockIdx.y: bins <- diag(BTpow) [2, M]; unless bins_only also G <- G0, right <- I, weight <- 1, and with_m0
 // M0 <- M00
 __global__ void thermal_creset_kernel(cplx *stack, cplx *G, cplx *right, cplx *M0, double *weight, const double *BTpow,
@@ -438,33 +162,10 @@ __global__ void thermal_creset_kernel(cplx *stack, cplx *G, cplx *right, cplx *M
     if (i == 0) weight[w] = 1.0;
 }
 
-int thc_launch_greens(afq_handle *h, const cplx *stack, cplx *G, cplx *det, int first, int src_w, int nblocks) {
-    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-    const size_t lds = thc_greens_lds(h->M);
-    AFQ_HIP(h, afq_raise_lds((const void *)thermal_cgreens_kernel, lds, lds_set));
-    AFQ_LAUNCH(h, thermal_cgreens_kernel, dim3(nblocks), dim3(THC_THREADS), lds, h->stream, stack, G, det, h->M, h->th_nbins,
-               first, src_w);
-    AFQ_POST(h);
-    return AFQ_OK;
-}
-
-int thc_first_bin(const afq_handle *h, int slice_ix) {
-    int bin_ix = slice_ix / h->th_ss;
-    if (bin_ix == h->th_nbins) bin_ix = -1;
-    return (bin_ix + 1) % h->th_nbins;
-}
-
-int thc_need(afq_handle *h) {
-    if (!h->th_on || !h->th_cplx || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, "thermal walkers: afq_thermal_configure_continuous first");
-    if (h->prop_pending) AFQ_FAIL(h, AFQ_ESTATE, "a step is half done: afq_propagate_finish first");
-    hipSetDevice(h->device);
-    return AFQ_OK;
-}
-
 }  // namespace
 
 int k_thermal_c_greens(afq_handle *h, int slice_ix) {
-    return thc_launch_greens(h, h->thc_stack, h->thc_G, h->thc_det, thc_first_bin(h, slice_ix), -1, 2 * h->nw);
+    return ts_launch_greens<cplx>(h, h->thc_stack, h->thc_G, h->thc_det, ts_first_bin(h, slice_ix), -1, 2 * h->nw);
 }
 
 // walkers/handler.py:424-430: bins, G, weight.  The reference's reset leaves walker.M0 at the determinant the last path
@@ -476,7 +177,7 @@ int k_thermal_c_reset(afq_handle *h, bool with_m0) {
     AFQ_LAUNCH(h, thermal_creset_kernel, dim3((unsigned)((per + 255) / 256), 1), dim3(256), 0, h->stream, h->thc_stack, h->thc_G,
                h->thc_right, h->thc_M0, h->weight, h->thc_BTpow, h->thc_G0, h->thc_M00, nbins, M, 1, 0);
     AFQ_POST(h);
-    AFQ_TRY(thc_launch_greens(h, h->thc_stack, h->thc_G0, h->thc_M00, thc_first_bin(h, 0), 0, 2));
+    AFQ_TRY(ts_launch_greens<cplx>(h, h->thc_stack, h->thc_G0, h->thc_M00, ts_first_bin(h, 0), 0, 2));
     AFQ_LAUNCH(h, thermal_creset_kernel, dim3((unsigned)((per + 255) / 256), h->nw), dim3(256), 0, h->stream, h->thc_stack,
                h->thc_G, h->thc_right, h->thc_M0, h->weight, h->thc_BTpow, h->thc_G0, h->thc_M00, nbins, M, 0, with_m0 ? 1 : 0);
     AFQ_POST(h);
@@ -485,17 +186,11 @@ int k_thermal_c_reset(afq_handle *h, bool with_m0) {
 }
 
 int k_thermal_c_energy(afq_handle *h, double *E_out, double *nav_out) {
-    AFQ_LAUNCH(h, thermal_crdm_kernel, dim3(h->nw), dim3(THC_THREADS), 0, h->stream, h->thc_G, h->G, h->th_nav, h->M);
-    AFQ_POST(h);
+    AFQ_TRY(ts_launch_rdm<cplx>(h, h->thc_G, h->th_nav));
     cplx *two = nullptr, *E = nullptr;                  // (the per-q pair sums are scratch here)
     AFQ_TRY(k_ueg_sf_two(h, h->nw, &two, &E));
     AFQ_TRY(k_ueg_pair_sums(h, h->G, h->nw, h->energy, two));
-    if (E_out) {
-        std::vector<double> e(6 * (size_t)h->nw);
-        AFQ_TRY(copy_out(h, e.data(), h->energy, sizeof(cplx) * 3 * (size_t)h->nw));
-        for (size_t i = 0; i < 3 * (size_t)h->nw; ++i) E_out[i] = e[2 * i];
-    }
-    return copy_out(h, nav_out, h->th_nav, sizeof(double) * (size_t)h->nw);
+    return th_energy_out(h, E_out, nav_out);
 }
 
 extern "C" {
@@ -515,11 +210,11 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
     if (!h->kind || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_configure_continuous: set the system and allocate the walkers first");
     if (h->kind != AFQ_SYS_UEG) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers with continuous fields: UEG systems only (no Generic, no continuous Hubbard)");
     const int M = h->M;
-    if (thc_greens_lds(M) > THC_LDS_MAX) {
+    if (ts_greens_lds<cplx>(M) > THC_LDS_MAX) {
         int mmax = M;
-        while (mmax > 1 && thc_greens_lds(mmax) > THC_LDS_MAX) --mmax;
+        while (mmax > 1 && ts_greens_lds<cplx>(mmax) > THC_LDS_MAX) --mmax;
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers with continuous fields: M = " + std::to_string(M) + " plane waves need " +
-                 std::to_string(thc_greens_lds(M)) + " bytes of LDS for the complex Green's function, a work-group has " +
+                 std::to_string(ts_greens_lds<cplx>(M)) + " bytes of LDS for the complex Green's function, a work-group has " +
                  std::to_string(THC_LDS_MAX) + " (M <= " + std::to_string(mmax) + ")");
     }
     if (k_comm_size(h) > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: one rank only");
@@ -569,7 +264,7 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
 int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi_out) {
     AFQ_API(h, "afq_thermal_propagate_continuous");
     if (!h) return AFQ_EINVAL;
-    AFQ_TRY(thc_need(h));
+    AFQ_TRY(th_need(h, true));
     if (h->th_slice >= h->th_L) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_propagate_continuous: the path is complete (afq_thermal_reset starts the next)");
     const int M = h->M;
     const size_t nf = (size_t)h->nw * h->K;
@@ -577,10 +272,9 @@ int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi
     if (xi) AFQ_HIP(h, hipMemcpyAsync(h->xi, xi, sizeof(double) * nf, hipMemcpyHostToDevice, h->stream));
     else AFQ_TRY(k_rng_normal_into(h, h->xi, (long)nf));
     // P = I - G^T, vbias = P . [iA | iB], xbar = -sqrt(dt) vbias clipped at 1, xs, cmf, cfb (planewave.py:219-276)
-    AFQ_LAUNCH(h, thermal_crdm_kernel, dim3(h->nw), dim3(THC_THREADS), 0, h->stream, h->thc_G, h->G, (double *)nullptr, M);
-    AFQ_POST(h);
+    AFQ_TRY(ts_launch_rdm<cplx>(h, h->thc_G, nullptr));
     AFQ_TRY(k_vbias_ueg(h));
-    AFQ_LAUNCH(h, thermal_cfields_kernel, dim3(h->nw), dim3(THC_THREADS), 0, h->stream, h->vbias, h->xi, h->thc_mf, h->xbar,
+    AFQ_LAUNCH(h, thermal_cfields_kernel, dim3(h->nw), dim3(TH_THREADS), 0, h->stream, h->vbias, h->xi, h->thc_mf, h->xbar,
                h->xs, h->cmf, h->cfb, h->K, h->sqrt_dt, h->thc_fb_bound, h->counters);
     AFQ_POST(h);
     AFQ_TRY(k_vhs_ueg(h));                              // VHS = sqrt(dt) (iA xs[:nq] + iB xs[nq:])
@@ -592,7 +286,7 @@ int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi
         static size_t lds_set[AFQ_MAX_DEVICES] = {0};
         const size_t lds = thc_slice_lds(M);
         AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_kernel, lds, lds_set));
-        AFQ_LAUNCH(h, thermal_cslice_kernel, dim3(h->nw), dim3(THC_THREADS), lds, h->stream, a);
+        AFQ_LAUNCH(h, thermal_cslice_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a);
         AFQ_POST(h);
     }
     // PropagatorStack.update_full_rank's counters (stack.py:322-324)
@@ -600,7 +294,7 @@ int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi
     h->th_block = h->th_slice / h->th_ss;
     h->th_counter = (h->th_counter + 1) % h->th_ss;
     // G = [I + S_{nbins - 1} .. S_0]^-1 on the walker's current bins, Mnew = det G, the weight
-    AFQ_TRY(thc_launch_greens(h, h->thc_stack, h->thc_G, h->thc_det, 0, -1, 2 * h->nw));
+    AFQ_TRY(ts_launch_greens<cplx>(h, h->thc_stack, h->thc_G, h->thc_det, 0, -1, 2 * h->nw));
     AFQ_LAUNCH(h, thermal_cweight_kernel, dim3((h->nw + 127) / 128), dim3(128), 0, h->stream, h->weight, h->thc_M0, h->thc_det,
                h->cmf, h->cfb, h->nw);
     AFQ_POST(h);
