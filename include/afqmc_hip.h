@@ -421,6 +421,15 @@ int afq_set_step_fusion(afq_handle *h, int mode);
  *      afq_propagate_finish (one weight_kernel launch).
  * AFQ_EINVAL for any other value.                                                                                   */
 int afq_set_step_fusion_scope(afq_handle *h, int scope);
+/* Mode 2's launch, for the walkers of the resident body (single real closed trial, which that tail's one-spin path needs
+ * anyway): with psi^H B made once per upload of the trial or the propagator, the tail's overlap matrix is (psi^H B) S -- S the
+ * Taylor sum the last product leaves in LDS --: the eight waves multiply it ahead of the closing one-body pass, one wave
+ * inverts it while the others run that pass, and the tail starts at O^-1 phi^T.  The overlap matrix is rounded as (psi^H B) S instead of psi^H (B S): overlaps,
+ * weights and Ghalf of those walkers move at rounding level.
+ *   1  (default) on      0  off: the launch of before, bit for bit
+ * Modes 0 and 1, and every walker that does not take the resident body, are not touched.  afq_counters_ext [8] counts the
+ * walker steps that took it.  AFQ_EINVAL for any other value.                                                       */
+int afq_set_step_tail_overlap(afq_handle *h, int on);
 
 /* Force bias of a multi-determinant trial (propagation/generic.py:154-157, walkers/multi_det.py:283-290) has two
  * device algorithms with the same result:
@@ -716,7 +725,8 @@ int afq_last_launch(afq_handle *h, char *buf, int len, uint64_t *queued, uint64_
  * Gauss-Jordan flagged as poorly conditioned block-wise and handed to the step-by-step kernel (diagnostic),
  * [3]=walker steps the fused propagator took through its closed-shell deal (spin blocks bitwise equal)       */
 int afq_counters(afq_handle *h, int64_t *out, int reset);
-/* the same, first n counters (n <= 8): [4]=walker energy evaluations whose exchange energy was evaluated for one spin and
+/* the same, first n counters (n <= 9; [8]=walker steps whose overlap matrix was made and inverted under the fused propagator's
+ * closing pass, afq_set_step_tail_overlap): [4]=walker energy evaluations whose exchange energy was evaluated for one spin and
  * counted twice (closed-shell population, decided on the device: energy_finish_kernel), [5]=walker Green's functions
  * computed for one spin (closed-shell walker, greens_small_kernel), [6]=per-determinant overlaps of a multi-determinant
  * trial that came out as NaN (0 x inf behind a zero pivot of a singular overlap matrix) and were taken as zero overlaps,

@@ -68,6 +68,7 @@ int build_rH1(afq_handle *h, const std::vector<double> &H1, const std::vector<do
 // host copies kept for derived operands (small: H1 and psi only)
 struct afq_host_cache {
     std::vector<double> H1, psi;
+    std::vector<double> BH1;        // Re BH1[0] [M, M] of the last afq_set_propagator (psiB_cT is made of it and psi)
 };
 static afq_host_cache *cache_of(afq_handle *h);
 
@@ -75,6 +76,8 @@ struct afq_handle_full : afq_handle {
     afq_host_cache cache;
 };
 static afq_host_cache *cache_of(afq_handle *h) { return &static_cast<afq_handle_full *>(h)->cache; }
+
+static int build_psiB(afq_handle *h);
 
 static int upload_psi(afq_handle *h, const double *psi) {
     const size_t n = (size_t)h->M * h->nt;
@@ -100,6 +103,29 @@ static int upload_psi(afq_handle *h, const double *psi) {
     }
     rc = dev_upload(h, LT_TRIAL, &o.psic, pc.data(), n);
     select_det(h, h->cur_det, true);
+    return rc ? rc : build_psiB(h);
+}
+
+// psiB_cT = psi^H B (afq_internal.h) from the host copies of the trial and the propagator: after every upload of either.
+// Anything but a single real closed trial with one real one-body matrix for both spins leaves the slot null, and the fused
+// propagator's tail then evaluates the overlap matrix itself.
+static int build_psiB(afq_handle *h) {
+    afq_host_cache *c = cache_of(h);
+    const int M = h->M, nt = h->nt, na = h->na;
+    const bool ok = h->have_prop && h->ndet <= 1 && h->psi_stride == 0 && h->psi_real && h->psi_closed &&
+                    h->bh1_real && h->bh1_same && c->psi.size() == (size_t)2 * M * nt && c->BH1.size() == (size_t)M * M;
+    h->psiB_psi = nullptr; h->psiB_bh1 = nullptr;
+    if (!ok) return dev_alloc(h, LT_TRIAL, &h->psiB_cT, 0);
+    std::vector<double> pb((size_t)na * M, 0.0);
+    for (int m = 0; m < M; ++m)
+        for (int i = 0; i < na; ++i) {
+            const double p = c->psi[2 * ((size_t)m * nt + i)];
+            const double *brow = &c->BH1[(size_t)m * M];
+            double *out = &pb[(size_t)i * M];
+            for (int k = 0; k < M; ++k) out[k] += p * brow[k];
+        }
+    const int rc = dev_upload(h, LT_TRIAL, &h->psiB_cT, pb.data(), pb.size());
+    if (!rc) { h->psiB_psi = h->dets[h->cur_det].psi; h->psiB_bh1 = h->BH1; }
     return rc;
 }
 
@@ -552,6 +578,11 @@ int afq_set_propagator(afq_handle *h, const double *BH1, const double *mf_shift,
     h->bh1_real = true;
     h->bh1_same = memcmp(BH1, BH1 + (size_t)2 * h->M * h->M, sizeof(double) * 2 * h->M * h->M) == 0;
     for (size_t i = 0, n = (size_t)2 * h->M * h->M; i < n && h->bh1_real; ++i) h->bh1_real = BH1[2 * i + 1] == 0.0;
+    {
+        std::vector<double> &b = cache_of(h)->BH1;
+        b.resize((size_t)h->M * h->M);
+        for (size_t i = 0; i < b.size(); ++i) b[i] = BH1[2 * i];
+    }
     if ((rc = dev_upload(h, LT_HANDLE, &h->mf_shift, mf_shift, (size_t)h->K))) return rc;
     if (h->kind == AFQ_SYS_UEG && (rc = k_ueg_fast_propagator(h, BH1))) return rc;
     h->dt = dt; h->sqrt_dt = std::pow(dt, 0.5); h->exp_order = exp_order;
@@ -561,6 +592,7 @@ int afq_set_propagator(afq_handle *h, const double *BH1, const double *mf_shift,
     h->vhs_diag = h->kind == AFQ_SYS_HUBBARD;
     h->nv = (h->kind == AFQ_SYS_HUBBARD && (flags & AFQ_PROP_HUBBARD_SPIN)) ? 2 : 1;
     h->have_prop = true;
+    if ((rc = build_psiB(h))) return rc;
     if (h->nw && (old_nv != h->nv || old_diag != h->vhs_diag || !h->vhs)) {
         // (diagonal potential: a second block of the same size holds its Taylor factors)
         const size_t per = h->vhs_diag ? (size_t)2 * h->nv * h->M : (size_t)h->nv * h->M * h->M;
@@ -1168,6 +1200,12 @@ int afq_set_step_fusion_scope(afq_handle *h, int scope) {
     return AFQ_OK;
 }
 
+int afq_set_step_tail_overlap(afq_handle *h, int on) {
+    if (!h || on < 0 || on > 1) return AFQ_EINVAL;
+    h->step_tail_overlap = on;
+    return AFQ_OK;
+}
+
 int afq_propagator_closed_form(afq_handle *h, int *mode) {
     if (!h || !mode) return AFQ_EINVAL;
     *mode = k_prop_closed_resident(h) ? 2 : 1;
@@ -1749,6 +1787,8 @@ int afq_set_propagator_hirsch(afq_handle *h, const double *bt2, double dt, int c
     h->bh1_real = true;         // (expm of a real hopping matrix: the one-body GEMM then needs two real products per pair)
     for (size_t i = 0, n = (size_t)2 * h->M * h->M; i < n && h->bh1_real; ++i) h->bh1_real = bt2[2 * i + 1] == 0.0;
     h->bh1_same = false;
+    cache_of(h)->BH1.clear();
+    if ((rc = build_psiB(h))) return rc;
     // propagation/hubbard.py:66-82
     typedef std::complex<double> C;
     C gamma, auxf[2][2], wfac[2];

@@ -40,7 +40,7 @@ __device__ inline cplx cdiv(cplx a, cplx b) {
 enum { AFQ_HS_HERMITIAN = 1, AFQ_HS_GENERAL = 2 };       // afq_handle::hs_cplx
 enum { T_GREENS = 0, T_ONEBODY, T_FB, T_VHS, T_EXP, T_OVLP, T_QR, T_ENERGY, T_COUNT };
 
-#define AFQ_NCOUNTERS 8     // afq_counters_ext (include/afqmc_hip.h)
+#define AFQ_NCOUNTERS 9     // afq_counters_ext (include/afqmc_hip.h)
 
 struct afq_handle {
     int device = 0;
@@ -78,6 +78,7 @@ struct afq_handle {
     int exx_mode = 0;               // afq_set_exchange_algorithm: 0 auto, 1 T-intermediate (exx_kernel), 2 quadratic form
     int step_fusion_mode = 2;       // afq_set_step_fusion: 0 never, 1 tail behind the 4-multiplication body, 2 behind the 3-multiplication one
     int step_fusion_scope = 0;      // afq_set_step_fusion_scope: 0 announced one-call steps, 1 every step of the shape class
+    int step_tail_overlap = 1;      // afq_set_step_tail_overlap: the mode-2 tail's overlap matrix and inverse under the closing pass
     int prop_closed_mode = 0;       // afq_set_propagator_closed_form: 0 auto, 1 streamed deal, 2 V resident in registers (where eligible)
     cplx *exq_y = nullptr;          // [2 * slices, nw, ceil(N M / 16)] per-tile partial sums of the quadratic form
     size_t exq_y_len = 0;
@@ -127,6 +128,11 @@ struct afq_handle {
     long psi_stride = 0;            // elements between per-walker 'trials' (back-propagation only; 0 = shared psi)
     bool psi_real = false;          // every imaginary part of the uploaded trial is exactly zero
     bool psi_closed = false;        // na == nb and the alpha and beta blocks of the (single, shared) trial are bitwise equal
+    // psi^H B for the fused propagator's early overlap (k_fused_closed.h): psiB_cT[i][k] = sum_m psi[m][i] BH1[0][m][k], [na, M]
+    // real, made on the host whenever the trial or the propagator is uploaded; null unless the trial is single, real and
+    // closed and BH1 real and the same for both spins
+    double *psiB_cT = nullptr;
+    const void *psiB_psi = nullptr, *psiB_bh1 = nullptr;    // the device trial and propagator it was made for (never dereferenced)
     // Closed-shell populations (round 5).  The Green's function kernel checks every walker's spin blocks for bitwise equality
     // (greens_small_kernel); a walker that fails raises closed_bad to the epoch of that launch (gf.closed says which Ghalf
     // the verdict is about).  The host never reads the flag.

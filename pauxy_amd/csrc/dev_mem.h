@@ -6,7 +6,7 @@
 // handle field, and nothing frees one but these three and DevMem::release:
 //   LT_HANDLE   afq_destroy              estimates, counters, closed_bad, scal, zero_page, BH1, mf_shift
 //   LT_SYSTEM   a new afq_set_system_*   the Hamiltonian's operands and what is derived from them alone
-//   LT_TRIAL    a new system or trial    dets[d].* (below), psicT, coeffs, msd_psicT*
+//   LT_TRIAL    a new system or trial    dets[d].* (below), psicT, coeffs, msd_psicT*, psiB_cT
 //   LT_WALKERS  afq_walkers_alloc        everything sized by nw, the windows configured after the walkers included
 // release(lifetime) frees every block of that lifetime, nulls its slot and zeroes the length that goes with it, so an
 // "ensure" or "grow" of a later configuration never meets a block sized for an earlier one.

@@ -56,9 +56,20 @@ struct GreensLaunch {
 // The body: walker w, `smem` the work-group's dynamic LDS (launch_greens' size).  known_closed: the caller has established that
 // the walker's spin blocks are bitwise equal (the propagator's resident body stores one result to both): the compare of the
 // copy in LDS is left out, afq_counters_ext [5] still counts the walker and closed_bad is not touched.
-template <bool INVERSE, bool WGJ>
+// EARLY (the fused propagator's 3-multiplication tail alone; off, greens_small_kernel and the other tail compile the text they
+// had): a walker whose early.on is set -- uniform over the work-group -- comes with phases 0 to 2 done by the resident body
+// (k_fused_closed.h): phi_l and O^-1 of spin up lie in `smem` where this body would have left them, and the determinant of
+// spin up is in early.ph / early.la of wave 7.  Such a walker is closed: afq_counters_ext [5] counts it, [8] counts the path.
+struct EarlyTail {
+    bool on;
+    cplx ph;
+    int la;
+};
+
+template <bool INVERSE, bool WGJ, bool EARLY = false>
 __device__ __attribute__((always_inline)) inline void greens_small_body(const GreensArgs &a, const WeightArgs &wa, const int w,
-                                                                       unsigned char *smem, const bool known_closed) {
+                                                                       unsigned char *smem, const bool known_closed,
+                                                                       const EarlyTail *early = nullptr) {
     __shared__ cplx ph_s[2];
     __shared__ double la_s[2];
     __shared__ unsigned long long pmax_s[2][48];
@@ -205,15 +216,22 @@ __device__ __attribute__((always_inline)) inline void greens_small_body(const Gr
             if (WGJ) break;
         }
     };
-    if (yreal) phase01(std::true_type{});
+    bool skip012 = false;                                     // (EARLY: uniform over the work-group)
+    if constexpr (EARLY) skip012 = early->on;
+    if (skip012) {
+        closed = true;
+        if (tid == 0 && a.counters) { atomicAdd(&a.counters[5], 1ull); atomicAdd(&a.counters[8], 1ull); }
+        if (tid == 448) { ph_s[0] = early->ph; ph_s[1] = early->ph; la_s[0] = (double)early->la; la_s[1] = (double)early->la; }
+    }
+    else if (yreal) phase01(std::true_type{});
     else phase01(std::false_type{});
-    __syncthreads();
+    if (!skip012) __syncthreads();
     // ---- phase 2
     __shared__ cplx gj_row[2][32], gj_piv[2][32];
     __shared__ int gj_prow[2][32];
     // (the two single-wave inversions run on different SIMDs: spin up on wave 0, spin down on wave 1 of its group = wave 5)
     if (WGJ) {
-        if (wave == g && !(closed && g == 1)) {
+        if (wave == g && !(closed && g == 1) && !skip012) {
             cplx ph;
             int la;
             gj_wave32(O, n, lane, INVERSE, gj_row[g], gj_piv[g], gj_prow[g], ph, la);

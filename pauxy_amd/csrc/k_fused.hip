@@ -134,7 +134,9 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr bool MUL3 = false;
 #define PF_LEAVE(stored_closed_) return
+#define PF_RESIDENT(KS_) prop_closed_resident<KS_, MUL3>(a, smem, phi, vhs)
 #include "k_fused_body.h"
+#undef PF_RESIDENT
 #undef PF_LEAVE
 }
 
@@ -145,14 +147,28 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
 // weight update where the shift is known, as greens_small_kernel<true, true> with the same arguments would leave them.  A
 // walker of the resident body is closed by construction (one result stored to both spin blocks) and skips the tail's compare.
 // A separate overload, not a flag of the kernel above: that one keeps its signature, its code and its registers.
+// psiB (MUL3 alone; null: off): psi^H B [na, M], real -- afq_set_step_tail_overlap.  A walker of the resident body then has its
+// overlap matrix multiplied from the Taylor sum ahead of the closing one-body pass and inverted by wave 7 under it
+// (k_fused_closed.h), and the tail starts at its phase 3.  Every other walker of the launch, and every walker with psiB
+// null, runs the statements it ran before.
 template <bool NARROW, int FULL, bool TAIL, bool MUL3>
-__global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a, GreensArgs ga, WeightArgs wa) {
+__global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a, GreensArgs ga, WeightArgs wa, const double *psiB) {
     static_assert(TAIL && !NARROW && FULL == 7, "the tail rides on the full wide deal only");
     extern __shared__ __align__(16) unsigned char smem[];
     bool stored_closed = false;
+    EarlyTail early;
+    early.on = false;
     do {
 #define PF_LEAVE(stored_closed_) { stored_closed = (stored_closed_); break; }
+#define PF_RESIDENT(KS_)                                                                                      \
+    do {                                                                                                      \
+        if constexpr (MUL3) {                                                                                 \
+            if (psiB) prop_closed_resident<KS_, true, true>(a, smem, phi, vhs, psiB, &early);                 \
+            else prop_closed_resident<KS_, true>(a, smem, phi, vhs);                                          \
+        } else prop_closed_resident<KS_, false>(a, smem, phi, vhs);                                           \
+    } while (0)
 #include "k_fused_body.h"
+#undef PF_RESIDENT
 #undef PF_LEAVE
     } while (0);
     // the tail's addressing starts from here: nothing of it may be computed (and held in registers) across the bodies above
@@ -160,7 +176,8 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a, Gree
     __syncthreads();
     int w = blockIdx.x;
     asm volatile("" : "+s"(w));
-    greens_small_body<true, true>(ga, wa, w, smem, stored_closed);
+    if constexpr (MUL3) greens_small_body<true, true, true>(ga, wa, w, smem, stored_closed, &early);
+    else greens_small_body<true, true>(ga, wa, w, smem, stored_closed);
 }
 
 int k_prop_fused_supported(afq_handle *h) {
@@ -210,6 +227,13 @@ int k_prop_fused(afq_handle *h, const GreensLaunch *tail, bool mul3) {
     const size_t lds = (size_t)NCH * 8192 + (size_t)PF_D * 16384;
     static size_t lds_set[8][AFQ_MAX_DEVICES] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
     const bool narrow = h->na <= 16 && h->nb <= 16;
+    // the overlap matrix and its inverse under the closing pass of the resident body (afq_set_step_tail_overlap): the
+    // 3-multiplication tail of a step whose closed walkers take the tail's one-spin path against a real trial -- psiB_cT exists
+    // for such a trial and one real one-body matrix only (afq_api.hip)
+    const bool early = tail && mul3 && h->step_tail_overlap && h->psiB_cT && k_prop_closed_resident(h) &&
+                       tail->a.psi_real && tail->a.psi_closed && tail->a.psi_stride == 0 &&
+                       (const void *)tail->a.psi == h->psiB_psi && (const void *)h->BH1 == h->psiB_bh1 &&
+                       tail->a.gsum && tail->a.ghalf && !tail->a.oinv;
     KernelTrace kt(h, AFQ_K_PROPAGATOR);
     {   // matrix-pipe flops of this launch: (order complex products by 3 multiplications + 2 one-body applications by 2 or
         // 3) x k-steps of 4 x existing 16 x 16 tiles (2048 flop per v_mfma_f64_16x16x4, 512 per 4x4x4 remainder unit)
@@ -241,6 +265,9 @@ int k_prop_fused(afq_handle *h, const GreensLaunch *tail, bool mul3) {
             const double spin = 2048.0 * (t16 * t16 * ks1 * (tail->a.psi_real ? 2.0 : 3.0) + t16 * m16 * ks3 * 3.0);
             h->prop_issued_open += 2.0 * spin;
             h->prop_issued_closed += (tail->a.psi_closed ? 1.0 : 2.0) * spin;
+            // ... with the overlap matrix made early by the resident body (psi^H B times the Taylor sum: four tiles over the
+            // ceil(M / 4) k-steps, two real multiplications each) in place of the tail's own
+            if (early) h->prop_issued_closed += 2048.0 * (4.0 * ((h->M + 3) / 4) * 2.0 - t16 * t16 * ks1 * 2.0);
             h->issued_flops[AFQ_K_PROPAGATOR] = h->prop_issued_open * h->nw;
         }
     }
@@ -265,10 +292,12 @@ int k_prop_fused(afq_handle *h, const GreensLaunch *tail, bool mul3) {
             AFQ_FAIL(h, AFQ_ESTATE, "internal: a Green's function tail on a propagator launch outside its shape class");
         if (mul3) {
             AFQ_HIP(h, afq_raise_lds((const void *)prop_fused_kernel<false, 7, true, true>, lds, lds_set[6]));
-            AFQ_LAUNCH(h, (prop_fused_kernel<false, 7, true, true>), dim3(h->nw), dim3(PF_NT), lds, h->stream, a, tail->a, tail->wa);
+            const double *psiB = early ? h->psiB_cT : nullptr;
+            AFQ_LAUNCH(h, (prop_fused_kernel<false, 7, true, true>), dim3(h->nw), dim3(PF_NT), lds, h->stream, a, tail->a, tail->wa, psiB);
         } else {
+            const double *psiB = nullptr;
             AFQ_HIP(h, afq_raise_lds((const void *)prop_fused_kernel<false, 7, true, false>, lds, lds_set[7]));
-            AFQ_LAUNCH(h, (prop_fused_kernel<false, 7, true, false>), dim3(h->nw), dim3(PF_NT), lds, h->stream, a, tail->a, tail->wa);
+            AFQ_LAUNCH(h, (prop_fused_kernel<false, 7, true, false>), dim3(h->nw), dim3(PF_NT), lds, h->stream, a, tail->a, tail->wa, psiB);
         }
     }
     else if (narrow && full) PF_LAUNCH_(true, 6, 0);

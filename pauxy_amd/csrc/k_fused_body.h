@@ -3,7 +3,7 @@
 // instruction, the code it had before the tail existed.  In scope at the point of inclusion: the kernel's template flags
 // NARROW and FULL, MUL3 (the resident closed-shell body's Taylor products in the 3-multiplication form), its argument `a`,
 // the dynamic LDS `smem`, and PF_LEAVE(stored_closed): how a walker leaves ahead of the end (a dead walker, or one the resident
-// body has stored closed by construction).
+// body has stored closed by construction); PF_RESIDENT(KS): the call of the resident body with KS k-steps.
     const int w = blockIdx.x;
     if (!a.alive[w]) PF_LEAVE(false);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -97,8 +97,8 @@
     // issued above have landed (the barrier of the check waits for them) in LDS the body does not use.
     if constexpr (!NARROW && FULL == 7 && PF_NW == 8) {
         if (closed && a.resident) {
-            if (M <= 100) prop_closed_resident<25, MUL3>(a, smem, phi, vhs);
-            else prop_closed_resident<26, MUL3>(a, smem, phi, vhs);
+            if (M <= 100) PF_RESIDENT(25);
+            else PF_RESIDENT(26);
             PF_LEAVE(true);
         }
     }

@@ -9,7 +9,9 @@
 //   * wave r (0 .. 6) owns row tile r and both alpha column slots.  Its A fragments of V -- lane (lr, lk) holds
 //     V[16 r + lr][4 s + lk] for k-step s, one 16-byte global load each -- are loaded ONCE per walker and step, under the
 //     opening one-body pass, and serve all `order` Taylor products: no operand ring, no chunk barrier, no DMA.
-//     Wave 7 takes part in the fill of T and in the barriers only.
+//     Wave 7 takes part in the fill of T and in the barriers only -- and, EARLY (the 3-multiplication tail kernel with psi^H B
+//     at hand, afq_set_step_tail_overlap), stages psi^H B in LDS and inverts the tail's overlap matrix under the closing pass:
+//     see the end of the body.
 //   * T (the right-hand operand, alpha half: M x 32 complex) lives in LDS in B-fragment order [k-step][slot][64 lanes x 16 B]
 //     (lane (lr, lk) of k-step s, slot j: T[4 s + lk][16 j + lr]), 2 KB per k-step, KS * 2 KB <= 52 KB per image.  Two
 //     images: a product reads one and writes the other, so a hand-over is ONE barrier.  The accumulator of row tile r
@@ -26,11 +28,13 @@
 
 #define PCR_LDS(p) ((__attribute__((address_space(3))) unsigned char *)(p))
 
-template <int KS, bool MUL3>
+template <int KS, bool MUL3, bool EARLY = false>
 __device__ __attribute__((always_inline)) inline void prop_closed_resident(const PropFusedArgs &a, unsigned char *smem_,
-                                                                           cplx *phi, const cplx *vhs) {
+                                                                           cplx *phi, const cplx *vhs,
+                                                                           const double *psiB = nullptr, EarlyTail *et = nullptr) {
     auto *smem = PCR_LDS(smem_);
     typedef __attribute__((address_space(3))) d2_t lds_d2;
+    typedef __attribute__((address_space(3))) double lds_f64;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int M = a.M, nt = a.nt, na = a.na;
     constexpr unsigned TB = KS * 2048;                          // one image of T
@@ -44,11 +48,14 @@ __device__ __attribute__((always_inline)) inline void prop_closed_resident(const
     };
 
     // ---- phi[w], alpha half -> image 0 (B-fragment order), padding zeroed
+    // (EARLY with an odd `order`: image 1, so that the Taylor sum ends in image 1 for either parity and image 0, where the
+    //  tail's overlap matrix lies, is dead behind the last product)
+    const unsigned base0 = (EARLY && (a.order & 1)) ? TB : 0u;
     for (int e = tid; e < KS * 128; e += PF_NT) {
         const int k = 4 * (e >> 7) + ((e >> 4) & 3), col = 16 * ((e >> 6) & 1) + (e & 15);
         const bool ok = k < M && col < na;
         const cplx v = phi[ok ? k * nt + col : 0];
-        ((lds_d2 *)smem)[e] = ok ? (d2_t){v.x, v.y} : (d2_t){0.0, 0.0};
+        ((lds_d2 *)(smem + base0))[e] = ok ? (d2_t){v.x, v.y} : (d2_t){0.0, 0.0};
     }
     __syncthreads();
 
@@ -105,13 +112,36 @@ __device__ __attribute__((always_inline)) inline void prop_closed_resident(const
             av[s] = *p;
         }
         // ---- T_0 = B phi: image 0 -> image 1, and the first term of the sum
-        one_body(0, bh, SR, SI);
-        put(TB, SR, SI);
+        one_body(base0, bh, SR, SI);
+        put(base0 ^ TB, SR, SI);
+    }
+    // EARLY: wave 7, idle here, stages psi^H B in the free LDS above both images as A fragments -- [row tile t of 16 trial
+    // orbitals][k-step s][64 lanes x 8 B], lane (lr, lk) = psiB[16 t + lr][4 s + lk], 2 * KS * 512 B <= 26 KB of the 48 KB --
+    // under the opening pass; every wave reads its share behind the last Taylor product (any barrier in between publishes it)
+    constexpr unsigned PB = 2 * TB;
+    if constexpr (EARLY) {
+        if (!mul) {
+            const int lane = lane_id(), lk = lane >> 4, lr = lane & 15;
+            double pv[2][KS];
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int s = 0; s < KS; ++s) {
+                    const int j = 16 * t + lr, k = 4 * s + lk;
+                    const double *p = (j < na && k < M) ? psiB + j * M + k : (const double *)a.zero16;
+                    pv[t][s] = *p;
+                }
+            auto *pb = smem + PB + lane * 8;
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int s = 0; s < KS; ++s) *(lds_f64 *)(pb + (t * KS + s) * 512) = pv[t][s];
+        }
     }
     lds_barrier();
 
     // ---- Taylor products from the resident fragments: image cur -> image cur ^ TB, one barrier each
-    unsigned cur = TB;
+    unsigned cur = base0 ^ TB;
     for (int n = 1; n <= a.order; ++n) {
         if (mul) {
             double inv_n = 1.0 / n;
@@ -159,6 +189,85 @@ __device__ __attribute__((always_inline)) inline void prop_closed_resident(const
         cur ^= TB;
     }
 
+    if constexpr (EARLY) {
+        // ---- The tail's overlap matrix first, its inverse under the closing pass.
+        // phi' = B S with S the Taylor sum in image 1 (= cur), so O = phi'^T conj(psi) = (psiB S)^T with psiB = psi^H B (real,
+        // made on the host once per upload, staged in LDS above).  LDS from here on:
+        //   [0, TB)         image 0, dead: the tail's carve of O (offset 0, where wave 7 inverts it in place) and, in spin down's
+        //                   block behind it -- which a closed walker's tail never touches -- the scratch of gj_wave32
+        //   [TB, 2 TB)      image 1 = S, read by the overlap units and by the closing pass
+        //   [2 TB, + 26 KB) psiB as A fragments
+        //   the tail's copy of the walker (phi_l) overlaps all three: written behind the last barrier below
+        // 1. the eight waves multiply the 2 x 2 tiles x (Re, Im) of psiB . S, one unit of KS MFMAs each (wave = 4 t + 2 j + part:
+        //    row tile t of psiB, column slot j of S), and store their halves of O's entries;
+        // 2. barrier: O is complete;
+        // 3. wave 7 inverts O (gj_wave32, ~33 k cycles) WHILE waves 0-6 run the closing one-body pass from S and store phi' to
+        //    both spin blocks of the walker, keeping their accumulators;
+        // 4. barrier: S is dead, O^-1 lies where the tail reads it;
+        // 5. waves 0-6 write their accumulators into phi_l; the barrier in front of the tail (prop_fused_kernel) publishes them.
+        // Every wave crosses every barrier, none waits for another anywhere else.
+        const int nn = na, nsq = nn * nn + 2 * nn;                  // the tail's carve (greens_small_body, nmax = na = nb)
+        cplx *O = (cplx *)smem_;
+        cplx *phi_l = (cplx *)smem_ + 2L * nsq + ((2 * nn + 3) / 4 + 1);
+        {
+            const int t = wave >> 2, j = (wave >> 1) & 1, part = wave & 1;     // wave-uniform
+            const auto *pa = smem + PB + t * (KS * 512) + lane_id() * 8;
+            const auto *tb = smem + cur + j * 1024 + part * 8 + lane_id() * 16;
+            d4_t acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};               // even and odd k-steps: two chains per wave
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                const double x = *(const lds_f64 *)(pa + s * 512), y = *(const lds_f64 *)(tb + s * 2048);
+                if (s & 1) acc1 = mfma16(x, y, acc1);
+                else acc0 = mfma16(x, y, acc0);
+            }
+            // register q, lane (lr, lk): (psiB S)[16 t + 4 q + lk][16 j + lr] = O[16 j + lr][16 t + 4 q + lk]
+            const int lane = lane_id(), lr = lane & 15, lk = lane >> 4;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = 16 * j + lr, jj = 16 * t + 4 * q + lk;
+                if (i < nn && jj < nn) ((double *)&O[i * nn + jj])[part] = acc0[q] + acc1[q];
+            }
+        }
+        lds_barrier();
+        d4_t P1[2], P2[2];
+        if (mul) {
+            double bh[KS];
+            load_b(bh);
+            one_body(cur, bh, P1, P2);
+            const int lane = lane_id(), lr = lane & 15, lk = lane >> 4;
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int orow = wave * 16 + lk + 4 * q, col = 16 * j + lr;
+                    if (orow < M && col < na) {
+                        const cplx v = cmake(P1[j][q], P2[j][q]);
+                        phi[(long)orow * nt + col] = v;
+                        phi[(long)orow * nt + na + col] = v;
+                    }
+                }
+        } else {
+            cplx *scr = O + nsq;                                    // spin down's block: 32 + 32 complex, 32 ints
+            gj_wave32(O, nn, lane_id(), true, scr, scr + 32, (int *)(scr + 64), et->ph, et->la);
+        }
+        lds_barrier();
+        if (mul) {
+            const int lane = lane_id(), lr = lane & 15, lk = lane >> 4;
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int orow = wave * 16 + lk + 4 * q, col = 16 * j + lr;
+                    if (orow < M && col < na) {
+                        const cplx v = cmake(P1[j][q], P2[j][q]);
+                        phi_l[orow * nt + col] = v;
+                        phi_l[orow * nt + na + col] = v;
+                    }
+                }
+        }
+        et->on = true;
+        return;
+    }
     // ---- closing one-body pass on the alpha half, stored to both spin blocks: beta is the stored copy of alpha
     if (mul) {
         d4_t P1[2], P2[2];

@@ -806,6 +806,11 @@ class AfqDevice(object):
         and propagate_begin() (see afq_set_step_fusion_scope)."""
         self._ck(self.lib.afq_set_step_fusion_scope(self.h, int(scope)))
 
+    def set_step_tail_overlap(self, on):
+        """Mode 2's tail takes the overlap matrix and its inverse from the resident body's closing pass (default on; off:
+        the launch of before, bit for bit; counters(n=9)[8] counts the walker steps; see afq_set_step_tail_overlap)."""
+        self._ck(self.lib.afq_set_step_tail_overlap(self.h, int(on)))
+
     def propagator_closed_form(self):
         m = ctypes.c_int()
         self._ck(self.lib.afq_propagator_closed_form(self.h, ctypes.byref(m)))
