@@ -655,6 +655,7 @@ int afq_estimates_get_end(afq_handle *h, double *est_out /* c128[10] */);
 #define AFQ_THERMAL_FREE_PROJECTION 2
 #define AFQ_THERMAL_LOW_RANK        4
 #define AFQ_THERMAL_AVERAGE_GF      8
+#define AFQ_THERMAL_STREAMED_GREENS 16  /* honoured by afq_thermal_configure_continuous (below), refused here by name */
 int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int nstblz, const double *BT,
                           const double *BT_inv, const double *BH1, const double *auxf, int options);
 int afq_thermal_reset(afq_handle *h);
@@ -669,7 +670,12 @@ int afq_thermal_state(afq_handle *h, int32_t *out4);
  * waves), full-rank walkers.  The walker's matrices are complex: AFQ_F_THERMAL_G c128[2, M, M], AFQ_F_THERMAL_STACK
  * c128[nbins, 2, M, M], AFQ_F_THERMAL_RIGHT, AFQ_F_THERMAL_M0; the comb, afq_walkers_copy and the pack carry all four.
  * M <= 47 plane waves: the complex Green's function keeps 4 matrices of 16 M (M | 1) bytes in the 160 KiB of LDS of
- * a work-group (the shells 7, 19, 27, 33 fit, 57 does not).
+ * a work-group (the shells 7, 19, 27, 33 fit, 57 does not).  With AFQ_THERMAL_STREAMED_GREENS in options every
+ * Green's function of the handle (afq_thermal_greens, _propagate_continuous, _reset) is made by the streamed form of
+ * the same engine: 2 matrices in LDS, T in nw * 2 * 2 * M^2 * 16 bytes of device memory of the handle's, the same
+ * bits.  The bound is then the smallest of the slice kernel's 48 M (M | 1) bytes of LDS, the streamed kernel's LDS and
+ * the 64 lanes of a wave: M <= 57, the next shell.  The bit is honoured, not refused; above the bound the call is
+ * refused with M, the kernel that does not fit, its bytes and the bound.  Without the bit nothing changes.
  *   afq_thermal_configure_continuous  after afq_set_system_ueg (index lists over ALL plane waves, for the energy) and
  *                          afq_walkers_alloc; no trial determinant, no afq_set_propagator.  BT, BT_inv, BH1
  *                          f64[2, M, M]: the trial's dmat and its inverse (diagonal) and
@@ -679,7 +685,8 @@ int afq_thermal_state(afq_handle *h, int32_t *out4);
  *                          afq_counters [0]).  The exponential is the degree-6 polynomial.  options:
  *                          AFQ_THERMAL_* bits of what the caller was asked for, refused by name.  Ends with
  *                          afq_thermal_reset.  AFQ_EUNSUPPORTED: the option bits, a system that is not the UEG,
- *                          M > 47 (the message carries M and the bytes), a trial that is not diagonal, more than
+ *                          M > 47 (the message carries M and the bytes; M > 57 with
+ *                          AFQ_THERMAL_STREAMED_GREENS), a trial that is not diagonal, more than
  *                          one rank, back-propagation / ITCF / mixed RDM on the handle.
  *   afq_thermal_propagate_continuous  one time slice of every walker, dead ones included: P = I - G^T,
  *                          xbar = -sqrt(dt) P.[iA | iB] (|xbar_i| > fb_bound: unit modulus), xs = xi - xbar, cmf = -sqrt(dt) xs.mf_shift,

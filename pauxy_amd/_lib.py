@@ -23,6 +23,7 @@ AFQ_PROP_HYBRID, AFQ_PROP_FORCE_BIAS, AFQ_PROP_FREE_PROJECTION, AFQ_PROP_HUBBARD
  F_XBAR, F_XSHIFTED, F_ENERGY, F_LOG_DETR, F_THERMAL_G, F_THERMAL_STACK, F_THERMAL_RIGHT, F_THERMAL_M0,
  F_THERMAL_DET, F_CMF, F_CFB) = range(21)
 THERMAL_CHARGE, THERMAL_FREE_PROJECTION, THERMAL_LOW_RANK, THERMAL_AVERAGE_GF = 1, 2, 4, 8
+THERMAL_STREAMED_GREENS = 16
 AFQ_EINVAL, AFQ_ESTATE, AFQ_EUNSUPPORTED = -1, -2, -5
 
 _h = c_void_p

@@ -262,6 +262,8 @@ struct afq_handle {
     double *thc_BTpow = nullptr;    // [2, M] diagonal of BT^stack_size
     double *thc_left = nullptr;     // [stack_size, 2, M] diagonal of left_k = BT^stack_size BT_inv^(k + 1)
     double *thc_bh1 = nullptr;      // [2, M] diagonal of BH1
+    bool thc_streamed = false;      // AFQ_THERMAL_STREAMED_GREENS: every Green's function by the streamed kernel
+    cplx *thc_tscratch = nullptr;   // [nw, 2, 2, M, M] T of the streamed kernel, two buffers per work-group (else null)
 
     // ---- propagator
     bool have_prop = false;

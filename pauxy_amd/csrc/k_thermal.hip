@@ -149,6 +149,7 @@ int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int n
     if (options & AFQ_THERMAL_FREE_PROJECTION) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: free_projection is not supported (constrained path only)");
     if (options & AFQ_THERMAL_LOW_RANK) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: low_rank is not supported");
     if (options & AFQ_THERMAL_AVERAGE_GF) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: average_gf is not supported");
+    if (options & AFQ_THERMAL_STREAMED_GREENS) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure: streamed_greens belongs to the continuous fields (the real walkers fit to M = 64 as they are)");
     if (options) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure: unknown option bits");
     if (!h->kind || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_configure: set the system and allocate the walkers first");
     if (h->kind != AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: Hubbard systems only (no Generic / UEG)");

@@ -5,8 +5,11 @@
 // `right` c128 [2, M, M] and M0_s = det G_s c128 [2].  The slice counter, the block and the in-bin counter are the
 // handle's, as for the real walkers of k_thermal.hip.  A walker's working set stays in LDS: 4 complex matrices of pitch
 // M | 1, which the 160 KiB of a compute unit hold up to M = 47 (the plane-wave shells: 7, 19, 27, 33; 57 does not fit).
+// With AFQ_THERMAL_STREAMED_GREENS the Green's function keeps 2 matrices in LDS and T in the handle's thc_tscratch; the
+// bound is then the slice kernel's three matrices: M = 57, the next shell.  81 is refused either way.
 //
 //   thermal_cgreens_kernel  G and det G of every (walker, spin) from the stack: thermal_strat.h's engine with T = cplx.
+//   thermal_cgreens_streamed_kernel  the same from thermal_strat.h's streamed form, for a handle configured with the bit.
 //   thermal_cslice_kernel   one work-group per walker: BV = sum_{n <= 6} VHS^n / n! by five Horner products in LDS,
 //                           once for both spins; per spin B = diag(BH1) BV diag(BH1), right <- B right (right = I at
 //                           in-bin counter 0), bin[block] = diag(left_k) right.
@@ -18,6 +21,7 @@
 #include <cstring>
 
 #define THC_LDS_MAX (160 * 1024)
+#define THC_LANES 64            // the engine works lane = column
 
 namespace {
 
@@ -164,8 +168,15 @@ __global__ void thermal_creset_kernel(cplx *stack, cplx *G, cplx *right, cplx *M
 
 }  // namespace
 
+// G and det of nblocks / 2 walkers by the engine the handle was configured with
+static int thc_launch_greens(afq_handle *h, cplx *G, cplx *det, int first, int src_w, int nblocks) {
+    if (h->thc_streamed)
+        return ts_launch_greens_streamed<cplx>(h, h->thc_stack, G, det, h->thc_tscratch, first, src_w, nblocks);
+    return ts_launch_greens<cplx>(h, h->thc_stack, G, det, first, src_w, nblocks);
+}
+
 int k_thermal_c_greens(afq_handle *h, int slice_ix) {
-    return ts_launch_greens<cplx>(h, h->thc_stack, h->thc_G, h->thc_det, ts_first_bin(h, slice_ix), -1, 2 * h->nw);
+    return thc_launch_greens(h, h->thc_G, h->thc_det, ts_first_bin(h, slice_ix), -1, 2 * h->nw);
 }
 
 // walkers/handler.py:424-430: bins, G, weight.  The reference's reset leaves walker.M0 at the determinant the last path
@@ -177,7 +188,7 @@ int k_thermal_c_reset(afq_handle *h, bool with_m0) {
     AFQ_LAUNCH(h, thermal_creset_kernel, dim3((unsigned)((per + 255) / 256), 1), dim3(256), 0, h->stream, h->thc_stack, h->thc_G,
                h->thc_right, h->thc_M0, h->weight, h->thc_BTpow, h->thc_G0, h->thc_M00, nbins, M, 1, 0);
     AFQ_POST(h);
-    AFQ_TRY(ts_launch_greens<cplx>(h, h->thc_stack, h->thc_G0, h->thc_M00, ts_first_bin(h, 0), 0, 2));
+    AFQ_TRY(thc_launch_greens(h, h->thc_G0, h->thc_M00, ts_first_bin(h, 0), 0, 2));
     AFQ_LAUNCH(h, thermal_creset_kernel, dim3((unsigned)((per + 255) / 256), h->nw), dim3(256), 0, h->stream, h->thc_stack,
                h->thc_G, h->thc_right, h->thc_M0, h->weight, h->thc_BTpow, h->thc_G0, h->thc_M00, nbins, M, 0, with_m0 ? 1 : 0);
     AFQ_POST(h);
@@ -206,16 +217,36 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
     if (options & AFQ_THERMAL_FREE_PROJECTION) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: free_projection is not supported (constrained path only)");
     if (options & AFQ_THERMAL_LOW_RANK) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: low_rank is not supported");
     if (options & AFQ_THERMAL_AVERAGE_GF) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: average_gf is not supported");
-    if (options) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure_continuous: unknown option bits");
+    const bool streamed = (options & AFQ_THERMAL_STREAMED_GREENS) != 0;
+    if (options & ~AFQ_THERMAL_STREAMED_GREENS) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure_continuous: unknown option bits");
     if (!h->kind || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_configure_continuous: set the system and allocate the walkers first");
     if (h->kind != AFQ_SYS_UEG) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers with continuous fields: UEG systems only (no Generic, no continuous Hubbard)");
     const int M = h->M;
-    if (ts_greens_lds<cplx>(M) > THC_LDS_MAX) {
+    if (streamed) {
+        // the smallest of what the slice kernel, the streamed Green's kernel and lane = column hold
+        auto fits = [](int m) {
+            return thc_slice_lds(m) <= THC_LDS_MAX && ts_greens_streamed_lds<cplx>(m) <= THC_LDS_MAX && m <= THC_LANES;
+        };
+        if (!fits(M)) {
+            int mmax = M;
+            while (mmax > 1 && !fits(mmax)) --mmax;
+            const std::string head = "thermal walkers with continuous fields (streamed_greens): M = " + std::to_string(M) + " plane waves ";
+            const std::string tail = " (M <= " + std::to_string(mmax) + ")";
+            if (thc_slice_lds(M) > THC_LDS_MAX)
+                AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(thc_slice_lds(M)) + " bytes of LDS for the slice kernel "
+                         "(thermal_cslice_kernel), a work-group has " + std::to_string(THC_LDS_MAX) + tail);
+            if (ts_greens_streamed_lds<cplx>(M) > THC_LDS_MAX)
+                AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(ts_greens_streamed_lds<cplx>(M)) + " bytes of LDS for the "
+                         "streamed Green's function (thermal_cgreens_streamed_kernel), a work-group has " + std::to_string(THC_LDS_MAX) + tail);
+            AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "are more than the " + std::to_string(THC_LANES) + " lanes of a wave, one per column" + tail);
+        }
+    } else if (ts_greens_lds<cplx>(M) > THC_LDS_MAX) {
         int mmax = M;
         while (mmax > 1 && ts_greens_lds<cplx>(mmax) > THC_LDS_MAX) --mmax;
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers with continuous fields: M = " + std::to_string(M) + " plane waves need " +
                  std::to_string(ts_greens_lds<cplx>(M)) + " bytes of LDS for the complex Green's function, a work-group has " +
-                 std::to_string(THC_LDS_MAX) + " (M <= " + std::to_string(mmax) + ")");
+                 std::to_string(THC_LDS_MAX) + " (M <= " + std::to_string(mmax) + "); AFQ_THERMAL_STREAMED_GREENS (streamed_greens) "
+                 "keeps T in device memory and reaches further");
     }
     if (k_comm_size(h) > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: one rank only");
     if (h->nbp > 0 || h->it_nmax > 0) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no back-propagation or ITCF window");
@@ -253,6 +284,9 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
         (rc = dev_alloc(h, LT_WALKERS, &h->thc_stack, 2 * mm * n * nbins)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_right, 2 * mm * n)) ||
         (rc = dev_alloc(h, LT_WALKERS, &h->thc_M0, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_M00, (size_t)2)) ||
         (rc = dev_alloc(h, LT_WALKERS, &h->thc_det, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_nav, n))) return rc;
+    // T of the streamed Green's kernel, two buffers per (walker, spin); a handle configured without it holds none
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->thc_tscratch, streamed ? 4 * mm * n : (size_t)0))) return rc;
+    h->thc_streamed = streamed;
     if ((rc = ensure_G(h))) return rc;                  // c128 [nw, 2, M, M]: the one-body density matrices
     h->thc_fb_bound = fb_bound;
     h->dt = dt; h->sqrt_dt = std::pow(dt, 0.5);        // (the handle's time step, as afq_set_propagator sets it)
@@ -294,7 +328,7 @@ int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi
     h->th_block = h->th_slice / h->th_ss;
     h->th_counter = (h->th_counter + 1) % h->th_ss;
     // G = [I + S_{nbins - 1} .. S_0]^-1 on the walker's current bins, Mnew = det G, the weight
-    AFQ_TRY(ts_launch_greens<cplx>(h, h->thc_stack, h->thc_G, h->thc_det, 0, -1, 2 * h->nw));
+    AFQ_TRY(thc_launch_greens(h, h->thc_G, h->thc_det, 0, -1, 2 * h->nw));
     AFQ_LAUNCH(h, thermal_cweight_kernel, dim3((h->nw + 127) / 128), dim3(128), 0, h->stream, h->weight, h->thc_M0, h->thc_det,
                h->cmf, h->cfb, h->nw);
     AFQ_POST(h);

@@ -15,6 +15,9 @@
 //   thermal_rdm_kernel<T>     P_s = I - G_s^T as c128 for the force bias and the energy, nav = Re(tr P_up + tr P_down).
 // A walker's working set stays in LDS: 4 matrices of pitch M | 1 in units of T, which the 160 KiB of a compute unit hold
 // up to M = 64 for double and M = 47 for cplx.
+//   thermal_greens_streamed_kernel<cplx>  the same engine with T in device memory and t read out of W: 2 matrices in
+//                             LDS, which hold a complex walker to M = 64 (117,536 B at the M = 57 shell).  Chosen per
+//                             handle by AFQ_THERMAL_STREAMED_GREENS; the same bits as the resident kernel.
 //
 // TsScalar<T> is the arithmetic the routines are written in.  Restricted to real numbers the complex formulas round as
 // the real ones do: a product with +-1 and a negation are exact, so alpha = -unit(x_0) ||x||, x_0 - alpha =
@@ -329,6 +332,87 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_greens_kernel(const T *sta
     if (tid == 0) det[slot] = dg;
 }
 
+// LDS of the streamed Green's kernel: W and Qt, D[64], v[64], part[512], aux[192] scalars, perm[64]
+template <class T> inline size_t ts_greens_streamed_lds(int M) { return sizeof(T) * (2 * ts_mat(M) + 64 + 64 + 512 + 192) + sizeof(int) * 64; }
+
+// The same G and det G with T outside LDS: W and Qt, which the QR sweeps four times per column, stay; T, touched once
+// per bin as the B operand and the result of t T, lives in the work-group's own scratch in device memory, two [M, M]
+// buffers used in turn (scratch [gridDim.x, 2, M, M], block b's at b); t = D^-1 R P^T is never stored: the A loader of
+// t T reads it out of W through the inverse permutation.  Every element goes through the operations of
+// thermal_greens_kernel in their order, so the two kernels give the same bits.  A work-group reads only what it has
+// written itself, across a __syncthreads().  Instantiated for cplx alone (the real walkers fit to M = 64 as they are).
+template <class T>
+__global__ __launch_bounds__(TH_THREADS) void thermal_greens_streamed_kernel(const T *stack, T *G, T *det, T *scratch, int M,
+                                                                              int nbins, int first, int src_w) {
+    typedef TsScalar<T> S;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int LD = M | 1, tid = threadIdx.x;
+    const size_t mat = ts_mat(M);
+    T *W = (T *)smem, *Qt = W + mat;
+    T *D = Qt + mat, *v = D + 64, *part = v + 64, *aux = part + 512;
+    int *perm = (int *)(aux + 192);
+    int *iperm = (int *)aux;                                         // (aux is the solve's: free until the chain is done)
+    const int w = src_w < 0 ? blockIdx.x >> 1 : src_w, s = blockIdx.x & 1;
+    const long mm = (long)M * M;
+    const T *Bw = stack + ((long)w * nbins * 2 + s) * mm;            // bin b at Bw + b * 2 * mm
+    T *Tin = scratch + (long)blockIdx.x * 2 * mm, *Tout = Tin + mm;  // pitch M
+
+    {
+        const T *B = Bw + (long)first * 2 * mm;
+        for (int e = tid; e < M * M; e += TH_THREADS) W[(e / M) * LD + e % M] = B[e];
+    }
+    __syncthreads();
+    ts_qrcp(W, Qt, M, LD, perm, v, part);
+    // T = D^-1 R P^T
+    for (int e = tid; e < M * M; e += TH_THREADS) {
+        const int i = e / M, j = e % M;
+        Tin[i * M + perm[j]] = j >= i ? S::div(W[i * LD + j], W[i * LD + i]) : S::zero();
+    }
+    if (tid < M) D[tid] = W[tid * LD + tid];
+    __syncthreads();
+    for (int n = 1; n < nbins; ++n) {
+        const T *B = Bw + (long)((first + n) % nbins) * 2 * mm;
+        // W = (B Q) D, Q[k][c] = conj(Qt[c][k])
+        ts_gemm<T>(M, [&](int r, int k) { return B[r * M + k]; }, [&](int k, int c) { return S::conj(Qt[c * LD + k]); },
+                   [&](int r, int c, T x) { W[r * LD + c] = S::mul(x, D[c]); });
+        __syncthreads();
+        ts_qrcp(W, Qt, M, LD, perm, v, part);
+        if (tid < M) { iperm[perm[tid]] = tid; D[tid] = W[tid * LD + tid]; }
+        __syncthreads();
+        // T <- t T, t[r][k] = (D^-1 R)[r][iperm[k]]
+        ts_gemm<T>(M, [&](int r, int k) { const int j = iperm[k]; return j >= r ? S::div(W[r * LD + j], W[r * LD + r]) : S::zero(); },
+                   [&](int k, int c) { return Tin[k * M + c]; }, [&](int r, int c, T x) { Tout[r * M + c] = x; });
+        __syncthreads();
+        T *t = Tin; Tin = Tout; Tout = t;
+    }
+    // (D_b Q^H + D_s T) G = D_b Q^H: R = D_b Q^H in place in Qt, X = R + D_s T into W, whose R is used up
+    for (int e = tid; e < M * M; e += TH_THREADS) {
+        const int i = e / M, j = e % M;
+        const T d = D[i];
+        const double ad = S::abs(d);
+        const double db = ad > 1.0 ? 1.0 / ad : 1.0;
+        const T ds = ad > 1.0 ? S::unit(d, ad) : d;
+        const T r = S::scale(Qt[i * LD + j], db);
+        T x = r;
+        S::fma(x, ds, Tin[i * M + j]);
+        W[i * LD + j] = x;
+        Qt[i * LD + j] = r;
+    }
+    __syncthreads();
+    ts_solve(W, Qt, M, LD, aux, aux + 64, aux + 128);
+    const long slot = (long)(src_w < 0 ? w : 0) * 2 + s;
+    T *Gd = G + slot * mm;
+    for (int e = tid; e < M * M; e += TH_THREADS) {
+        const T g = Qt[(e / M) * LD + e % M];
+        Gd[e] = g;
+        if (det) W[(e / M) * LD + e % M] = g;
+    }
+    if (!det) return;
+    __syncthreads();
+    const T dg = ts_det(W, M, LD, aux);
+    if (tid == 0) det[slot] = dg;
+}
+
 // P_s = I - G_s^T as c128 [nw, 2, M, M], nav = Re(tr P_up + tr P_down) (nav may be null)
 template <class T>
 __global__ __launch_bounds__(TH_THREADS) void thermal_rdm_kernel(const T *G, cplx *P, double *nav, int M) {
@@ -381,6 +465,20 @@ template <class T> int ts_launch_greens(afq_handle *h, const T *stack, T *G, T *
     afq_note_launch(h, std::is_same<T, cplx>::value ? "thermal_cgreens_kernel" : "thermal_greens_kernel");
     hipLaunchKernelGGL(thermal_greens_kernel<T>, dim3(nblocks), dim3(TH_THREADS), lds, h->stream, stack, G, det, h->M,
                        h->th_nbins, first, src_w);
+    AFQ_POST(h);
+    return AFQ_OK;
+}
+
+// The streamed form; scratch [nblocks, 2, M, M].  Its own name in the trace: thermal_cgreens_kernel stays the resident one.
+template <class T> int ts_launch_greens_streamed(afq_handle *h, const T *stack, T *G, T *det, T *scratch, int first, int src_w,
+                                                 int nblocks) {
+    static_assert(std::is_same<T, cplx>::value, "the streamed Green's function is the complex walkers' alone");
+    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
+    const size_t lds = ts_greens_streamed_lds<T>(h->M);
+    AFQ_HIP(h, afq_raise_lds((const void *)thermal_greens_streamed_kernel<T>, lds, lds_set));
+    afq_note_launch(h, "thermal_cgreens_streamed_kernel");
+    hipLaunchKernelGGL(thermal_greens_streamed_kernel<T>, dim3(nblocks), dim3(TH_THREADS), lds, h->stream, stack, G, det, scratch,
+                       h->M, h->th_nbins, first, src_w);
     AFQ_POST(h);
     return AFQ_OK;
 }

@@ -20,6 +20,7 @@ import scipy.linalg
 from pauxy_amd.context import hidden
 
 MAX_BASIS = 47          # the complex Green's function keeps a walker's working set in LDS (k_thermal_cplx.hip)
+MAX_BASIS_STREAMED = 57  # walkers: {streamed_greens: True}: T in device memory; the slice kernel's LDS is the bound
 
 
 def planewave_constants(system, trial, dt):

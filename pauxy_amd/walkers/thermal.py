@@ -11,7 +11,7 @@ import numpy
 from pauxy_amd import _lib as L
 from pauxy_amd.context import get_context, hidden
 from pauxy_amd.propagation.thermal_hubbard import thermal_constants
-from pauxy_amd.propagation.thermal_planewave import MAX_BASIS, planewave_constants
+from pauxy_amd.propagation.thermal_planewave import MAX_BASIS, MAX_BASIS_STREAMED, planewave_constants
 from pauxy_amd.trial_density import update_stack
 
 
@@ -100,9 +100,19 @@ class ThermalWalkers(object):
         if self.pcont_method != 'comb':
             raise NotImplementedError("thermal walkers: population control '%s' is not supported (pair_branch "
                                       "included): comb only" % self.pcont_method)
-        if self.continuous and system.nbasis > MAX_BASIS:
+        # the Green's function with T in device memory (k_thermal_cplx.hip, AFQ_THERMAL_STREAMED_GREENS)
+        self.streamed_greens = bool(walker_opts.get('streamed_greens', False))
+        if self.streamed_greens and not self.continuous:
+            raise NotImplementedError("thermal walkers: streamed_greens belongs to the UEG's continuous fields (Hubbard "
+                                      "walkers fit to M = 64 as they are)")
+        if self.streamed_greens and system.nbasis > MAX_BASIS_STREAMED:
+            raise NotImplementedError("thermal walkers: M = %d > %d plane waves is not supported with streamed_greens "
+                                      "(the slice kernel keeps three complex matrices in LDS)"
+                                      % (system.nbasis, MAX_BASIS_STREAMED))
+        if self.continuous and not self.streamed_greens and system.nbasis > MAX_BASIS:
             raise NotImplementedError("thermal walkers: M = %d > %d plane waves is not supported (the complex Green's "
-                                      "function keeps a walker's working set in LDS)" % (system.nbasis, MAX_BASIS))
+                                      "function keeps a walker's working set in LDS; walkers: {streamed_greens: True} "
+                                      "reaches M = %d)" % (system.nbasis, MAX_BASIS, MAX_BASIS_STREAMED))
         if system.nbasis > 64:
             raise NotImplementedError("thermal walkers: M = %d > 64 sites is not supported" % system.nbasis)
         self.nwalkers = qmc.nwalkers
@@ -171,7 +181,8 @@ class ThermalWalkers(object):
         BH1, mf_shift = (prop.BH1, prop.mf_shift) if prop is not None else planewave_constants(self.system, self.trial,
                                                                                                 self.dt)
         self.dev.thermal_configure_continuous(self.num_slices, self.stack_size, self.dt, self.trial.dmat,
-                                              self.trial.dmat_inv, BH1, mf_shift, fb_bound)
+                                              self.trial.dmat_inv, BH1, mf_shift, fb_bound,
+                                              L.THERMAL_STREAMED_GREENS if self.streamed_greens else 0)
         self.configured_fb_bound = fb_bound
 
     def set_total_weight(self, total_weight):
