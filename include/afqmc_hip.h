@@ -430,6 +430,16 @@ int afq_set_step_fusion_scope(afq_handle *h, int scope);
  * Modes 0 and 1, and every walker that does not take the resident body, are not touched.  afq_counters_ext [8] counts the
  * walker steps that took it.  AFQ_EINVAL for any other value.                                                       */
 int afq_set_step_tail_overlap(afq_handle *h, int on);
+/* The step hand-over of that launch (mode 2 with the early overlap, same walkers): under the inversion the idle waves also
+ * make the opening one-body pass of the NEXT step, T_0 = B phi' = (B B) S with B B made on the host once per upload of the
+ * propagator, and leave it in a per-walker buffer of the handle; the next launch of the kernel starts such a walker at its
+ * Taylor products and reads no phi.  The handle drops the hand-over whenever anything comes between the two launches that
+ * writes phi or moves a walker to another slot (re-orthogonalisation, population control, copy, unpack, exchange, upload,
+ * a window), changes the propagator, the trial or one of the step's mode switches, or launches any other propagator; the
+ * next step then runs its own opening pass.  T_0 is rounded as (B B) S instead of B (B S): results move at rounding level.
+ *   1  (default) on      0  off: the launch of before
+ * afq_counters_ext [9] counts the walker steps that started from a hand-over.  AFQ_EINVAL for any other value.        */
+int afq_set_step_handover(afq_handle *h, int on);
 
 /* Force bias of a multi-determinant trial (propagation/generic.py:154-157, walkers/multi_det.py:283-290) has two
  * device algorithms with the same result:
@@ -732,8 +742,8 @@ int afq_last_launch(afq_handle *h, char *buf, int len, uint64_t *queued, uint64_
  * Gauss-Jordan flagged as poorly conditioned block-wise and handed to the step-by-step kernel (diagnostic),
  * [3]=walker steps the fused propagator took through its closed-shell deal (spin blocks bitwise equal)       */
 int afq_counters(afq_handle *h, int64_t *out, int reset);
-/* the same, first n counters (n <= 9; [8]=walker steps whose overlap matrix was made and inverted under the fused propagator's
- * closing pass, afq_set_step_tail_overlap): [4]=walker energy evaluations whose exchange energy was evaluated for one spin and
+/* the same, first n counters (n <= 10; [8]=walker steps whose overlap matrix was made and inverted under the fused propagator's
+ * closing pass, afq_set_step_tail_overlap; [9]=walker steps that started from the step hand-over, afq_set_step_handover): [4]=walker energy evaluations whose exchange energy was evaluated for one spin and
  * counted twice (closed-shell population, decided on the device: energy_finish_kernel), [5]=walker Green's functions
  * computed for one spin (closed-shell walker, greens_small_kernel), [6]=per-determinant overlaps of a multi-determinant
  * trial that came out as NaN (0 x inf behind a zero pivot of a singular overlap matrix) and were taken as zero overlaps,

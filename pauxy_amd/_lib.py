@@ -146,6 +146,7 @@ SIGNATURES = {
     "afq_set_step_fusion": [_h, c_int],
     "afq_set_step_fusion_scope": [_h, c_int],
     "afq_set_step_tail_overlap": [_h, c_int],
+    "afq_set_step_handover": [_h, c_int],
     "afq_set_msd_force_bias": [_h, c_int],
     "afq_msd_force_bias": [_h, POINTER(c_int)],
     "afq_kernel_trace": [_h, c_int],

@@ -108,14 +108,19 @@ static int upload_psi(afq_handle *h, const double *psi) {
 
 // psiB_cT = psi^H B (afq_internal.h) from the host copies of the trial and the propagator: after every upload of either.
 // Anything but a single real closed trial with one real one-body matrix for both spins leaves the slot null, and the fused
-// propagator's tail then evaluates the overlap matrix itself.
+// propagator's tail then evaluates the overlap matrix itself.  B2 = B B (the step hand-over) is made here too, under the same
+// conditions and in the same lifetime slot; a new trial or propagator drops the hand-over that was made with the old one.
 static int build_psiB(afq_handle *h) {
     afq_host_cache *c = cache_of(h);
     const int M = h->M, nt = h->nt, na = h->na;
     const bool ok = h->have_prop && h->ndet <= 1 && h->psi_stride == 0 && h->psi_real && h->psi_closed &&
                     h->bh1_real && h->bh1_same && c->psi.size() == (size_t)2 * M * nt && c->BH1.size() == (size_t)M * M;
-    h->psiB_psi = nullptr; h->psiB_bh1 = nullptr;
-    if (!ok) return dev_alloc(h, LT_TRIAL, &h->psiB_cT, 0);
+    h->psiB_psi = nullptr; h->psiB_bh1 = nullptr; h->b2_bh1 = nullptr;
+    h->handover.drop();
+    if (!ok) {
+        const int rc0 = dev_alloc(h, LT_TRIAL, &h->B2, 0);
+        return rc0 ? rc0 : dev_alloc(h, LT_TRIAL, &h->psiB_cT, 0);
+    }
     std::vector<double> pb((size_t)na * M, 0.0);
     for (int m = 0; m < M; ++m)
         for (int i = 0; i < na; ++i) {
@@ -124,8 +129,24 @@ static int build_psiB(afq_handle *h) {
             double *out = &pb[(size_t)i * M];
             for (int k = 0; k < M; ++k) out[k] += p * brow[k];
         }
-    const int rc = dev_upload(h, LT_TRIAL, &h->psiB_cT, pb.data(), pb.size());
+    int rc = dev_upload(h, LT_TRIAL, &h->psiB_cT, pb.data(), pb.size());
     if (!rc) { h->psiB_psi = h->dets[h->cur_det].psi; h->psiB_bh1 = h->BH1; }
+    if (rc) return rc;
+    // B2 = B B for the step hand-over (the next step's opening pass as (B B) S, k_fused_closed.h): extended accumulation, one
+    // rounding per element
+    std::vector<double> b2((size_t)M * M);
+    std::vector<long double> acc(M);
+    for (int m = 0; m < M; ++m) {
+        std::fill(acc.begin(), acc.end(), 0.0L);
+        for (int j = 0; j < M; ++j) {
+            const long double x = c->BH1[(size_t)m * M + j];
+            const double *brow = &c->BH1[(size_t)j * M];
+            for (int k = 0; k < M; ++k) acc[k] += x * (long double)brow[k];
+        }
+        for (int k = 0; k < M; ++k) b2[(size_t)m * M + k] = (double)acc[k];
+    }
+    rc = dev_upload(h, LT_TRIAL, &h->B2, b2.data(), b2.size());
+    if (!rc) h->b2_bh1 = h->BH1;
     return rc;
 }
 
@@ -282,7 +303,7 @@ static int upload_rchol(afq_handle *h, const double *rchol, bool real) {
 
 int afq_set_system_generic(afq_handle *h, int M, int K, int na, int nb, const double *hs_pot,
                            const double *rchol, const double *H1, double ecore) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !hs_pot || !rchol || !H1) return AFQ_EINVAL;
     int rc = set_dims(h, AFQ_SYS_GENERIC, M, K, na, nb);
     if (rc) return rc;
@@ -330,7 +351,7 @@ int afq_set_system_generic(afq_handle *h, int M, int K, int na, int nb, const do
 // complex Cholesky vectors: Re and Im parts as two transposed real panels (afq_internal.h: hs_cplx)
 int afq_set_system_generic_c128(afq_handle *h, int M, int K, int na, int nb, const double *hs_pot,
                                 const double *rchol, const double *H1, double ecore) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !hs_pot || !rchol || !H1) return AFQ_EINVAL;
     if (M <= 0 || K <= 0) AFQ_FAIL(h, AFQ_EINVAL, "bad dimensions");
     const size_t mm = (size_t)M * M, nq = (size_t)(na + nb) * M;
@@ -392,7 +413,7 @@ int afq_set_system_generic_c128(afq_handle *h, int M, int K, int na, int nb, con
 }
 
 int afq_set_system_hubbard(afq_handle *h, int M, int na, int nb, double U, const double *T) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !T) return AFQ_EINVAL;
     int rc = set_dims(h, AFQ_SYS_HUBBARD, M, M, na, nb);
     if (rc) return rc;
@@ -428,7 +449,7 @@ int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64
                        const int64_t *kpq_i, const int64_t *kpq_kpq, const int64_t *pmq_off,
                        const int64_t *pmq_i, const int64_t *pmq_pmq, const double *vqvec, double vol,
                        const double *H1diag, double ecore) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !iA_colptr || !iB_colptr || !kpq_off || !pmq_off || !vqvec || !H1diag) return AFQ_EINVAL;
     int rc = set_dims(h, AFQ_SYS_UEG, M, 2 * nq, na, nb);
     if (rc) return rc;
@@ -512,7 +533,7 @@ int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64
 }
 
 int afq_set_trial(afq_handle *h, const double *psi) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !psi) return AFQ_EINVAL;
     if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "set the system before the trial");
     if (h->ndet > 1) AFQ_FAIL(h, AFQ_ESTATE, "a multi-determinant trial is set; set the system again first");
@@ -525,7 +546,7 @@ int afq_set_trial(afq_handle *h, const double *psi) {
 }
 
 int afq_set_trial_multi(afq_handle *h, int ndet, const double *psi, const double *coeffs, const double *rchol) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !psi || !coeffs || !rchol || ndet < 1) return AFQ_EINVAL;
     if (h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "multi-determinant trials need a generic system");
     if (h->nw) AFQ_FAIL(h, AFQ_ESTATE, "set the trial before allocating walkers");
@@ -569,7 +590,7 @@ int afq_set_trial_multi(afq_handle *h, int ndet, const double *psi, const double
 
 int afq_set_propagator(afq_handle *h, const double *BH1, const double *mf_shift, double dt, int exp_order,
                        int flags) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !BH1 || !mf_shift || dt <= 0 || exp_order < 0) return AFQ_EINVAL;
     if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "set the system before the propagator");
     hipSetDevice(h->device);
@@ -603,7 +624,7 @@ int afq_set_propagator(afq_handle *h, const double *BH1, const double *mf_shift,
 
 // ------------------------------------------------------------------ walkers
 int afq_walkers_alloc(afq_handle *h, int nw) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || nw <= 0) return AFQ_EINVAL;
     if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "set the system before allocating walkers");
     hipSetDevice(h->device);
@@ -717,6 +738,7 @@ static int ensure_spin_ghalf(afq_handle *h);
 
 int afq_walkers_set(afq_handle *h, int field, const void *host, int first, int count) {
     if (h && (field == AFQ_F_PHI || field == AFQ_F_GHALF)) { h->gf.drop(); h->gf.rewritten(); }
+    if (h && field == AFQ_F_PHI) h->handover.drop();
     if (!h || !host) return AFQ_EINVAL;
     if (!h->nw) AFQ_FAIL(h, AFQ_ESTATE, "no walkers allocated");
     if (first < 0 || count < 0 || first + count > h->nw) AFQ_FAIL(h, AFQ_EINVAL, "walker range out of bounds");
@@ -757,6 +779,7 @@ int afq_walkers_device_ptr(afq_handle *h, int field, void **dev_ptr, int64_t *by
         if ((rc = ensure_spin_ghalf(h))) return rc;
     }
     h->gf.drop(); h->gf.enabled = false;                 // the caller may write through the pointer
+    if (field == AFQ_F_PHI) { h->handover.drop(); h->handover.enabled = false; }
     *dev_ptr = base;
     if (bytes_per_walker) *bytes_per_walker = (int64_t)bytes;
     return AFQ_OK;
@@ -948,6 +971,7 @@ int afq_propagate_begin(afq_handle *h, const double *xi) {
             else if ((rc = local_energy(h))) return rc;
         }
     }
+    if (k_ueg_fast_supported(h) || hubbard_fused || !k_prop_fused_supported(h)) h->handover.drop();   // (not the fused propagator)
     if (k_ueg_fast_supported(h)) {
         // plane waves: force bias from the occupied rows of G, fields, and the ~2 nq coefficients that ARE the HS
         // potential, in one launch; B exp(V) B from those coefficients in a second one (k_ueg.hip)
@@ -1120,6 +1144,7 @@ int afq_log_ovlp_sums(afq_handle *h, double *sums3) {
 int afq_reortho(afq_handle *h, double *detR_out) {
     AFQ_API(h, "afq_reortho");
     if (!h) return AFQ_EINVAL;
+    h->handover.drop();                 // (phi -> phi R^-1: the Green's function survives the QR, B phi does not)
     int rc = need_ready(h, false);
     if (rc) { h->gf.drop(); return rc; }
     // Ghalf = (phi^T psi*)^-1 phi^T does not change when phi -> phi R^-1, so a Green's function kept from
@@ -1185,24 +1210,35 @@ int afq_set_exchange_algorithm(afq_handle *h, int mode) {
 int afq_set_propagator_closed_form(afq_handle *h, int mode) {
     if (!h || mode < 0 || mode > 2) return AFQ_EINVAL;
     h->prop_closed_mode = mode;
+    h->handover.drop();
     return AFQ_OK;
 }
 
 int afq_set_step_fusion(afq_handle *h, int mode) {
     if (!h || mode < 0 || mode > 2) return AFQ_EINVAL;
     h->step_fusion_mode = mode;
+    h->handover.drop();
     return AFQ_OK;
 }
 
 int afq_set_step_fusion_scope(afq_handle *h, int scope) {
     if (!h || scope < 0 || scope > 1) return AFQ_EINVAL;
     h->step_fusion_scope = scope;
+    h->handover.drop();
     return AFQ_OK;
 }
 
 int afq_set_step_tail_overlap(afq_handle *h, int on) {
     if (!h || on < 0 || on > 1) return AFQ_EINVAL;
     h->step_tail_overlap = on;
+    h->handover.drop();
+    return AFQ_OK;
+}
+
+int afq_set_step_handover(afq_handle *h, int on) {
+    if (!h || on < 0 || on > 1) return AFQ_EINVAL;
+    h->step_handover = on;
+    h->handover.drop();
     return AFQ_OK;
 }
 
@@ -1283,7 +1319,7 @@ int afq_vhs(afq_handle *h, const double *xs, double *vhs_out) {
 }
 
 int afq_apply_exponential(afq_handle *h, const double *vhs) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !vhs) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;
@@ -1305,7 +1341,7 @@ int afq_apply_exponential(afq_handle *h, const double *vhs) {
 }
 
 int afq_kinetic(afq_handle *h) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;
@@ -1335,6 +1371,7 @@ int afq_popcontrol_comb(afq_handle *h, double r, double target_weight, int32_t *
     if (h) h->scal_cache_valid = false;
     AFQ_API(h, "afq_popcontrol_comb");
     if (!h) return AFQ_EINVAL;
+    h->handover.drop();                 // (walkers change slots: the images do not travel with the clones)
     const bool thermal = h->th_on && h->nw;              // thermal walkers: no trial determinant, G and the bins travel
     int rc = AFQ_OK;
     if (thermal) {
@@ -1366,6 +1403,7 @@ int afq_popcontrol_pair_branch(afq_handle *h, const double *u, int nu, double ta
     if (h) h->scal_cache_valid = false;
     AFQ_API(h, "afq_popcontrol_pair_branch");
     if (!h) return AFQ_EINVAL;
+    h->handover.drop();
     if (h->th_on) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: pair_branch population control is not supported (comb only)");
     int rc = need_ready(h, false);
     if (rc) { h->gf.drop(); return rc; }
@@ -1438,7 +1476,7 @@ int afq_walker_pack(afq_handle *h, int iw, void *dev_buf) {
 }
 
 int afq_walker_unpack(afq_handle *h, int iw, const void *dev_buf) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !dev_buf) return AFQ_EINVAL;
     int rc = need_ready(h, false);
     if (rc) return rc;
@@ -1447,7 +1485,7 @@ int afq_walker_unpack(afq_handle *h, int iw, const void *dev_buf) {
 }
 
 int afq_walkers_copy(afq_handle *h, int src, int dst) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h) return AFQ_EINVAL;
     int rc = need_ready(h, false);
     if (rc) return rc;
@@ -1777,7 +1815,7 @@ static int hirsch_ready(afq_handle *h) {
 }
 
 int afq_set_propagator_hirsch(afq_handle *h, const double *bt2, double dt, int charge_decomposition) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !bt2 || dt <= 0) return AFQ_EINVAL;
     if (h->kind != AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_ESTATE, "the Hirsch transformation needs a Hubbard system");
     if (h->ndet > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "Hirsch propagator: single-determinant trials");
@@ -1827,7 +1865,7 @@ int afq_set_propagator_hirsch(afq_handle *h, const double *bt2, double dt, int c
 }
 
 int afq_hirsch_kinetic(afq_handle *h) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1836,7 +1874,7 @@ int afq_hirsch_kinetic(afq_handle *h) {
 }
 
 int afq_hirsch_two_body(afq_handle *h, const double *u, int32_t *fields_out, int32_t *used_out) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !u) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1849,7 +1887,7 @@ int afq_hirsch_two_body(afq_handle *h, const double *u, int32_t *fields_out, int
 }
 
 int afq_hirsch_finish(afq_handle *h, double eshift) {
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1861,7 +1899,7 @@ int afq_hirsch_finish(afq_handle *h, double eshift) {
 
 int afq_propagate_hirsch(afq_handle *h, double eshift) {
     AFQ_API(h, "afq_propagate_hirsch");
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1895,7 +1933,7 @@ int afq_hirsch_free_projection(afq_handle *h, int on) {
 
 int afq_propagate_hirsch_free(afq_handle *h, const double *u, int32_t *fields_out, double eshift) {
     AFQ_API(h, "afq_propagate_hirsch_free");
-    if (h) h->gf.drop();
+    if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;

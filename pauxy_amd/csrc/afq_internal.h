@@ -40,7 +40,19 @@ __device__ inline cplx cdiv(cplx a, cplx b) {
 enum { AFQ_HS_HERMITIAN = 1, AFQ_HS_GENERAL = 2 };       // afq_handle::hs_cplx
 enum { T_GREENS = 0, T_ONEBODY, T_FB, T_VHS, T_EXP, T_OVLP, T_QR, T_ENERGY, T_COUNT };
 
-#define AFQ_NCOUNTERS 9     // afq_counters_ext (include/afqmc_hip.h)
+#define AFQ_NCOUNTERS 10    // afq_counters_ext (include/afqmc_hip.h)
+
+// Whether the hand-over buffers of the handle (t0_next, t0_ready) describe the walkers as they are now.  A launch of the
+// fused propagator that produced sets `current`; everything that writes phi, moves a walker to another slot, changes the
+// propagator, the trial, the Taylor order or a mode switch of the step drops it, and so does every propagator launch that is
+// not that kernel with the early overlap (k_prop_fused drops on entry and sets again behind a launch that produced).  A device
+// pointer to phi handed out (afq_walkers_device_ptr) turns it off for the life of the handle: the caller may write through it.
+struct StepHandover {
+    bool current = false;
+    bool enabled = true;
+    void drop() { current = false; }
+    void produced() { current = enabled; }
+};
 
 struct afq_handle {
     int device = 0;
@@ -79,6 +91,7 @@ struct afq_handle {
     int step_fusion_mode = 2;       // afq_set_step_fusion: 0 never, 1 tail behind the 4-multiplication body, 2 behind the 3-multiplication one
     int step_fusion_scope = 0;      // afq_set_step_fusion_scope: 0 announced one-call steps, 1 every step of the shape class
     int step_tail_overlap = 1;      // afq_set_step_tail_overlap: the mode-2 tail's overlap matrix and inverse under the closing pass
+    int step_handover = 1;          // afq_set_step_handover: that launch also makes the next step's opening one-body pass
     int prop_closed_mode = 0;       // afq_set_propagator_closed_form: 0 auto, 1 streamed deal, 2 V resident in registers (where eligible)
     cplx *exq_y = nullptr;          // [2 * slices, nw, ceil(N M / 16)] per-tile partial sums of the quadratic form
     size_t exq_y_len = 0;
@@ -133,6 +146,10 @@ struct afq_handle {
     // closed and BH1 real and the same for both spins
     double *psiB_cT = nullptr;
     const void *psiB_psi = nullptr, *psiB_bh1 = nullptr;    // the device trial and propagator it was made for (never dereferenced)
+    // B2 = Re(BH1[0]) . Re(BH1[0]), [M, M] real, for the step hand-over (k_fused_closed.h): made with psiB_cT, under the same
+    // conditions, in long double on the host; b2_bh1 is the device propagator it was made for (never dereferenced)
+    double *B2 = nullptr;
+    const void *b2_bh1 = nullptr;
     // Closed-shell populations (round 5).  The Green's function kernel checks every walker's spin blocks for bitwise equality
     // (greens_small_kernel); a walker that fails raises closed_bad to the epoch of that launch (gf.closed says which Ghalf
     // the verdict is about).  The host never reads the flag.
@@ -300,6 +317,12 @@ struct afq_handle {
     cplx *gdiag = nullptr;          // Hubbard: diag(G_s) as partial sums over row blocks of Ghalf, [2 nw, gdiag_parts, M]
     int gdiag_parts = 0;
     GreensCache gf;                 // what ghalf / ghalf_sum / gdiag / vbias / ovlp_new hold for the current walkers
+    // The step hand-over of the fused propagator's 3-multiplication tail kernel: t0_next[w] holds T_0 = B phi[w] of the NEXT
+    // step as the resident body's image of T, t0_ready[w] says for which walkers (written by every launch of that kernel);
+    // both are allocated the first time a launch can produce.  `handover` says whether they are about the CURRENT phi.
+    unsigned char *t0_next = nullptr;   // [nw][ceil(M / 4) * 2048 B]
+    int *t0_ready = nullptr;            // [nw]
+    StepHandover handover;
     cplx *xbar = nullptr, *xs = nullptr;              // [nw, K]
     cplx *cmf = nullptr, *cfb = nullptr;              // [nw]
     cplx *vhs = nullptr;            // [nw, nv, M, M] or [nw, nv, M] when vhs_diag

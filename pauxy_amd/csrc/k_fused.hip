@@ -121,6 +121,18 @@ __device__ inline void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
+// The step hand-over of the 3-multiplication tail kernel (afq_set_step_handover; afq_handle::handover owns its validity):
+// a walker of the EARLY resident body leaves the opening pass of its NEXT step behind, and starts from the one the launch
+// before left.  Passed to that kernel alone, by value, behind its other arguments.
+struct StepHandoverArgs {
+    unsigned char *t0_next;     // [nw][KS * 2048 B] T_0 = B phi' as the resident body's image of T (B-fragment order)
+    int *ready;                 // [nw] written for EVERY walker of EVERY launch: 1 = t0_next[w] is the walker's, made by this launch
+    const double *B2;           // Re(BH1[0]) . Re(BH1[0]), [M, M] real (host-made)
+    unsigned long long *n_handed;   // afq_counters_ext [9]
+    int consume;                // the host holds the last launch's hand-over current: a walker whose flag is set starts from it
+    int produce;                // EARLY walkers make the next one
+};
+
 #include "k_fused_closed.h"
 
 // NARROW: at most one column tile per spin (na, nb <= 16); a separate instantiation so that each carries only the
@@ -134,9 +146,11 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr bool MUL3 = false;
 #define PF_LEAVE(stored_closed_) return
+#define PF_HANDOVER
 #define PF_RESIDENT(KS_) prop_closed_resident<KS_, MUL3>(a, smem, phi, vhs)
 #include "k_fused_body.h"
 #undef PF_RESIDENT
+#undef PF_HANDOVER
 #undef PF_LEAVE
 }
 
@@ -154,21 +168,16 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
 template <bool NARROW, int FULL, bool TAIL, bool MUL3>
 __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a, GreensArgs ga, WeightArgs wa, const double *psiB) {
     static_assert(TAIL && !NARROW && FULL == 7, "the tail rides on the full wide deal only");
+    static_assert(!MUL3, "the 3-multiplication tail kernel takes the step hand-over: the overload below");
     extern __shared__ __align__(16) unsigned char smem[];
     bool stored_closed = false;
-    EarlyTail early;
-    early.on = false;
     do {
 #define PF_LEAVE(stored_closed_) { stored_closed = (stored_closed_); break; }
-#define PF_RESIDENT(KS_)                                                                                      \
-    do {                                                                                                      \
-        if constexpr (MUL3) {                                                                                 \
-            if (psiB) prop_closed_resident<KS_, true, true>(a, smem, phi, vhs, psiB, &early);                 \
-            else prop_closed_resident<KS_, true>(a, smem, phi, vhs);                                          \
-        } else prop_closed_resident<KS_, false>(a, smem, phi, vhs);                                           \
-    } while (0)
+#define PF_HANDOVER
+#define PF_RESIDENT(KS_) prop_closed_resident<KS_, false>(a, smem, phi, vhs)
 #include "k_fused_body.h"
 #undef PF_RESIDENT
+#undef PF_HANDOVER
 #undef PF_LEAVE
     } while (0);
     // the tail's addressing starts from here: nothing of it may be computed (and held in registers) across the bodies above
@@ -176,8 +185,49 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a, Gree
     __syncthreads();
     int w = blockIdx.x;
     asm volatile("" : "+s"(w));
-    if constexpr (MUL3) greens_small_body<true, true, true>(ga, wa, w, smem, stored_closed, &early);
-    else greens_small_body<true, true>(ga, wa, w, smem, stored_closed);
+    greens_small_body<true, true>(ga, wa, w, smem, stored_closed);
+}
+
+// The 3-multiplication tail kernel: the same, with the early overlap (psiB) and the step hand-over (ho).  An overload by its
+// argument list, under the same name: the 4-multiplication tail kernel above keeps its signature, its code and its registers.
+// PF_HANDOVER (k_fused_body.h, ahead of everything that reads the walker): when the host holds the hand-over current
+// (ho.consume) and the launch before set this walker's flag, the walker is closed by construction and goes straight to the
+// EARLY resident body, which then starts at its Taylor products -- through the ONE call of that body this kernel has
+// (a run-time flag of the call, not a second copy of the unrolled products).
+// ho.ready[w] is written for every walker of every launch, by one lane, behind the bodies: 1 exactly when the walker went
+// through the EARLY body with ho.produce set; a dead, an open-shell or a streamed walker clears it.
+template <bool NARROW, int FULL, bool TAIL, bool MUL3>
+__global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a, GreensArgs ga, WeightArgs wa, const double *psiB,
+                                                           StepHandoverArgs ho) {
+    static_assert(TAIL && !NARROW && FULL == 7 && MUL3, "the tail rides on the full wide deal only");
+    extern __shared__ __align__(16) unsigned char smem[];
+    bool stored_closed = false;
+    EarlyTail early;
+    early.on = false;
+    do {
+#define PF_LEAVE(stored_closed_) { stored_closed = (stored_closed_); break; }
+#define PF_HANDOVER                                                                                           \
+    if (ho.consume) {                                                                                         \
+        handed = __builtin_amdgcn_readfirstlane(ho.ready[w]) != 0;                                            \
+        if (handed && threadIdx.x == 0) { atomicAdd(a.n_closed, 1ULL); atomicAdd(ho.n_handed, 1ULL); }        \
+    }
+#define PF_RESIDENT(KS_)                                                                                      \
+    do {                                                                                                      \
+        if (psiB) prop_closed_resident<KS_, true, true>(a, smem, phi, vhs, psiB, &early, &ho, handed);        \
+        else prop_closed_resident<KS_, true>(a, smem, phi, vhs);                                              \
+    } while (0)
+#include "k_fused_body.h"
+#undef PF_RESIDENT
+#undef PF_HANDOVER
+#undef PF_LEAVE
+    } while (0);
+    if (ho.ready && threadIdx.x == 0) ho.ready[blockIdx.x] = (early.on && ho.produce) ? 1 : 0;
+    // the tail's addressing starts from here: nothing of it may be computed (and held in registers) across the bodies above
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+    int w = blockIdx.x;
+    asm volatile("" : "+s"(w));
+    greens_small_body<true, true, true>(ga, wa, w, smem, stored_closed, &early);
 }
 
 int k_prop_fused_supported(afq_handle *h) {
@@ -234,6 +284,15 @@ int k_prop_fused(afq_handle *h, const GreensLaunch *tail, bool mul3) {
                        tail->a.psi_real && tail->a.psi_closed && tail->a.psi_stride == 0 &&
                        (const void *)tail->a.psi == h->psiB_psi && (const void *)h->BH1 == h->psiB_bh1 &&
                        tail->a.gsum && tail->a.ghalf && !tail->a.oinv;
+    // The step hand-over (afq_handle::handover): what the launch before left is taken only when the host still holds it current
+    // and this launch is the kernel that made it; whatever this launch turns out to be, the old one is gone with it.
+    const bool consumes = early && h->handover.current && h->handover.enabled && h->t0_next && h->t0_ready;
+    h->handover.drop();
+    const bool produces = early && h->step_handover && h->handover.enabled && h->B2 && (const void *)h->BH1 == h->b2_bh1;
+    if (produces && (!h->t0_next || !h->t0_ready)) {
+        AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->t0_next, (size_t)h->nw * ((h->M + 3) / 4) * 2048, "step hand-over image"));
+        AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->t0_ready, (size_t)h->nw, "step hand-over flags"));
+    }
     KernelTrace kt(h, AFQ_K_PROPAGATOR);
     {   // matrix-pipe flops of this launch: (order complex products by 3 multiplications + 2 one-body applications by 2 or
         // 3) x k-steps of 4 x existing 16 x 16 tiles (2048 flop per v_mfma_f64_16x16x4, 512 per 4x4x4 remainder unit)
@@ -252,8 +311,12 @@ int k_prop_fused(afq_handle *h, const GreensLaunch *tail, bool mul3) {
         h->prop_issued_closed = 3.0 * h->exp_order * closed_pass + 2.0 * (a.b_real ? 2.0 : 3.0) * per_pass;
         // ... through the resident body: seven padded row tiles x the two alpha slots x ceil(M / 4) k-steps in every product
         // (4-multiplication Taylor products, two real products in each of the two one-body passes)
-        if (k_prop_closed_resident(h))
-            h->prop_issued_closed = ((tail && mul3 ? 3.0 : 4.0) * h->exp_order + 2.0 * 2.0) * ((h->M + 3) / 4) * 2048.0 * 7 * 2;
+        // (the one-body passes the launch really issues: the opening one unless the walkers start from the hand-over, the
+        //  closing one, and the next step's opening one where the launch produces -- two in steady state, as without it)
+        if (k_prop_closed_resident(h)) {
+            const double passes = (consumes ? 0.0 : 1.0) + 1.0 + (produces ? 1.0 : 0.0);
+            h->prop_issued_closed = ((tail && mul3 ? 3.0 : 4.0) * h->exp_order + passes * 2.0) * ((h->M + 3) / 4) * 2048.0 * 7 * 2;
+        }
         if (tail) {
             // ... and the tail's (greens_small_body, n <= 32): the overlap matrix as (n / 16)^2 tiles per spin over the k-steps of M
             // in whole groups of four, two multiplications per k-step against a real trial, else three; O^-1 phi^T as (n / 16) x
@@ -291,12 +354,18 @@ int k_prop_fused(afq_handle *h, const GreensLaunch *tail, bool mul3) {
         if (full != 7 || !a.resident || tail->lds > lds)
             AFQ_FAIL(h, AFQ_ESTATE, "internal: a Green's function tail on a propagator launch outside its shape class");
         if (mul3) {
-            AFQ_HIP(h, afq_raise_lds((const void *)prop_fused_kernel<false, 7, true, true>, lds, lds_set[6]));
+            void (*const kern)(PropFusedArgs, GreensArgs, WeightArgs, const double *, StepHandoverArgs) =
+                prop_fused_kernel<false, 7, true, true>;
+            AFQ_HIP(h, afq_raise_lds((const void *)kern, lds, lds_set[6]));
             const double *psiB = early ? h->psiB_cT : nullptr;
-            AFQ_LAUNCH(h, (prop_fused_kernel<false, 7, true, true>), dim3(h->nw), dim3(PF_NT), lds, h->stream, a, tail->a, tail->wa, psiB);
+            StepHandoverArgs ho;
+            ho.t0_next = h->t0_next; ho.ready = h->t0_ready; ho.B2 = h->B2; ho.n_handed = h->counters + 9;
+            ho.consume = consumes ? 1 : 0; ho.produce = produces ? 1 : 0;
+            AFQ_LAUNCH(h, (prop_fused_kernel<false, 7, true, true>), dim3(h->nw), dim3(PF_NT), lds, h->stream, a, tail->a, tail->wa, psiB, ho);
         } else {
             const double *psiB = nullptr;
-            AFQ_HIP(h, afq_raise_lds((const void *)prop_fused_kernel<false, 7, true, false>, lds, lds_set[7]));
+            void (*const kern)(PropFusedArgs, GreensArgs, WeightArgs, const double *) = prop_fused_kernel<false, 7, true, false>;
+            AFQ_HIP(h, afq_raise_lds((const void *)kern, lds, lds_set[7]));
             AFQ_LAUNCH(h, (prop_fused_kernel<false, 7, true, false>), dim3(h->nw), dim3(PF_NT), lds, h->stream, a, tail->a, tail->wa, psiB);
         }
     }
@@ -308,5 +377,6 @@ int k_prop_fused(afq_handle *h, const GreensLaunch *tail, bool mul3) {
     else PF_LAUNCH_(false, 0, 5);
 #undef PF_LAUNCH_
     AFQ_POST(h);
+    if (produces) h->handover.produced();
     return AFQ_OK;
 }

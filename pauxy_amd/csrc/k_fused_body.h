@@ -3,7 +3,8 @@
 // instruction, the code it had before the tail existed.  In scope at the point of inclusion: the kernel's template flags
 // NARROW and FULL, MUL3 (the resident closed-shell body's Taylor products in the 3-multiplication form), its argument `a`,
 // the dynamic LDS `smem`, and PF_LEAVE(stored_closed): how a walker leaves ahead of the end (a dead walker, or one the resident
-// body has stored closed by construction); PF_RESIDENT(KS): the call of the resident body with KS k-steps.
+// body has stored closed by construction); PF_RESIDENT(KS): the call of the resident body with KS k-steps; PF_HANDOVER: the
+// 3-multiplication tail kernel's test for a step hand-over (sets `handed`), empty in every other kernel.
     const int w = blockIdx.x;
     if (!a.alive[w]) PF_LEAVE(false);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -73,14 +74,21 @@
         if (++gi_slot == PF_D) gi_slot = 0;
         prepared = false;
     };
+    // The step hand-over (the 3-multiplication tail kernel alone; PF_HANDOVER is empty everywhere else and `handed` then a
+    // constant): the launch before has left this walker's opening pass behind.  Such a walker is closed by construction; it
+    // issues no ring chunk and reads no phi, neither for the compare nor for the image.
+    bool handed = false;
+    PF_HANDOVER
+    if (!handed) {
     issueA(); issueA();                                          // PF_D - 1 chunks in flight
     prepare();
+    }
     // ---- Closed-shell walker?  (spin blocks bitwise equal: checked on the walker itself, every launch, no state.)  Every
     // matrix of the chain acts on both spins alike (closed_try: one one-body matrix, as many electrons of either spin), so the
     // beta half would stay the bitwise copy of the alpha half through all the products: the Taylor stage multiplies the
     // alpha half only (closed-shell deals below) and copies it into the beta half ahead of the closing one-body pass.
-    bool closed = false;
-    if (a.closed_try) {
+    bool closed = handed;
+    if (!handed && a.closed_try) {
         bool same = true;
         for (int p = tid >> 5; p < M; p += PF_NT / 32) {
             const int c = tid & 31;

@@ -23,6 +23,9 @@
 //     3-multiplication form of taylor(), im = P3 - P1 - P2) (re = P1 - P2 at the end, im accumulated in one
 //     register set): k ascending in steps of 4, T_n = product / n, sum += T_n as in taylor().  Four MFMAs per k-step and slot
 //     where taylor()'s 3-multiplication form has three: see DESIGN section 4 for why this body pays them.
+//   * EARLY with the step hand-over (StepHandoverArgs, afq_set_step_handover): under wave 7's inversion the other waves also
+//     make the opening pass of the NEXT step, (B B) S, and store it as an image of T in memory; a walker that finds one from the
+//     launch before starts at the Taylor products.  See "Hand-over" in the body.
 // Rows and k >= M read a zero page: the padding of T stays zero through every product.
 #pragma once
 
@@ -31,8 +34,11 @@
 template <int KS, bool MUL3, bool EARLY = false>
 __device__ __attribute__((always_inline)) inline void prop_closed_resident(const PropFusedArgs &a, unsigned char *smem_,
                                                                            cplx *phi, const cplx *vhs,
-                                                                           const double *psiB = nullptr, EarlyTail *et = nullptr) {
+                                                                           const double *psiB = nullptr, EarlyTail *et = nullptr,
+                                                                           const StepHandoverArgs *ho = nullptr, const bool handed_ = false) {
     auto *smem = PCR_LDS(smem_);
+    // EARLY alone: the walker starts from the image of T_0 the launch before left in ho->t0_next (see "Hand-over" below)
+    const bool handed = EARLY && handed_;                       // work-group uniform
     typedef __attribute__((address_space(3))) d2_t lds_d2;
     typedef __attribute__((address_space(3))) double lds_f64;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -51,13 +57,29 @@ __device__ __attribute__((always_inline)) inline void prop_closed_resident(const
     // (EARLY with an odd `order`: image 1, so that the Taylor sum ends in image 1 for either parity and image 0, where the
     //  tail's overlap matrix lies, is dead behind the last product)
     const unsigned base0 = (EARLY && (a.order & 1)) ? TB : 0u;
-    for (int e = tid; e < KS * 128; e += PF_NT) {
-        const int k = 4 * (e >> 7) + ((e >> 4) & 3), col = 16 * ((e >> 6) & 1) + (e & 15);
-        const bool ok = k < M && col < na;
-        const cplx v = phi[ok ? k * nt + col : 0];
-        ((lds_d2 *)(smem + base0))[e] = ok ? (d2_t){v.x, v.y} : (d2_t){0.0, 0.0};
+    // Hand-over (EARLY, afq_set_step_handover): T_0 = B phi of THIS step was made by the launch before, as (B B) S under its
+    // inversion, and lies in ho->t0_next[w] as the image itself -- same linear offsets, padding included.  The walker then
+    // reads no phi at all: the work-group requests the image (16 bytes per thread and trip) and, right behind it, waves 0-6
+    // their own accumulator slice of it (the first term of the sum) and their fragments of V; the image goes to LDS ahead of
+    // the barrier in front of the Taylor products, V stays in flight as on the other path.
+    constexpr int NCP = (KS * 128 + PF_NT - 1) / PF_NT;
+    d2_t cp[NCP];
+    if (handed) {
+        const d2_t *t0 = (const d2_t *)(ho->t0_next + (size_t)blockIdx.x * TB);
+#pragma unroll
+        for (int i = 0; i < NCP; ++i) {
+            const int e = tid + i * PF_NT;
+            cp[i] = t0[e < KS * 128 ? e : 0];
+        }
+    } else {
+        for (int e = tid; e < KS * 128; e += PF_NT) {
+            const int k = 4 * (e >> 7) + ((e >> 4) & 3), col = 16 * ((e >> 6) & 1) + (e & 15);
+            const bool ok = k < M && col < na;
+            const cplx v = phi[ok ? k * nt + col : 0];
+            ((lds_d2 *)(smem + base0))[e] = ok ? (d2_t){v.x, v.y} : (d2_t){0.0, 0.0};
+        }
+        __syncthreads();
     }
-    __syncthreads();
 
     // A fragments of Re(BH1), this wave's row tile
     auto load_b = [&](double (&bh)[KS]) __attribute__((always_inline)) {
@@ -101,7 +123,19 @@ __device__ __attribute__((always_inline)) inline void prop_closed_resident(const
         // ---- V fragments: issued here, behind the operands of the opening pass, and consumed from the first Taylor product
         // on -- the loads travel under that pass
         double bh[KS];
-        load_b(bh);
+        if (handed) {
+            // register q of row tile `wave`, slot j = lane image of k-step 4 wave + q, slot j (see put)
+            const d2_t *t0 = (const d2_t *)(ho->t0_next + (size_t)blockIdx.x * TB) + lane_id();
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const d2_t v = 4 * wave + q < KS ? t0[((4 * wave + q) * 2 + j) * 64] : (d2_t){0.0, 0.0};
+                    SR[j][q] = v[0]; SI[j][q] = v[1];
+                }
+        } else {
+            load_b(bh);
+        }
         const int lane = lane_id(), lk = lane >> 4, row = wave * 16 + (lane & 15);   // this lane's row and k of the A operands
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
@@ -111,9 +145,11 @@ __device__ __attribute__((always_inline)) inline void prop_closed_resident(const
             const d2_t *p = (row < M && k < M) ? (const d2_t *)(vhs + off) : (const d2_t *)a.zero16;
             av[s] = *p;
         }
-        // ---- T_0 = B phi: image 0 -> image 1, and the first term of the sum
-        one_body(base0, bh, SR, SI);
-        put(base0 ^ TB, SR, SI);
+        if (!handed) {
+            // ---- T_0 = B phi: image 0 -> image 1, and the first term of the sum
+            one_body(base0, bh, SR, SI);
+            put(base0 ^ TB, SR, SI);
+        }
     }
     // EARLY: wave 7, idle here, stages psi^H B in the free LDS above both images as A fragments -- [row tile t of 16 trial
     // orbitals][k-step s][64 lanes x 8 B], lane (lr, lk) = psiB[16 t + lr][4 s + lk], 2 * KS * 512 B <= 26 KB of the 48 KB --
@@ -136,6 +172,13 @@ __device__ __attribute__((always_inline)) inline void prop_closed_resident(const
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int s = 0; s < KS; ++s) *(lds_f64 *)(pb + (t * KS + s) * 512) = pv[t][s];
+        }
+    }
+    if (handed) {
+#pragma unroll
+        for (int i = 0; i < NCP; ++i) {
+            const int e = tid + i * PF_NT;
+            if (e < KS * 128) ((lds_d2 *)(smem + (base0 ^ TB)))[e] = cp[i];
         }
     }
     lds_barrier();
@@ -246,6 +289,59 @@ __device__ __attribute__((always_inline)) inline void prop_closed_resident(const
                         phi[(long)orow * nt + na + col] = v;
                     }
                 }
+            // Hand-over, producing side: the opening pass of the NEXT step, T_0 = B phi' = (B B) S, from the same image with
+            // the A fragments of B2 = B B (host-made, as psiB), still under wave 7's inversion; its accumulators are stored
+            // lane-linearly as the image the consumer copies (put's layout: all KS k-steps x 2 slots, padding included).
+            // Deal: wave 3 shares SIMD 3 with the inverting wave 7, and fp64 MFMAs beside the inversion lengthen it.  A result
+            // that is only stored needs no fixed owner, so wave 3 sits this pass out and the two units of its row tile go to
+            // waves 4 and 5 (SIMDs 0 and 1: three units each, slot wave - 4 of row tile 3 as the third).
+            if (ho->produce && wave != 3) {
+                const bool third = wave == 4 || wave == 5;          // wave-uniform
+                auto load_b2 = [&](const int rt, double (&bf)[KS]) __attribute__((always_inline)) {
+                    const int ln = lane_id(), hk = ln >> 4, hrow = rt * 16 + (ln & 15);
+#pragma unroll
+                    for (int s = 0; s < KS; ++s) {
+                        const int k = 4 * s + hk;
+                        const double *p = (hrow < M && k < M) ? ho->B2 + hrow * M + k : (const double *)a.zero16;
+                        bf[s] = *p;
+                    }
+                };
+                auto store_t0 = [&](const int rt, const int j, const d4_t &re, const d4_t &im) __attribute__((always_inline)) {
+                    d2_t *t0 = (d2_t *)(ho->t0_next + (size_t)blockIdx.x * TB) + lane_id();
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (4 * rt + q < KS) t0[((4 * rt + q) * 2 + j) * 64] = (d2_t){re[q], im[q]};
+                };
+                d4_t Q1[2], Q2[2];
+                load_b2(wave, bh);
+                if (third) {
+                    double b3[KS];
+                    load_b2(3, b3);
+                    const int j3 = wave - 4;
+                    d4_t X1 = {0, 0, 0, 0}, X2 = {0, 0, 0, 0};
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) { Q1[j] = (d4_t){0, 0, 0, 0}; Q2[j] = (d4_t){0, 0, 0, 0}; }
+                    const auto *tb = smem + cur + lane_id() * 16;
+                    const auto *tx = tb + j3 * 1024;
+#pragma unroll
+                    for (int s = 0; s < KS; ++s) {
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const d2_t b = *(const lds_d2 *)(tb + (s * 2 + j) * 1024);
+                            Q1[j] = mfma16(bh[s], b[0], Q1[j]);
+                            Q2[j] = mfma16(bh[s], b[1], Q2[j]);
+                        }
+                        const d2_t b = *(const lds_d2 *)(tx + s * 2048);
+                        X1 = mfma16(b3[s], b[0], X1);
+                        X2 = mfma16(b3[s], b[1], X2);
+                    }
+                    store_t0(3, j3, X1, X2);
+                } else {
+                    one_body(cur, bh, Q1, Q2);
+                }
+#pragma unroll
+                for (int j = 0; j < 2; ++j) store_t0(wave, j, Q1[j], Q2[j]);
+            }
         } else {
             cplx *scr = O + nsq;                                    // spin down's block: 32 + 32 complex, 32 ints
             gj_wave32(O, nn, lane_id(), true, scr, scr + 32, (int *)(scr + 64), et->ph, et->la);

@@ -718,7 +718,8 @@ class AfqDevice(object):
     def counters(self, reset=False, n=4):
         """[nfb_trig, nhe_trig, flagged overlap matrices, closed-deal propagator walker steps] and with n = 8 also
         [.., one-spin exchange-energy walker evaluations, one-spin Green's functions, NaN determinant overlaps taken as zero,
-        closed-shell walker steps of the large-system GEMM chain] (afq_counters_ext)."""
+        closed-shell walker steps of the large-system GEMM chain] (afq_counters_ext); [8] and [9] (n = 10): walker steps of
+        the early overlap and of the step hand-over."""
         out = numpy.zeros(max(4, n), dtype=numpy.int64)
         self._ck(self.lib.afq_counters_ext(self.h, _p(out), int(max(4, n)), int(reset)))
         return out
@@ -810,6 +811,12 @@ class AfqDevice(object):
         """Mode 2's tail takes the overlap matrix and its inverse from the resident body's closing pass (default on; off:
         the launch of before, bit for bit; counters(n=9)[8] counts the walker steps; see afq_set_step_tail_overlap)."""
         self._ck(self.lib.afq_set_step_tail_overlap(self.h, int(on)))
+
+    def set_step_handover(self, on):
+        """Mode 2's launch with the early overlap also makes the next step's opening one-body pass under its inversion, and
+        a step that nothing has come between starts from it (default on; off: the launch of before; counters(n=10)[9] counts
+        the walker steps; see afq_set_step_handover)."""
+        self._ck(self.lib.afq_set_step_handover(self.h, int(on)))
 
     def propagator_closed_form(self):
         m = ctypes.c_int()
