@@ -719,6 +719,39 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
                                      int options);
 int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi_out);
 
+/* ---- finite-temperature AFQMC with continuous fields: thermal walkers of the Hubbard model --------------------
+ * thermal_propagation/continuous.py:84-120,202-257 (Continuous, phaseless, force bias, hybrid weight) with
+ * thermal_propagation/hubbard.py:199-250 (HubbardContinuous, the charge form) and the non-diagonal branch of
+ * walkers/stack.py:299-324.  The walkers are the complex ones above; the trial's density matrix and BH1 are dense and
+ * real, the field exponential is a diagonal.
+ *   afq_thermal_configure_hubbard_continuous  after afq_set_system_hubbard and afq_walkers_alloc.  BT, BT_inv, BH1
+ *                          f64[2, M, M], all dense: the trial's dmat, its inverse, and
+ *                          expm(-dt/2 (h1e_mod - i sqrt(U) diag(mf_shift) + sign mu)); mf_shift c128[M] =
+ *                          i sqrt(U) diag(P_up + P_dn) of the trial; mf_const_fac c128[1] = exp(-dt mf_shift.mf_shift / 2).
+ *                          left_k = BT^stack_size BT_inv^(k + 1) is built on the host in the reference's order.
+ *                          options: AFQ_THERMAL_STREAMED_GREENS is honoured, the other AFQ_THERMAL_* bits are
+ *                          refused by name.  The bound on M is the smallest of the slice kernel's
+ *                          40 M (M | 1) + 1024 bytes of LDS (M <= 63), the Green's kernel's (M <= 47 resident, 64
+ *                          streamed) and the 64 lanes of a wave: M <= 47, and M <= 63 with the bit.  Above it
+ *                          AFQ_EUNSUPPORTED names M, the kernel that does not fit, its bytes and the bound.  Also
+ *                          refused: a system that is not Hubbard, more than one rank, back-propagation / ITCF /
+ *                          mixed RDM on the handle.  Ends with afq_thermal_reset and M0 = det of the trial's G.
+ *   afq_thermal_propagate_continuous  on such a handle: vbias_i = i sqrt(U) (P_up,ii + P_dn,ii),
+ *                          xbar = -sqrt(dt) (vbias - mf_shift), |xbar_i| > 1 scaled to unit modulus (each counted in
+ *                          afq_counters [0]), xs, cmf, cfb as above; BV = diag(sum_{n <= 6} v^n / n!),
+ *                          v = sqrt(dt) i sqrt(U) xs; B_s = BH1_s (BV BH1_s); the stack, G_s and Mnew_s as above;
+ *                          magn = |mf_const_fac exp(hyb)|, the rest of the weight update as above.  K = M fields.
+ *   afq_thermal_reset / _greens / _energy / _state serve it; energy is the Hubbard energy of P_s = I - G_s^T.
+ *   afq_thermal_left_table  the host-side table the configuration uploads, for inspection (no handle, no device):
+ *                          BTpow_out f64[2, M, M] = BT left-multiplied stack_size times onto I and left_out
+ *                          f64[stack_size, 2, M, M], left_k = left_(k - 1) BT_inv, in the reference's order of
+ *                          operations (walkers/stack.py:238-243,309-310), every element one chain of fused
+ *                          multiply-adds over k ascending.                                                        */
+int afq_thermal_left_table(int M, int stack_size, const double *BT, const double *BT_inv, double *BTpow_out, double *left_out);
+int afq_thermal_configure_hubbard_continuous(afq_handle *h, int ntime_slices, int stack_size, double dt, const double *BT,
+                                             const double *BT_inv, const double *BH1, const double *mf_shift,
+                                             const double *mf_const_fac, int options);
+
 /* ---- misc ------------------------------------------------------------------ */
 /* Device stream of auxiliary fields (used by afq_propagate with xi == NULL; replaces numpy.random.normal of
  * propagation/continuous.py:133 when parity with the host stream is not required): Philox4x32-10 (Salmon et

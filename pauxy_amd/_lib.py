@@ -161,6 +161,8 @@ SIGNATURES = {
     "afq_thermal_state": [_h, c_void_p],
     "afq_thermal_configure_continuous": [_h, c_int, c_int, c_double, _dp, _dp, _dp, _dp, c_double, c_int],
     "afq_thermal_propagate_continuous": [_h, _dp, _dp],
+    "afq_thermal_configure_hubbard_continuous": [_h, c_int, c_int, c_double, _dp, _dp, _dp, _dp, _dp, c_int],
+    "afq_thermal_left_table": [c_int, c_int, _dp, _dp, _dp, _dp],
 }
 
 

@@ -281,6 +281,14 @@ struct afq_handle {
     double *thc_bh1 = nullptr;      // [2, M] diagonal of BH1
     bool thc_streamed = false;      // AFQ_THERMAL_STREAMED_GREENS: every Green's function by the streamed kernel
     cplx *thc_tscratch = nullptr;   // [nw, 2, 2, M, M] T of the streamed kernel, two buffers per work-group (else null)
+    // continuous fields with a dense trial and a dense BH1 (afq_thermal_configure_hubbard_continuous; thermal_propagation/
+    // continuous.py, hubbard.py:199-250): the thc_* walkers above, with these in place of the three diagonals
+    bool thc_dense = false;
+    double *thd_BTpow = nullptr;    // [2, M, M] BT^stack_size
+    double *thd_left = nullptr;     // [stack_size, 2, M, M] left_k = BT^stack_size BT_inv^(k + 1)
+    double *thd_bh1 = nullptr;      // [2, M, M]
+    double thd_mf_const[2] = {1.0, 0.0};   // exp(-dt mf_core) (re, im)
+    double thd_sqrt_u = 0.0;        // iu_fac = i sqrt(U)
 
     // ---- propagator
     bool have_prop = false;

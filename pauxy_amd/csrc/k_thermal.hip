@@ -143,7 +143,7 @@ int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int n
                           const double *BT_inv, const double *BH1, const double *auxf, int options) {
     AFQ_API(h, "afq_thermal_configure");
     if (!h) return AFQ_EINVAL;
-    h->th_on = false; h->th_cplx = false;
+    h->th_on = false; h->th_cplx = false; h->thc_dense = false;
     if (!BT || !BT_inv || !BH1 || !auxf) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure: null operand");
     if (options & AFQ_THERMAL_CHARGE) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: charge_decomposition is not supported (spin decomposition only)");
     if (options & AFQ_THERMAL_FREE_PROJECTION) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: free_projection is not supported (constrained path only)");

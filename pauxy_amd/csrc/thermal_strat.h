@@ -443,7 +443,7 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_rdm_kernel(const T *G, cpl
 // what every thermal entry point asks first; want_cplx: the continuous fields' walkers are needed
 inline int th_need(afq_handle *h, bool want_cplx) {
     if (!h->th_on || !h->nw || (want_cplx && !h->th_cplx))
-        AFQ_FAIL(h, AFQ_ESTATE, want_cplx ? "thermal walkers: afq_thermal_configure_continuous first"
+        AFQ_FAIL(h, AFQ_ESTATE, want_cplx ? "thermal walkers: afq_thermal_configure_continuous or afq_thermal_configure_hubbard_continuous first"
                                           : "thermal walkers: afq_thermal_configure or afq_thermal_configure_continuous first");
     if (h->prop_pending) AFQ_FAIL(h, AFQ_ESTATE, "a step is half done: afq_propagate_finish first");
     hipSetDevice(h->device);

@@ -420,6 +420,19 @@ class AfqDevice(object):
         self.thermal_nbins = int(ntime_slices) // int(stack_size)
         self.thermal_dtype = numpy.complex128
 
+    def thermal_configure_hubbard_continuous(self, ntime_slices, stack_size, dt, BT, BT_inv, BH1, mf_shift, mf_const_fac,
+                                             options=0):
+        """Hubbard with continuous fields (dense trial, dense BH1): the walkers' G and bins are complex from here on."""
+        M = self.M
+        BT, BT_inv, BH1 = _f64(BT, (2, M, M)), _f64(BT_inv, (2, M, M)), _f64(BH1, (2, M, M))
+        mf_shift = _c128(mf_shift, (M,))
+        mfc = _c128(numpy.array([mf_const_fac]), (1,))
+        self._ck(self.lib.afq_thermal_configure_hubbard_continuous(self.h, int(ntime_slices), int(stack_size), float(dt),
+                                                                   _p(BT), _p(BT_inv), _p(BH1), _p(mf_shift), _p(mfc),
+                                                                   int(options)))
+        self.thermal_nbins = int(ntime_slices) // int(stack_size)
+        self.thermal_dtype = numpy.complex128
+
     def thermal_propagate_continuous(self, xi=None, fetch_fields=False):
         """One slice of every walker; xi [nw, K] or None for the device's stream.  -> the fields used, when asked for."""
         if xi is not None:

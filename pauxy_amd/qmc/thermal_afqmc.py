@@ -12,6 +12,7 @@ import numpy
 
 from pauxy_amd.comm import FakeComm
 from pauxy_amd.estimators.handler import Estimators
+from pauxy_amd.propagation.thermal_continuous import Continuous
 from pauxy_amd.propagation.thermal_hubbard import ThermalDiscrete
 from pauxy_amd.propagation.thermal_planewave import PlaneWave
 from pauxy_amd.qmc.options import QMCOpts
@@ -37,10 +38,19 @@ def get_trial_density_matrix(system, beta, dt, options={}, verbose=False):
     raise NotImplementedError("trial density matrix '%s' is not supported (MeanField included): one_body only" % name)
 
 
+def continuous_hubbard(system, options):
+    """thermal_propagation/utils.py:26-35: a Hubbard run takes continuous fields when ``hubbard_stratonovich`` is given
+    and is not 'discrete'."""
+    return system.name == "Hubbard" and options.get('hubbard_stratonovich', 'discrete') != 'discrete'
+
+
 def get_propagator(system, trial, qmc, options={}, lowrank=False):
-    """thermal_propagation/utils.py: discrete Hirsch fields for the Hubbard model, plane waves for the UEG."""
+    """thermal_propagation/utils.py: plane waves for the UEG; for the Hubbard model discrete Hirsch fields (the
+    default), or ``Continuous`` when ``hubbard_stratonovich`` names anything else."""
     if system.name == "UEG":
         return PlaneWave(system, trial, qmc, options=options, lowrank=lowrank)
+    if continuous_hubbard(system, options):
+        return Continuous(options, qmc, system, trial, lowrank=lowrank)
     return ThermalDiscrete(system, trial, qmc, options=options, lowrank=lowrank)
 
 
@@ -77,9 +87,11 @@ class ThermalAFQMC(object):
         self.trial = trial
         self.qmc.nwalkers = max(1, int(self.qmc.nwalkers / self.comm.size))
         self.qmc.ntot_walkers = self.qmc.nwalkers * self.nprocs
-        self.walk = Walkers(system, trial, self.qmc, walker_opts=_opt(options, 'walkers', ['walker', 'walker_opts']),
-                            comm=self.comm)
         prop_opts = _opt(options, 'propagator', ['prop', 'propagation'])
+        walker_opts = _opt(options, 'walkers', ['walker', 'walker_opts'])
+        if continuous_hubbard(system, prop_opts):                           # complex walkers with a dense trial
+            walker_opts = dict(walker_opts, continuous_fields=True)
+        self.walk = Walkers(system, trial, self.qmc, walker_opts=walker_opts, comm=self.comm)
         self.propagators = get_propagator(system, trial, self.qmc, prop_opts, self.walk.walkers[0].lowrank)
         est_opts = _opt(options, 'estimators', ['estimates'])
         if est_opts.get('back_propagation', est_opts.get('back_propagated')) is not None or est_opts.get('itcf') is not None:

@@ -2,17 +2,26 @@
 and walkers/thermal.py, walkers/stack.py of the reference).
 
 A thermal walker is its Green's function G [2, M, M] and a stack of propagator products; both live in the library
-(k_thermal.hip: Hubbard, discrete fields, real matrices; k_thermal_cplx.hip: UEG, continuous fields, complex matrices,
-and with them the running product of the current bin and M0 = det G).  ``walkers[i]`` are light views with the members
-the reference's driver and estimators read (``weight``, ``G``, ``M0``, ``stack``, ``stack_size``, ``stack_length``,
-``local_energy``, ``greens_function``)."""
+(k_thermal.hip: Hubbard, discrete fields, real matrices; k_thermal_cplx.hip: continuous fields, complex matrices, and
+with them the running product of the current bin and M0 = det G -- the UEG with its diagonal trial, and the Hubbard
+model with a dense trial when a ``Continuous`` propagator configures the population).  ``walkers[i]`` are light views
+with the members the reference's driver and estimators read (``weight``, ``G``, ``M0``, ``stack``, ``stack_size``,
+``stack_length``, ``local_energy``, ``greens_function``)."""
 import numpy
 
 from pauxy_amd import _lib as L
 from pauxy_amd.context import get_context, hidden
+from pauxy_amd.propagation import thermal_continuous
 from pauxy_amd.propagation.thermal_hubbard import thermal_constants
 from pauxy_amd.propagation.thermal_planewave import MAX_BASIS, MAX_BASIS_STREAMED, planewave_constants
 from pauxy_amd.trial_density import update_stack
+
+
+class _QmcOf(object):
+    """What a propagator's constructor reads of the QMC options."""
+
+    def __init__(self, dt, nstblz):
+        self.dt, self.nstblz = dt, nstblz
 
 
 class ThermalWalkerView(object):
@@ -51,7 +60,7 @@ class ThermalWalkerView(object):
 
     @property
     def M0(self):
-        """det G_s the next weight update divides by (UEG, continuous fields)."""
+        """det G_s the next weight update divides by (continuous fields)."""
         self._h.ensure_configured()
         return self._h.dev.get(L.F_THERMAL_M0, self.index, 1)[0]
 
@@ -91,7 +100,13 @@ class ThermalWalkers(object):
         if system.name not in ("Hubbard", "UEG"):
             raise NotImplementedError("thermal walkers: Hubbard systems only (no Generic / UEG) with discrete fields, and "
                                       "the UEG with continuous fields; %s has no thermal path" % system.name)
+        # The walker kind: real (Hubbard, discrete fields), complex with a diagonal trial (UEG), complex with a dense
+        # trial (Hubbard, continuous fields).  The UEG's is known here.  A Hubbard population's is decided by the
+        # propagator that configures it (ensure_configured(prop)); `continuous_fields: True` among the walkers' options
+        # announces the dense kind, which is what lets `streamed_greens` through before a propagator exists.
         self.continuous = system.name == "UEG"
+        self.dense = False
+        self.expect_dense = system.name == "Hubbard" and bool(walker_opts.get('continuous_fields', False))
         if not hasattr(trial, 'dmat_inv'):
             raise NotImplementedError("thermal walkers: a OneBody trial density matrix is needed (no MeanField)")
         if walker_opts.get('low_rank', False):
@@ -102,10 +117,14 @@ class ThermalWalkers(object):
                                       "included): comb only" % self.pcont_method)
         # the Green's function with T in device memory (k_thermal_cplx.hip, AFQ_THERMAL_STREAMED_GREENS)
         self.streamed_greens = bool(walker_opts.get('streamed_greens', False))
-        if self.streamed_greens and not self.continuous:
-            raise NotImplementedError("thermal walkers: streamed_greens belongs to the UEG's continuous fields (Hubbard "
-                                      "walkers fit to M = 64 as they are)")
-        if self.streamed_greens and system.nbasis > MAX_BASIS_STREAMED:
+        if self.streamed_greens and not self.continuous and not self.expect_dense:
+            raise NotImplementedError("thermal walkers: streamed_greens belongs to the continuous fields (Hubbard "
+                                      "walkers with discrete fields fit to M = 64 as they are; with "
+                                      "hubbard_stratonovich: 'continuous' the driver announces the complex walkers, and "
+                                      "walkers: {continuous_fields: True} does so by hand)")
+        if self.expect_dense:
+            self._check_dense_bound(system.nbasis)
+        if self.continuous and self.streamed_greens and system.nbasis > MAX_BASIS_STREAMED:
             raise NotImplementedError("thermal walkers: M = %d > %d plane waves is not supported with streamed_greens "
                                       "(the slice kernel keeps three complex matrices in LDS)"
                                       % (system.nbasis, MAX_BASIS_STREAMED))
@@ -156,6 +175,12 @@ class ThermalWalkers(object):
         """The library is configured on first use: the propagator's stabilisation period decides when it is known."""
         if self.continuous:
             return self._ensure_configured_continuous(prop)
+        if self.dense or getattr(prop, 'hs_type', None) == 'continuous' or (prop is None and self.expect_dense and
+                                                                            self.configured_nstblz is None):
+            return self._ensure_configured_dense(prop)
+        if self.streamed_greens:
+            raise NotImplementedError("thermal walkers: streamed_greens belongs to the continuous fields (Hubbard "
+                                      "walkers with discrete fields fit to M = 64 as they are)")
         nstblz = self.nstblz if prop is None else prop.nstblz
         if self.configured_nstblz == nstblz:
             return
@@ -184,6 +209,36 @@ class ThermalWalkers(object):
                                               self.trial.dmat_inv, BH1, mf_shift, fb_bound,
                                               L.THERMAL_STREAMED_GREENS if self.streamed_greens else 0)
         self.configured_fb_bound = fb_bound
+
+    def _check_dense_bound(self, M):
+        bound = thermal_continuous.MAX_BASIS_STREAMED if self.streamed_greens else thermal_continuous.MAX_BASIS
+        if M > bound:
+            raise NotImplementedError(
+                "thermal walkers with continuous fields: M = %d > %d sites is not supported%s" % (
+                    M, bound, " with streamed_greens (the slice kernel keeps two complex matrices and BH1 in LDS)"
+                    if self.streamed_greens else " (the complex Green's function keeps a walker's working set in LDS; "
+                    "walkers: {streamed_greens: True} reaches M = %d)" % thermal_continuous.MAX_BASIS_STREAMED))
+
+    def _ensure_configured_dense(self, prop):
+        """Hubbard with continuous fields: the propagator's constants (BH1, mf_shift, mf_const_fac) go to the library
+        with the trial's dense matrices; without a propagator yet they are what ``Continuous`` computes from the system
+        and the trial, which is all they depend on.  A population that ran discrete fields becomes complex only at time
+        slice 0, and starts afresh; the way back is refused."""
+        if prop is not None and getattr(prop, 'hs_type', None) != 'continuous':
+            raise RuntimeError("thermal walkers: the population carries complex walkers (continuous fields); a '%s' "
+                               "propagator cannot move it" % getattr(prop, 'hs_type', None))
+        if self.dense:
+            return
+        if self.configured_nstblz is not None and self.time_slice != 0:
+            raise RuntimeError("thermal walkers: the kind of field changed in the middle of a path")
+        if prop is None:
+            prop = thermal_continuous.Continuous({}, _QmcOf(self.dt, self.nstblz), self.system, self.trial)
+        self._check_dense_bound(self.system.nbasis)
+        self.dev.thermal_configure_hubbard_continuous(self.num_slices, self.stack_size, self.dt, self.trial.dmat,
+                                                      self.trial.dmat_inv, prop.BH1, prop.mf_shift, prop.mf_const_fac,
+                                                      L.THERMAL_STREAMED_GREENS if self.streamed_greens else 0)
+        self.dense = True
+        self.configured_nstblz = None
 
     def set_total_weight(self, total_weight):
         self.total_weight = total_weight
