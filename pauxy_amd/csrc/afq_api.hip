@@ -36,7 +36,7 @@ void free_walkers(afq_handle *h) {
     h->msd_fb_gbar = false;
     h->nbp = 0; h->bpo_two = h->bpo_ekt = h->bpo_sf = h->bpo_corr = h->bpo_pair = 0; h->bpo_nL = 0; h->it_nmax = 0;
     h->rdm_on = false; h->sf_on = false;
-    h->th_on = false;
+    h->th_kind = TH_NONE;
     h->nw = 0;
 }
 
@@ -718,14 +718,14 @@ static int field_info(afq_handle *h, int field, void **base, size_t *bytes) {
     case AFQ_F_ENERGY: *base = h->energy; *bytes = 3 * sizeof(cplx); break;
     case AFQ_F_LOG_DETR: *base = h->log_detR; *bytes = sizeof(double); break;
     case AFQ_F_THERMAL_G:
-        if (h->th_on && h->th_cplx) { *base = h->thc_G; *bytes = (size_t)2 * h->M * h->M * sizeof(cplx); break; }
+        if (th_complex(h)) { *base = h->thc_G; *bytes = (size_t)2 * h->M * h->M * sizeof(cplx); break; }
         *base = h->th_G; *bytes = (size_t)2 * h->M * h->M * sizeof(double); break;
     case AFQ_F_THERMAL_STACK:
-        if (h->th_on && h->th_cplx) { *base = h->thc_stack; *bytes = (size_t)2 * h->M * h->M * h->th_nbins * sizeof(cplx); break; }
+        if (th_complex(h)) { *base = h->thc_stack; *bytes = (size_t)2 * h->M * h->M * h->th_nbins * sizeof(cplx); break; }
         *base = h->th_stack; *bytes = (size_t)2 * h->M * h->M * h->th_nbins * sizeof(double); break;
-    case AFQ_F_THERMAL_RIGHT: *base = h->th_on && h->th_cplx ? h->thc_right : nullptr; *bytes = (size_t)2 * h->M * h->M * sizeof(cplx); break;
-    case AFQ_F_THERMAL_M0: *base = h->th_on && h->th_cplx ? h->thc_M0 : nullptr; *bytes = 2 * sizeof(cplx); break;
-    case AFQ_F_THERMAL_DET: *base = h->th_on && h->th_cplx ? h->thc_det : nullptr; *bytes = 2 * sizeof(cplx); break;
+    case AFQ_F_THERMAL_RIGHT: *base = th_complex(h) ? h->thc_right : nullptr; *bytes = (size_t)2 * h->M * h->M * sizeof(cplx); break;
+    case AFQ_F_THERMAL_M0: *base = th_complex(h) ? h->thc_M0 : nullptr; *bytes = 2 * sizeof(cplx); break;
+    case AFQ_F_THERMAL_DET: *base = th_complex(h) ? h->thc_det : nullptr; *bytes = 2 * sizeof(cplx); break;
     case AFQ_F_CMF: *base = h->cmf; *bytes = sizeof(cplx); break;
     case AFQ_F_CFB: *base = h->cfb; *bytes = sizeof(cplx); break;
     default: AFQ_FAIL(h, AFQ_EINVAL, "unknown walker field");
@@ -1360,7 +1360,7 @@ int afq_set_weight_cap(afq_handle *h, double frac, double total_weight) {
 
 int afq_cap_weights(afq_handle *h, double frac, double total_weight) {
     if (!h) return AFQ_EINVAL;
-    if (h->th_on && h->nw) { hipSetDevice(h->device); return k_cap_weights(h, frac, total_weight); }   // (no trial determinant)
+    if (th_thermal(h) && h->nw) { hipSetDevice(h->device); return k_cap_weights(h, frac, total_weight); }   // (no trial determinant)
     int rc = need_ready(h, false);
     if (rc) return rc;
     return k_cap_weights(h, frac, total_weight);
@@ -1372,7 +1372,7 @@ int afq_popcontrol_comb(afq_handle *h, double r, double target_weight, int32_t *
     AFQ_API(h, "afq_popcontrol_comb");
     if (!h) return AFQ_EINVAL;
     h->handover.drop();                 // (walkers change slots: the images do not travel with the clones)
-    const bool thermal = h->th_on && h->nw;              // thermal walkers: no trial determinant, G and the bins travel
+    const bool thermal = th_thermal(h) && h->nw;              // thermal walkers: no trial determinant, G and the bins travel
     int rc = AFQ_OK;
     if (thermal) {
         h->gf.drop();
@@ -1404,7 +1404,7 @@ int afq_popcontrol_pair_branch(afq_handle *h, const double *u, int nu, double ta
     AFQ_API(h, "afq_popcontrol_pair_branch");
     if (!h) return AFQ_EINVAL;
     h->handover.drop();
-    if (h->th_on) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: pair_branch population control is not supported (comb only)");
+    if (th_thermal(h)) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: pair_branch population control is not supported (comb only)");
     int rc = need_ready(h, false);
     if (rc) { h->gf.drop(); return rc; }
     if (k_comm_size(h) > 1) {
@@ -1561,7 +1561,7 @@ int afq_estimates_update_publish(afq_handle *h, int eval_energy, int zero) {
 
 int afq_estimates_rdm(afq_handle *h, int on) {
     if (!h) return AFQ_EINVAL;
-    if (h->th_on) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no mixed one_rdm / two_rdm");
+    if (th_thermal(h)) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no mixed one_rdm / two_rdm");
     int rc = need_ready(h, false);
     if (rc) return rc;
     if (h->ndet > 1 || h->hirsch) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "mixed one_rdm: single-determinant trial, continuous propagator");

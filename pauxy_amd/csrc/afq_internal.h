@@ -42,6 +42,10 @@ enum { T_GREENS = 0, T_ONEBODY, T_FB, T_VHS, T_EXP, T_OVLP, T_QR, T_ENERGY, T_CO
 
 #define AFQ_NCOUNTERS 10    // afq_counters_ext (include/afqmc_hip.h)
 
+// The kind of thermal walker a handle holds: none, real (afq_thermal_configure), complex with a diagonal trial
+// (afq_thermal_configure_continuous), complex with a dense trial (afq_thermal_configure_hubbard_continuous)
+enum ThKind { TH_NONE = 0, TH_REAL, TH_CPLX_DIAG, TH_CPLX_DENSE };
+
 // Whether the hand-over buffers of the handle (t0_next, t0_ready) describe the walkers as they are now.  A launch of the
 // fused propagator that produced sets `current`; everything that writes phi, moves a walker to another slot, changes the
 // propagator, the trial, the Taylor order or a mode switch of the step drops it, and so does every propagator launch that is
@@ -253,7 +257,7 @@ struct afq_handle {
     int *hs_alive0 = nullptr;       // [nw] walkers the driver propagates this step (|w| > 1e-8)
 
     // ---- finite-temperature walkers (k_thermal.hip; walkers/thermal.py, walkers/stack.py, thermal_propagation/hubbard.py)
-    bool th_on = false;             // afq_thermal_configure done: the walkers are thermal walkers
+    ThKind th_kind = TH_NONE;       // which configure entry point succeeded last: what kind of thermal walker the handle holds
     int th_L = 0, th_ss = 0, th_nbins = 0, th_nstblz = 0;   // time slices, stack_size, bins, stabilisation period
     int th_slice = 0, th_block = 0, th_counter = 0;          // PropagatorStack.time_slice / block / counter (every walker's)
     double th_auxf[2][2];           // [field][spin], the chemical-potential shift folded in
@@ -265,8 +269,8 @@ struct afq_handle {
     double *th_u = nullptr;         // [nw, M] uniforms of the slice
     int *th_fields = nullptr;       // [nw, M] chosen fields (-1: both probabilities vanished)
     double *th_nav = nullptr;       // [nw]
-    // continuous fields, UEG (k_thermal_cplx.hip; thermal_propagation/planewave.py): the walker's matrices are complex
-    bool th_cplx = false;           // afq_thermal_configure_continuous done (th_on too): thc_* are the walkers' state
+    // continuous fields (k_thermal_cplx.hip; thermal_propagation/planewave.py, continuous.py with hubbard.py:199-250): the
+    // walker's matrices are complex, thc_* are its state
     cplx *thc_G = nullptr;          // [nw, 2, M, M]
     cplx *thc_G0 = nullptr;         // [2, M, M] the trial's G
     cplx *thc_stack = nullptr;      // [nw, nbins, 2, M, M]
@@ -276,17 +280,13 @@ struct afq_handle {
     cplx *thc_det = nullptr;        // [nw, 2] det G_s of the last evaluation
     cplx *thc_mf = nullptr;         // [K] mean-field shift
     double thc_fb_bound = 1.0;      // |xbar_i| above it is scaled to unit modulus
-    double *thc_BTpow = nullptr;    // [2, M] diagonal of BT^stack_size
-    double *thc_left = nullptr;     // [stack_size, 2, M] diagonal of left_k = BT^stack_size BT_inv^(k + 1)
-    double *thc_bh1 = nullptr;      // [2, M] diagonal of BH1
+    // the trial's tables: diagonals [.., 2, M] with a diagonal trial (UEG), full matrices [.., 2, M, M] with a dense one
+    double *thc_BTpow = nullptr;    // BT^stack_size
+    double *thc_left = nullptr;     // [stack_size, ..] left_k = BT^stack_size BT_inv^(k + 1)
+    double *thc_bh1 = nullptr;      // BH1
     bool thc_streamed = false;      // AFQ_THERMAL_STREAMED_GREENS: every Green's function by the streamed kernel
     cplx *thc_tscratch = nullptr;   // [nw, 2, 2, M, M] T of the streamed kernel, two buffers per work-group (else null)
-    // continuous fields with a dense trial and a dense BH1 (afq_thermal_configure_hubbard_continuous; thermal_propagation/
-    // continuous.py, hubbard.py:199-250): the thc_* walkers above, with these in place of the three diagonals
-    bool thc_dense = false;
-    double *thd_BTpow = nullptr;    // [2, M, M] BT^stack_size
-    double *thd_left = nullptr;     // [stack_size, 2, M, M] left_k = BT^stack_size BT_inv^(k + 1)
-    double *thd_bh1 = nullptr;      // [2, M, M]
+    // the dense trial's alone (afq_thermal_configure_hubbard_continuous)
     double thd_mf_const[2] = {1.0, 0.0};   // exp(-dt mf_core) (re, im)
     double thd_sqrt_u = 0.0;        // iu_fac = i sqrt(U)
 
@@ -418,6 +418,9 @@ struct afq_handle {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_energy_ms = 0.0;
 };
+
+inline bool th_thermal(const afq_handle *h) { return h->th_kind != TH_NONE; }
+inline bool th_complex(const afq_handle *h) { return h->th_kind == TH_CPLX_DIAG || h->th_kind == TH_CPLX_DENSE; }
 
 #define AFQ_HIP(h, call)                                                        \
     do {                                                                        \

@@ -271,7 +271,7 @@ extern "C" {
 // ---------------------------------------------------------------- back-propagation
 int afq_bp_configure(afq_handle *h, int nbp) {
     if (!h || nbp < 1) return AFQ_EINVAL;
-    if (h->th_on) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no back-propagation");
+    if (th_thermal(h)) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no back-propagation");
     int rc = need_ready(h, true);
     if (rc) return rc;
     if (h->ndet > 1 && h->kind != AFQ_SYS_GENERIC)
@@ -495,7 +495,7 @@ int afq_bp_pairing(afq_handle *h, int on) {
 // ---------------------------------------------------------------- imaginary-time Green's function (k_itcf.hip)
 int afq_itcf_configure(afq_handle *h, int nmax, int neqlb, int stable, int restore_weights) {
     if (!h || nmax < 1 || neqlb < 0) return AFQ_EINVAL;
-    if (h->th_on) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no ITCF window");
+    if (th_thermal(h)) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no ITCF window");
     int rc = need_ready(h, true);
     if (rc) return rc;
     if (h->M > 128) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "ITCF: M > 128 (the batched Gauss-Jordan inverse)");

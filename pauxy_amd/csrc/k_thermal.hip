@@ -143,22 +143,14 @@ int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int n
                           const double *BT_inv, const double *BH1, const double *auxf, int options) {
     AFQ_API(h, "afq_thermal_configure");
     if (!h) return AFQ_EINVAL;
-    h->th_on = false; h->th_cplx = false; h->thc_dense = false;
+    h->th_kind = TH_NONE;
     if (!BT || !BT_inv || !BH1 || !auxf) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure: null operand");
-    if (options & AFQ_THERMAL_CHARGE) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: charge_decomposition is not supported (spin decomposition only)");
-    if (options & AFQ_THERMAL_FREE_PROJECTION) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: free_projection is not supported (constrained path only)");
-    if (options & AFQ_THERMAL_LOW_RANK) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: low_rank is not supported");
-    if (options & AFQ_THERMAL_AVERAGE_GF) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: average_gf is not supported");
-    if (options & AFQ_THERMAL_STREAMED_GREENS) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure: streamed_greens belongs to the continuous fields (the real walkers fit to M = 64 as they are)");
-    if (options) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure: unknown option bits");
-    if (!h->kind || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_configure: set the system and allocate the walkers first");
-    if (h->kind != AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: Hubbard systems only (no Generic / UEG)");
+    const ThEntry me = {"afq_thermal_configure: ", 0, AFQ_EUNSUPPORTED,
+                        "thermal walkers: charge_decomposition is not supported (spin decomposition only)", AFQ_SYS_HUBBARD,
+                        "thermal walkers: Hubbard systems only (no Generic / UEG)", "all"};
+    AFQ_TRY(th_screen_options(h, me, options));
     if (h->M > TH_MAXM) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: M = " + std::to_string(h->M) + " > 64 sites do not fit a work-group's LDS");
-    if (k_comm_size(h) > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: one rank only");
-    if (h->nbp > 0 || h->it_nmax > 0) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no back-propagation or ITCF window");
-    if (h->rdm_on) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no mixed one_rdm / two_rdm");
-    if (ntime_slices < 1 || stack_size < 1 || nstblz < 1 || ntime_slices % stack_size)
-        AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure: stack_size must divide ntime_slices (all >= 1)");
+    AFQ_TRY(th_screen_state(h, me, ntime_slices, stack_size, nstblz));
     hipSetDevice(h->device);
     const int M = h->M, nbins = ntime_slices / stack_size;
     const size_t mm = (size_t)M * M, n = h->nw;
@@ -188,7 +180,7 @@ int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int n
     if ((rc = ensure_G(h))) return rc;                  // c128 [nw, 2, M, M]: the one-body density matrices of afq_thermal_energy
     for (int f = 0; f < 2; ++f) for (int s = 0; s < 2; ++s) h->th_auxf[f][s] = auxf[2 * f + s];
     h->th_L = ntime_slices; h->th_ss = stack_size; h->th_nbins = nbins; h->th_nstblz = nstblz;
-    h->th_on = true;
+    h->th_kind = TH_REAL;
     return afq_thermal_reset(h);
 }
 
@@ -196,7 +188,7 @@ int afq_thermal_reset(afq_handle *h) {
     AFQ_API(h, "afq_thermal_reset");
     if (!h) return AFQ_EINVAL;
     AFQ_TRY(th_need(h, false));
-    if (h->th_cplx) return k_thermal_c_reset(h, false);
+    if (th_complex(h)) return k_thermal_c_reset(h, false);
     const int M = h->M, nbins = h->th_nbins;
     const long per = 2L * M * M;
     // the trial's G once, from walker 0's fresh bins (every bin is BT^stack_size), then broadcast
@@ -215,14 +207,14 @@ int afq_thermal_greens(afq_handle *h, int slice_ix) {
     if (!h) return AFQ_EINVAL;
     AFQ_TRY(th_need(h, false));
     if (slice_ix < 0 || slice_ix > h->th_L) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_greens: slice_ix outside 0 .. ntime_slices");
-    return h->th_cplx ? k_thermal_c_greens(h, slice_ix) : k_thermal_greens(h, slice_ix);
+    return th_complex(h) ? k_thermal_c_greens(h, slice_ix) : k_thermal_greens(h, slice_ix);
 }
 
 int afq_thermal_propagate(afq_handle *h, const double *u, int32_t *fields_out, double eshift) {
     AFQ_API(h, "afq_thermal_propagate");
     if (!h) return AFQ_EINVAL;
     AFQ_TRY(th_need(h, false));
-    if (h->th_cplx) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_propagate: continuous fields are configured (afq_thermal_propagate_continuous)");
+    if (th_complex(h)) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_propagate: continuous fields are configured (afq_thermal_propagate_continuous)");
     if (!u) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_propagate: the uniforms f64[nw, M] are needed");
     if (h->th_slice >= h->th_L) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_propagate: the path is complete (afq_thermal_reset starts the next)");
     const int M = h->M;
@@ -239,10 +231,7 @@ int afq_thermal_propagate(afq_handle *h, const double *u, int32_t *fields_out, d
         AFQ_LAUNCH(h, thermal_slice_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a);
         AFQ_POST(h);
     }
-    // PropagatorStack.update's counters (stack.py:295-297)
-    h->th_slice += 1;
-    h->th_block = h->th_slice / h->th_ss;
-    h->th_counter = (h->th_counter + 1) % h->th_ss;
+    th_advance(h);
     if (h->th_slice % h->th_nstblz == 0) AFQ_TRY(k_thermal_greens(h, h->th_slice - 1));
     if (h->th_slice < h->th_L) {
         AFQ_LAUNCH(h, thermal_wrap_kernel, dim3(2 * h->nw), dim3(TH_THREADS), th_wrap_lds(M), h->stream, h->th_G, h->th_BT,
@@ -258,7 +247,7 @@ int afq_thermal_energy(afq_handle *h, double *E_out, double *nav_out) {
     if (!h) return AFQ_EINVAL;
     AFQ_TRY(th_need(h, false));
     if (!E_out && !nav_out) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_energy: nothing asked for");
-    if (h->th_cplx) return k_thermal_c_energy(h, E_out, nav_out);
+    if (th_complex(h)) return k_thermal_c_energy(h, E_out, nav_out);
     AFQ_TRY(ts_launch_rdm<double>(h, h->th_G, h->th_nav));
     AFQ_TRY(k_energy_hubbard_full_g(h, h->G, h->nw, h->energy));
     return th_energy_out(h, E_out, nav_out);

@@ -91,33 +91,31 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_kernel(ThcSliceArgs
     }
 }
 
-// planewave.py:239-269 for one walker per work-group, whatever its weight: xbar = -sqrt(dt) vbias, a component with
-// |xbar| > fb_bound scaled to unit modulus (counted in counters[0], as the ground-state field kernel counts its own),
-// xs = xi - xbar, cmf = -sqrt(dt) xs . mf, cfb = xi . xbar - xbar . xbar / 2 (unconjugated).  Every thread sums its
-// fields in order and the 256 partial sums are added in a fixed tree: the same bits on every run.
-__global__ __launch_bounds__(TH_THREADS) void thermal_cfields_kernel(const cplx *vbias, const double *xi, const cplx *mf,
-                                                                       cplx *xbar, cplx *xs, cplx *cmf, cplx *cfb, int K,
-                                                                       double sqrt_dt, double fb_bound,
-                                                                       unsigned long long *counters) {
+// planewave.py:239-269 / continuous.py:97-115 for one field n of walker w, whatever the walker's weight: a component of
+// xbar = b with |b| > fb_bound is scaled to unit modulus (counted in acc[6]), xs = xi - xbar, and the field's terms of
+// xs . mf (acc[0, 1]), xi . xbar (acc[2, 3]) and xbar . xbar (acc[4, 5], unconjugated).  -> xs
+__device__ __forceinline__ cplx thc_field_terms(cplx b, double fb_bound, double x, cplx m, long e, cplx *xbar, cplx *xs,
+                                                double *acc) {
+    const double ab = hypot(b.x, b.y);
+    if (ab > fb_bound) { b.x /= ab; b.y /= ab; acc[6] += 1.0; }
+    const cplx sft = cmake(x - b.x, -b.y);
+    xbar[e] = b;
+    xs[e] = sft;
+    acc[0] += sft.x * m.x - sft.y * m.y;
+    acc[1] += sft.x * m.y + sft.y * m.x;
+    acc[2] += x * b.x; acc[3] += x * b.y;
+    acc[4] += b.x * b.x - b.y * b.y;
+    acc[5] += 2.0 * b.x * b.y;
+    return sft;
+}
+
+// Every thread has summed its fields in order; the 256 partial sums are added in a fixed tree: the same bits on every
+// run.  cmf = -sqrt(dt) xs . mf, cfb = xi . xbar - xbar . xbar / 2, the clipped components onto counters[0] (as the
+// ground-state field kernel counts its own).
+__device__ __forceinline__ void thc_field_sums(const double *acc, int w, double sqrt_dt, cplx *cmf, cplx *cfb,
+                                               unsigned long long *counters) {
     __shared__ double red[7][TH_THREADS];
-    const int w = blockIdx.x, tid = threadIdx.x;
-    double acc[7] = {0, 0, 0, 0, 0, 0, 0};      // xs . mf (re, im), xi . xbar (re, im), xbar . xbar (re, im), clipped
-    for (int n = tid; n < K; n += TH_THREADS) {
-        const long e = (long)w * K + n;
-        const cplx v = vbias[e], m = mf[n];
-        cplx b = cmake(-sqrt_dt * v.x, -sqrt_dt * v.y);
-        const double ab = hypot(b.x, b.y);
-        if (ab > fb_bound) { b.x /= ab; b.y /= ab; acc[6] += 1.0; }
-        const double x = xi[e];
-        const cplx sft = cmake(x - b.x, -b.y);
-        xbar[e] = b;
-        xs[e] = sft;
-        acc[0] += sft.x * m.x - sft.y * m.y;
-        acc[1] += sft.x * m.y + sft.y * m.x;
-        acc[2] += x * b.x; acc[3] += x * b.y;
-        acc[4] += b.x * b.x - b.y * b.y;
-        acc[5] += 2.0 * b.x * b.y;
-    }
+    const int tid = threadIdx.x;
 #pragma unroll
     for (int q = 0; q < 7; ++q) red[q][tid] = acc[q];
     __syncthreads();
@@ -134,10 +132,28 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_cfields_kernel(const cplx 
     }
 }
 
-// planewave.py:493-517: oratio = M0_up M0_dn / (Mnew_up Mnew_dn), hyb = log(oratio) + cfb + cmf, magn = |exp(hyb)|;
-// a zero denominator or a magn that is not finite: weight 0 and M0 kept; else weight *= magn max(0, cos arg exp(hyb - cfb)) and
-// M0 <- Mnew (also when the cosine factor is 0).
-__global__ void thermal_cweight_kernel(double *weight, cplx *M0, const cplx *Mnew, const cplx *cmf, const cplx *cfb, int nw) {
+// planewave.py:239-269 for one walker per work-group: xbar = -sqrt(dt) vbias clipped at fb_bound, xs, cmf, cfb
+__global__ __launch_bounds__(TH_THREADS) void thermal_cfields_kernel(const cplx *vbias, const double *xi, const cplx *mf,
+                                                                       cplx *xbar, cplx *xs, cplx *cmf, cplx *cfb, int K,
+                                                                       double sqrt_dt, double fb_bound,
+                                                                       unsigned long long *counters) {
+    const int w = blockIdx.x, tid = threadIdx.x;
+    double acc[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int n = tid; n < K; n += TH_THREADS) {
+        const long e = (long)w * K + n;
+        const cplx v = vbias[e];
+        thc_field_terms(cmake(-sqrt_dt * v.x, -sqrt_dt * v.y), fb_bound, xi[e], mf[n], e, xbar, xs, acc);
+    }
+    thc_field_sums(acc, w, sqrt_dt, cmf, cfb, counters);
+}
+
+// planewave.py:493-517: oratio = M0_up M0_dn / (Mnew_up Mnew_dn), hyb = log(oratio) + cfb + cmf, magn = |exp(hyb)|, or
+// with MF (continuous.py:234-257) |mfc exp(hyb)|, mfc the constant of the mean-field shift; a zero denominator or a magn
+// that is not finite: weight 0 and M0 kept; else weight *= magn max(0, cos arg exp(hyb - cfb)) and M0 <- Mnew (also when
+// the cosine factor is 0).
+template <bool MF>
+__device__ __forceinline__ void thc_weight_update(double *weight, cplx *M0, const cplx *Mnew, const cplx *cmf, const cplx *cfb,
+                                                  cplx mfc, int nw) {
     const int w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= nw) return;
     const cplx num = cmul(M0[2 * w], M0[2 * w + 1]), den = cmul(Mnew[2 * w], Mnew[2 * w + 1]);
@@ -145,13 +161,26 @@ __global__ void thermal_cweight_kernel(double *weight, cplx *M0, const cplx *Mne
     const cplx oratio = cdiv(num, den);
     const cplx lg = cmake(log(hypot(oratio.x, oratio.y)), atan2(oratio.y, oratio.x));
     const cplx hyb = cadd(cadd(lg, cfb[w]), cmf[w]);
-    const double magn = exp(hyb.x);
+    double magn = exp(hyb.x);
+    if (MF) {
+        const cplx eq = cmul(mfc, cmake(magn * cos(hyb.y), magn * sin(hyb.y)));
+        magn = hypot(eq.x, eq.y);
+    }
     if (!(magn < INFINITY)) { weight[w] = 0.0; return; }      // infinite or NaN (a NaN M0 or Mnew): dies, keeps M0
     const double dtheta = hyb.y - cfb[w].y;
     const double cosine = fmax(0.0, cos(dtheta));
     weight[w] *= magn * cosine;
     M0[2 * w] = Mnew[2 * w];
     M0[2 * w + 1] = Mnew[2 * w + 1];
+}
+
+__global__ void thermal_cweight_kernel(double *weight, cplx *M0, const cplx *Mnew, const cplx *cmf, const cplx *cfb, int nw) {
+    thc_weight_update<false>(weight, M0, Mnew, cmf, cfb, cmake(1.0, 0.0), nw);
+}
+
+__global__ void thermal_cweight_mf_kernel(double *weight, cplx *M0, const cplx *Mnew, const cplx *cmf, const cplx *cfb,
+                                          cplx mfc, int nw) {
+    thc_weight_update<true>(weight, M0, Mnew, cmf, cfb, mfc, nw);
 }
 
 // ---- a dense real trial and a dense real BH1 with a diagonal field exponential: the Hubbard model with continuous
@@ -260,36 +289,23 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_dense_kernel(ThdSli
     }
 }
 
-// continuous.py:97-115 with hubbard.py:241-250 for one walker per work-group, whatever its weight: vbias_i =
-// i sqrt(U) (P_up,ii + P_dn,ii) from the diagonal of P [nw, 2, M, M], xbar = -sqrt(dt) (vbias - mf), a component with
-// |xbar| > 1 scaled to unit modulus (each counted in counters[0]), xs, cmf, cfb as thermal_cfields_kernel makes them
-// and in its order of summation, and the diagonal of BV: bv_i = sum_{n <= 6} v^n / n!, v = sqrt(dt) i sqrt(U) xs_i, by
-// the reference's recurrence t <- v t / n.
+// continuous.py:97-115 with hubbard.py:241-250 for one walker per work-group: vbias_i = i sqrt(U) (P_up,ii + P_dn,ii)
+// from the diagonal of P [nw, 2, M, M], xbar = -sqrt(dt) (vbias - mf) clipped at 1, xs, cmf, cfb as
+// thermal_cfields_kernel makes them, and the diagonal of BV: bv_i = sum_{n <= 6} v^n / n!, v = sqrt(dt) i sqrt(U) xs_i,
+// by the reference's recurrence t <- v t / n.
 __global__ __launch_bounds__(TH_THREADS) void thermal_cfields_dense_kernel(const cplx *P, const double *xi, const cplx *mf,
                                                                              cplx *xbar, cplx *xs, cplx *cmf, cplx *cfb,
                                                                              cplx *bv, int M, double sqrt_dt, double sqrt_u,
                                                                              unsigned long long *counters) {
-    __shared__ double red[7][TH_THREADS];
     const int w = blockIdx.x, tid = threadIdx.x;
     const long mm = (long)M * M;
     const cplx *Pw = P + (long)w * 2 * mm;
-    double acc[7] = {0, 0, 0, 0, 0, 0, 0};      // xs . mf (re, im), xi . xbar (re, im), xbar . xbar (re, im), clipped
+    double acc[7] = {0, 0, 0, 0, 0, 0, 0};
     for (int n = tid; n < M; n += TH_THREADS) {
         const long e = (long)w * M + n;
         const cplx pu = Pw[(long)n * M + n], pd = Pw[mm + (long)n * M + n], m = mf[n];
         const cplx v = cmake(-sqrt_u * (pu.y + pd.y), sqrt_u * (pu.x + pd.x));
-        cplx b = cmake(-sqrt_dt * (v.x - m.x), -sqrt_dt * (v.y - m.y));
-        const double ab = hypot(b.x, b.y);
-        if (ab > 1.0) { b.x /= ab; b.y /= ab; acc[6] += 1.0; }
-        const double x = xi[e];
-        const cplx sft = cmake(x - b.x, -b.y);
-        xbar[e] = b;
-        xs[e] = sft;
-        acc[0] += sft.x * m.x - sft.y * m.y;
-        acc[1] += sft.x * m.y + sft.y * m.x;
-        acc[2] += x * b.x; acc[3] += x * b.y;
-        acc[4] += b.x * b.x - b.y * b.y;
-        acc[5] += 2.0 * b.x * b.y;
+        const cplx sft = thc_field_terms(cmake(-sqrt_dt * (v.x - m.x), -sqrt_dt * (v.y - m.y)), 1.0, xi[e], m, e, xbar, xs, acc);
         const double f = sqrt_dt * sqrt_u;
         const cplx vh = cmake(-f * sft.y, f * sft.x);
         cplx t = cmake(1.0, 0.0), phi = cmake(1.0, 0.0);
@@ -300,41 +316,7 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_cfields_dense_kernel(const
         }
         bv[e] = phi;
     }
-#pragma unroll
-    for (int q = 0; q < 7; ++q) red[q][tid] = acc[q];
-    __syncthreads();
-    for (int o = TH_THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o)
-#pragma unroll
-            for (int q = 0; q < 7; ++q) red[q][tid] += red[q][tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        cmf[w] = cmake(-sqrt_dt * red[0][0], -sqrt_dt * red[1][0]);
-        cfb[w] = cmake(red[2][0] - 0.5 * red[4][0], red[3][0] - 0.5 * red[5][0]);
-        if (red[6][0] > 0 && counters) atomicAdd(&counters[0], (unsigned long long)red[6][0]);
-    }
-}
-
-// continuous.py:234-257: thermal_cweight_kernel with the constant of the mean-field shift: magn = |mfc exp(hyb)|
-__global__ void thermal_cweight_mf_kernel(double *weight, cplx *M0, const cplx *Mnew, const cplx *cmf, const cplx *cfb,
-                                          cplx mfc, int nw) {
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= nw) return;
-    const cplx num = cmul(M0[2 * w], M0[2 * w + 1]), den = cmul(Mnew[2 * w], Mnew[2 * w + 1]);
-    if (den.x == 0.0 && den.y == 0.0) { weight[w] = 0.0; return; }
-    const cplx oratio = cdiv(num, den);
-    const cplx lg = cmake(log(hypot(oratio.x, oratio.y)), atan2(oratio.y, oratio.x));
-    const cplx hyb = cadd(cadd(lg, cfb[w]), cmf[w]);
-    const double ex = exp(hyb.x);
-    const cplx eq = cmul(mfc, cmake(ex * cos(hyb.y), ex * sin(hyb.y)));
-    const double magn = hypot(eq.x, eq.y);
-    if (!(magn < INFINITY)) { weight[w] = 0.0; return; }      // infinite or NaN: dies, keeps M0
-    const double dtheta = hyb.y - cfb[w].y;
-    const double cosine = fmax(0.0, cos(dtheta));
-    weight[w] *= magn * cosine;
-    M0[2 * w] = Mnew[2 * w];
-    M0[2 * w + 1] = Mnew[2 * w + 1];
+    thc_field_sums(acc, w, sqrt_dt, cmf, cfb, counters);
 }
 
 // walker blockIdx.y: bins <- diag(BTpow) [2, M], or with dense the matrices BTpow [2, M, M]; unless bins_only also
@@ -378,14 +360,13 @@ int k_thermal_c_reset(afq_handle *h, bool with_m0) {
     const int M = h->M, nbins = h->th_nbins;
     const long per = 2L * M * M;
     // the trial's G and M0 once, from walker 0's fresh bins (every bin is BT^stack_size), then broadcast
-    const double *BTpow = h->thc_dense ? h->thd_BTpow : h->thc_BTpow;
-    const int dense = h->thc_dense ? 1 : 0;
+    const int dense = h->th_kind == TH_CPLX_DENSE ? 1 : 0;
     AFQ_LAUNCH(h, thermal_creset_kernel, dim3((unsigned)((per + 255) / 256), 1), dim3(256), 0, h->stream, h->thc_stack, h->thc_G,
-               h->thc_right, h->thc_M0, h->weight, BTpow, h->thc_G0, h->thc_M00, nbins, M, 1, 0, dense);
+               h->thc_right, h->thc_M0, h->weight, h->thc_BTpow, h->thc_G0, h->thc_M00, nbins, M, 1, 0, dense);
     AFQ_POST(h);
     AFQ_TRY(thc_launch_greens(h, h->thc_G0, h->thc_M00, ts_first_bin(h, 0), 0, 2));
     AFQ_LAUNCH(h, thermal_creset_kernel, dim3((unsigned)((per + 255) / 256), h->nw), dim3(256), 0, h->stream, h->thc_stack,
-               h->thc_G, h->thc_right, h->thc_M0, h->weight, BTpow, h->thc_G0, h->thc_M00, nbins, M, 0, with_m0 ? 1 : 0, dense);
+               h->thc_G, h->thc_right, h->thc_M0, h->weight, h->thc_BTpow, h->thc_G0, h->thc_M00, nbins, M, 0, with_m0 ? 1 : 0, dense);
     AFQ_POST(h);
     h->th_slice = 0; h->th_block = 0; h->th_counter = 0;
     return AFQ_OK;
@@ -393,7 +374,7 @@ int k_thermal_c_reset(afq_handle *h, bool with_m0) {
 
 int k_thermal_c_energy(afq_handle *h, double *E_out, double *nav_out) {
     AFQ_TRY(ts_launch_rdm<cplx>(h, h->thc_G, h->th_nav));
-    if (h->thc_dense) {                                 // Hubbard: the full-G energy of P, as the real walkers' (k_thermal.hip)
+    if (h->th_kind == TH_CPLX_DENSE) {                  // Hubbard: the full-G energy of P, as the real walkers' (k_thermal.hip)
         AFQ_TRY(k_energy_hubbard_full_g(h, h->G, h->nw, h->energy));
         return th_energy_out(h, E_out, nav_out);
     }
@@ -403,6 +384,122 @@ int k_thermal_c_energy(afq_handle *h, double *E_out, double *nav_out) {
     return th_energy_out(h, E_out, nav_out);
 }
 
+namespace {
+
+// ---- configuring: what the two entry points share
+
+// One kernel's LDS as the refusal words it: "need <bytes(M)> bytes of LDS for <what>, a work-group has .. <hint>"
+struct ThcLds {
+    const char *what;
+    size_t (*bytes)(int M);
+    const char *hint;
+};
+const char *const THC_RESIDENT_HINT = "; AFQ_THERMAL_STREAMED_GREENS (streamed_greens) keeps T in device memory and reaches further";
+
+// M within what every kernel of `need` and lane = column hold; else the refusal names the first of them that does not
+// fit, with its bytes, and the largest M that passes.  who: "" or ", Hubbard"; unit: what M counts.
+int thc_screen_bound(afq_handle *h, const char *who, const char *unit, bool streamed, std::initializer_list<ThcLds> need) {
+    auto fits = [&](int m) {
+        for (const ThcLds &k : need)
+            if (k.bytes(m) > THC_LDS_MAX) return false;
+        return m <= THC_LANES;
+    };
+    const int M = h->M;
+    if (fits(M)) return AFQ_OK;
+    int mmax = M;
+    while (mmax > 1 && !fits(mmax)) --mmax;
+    const std::string head = std::string("thermal walkers with continuous fields") + who + (streamed ? " (streamed_greens)" : "") +
+                             ": M = " + std::to_string(M) + " " + unit + " ";
+    const std::string tail = " (M <= " + std::to_string(mmax) + ")";
+    for (const ThcLds &k : need)
+        if (k.bytes(M) > THC_LDS_MAX)
+            AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(k.bytes(M)) + " bytes of LDS for " + k.what +
+                     ", a work-group has " + std::to_string(THC_LDS_MAX) + tail + k.hint);
+    AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "are more than the " + std::to_string(THC_LANES) + " lanes of a wave, one per column" + tail);
+}
+
+// Behind an entry point's own checks: its host-built tables (`per` numbers per slice: 2 M diagonals or 2 M M), the
+// walkers' buffers, the path's shape, the kind, and a fresh population.
+int thc_configure_common(afq_handle *h, ThKind kind, int ntime_slices, int stack_size, double dt, bool streamed, double fb_bound,
+                         const double *BTpow, const double *left, const double *bh1, size_t per, const double *mf_shift) {
+    const size_t mm = (size_t)h->M * h->M, n = h->nw;
+    const int nbins = ntime_slices / stack_size;
+    int rc;
+    if ((rc = dev_upload(h, LT_WALKERS, &h->thc_BTpow, BTpow, per)) ||
+        (rc = dev_upload(h, LT_WALKERS, &h->thc_left, left, (size_t)stack_size * per)) ||
+        (rc = dev_upload(h, LT_WALKERS, &h->thc_bh1, bh1, per)) ||
+        (rc = dev_upload(h, LT_WALKERS, &h->thc_mf, mf_shift, (size_t)h->K))) return rc;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->thc_G, 2 * mm * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_G0, 2 * mm)) ||
+        (rc = dev_alloc(h, LT_WALKERS, &h->thc_stack, 2 * mm * n * nbins)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_right, 2 * mm * n)) ||
+        (rc = dev_alloc(h, LT_WALKERS, &h->thc_M0, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_M00, (size_t)2)) ||
+        (rc = dev_alloc(h, LT_WALKERS, &h->thc_det, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_nav, n))) return rc;
+    // T of the streamed Green's kernel, two buffers per (walker, spin); a handle configured without it holds none
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->thc_tscratch, streamed ? 4 * mm * n : (size_t)0))) return rc;
+    h->thc_streamed = streamed;
+    if ((rc = ensure_G(h))) return rc;                  // c128 [nw, 2, M, M]: the one-body density matrices
+    h->thc_fb_bound = fb_bound;
+    h->dt = dt; h->sqrt_dt = std::pow(dt, 0.5);        // (the handle's time step, as afq_set_propagator sets it)
+    h->th_L = ntime_slices; h->th_ss = stack_size; h->th_nbins = nbins; h->th_nstblz = 1;
+    h->th_kind = kind;
+    return k_thermal_c_reset(h, true);
+}
+
+// ---- one slice: the two steps that depend on the trial's kind
+
+// UEG: vbias = P . [iA | iB], xbar = -sqrt(dt) vbias clipped at fb_bound, xs, cmf, cfb (planewave.py:219-276), VHS,
+// and the slice kernel on the trial's diagonals
+int thc_slice_diag(afq_handle *h) {
+    const int M = h->M;
+    AFQ_TRY(k_vbias_ueg(h));
+    AFQ_LAUNCH(h, thermal_cfields_kernel, dim3(h->nw), dim3(TH_THREADS), 0, h->stream, h->vbias, h->xi, h->thc_mf, h->xbar,
+               h->xs, h->cmf, h->cfb, h->K, h->sqrt_dt, h->thc_fb_bound, h->counters);
+    AFQ_POST(h);
+    AFQ_TRY(k_vhs_ueg(h));                              // VHS = sqrt(dt) (iA xs[:nq] + iB xs[nq:])
+    ThcSliceArgs a;
+    a.vhs = h->vhs; a.right = h->thc_right; a.stack = h->thc_stack; a.bh1 = h->thc_bh1;
+    a.left = h->thc_left + (size_t)h->th_counter * 2 * M;
+    a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
+    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
+    const size_t lds = thc_slice_lds(M);
+    AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_kernel, lds, lds_set));
+    AFQ_LAUNCH(h, thermal_cslice_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a);
+    AFQ_POST(h);
+    return AFQ_OK;
+}
+
+// Hubbard: the force bias, the clip at 1, xs, cmf, cfb and the diagonal of BV from P's diagonal, and the slice kernel
+// on the trial's matrices
+int thc_slice_dense(afq_handle *h) {
+    const int M = h->M;
+    AFQ_LAUNCH(h, thermal_cfields_dense_kernel, dim3(h->nw), dim3(TH_THREADS), 0, h->stream, h->G, h->xi, h->thc_mf,
+               h->xbar, h->xs, h->cmf, h->cfb, h->vhs, M, h->sqrt_dt, h->thd_sqrt_u, h->counters);
+    AFQ_POST(h);
+    ThdSliceArgs a;
+    a.bv = h->vhs; a.right = h->thc_right; a.stack = h->thc_stack; a.bh1 = h->thc_bh1;
+    a.left = h->thc_left + (size_t)h->th_counter * 2 * M * M;
+    a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
+    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
+    const size_t lds = thd_slice_lds(M);
+    AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_dense_kernel, lds, lds_set));
+    AFQ_LAUNCH(h, thermal_cslice_dense_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a);
+    AFQ_POST(h);
+    return AFQ_OK;
+}
+
+// the phaseless weight from the determinant ratio; the dense kind's carries the constant of the mean-field shift
+int thc_weight(afq_handle *h) {
+    if (h->th_kind == TH_CPLX_DENSE)
+        AFQ_LAUNCH(h, thermal_cweight_mf_kernel, dim3((h->nw + 127) / 128), dim3(128), 0, h->stream, h->weight, h->thc_M0,
+                   h->thc_det, h->cmf, h->cfb, cmake(h->thd_mf_const[0], h->thd_mf_const[1]), h->nw);
+    else
+        AFQ_LAUNCH(h, thermal_cweight_kernel, dim3((h->nw + 127) / 128), dim3(128), 0, h->stream, h->weight, h->thc_M0, h->thc_det,
+                   h->cmf, h->cfb, h->nw);
+    AFQ_POST(h);
+    return AFQ_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_size, double dt, const double *BT,
@@ -410,57 +507,29 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
                                      int options) {
     AFQ_API(h, "afq_thermal_configure_continuous");
     if (!h) return AFQ_EINVAL;
-    h->th_on = false; h->th_cplx = false; h->thc_dense = false;
-    if (!BT || !BT_inv || !BH1 || !mf_shift) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure_continuous: null operand");
-    if (options & AFQ_THERMAL_CHARGE) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure_continuous: charge_decomposition belongs to the discrete fields");
-    if (options & AFQ_THERMAL_FREE_PROJECTION) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: free_projection is not supported (constrained path only)");
-    if (options & AFQ_THERMAL_LOW_RANK) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: low_rank is not supported");
-    if (options & AFQ_THERMAL_AVERAGE_GF) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: average_gf is not supported");
+    h->th_kind = TH_NONE;
+    const ThEntry me = {"afq_thermal_configure_continuous: ", AFQ_THERMAL_STREAMED_GREENS, AFQ_EINVAL,
+                        "afq_thermal_configure_continuous: charge_decomposition belongs to the discrete fields", AFQ_SYS_UEG,
+                        "thermal walkers with continuous fields: UEG systems only (no Generic, no continuous Hubbard)", "both"};
+    if (!BT || !BT_inv || !BH1 || !mf_shift) AFQ_FAIL(h, AFQ_EINVAL, me.me + "null operand");
+    AFQ_TRY(th_screen_options(h, me, options));
     const bool streamed = (options & AFQ_THERMAL_STREAMED_GREENS) != 0;
-    if (options & ~AFQ_THERMAL_STREAMED_GREENS) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure_continuous: unknown option bits");
-    if (!h->kind || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_configure_continuous: set the system and allocate the walkers first");
-    if (h->kind != AFQ_SYS_UEG) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers with continuous fields: UEG systems only (no Generic, no continuous Hubbard)");
+    const ThcLds slice = {"the slice kernel (thermal_cslice_kernel)", thc_slice_lds, ""};
+    if (streamed)
+        AFQ_TRY(thc_screen_bound(h, "", "plane waves", true, {slice,
+                {"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}}));
+    else
+        AFQ_TRY(thc_screen_bound(h, "", "plane waves", false, {{"the complex Green's function", ts_greens_lds<cplx>, THC_RESIDENT_HINT}, slice}));
+    AFQ_TRY(th_screen_state(h, me, ntime_slices, stack_size, 1));
+    if (!(dt > 0.0) || !(fb_bound >= 0.0)) AFQ_FAIL(h, AFQ_EINVAL, me.me + "dt must be positive, fb_bound not negative");
     const int M = h->M;
-    if (streamed) {
-        // the smallest of what the slice kernel, the streamed Green's kernel and lane = column hold
-        auto fits = [](int m) {
-            return thc_slice_lds(m) <= THC_LDS_MAX && ts_greens_streamed_lds<cplx>(m) <= THC_LDS_MAX && m <= THC_LANES;
-        };
-        if (!fits(M)) {
-            int mmax = M;
-            while (mmax > 1 && !fits(mmax)) --mmax;
-            const std::string head = "thermal walkers with continuous fields (streamed_greens): M = " + std::to_string(M) + " plane waves ";
-            const std::string tail = " (M <= " + std::to_string(mmax) + ")";
-            if (thc_slice_lds(M) > THC_LDS_MAX)
-                AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(thc_slice_lds(M)) + " bytes of LDS for the slice kernel "
-                         "(thermal_cslice_kernel), a work-group has " + std::to_string(THC_LDS_MAX) + tail);
-            if (ts_greens_streamed_lds<cplx>(M) > THC_LDS_MAX)
-                AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(ts_greens_streamed_lds<cplx>(M)) + " bytes of LDS for the "
-                         "streamed Green's function (thermal_cgreens_streamed_kernel), a work-group has " + std::to_string(THC_LDS_MAX) + tail);
-            AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "are more than the " + std::to_string(THC_LANES) + " lanes of a wave, one per column" + tail);
-        }
-    } else if (ts_greens_lds<cplx>(M) > THC_LDS_MAX) {
-        int mmax = M;
-        while (mmax > 1 && ts_greens_lds<cplx>(mmax) > THC_LDS_MAX) --mmax;
-        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers with continuous fields: M = " + std::to_string(M) + " plane waves need " +
-                 std::to_string(ts_greens_lds<cplx>(M)) + " bytes of LDS for the complex Green's function, a work-group has " +
-                 std::to_string(THC_LDS_MAX) + " (M <= " + std::to_string(mmax) + "); AFQ_THERMAL_STREAMED_GREENS (streamed_greens) "
-                 "keeps T in device memory and reaches further");
-    }
-    if (k_comm_size(h) > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: one rank only");
-    if (h->nbp > 0 || h->it_nmax > 0) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no back-propagation or ITCF window");
-    if (h->rdm_on) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no mixed one_rdm / two_rdm");
-    if (ntime_slices < 1 || stack_size < 1 || ntime_slices % stack_size)
-        AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure_continuous: stack_size must divide ntime_slices (both >= 1)");
-    if (!(dt > 0.0) || !(fb_bound >= 0.0)) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure_continuous: dt must be positive, fb_bound not negative");
-    const size_t mm = (size_t)M * M, n = h->nw;
+    const size_t mm = (size_t)M * M;
     for (int s = 0; s < 2; ++s)
         for (int i = 0; i < M; ++i)
             for (int j = 0; j < M; ++j)
                 if (i != j && (BT[s * mm + (size_t)i * M + j] != 0.0 || BT_inv[s * mm + (size_t)i * M + j] != 0.0))
                     AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers with continuous fields: a diagonal trial density matrix only (OneBody on plane waves)");
     hipSetDevice(h->device);
-    const int nbins = ntime_slices / stack_size;
     // PropagatorStack.set_all and update_full_rank with a diagonal trial (stack.py:229-236,305-307): left = BT applied
     // stack_size times to 1; the k-th slice of a bin multiplies it by BT_inv once more.  The reference reads only the
     // diagonal of BH1 (planewave.py:462-469).
@@ -474,24 +543,8 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
             for (int k = 0; k < stack_size; ++k) { p = p * bi; left[((size_t)k * 2 + s) * M + i] = p; }
             bh[(size_t)s * M + i] = BH1[s * mm + (size_t)i * M + i];
         }
-    int rc;
-    if ((rc = dev_upload(h, LT_WALKERS, &h->thc_BTpow, pw.data(), pw.size())) ||
-        (rc = dev_upload(h, LT_WALKERS, &h->thc_left, left.data(), left.size())) ||
-        (rc = dev_upload(h, LT_WALKERS, &h->thc_bh1, bh.data(), bh.size())) ||
-        (rc = dev_upload(h, LT_WALKERS, &h->thc_mf, mf_shift, (size_t)h->K))) return rc;
-    if ((rc = dev_alloc(h, LT_WALKERS, &h->thc_G, 2 * mm * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_G0, 2 * mm)) ||
-        (rc = dev_alloc(h, LT_WALKERS, &h->thc_stack, 2 * mm * n * nbins)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_right, 2 * mm * n)) ||
-        (rc = dev_alloc(h, LT_WALKERS, &h->thc_M0, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_M00, (size_t)2)) ||
-        (rc = dev_alloc(h, LT_WALKERS, &h->thc_det, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_nav, n))) return rc;
-    // T of the streamed Green's kernel, two buffers per (walker, spin); a handle configured without it holds none
-    if ((rc = dev_alloc(h, LT_WALKERS, &h->thc_tscratch, streamed ? 4 * mm * n : (size_t)0))) return rc;
-    h->thc_streamed = streamed;
-    if ((rc = ensure_G(h))) return rc;                  // c128 [nw, 2, M, M]: the one-body density matrices
-    h->thc_fb_bound = fb_bound;
-    h->dt = dt; h->sqrt_dt = std::pow(dt, 0.5);        // (the handle's time step, as afq_set_propagator sets it)
-    h->th_L = ntime_slices; h->th_ss = stack_size; h->th_nbins = nbins; h->th_nstblz = 1;
-    h->th_on = true; h->th_cplx = true;
-    return k_thermal_c_reset(h, true);
+    return thc_configure_common(h, TH_CPLX_DIAG, ntime_slices, stack_size, dt, streamed, fb_bound, pw.data(), left.data(),
+                                bh.data(), 2 * (size_t)M, mf_shift);
 }
 
 int afq_thermal_left_table(int M, int stack_size, const double *BT, const double *BT_inv, double *BTpow_out, double *left_out) {
@@ -505,71 +558,29 @@ int afq_thermal_configure_hubbard_continuous(afq_handle *h, int ntime_slices, in
                                              const double *mf_const_fac, int options) {
     AFQ_API(h, "afq_thermal_configure_hubbard_continuous");
     if (!h) return AFQ_EINVAL;
-    h->th_on = false; h->th_cplx = false; h->thc_dense = false;
-    const std::string me = "afq_thermal_configure_hubbard_continuous: ";
-    if (!BT || !BT_inv || !BH1 || !mf_shift || !mf_const_fac) AFQ_FAIL(h, AFQ_EINVAL, me + "null operand");
-    if (options & AFQ_THERMAL_CHARGE) AFQ_FAIL(h, AFQ_EINVAL, me + "charge_decomposition belongs to the discrete fields (the continuous form is the charge form alone)");
-    if (options & AFQ_THERMAL_FREE_PROJECTION) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: free_projection is not supported (constrained path only)");
-    if (options & AFQ_THERMAL_LOW_RANK) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: low_rank is not supported");
-    if (options & AFQ_THERMAL_AVERAGE_GF) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: average_gf is not supported");
+    h->th_kind = TH_NONE;
+    const ThEntry me = {"afq_thermal_configure_hubbard_continuous: ", AFQ_THERMAL_STREAMED_GREENS, AFQ_EINVAL,
+                        "afq_thermal_configure_hubbard_continuous: charge_decomposition belongs to the discrete fields (the "
+                        "continuous form is the charge form alone)", AFQ_SYS_HUBBARD,
+                        "thermal walkers with continuous fields and a dense trial: Hubbard systems only (no Generic)", "both"};
+    if (!BT || !BT_inv || !BH1 || !mf_shift || !mf_const_fac) AFQ_FAIL(h, AFQ_EINVAL, me.me + "null operand");
+    AFQ_TRY(th_screen_options(h, me, options));
     const bool streamed = (options & AFQ_THERMAL_STREAMED_GREENS) != 0;
-    if (options & ~AFQ_THERMAL_STREAMED_GREENS) AFQ_FAIL(h, AFQ_EINVAL, me + "unknown option bits");
-    if (!h->kind || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, me + "set the system and allocate the walkers first");
-    if (h->kind != AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers with continuous fields and a dense trial: Hubbard systems only (no Generic)");
-    const int M = h->M;
-    {
-        // the smallest of what the slice kernel, the Green's kernel of the handle and lane = column hold
-        auto greens_lds = [&](int m) { return streamed ? ts_greens_streamed_lds<cplx>(m) : ts_greens_lds<cplx>(m); };
-        auto fits = [&](int m) { return thd_slice_lds(m) <= THC_LDS_MAX && greens_lds(m) <= THC_LDS_MAX && m <= THC_LANES; };
-        if (!fits(M)) {
-            int mmax = M;
-            while (mmax > 1 && !fits(mmax)) --mmax;
-            const std::string head = std::string("thermal walkers with continuous fields, Hubbard") + (streamed ? " (streamed_greens)" : "") +
-                                     ": M = " + std::to_string(M) + " sites ";
-            const std::string tail = " (M <= " + std::to_string(mmax) + ")";
-            if (greens_lds(M) > THC_LDS_MAX)
-                AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(greens_lds(M)) + " bytes of LDS for the " +
-                         (streamed ? "streamed Green's function (thermal_cgreens_streamed_kernel)"
-                                   : "complex Green's function (thermal_cgreens_kernel)") +
-                         ", a work-group has " + std::to_string(THC_LDS_MAX) + tail +
-                         (streamed ? "" : "; AFQ_THERMAL_STREAMED_GREENS (streamed_greens) keeps T in device memory and reaches further"));
-            if (thd_slice_lds(M) > THC_LDS_MAX)
-                AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(thd_slice_lds(M)) + " bytes of LDS for the slice kernel "
-                         "(thermal_cslice_dense_kernel), a work-group has " + std::to_string(THC_LDS_MAX) + tail);
-            AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "are more than the " + std::to_string(THC_LANES) + " lanes of a wave, one per column" + tail);
-        }
-    }
-    if (k_comm_size(h) > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: one rank only");
-    if (h->nbp > 0 || h->it_nmax > 0) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no back-propagation or ITCF window");
-    if (h->rdm_on) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no mixed one_rdm / two_rdm");
-    if (ntime_slices < 1 || stack_size < 1 || ntime_slices % stack_size)
-        AFQ_FAIL(h, AFQ_EINVAL, me + "stack_size must divide ntime_slices (both >= 1)");
-    if (!(dt > 0.0)) AFQ_FAIL(h, AFQ_EINVAL, me + "dt must be positive");
-    if (!(h->U >= 0.0)) AFQ_FAIL(h, AFQ_EINVAL, me + "U must not be negative (iu_fac = i sqrt(U))");
+    const ThcLds greens = streamed ? ThcLds{"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}
+                                   : ThcLds{"the complex Green's function (thermal_cgreens_kernel)", ts_greens_lds<cplx>, THC_RESIDENT_HINT};
+    AFQ_TRY(thc_screen_bound(h, ", Hubbard", "sites", streamed,
+                             {greens, {"the slice kernel (thermal_cslice_dense_kernel)", thd_slice_lds, ""}}));
+    AFQ_TRY(th_screen_state(h, me, ntime_slices, stack_size, 1));
+    if (!(dt > 0.0)) AFQ_FAIL(h, AFQ_EINVAL, me.me + "dt must be positive");
+    if (!(h->U >= 0.0)) AFQ_FAIL(h, AFQ_EINVAL, me.me + "U must not be negative (iu_fac = i sqrt(U))");
     hipSetDevice(h->device);
-    const size_t mm = (size_t)M * M, n = h->nw;
-    const int nbins = ntime_slices / stack_size;
+    const size_t mm = (size_t)h->M * h->M;
     std::vector<double> pw(2 * mm), left((size_t)stack_size * 2 * mm);
-    thd_left_table(M, stack_size, BT, BT_inv, pw.data(), left.data());
-    int rc;
-    if ((rc = dev_upload(h, LT_WALKERS, &h->thd_BTpow, pw.data(), pw.size())) ||
-        (rc = dev_upload(h, LT_WALKERS, &h->thd_left, left.data(), left.size())) ||
-        (rc = dev_upload(h, LT_WALKERS, &h->thd_bh1, BH1, 2 * mm)) ||
-        (rc = dev_upload(h, LT_WALKERS, &h->thc_mf, mf_shift, (size_t)M))) return rc;
-    if ((rc = dev_alloc(h, LT_WALKERS, &h->thc_G, 2 * mm * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_G0, 2 * mm)) ||
-        (rc = dev_alloc(h, LT_WALKERS, &h->thc_stack, 2 * mm * n * nbins)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_right, 2 * mm * n)) ||
-        (rc = dev_alloc(h, LT_WALKERS, &h->thc_M0, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_M00, (size_t)2)) ||
-        (rc = dev_alloc(h, LT_WALKERS, &h->thc_det, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_nav, n))) return rc;
-    if ((rc = dev_alloc(h, LT_WALKERS, &h->thc_tscratch, streamed ? 4 * mm * n : (size_t)0))) return rc;
-    h->thc_streamed = streamed;
-    if ((rc = ensure_G(h))) return rc;                  // c128 [nw, 2, M, M]: the one-body density matrices
+    thd_left_table(h->M, stack_size, BT, BT_inv, pw.data(), left.data());
     h->thd_mf_const[0] = mf_const_fac[0]; h->thd_mf_const[1] = mf_const_fac[1];
     h->thd_sqrt_u = std::pow(h->U, 0.5);
-    h->thc_fb_bound = 1.0;
-    h->dt = dt; h->sqrt_dt = std::pow(dt, 0.5);
-    h->th_L = ntime_slices; h->th_ss = stack_size; h->th_nbins = nbins; h->th_nstblz = 1;
-    h->th_on = true; h->th_cplx = true; h->thc_dense = true;
-    return k_thermal_c_reset(h, true);
+    return thc_configure_common(h, TH_CPLX_DENSE, ntime_slices, stack_size, dt, streamed, 1.0, pw.data(), left.data(), BH1,
+                                2 * mm, mf_shift);
 }
 
 int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi_out) {
@@ -577,63 +588,16 @@ int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi
     if (!h) return AFQ_EINVAL;
     AFQ_TRY(th_need(h, true));
     if (h->th_slice >= h->th_L) AFQ_FAIL(h, AFQ_ESTATE, "afq_thermal_propagate_continuous: the path is complete (afq_thermal_reset starts the next)");
-    const int M = h->M;
     const size_t nf = (size_t)h->nw * h->K;
     // the fields of every walker, dead ones included (the thermal driver skips none): the host's, or the device stream
     if (xi) AFQ_HIP(h, hipMemcpyAsync(h->xi, xi, sizeof(double) * nf, hipMemcpyHostToDevice, h->stream));
     else AFQ_TRY(k_rng_normal_into(h, h->xi, (long)nf));
-    if (h->thc_dense) {
-        // P = I - G^T; the force bias, the clip at 1, xs, cmf, cfb and the diagonal of BV from P's diagonal
-        AFQ_TRY(ts_launch_rdm<cplx>(h, h->thc_G, nullptr));
-        AFQ_LAUNCH(h, thermal_cfields_dense_kernel, dim3(h->nw), dim3(TH_THREADS), 0, h->stream, h->G, h->xi, h->thc_mf,
-                   h->xbar, h->xs, h->cmf, h->cfb, h->vhs, M, h->sqrt_dt, h->thd_sqrt_u, h->counters);
-        AFQ_POST(h);
-        ThdSliceArgs a;
-        a.bv = h->vhs; a.right = h->thc_right; a.stack = h->thc_stack; a.bh1 = h->thd_bh1;
-        a.left = h->thd_left + (size_t)h->th_counter * 2 * M * M;
-        a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
-        static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-        const size_t lds = thd_slice_lds(M);
-        AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_dense_kernel, lds, lds_set));
-        AFQ_LAUNCH(h, thermal_cslice_dense_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a);
-        AFQ_POST(h);
-        h->th_slice += 1;
-        h->th_block = h->th_slice / h->th_ss;
-        h->th_counter = (h->th_counter + 1) % h->th_ss;
-        AFQ_TRY(thc_launch_greens(h, h->thc_G, h->thc_det, 0, -1, 2 * h->nw));
-        AFQ_LAUNCH(h, thermal_cweight_mf_kernel, dim3((h->nw + 127) / 128), dim3(128), 0, h->stream, h->weight, h->thc_M0,
-                   h->thc_det, h->cmf, h->cfb, cmake(h->thd_mf_const[0], h->thd_mf_const[1]), h->nw);
-        AFQ_POST(h);
-        if (xi_out) return copy_out(h, xi_out, h->xi, sizeof(double) * nf);
-        return AFQ_OK;
-    }
-    // P = I - G^T, vbias = P . [iA | iB], xbar = -sqrt(dt) vbias clipped at 1, xs, cmf, cfb (planewave.py:219-276)
-    AFQ_TRY(ts_launch_rdm<cplx>(h, h->thc_G, nullptr));
-    AFQ_TRY(k_vbias_ueg(h));
-    AFQ_LAUNCH(h, thermal_cfields_kernel, dim3(h->nw), dim3(TH_THREADS), 0, h->stream, h->vbias, h->xi, h->thc_mf, h->xbar,
-               h->xs, h->cmf, h->cfb, h->K, h->sqrt_dt, h->thc_fb_bound, h->counters);
-    AFQ_POST(h);
-    AFQ_TRY(k_vhs_ueg(h));                              // VHS = sqrt(dt) (iA xs[:nq] + iB xs[nq:])
-    {
-        ThcSliceArgs a;
-        a.vhs = h->vhs; a.right = h->thc_right; a.stack = h->thc_stack; a.bh1 = h->thc_bh1;
-        a.left = h->thc_left + (size_t)h->th_counter * 2 * M;
-        a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
-        static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-        const size_t lds = thc_slice_lds(M);
-        AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_kernel, lds, lds_set));
-        AFQ_LAUNCH(h, thermal_cslice_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a);
-        AFQ_POST(h);
-    }
-    // PropagatorStack.update_full_rank's counters (stack.py:322-324)
-    h->th_slice += 1;
-    h->th_block = h->th_slice / h->th_ss;
-    h->th_counter = (h->th_counter + 1) % h->th_ss;
+    AFQ_TRY(ts_launch_rdm<cplx>(h, h->thc_G, nullptr));                // P = I - G^T
+    AFQ_TRY(h->th_kind == TH_CPLX_DENSE ? thc_slice_dense(h) : thc_slice_diag(h));
+    th_advance(h);
     // G = [I + S_{nbins - 1} .. S_0]^-1 on the walker's current bins, Mnew = det G, the weight
     AFQ_TRY(thc_launch_greens(h, h->thc_G, h->thc_det, 0, -1, 2 * h->nw));
-    AFQ_LAUNCH(h, thermal_cweight_kernel, dim3((h->nw + 127) / 128), dim3(128), 0, h->stream, h->weight, h->thc_M0, h->thc_det,
-               h->cmf, h->cfb, h->nw);
-    AFQ_POST(h);
+    AFQ_TRY(thc_weight(h));
     if (xi_out) return copy_out(h, xi_out, h->xi, sizeof(double) * nf);
     return AFQ_OK;
 }

@@ -442,12 +442,55 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_rdm_kernel(const T *G, cpl
 
 // what every thermal entry point asks first; want_cplx: the continuous fields' walkers are needed
 inline int th_need(afq_handle *h, bool want_cplx) {
-    if (!h->th_on || !h->nw || (want_cplx && !h->th_cplx))
+    if (!th_thermal(h) || !h->nw || (want_cplx && !th_complex(h)))
         AFQ_FAIL(h, AFQ_ESTATE, want_cplx ? "thermal walkers: afq_thermal_configure_continuous or afq_thermal_configure_hubbard_continuous first"
                                           : "thermal walkers: afq_thermal_configure or afq_thermal_configure_continuous first");
     if (h->prop_pending) AFQ_FAIL(h, AFQ_ESTATE, "a step is half done: afq_propagate_finish first");
     hipSetDevice(h->device);
     return AFQ_OK;
+}
+
+// ---- what the three configure entry points refuse alike, in the order they refuse it.  An entry point words a few of
+// the refusals its own way: those words are this description of it.
+struct ThEntry {
+    std::string me;             // "<entry point>: "
+    int allowed;                // the option bits it takes
+    int charge_code;            // AFQ_THERMAL_CHARGE: the error code and the text
+    std::string charge_text;
+    int system;                 // the AFQ_SYS_ kind it serves, and the refusal of another
+    std::string system_text;
+    const char *ge1;            // "all" / "both" of "(.. >= 1)"
+};
+
+// the option bits, then the system and the walkers; the entry point's own bound on M follows
+inline int th_screen_options(afq_handle *h, const ThEntry &e, int options) {
+    if (options & AFQ_THERMAL_CHARGE) AFQ_FAIL(h, e.charge_code, e.charge_text);
+    if (options & AFQ_THERMAL_FREE_PROJECTION) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: free_projection is not supported (constrained path only)");
+    if (options & AFQ_THERMAL_LOW_RANK) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: low_rank is not supported");
+    if (options & AFQ_THERMAL_AVERAGE_GF) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: average_gf is not supported");
+    if (options & AFQ_THERMAL_STREAMED_GREENS & ~e.allowed)
+        AFQ_FAIL(h, AFQ_EINVAL, e.me + "streamed_greens belongs to the continuous fields (the real walkers fit to M = 64 as they are)");
+    if (options & ~e.allowed) AFQ_FAIL(h, AFQ_EINVAL, e.me + "unknown option bits");
+    if (!h->kind || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, e.me + "set the system and allocate the walkers first");
+    if (h->kind != e.system) AFQ_FAIL(h, AFQ_EUNSUPPORTED, e.system_text);
+    return AFQ_OK;
+}
+
+// behind the bound on M: what else the handle is doing, and the shape of the path (nstblz: 1 where there is none)
+inline int th_screen_state(afq_handle *h, const ThEntry &e, int ntime_slices, int stack_size, int nstblz) {
+    if (k_comm_size(h) > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: one rank only");
+    if (h->nbp > 0 || h->it_nmax > 0) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no back-propagation or ITCF window");
+    if (h->rdm_on) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: no mixed one_rdm / two_rdm");
+    if (ntime_slices < 1 || stack_size < 1 || nstblz < 1 || ntime_slices % stack_size)
+        AFQ_FAIL(h, AFQ_EINVAL, e.me + "stack_size must divide ntime_slices (" + e.ge1 + " >= 1)");
+    return AFQ_OK;
+}
+
+// PropagatorStack.update's counters behind a slice (stack.py:295-297, 322-324)
+inline void th_advance(afq_handle *h) {
+    h->th_slice += 1;
+    h->th_block = h->th_slice / h->th_ss;
+    h->th_counter = (h->th_counter + 1) % h->th_ss;
 }
 
 // first bin of the chain for the Green's function at slice_ix (walkers/thermal.py:477-492)

@@ -48,8 +48,8 @@ inline WalkerFields walker_fields(const afq_handle *h, int want) {
     if (want & WF_GREENS) { f.ghalf = f.n; add(h->ghalf, per); add(h->ovlp_new, 1); }
     if (want & WF_GSUM) add(h->ghalf_sum, (size_t)h->na * h->M);
     if (want & WF_GDIAG) add(h->gdiag, (size_t)2 * h->gdiag_parts * h->M);
-    if (h->th_on && !h->th_cplx) { add(h->th_G, mm2); add(h->th_stack, mm2 * h->th_nbins); }   // thermal walkers: G and the bins
-    if (h->th_on && h->th_cplx) {                   // continuous fields: complex G and bins, the current bin's product, M0
+    if (h->th_kind == TH_REAL) { add(h->th_G, mm2); add(h->th_stack, mm2 * h->th_nbins); }   // thermal walkers: G and the bins
+    if (th_complex(h)) {                  // continuous fields: complex G and bins, the current bin's product, M0
         add(h->thc_G, mm2); add(h->thc_stack, mm2 * h->th_nbins); add(h->thc_right, mm2); add(h->thc_M0, 2);
     }
     return f;

@@ -19,9 +19,6 @@ import scipy.linalg
 
 from pauxy_amd.context import hidden
 
-MAX_BASIS = 47          # the complex Green's function keeps a walker's working set in LDS (k_thermal_cplx.hip)
-MAX_BASIS_STREAMED = 57  # walkers: {streamed_greens: True}: T in device memory; the slice kernel's LDS is the bound
-
 
 def planewave_constants(system, trial, dt):
     """(BH1 [2, M, M], mf_shift [nfields]) of planewave.py:83-108."""
@@ -41,10 +38,41 @@ def planewave_constants(system, trial, dt):
     return BH1, mf_shift
 
 
-class PlaneWave(object):
+class BatchedFields(object):
+    """What the propagators with continuous fields share (``PlaneWave`` here, ``Continuous`` for the Hubbard model): one
+    call of the library per time slice for the whole population, behind the reference's per-walker interface."""
     _pending = hidden()         # calls of the current slice still to swallow, per population
-    _dev = hidden()
+    _dev = hidden()             # the device of the population moved last: its counters are behind nfb_trig
 
+    def __init__(self):
+        self._pending = {}
+        self._dev = None
+        self.last_fields = None
+
+    def propagate_walkers(self, walk, eshift=0):
+        """One time slice of the whole population (planewave.py:445-517, continuous.py:202-257 for every walker)."""
+        walk.ensure_configured(self)
+        dev = self._dev = walk.dev
+        xi = numpy.empty((dev.nw, dev.K))
+        for iw in range(dev.nw):
+            xi[iw] = numpy.random.normal(0.0, 1.0, dev.K)                 # planewave.py:240, continuous.py:97
+        dev.thermal_propagate_continuous(xi)
+        self.last_fields = xi
+        walk.time_slice += 1
+
+    def propagate_walker(self, system, walker, trial, eshift=0):
+        walk = walker._h
+        left = self._pending.get(id(walk), 0)
+        if left > 0:
+            self._pending[id(walk)] = left - 1
+            return
+        self.propagate_walkers(walk, eshift)
+        self._pending[id(walk)] = walk.nw - 1             # (set behind the call: a slice that raised leaves nothing to swallow)
+
+    propagate_walker_phaseless = propagate_walker
+
+
+class PlaneWave(BatchedFields):
     def __init__(self, system, trial, qmc, options={}, verbose=False, lowrank=False):
         if system.name != "UEG":
             raise NotImplementedError("PlaneWave (thermal): UEG systems only (no Generic, no continuous Hubbard)")
@@ -75,9 +103,7 @@ class PlaneWave(object):
         self.BT_BP = self.BT
         self.ebound = (2.0 / self.dt) ** 0.5
         self.mean_local_energy = 0
-        self._pending = {}
-        self._dev = None
-        self.last_fields = None
+        BatchedFields.__init__(self)
 
     @property
     def nfb_trig(self):
@@ -85,25 +111,3 @@ class PlaneWave(object):
         reference's flag ("printed once per thread").  It reads the handle's count of rescaled force-bias components
         (afq_counters [0]), which lives as long as the handle and counts for every propagator of that handle."""
         return self._dev is not None and int(self._dev.counters()[0]) > 0
-
-    def propagate_walkers(self, walk, eshift=0):
-        """One time slice of the whole population (planewave.py:445-517 for every walker)."""
-        walk.ensure_configured(self)
-        dev = self._dev = walk.dev
-        xi = numpy.empty((dev.nw, dev.K))
-        for iw in range(dev.nw):
-            xi[iw] = numpy.random.normal(0.0, 1.0, dev.K)                 # planewave.py:240
-        dev.thermal_propagate_continuous(xi)
-        self.last_fields = xi
-        walk.time_slice += 1
-
-    def propagate_walker(self, system, walker, trial, eshift=0):
-        walk = walker._h
-        left = self._pending.get(id(walk), 0)
-        if left > 0:
-            self._pending[id(walk)] = left - 1
-            return
-        self.propagate_walkers(walk, eshift)
-        self._pending[id(walk)] = walk.nw - 1             # (set behind the call: a slice that raised leaves nothing to swallow)
-
-    propagate_walker_phaseless = propagate_walker

@@ -13,8 +13,22 @@ from pauxy_amd import _lib as L
 from pauxy_amd.context import get_context, hidden
 from pauxy_amd.propagation import thermal_continuous
 from pauxy_amd.propagation.thermal_hubbard import thermal_constants
-from pauxy_amd.propagation.thermal_planewave import MAX_BASIS, MAX_BASIS_STREAMED, planewave_constants
+from pauxy_amd.propagation.thermal_planewave import planewave_constants
 from pauxy_amd.trial_density import update_stack
+
+# The largest basis of the complex walkers by (kind, streamed_greens): what fits the 160 KiB of LDS of a work-group.
+MAX_BASIS = {
+    ('planewave', False): 47,            # ts_greens_lds<cplx> (thermal_strat.h): four complex matrices
+    ('planewave', True): 57,             # thc_slice_lds (k_thermal_cplx.hip): three complex matrices
+    ('hubbard_continuous', False): 47,   # ts_greens_lds<cplx>
+    ('hubbard_continuous', True): 63,    # thd_slice_lds (k_thermal_cplx.hip): two complex matrices and BH1
+}
+# how the refusal speaks of a kind: whose walkers, what M counts, what the slice kernel keeps in LDS
+_BOUND_WORDS = {'planewave': ("thermal walkers", "plane waves", "three complex matrices"),
+                'hubbard_continuous': ("thermal walkers with continuous fields", "sites", "two complex matrices and BH1")}
+# a configuration changed away from time slice 0: within a kind by what its key is, else the kind itself
+_CHANGED = {'discrete': "the stabilisation period", 'planewave': "the propagator's fb_bound",
+            None: "the kind of field"}
 
 
 class _QmcOf(object):
@@ -100,13 +114,14 @@ class ThermalWalkers(object):
         if system.name not in ("Hubbard", "UEG"):
             raise NotImplementedError("thermal walkers: Hubbard systems only (no Generic / UEG) with discrete fields, and "
                                       "the UEG with continuous fields; %s has no thermal path" % system.name)
-        # The walker kind: real (Hubbard, discrete fields), complex with a diagonal trial (UEG), complex with a dense
-        # trial (Hubbard, continuous fields).  The UEG's is known here.  A Hubbard population's is decided by the
-        # propagator that configures it (ensure_configured(prop)); `continuous_fields: True` among the walkers' options
-        # announces the dense kind, which is what lets `streamed_greens` through before a propagator exists.
-        self.continuous = system.name == "UEG"
-        self.dense = False
-        self.expect_dense = system.name == "Hubbard" and bool(walker_opts.get('continuous_fields', False))
+        # The walker kind: 'discrete' (Hubbard, real matrices), 'planewave' (UEG: complex, diagonal trial),
+        # 'hubbard_continuous' (complex, dense trial).  The UEG's is known here.  A Hubbard population's is decided by
+        # the propagator that configures it (ensure_configured(prop)); `continuous_fields: True` among the walkers'
+        # options announces the dense kind, which is what lets `streamed_greens` through before a propagator exists.
+        if system.name == "UEG":
+            self.kind = 'planewave'
+        else:
+            self.kind = 'hubbard_continuous' if walker_opts.get('continuous_fields', False) else 'discrete'
         if not hasattr(trial, 'dmat_inv'):
             raise NotImplementedError("thermal walkers: a OneBody trial density matrix is needed (no MeanField)")
         if walker_opts.get('low_rank', False):
@@ -117,21 +132,13 @@ class ThermalWalkers(object):
                                       "included): comb only" % self.pcont_method)
         # the Green's function with T in device memory (k_thermal_cplx.hip, AFQ_THERMAL_STREAMED_GREENS)
         self.streamed_greens = bool(walker_opts.get('streamed_greens', False))
-        if self.streamed_greens and not self.continuous and not self.expect_dense:
+        if self.streamed_greens and self.kind == 'discrete':
             raise NotImplementedError("thermal walkers: streamed_greens belongs to the continuous fields (Hubbard "
                                       "walkers with discrete fields fit to M = 64 as they are; with "
                                       "hubbard_stratonovich: 'continuous' the driver announces the complex walkers, and "
                                       "walkers: {continuous_fields: True} does so by hand)")
-        if self.expect_dense:
-            self._check_dense_bound(system.nbasis)
-        if self.continuous and self.streamed_greens and system.nbasis > MAX_BASIS_STREAMED:
-            raise NotImplementedError("thermal walkers: M = %d > %d plane waves is not supported with streamed_greens "
-                                      "(the slice kernel keeps three complex matrices in LDS)"
-                                      % (system.nbasis, MAX_BASIS_STREAMED))
-        if self.continuous and not self.streamed_greens and system.nbasis > MAX_BASIS:
-            raise NotImplementedError("thermal walkers: M = %d > %d plane waves is not supported (the complex Green's "
-                                      "function keeps a walker's working set in LDS; walkers: {streamed_greens: True} "
-                                      "reaches M = %d)" % (system.nbasis, MAX_BASIS, MAX_BASIS_STREAMED))
+        if self.kind != 'discrete':
+            self._check_bound(self.kind, system.nbasis)
         if system.nbasis > 64:
             raise NotImplementedError("thermal walkers: M = %d > 64 sites is not supported" % system.nbasis)
         self.nwalkers = qmc.nwalkers
@@ -165,80 +172,89 @@ class ThermalWalkers(object):
         self.total_weight = float(qmc.ntot_walkers)
         self.time_slice = 0
         self.path_index = 0
-        self.configured_nstblz = None
-        self.configured_fb_bound = None         # (continuous fields: what the library's configuration is keyed on)
+        self.configured = None      # (kind, key) the library is configured with; the key is what its configuration depends on
         self._prop = None
         self.last_parent_ix = None
         self.walkers = [ThermalWalkerView(self, i) for i in range(self.nw)]
 
+    @property
+    def continuous(self):
+        """The UEG's walkers: complex with a diagonal trial."""
+        return self.kind == 'planewave'
+
+    @property
+    def dense(self):
+        """The library holds complex walkers with a dense trial (Hubbard with continuous fields)."""
+        return self.configured is not None and self.configured[0] == 'hubbard_continuous'
+
     def ensure_configured(self, prop=None):
-        """The library is configured on first use: the propagator's stabilisation period decides when it is known."""
-        if self.continuous:
-            return self._ensure_configured_continuous(prop)
-        if self.dense or getattr(prop, 'hs_type', None) == 'continuous' or (prop is None and self.expect_dense and
-                                                                            self.configured_nstblz is None):
-            return self._ensure_configured_dense(prop)
+        """The library is configured on first use, by the kind's entry point with the propagator's constants; without a
+        propagator yet (a walker's G read first) with the ones the kind's propagator would compute.  A propagator whose
+        key differs from what was configured configures the library again: allowed only at time slice 0, and it starts
+        the population afresh (bins, G, weights, and for the complex walkers right and M0 = the trial's; anything set on
+        the walkers before is lost).  Complex walkers never go back to a discrete propagator."""
+        if self.configured is not None and prop is None:
+            return
+        kind = self.kind
+        if self.system.name == "Hubbard":
+            hs_type = getattr(prop, 'hs_type', None)
+            if self.dense and hs_type != 'continuous':
+                raise RuntimeError("thermal walkers: the population carries complex walkers (continuous fields); a '%s' "
+                                   "propagator cannot move it" % hs_type)
+            if prop is not None:
+                kind = 'hubbard_continuous' if hs_type == 'continuous' else 'discrete'
+        key, configure = getattr(self, '_configure_' + kind)(prop)
+        if self.configured == (kind, key):
+            return
+        if self.configured is not None and self.time_slice != 0:
+            raise RuntimeError("thermal walkers: %s changed in the middle of a path"
+                               % _CHANGED[kind if self.configured[0] == kind else None])
+        configure(L.THERMAL_STREAMED_GREENS if self.streamed_greens else 0)
+        self.kind, self.configured = kind, (kind, key)
+
+    def _configure_discrete(self, prop):
+        """Key: the propagator's stabilisation period, which decides when the Green's function is refreshed."""
         if self.streamed_greens:
             raise NotImplementedError("thermal walkers: streamed_greens belongs to the continuous fields (Hubbard "
                                       "walkers with discrete fields fit to M = 64 as they are)")
         nstblz = self.nstblz if prop is None else prop.nstblz
-        if self.configured_nstblz == nstblz:
-            return
-        if self.configured_nstblz is not None and self.time_slice != 0:
-            raise RuntimeError("thermal walkers: the stabilisation period changed in the middle of a path")
-        _, auxf, _, _, BH1 = thermal_constants(self.system, self.trial, self.dt)
-        self.dev.thermal_configure(self.num_slices, self.stack_size, nstblz, self.trial.dmat, self.trial.dmat_inv,
-                                   BH1, auxf)
-        self.configured_nstblz = nstblz
-        self.nstblz = nstblz
 
-    def _ensure_configured_continuous(self, prop):
-        """UEG: the propagator's constants (BH1, mf_shift, fb_bound) go to the library with the trial's; without a
-        propagator yet (a walker's G read first) they are the defaults the propagator would compute.  A propagator
-        whose fb_bound differs from what was configured configures the library again: allowed only at time slice 0, and
-        it starts the population afresh (bins, G, right, weights, and M0 = the trial's; anything set on the walkers
-        before is lost)."""
+        def configure(options):
+            _, auxf, _, _, BH1 = thermal_constants(self.system, self.trial, self.dt)
+            self.dev.thermal_configure(self.num_slices, self.stack_size, nstblz, self.trial.dmat, self.trial.dmat_inv,
+                                       BH1, auxf)
+            self.nstblz = nstblz
+        return nstblz, configure
+
+    def _configure_planewave(self, prop):
+        """Key: fb_bound.  BH1 and mf_shift are the propagator's, or what it would compute."""
         fb_bound = 1.0 if prop is None else prop.fb_bound
-        if self.configured_fb_bound is not None and (prop is None or self.configured_fb_bound == fb_bound):
-            return
-        if self.configured_fb_bound is not None and self.time_slice != 0:
-            raise RuntimeError("thermal walkers: the propagator's fb_bound changed in the middle of a path")
-        BH1, mf_shift = (prop.BH1, prop.mf_shift) if prop is not None else planewave_constants(self.system, self.trial,
-                                                                                                self.dt)
-        self.dev.thermal_configure_continuous(self.num_slices, self.stack_size, self.dt, self.trial.dmat,
-                                              self.trial.dmat_inv, BH1, mf_shift, fb_bound,
-                                              L.THERMAL_STREAMED_GREENS if self.streamed_greens else 0)
-        self.configured_fb_bound = fb_bound
 
-    def _check_dense_bound(self, M):
-        bound = thermal_continuous.MAX_BASIS_STREAMED if self.streamed_greens else thermal_continuous.MAX_BASIS
+        def configure(options):
+            BH1, mf_shift = (prop.BH1, prop.mf_shift) if prop is not None else planewave_constants(
+                self.system, self.trial, self.dt)
+            self.dev.thermal_configure_continuous(self.num_slices, self.stack_size, self.dt, self.trial.dmat,
+                                                  self.trial.dmat_inv, BH1, mf_shift, fb_bound, options)
+        return fb_bound, configure
+
+    def _configure_hubbard_continuous(self, prop):
+        """No key: BH1, mf_shift and mf_const_fac are what ``Continuous`` computes from the system and the trial, which
+        is all they depend on."""
+        def configure(options):
+            p = prop or thermal_continuous.Continuous({}, _QmcOf(self.dt, self.nstblz), self.system, self.trial)
+            self._check_bound('hubbard_continuous', self.system.nbasis)
+            self.dev.thermal_configure_hubbard_continuous(self.num_slices, self.stack_size, self.dt, self.trial.dmat,
+                                                          self.trial.dmat_inv, p.BH1, p.mf_shift, p.mf_const_fac, options)
+        return (), configure
+
+    def _check_bound(self, kind, M):
+        who, unit, slice_keeps = _BOUND_WORDS[kind]
+        bound = MAX_BASIS[kind, self.streamed_greens]
         if M > bound:
-            raise NotImplementedError(
-                "thermal walkers with continuous fields: M = %d > %d sites is not supported%s" % (
-                    M, bound, " with streamed_greens (the slice kernel keeps two complex matrices and BH1 in LDS)"
-                    if self.streamed_greens else " (the complex Green's function keeps a walker's working set in LDS; "
-                    "walkers: {streamed_greens: True} reaches M = %d)" % thermal_continuous.MAX_BASIS_STREAMED))
-
-    def _ensure_configured_dense(self, prop):
-        """Hubbard with continuous fields: the propagator's constants (BH1, mf_shift, mf_const_fac) go to the library
-        with the trial's dense matrices; without a propagator yet they are what ``Continuous`` computes from the system
-        and the trial, which is all they depend on.  A population that ran discrete fields becomes complex only at time
-        slice 0, and starts afresh; the way back is refused."""
-        if prop is not None and getattr(prop, 'hs_type', None) != 'continuous':
-            raise RuntimeError("thermal walkers: the population carries complex walkers (continuous fields); a '%s' "
-                               "propagator cannot move it" % getattr(prop, 'hs_type', None))
-        if self.dense:
-            return
-        if self.configured_nstblz is not None and self.time_slice != 0:
-            raise RuntimeError("thermal walkers: the kind of field changed in the middle of a path")
-        if prop is None:
-            prop = thermal_continuous.Continuous({}, _QmcOf(self.dt, self.nstblz), self.system, self.trial)
-        self._check_dense_bound(self.system.nbasis)
-        self.dev.thermal_configure_hubbard_continuous(self.num_slices, self.stack_size, self.dt, self.trial.dmat,
-                                                      self.trial.dmat_inv, prop.BH1, prop.mf_shift, prop.mf_const_fac,
-                                                      L.THERMAL_STREAMED_GREENS if self.streamed_greens else 0)
-        self.dense = True
-        self.configured_nstblz = None
+            raise NotImplementedError("%s: M = %d > %d %s is not supported%s" % (
+                who, M, bound, unit, " with streamed_greens (the slice kernel keeps %s in LDS)" % slice_keeps
+                if self.streamed_greens else " (the complex Green's function keeps a walker's working set in LDS; "
+                "walkers: {streamed_greens: True} reaches M = %d)" % MAX_BASIS[kind, True]))
 
     def set_total_weight(self, total_weight):
         self.total_weight = total_weight

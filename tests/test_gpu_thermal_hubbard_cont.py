@@ -515,27 +515,51 @@ def digest(arrays):
     return h.hexdigest()
 
 
-def ueg_path_digest():
-    """Case a2 of thermal_ueg.npz (M = 19, two bins) beside a second walker: every slice's state, the energies, a reset
-    and one more slice."""
+def continuous_path(dev, xis, K):
+    """(digest, clip count) of a two-walker path on a fresh complex handle: the fixture's fields for walker 0, a stream
+    of RandomState(42) for walker 1; every slice's state with xbar, cmf and cfb, the energies after the last slice, a
+    reset and one more slice."""
+    rng = numpy.random.RandomState(42)
+    nslice = len(xis)
+    out = []
+    for ts in range(nslice + 1):
+        if ts == nslice:
+            dev.thermal_reset()
+        xi = numpy.array([xis[ts % nslice], rng.normal(size=K)])
+        dev.thermal_propagate_continuous(xi)
+        out += [dev.get(f) for f in STATE + (L.F_XBAR, L.F_CMF, L.F_CFB)]
+        if ts == nslice - 1:
+            out += list(dev.thermal_energy())
+    return digest(out), int(dev.counters()[0])
+
+
+def ueg_case(pre):
     from tests.thermal_ueg_cases import Case as UCase
     d = numpy.load(os.path.join(C.HERE, "golden", "thermal_ueg.npz"))
-    pre = 'a2_'
     c = UCase(float(d[pre + 'ecut']), int(d[pre + 'nelec']), rs=float(d[pre + 'rs']), beta=float(d[pre + 'beta']),
               dt=float(d[pre + 'dt']), mu=float(d[pre + 'mu_system']), fb_bound=float(d[pre + 'fb_bound']))
-    rng = numpy.random.RandomState(42)
-    dev = c.device(2, int(d[pre + 'stack_size']))
+    return c, int(d[pre + 'stack_size']), d[pre + 'xi'][:c.L]
+
+
+def ueg_path_digest(pre='a2_', options=0, with_count=False):
+    """Case a2 of thermal_ueg.npz (M = 19, two bins) beside a second walker: every slice's state, the energies, a reset
+    and one more slice.  Case a4 (fb_bound 0.01) is the same basis with the clip firing."""
+    c, ss, xis = ueg_case(pre)
+    dev = c.device(2, ss, options)
     try:
-        out = []
-        for ts in range(c.L + 1):
-            if ts == c.L:
-                dev.thermal_reset()
-            xi = numpy.array([d[pre + 'xi'][ts % c.L], rng.normal(size=c.K)])
-            dev.thermal_propagate_continuous(xi)
-            out += [dev.get(f) for f in STATE + (L.F_XBAR, L.F_CMF, L.F_CFB)]
-            if ts == c.L - 1:
-                out += list(dev.thermal_energy())
-        return digest(out)
+        got = continuous_path(dev, xis, c.K)
+        return got if with_count else got[0]
+    finally:
+        dev.close()
+
+
+def hubbard_continuous_digest(pre, options):
+    """A case of thermal_hubbard_cont.npz beside a second walker -> (digest, clip count).  a7: 3 x 3, odd pitch, the
+    clip fires and the fixture's walker is killed; a0: 2 x 2."""
+    d = C.golden()
+    dev = C.device(pre, 2, options=options)
+    try:
+        return continuous_path(dev, d[pre + 'xi'], int(d[pre + 'nx']) * int(d[pre + 'ny']))
     finally:
         dev.close()
 
@@ -575,6 +599,224 @@ def test_ueg_and_discrete_hubbard_paths_keep_their_bits():
         dev.thermal_propagate_continuous(numpy.random.RandomState(1).normal(size=(2, 4)))
         assert hubbard_discrete_digest() == HUBBARD_DIGEST_BEFORE
         assert ueg_path_digest() == UEG_DIGEST_BEFORE
+    finally:
+        dev.close()
+
+
+# ---- all three walker kinds held to what commit 11c5486 ("Finite-temperature AFQMC for the Hubbard model with
+# continuous fields") computed, launched and refused: every literal below was recorded by running these functions on an
+# MI355X with that commit's library.
+STREAMED = L.THERMAL_STREAMED_GREENS
+PATHS_11C5486 = {       # (kind, case, options) -> (digest, counters()[0] behind the path)
+    ('hubbard', 'a7_', 0): ("092e4dd87a21a60a5e72f34f0c216463c70d118df6c3f39312b5f8b29cc766cd", 94),
+    ('hubbard', 'a7_', STREAMED): ("092e4dd87a21a60a5e72f34f0c216463c70d118df6c3f39312b5f8b29cc766cd", 94),
+    ('hubbard', 'a0_', 0): ("7ffb19a21451c49bea1e787db63a5ee43590a5583d6f8f48cdc184cbc954f7ea", 0),
+    ('hubbard', 'a0_', STREAMED): ("7ffb19a21451c49bea1e787db63a5ee43590a5583d6f8f48cdc184cbc954f7ea", 0),
+    ('ueg', 'a2_', 0): ("7d7d307737cafe2f20f82a1462e6e111dfcb1321c371cd06100a1bff3c4d09de", 0),
+    ('ueg', 'a2_', STREAMED): ("7d7d307737cafe2f20f82a1462e6e111dfcb1321c371cd06100a1bff3c4d09de", 0),
+    ('ueg', 'a4_', 0): ("abb0948439b0c8548a90df5d142961ee797e26af324af2834511699c5378c342", 18),
+    ('ueg', 'a4_', STREAMED): ("abb0948439b0c8548a90df5d142961ee797e26af324af2834511699c5378c342", 18),
+}
+
+
+@pytest.mark.parametrize("key", sorted(PATHS_11C5486), ids=lambda k: "%s-%s%d" % k)
+def test_continuous_paths_keep_their_bits_and_clip_counts(key):
+    kind, pre, options = key
+    got = hubbard_continuous_digest(pre, options) if kind == 'hubbard' else ueg_path_digest(pre, options, with_count=True)
+    assert got == PATHS_11C5486[key]
+
+
+def slice_launches(kind, options=0):
+    """[(name, launches)] of the second slice of a path of the kind, in the order of the launch trace."""
+    if kind == 'discrete':
+        chain = C.Chain(4)
+        s = chain.system
+        from pauxy_amd.device import AfqDevice
+        dev = AfqDevice(0)
+        dev.set_system_hubbard(numpy.asarray(s.H1).astype(complex), s.U, s.nup, s.ndown)
+        dev.walkers_alloc(2)
+        dev.thermal_configure(chain.L, 2, 1, chain.BT, chain.BT_inv, chain.BH1, numpy.ones((2, 2)))
+        move = lambda: dev.thermal_propagate(numpy.full((2, 4), 0.5))
+    elif kind == 'planewave':
+        c, ss, xis = ueg_case('a2_')
+        dev = c.device(2, ss, options)
+        move = lambda: dev.thermal_propagate_continuous(numpy.array([xis[0], xis[1]]))
+    else:
+        dev = C.device('a0_', 2, options=options)
+        move = lambda: dev.thermal_propagate_continuous(numpy.random.RandomState(1).normal(size=(2, 4)))
+    try:
+        move()
+        dev.launch_trace(True)
+        move()
+        dev.launch_trace(False)
+        return [(name, n) for name, (n, _) in dev.launch_trace_get().items()]
+    finally:
+        dev.close()
+
+
+LAUNCHES_11C5486 = {       # (kind, options) -> the names in the order of the trace, each launched once
+    ('discrete', 0): ["thermal_slice_kernel", "thermal_greens_kernel", "thermal_wrap_kernel"],
+    ('planewave', 0): ["thermal_crdm_kernel", "vbias_ueg_lds_kernel", "thermal_cfields_kernel", "vhs_ueg_kernel",
+                       "thermal_cslice_kernel", "thermal_cgreens_kernel", "thermal_cweight_kernel"],
+    ('planewave', STREAMED): ["thermal_crdm_kernel", "vbias_ueg_lds_kernel", "thermal_cfields_kernel", "vhs_ueg_kernel",
+                              "thermal_cslice_kernel", "thermal_cgreens_streamed_kernel", "thermal_cweight_kernel"],
+    ('hubbard_continuous', 0): ["thermal_crdm_kernel", "thermal_cfields_dense_kernel", "thermal_cslice_dense_kernel",
+                                "thermal_cgreens_kernel", "thermal_cweight_mf_kernel"],
+    ('hubbard_continuous', STREAMED): ["thermal_crdm_kernel", "thermal_cfields_dense_kernel", "thermal_cslice_dense_kernel",
+                                       "thermal_cgreens_streamed_kernel", "thermal_cweight_mf_kernel"],
+}
+
+
+@pytest.mark.parametrize("key", sorted(LAUNCHES_11C5486), ids=lambda k: "%s%d" % k)
+def test_a_slice_launches_the_kernels_it_launched(key):
+    assert slice_launches(*key) == [(name, 1) for name in LAUNCHES_11C5486[key]]
+
+
+def configure_raw(dev, entry, M, K, L_=4, ss=2, dt=0.05, options=0, fb_bound=1.0, nstblz=1, null=False, BT=None):
+    """(code, last_error) of a configure entry point called with unit matrices (every refusal but the diagonal-trial
+    one fires before an operand is read); null: no BT."""
+    import ctypes
+    eye = numpy.ascontiguousarray([numpy.eye(M)] * 2)
+    bt = eye if BT is None else numpy.ascontiguousarray(BT, dtype=numpy.float64)
+    mf, two = numpy.zeros(max(K, 1), dtype=complex), numpy.ones(4)        # (auxf [2, 2]; mf_const_fac (re, im))
+    p = lambda a: ctypes.c_void_p(a.ctypes.data)
+    b = None if null else p(bt)
+    lib, h = dev.lib, dev.h
+    if entry == 'discrete':
+        rc = lib.afq_thermal_configure(h, L_, ss, nstblz, b, p(eye), p(eye), p(two), options)
+    elif entry == 'planewave':
+        rc = lib.afq_thermal_configure_continuous(h, L_, ss, dt, b, p(eye), p(eye), p(mf), fb_bound, options)
+    else:
+        rc = lib.afq_thermal_configure_hubbard_continuous(h, L_, ss, dt, b, p(eye), p(eye), p(mf), p(two), options)
+    return rc, lib.afq_last_error(h).decode()
+
+
+def bare_handle(system, nw=1):
+    """system: 'hubbard<M>' (a chain), 'ueg<M>', or None for a handle without a system; nw 0: no walkers."""
+    from pauxy_amd.device import AfqDevice
+    from tests.thermal_ueg_cases import Case as UCase, ECUT_OF_M
+    dev = AfqDevice(0)
+    M = K = 4
+    try:
+        if system and system.startswith('hubbard'):
+            s = C.Chain(int(system[7:])).system
+            dev.set_system_hubbard(numpy.asarray(s.H1).astype(complex), s.U, s.nup, s.ndown)
+            M, K = dev.M, dev.K
+        elif system:
+            s = UCase(3.0 if system == 'ueg81' else ECUT_OF_M[int(system[3:])], 1).system
+            dev.set_system_ueg(s.iA, s.iB, s.ikpq_i, s.ikpq_kpq, s.ipmq_i, s.ipmq_pmq, s.vqvec, s.vol,
+                               numpy.array([s.H1[0].diagonal(), s.H1[1].diagonal()]), s.ecore, s.nup, s.ndown)
+            M, K = dev.M, dev.K
+            assert M == int(system[3:])
+        if nw and system:                   # (walkers need a system)
+            dev.walkers_alloc(nw)
+    except Exception:
+        dev.close()
+        raise
+    return dev, M, K
+
+
+HOME = {'discrete': 'hubbard4', 'planewave': 'ueg7', 'hubbard_continuous': 'hubbard4'}
+AWAY = {'discrete': 'ueg7', 'planewave': 'hubbard4', 'hubbard_continuous': 'ueg7'}
+# (entry point, what is wrong) -> (handle, walkers, arguments of configure_raw, code, last_error)
+REFUSALS_11C5486 = {}
+
+
+def _refusal(entry, what, code, text, system=0, nw=1, **kw):
+    REFUSALS_11C5486[(entry, what)] = (HOME[entry] if system == 0 else system, nw, kw, code, text)
+
+
+for _e, _me in (('discrete', "afq_thermal_configure"), ('planewave', "afq_thermal_configure_continuous"),
+                ('hubbard_continuous', "afq_thermal_configure_hubbard_continuous")):
+    _refusal(_e, 'null operand', L.AFQ_EINVAL, _me + ": null operand", null=True)
+    _refusal(_e, 'free_projection', L.AFQ_EUNSUPPORTED,
+             "thermal walkers: free_projection is not supported (constrained path only)", options=L.THERMAL_FREE_PROJECTION)
+    _refusal(_e, 'low_rank', L.AFQ_EUNSUPPORTED, "thermal walkers: low_rank is not supported", options=L.THERMAL_LOW_RANK)
+    _refusal(_e, 'average_gf', L.AFQ_EUNSUPPORTED, "thermal walkers: average_gf is not supported",
+             options=L.THERMAL_AVERAGE_GF)
+    _refusal(_e, 'unknown bits', L.AFQ_EINVAL, _me + ": unknown option bits", options=64)
+    _refusal(_e, 'unknown bits beside streamed', L.AFQ_EINVAL,
+             _me + (": streamed_greens belongs to the continuous fields (the real walkers fit to M = 64 as they are)"
+                    if _e == 'discrete' else ": unknown option bits"), options=64 | STREAMED)
+    _refusal(_e, 'every bit', L.AFQ_EUNSUPPORTED if _e == 'discrete' else L.AFQ_EINVAL,
+             {'discrete': "thermal walkers: charge_decomposition is not supported (spin decomposition only)",
+              'planewave': _me + ": charge_decomposition belongs to the discrete fields",
+              'hubbard_continuous': _me + ": charge_decomposition belongs to the discrete fields (the continuous form is "
+                                          "the charge form alone)"}[_e], options=127)
+    _refusal(_e, 'no system', L.AFQ_ESTATE, _me + ": set the system and allocate the walkers first", system=None)
+    _refusal(_e, 'no walkers', L.AFQ_ESTATE, _me + ": set the system and allocate the walkers first", nw=0)
+    _refusal(_e, 'stack_size 3 of 4 slices', L.AFQ_EINVAL,
+             _me + ": stack_size must divide ntime_slices (%s >= 1)" % ("all" if _e == 'discrete' else "both"), ss=3)
+    _refusal(_e, 'stack_size 0', L.AFQ_EINVAL,
+             _me + ": stack_size must divide ntime_slices (%s >= 1)" % ("all" if _e == 'discrete' else "both"), ss=0)
+    _refusal(_e, 'no slices', L.AFQ_EINVAL,
+             _me + ": stack_size must divide ntime_slices (%s >= 1)" % ("all" if _e == 'discrete' else "both"), L_=0)
+_refusal('discrete', 'charge_decomposition', L.AFQ_EUNSUPPORTED,
+         "thermal walkers: charge_decomposition is not supported (spin decomposition only)", options=L.THERMAL_CHARGE)
+_refusal('planewave', 'charge_decomposition', L.AFQ_EINVAL,
+         "afq_thermal_configure_continuous: charge_decomposition belongs to the discrete fields", options=L.THERMAL_CHARGE)
+_refusal('hubbard_continuous', 'charge_decomposition', L.AFQ_EINVAL,
+         "afq_thermal_configure_hubbard_continuous: charge_decomposition belongs to the discrete fields (the continuous "
+         "form is the charge form alone)", options=L.THERMAL_CHARGE)
+_refusal('discrete', 'streamed_greens', L.AFQ_EINVAL, "afq_thermal_configure: streamed_greens belongs to the continuous "
+         "fields (the real walkers fit to M = 64 as they are)", options=STREAMED)
+_refusal('discrete', 'nstblz 0', L.AFQ_EINVAL, "afq_thermal_configure: stack_size must divide ntime_slices (all >= 1)",
+         nstblz=0)
+_refusal('discrete', 'wrong system', L.AFQ_EUNSUPPORTED, "thermal walkers: Hubbard systems only (no Generic / UEG)",
+         system=AWAY['discrete'])
+_refusal('planewave', 'wrong system', L.AFQ_EUNSUPPORTED, "thermal walkers with continuous fields: UEG systems only (no "
+         "Generic, no continuous Hubbard)", system=AWAY['planewave'])
+_refusal('hubbard_continuous', 'wrong system', L.AFQ_EUNSUPPORTED, "thermal walkers with continuous fields and a dense "
+         "trial: Hubbard systems only (no Generic)", system=AWAY['hubbard_continuous'])
+# (a wrong system is refused before its size: the UEG's 7 plane waves on the Hubbard entry points, and streamed too)
+_refusal('hubbard_continuous', 'wrong system, streamed', L.AFQ_EUNSUPPORTED, "thermal walkers with continuous fields and "
+         "a dense trial: Hubbard systems only (no Generic)", system=AWAY['hubbard_continuous'], options=STREAMED)
+_refusal('planewave', 'dt 0', L.AFQ_EINVAL, "afq_thermal_configure_continuous: dt must be positive, fb_bound not negative",
+         dt=0.0)
+_refusal('planewave', 'dt negative', L.AFQ_EINVAL,
+         "afq_thermal_configure_continuous: dt must be positive, fb_bound not negative", dt=-0.05)
+_refusal('planewave', 'fb_bound negative', L.AFQ_EINVAL,
+         "afq_thermal_configure_continuous: dt must be positive, fb_bound not negative", fb_bound=-1.0)
+_refusal('planewave', 'dt before the trial', L.AFQ_EINVAL,
+         "afq_thermal_configure_continuous: dt must be positive, fb_bound not negative", dt=0.0, BT=numpy.ones((2, 7, 7)))
+_refusal('planewave', 'stack_size before dt', L.AFQ_EINVAL,
+         "afq_thermal_configure_continuous: stack_size must divide ntime_slices (both >= 1)", ss=3, dt=0.0)
+_refusal('planewave', 'dense trial', L.AFQ_EUNSUPPORTED, "thermal walkers with continuous fields: a diagonal trial density "
+         "matrix only (OneBody on plane waves)", BT=numpy.ones((2, 7, 7)))
+_refusal('hubbard_continuous', 'dt 0', L.AFQ_EINVAL, "afq_thermal_configure_hubbard_continuous: dt must be positive", dt=0.0)
+_refusal('hubbard_continuous', 'dt negative', L.AFQ_EINVAL, "afq_thermal_configure_hubbard_continuous: dt must be positive",
+         dt=-0.05)
+_refusal('hubbard_continuous', 'stack_size before dt', L.AFQ_EINVAL,
+         "afq_thermal_configure_hubbard_continuous: stack_size must divide ntime_slices (both >= 1)", ss=3, dt=0.0)
+# the four bounds with their numbers; the bound is refused before stack_size and dt are looked at
+_refusal('hubbard_continuous', 'M = 48 resident', L.AFQ_EUNSUPPORTED,
+         "thermal walkers with continuous fields, Hubbard: M = 48 sites need 164096 bytes of LDS for the "
+         "complex Green's function (thermal_cgreens_kernel), a work-group has 163840 (M <= 47); "
+         "AFQ_THERMAL_STREAMED_GREENS (streamed_greens) keeps T in device memory and reaches further",
+         system='hubbard48', ss=3, dt=0.0)
+_refusal('hubbard_continuous', 'M = 64 streamed', L.AFQ_EUNSUPPORTED,
+         "thermal walkers with continuous fields, Hubbard (streamed_greens): M = 64 sites need 167424 "
+         "bytes of LDS for the slice kernel (thermal_cslice_dense_kernel), a work-group has 163840 (M <= "
+         "63)", system='hubbard64', options=STREAMED, ss=3)
+_refusal('planewave', 'M = 57 resident', L.AFQ_EUNSUPPORTED,
+         "thermal walkers with continuous fields: M = 57 plane waves need 221504 bytes of LDS for the "
+         "complex Green's function, a work-group has 163840 (M <= 47); AFQ_THERMAL_STREAMED_GREENS "
+         "(streamed_greens) keeps T in device memory and reaches further",
+         system='ueg57', ss=3, dt=0.0)
+_refusal('planewave', 'M = 81 streamed', L.AFQ_EUNSUPPORTED,
+         "thermal walkers with continuous fields (streamed_greens): M = 81 plane waves need 314928 bytes "
+         "of LDS for the slice kernel (thermal_cslice_kernel), a work-group has 163840 (M <= 57)",
+         system='ueg81', options=STREAMED, ss=3)
+
+
+@pytest.mark.parametrize("key", sorted(REFUSALS_11C5486), ids=lambda k: ("%s-%s" % k).replace(" ", "_"))
+def test_every_refusal_keeps_its_code_and_its_words(key):
+    system, nw, kw, code, text = REFUSALS_11C5486[key]
+    dev, M, K = bare_handle(system, nw)
+    try:
+        assert configure_raw(dev, key[0], M, K, **kw) == (code, text)
+        # and the handle holds no thermal walkers afterwards
+        assert dev.lib.afq_thermal_reset(dev.h) == L.AFQ_ESTATE
     finally:
         dev.close()
 
