@@ -674,6 +674,28 @@ int afq_thermal_greens(afq_handle *h, int slice_ix);
 int afq_thermal_energy(afq_handle *h, double *E_out, double *nav_out);
 int afq_thermal_state(afq_handle *h, int32_t *out4);
 
+/* ---- the mixed estimator's sums of a thermal population (estimators/mixed.py:180-233 of the reference), every kind of
+ * thermal handle.  Without AVERAGE_GF: G rebuilt at the handle's current slice and its energies, bit for bit what
+ * afq_thermal_greens(h, slice) + afq_thermal_energy give; cols_out f64[nw, 4] = (E, T, V, nav) per walker, per_bin_out
+ * (or NULL) gets the same as its one row.  With AVERAGE_GF: for ts = 0 .. nbins - 1 the Green's function at
+ * slice_ix = ts stack_size and its (E, T, V, nav) -- per_bin_out f64[nbins, nw, 4] in that order, each bit for bit the
+ * loop's -- and cols_out their SUMS, added in ts order from zero (the caller multiplies by the weight and divides by
+ * nbins, mixed.py:195-199).  The whole sweep is one launch per stage (Green's functions on a grid (2 nw, bins), P, energy,
+ * sums) whatever nbins is, taken in chunks of whole bins when its scratch (G, P, and T of the streamed engine: per bin
+ * 2 M M nw (sizeof G + 16) bytes, + 64 M M nw streamed) exceeds the budget: 2 GiB unless
+ * afq_thermal_set_sweep_budget says otherwise (0: the default; a chunk holds at least one bin; chunking changes no bit).
+ * Afterwards the walkers' G (and det, complex kinds) are what afq_thermal_greens(h, (nbins - 1) stack_size) leaves.
+ * ONE_RDM: one_rdm_out f64[2, M, M] = sum_w weight_w Re G_w of the G the call leaves, every walker in walker order.
+ * TWO_RDM (UEG): two_rdm_out f64[2, 2, nq] = sum_w weight_w Re two_rdm[P_w] of the same G, from the pair sums of the
+ * energy launch.  AFQ_ESTATE: no thermal configuration; AFQ_EINVAL: unknown bits in what, a needed output NULL;
+ * AFQ_EUNSUPPORTED: TWO_RDM on a Hubbard handle. */
+#define AFQ_THERMAL_EST_AVERAGE_GF 1
+#define AFQ_THERMAL_EST_ONE_RDM    2
+#define AFQ_THERMAL_EST_TWO_RDM    4   /* UEG walkers only: AFQ_EUNSUPPORTED otherwise */
+int afq_thermal_estimates(afq_handle *h, int what, double *cols_out, double *per_bin_out, double *one_rdm_out,
+                          double *two_rdm_out);
+int afq_thermal_set_sweep_budget(afq_handle *h, size_t bytes);
+
 /* ---- finite-temperature AFQMC with continuous fields: thermal walkers of the uniform electron gas -----------
  * thermal_propagation/planewave.py:219-276,445-517, walkers/stack.py:299-324, walkers/thermal.py of the reference:
  * PlaneWave with the phaseless constraint and the force bias, OneBody trial density matrix (diagonal for plane

@@ -289,6 +289,10 @@ struct afq_handle {
     // the dense trial's alone (afq_thermal_configure_hubbard_continuous)
     double thd_mf_const[2] = {1.0, 0.0};   // exp(-dt mf_core) (re, im)
     double thd_sqrt_u = 0.0;        // iu_fac = i sqrt(U)
+    // afq_thermal_estimates (k_thermal.hip): the sweep's chunk of G, P and (streamed) T, taken in whole bins under
+    // th_sw_budget bytes (0: the default), and its small results (energies, nav, the sums); both grown on demand
+    unsigned char *th_sw_ws = nullptr, *th_sw_out = nullptr;
+    size_t th_sw_ws_len = 0, th_sw_out_len = 0, th_sw_budget = 0;
 
     // ---- propagator
     bool have_prop = false;
@@ -727,6 +731,10 @@ int k_thermal_greens(afq_handle *h, int slice_ix);          // th_G of every wal
 int k_thermal_c_greens(afq_handle *h, int slice_ix);        // thc_G and thc_det of every walker from its stack
 int k_thermal_c_reset(afq_handle *h, bool with_m0);         // with_m0: M0 <- the trial's (a fresh population)
 int k_thermal_c_energy(afq_handle *h, double *E_out, double *nav_out);
+// the sweep of afq_thermal_estimates on the complex walkers: G of nb bins from ts0 on into Gs (Ts: the streamed engine's
+// scratch), then P and nav of those nb nw Green's functions
+int k_thermal_c_sweep_greens(afq_handle *h, cplx *Gs, cplx *Ts, int ts0, int nb);
+int k_thermal_c_sweep_rdm(afq_handle *h, const cplx *Gs, cplx *P, double *nav, int n);
 // k_corr.hip: <n_is n_jt> and <S+_i S-_j> of full Green's functions G_dev [n, 2, M, M] -> out_dev [n, 5, M, M], and
 // their weighted sum over n -> out_dev [5, M, M] (Green's functions of weight zero left out), in index order
 int k_corr_full_g(afq_handle *h, const cplx *G_dev, int n, cplx *out_dev);

@@ -10,6 +10,9 @@
 //   thermal_slice_kernel    one work-group per walker, both spins' G in LDS: the M single-site updates of
 //                           propagate_walker_constrained, then B_s = diag(BV_s) BH1_s onto the walker's current bin.
 //   thermal_wrap_kernel     G_s <- BT_s G_s BT_s^-1 (two MFMA products) per (walker, spin).
+// and, for every kind of thermal handle, afq_thermal_estimates: the mixed estimator's sums (estimators/mixed.py:180-233)
+//   thermal_sweep_reduce_kernel   every walker's (E, T, V, nav) over the bins of the sweep, added in bin order.
+//   thermal_one_rdm_kernel        sum_w weight_w Re G_w.
 #include "thermal_strat.h"
 #include <cstring>
 
@@ -129,6 +132,48 @@ __global__ void thermal_reset_kernel(double *stack, double *G, double *weight, c
         G[(long)w * per + i] = G0[i];
     }
     if (i == 0) weight[w] = 1.0;
+}
+
+// ---- afq_thermal_estimates: the estimators' sums of a population of thermal walkers
+
+#define TH_SWEEP_BUDGET ((size_t)2 << 30)      // bytes of G, P and T scratch a sweep takes at a time unless told otherwise
+
+// One thread per walker: (E, T, V, nav) of its nbins Green's functions (E c128 [nbins, nw, 3], nav [nbins, nw]) into
+// per_bin [nbins, nw, 4], and their sums, added in bin order from zero, into cols [nw, 4].
+__global__ void thermal_sweep_reduce_kernel(const cplx *E, const double *nav, int nw, int nbins, double *cols, double *per_bin) {
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= nw) return;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int ts = 0; ts < nbins; ++ts) {
+        const long g = (long)ts * nw + w;
+        const double v[4] = {E[3 * g].x, E[3 * g + 1].x, E[3 * g + 2].x, nav[g]};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { per_bin[4 * g + q] = v[q]; s[q] += v[q]; }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cols[4 * w + q] = s[q];
+}
+
+// out[e] = sum_w weight_w Re G_w[e] over every walker in walker order, one thread per element: no atomics, the same
+// bits on every run
+template <class T>
+__global__ void thermal_one_rdm_kernel(const T *G, const double *weight, int nw, long len, double *out) {
+    const long e = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (e >= len) return;
+    double acc = 0.0;
+    for (int w = 0; w < nw; ++w) acc += weight[w] * TsScalar<T>::re(G[(long)w * len + e]);
+    out[e] = acc;
+}
+
+inline size_t th_up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// the energies of n Green's functions from their P [n, 2, M, M]: E c128 [n, 3]; *two (UEG) the per-q pair sums
+// [n, 2, 2, nq] in the handle's scratch
+int th_energy_n(afq_handle *h, const cplx *P, int n, cplx *E, cplx **two) {
+    if (h->th_kind != TH_CPLX_DIAG) return k_energy_hubbard_full_g(h, P, n, E);
+    cplx *e_unused = nullptr;
+    AFQ_TRY(k_ueg_sf_two(h, n, two, &e_unused));
+    return k_ueg_pair_sums(h, P, n, E, *two);
 }
 
 }  // namespace
@@ -251,6 +296,92 @@ int afq_thermal_energy(afq_handle *h, double *E_out, double *nav_out) {
     AFQ_TRY(ts_launch_rdm<double>(h, h->th_G, h->th_nav));
     AFQ_TRY(k_energy_hubbard_full_g(h, h->G, h->nw, h->energy));
     return th_energy_out(h, E_out, nav_out);
+}
+
+int afq_thermal_set_sweep_budget(afq_handle *h, size_t bytes) {
+    if (!h) return AFQ_EINVAL;
+    h->th_sw_budget = bytes;
+    return AFQ_OK;
+}
+
+int afq_thermal_estimates(afq_handle *h, int what, double *cols_out, double *per_bin_out, double *one_rdm_out,
+                          double *two_rdm_out) {
+    AFQ_API(h, "afq_thermal_estimates");
+    if (!h) return AFQ_EINVAL;
+    AFQ_TRY(th_need(h, false));
+    const bool avg = what & AFQ_THERMAL_EST_AVERAGE_GF, one = what & AFQ_THERMAL_EST_ONE_RDM, two = what & AFQ_THERMAL_EST_TWO_RDM;
+    if (what & ~(AFQ_THERMAL_EST_AVERAGE_GF | AFQ_THERMAL_EST_ONE_RDM | AFQ_THERMAL_EST_TWO_RDM))
+        AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_estimates: unknown bits in what");
+    if (!cols_out || (one && !one_rdm_out) || (two && !two_rdm_out))
+        AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_estimates: null output (cols_out always, one_rdm_out with ONE_RDM, two_rdm_out with TWO_RDM)");
+    if (two && h->th_kind != TH_CPLX_DIAG)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "afq_thermal_estimates: two_rdm is the structure factor of the UEG walkers (no Hubbard)");
+    const bool cx = th_complex(h);
+    const int M = h->M, nw = h->nw, nbins = h->th_nbins, nbt = avg ? nbins : 1;
+    const size_t mm = (size_t)M * M, n = nw, nq4 = two ? 4 * (size_t)h->nq : 0;
+    // the small results, fetched in one copy: cols [nw, 4], per_bin [nbt, nw, 4], one_rdm [2, M, M], two_rdm c128 [2, 2, nq];
+    // behind them the sweep's energies c128 [nbins, nw, 3] and nav [nbins, nw]
+    const size_t o_cols = 0, o_bin = o_cols + sizeof(double) * 4 * n, o_rdm = o_bin + sizeof(double) * 4 * n * nbt,
+                 o_two = th_up256(o_rdm + sizeof(double) * 2 * mm), o_end = o_two + sizeof(cplx) * nq4,
+                 o_E = th_up256(o_end), o_nav = o_E + sizeof(cplx) * 3 * n * nbins, o_all = o_nav + sizeof(double) * n * nbins;
+    AFQ_TRY(dev_grow(h, LT_WALKERS, &h->th_sw_out, &h->th_sw_out_len, o_all, "thermal estimates"));
+    unsigned char *out = h->th_sw_out;
+    double *cols = (double *)(out + o_cols), *per_bin = (double *)(out + o_bin), *rdm = (double *)(out + o_rdm);
+    cplx *two_sum = (cplx *)(out + o_two), *two_src = nullptr;
+    if (!avg) {
+        // what update_thermal has always done: G at the handle's slice, then the energy's own launches
+        AFQ_TRY(cx ? k_thermal_c_greens(h, h->th_slice) : k_thermal_greens(h, h->th_slice));
+        AFQ_TRY(cx ? ts_launch_rdm<cplx>(h, h->thc_G, h->th_nav) : ts_launch_rdm<double>(h, h->th_G, h->th_nav));
+        AFQ_TRY(th_energy_n(h, h->G, nw, h->energy, &two_src));
+        AFQ_LAUNCH(h, thermal_sweep_reduce_kernel, dim3((nw + 127) / 128), dim3(128), 0, h->stream, h->energy, h->th_nav, nw, 1,
+                   cols, per_bin);
+        AFQ_POST(h);
+    } else {
+        // G [cb, nw, 2, M, M], P c128 of the same shape and, streamed, T [cb, 2 nw, 2, M, M]: cb whole bins under the budget
+        const size_t gsz = cx ? sizeof(cplx) : sizeof(double);
+        const size_t b_P = sizeof(cplx) * 2 * mm * n, b_G = gsz * 2 * mm * n, b_T = h->thc_streamed && cx ? sizeof(cplx) * 4 * mm * n : 0;
+        const size_t budget = h->th_sw_budget ? h->th_sw_budget : TH_SWEEP_BUDGET;
+        size_t cb = budget / (b_P + b_G + b_T);
+        cb = cb < 1 ? 1 : cb > (size_t)nbins ? (size_t)nbins : cb;
+        AFQ_TRY(dev_grow(h, LT_WALKERS, &h->th_sw_ws, &h->th_sw_ws_len, cb * (b_P + b_G + b_T), "thermal estimates: the sweep's scratch"));
+        cplx *P = (cplx *)h->th_sw_ws, *Ts = (cplx *)(h->th_sw_ws + cb * (b_P + b_G));
+        void *Gs = h->th_sw_ws + cb * b_P;
+        cplx *E = (cplx *)(out + o_E);
+        double *nav = (double *)(out + o_nav);
+        for (int ts0 = 0; ts0 < nbins; ts0 += (int)cb) {
+            const int nb = nbins - ts0 < (int)cb ? nbins - ts0 : (int)cb;
+            if (cx) {
+                AFQ_TRY(k_thermal_c_sweep_greens(h, (cplx *)Gs, Ts, ts0, nb));
+                AFQ_TRY(k_thermal_c_sweep_rdm(h, (const cplx *)Gs, P, nav + (size_t)ts0 * n, nb * nw));
+            } else {
+                AFQ_TRY(ts_launch_greens_sweep<double>(h, h->th_stack, (double *)Gs, h->th_G, nullptr, ts0, nb));
+                AFQ_TRY(ts_launch_rdm_n<double>(h, (const double *)Gs, P, nav + (size_t)ts0 * n, nb * nw));
+            }
+            AFQ_TRY(th_energy_n(h, P, nb * nw, E + 3 * (size_t)ts0 * n, &two_src));
+            if (two_src) two_src += (size_t)(nb - 1) * n * nq4;       // (behind the loop: the path's last bin)
+        }
+        AFQ_LAUNCH(h, thermal_sweep_reduce_kernel, dim3((nw + 127) / 128), dim3(128), 0, h->stream, E, nav, nw, nbins, cols, per_bin);
+        AFQ_POST(h);
+    }
+    if (one) {
+        const long len = 2L * M * M;
+        const dim3 grid((unsigned)((len + 127) / 128)), block(128);
+        afq_note_launch(h, "thermal_one_rdm_kernel");
+        if (cx) hipLaunchKernelGGL(thermal_one_rdm_kernel<cplx>, grid, block, 0, h->stream, h->thc_G, h->weight, nw, len, rdm);
+        else hipLaunchKernelGGL(thermal_one_rdm_kernel<double>, grid, block, 0, h->stream, h->th_G, h->weight, nw, len, rdm);
+        AFQ_POST(h);
+    }
+    if (two) AFQ_TRY(k_ueg_sf_wsum(h, two_src, nw, nullptr, h->weight, two_sum, nullptr));
+    std::vector<unsigned char> host(o_end);
+    AFQ_TRY(copy_out(h, host.data(), out, o_end));
+    memcpy(cols_out, host.data() + o_cols, sizeof(double) * 4 * n);
+    if (per_bin_out) memcpy(per_bin_out, host.data() + o_bin, sizeof(double) * 4 * n * nbt);
+    if (one) memcpy(one_rdm_out, host.data() + o_rdm, sizeof(double) * 2 * mm);
+    if (two) {
+        const double *t = (const double *)(host.data() + o_two);
+        for (size_t i = 0; i < nq4; ++i) two_rdm_out[i] = t[2 * i];
+    }
+    return AFQ_OK;
 }
 
 int afq_thermal_state(afq_handle *h, int32_t *out4) {

@@ -372,6 +372,13 @@ int k_thermal_c_reset(afq_handle *h, bool with_m0) {
     return AFQ_OK;
 }
 
+int k_thermal_c_sweep_greens(afq_handle *h, cplx *Gs, cplx *Ts, int ts0, int nb) {
+    if (h->thc_streamed) return ts_launch_greens_streamed_sweep<cplx>(h, h->thc_stack, Gs, h->thc_G, h->thc_det, Ts, ts0, nb);
+    return ts_launch_greens_sweep<cplx>(h, h->thc_stack, Gs, h->thc_G, h->thc_det, ts0, nb);
+}
+
+int k_thermal_c_sweep_rdm(afq_handle *h, const cplx *Gs, cplx *P, double *nav, int n) { return ts_launch_rdm_n<cplx>(h, Gs, P, nav, n); }
+
 int k_thermal_c_energy(afq_handle *h, double *E_out, double *nav_out) {
     AFQ_TRY(ts_launch_rdm<cplx>(h, h->thc_G, h->th_nav));
     if (h->th_kind == TH_CPLX_DENSE) {                  // Hubbard: the full-G energy of P, as the real walkers' (k_thermal.hip)

@@ -19,6 +19,12 @@
 //                             LDS, which hold a complex walker to M = 64 (117,536 B at the M = 57 shell).  Chosen per
 //                             handle by AFQ_THERMAL_STREAMED_GREENS; the same bits as the resident kernel.
 //
+//   thermal_greens_sweep_kernel<T>, thermal_greens_streamed_sweep_kernel<cplx>  the same two engines (their bodies are
+//                             the device functions ts_greens_body / ts_greens_streamed_body, which the kernels above
+//                             call too) on a grid (2 nw, bins): work-group (x, y) makes G of (walker, spin) x at
+//                             slice_ix = (ts0 + y) stack_size into a scratch [bins, nw, 2, M, M] -- the averaged
+//                             estimators' sweep of afq_thermal_estimates, one launch whatever the number of bins.
+//
 // TsScalar<T> is the arithmetic the routines are written in.  Restricted to real numbers the complex formulas round as
 // the real ones do: a product with +-1 and a negation are exact, so alpha = -unit(x_0) ||x||, x_0 - alpha =
 // unit(x_0) (|x_0| + ||x||) and tau = (||x|| + |x_0|) / ||x|| are the doubles of alpha = x_0 >= 0 ? -||x|| : ||x|| and
@@ -250,25 +256,30 @@ template <class T> __device__ T ts_det(T *X, int M, int LD, T *colv) {
 }
 
 __host__ __device__ inline size_t ts_mat(int M) { return (size_t)M * (M | 1); }
+// first bin of the chain for the Green's function at slice_ix (walkers/thermal.py:477-492)
+__host__ __device__ inline int ts_first_of(int slice_ix, int stack_size, int nbins) {
+    int bin_ix = slice_ix / stack_size;
+    if (bin_ix == nbins) bin_ix = -1;
+    return (bin_ix + 1) % nbins;
+}
 // LDS of the Green's kernel: 4 matrices, D[64], v[64], part[512], aux[192] scalars, perm[64]
 template <class T> inline size_t ts_greens_lds(int M) { return sizeof(T) * (4 * ts_mat(M) + 64 + 64 + 512 + 192) + sizeof(int) * 64; }
 
 // G[w, s] and det G[w, s] from the bins of walker w in the order first, first + 1, .. (mod nbins).
 // stack [nw, nbins, 2, M, M]; src_w < 0: block b works on walker b / 2, otherwise every block works on walker src_w and
 // writes walker 0's place (grid of 2 blocks).  det may be null.
+// The work of one work-group: G of one (walker, spin) from its bins Bw (bin b at Bw + b * 2 * M * M) in the order first,
+// first + 1, .. (mod nbins), into Gd [M, M] and, where given, into Gd2 as well; det G into *detd where given.
 template <class T>
-__global__ __launch_bounds__(TH_THREADS) void thermal_greens_kernel(const T *stack, T *G, T *det, int M, int nbins, int first,
-                                                                     int src_w) {
+__device__ __forceinline__ void ts_greens_body(unsigned char *smem, const T *Bw, int M, int nbins, int first, T *Gd, T *Gd2,
+                                               T *detd) {
     typedef TsScalar<T> S;
-    extern __shared__ __align__(16) unsigned char smem[];
     const int LD = M | 1, tid = threadIdx.x;
     const size_t mat = ts_mat(M);
     T *W = (T *)smem, *Qt = W + mat, *Tm = Qt + mat, *X = Tm + mat;
     T *D = X + mat, *v = D + 64, *part = v + 64, *aux = part + 512;
     int *perm = (int *)(aux + 192);
-    const int w = src_w < 0 ? blockIdx.x >> 1 : src_w, s = blockIdx.x & 1;
     const long mm = (long)M * M;
-    const T *Bw = stack + ((long)w * nbins * 2 + s) * mm;            // bin b at Bw + b * 2 * mm
 
     {
         const T *B = Bw + (long)first * 2 * mm;
@@ -317,19 +328,44 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_greens_kernel(const T *sta
     }
     __syncthreads();
     ts_solve(X, W, M, LD, aux, aux + 64, aux + 128);
-    const long slot = (long)(src_w < 0 ? w : 0) * 2 + s;
-    T *Gd = G + slot * mm;
     // (only the complex walkers carry determinants: the real kernel holds no code for them)
-    const bool want_det = std::is_same<T, cplx>::value && det;
+    const bool want_det = std::is_same<T, cplx>::value && detd;
     for (int e = tid; e < M * M; e += TH_THREADS) {
         const T g = W[(e / M) * LD + e % M];
         Gd[e] = g;
+        if (Gd2) Gd2[e] = g;
         if (want_det) X[(e / M) * LD + e % M] = g;
     }
     if (!want_det) return;
     __syncthreads();
     const T dg = ts_det(X, M, LD, aux);
-    if (tid == 0) det[slot] = dg;
+    if (tid == 0) *detd = dg;
+}
+
+template <class T>
+__global__ __launch_bounds__(TH_THREADS) void thermal_greens_kernel(const T *stack, T *G, T *det, int M, int nbins, int first,
+                                                                     int src_w) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int w = src_w < 0 ? blockIdx.x >> 1 : src_w, s = blockIdx.x & 1;
+    const long mm = (long)M * M;
+    const long slot = (long)(src_w < 0 ? w : 0) * 2 + s;
+    ts_greens_body<T>(smem, stack + ((long)w * nbins * 2 + s) * mm, M, nbins, first, G + slot * mm, nullptr,
+                      det ? det + slot : nullptr);
+}
+
+// The sweep of the averaged estimators (afq_thermal_estimates): work-group (x, y) makes G of (walker, spin) x at
+// slice_ix = (ts0 + y) stack_size, for every y at once, into Gs [gridDim.y, nw, 2, M, M].  The last bin of the path
+// (ts = nbins - 1) also goes to the walkers' own G and det: what afq_thermal_greens leaves there.
+template <class T>
+__global__ __launch_bounds__(TH_THREADS) void thermal_greens_sweep_kernel(const T *stack, T *Gs, T *G, T *det, int M, int nbins,
+                                                                           int stack_size, int ts0) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int w = blockIdx.x >> 1, s = blockIdx.x & 1, ts = ts0 + (int)blockIdx.y;
+    const long mm = (long)M * M, slot = (long)w * 2 + s;
+    const bool last = ts == nbins - 1;
+    ts_greens_body<T>(smem, stack + ((long)w * nbins * 2 + s) * mm, M, nbins, ts_first_of(ts * stack_size, stack_size, nbins),
+                      Gs + ((long)blockIdx.y * gridDim.x + blockIdx.x) * mm, last ? G + slot * mm : nullptr,
+                      last && det ? det + slot : nullptr);
 }
 
 // LDS of the streamed Green's kernel: W and Qt, D[64], v[64], part[512], aux[192] scalars, perm[64]
@@ -341,21 +377,19 @@ template <class T> inline size_t ts_greens_streamed_lds(int M) { return sizeof(T
 // t T reads it out of W through the inverse permutation.  Every element goes through the operations of
 // thermal_greens_kernel in their order, so the two kernels give the same bits.  A work-group reads only what it has
 // written itself, across a __syncthreads().  Instantiated for cplx alone (the real walkers fit to M = 64 as they are).
+// The streamed work of one work-group, as ts_greens_body; Tin: the work-group's own [2, M, M] in device memory.
 template <class T>
-__global__ __launch_bounds__(TH_THREADS) void thermal_greens_streamed_kernel(const T *stack, T *G, T *det, T *scratch, int M,
-                                                                              int nbins, int first, int src_w) {
+__device__ __forceinline__ void ts_greens_streamed_body(unsigned char *smem, const T *Bw, T *Tin, int M, int nbins, int first,
+                                                        T *Gd, T *Gd2, T *detd) {
     typedef TsScalar<T> S;
-    extern __shared__ __align__(16) unsigned char smem[];
     const int LD = M | 1, tid = threadIdx.x;
     const size_t mat = ts_mat(M);
     T *W = (T *)smem, *Qt = W + mat;
     T *D = Qt + mat, *v = D + 64, *part = v + 64, *aux = part + 512;
     int *perm = (int *)(aux + 192);
     int *iperm = (int *)aux;                                         // (aux is the solve's: free until the chain is done)
-    const int w = src_w < 0 ? blockIdx.x >> 1 : src_w, s = blockIdx.x & 1;
     const long mm = (long)M * M;
-    const T *Bw = stack + ((long)w * nbins * 2 + s) * mm;            // bin b at Bw + b * 2 * mm
-    T *Tin = scratch + (long)blockIdx.x * 2 * mm, *Tout = Tin + mm;  // pitch M
+    T *Tout = Tin + mm;                                              // pitch M
 
     {
         const T *B = Bw + (long)first * 2 * mm;
@@ -400,17 +434,40 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_greens_streamed_kernel(con
     }
     __syncthreads();
     ts_solve(W, Qt, M, LD, aux, aux + 64, aux + 128);
-    const long slot = (long)(src_w < 0 ? w : 0) * 2 + s;
-    T *Gd = G + slot * mm;
     for (int e = tid; e < M * M; e += TH_THREADS) {
         const T g = Qt[(e / M) * LD + e % M];
         Gd[e] = g;
-        if (det) W[(e / M) * LD + e % M] = g;
+        if (Gd2) Gd2[e] = g;
+        if (detd) W[(e / M) * LD + e % M] = g;
     }
-    if (!det) return;
+    if (!detd) return;
     __syncthreads();
     const T dg = ts_det(W, M, LD, aux);
-    if (tid == 0) det[slot] = dg;
+    if (tid == 0) *detd = dg;
+}
+
+template <class T>
+__global__ __launch_bounds__(TH_THREADS) void thermal_greens_streamed_kernel(const T *stack, T *G, T *det, T *scratch, int M,
+                                                                              int nbins, int first, int src_w) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int w = src_w < 0 ? blockIdx.x >> 1 : src_w, s = blockIdx.x & 1;
+    const long mm = (long)M * M;
+    const long slot = (long)(src_w < 0 ? w : 0) * 2 + s;
+    ts_greens_streamed_body<T>(smem, stack + ((long)w * nbins * 2 + s) * mm, scratch + (long)blockIdx.x * 2 * mm, M, nbins, first,
+                               G + slot * mm, nullptr, det ? det + slot : nullptr);
+}
+
+// thermal_greens_sweep_kernel by the streamed engine; scratch [gridDim.y, gridDim.x, 2, M, M]: every work-group its own
+template <class T>
+__global__ __launch_bounds__(TH_THREADS) void thermal_greens_streamed_sweep_kernel(const T *stack, T *Gs, T *G, T *det, T *scratch,
+                                                                                    int M, int nbins, int stack_size, int ts0) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int w = blockIdx.x >> 1, s = blockIdx.x & 1, ts = ts0 + (int)blockIdx.y;
+    const long mm = (long)M * M, slot = (long)w * 2 + s, wg = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    const bool last = ts == nbins - 1;
+    ts_greens_streamed_body<T>(smem, stack + ((long)w * nbins * 2 + s) * mm, scratch + wg * 2 * mm, M, nbins,
+                               ts_first_of(ts * stack_size, stack_size, nbins), Gs + wg * mm, last ? G + slot * mm : nullptr,
+                               last && det ? det + slot : nullptr);
 }
 
 // P_s = I - G_s^T as c128 [nw, 2, M, M], nav = Re(tr P_up + tr P_down) (nav may be null)
@@ -494,11 +551,7 @@ inline void th_advance(afq_handle *h) {
 }
 
 // first bin of the chain for the Green's function at slice_ix (walkers/thermal.py:477-492)
-inline int ts_first_bin(const afq_handle *h, int slice_ix) {
-    int bin_ix = slice_ix / h->th_ss;
-    if (bin_ix == h->th_nbins) bin_ix = -1;
-    return (bin_ix + 1) % h->th_nbins;
-}
+inline int ts_first_bin(const afq_handle *h, int slice_ix) { return ts_first_of(slice_ix, h->th_ss, h->th_nbins); }
 
 // The launch trace names the kernel by walker kind, not by its template: the benchmarks' tables are keyed by these names.
 template <class T> int ts_launch_greens(afq_handle *h, const T *stack, T *G, T *det, int first, int src_w, int nblocks) {
@@ -526,13 +579,41 @@ template <class T> int ts_launch_greens_streamed(afq_handle *h, const T *stack, 
     return AFQ_OK;
 }
 
-// P [nw, 2, M, M] into the handle's c128 G buffer, nav (or null) from the walkers' G
-template <class T> int ts_launch_rdm(afq_handle *h, const T *G, double *nav) {
-    afq_note_launch(h, std::is_same<T, cplx>::value ? "thermal_crdm_kernel" : "thermal_rdm_kernel");
-    hipLaunchKernelGGL(thermal_rdm_kernel<T>, dim3(h->nw), dim3(TH_THREADS), 0, h->stream, G, h->G, nav, h->M);
+// The sweep's launches: nb bins from ts0 on, Gs [nb, nw, 2, M, M] (and Ts [nb, 2 nw, 2, M, M] of the streamed engine);
+// G, det: the walkers' own, written by the path's last bin (det null for the real walkers).  Their own names in the trace.
+template <class T> int ts_launch_greens_sweep(afq_handle *h, const T *stack, T *Gs, T *G, T *det, int ts0, int nb) {
+    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
+    const size_t lds = ts_greens_lds<T>(h->M);
+    AFQ_HIP(h, afq_raise_lds((const void *)thermal_greens_sweep_kernel<T>, lds, lds_set));
+    afq_note_launch(h, std::is_same<T, cplx>::value ? "thermal_cgreens_sweep_kernel" : "thermal_greens_sweep_kernel");
+    hipLaunchKernelGGL(thermal_greens_sweep_kernel<T>, dim3(2 * h->nw, nb), dim3(TH_THREADS), lds, h->stream, stack, Gs, G, det,
+                       h->M, h->th_nbins, h->th_ss, ts0);
     AFQ_POST(h);
     return AFQ_OK;
 }
+
+template <class T> int ts_launch_greens_streamed_sweep(afq_handle *h, const T *stack, T *Gs, T *G, T *det, T *Ts, int ts0, int nb) {
+    static_assert(std::is_same<T, cplx>::value, "the streamed Green's function is the complex walkers' alone");
+    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
+    const size_t lds = ts_greens_streamed_lds<T>(h->M);
+    AFQ_HIP(h, afq_raise_lds((const void *)thermal_greens_streamed_sweep_kernel<T>, lds, lds_set));
+    afq_note_launch(h, "thermal_cgreens_streamed_sweep_kernel");
+    hipLaunchKernelGGL(thermal_greens_streamed_sweep_kernel<T>, dim3(2 * h->nw, nb), dim3(TH_THREADS), lds, h->stream, stack, Gs, G,
+                       det, Ts, h->M, h->th_nbins, h->th_ss, ts0);
+    AFQ_POST(h);
+    return AFQ_OK;
+}
+
+// P_s = I - G_s^T of n Green's functions G [n, 2, M, M] into P, nav [n] (or null): the sweep's own scratch
+template <class T> int ts_launch_rdm_n(afq_handle *h, const T *G, cplx *P, double *nav, int n) {
+    afq_note_launch(h, std::is_same<T, cplx>::value ? "thermal_crdm_kernel" : "thermal_rdm_kernel");
+    hipLaunchKernelGGL(thermal_rdm_kernel<T>, dim3(n), dim3(TH_THREADS), 0, h->stream, G, P, nav, h->M);
+    AFQ_POST(h);
+    return AFQ_OK;
+}
+
+// P [nw, 2, M, M] into the handle's c128 G buffer, nav (or null) from the walkers' G
+template <class T> int ts_launch_rdm(afq_handle *h, const T *G, double *nav) { return ts_launch_rdm_n<T>(h, G, h->G, nav, h->nw); }
 
 // (E, T, V) of every walker as the real parts of the handle's c128 [3, nw] energies, and nav; either may be null
 inline int th_energy_out(afq_handle *h, double *E_out, double *nav_out) {

@@ -460,6 +460,30 @@ class AfqDevice(object):
         self._ck(self.lib.afq_thermal_energy(self.h, _p(E), _p(nav)))
         return E, nav
 
+    def thermal_estimates(self, average_gf=False, one_rdm=False, two_rdm=False, per_bin=False):
+        """The mixed estimator's sums of the thermal population (afq_thermal_estimates) -> dict:
+        'cols' [nw, 4] = (E, T, V, nav) per walker -- with average_gf their sums over the Green's functions at
+        slice_ix = ts * stack_size, ts = 0 .. nbins - 1, in that order; 'per_bin' [nbins, nw, 4] (one row without
+        average_gf) when asked for; 'one_rdm' [2, M, M] = sum_w weight_w Re G_w and 'two_rdm' [2, 2, nq] (UEG) =
+        sum_w weight_w Re two_rdm[P_w] of the G the call leaves: the last of the sweep, or the one at the current slice."""
+        what = ((L.THERMAL_EST_AVERAGE_GF if average_gf else 0) | (L.THERMAL_EST_ONE_RDM if one_rdm else 0)
+                | (L.THERMAL_EST_TWO_RDM if two_rdm else 0))
+        nb = getattr(self, 'thermal_nbins', 1) if average_gf else 1
+        out = {'cols': numpy.zeros((self.nw, 4), dtype=numpy.float64)}
+        if per_bin:
+            out['per_bin'] = numpy.zeros((nb, self.nw, 4), dtype=numpy.float64)
+        if one_rdm:
+            out['one_rdm'] = numpy.zeros((2, self.M, self.M), dtype=numpy.float64)
+        if two_rdm:
+            out['two_rdm'] = numpy.zeros((2, 2, getattr(self, 'nq', 0)), dtype=numpy.float64)
+        self._ck(self.lib.afq_thermal_estimates(self.h, what, _p(out['cols']), _p(out.get('per_bin')),
+                                                _p(out.get('one_rdm')), _p(out.get('two_rdm'))))
+        return out
+
+    def thermal_set_sweep_budget(self, nbytes=0):
+        """Bytes of scratch (G, P and the streamed T) the averaged sweep takes at a time; 0: the library's default."""
+        self._ck(self.lib.afq_thermal_set_sweep_budget(self.h, int(nbytes)))
+
     def thermal_state(self):
         """(time slice, block, in-bin counter, nbins)."""
         out = numpy.zeros(4, dtype=numpy.int32)

@@ -29,7 +29,7 @@ def _touch(filename):
 
 class Estimators(object):
     def __init__(self, estimates, root, qmc, system, trial, BT2, verbose=False, discrete=None,
-                 free_projection=False):
+                 free_projection=False, thermal_sweep=False):
         opts = estimates
         self.index = opts.get('index', 0)
         self.basename = opts.get('basename', 'estimates')                    # handler.py:62
@@ -49,7 +49,8 @@ class Estimators(object):
             _touch(name)
         self.estimators = {}
         mixed_opts = dict(opts.get('mixed', {}), flush_every=opts.get('mixed', {}).get('flush_every', self.flush_every))
-        self.estimators['mixed'] = Mixed(mixed_opts, system, root, name, qmc, trial, complex)
+        self.estimators['mixed'] = Mixed(mixed_opts, system, root, name, qmc, trial, complex,
+                                         thermal_sweep=thermal_sweep)
         bp_opts = opts.get('back_propagation', opts.get('back_propagated'))              # handler.py:83-85
         self.calc_itcf = opts.get('itcf') is not None
         if self.calc_itcf and bp_opts is not None:

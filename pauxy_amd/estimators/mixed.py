@@ -17,6 +17,16 @@ fills.  Per block the root pushes ``basic/two_rdm/<block>`` = (the accumulator s
 EDenom) and keeps it in ``self.two_rdm``: the energy's own estimator per momentum transfer, so that
 1 / (2 vol) * vqvec . two_rdm.sum((0, 1)) of a block is that block's E2Body.  (The reference's non-thermal branch never
 hands its two_rdm array to the energy call, mixed.py:214, and writes zeros; this normalisation is this package's.)
+
+Thermal walkers (``qmc.beta``) with ``Mixed(..., thermal_sweep=True)`` -- what ``ThermalAFQMC`` passes; without the
+keyword the three options are refused as before -- take ``one_rdm: True``, ``two_rdm: 'structure_factor'`` (UEG) and
+``average_gf: True`` (mixed.py:180-233): the library's afq_thermal_estimates makes every walker's sums in one call.
+Per block ``basic/one_rdm/<block>`` = sum_w weight_w Re G_w / nsteps / Weight [2, M, M] and ``basic/two_rdm/<block>`` =
+sum_w weight_w Re two_rdm[P_w] / nsteps / Weight [2, 2, nq] with P_w = I - G_w^T: for thermal walkers this is the
+reference's normalisation (mixed.py:279-287), not the ground state's / EDenom above.
+One deliberate deviation: with ``average_gf`` EDenom accumulates the walkers' weights.  The reference's ``average_gf``
+branch (mixed.py:182-199) has no EDenom line, so its ETotal, E1Body and E2Body columns are +-inf or NaN; the numerators
+(ENumer and the raw one- and two-body sums), Nav, Weight and the RDMs are the reference's.
 """
 import time
 
@@ -41,13 +51,19 @@ class Mixed(object):
     _sf_armed = False
     thermal = False             # set with a finite-temperature run (qmc.beta, mixed.py:87-92): the Nav column
 
-    def __init__(self, mixed, system, root, filename, qmc, trial, dtype=complex):
+    average_gf = False          # thermal, with thermal_sweep: energies and Nav averaged over the stack_length Green's functions
+
+    def __init__(self, mixed, system, root, filename, qmc, trial, dtype=complex, thermal_sweep=False):
         if getattr(qmc, 'beta', None) is not None:
             self.thermal = True
-            if mixed.get('average_gf', False):
-                raise NotImplementedError("mixed estimator: average_gf is not supported with a thermal trial")
-            if mixed.get('one_rdm', False) or mixed.get('two_rdm', None) is not None:
-                raise NotImplementedError("mixed estimator: one_rdm / two_rdm are not supported with a thermal trial")
+            if not thermal_sweep:
+                if mixed.get('average_gf', False):
+                    raise NotImplementedError("mixed estimator: average_gf is not supported with a thermal trial "
+                                              "(Mixed(..., thermal_sweep=True), which ThermalAFQMC passes, takes it)")
+                if mixed.get('one_rdm', False) or mixed.get('two_rdm', None) is not None:
+                    raise NotImplementedError("mixed estimator: one_rdm / two_rdm are not supported with a thermal trial "
+                                              "(Mixed(..., thermal_sweep=True), which ThermalAFQMC passes, takes them)")
+            self.average_gf = bool(mixed.get('average_gf', False))
         self.eval_energy = mixed.get('evaluate_energy', True)
         self.calc_one_rdm = mixed.get('one_rdm', False)
         two = mixed.get('two_rdm', None)
@@ -133,6 +149,8 @@ class Mixed(object):
         """mixed.py:200-209,222-225 for a population of thermal walkers: G rebuilt from every walker's stack at its
         current time slice (the end of the path), the energies and particle numbers from the device, the weighted
         sums -- once per path -- here."""
+        if self.average_gf or self.calc_one_rdm or self.structure_factor:
+            return self.update_thermal_sweep(psi)
         ns, es = self.names, self.estimates
         psi.recompute_greens_function(None)
         E, nav = psi.dev.thermal_energy()
@@ -148,6 +166,41 @@ class Mixed(object):
             es[ns.weight] += w[i]
             es[ns.ovlp] += w[i] * 1.0                                   # walker.ot stays 1 (walkers/walker.py)
             es[ns.ehyb] += w[i] * 0.0                                   # walker.hybrid_energy stays 0
+
+    def update_thermal_sweep(self, psi):
+        """mixed.py:180-233 with ``average_gf``, ``one_rdm`` or ``two_rdm`` (``Mixed(..., thermal_sweep=True)``): one
+        call of the library (afq_thermal_estimates) for the whole population.  With ``average_gf`` every walker's
+        energies and particle number are summed over the Green's functions at slice_ix = ts * stack_size,
+        ts = 0 .. stack_length - 1, multiplied by the weight and divided by stack_length (mixed.py:195-199); the RDMs
+        then are the last of those Green's functions', as in the reference, whose loop leaves it on the walker."""
+        from pauxy_amd import _lib as L
+        ns, es = self.names, self.estimates
+        psi.ensure_configured()
+        if psi.dev.thermal_state()[0] != psi.time_slice:                # (the library evaluates at ITS slice counter)
+            raise RuntimeError("mixed estimator: the population's time slice and the library's differ")
+        res = psi.dev.thermal_estimates(average_gf=self.average_gf, one_rdm=bool(self.calc_one_rdm),
+                                        two_rdm=self.structure_factor)
+        cols = res['cols']
+        w = psi.dev.get(L.F_WEIGHT)
+        uw = psi.dev.get(L.F_UNSCALED_WEIGHT)
+        nb = psi.stack_length
+        for i in range(len(w)):                                         # (walker order, as the reference sums)
+            if self.average_gf:
+                es[ns.nav] += w[i] * cols[i, 3] / nb
+                es[ns.enumer] += w[i] * cols[i, 0] / nb
+                es[ns.e1b:ns.e2b + 1] += w[i] * cols[i, 1:3] / nb
+            else:
+                es[ns.nav] += w[i] * cols[i, 3]
+                es[ns.enumer] += w[i] * cols[i, 0]
+                es[ns.e1b:ns.e2b + 1] += w[i] * cols[i, 1:3]
+            es[ns.edenom] += w[i]                                       # (with average_gf: this package's, see the module)
+            es[ns.uweight] += uw[i]
+            es[ns.weight] += w[i]
+            es[ns.ovlp] += w[i] * 1.0                                   # walker.ot stays 1, walker.hybrid_energy 0
+        if self.calc_one_rdm:
+            self.rdm_acc += res['one_rdm']                              # mixed.py:226-229
+        if self.structure_factor:
+            self.sf_acc += res['two_rdm']                               # mixed.py:230-233
 
     def arm_rdm(self, dev):
         """one_rdm: True -> the device accumulates weight * walker.G.real with every estimator update."""
@@ -205,8 +258,10 @@ class Mixed(object):
             self.blocks.append(numpy.array(row))
             if self.structure_factor:
                 # the energy's estimator per momentum transfer: the block's sums over its (global) energy denominator
+                # (thermal: the reference's own rdm / nsteps / Weight, mixed.py:284-287)
                 with numpy.errstate(divide='ignore', invalid='ignore'):
-                    self.two_rdm.append(self.sf_acc / gs[ns.edenom].real)
+                    self.two_rdm.append(self.sf_acc / nsteps / gs[ns.weight].real if self.thermal
+                                        else self.sf_acc / gs[ns.edenom].real)
             if self.calc_one_rdm:                               # mixed.py:279-283
                 rdm = self.rdm_acc / nsteps / gs[ns.weight].real
                 self.one_rdm.append(rdm)

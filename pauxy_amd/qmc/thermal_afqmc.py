@@ -96,7 +96,9 @@ class ThermalAFQMC(object):
         est_opts = _opt(options, 'estimators', ['estimates'])
         if est_opts.get('back_propagation', est_opts.get('back_propagated')) is not None or est_opts.get('itcf') is not None:
             raise NotImplementedError("ThermalAFQMC: back-propagation and ITCF are not supported with a thermal trial")
-        self.estimators = Estimators(est_opts, self.root, self.qmc, system, trial, self.propagators.BT_BP, verbose)
+        # (thermal_sweep: the mixed estimator takes average_gf, one_rdm and two_rdm: 'structure_factor')
+        self.estimators = Estimators(est_opts, self.root, self.qmc, system, trial, self.propagators.BT_BP, verbose,
+                                     thermal_sweep=True)
         if self.qmc.nstblz != self.propagators.nstblz:                      # thermal_afqmc.py:179-181
             self.propagators.nstblz = self.qmc.nstblz
         self.setup_timers()

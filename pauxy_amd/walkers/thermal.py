@@ -91,9 +91,17 @@ class ThermalWalkerView(object):
         self._h.recompute_greens_function(trial, slice_ix)
 
     def local_energy(self, system, two_rdm=None):
-        if two_rdm is not None:
-            raise NotImplementedError("thermal walkers: no two_rdm")
+        """(E, T, V) of this walker's G.  ``two_rdm`` (UEG): an array [2, 2, nq] that receives the pair sums of
+        P = I - G^T per momentum transfer, what local_energy_ueg(system, P, two_rdm=...) fills (walkers/thermal.py:545-547)."""
         self._h.ensure_configured()
+        if two_rdm is not None:
+            if system.name != "UEG":
+                raise NotImplementedError("thermal walkers: two_rdm is the structure factor of the UEG")
+            G = self.G
+            P = numpy.array([numpy.eye(G.shape[-1]) - G[s].T for s in range(2)])
+            E, two = self._h.dev.ueg_pair_sums(P[None])
+            two_rdm[...] = two[0]
+            return tuple(E[0].real)
         E, _ = self._h.dev.thermal_energy()
         return tuple(E[self.index])
 
