@@ -666,6 +666,7 @@ int afq_estimates_get_end(afq_handle *h, double *est_out /* c128[10] */);
 #define AFQ_THERMAL_LOW_RANK        4
 #define AFQ_THERMAL_AVERAGE_GF      8
 #define AFQ_THERMAL_STREAMED_GREENS 16  /* honoured by afq_thermal_configure_continuous (below), refused here by name */
+#define AFQ_THERMAL_WIDE            32  /* honoured by the two continuous entry points (below), refused here by name */
 int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int nstblz, const double *BT,
                           const double *BT_inv, const double *BH1, const double *auxf, int options);
 int afq_thermal_reset(afq_handle *h);
@@ -688,7 +689,7 @@ int afq_thermal_state(afq_handle *h, int32_t *out4);
  * ONE_RDM: one_rdm_out f64[2, M, M] = sum_w weight_w Re G_w of the G the call leaves, every walker in walker order.
  * TWO_RDM (UEG): two_rdm_out f64[2, 2, nq] = sum_w weight_w Re two_rdm[P_w] of the same G, from the pair sums of the
  * energy launch.  AFQ_ESTATE: no thermal configuration; AFQ_EINVAL: unknown bits in what, a needed output NULL;
- * AFQ_EUNSUPPORTED: TWO_RDM on a Hubbard handle. */
+ * AFQ_EUNSUPPORTED: TWO_RDM on a Hubbard handle; AVERAGE_GF on a handle configured with AFQ_THERMAL_WIDE. */
 #define AFQ_THERMAL_EST_AVERAGE_GF 1
 #define AFQ_THERMAL_EST_ONE_RDM    2
 #define AFQ_THERMAL_EST_TWO_RDM    4   /* UEG walkers only: AFQ_EUNSUPPORTED otherwise */
@@ -708,6 +709,17 @@ int afq_thermal_set_sweep_budget(afq_handle *h, size_t bytes);
  * bits.  The bound is then the smallest of the slice kernel's 48 M (M | 1) bytes of LDS, the streamed kernel's LDS and
  * the 64 lanes of a wave: M <= 57, the next shell.  The bit is honoured, not refused; above the bound the call is
  * refused with M, the kernel that does not fit, its bytes and the bound.  Without the bit nothing changes.
+ * With AFQ_THERMAL_WIDE the handle takes a third route instead (the two bits together are AFQ_EINVAL): the Green's
+ * function (thermal_cgreens_wide_kernel) and the slice kernel (thermal_cslice_wide_kernel, Hubbard:
+ * thermal_cslice_dense_wide_kernel) keep ONE complex matrix of 16 M (M | 1) bytes in LDS, a lane owns two columns, and
+ * everything else lives in nw * 2 * 4 * M^2 * 16 bytes of device memory of the handle's.  The bound is the Green's
+ * kernel's 16 (M (M | 1) + 1152) + 512 bytes of LDS: M <= 95 = afq_thermal_wide_max_basis(), which holds the shells of
+ * 81 and 93 plane waves (138,384 + 18,944 bytes at M = 93) and the 8 x 8 and 9 x 9 Hubbard lattices.  The same
+ * algorithm, carried differently (reflectors applied in place of an accumulated Q, LU and substitution in place of
+ * Gauss-Jordan): G and det G agree with the other two routes to rounding, not to the bit; the slice kernels' right and
+ * bins are the same bits.  afq_thermal_reset / _greens / _energy / _state, the comb, afq_walkers_copy and the pack
+ * serve a wide handle; afq_thermal_estimates runs ONE_RDM and TWO_RDM on it and refuses AVERAGE_GF by name
+ * (AFQ_EUNSUPPORTED: the wide route has no sweep kernel yet).
  *   afq_thermal_configure_continuous  after afq_set_system_ueg (index lists over ALL plane waves, for the energy) and
  *                          afq_walkers_alloc; no trial determinant, no afq_set_propagator.  BT, BT_inv, BH1
  *                          f64[2, M, M]: the trial's dmat and its inverse (diagonal) and
@@ -718,7 +730,7 @@ int afq_thermal_set_sweep_budget(afq_handle *h, size_t bytes);
  *                          AFQ_THERMAL_* bits of what the caller was asked for, refused by name.  Ends with
  *                          afq_thermal_reset.  AFQ_EUNSUPPORTED: the option bits, a system that is not the UEG,
  *                          M > 47 (the message carries M and the bytes; M > 57 with
- *                          AFQ_THERMAL_STREAMED_GREENS), a trial that is not diagonal, more than
+ *                          AFQ_THERMAL_STREAMED_GREENS, M > 95 with AFQ_THERMAL_WIDE), a trial that is not diagonal, more than
  *                          one rank, back-propagation / ITCF / mixed RDM on the handle.
  *   afq_thermal_propagate_continuous  one time slice of every walker, dead ones included: P = I - G^T,
  *                          xbar = -sqrt(dt) P.[iA | iB] (|xbar_i| > fb_bound: unit modulus), xs = xi - xbar, cmf = -sqrt(dt) xs.mf_shift,
@@ -740,6 +752,8 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
                                      const double *BT_inv, const double *BH1, const double *mf_shift, double fb_bound,
                                      int options);
 int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi_out);
+/* the largest M a handle configured with AFQ_THERMAL_WIDE admits (no handle, no device) */
+int afq_thermal_wide_max_basis(void);
 
 /* ---- finite-temperature AFQMC with continuous fields: thermal walkers of the Hubbard model --------------------
  * thermal_propagation/continuous.py:84-120,202-257 (Continuous, phaseless, force bias, hybrid weight) with
@@ -751,8 +765,9 @@ int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi
  *                          expm(-dt/2 (h1e_mod - i sqrt(U) diag(mf_shift) + sign mu)); mf_shift c128[M] =
  *                          i sqrt(U) diag(P_up + P_dn) of the trial; mf_const_fac c128[1] = exp(-dt mf_shift.mf_shift / 2).
  *                          left_k = BT^stack_size BT_inv^(k + 1) is built on the host in the reference's order.
- *                          options: AFQ_THERMAL_STREAMED_GREENS is honoured, the other AFQ_THERMAL_* bits are
- *                          refused by name.  The bound on M is the smallest of the slice kernel's
+ *                          options: AFQ_THERMAL_STREAMED_GREENS or AFQ_THERMAL_WIDE is honoured (both: AFQ_EINVAL; with
+ *                          WIDE the bound is M <= 95, as above), the other AFQ_THERMAL_* bits are
+ *                          refused by name.  Without WIDE the bound on M is the smallest of the slice kernel's
  *                          40 M (M | 1) + 1024 bytes of LDS (M <= 63), the Green's kernel's (M <= 47 resident, 64
  *                          streamed) and the 64 lanes of a wave: M <= 47, and M <= 63 with the bit.  Above it
  *                          AFQ_EUNSUPPORTED names M, the kernel that does not fit, its bytes and the bound.  Also

@@ -1454,6 +1454,15 @@ int afq_walker_pack_bytes(afq_handle *h, int64_t *bytes) {
     return AFQ_OK;
 }
 
+// What copy, pack and unpack ask first: a thermal handle has no trial determinant, its configuration stands in for one
+// (the walker table then holds G, the bins, right and M0, as the header says of these three calls).
+static int need_walkers(afq_handle *h) {
+    if (!th_thermal(h) || !h->nw) return need_ready(h, false);
+    if (h->prop_pending) AFQ_FAIL(h, AFQ_ESTATE, "a step is half done: afq_propagate_finish first");
+    hipSetDevice(h->device);
+    return AFQ_OK;
+}
+
 static int pack_io(afq_handle *h, int iw, char *buf, bool pack) {
     const WalkerFields f = walker_fields(h, WF_WEIGHT);
     long off = 0;
@@ -1469,7 +1478,7 @@ static int pack_io(afq_handle *h, int iw, char *buf, bool pack) {
 
 int afq_walker_pack(afq_handle *h, int iw, void *dev_buf) {
     if (!h || !dev_buf) return AFQ_EINVAL;
-    int rc = need_ready(h, false);
+    int rc = need_walkers(h);
     if (rc) return rc;
     if (iw < 0 || iw >= h->nw) AFQ_FAIL(h, AFQ_EINVAL, "walker index out of range");
     return pack_io(h, iw, (char *)dev_buf, true);
@@ -1478,7 +1487,7 @@ int afq_walker_pack(afq_handle *h, int iw, void *dev_buf) {
 int afq_walker_unpack(afq_handle *h, int iw, const void *dev_buf) {
     if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h || !dev_buf) return AFQ_EINVAL;
-    int rc = need_ready(h, false);
+    int rc = need_walkers(h);
     if (rc) return rc;
     if (iw < 0 || iw >= h->nw) AFQ_FAIL(h, AFQ_EINVAL, "walker index out of range");
     return pack_io(h, iw, (char *)dev_buf, false);
@@ -1487,7 +1496,7 @@ int afq_walker_unpack(afq_handle *h, int iw, const void *dev_buf) {
 int afq_walkers_copy(afq_handle *h, int src, int dst) {
     if (h) { h->gf.drop(); h->handover.drop(); }
     if (!h) return AFQ_EINVAL;
-    int rc = need_ready(h, false);
+    int rc = need_walkers(h);
     if (rc) return rc;
     if (src < 0 || dst < 0 || src >= h->nw || dst >= h->nw) AFQ_FAIL(h, AFQ_EINVAL, "walker index out of range");
     if (src == dst) return AFQ_OK;

@@ -285,7 +285,9 @@ struct afq_handle {
     double *thc_left = nullptr;     // [stack_size, ..] left_k = BT^stack_size BT_inv^(k + 1)
     double *thc_bh1 = nullptr;      // BH1
     bool thc_streamed = false;      // AFQ_THERMAL_STREAMED_GREENS: every Green's function by the streamed kernel
-    cplx *thc_tscratch = nullptr;   // [nw, 2, 2, M, M] T of the streamed kernel, two buffers per work-group (else null)
+    bool thc_wide = false;          // AFQ_THERMAL_WIDE: the wide Green's function and slice kernels (one matrix in LDS)
+    cplx *thc_tscratch = nullptr;   // [nw, 2, 2, M, M] T of the streamed kernel, two buffers per work-group; wide:
+                                    // [nw, 2, 4, M, M], four per work-group (else null)
     // the dense trial's alone (afq_thermal_configure_hubbard_continuous)
     double thd_mf_const[2] = {1.0, 0.0};   // exp(-dt mf_core) (re, im)
     double thd_sqrt_u = 0.0;        // iu_fac = i sqrt(U)

@@ -317,6 +317,8 @@ int afq_thermal_estimates(afq_handle *h, int what, double *cols_out, double *per
     if (two && h->th_kind != TH_CPLX_DIAG)
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "afq_thermal_estimates: two_rdm is the structure factor of the UEG walkers (no Hubbard)");
     const bool cx = th_complex(h);
+    if (avg && cx && h->thc_wide)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "afq_thermal_estimates: average_gf is not supported on a wide_basis handle (AFQ_THERMAL_WIDE has no sweep kernel)");
     const int M = h->M, nw = h->nw, nbins = h->th_nbins, nbt = avg ? nbins : 1;
     const size_t mm = (size_t)M * M, n = nw, nq4 = two ? 4 * (size_t)h->nq : 0;
     // the small results, fetched in one copy: cols [nw, 4], per_bin [nbt, nw, 4], one_rdm [2, M, M], two_rdm c128 [2, 2, nq];

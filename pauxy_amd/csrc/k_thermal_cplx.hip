@@ -6,10 +6,15 @@
 // handle's, as for the real walkers of k_thermal.hip.  A walker's working set stays in LDS: 4 complex matrices of pitch
 // M | 1, which the 160 KiB of a compute unit hold up to M = 47 (the plane-wave shells: 7, 19, 27, 33; 57 does not fit).
 // With AFQ_THERMAL_STREAMED_GREENS the Green's function keeps 2 matrices in LDS and T in the handle's thc_tscratch; the
-// bound is then the slice kernel's three matrices: M = 57, the next shell.  81 is refused either way.
+// bound is then the slice kernel's three matrices: M = 57, the next shell.  81 is refused on both of these routes.
+// With AFQ_THERMAL_WIDE the handle takes a third route: thermal_wide.h's engine and the two wide slice kernels below
+// keep ONE complex matrix in LDS and the rest in thc_tscratch, and a lane owns two columns: M <= 95, which holds the
+// shells of 81 and 93 plane waves and the Hubbard lattices to 9 x 9.
 //
 //   thermal_cgreens_kernel  G and det G of every (walker, spin) from the stack: thermal_strat.h's engine with T = cplx.
 //   thermal_cgreens_streamed_kernel  the same from thermal_strat.h's streamed form, for a handle configured with the bit.
+//   thermal_cgreens_wide_kernel  thermal_wide.h's engine, for a handle configured with AFQ_THERMAL_WIDE.
+//   thermal_cslice_wide_kernel, thermal_cslice_dense_wide_kernel  the two slice kernels below with one matrix in LDS.
 //   thermal_cslice_kernel   one work-group per walker: BV = sum_{n <= 6} VHS^n / n! by five Horner products in LDS,
 //                           once for both spins; per spin B = diag(BH1) BV diag(BH1), right <- B right (right = I at
 //                           in-bin counter 0), bin[block] = diag(left_k) right.
@@ -27,6 +32,7 @@
 //                                 Green's function the bound stays 47.
 //   thermal_cweight_mf_kernel     the weight update with the constant of the mean-field shift.
 #include "thermal_strat.h"
+#include "thermal_wide.h"
 #include <cstring>
 
 #define THC_LDS_MAX (160 * 1024)
@@ -86,6 +92,62 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_kernel(ThcSliceArgs
             const cplx x = T2[r * LD + c];
             R[e] = x;
             S[e] = cscale(x, lf[r]);
+        }
+        __syncthreads();
+    }
+}
+
+// thermal_cslice_kernel with one matrix in LDS (AFQ_THERMAL_WIDE): V, the A operand of all five Horner products, stays
+// in LDS; the Horner iterates T_n live in two [M, M] buffers of the walker's scratch in device memory, used in turn (a
+// work-group reads back only what it wrote, across a barrier).  Behind the Horner chain BV takes V's place in LDS as the
+// A operand of right <- B right.  Every element goes through thermal_cslice_kernel's operations in their order -- the
+// same ts_gemm with other loaders -- so the two kernels give the same bits where both run.
+inline size_t thc_slice_wide_lds(int M) { return sizeof(cplx) * ts_mat(M); }
+
+__global__ __launch_bounds__(TH_THREADS) void thermal_cslice_wide_kernel(ThcSliceArgs a, cplx *scratch, long stride) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int M = a.M, LD = M | 1, tid = threadIdx.x, w = blockIdx.x;
+    cplx *V = (cplx *)smem;
+    const long mm = (long)M * M;
+    cplx *T1 = scratch + (long)w * stride, *T2 = T1 + mm;           // pitch M
+    const cplx *Vw = a.vhs + (long)w * mm;
+    for (int e = tid; e < M * M; e += TH_THREADS) {
+        const int r = e / M, c = e % M;
+        const cplx x = Vw[e];
+        V[r * LD + c] = x;
+        T1[e] = cmake(x.x / 6.0 + (r == c ? 1.0 : 0.0), x.y / 6.0);
+    }
+    __syncthreads();
+    for (int n = 5; n >= 1; --n) {
+        const double dn = (double)n;
+        ts_gemm<cplx>(M, [&](int r, int k) { return V[r * LD + k]; }, [&](int k, int c) { return T1[k * M + c]; },
+                 [&](int r, int c, cplx x) { T2[r * M + c] = cmake(x.x / dn + (r == c ? 1.0 : 0.0), x.y / dn); });
+        __syncthreads();
+        cplx *t = T1; T1 = T2; T2 = t;
+    }
+    for (int e = tid; e < M * M; e += TH_THREADS) V[(e / M) * LD + e % M] = T1[e];
+    __syncthreads();
+    const cplx *BV = V;
+    for (int s = 0; s < 2; ++s) {
+        const double *d = a.bh1 + s * M, *lf = a.left + s * M;
+        cplx *R = a.right + ((long)w * 2 + s) * mm;
+        cplx *S = a.stack + (((long)w * a.nbins + a.block) * 2 + s) * mm;
+        if (a.counter == 0) {
+            for (int e = tid; e < M * M; e += TH_THREADS) {
+                const int r = e / M, c = e % M;
+                const cplx x = cscale(cscale(BV[r * LD + c], d[c]), d[r]);
+                R[e] = x;
+                S[e] = cscale(x, lf[r]);
+            }
+            continue;
+        }
+        ts_gemm<cplx>(M, [&](int r, int k) { return cscale(cscale(BV[r * LD + k], d[k]), d[r]); },
+                 [&](int k, int c) { return R[k * M + c]; }, [&](int r, int c, cplx x) { T2[r * M + c] = x; });
+        __syncthreads();
+        for (int e = tid; e < M * M; e += TH_THREADS) {
+            const cplx x = T2[e];
+            R[e] = x;
+            S[e] = cscale(x, lf[e / M]);
         }
         __syncthreads();
     }
@@ -289,6 +351,51 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_dense_kernel(ThdSli
     }
 }
 
+// thermal_cslice_dense_kernel with one staging matrix in LDS (AFQ_THERMAL_WIDE), which holds in turn BH1_s (real, the
+// operand of both products that make B_s), B_s (the A operand of right <- B right) and the new right (the B operand of
+// left_k right); B_s and the new right pass through two [M, M] buffers of the walker's scratch in device memory.  The
+// products are thermal_cslice_dense_kernel's with other loaders: the same bits where both run.
+inline size_t thd_slice_wide_lds(int M) { return sizeof(cplx) * (ts_mat(M) + TW_COLS); }
+
+__global__ __launch_bounds__(TH_THREADS) void thermal_cslice_dense_wide_kernel(ThdSliceArgs a, cplx *scratch, long stride) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int M = a.M, LD = M | 1, tid = threadIdx.x, w = blockIdx.x;
+    const size_t mat = ts_mat(M);
+    cplx *Z = (cplx *)smem, *bv = Z + mat;
+    double *H = (double *)Z;
+    const long mm = (long)M * M;
+    cplx *B0 = scratch + (long)w * stride, *B1 = B0 + mm;           // pitch M
+    if (tid < M) bv[tid] = a.bv[(long)w * M + tid];
+    for (int s = 0; s < 2; ++s) {
+        const double *Hs = a.bh1 + s * mm, *lf = a.left + s * mm;
+        cplx *R = a.right + ((long)w * 2 + s) * mm;
+        cplx *S = a.stack + (((long)w * a.nbins + a.block) * 2 + s) * mm;
+        for (int e = tid; e < M * M; e += TH_THREADS) H[(e / M) * LD + e % M] = Hs[e];
+        __syncthreads();
+        thd_gemm_rc(M, [&](int r, int k) { return H[r * LD + k]; }, [&](int k, int c) { return cscale(bv[k], H[k * LD + c]); },
+                    [&](int r, int c, cplx x) { B0[r * M + c] = x; });
+        __syncthreads();
+        const cplx *Rn = B0;
+        if (a.counter != 0) {
+            for (int e = tid; e < M * M; e += TH_THREADS) Z[(e / M) * LD + e % M] = B0[e];
+            __syncthreads();
+            ts_gemm<cplx>(M, [&](int r, int k) { return Z[r * LD + k]; }, [&](int k, int c) { return R[k * M + c]; },
+                          [&](int r, int c, cplx x) { B1[r * M + c] = x; });
+            __syncthreads();
+            Rn = B1;
+        }
+        for (int e = tid; e < M * M; e += TH_THREADS) {
+            const cplx x = Rn[e];
+            R[e] = x;
+            Z[(e / M) * LD + e % M] = x;
+        }
+        __syncthreads();
+        thd_gemm_rc(M, [&](int r, int k) { return lf[r * M + k]; }, [&](int k, int c) { return Z[k * LD + c]; },
+                    [&](int r, int c, cplx x) { S[r * M + c] = x; });
+        __syncthreads();
+    }
+}
+
 // continuous.py:97-115 with hubbard.py:241-250 for one walker per work-group: vbias_i = i sqrt(U) (P_up,ii + P_dn,ii)
 // from the diagonal of P [nw, 2, M, M], xbar = -sqrt(dt) (vbias - mf) clipped at 1, xs, cmf, cfb as
 // thermal_cfields_kernel makes them, and the diagonal of BV: bv_i = sum_{n <= 6} v^n / n!, v = sqrt(dt) i sqrt(U) xs_i,
@@ -345,6 +452,8 @@ __global__ void thermal_creset_kernel(cplx *stack, cplx *G, cplx *right, cplx *M
 
 // G and det of nblocks / 2 walkers by the engine the handle was configured with
 static int thc_launch_greens(afq_handle *h, cplx *G, cplx *det, int first, int src_w, int nblocks) {
+    if (h->thc_wide)
+        return ts_launch_greens_wide(h, h->thc_stack, G, det, h->thc_tscratch, first, src_w, nblocks);
     if (h->thc_streamed)
         return ts_launch_greens_streamed<cplx>(h, h->thc_stack, G, det, h->thc_tscratch, first, src_w, nblocks);
     return ts_launch_greens<cplx>(h, h->thc_stack, G, det, first, src_w, nblocks);
@@ -403,31 +512,47 @@ struct ThcLds {
 };
 const char *const THC_RESIDENT_HINT = "; AFQ_THERMAL_STREAMED_GREENS (streamed_greens) keeps T in device memory and reaches further";
 
+// Which Green's function and slice kernels a handle runs: chosen by the option bits of its configuration.
+enum ThcRoute { THC_RESIDENT, THC_STREAMED, THC_WIDE };
+
+// STREAMED_GREENS and WIDE name two placements of the same working set: together they mean nothing
+int thc_route_of(afq_handle *h, const std::string &me, int options, ThcRoute *route) {
+    const bool streamed = (options & AFQ_THERMAL_STREAMED_GREENS) != 0, wide = (options & AFQ_THERMAL_WIDE) != 0;
+    if (streamed && wide)
+        AFQ_FAIL(h, AFQ_EINVAL, me + "wide_basis and streamed_greens are two placements of the same matrices: ask for one");
+    *route = wide ? THC_WIDE : streamed ? THC_STREAMED : THC_RESIDENT;
+    return AFQ_OK;
+}
+
+const ThcLds THC_WIDE_GREENS = {"the wide Green's function (thermal_cgreens_wide_kernel)", ts_greens_wide_lds, ""};
+
 // M within what every kernel of `need` and lane = column hold; else the refusal names the first of them that does not
 // fit, with its bytes, and the largest M that passes.  who: "" or ", Hubbard"; unit: what M counts.
-int thc_screen_bound(afq_handle *h, const char *who, const char *unit, bool streamed, std::initializer_list<ThcLds> need) {
+int thc_screen_bound(afq_handle *h, const char *who, const char *unit, ThcRoute route, std::initializer_list<ThcLds> need) {
+    const int lanes = route == THC_WIDE ? TW_COLS : THC_LANES;       // (wide: two columns per lane)
     auto fits = [&](int m) {
         for (const ThcLds &k : need)
             if (k.bytes(m) > THC_LDS_MAX) return false;
-        return m <= THC_LANES;
+        return m <= lanes;
     };
     const int M = h->M;
     if (fits(M)) return AFQ_OK;
     int mmax = M;
     while (mmax > 1 && !fits(mmax)) --mmax;
-    const std::string head = std::string("thermal walkers with continuous fields") + who + (streamed ? " (streamed_greens)" : "") +
+    const std::string head = std::string("thermal walkers with continuous fields") + who + (route == THC_STREAMED ? " (streamed_greens)" : route == THC_WIDE ? " (wide_basis)" : "") +
                              ": M = " + std::to_string(M) + " " + unit + " ";
     const std::string tail = " (M <= " + std::to_string(mmax) + ")";
     for (const ThcLds &k : need)
         if (k.bytes(M) > THC_LDS_MAX)
             AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(k.bytes(M)) + " bytes of LDS for " + k.what +
                      ", a work-group has " + std::to_string(THC_LDS_MAX) + tail + k.hint);
-    AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "are more than the " + std::to_string(THC_LANES) + " lanes of a wave, one per column" + tail);
+    AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "are more than the " + (route == THC_WIDE ? std::to_string(TW_COLS) + " columns of a wave, two per lane"
+                                                                          : std::to_string(THC_LANES) + " lanes of a wave, one per column") + tail);
 }
 
 // Behind an entry point's own checks: its host-built tables (`per` numbers per slice: 2 M diagonals or 2 M M), the
 // walkers' buffers, the path's shape, the kind, and a fresh population.
-int thc_configure_common(afq_handle *h, ThKind kind, int ntime_slices, int stack_size, double dt, bool streamed, double fb_bound,
+int thc_configure_common(afq_handle *h, ThKind kind, int ntime_slices, int stack_size, double dt, ThcRoute route, double fb_bound,
                          const double *BTpow, const double *left, const double *bh1, size_t per, const double *mf_shift) {
     const size_t mm = (size_t)h->M * h->M, n = h->nw;
     const int nbins = ntime_slices / stack_size;
@@ -440,9 +565,12 @@ int thc_configure_common(afq_handle *h, ThKind kind, int ntime_slices, int stack
         (rc = dev_alloc(h, LT_WALKERS, &h->thc_stack, 2 * mm * n * nbins)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_right, 2 * mm * n)) ||
         (rc = dev_alloc(h, LT_WALKERS, &h->thc_M0, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_M00, (size_t)2)) ||
         (rc = dev_alloc(h, LT_WALKERS, &h->thc_det, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_nav, n))) return rc;
-    // T of the streamed Green's kernel, two buffers per (walker, spin); a handle configured without it holds none
-    if ((rc = dev_alloc(h, LT_WALKERS, &h->thc_tscratch, streamed ? 4 * mm * n : (size_t)0))) return rc;
-    h->thc_streamed = streamed;
+    // T of the streamed Green's kernel, two buffers per (walker, spin); the wide route's scratch, four per (walker,
+    // spin), of which the wide slice kernels use the walker's first two; a handle configured without either holds none
+    const size_t tscratch = route == THC_STREAMED ? 4 * mm * n : route == THC_WIDE ? 2 * ts_greens_wide_scratch(h->M) * n : (size_t)0;
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->thc_tscratch, tscratch))) return rc;
+    h->thc_streamed = route == THC_STREAMED;
+    h->thc_wide = route == THC_WIDE;
     if ((rc = ensure_G(h))) return rc;                  // c128 [nw, 2, M, M]: the one-body density matrices
     h->thc_fb_bound = fb_bound;
     h->dt = dt; h->sqrt_dt = std::pow(dt, 0.5);        // (the handle's time step, as afq_set_propagator sets it)
@@ -466,6 +594,15 @@ int thc_slice_diag(afq_handle *h) {
     a.vhs = h->vhs; a.right = h->thc_right; a.stack = h->thc_stack; a.bh1 = h->thc_bh1;
     a.left = h->thc_left + (size_t)h->th_counter * 2 * M;
     a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
+    if (h->thc_wide) {
+        static size_t lds_set[AFQ_MAX_DEVICES] = {0};
+        const size_t lds = thc_slice_wide_lds(M);
+        AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_wide_kernel, lds, lds_set));
+        AFQ_LAUNCH(h, thermal_cslice_wide_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a, h->thc_tscratch,
+                   (long)(2 * ts_greens_wide_scratch(M)));
+        AFQ_POST(h);
+        return AFQ_OK;
+    }
     static size_t lds_set[AFQ_MAX_DEVICES] = {0};
     const size_t lds = thc_slice_lds(M);
     AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_kernel, lds, lds_set));
@@ -485,6 +622,15 @@ int thc_slice_dense(afq_handle *h) {
     a.bv = h->vhs; a.right = h->thc_right; a.stack = h->thc_stack; a.bh1 = h->thc_bh1;
     a.left = h->thc_left + (size_t)h->th_counter * 2 * M * M;
     a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
+    if (h->thc_wide) {
+        static size_t lds_set[AFQ_MAX_DEVICES] = {0};
+        const size_t lds = thd_slice_wide_lds(M);
+        AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_dense_wide_kernel, lds, lds_set));
+        AFQ_LAUNCH(h, thermal_cslice_dense_wide_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a, h->thc_tscratch,
+                   (long)(2 * ts_greens_wide_scratch(M)));
+        AFQ_POST(h);
+        return AFQ_OK;
+    }
     static size_t lds_set[AFQ_MAX_DEVICES] = {0};
     const size_t lds = thd_slice_lds(M);
     AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_dense_kernel, lds, lds_set));
@@ -515,18 +661,22 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
     AFQ_API(h, "afq_thermal_configure_continuous");
     if (!h) return AFQ_EINVAL;
     h->th_kind = TH_NONE;
-    const ThEntry me = {"afq_thermal_configure_continuous: ", AFQ_THERMAL_STREAMED_GREENS, AFQ_EINVAL,
+    const ThEntry me = {"afq_thermal_configure_continuous: ", AFQ_THERMAL_STREAMED_GREENS | AFQ_THERMAL_WIDE, AFQ_EINVAL,
                         "afq_thermal_configure_continuous: charge_decomposition belongs to the discrete fields", AFQ_SYS_UEG,
                         "thermal walkers with continuous fields: UEG systems only (no Generic, no continuous Hubbard)", "both"};
     if (!BT || !BT_inv || !BH1 || !mf_shift) AFQ_FAIL(h, AFQ_EINVAL, me.me + "null operand");
     AFQ_TRY(th_screen_options(h, me, options));
-    const bool streamed = (options & AFQ_THERMAL_STREAMED_GREENS) != 0;
+    ThcRoute route;
+    AFQ_TRY(thc_route_of(h, me.me, options, &route));
     const ThcLds slice = {"the slice kernel (thermal_cslice_kernel)", thc_slice_lds, ""};
-    if (streamed)
-        AFQ_TRY(thc_screen_bound(h, "", "plane waves", true, {slice,
+    if (route == THC_WIDE)
+        AFQ_TRY(thc_screen_bound(h, "", "plane waves", route, {THC_WIDE_GREENS,
+                {"the wide slice kernel (thermal_cslice_wide_kernel)", thc_slice_wide_lds, ""}}));
+    else if (route == THC_STREAMED)
+        AFQ_TRY(thc_screen_bound(h, "", "plane waves", route, {slice,
                 {"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}}));
     else
-        AFQ_TRY(thc_screen_bound(h, "", "plane waves", false, {{"the complex Green's function", ts_greens_lds<cplx>, THC_RESIDENT_HINT}, slice}));
+        AFQ_TRY(thc_screen_bound(h, "", "plane waves", route, {{"the complex Green's function", ts_greens_lds<cplx>, THC_RESIDENT_HINT}, slice}));
     AFQ_TRY(th_screen_state(h, me, ntime_slices, stack_size, 1));
     if (!(dt > 0.0) || !(fb_bound >= 0.0)) AFQ_FAIL(h, AFQ_EINVAL, me.me + "dt must be positive, fb_bound not negative");
     const int M = h->M;
@@ -550,8 +700,14 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
             for (int k = 0; k < stack_size; ++k) { p = p * bi; left[((size_t)k * 2 + s) * M + i] = p; }
             bh[(size_t)s * M + i] = BH1[s * mm + (size_t)i * M + i];
         }
-    return thc_configure_common(h, TH_CPLX_DIAG, ntime_slices, stack_size, dt, streamed, fb_bound, pw.data(), left.data(),
+    return thc_configure_common(h, TH_CPLX_DIAG, ntime_slices, stack_size, dt, route, fb_bound, pw.data(), left.data(),
                                 bh.data(), 2 * (size_t)M, mf_shift);
+}
+
+int afq_thermal_wide_max_basis(void) {
+    int m = TW_COLS;
+    while (m > 1 && (ts_greens_wide_lds(m) > THC_LDS_MAX || thc_slice_wide_lds(m) > THC_LDS_MAX || thd_slice_wide_lds(m) > THC_LDS_MAX)) --m;
+    return m;
 }
 
 int afq_thermal_left_table(int M, int stack_size, const double *BT, const double *BT_inv, double *BTpow_out, double *left_out) {
@@ -566,17 +722,20 @@ int afq_thermal_configure_hubbard_continuous(afq_handle *h, int ntime_slices, in
     AFQ_API(h, "afq_thermal_configure_hubbard_continuous");
     if (!h) return AFQ_EINVAL;
     h->th_kind = TH_NONE;
-    const ThEntry me = {"afq_thermal_configure_hubbard_continuous: ", AFQ_THERMAL_STREAMED_GREENS, AFQ_EINVAL,
+    const ThEntry me = {"afq_thermal_configure_hubbard_continuous: ", AFQ_THERMAL_STREAMED_GREENS | AFQ_THERMAL_WIDE, AFQ_EINVAL,
                         "afq_thermal_configure_hubbard_continuous: charge_decomposition belongs to the discrete fields (the "
                         "continuous form is the charge form alone)", AFQ_SYS_HUBBARD,
                         "thermal walkers with continuous fields and a dense trial: Hubbard systems only (no Generic)", "both"};
     if (!BT || !BT_inv || !BH1 || !mf_shift || !mf_const_fac) AFQ_FAIL(h, AFQ_EINVAL, me.me + "null operand");
     AFQ_TRY(th_screen_options(h, me, options));
-    const bool streamed = (options & AFQ_THERMAL_STREAMED_GREENS) != 0;
-    const ThcLds greens = streamed ? ThcLds{"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}
+    ThcRoute route;
+    AFQ_TRY(thc_route_of(h, me.me, options, &route));
+    const bool streamed = route == THC_STREAMED;
+    const ThcLds greens = route == THC_WIDE ? THC_WIDE_GREENS : streamed ? ThcLds{"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}
                                    : ThcLds{"the complex Green's function (thermal_cgreens_kernel)", ts_greens_lds<cplx>, THC_RESIDENT_HINT};
-    AFQ_TRY(thc_screen_bound(h, ", Hubbard", "sites", streamed,
-                             {greens, {"the slice kernel (thermal_cslice_dense_kernel)", thd_slice_lds, ""}}));
+    const ThcLds slice = route == THC_WIDE ? ThcLds{"the wide slice kernel (thermal_cslice_dense_wide_kernel)", thd_slice_wide_lds, ""}
+                                           : ThcLds{"the slice kernel (thermal_cslice_dense_kernel)", thd_slice_lds, ""};
+    AFQ_TRY(thc_screen_bound(h, ", Hubbard", "sites", route, {greens, slice}));
     AFQ_TRY(th_screen_state(h, me, ntime_slices, stack_size, 1));
     if (!(dt > 0.0)) AFQ_FAIL(h, AFQ_EINVAL, me.me + "dt must be positive");
     if (!(h->U >= 0.0)) AFQ_FAIL(h, AFQ_EINVAL, me.me + "U must not be negative (iu_fac = i sqrt(U))");
@@ -586,7 +745,7 @@ int afq_thermal_configure_hubbard_continuous(afq_handle *h, int ntime_slices, in
     thd_left_table(h->M, stack_size, BT, BT_inv, pw.data(), left.data());
     h->thd_mf_const[0] = mf_const_fac[0]; h->thd_mf_const[1] = mf_const_fac[1];
     h->thd_sqrt_u = std::pow(h->U, 0.5);
-    return thc_configure_common(h, TH_CPLX_DENSE, ntime_slices, stack_size, dt, streamed, 1.0, pw.data(), left.data(), BH1,
+    return thc_configure_common(h, TH_CPLX_DENSE, ntime_slices, stack_size, dt, route, 1.0, pw.data(), left.data(), BH1,
                                 2 * mm, mf_shift);
 }
 

@@ -16,12 +16,24 @@ from pauxy_amd.propagation.thermal_hubbard import thermal_constants
 from pauxy_amd.propagation.thermal_planewave import planewave_constants
 from pauxy_amd.trial_density import update_stack
 
-# The largest basis of the complex walkers by (kind, streamed_greens): what fits the 160 KiB of LDS of a work-group.
+def _wide_max_basis():
+    """The wide route's bound as the library computes it from ts_greens_wide_lds (thermal_wide.h); a library that does
+    not export it, or none built yet, leaves the literal: 16 (M (M | 1) + 1152) + 512 bytes within 160 KiB."""
+    try:
+        return int(L.load().afq_thermal_wide_max_basis())
+    except (L.AfqLibraryError, AttributeError):
+        return 95
+
+
+# The largest basis of the complex walkers by (kind, route): what fits the 160 KiB of LDS of a work-group.  The route is
+# streamed_greens (False / True) or 'wide' (walkers: {wide_basis: True}: one complex matrix in LDS, two columns per lane).
 MAX_BASIS = {
     ('planewave', False): 47,            # ts_greens_lds<cplx> (thermal_strat.h): four complex matrices
     ('planewave', True): 57,             # thc_slice_lds (k_thermal_cplx.hip): three complex matrices
+    ('planewave', 'wide'): _wide_max_basis(),             # ts_greens_wide_lds (thermal_wide.h): one complex matrix
     ('hubbard_continuous', False): 47,   # ts_greens_lds<cplx>
     ('hubbard_continuous', True): 63,    # thd_slice_lds (k_thermal_cplx.hip): two complex matrices and BH1
+    ('hubbard_continuous', 'wide'): _wide_max_basis(),    # ts_greens_wide_lds
 }
 # how the refusal speaks of a kind: whose walkers, what M counts, what the slice kernel keeps in LDS
 _BOUND_WORDS = {'planewave': ("thermal walkers", "plane waves", "three complex matrices"),
@@ -145,9 +157,19 @@ class ThermalWalkers(object):
                                       "walkers with discrete fields fit to M = 64 as they are; with "
                                       "hubbard_stratonovich: 'continuous' the driver announces the complex walkers, and "
                                       "walkers: {continuous_fields: True} does so by hand)")
+        # one complex matrix in LDS and two columns per lane (thermal_wide.h, AFQ_THERMAL_WIDE)
+        self.wide_basis = bool(walker_opts.get('wide_basis', False))
+        if self.wide_basis and self.kind == 'discrete':
+            raise NotImplementedError("thermal walkers: wide_basis belongs to the continuous fields (Hubbard walkers "
+                                      "with discrete fields work one lane per column, M <= 64; with "
+                                      "hubbard_stratonovich: 'continuous' the driver announces the complex walkers, and "
+                                      "walkers: {continuous_fields: True} does so by hand)")
+        if self.wide_basis and self.streamed_greens:
+            raise NotImplementedError("thermal walkers: wide_basis and streamed_greens are two placements of the same "
+                                      "matrices: ask for one")
         if self.kind != 'discrete':
             self._check_bound(self.kind, system.nbasis)
-        if system.nbasis > 64:
+        if system.nbasis > 64 and not self.wide_basis:
             raise NotImplementedError("thermal walkers: M = %d > 64 sites is not supported" % system.nbasis)
         self.nwalkers = qmc.nwalkers
         self.ntot_walkers = qmc.ntot_walkers
@@ -217,7 +239,7 @@ class ThermalWalkers(object):
         if self.configured is not None and self.time_slice != 0:
             raise RuntimeError("thermal walkers: %s changed in the middle of a path"
                                % _CHANGED[kind if self.configured[0] == kind else None])
-        configure(L.THERMAL_STREAMED_GREENS if self.streamed_greens else 0)
+        configure(L.THERMAL_WIDE if self.wide_basis else L.THERMAL_STREAMED_GREENS if self.streamed_greens else 0)
         self.kind, self.configured = kind, (kind, key)
 
     def _configure_discrete(self, prop):
@@ -225,6 +247,9 @@ class ThermalWalkers(object):
         if self.streamed_greens:
             raise NotImplementedError("thermal walkers: streamed_greens belongs to the continuous fields (Hubbard "
                                       "walkers with discrete fields fit to M = 64 as they are)")
+        if self.wide_basis:
+            raise NotImplementedError("thermal walkers: wide_basis belongs to the continuous fields (Hubbard walkers "
+                                      "with discrete fields work one lane per column, M <= 64)")
         nstblz = self.nstblz if prop is None else prop.nstblz
 
         def configure(options):
@@ -257,6 +282,13 @@ class ThermalWalkers(object):
 
     def _check_bound(self, kind, M):
         who, unit, slice_keeps = _BOUND_WORDS[kind]
+        if self.wide_basis:
+            bound = MAX_BASIS[kind, 'wide']
+            if M > bound:
+                raise NotImplementedError("%s: M = %d > %d %s is not supported with wide_basis (the wide Green's function "
+                                          "keeps one complex matrix of 16 M (M | 1) bytes and 18,944 bytes of vectors in the "
+                                          "160 KiB of LDS)" % (who, M, bound, unit))
+            return
         bound = MAX_BASIS[kind, self.streamed_greens]
         if M > bound:
             raise NotImplementedError("%s: M = %d > %d %s is not supported%s" % (

@@ -13,10 +13,12 @@ The kernels are timed with event pairs around every launch (afq_launch_trace) ov
   thermal_cgreens_kernel         the complex stratified G of all bins and det G (every slice, and once per reset);
                                  streamed: thermal_cgreens_streamed_kernel, T in device memory
   thermal_cweight_mf_kernel      the phaseless weight update with mf_const_fac
+With `--wide` the engines run in turn are the wide route alone (AFQ_THERMAL_WIDE: thermal_cgreens_wide_kernel and
+thermal_cslice_dense_wide_kernel, one matrix in LDS), which is the only one above 63 sites (`--nx 8`).
 `slice_ms` = all of them over the slices run; `path_kernel_ms` = the same per path; `path_wall_ms` the host's wall time
 of a path, fields and copies included, taken in a separate pass without the event pairs.
 
-  python tools/thermal_hubbard_cont_bench.py [--rounds 3] [--paths 5] [--warmup 2] [--nx 6] [--stack-size 5] [--out FILE]
+  python tools/thermal_hubbard_cont_bench.py [--rounds 3] [--paths 5] [--warmup 2] [--nx 6] [--stack-size 5] [--wide] [--out FILE]
 """
 import argparse
 import json
@@ -35,9 +37,14 @@ from pauxy_amd.propagation.thermal_continuous import Continuous                #
 from pauxy_amd.systems import Hubbard                                           # noqa: E402
 from pauxy_amd.trial_density import OneBody                                     # noqa: E402
 
-GREENS = {False: 'thermal_cgreens_kernel', True: 'thermal_cgreens_streamed_kernel'}
+GREENS = {'resident': 'thermal_cgreens_kernel', 'streamed': 'thermal_cgreens_streamed_kernel',
+          'wide': 'thermal_cgreens_wide_kernel'}
+OPTIONS = {'resident': 0, 'streamed': L.THERMAL_STREAMED_GREENS, 'wide': L.THERMAL_WIDE}
 SMALL = ('thermal_crdm_kernel', 'thermal_cfields_dense_kernel', 'thermal_cweight_mf_kernel')
-SLICE = 'thermal_cslice_dense_kernel'
+
+
+def slice_of(engine):
+    return 'thermal_cslice_dense_wide_kernel' if engine == 'wide' else 'thermal_cslice_dense_kernel'
 
 
 class Qmc(object):
@@ -57,7 +64,7 @@ def spread(values):
     return {'median': float(numpy.median(values)), 'min': float(min(values)), 'max': float(max(values))}
 
 
-def run(a, streamed):
+def run(a, engine):
     M = a.nx * a.nx
     system = Hubbard(a.nx, a.nx, M // 2 - 1, M // 2 - 1, 4.0, mu=1.0)
     trial = OneBody(system, a.beta, a.dt)
@@ -68,7 +75,7 @@ def run(a, streamed):
     dev.walkers_alloc(a.walkers)
     dev.thermal_configure_hubbard_continuous(nslices, a.stack_size, a.dt, trial.dmat, trial.dmat_inv, prop.BH1,
                                              prop.mf_shift, prop.mf_const_fac,
-                                             L.THERMAL_STREAMED_GREENS if streamed else 0)
+                                             OPTIONS[engine])
     M00 = dev.get(L.F_THERMAL_M0)
     rng = numpy.random.RandomState(5)
     for _ in range(a.warmup):
@@ -85,9 +92,9 @@ def run(a, streamed):
     dev.launch_trace(False)
     res = {'system': 'Hubbard %dx%d U=4 mu=1' % (a.nx, a.nx), 'M': M, 'walkers': a.walkers, 'beta': a.beta, 'dt': a.dt,
            'slices': nslices, 'stack_size': a.stack_size, 'nbins': nslices // a.stack_size, 'trial_mu': trial.mu,
-           'paths': a.paths, 'engine': 'streamed' if streamed else 'resident', 'kernels': {}}
+           'paths': a.paths, 'engine': engine, 'kernels': {}}
     total = 0.0
-    for k in SMALL + (SLICE, GREENS[streamed]):
+    for k in SMALL + (slice_of(engine), GREENS[engine]):
         n, ms = trace.get(k, (0, 0.0))
         res['kernels'][k] = {'launches': n, 'total_ms': ms, 'mean_ms': ms / n if n else 0.0}
         total += ms
@@ -111,26 +118,30 @@ def main():
     ap.add_argument('--paths', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--rounds', type=int, default=3, help='runs of each engine, resident and streamed in turn')
+    ap.add_argument('--wide', action='store_true', help='the wide route alone (AFQ_THERMAL_WIDE); with --nx 6 beside the other two')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
-    runs = {'resident': [], 'streamed': []}
+    names = (('resident', 'streamed', 'wide') if a.nx * a.nx <= 47 else ('wide',)) if a.wide else ('resident', 'streamed')
+    runs = {name: [] for name in names}
     for _ in range(a.rounds):
-        for name in ('resident', 'streamed'):
-            runs[name].append(run(a, name == 'streamed'))
-    res = dict((k, v) for k, v in runs['resident'][0].items()
+        for name in names:
+            runs[name].append(run(a, name))
+    res = dict((k, v) for k, v in runs[names[0]][0].items()
                if k not in ('kernels', 'slice_ms', 'path_kernel_ms', 'small_kernels_mean_ms', 'path_wall_ms', 'finite', 'engine'))
     res['rounds'] = a.rounds
-    for name in ('resident', 'streamed'):
-        g = GREENS[name == 'streamed']
-        res[name] = {'slice_kernel_mean_ms': spread([r['kernels'][SLICE]['mean_ms'] for r in runs[name]]),
+    for name in names:
+        g = GREENS[name]
+        res[name] = {'slice_kernel_mean_ms': spread([r['kernels'][slice_of(name)]['mean_ms'] for r in runs[name]]),
                      'greens_mean_ms': spread([r['kernels'][g]['mean_ms'] for r in runs[name]]),
                      'small_kernels_mean_ms': spread([r['small_kernels_mean_ms'] for r in runs[name]]),
                      'slice_ms': spread([r['slice_ms'] for r in runs[name]]),
                      'path_kernel_ms': spread([r['path_kernel_ms'] for r in runs[name]]),
                      'path_wall_ms': spread([r['path_wall_ms']['median'] for r in runs[name]]),
                      'finite': all(r['finite'] for r in runs[name])}
-    res['streamed_over_resident'] = {k: res['streamed'][k]['median'] / res['resident'][k]['median']
-                                     for k in ('slice_ms', 'greens_mean_ms', 'path_wall_ms')}
+    for other, base in (('streamed', 'resident'), ('wide', 'streamed')):
+        if other in res and base in res:
+            res['%s_over_%s' % (other, base)] = {k: res[other][k]['median'] / res[base][k]['median']
+                                                 for k in ('slice_ms', 'greens_mean_ms', 'path_wall_ms')}
     res['runs'] = runs
     print(json.dumps(res))
     if a.out:

@@ -11,17 +11,20 @@ The kernels are timed with event pairs around every launch (afq_launch_trace) ov
   vhs_ueg_kernel           the plane-wave HS potential (k_models.hip)
   thermal_cslice_kernel    BV by five Horner products, B, right <- B right, the bin
   thermal_cgreens_kernel   the complex stratified G of all bins and det G (every slice, and once per reset);
-                           with --streamed thermal_cgreens_streamed_kernel, T in device memory (needed above M = 47)
+                           with --streamed thermal_cgreens_streamed_kernel, T in device memory (needed above M = 47);
+                           with --wide thermal_cgreens_wide_kernel and thermal_cslice_wide_kernel, one matrix in LDS
+                           (AFQ_THERMAL_WIDE, needed above M = 57: ecut 3.0 is M = 81, ecut 4.0 is M = 93)
   thermal_cweight_kernel   the phaseless weight update
 `slice_ms` = all of them over the slices run; `path_wall_ms` the host's wall time of a path, fields and copies included
 (median and spread over the paths), taken in a separate pass without the event pairs.
 
 With `--alternate N` the resident and the streamed engine are run in turn, N times each, on the same shape (M <= 47):
 the JSON then holds every run's figures under `runs` and the median and spread of slice_ms, of the Green's kernel's
-mean and of the path's wall time per engine.
+mean and of the path's wall time per engine.  `--alternate N --wide` sets the streamed and the wide route side by side
+instead (M <= 57).
 
-  python tools/thermal_ueg_bench.py [--paths 5] [--warmup 2] [--ecut 2.0] [--stack-size 5] [--streamed | --alternate N]
-                                    [--out FILE]
+  python tools/thermal_ueg_bench.py [--paths 5] [--warmup 2] [--ecut 2.0] [--stack-size 5]
+                                    [--streamed | --wide | --alternate N [--wide]] [--out FILE]
 """
 import argparse
 import json
@@ -40,12 +43,15 @@ from pauxy_amd.propagation.thermal_planewave import planewave_constants        #
 from pauxy_amd.systems import UEG                                               # noqa: E402
 from pauxy_amd.trial_density import OneBody                                     # noqa: E402
 
-GREENS = {False: 'thermal_cgreens_kernel', True: 'thermal_cgreens_streamed_kernel'}
+GREENS = {'resident': 'thermal_cgreens_kernel', 'streamed': 'thermal_cgreens_streamed_kernel',
+          'wide': 'thermal_cgreens_wide_kernel'}
+OPTIONS = {'resident': 0, 'streamed': L.THERMAL_STREAMED_GREENS, 'wide': L.THERMAL_WIDE}
 
 
-def kernels_of(streamed):
+def kernels_of(engine):
     return ('thermal_crdm_kernel', 'vbias_ueg_lds_kernel', 'thermal_cfields_kernel', 'vhs_ueg_kernel',
-            'thermal_cslice_kernel', GREENS[streamed], 'thermal_cweight_kernel')
+            'thermal_cslice_wide_kernel' if engine == 'wide' else 'thermal_cslice_kernel', GREENS[engine],
+            'thermal_cweight_kernel')
 
 
 def one_path(dev, rng, nslices, M00):
@@ -70,34 +76,37 @@ def main():
     ap.add_argument('--paths', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--streamed', action='store_true', help='AFQ_THERMAL_STREAMED_GREENS: T of the Green\'s function in device memory')
-    ap.add_argument('--alternate', type=int, default=0, help='N runs each of the resident and the streamed engine, in turn')
+    ap.add_argument('--wide', action='store_true', help='AFQ_THERMAL_WIDE: one matrix in LDS, two columns per lane')
+    ap.add_argument('--alternate', type=int, default=0, help='N runs each of the resident and the streamed engine, in turn '
+                    '(with --wide: of the streamed and the wide route)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.alternate > 0:
-        runs = {'resident': [], 'streamed': []}
+        base, other = ('streamed', 'wide') if a.wide else ('resident', 'streamed')
+        runs = {base: [], other: []}
         for _ in range(a.alternate):
-            for name in ('resident', 'streamed'):
-                runs[name].append(run(a, name == 'streamed'))
-        res = dict((k, v) for k, v in runs['resident'][0].items() if k not in ('kernels', 'slice_ms', 'path_wall_ms', 'finite', 'engine'))
+            for name in (base, other):
+                runs[name].append(run(a, name))
+        res = dict((k, v) for k, v in runs[base][0].items() if k not in ('kernels', 'slice_ms', 'path_wall_ms', 'finite', 'engine'))
         res['rounds'] = a.alternate
-        for name in ('resident', 'streamed'):
-            g = GREENS[name == 'streamed']
+        for name in (base, other):
+            g = GREENS[name]
             res[name] = {'slice_ms': spread([r['slice_ms'] for r in runs[name]]),
                          'greens_mean_ms': spread([r['kernels'][g]['mean_ms'] for r in runs[name]]),
                          'path_wall_ms': spread([r['path_wall_ms']['median'] for r in runs[name]]),
                          'finite': all(r['finite'] for r in runs[name])}
-        res['streamed_over_resident'] = {k: res['streamed'][k]['median'] / res['resident'][k]['median']
-                                         for k in ('slice_ms', 'greens_mean_ms', 'path_wall_ms')}
+        res['%s_over_%s' % (other, base)] = {k: res[other][k]['median'] / res[base][k]['median']
+                                             for k in ('slice_ms', 'greens_mean_ms', 'path_wall_ms')}
         res['runs'] = runs
     else:
-        res = run(a, a.streamed)
+        res = run(a, 'wide' if a.wide else 'streamed' if a.streamed else 'resident')
     print(json.dumps(res))
     if a.out:
         with open(a.out, 'w') as f:
             f.write(json.dumps(res, indent=1) + "\n")
 
 
-def run(a, streamed):
+def run(a, engine):
     s = UEG(1.0, 2, 2, a.ecut, full_lists=True, mu=0.245)
     trial = OneBody(s, a.beta, a.dt)
     nslices = trial.num_slices
@@ -107,7 +116,7 @@ def run(a, streamed):
                        numpy.array([s.H1[0].diagonal(), s.H1[1].diagonal()]), s.ecore, s.nup, s.ndown)
     dev.walkers_alloc(a.walkers)
     dev.thermal_configure_continuous(nslices, a.stack_size, a.dt, trial.dmat, trial.dmat_inv, BH1, mf_shift,
-                                     options=L.THERMAL_STREAMED_GREENS if streamed else 0)
+                                     options=OPTIONS[engine])
     M00 = dev.get(L.F_THERMAL_M0)
     rng = numpy.random.RandomState(5)
     for _ in range(a.warmup):
@@ -124,9 +133,9 @@ def run(a, streamed):
     dev.launch_trace(False)
     res = {'system': 'UEG rs=1 ecut=%g 2+2 mu=0.245' % a.ecut, 'M': s.nbasis, 'fields': s.nfields, 'walkers': a.walkers,
            'beta': a.beta, 'dt': a.dt, 'slices': nslices, 'stack_size': a.stack_size, 'nbins': nslices // a.stack_size,
-           'trial_mu': trial.mu, 'paths': a.paths, 'engine': 'streamed' if streamed else 'resident', 'kernels': {}}
+           'trial_mu': trial.mu, 'paths': a.paths, 'engine': engine, 'kernels': {}}
     total = 0.0
-    for k in kernels_of(streamed):
+    for k in kernels_of(engine):
         n, ms = trace.get(k, (0, 0.0))
         res['kernels'][k] = {'launches': n, 'total_ms': ms, 'mean_ms': ms / n if n else 0.0}
         total += ms
