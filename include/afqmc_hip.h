@@ -639,7 +639,7 @@ int afq_estimates_get_end(afq_handle *h, double *est_out /* c128[10] */);
  *                          chemical-potential shift folded in; nstblz the period of the stable rebuild of G;
  *                          stack_size must divide ntime_slices.  options: AFQ_THERMAL_* bits of what the caller
  *                          was asked for -- each of them is refused by name.  Ends with afq_thermal_reset.
- *                          AFQ_EUNSUPPORTED: the option bits, M > 64, a system that is not Hubbard, a communicator
+ *                          AFQ_EUNSUPPORTED: the option bits, M > 64 (M > 128 with AFQ_THERMAL_DELAYED), a system that is not Hubbard, a communicator
  *                          of more than one rank, a handle with back-propagation, ITCF or the mixed RDM switched on
  *                          (and afq_bp_configure, afq_itcf_configure, afq_estimates_rdm, afq_popcontrol_pair_branch
  *                          on a thermal handle afterwards).
@@ -667,9 +667,29 @@ int afq_estimates_get_end(afq_handle *h, double *est_out /* c128[10] */);
 #define AFQ_THERMAL_AVERAGE_GF      8
 #define AFQ_THERMAL_STREAMED_GREENS 16  /* honoured by afq_thermal_configure_continuous (below), refused here by name */
 #define AFQ_THERMAL_WIDE            32  /* honoured by the two continuous entry points (below), refused here by name */
+#define AFQ_THERMAL_DELAYED         128 /* honoured by afq_thermal_configure alone: the delayed-update route (below);
+                                           AFQ_EINVAL on the two continuous entry points, by name */
 int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int nstblz, const double *BT,
                           const double *BT_inv, const double *BH1, const double *auxf, int options);
+/* With AFQ_THERMAL_DELAYED in options the handle takes the real walkers' second route, for any M >= 1: every Green's
+ * function (afq_thermal_reset, _greens, the rebuild of _propagate) is made by thermal_greens_wide_kernel -- the wide
+ * engine of the continuous fields on real matrices: one matrix of 8 M (M | 1) bytes in LDS, two columns per lane, four
+ * [M, M] buffers of device memory per (walker, spin) -- and the slice by thermal_slice_delayed_kernel: the M single-site
+ * updates as delayed (blocked) updates, G in device memory, per panel of 16 sites the panel's columns and rows current
+ * in LDS and G <- G + U W as one fp64 MFMA product.  The fields are those of the direct route wherever no decision lies
+ * within rounding of its threshold; G, the stack and the weights agree to rounding, not to the bit.  The bound is the
+ * smallest of the kernels' LDS (8 (M (M | 1) + 1152) + 512 bytes for the Green's function, 141,824 at M = 128) and the
+ * 128 columns of two per lane: M <= 128 = afq_thermal_delayed_max_basis(); above it AFQ_EUNSUPPORTED with M and the
+ * numbers, before stack_size is looked at.  Bits 16 and 32 next to it are refused as without it.
+ * afq_thermal_estimates with AFQ_THERMAL_EST_AVERAGE_GF on such a handle is AFQ_EUNSUPPORTED (no sweep kernel).  Without
+ * the bit nothing changes: M > 64 is refused. */
 int afq_thermal_reset(afq_handle *h);
+/* the largest M a handle configured with AFQ_THERMAL_DELAYED admits (no handle, no device) */
+int afq_thermal_delayed_max_basis(void);
+/* the number of device blocks the handle has allocated since afq_create (every buffer of the handle goes through one
+ * allocator): a thermal handle's buffers, the wide Green's function's scratch included, are allocated by its configure
+ * call, so the count stands still over afq_thermal_propagate / _greens / _reset.  AFQ_EINVAL: a NULL argument. */
+int afq_thermal_device_allocations(afq_handle *h, int64_t *out);
 int afq_thermal_propagate(afq_handle *h, const double *u, int32_t *fields_out, double eshift);
 int afq_thermal_greens(afq_handle *h, int slice_ix);
 int afq_thermal_energy(afq_handle *h, double *E_out, double *nav_out);
@@ -689,7 +709,8 @@ int afq_thermal_state(afq_handle *h, int32_t *out4);
  * ONE_RDM: one_rdm_out f64[2, M, M] = sum_w weight_w Re G_w of the G the call leaves, every walker in walker order.
  * TWO_RDM (UEG): two_rdm_out f64[2, 2, nq] = sum_w weight_w Re two_rdm[P_w] of the same G, from the pair sums of the
  * energy launch.  AFQ_ESTATE: no thermal configuration; AFQ_EINVAL: unknown bits in what, a needed output NULL;
- * AFQ_EUNSUPPORTED: TWO_RDM on a Hubbard handle; AVERAGE_GF on a handle configured with AFQ_THERMAL_WIDE. */
+ * AFQ_EUNSUPPORTED: TWO_RDM on a Hubbard handle; AVERAGE_GF on a handle configured with AFQ_THERMAL_WIDE or
+ * AFQ_THERMAL_DELAYED. */
 #define AFQ_THERMAL_EST_AVERAGE_GF 1
 #define AFQ_THERMAL_EST_ONE_RDM    2
 #define AFQ_THERMAL_EST_TWO_RDM    4   /* UEG walkers only: AFQ_EUNSUPPORTED otherwise */

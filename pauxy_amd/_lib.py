@@ -25,6 +25,7 @@ AFQ_PROP_HYBRID, AFQ_PROP_FORCE_BIAS, AFQ_PROP_FREE_PROJECTION, AFQ_PROP_HUBBARD
 THERMAL_CHARGE, THERMAL_FREE_PROJECTION, THERMAL_LOW_RANK, THERMAL_AVERAGE_GF = 1, 2, 4, 8
 THERMAL_STREAMED_GREENS = 16
 THERMAL_WIDE = 32
+THERMAL_DELAYED = 128          # (64 stays unknown)
 THERMAL_EST_AVERAGE_GF, THERMAL_EST_ONE_RDM, THERMAL_EST_TWO_RDM = 1, 2, 4      # afq_thermal_estimates
 AFQ_EINVAL, AFQ_ESTATE, AFQ_EUNSUPPORTED = -1, -2, -5
 
@@ -166,6 +167,8 @@ SIGNATURES = {
     "afq_thermal_configure_hubbard_continuous": [_h, c_int, c_int, c_double, _dp, _dp, _dp, _dp, _dp, c_int],
     "afq_thermal_left_table": [c_int, c_int, _dp, _dp, _dp, _dp],
     "afq_thermal_wide_max_basis": [],
+    "afq_thermal_delayed_max_basis": [],
+    "afq_thermal_device_allocations": [_h, c_void_p],
     "afq_thermal_estimates": [_h, c_int, _dp, _dp, _dp, _dp],
     "afq_thermal_set_sweep_budget": [_h, ctypes.c_size_t],
 }

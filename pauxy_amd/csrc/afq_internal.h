@@ -269,6 +269,8 @@ struct afq_handle {
     double *th_u = nullptr;         // [nw, M] uniforms of the slice
     int *th_fields = nullptr;       // [nw, M] chosen fields (-1: both probabilities vanished)
     double *th_nav = nullptr;       // [nw]
+    bool th_delayed = false;        // AFQ_THERMAL_DELAYED: the delayed slice kernel and the wide real Green's function
+    double *th_wscratch = nullptr;  // [nw, 2, 4, M, M] the wide Green's function's scratch (a delayed handle; else none)
     // continuous fields (k_thermal_cplx.hip; thermal_propagation/planewave.py, continuous.py with hubbard.py:199-250): the
     // walker's matrices are complex, thc_* are its state
     cplx *thc_G = nullptr;          // [nw, 2, M, M]

@@ -30,6 +30,7 @@ enum Lifetime { LT_HANDLE = 0, LT_SYSTEM, LT_TRIAL, LT_WALKERS, LT_COUNT };
 struct DevMem {
     struct Slot { void **p; size_t *len; };
     std::vector<Slot> owned[LT_COUNT];
+    long allocations = 0;       // blocks allocated so far (afq_thermal_device_allocations: a test that nothing allocates per call)
 
     // frees what the slot holds, allocates bytes (0: leaves it null) and enters the slot under lt; *len is zeroed
     hipError_t replace(Lifetime lt, void **p, size_t bytes, size_t *len) {
@@ -42,6 +43,7 @@ struct DevMem {
         if (!bytes) return hipSuccess;
         const hipError_t e = hipMalloc(p, bytes);
         if (e != hipSuccess) *p = nullptr;
+        else ++allocations;
         return e;
     }
     void release(Lifetime lt) {

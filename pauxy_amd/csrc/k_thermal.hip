@@ -4,24 +4,41 @@
 // A thermal walker has no Slater determinant: it carries G_s = [I + B_L .. B_1]^-1 per spin, f64 [2, M, M], and a stack
 // of nbins products of stack_size propagators each, f64 [nbins, 2, M, M].  The slice counter, the block and the in-bin
 // counter are the same for every walker and live on the handle; the driver moves the population through the slices
-// together.  M <= 64: a walker's working set stays in LDS.
+// together.  M <= 64: a walker's working set stays in LDS.  A handle configured with AFQ_THERMAL_DELAYED takes the second
+// route below and reaches M = 128 = afq_thermal_delayed_max_basis().
 //
 //   thermal_greens_kernel   G of every (walker, spin) from the stack: thermal_strat.h's engine with T = double.
 //   thermal_slice_kernel    one work-group per walker, both spins' G in LDS: the M single-site updates of
 //                           propagate_walker_constrained, then B_s = diag(BV_s) BH1_s onto the walker's current bin.
 //   thermal_wrap_kernel     G_s <- BT_s G_s BT_s^-1 (two MFMA products) per (walker, spin).
+// With AFQ_THERMAL_DELAYED
+//   thermal_greens_wide_kernel    thermal_wide.h's engine with T = double: one real matrix in LDS, two columns per lane.
+//   thermal_slice_delayed_kernel  the same M single-site updates as the delayed (blocked) updates of determinant QMC:
+//                           G of both spins stays in device memory; per panel of TD_KB sites the panel's columns and rows
+//                           are loaded into LDS and kept current site by site, the rank-1 factors accumulate as
+//                           U [M, KB] and W [KB, M], and G <- G + U W closes the panel as one fp64 MFMA product.
 // and, for every kind of thermal handle, afq_thermal_estimates: the mixed estimator's sums (estimators/mixed.py:180-233)
 //   thermal_sweep_reduce_kernel   every walker's (E, T, V, nav) over the bins of the sweep, added in bin order.
 //   thermal_one_rdm_kernel        sum_w weight_w Re G_w.
-#include "thermal_strat.h"
+#include "thermal_wide.h"
 #include <cstring>
 
 #define TH_MAXM 64
+#define TH_LDS_MAX (160 * 1024)
+#define TD_KB 16                // sites per panel of the delayed updates (a multiple of the MFMA's k = 4)
+#define TD_CP (TD_KB + 1)       // pitch of the [M, TD_KB] panels in LDS: a column read walks the banks
 
 namespace {
 
 inline size_t th_slice_lds(int M) { return sizeof(double) * (3 * ts_mat(M) + 6 * 64); }
 inline size_t th_wrap_lds(int M) { return sizeof(double) * ts_mat(M); }
+// LDS of the delayed slice kernel: bv [2][128]; per spin the panel's columns and U [M, TD_KB] (pitch TD_CP), its rows and
+// W [TD_KB, M | 1]; behind the sites the same room holds the one matrix of the stack update
+inline size_t td_panel_scalars(int M) { return 2 * (2 * (size_t)M * TD_CP + 2 * (size_t)TD_KB * (M | 1)); }
+inline size_t th_slice_delayed_lds(int M) {
+    const size_t p = td_panel_scalars(M), x = ts_mat(M);
+    return sizeof(double) * (2 * TW_COLS + (p > x ? p : x));
+}
 
 struct ThSliceArgs {
     double *G, *stack, *weight;
@@ -106,6 +123,127 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_slice_kernel(ThSliceArgs a
     }
 }
 
+// The slice by delayed updates.  Site i = i0 + j of the panel i0 .. i0 + kb - 1 reads the current G_ii of both spins off
+// the panel's columns, decides as thermal_slice_kernel does, and leaves u = -f col_i in column j of U and w = e_i - row_i
+// in row j of W (zeros for a site whose probabilities both vanish); only the panel's later columns and rows are brought
+// up to date, by the fma of the direct kernel, so within a panel every decision sees the direct route's bits.  The
+// trailing G <- G + U W runs over G in device memory, 16 x 16 tiles with G's tile as the accumulator's start; rows,
+// columns and k beyond M or beyond kb enter as zero operands.  No trip count depends on data, every branch is uniform
+// over the work-group, every wave is at every barrier.
+__global__ __launch_bounds__(TH_THREADS) void thermal_slice_delayed_kernel(ThSliceArgs a) {
+    static_assert(TD_KB % 4 == 0 && TD_KB >= 4, "the trailing update steps k by the MFMA's 4");
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int M = a.M, LD = M | 1, tid = threadIdx.x, w = blockIdx.x;
+    const long mm = (long)M * M;
+    double *bv = (double *)smem;                       // [2][128]
+    double *Cp = bv + 2 * TW_COLS;                     // [2][M][TD_CP] the panel's columns
+    double *Up = Cp + 2 * M * TD_CP;                   // [2][M][TD_CP]
+    double *Rp = Up + 2 * M * TD_CP;                   // [2][TD_KB][LD] the panel's rows
+    double *Wp = Rp + 2 * TD_KB * LD;                  // [2][TD_KB][LD]
+    double *X = Cp;                                    // [M][LD] behind the sites
+    double *Gw = a.G + (long)w * 2 * mm;
+    const int lane = tid & 63, wave = tid >> 6, lr = lane & 15, lk = lane >> 4, nt = (M + 15) >> 4;
+    double wt = a.weight[w];
+    for (int i0 = 0; i0 < M; i0 += TD_KB) {
+        const int kb = M - i0 < TD_KB ? M - i0 : TD_KB;
+        for (int e = tid; e < 2 * M * kb; e += TH_THREADS) {
+            const int s = e / (M * kb), r = (e / kb) % M, jj = e % kb;
+            Cp[(s * M + r) * TD_CP + jj] = Gw[s * mm + (long)r * M + i0 + jj];
+        }
+        for (int e = tid; e < 2 * kb * M; e += TH_THREADS) {
+            const int s = e / (kb * M), jj = (e / M) % kb, c = e % M;
+            Rp[(s * TD_KB + jj) * LD + c] = Gw[s * mm + (long)(i0 + jj) * M + c];
+        }
+        __syncthreads();
+        for (int j = 0; j < kb; ++j) {
+            const int i = i0 + j;
+            const double g0 = Cp[i * TD_CP + j], g1 = Cp[(M + i) * TD_CP + j];
+            double p0 = 0.5 * ((1.0 + (1.0 - g0) * a.delta[0][0]) * (1.0 + (1.0 - g1) * a.delta[0][1]));
+            double p1 = 0.5 * ((1.0 + (1.0 - g0) * a.delta[1][0]) * (1.0 + (1.0 - g1) * a.delta[1][1]));
+            p0 = p0 > 0.0 ? p0 : 0.0; p1 = p1 > 0.0 ? p1 : 0.0;
+            const double norm = p0 + p1;
+            const double u = a.u[(long)w * M + i];        // consumed whatever norm is
+            const bool live = norm > 0.0;                 // (the same value in every thread: uniform branches)
+            int x = 0;
+            double f0 = 0.0, f1 = 0.0;
+            if (live) {
+                wt = wt * norm * a.exp_eshift;
+                x = u < p0 / norm ? 0 : 1;
+                f0 = a.delta[x][0] / (1.0 + (1.0 - g0) * a.delta[x][0]);
+                f1 = a.delta[x][1] / (1.0 + (1.0 - g1) * a.delta[x][1]);
+            } else {
+                wt = 0.0;
+            }
+            {
+                const int s = tid >> 7, r = tid & 127;
+                if (r < M) {
+                    Up[(s * M + r) * TD_CP + j] = live ? -(s ? f1 : f0) * Cp[(s * M + r) * TD_CP + j] : 0.0;
+                    Wp[(s * TD_KB + j) * LD + r] = live ? (r == i ? 1.0 : 0.0) - Rp[(s * TD_KB + j) * LD + r] : 0.0;
+                }
+            }
+            if (tid == 0) {
+                bv[i] = a.auxf[x][0]; bv[TW_COLS + i] = a.auxf[x][1];
+                if (a.fields) a.fields[(long)w * M + i] = live ? x : -1;
+            }
+            __syncthreads();
+            if (live) {
+                const int nc = kb - j - 1;                // the panel's columns and rows still to come
+                for (int e = tid; e < 2 * M * nc; e += TH_THREADS) {
+                    const int s = e / (M * nc), r = (e / nc) % M, jj = j + 1 + e % nc;
+                    double *g = &Cp[(s * M + r) * TD_CP + jj];
+                    *g = fma(Up[(s * M + r) * TD_CP + j], Wp[(s * TD_KB + j) * LD + i0 + jj], *g);
+                }
+                for (int e = tid; e < 2 * nc * M; e += TH_THREADS) {
+                    const int s = e / (nc * M), jj = j + 1 + (e / M) % nc, c = e % M;
+                    double *g = &Rp[(s * TD_KB + jj) * LD + c];
+                    *g = fma(Up[(s * M + i0 + jj) * TD_CP + j], Wp[(s * TD_KB + j) * LD + c], *g);
+                }
+            }
+            __syncthreads();
+        }
+        // G <- G + U W
+        for (int tile = wave; tile < 2 * nt * nt; tile += TH_THREADS / 64) {
+            const int s = tile / (nt * nt), t2 = tile % (nt * nt);
+            const int row0 = (t2 / nt) << 4, col0 = (t2 % nt) << 4, arow = row0 + lr, bcol = col0 + lr;
+            double *Gs = Gw + s * mm;
+            d4_t acc;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = row0 + lk + 4 * r;
+                acc[r] = (row < M && bcol < M) ? Gs[(long)row * M + bcol] : 0.0;
+            }
+#pragma unroll
+            for (int k0 = 0; k0 < TD_KB; k0 += 4) {
+                const int k = k0 + lk;
+                const double ua = (arow < M && k < kb) ? Up[(s * M + arow) * TD_CP + k] : 0.0;
+                const double wb = (bcol < M && k < kb) ? Wp[(s * TD_KB + k) * LD + bcol] : 0.0;
+                acc = mfma16(ua, wb, acc);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = row0 + lk + 4 * r;
+                if (row < M && bcol < M) Gs[(long)row * M + bcol] = acc[r];
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) a.weight[w] = wt;
+    // stack[block, s] = diag(BV_s) BH1_s (counter == 0 ? I : stack[block, s]); the bin is read whole before it is written
+    for (int s = 0; s < 2; ++s) {
+        double *S = a.stack + (((long)w * a.nbins + a.block) * 2 + s) * mm;
+        const double *BH = a.BH1 + s * mm, *b = bv + s * TW_COLS;
+        if (a.counter == 0) {
+            for (int e = tid; e < M * M; e += TH_THREADS) S[e] = b[e / M] * BH[e];
+        } else {
+            ts_gemm<double>(M, [&](int r, int k) { return b[r] * BH[r * M + k]; }, [&](int k, int c) { return S[k * M + c]; },
+                    [&](int r, int c, double x) { X[r * LD + c] = x; });
+            __syncthreads();
+            for (int e = tid; e < M * M; e += TH_THREADS) S[e] = X[(e / M) * LD + e % M];
+            __syncthreads();
+        }
+    }
+}
+
 // G_s <- BT_s G_s BT_s^-1 per (walker, spin)
 __global__ __launch_bounds__(TH_THREADS) void thermal_wrap_kernel(double *G, const double *BT, const double *BTinv, int M) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -176,10 +314,23 @@ int th_energy_n(afq_handle *h, const cplx *P, int n, cplx *E, cplx **two) {
     return k_ueg_pair_sums(h, P, n, E, *two);
 }
 
+// the largest M of a delayed handle: what its three kernels' LDS and the 128 columns of two per lane admit
+int th_delayed_bound() {
+    int m = TW_COLS;
+    while (m > 1 && (ts_greens_wide_lds<double>(m) > TH_LDS_MAX || th_slice_delayed_lds(m) > TH_LDS_MAX || th_wrap_lds(m) > TH_LDS_MAX)) --m;
+    return m;
+}
+
+// G of nblocks / 2 walkers by the engine the handle was configured with
+int th_launch_greens(afq_handle *h, double *G, int first, int src_w, int nblocks) {
+    if (h->th_delayed) return ts_launch_greens_wide<double>(h, h->th_stack, G, nullptr, h->th_wscratch, first, src_w, nblocks);
+    return ts_launch_greens<double>(h, h->th_stack, G, nullptr, first, src_w, nblocks);
+}
+
 }  // namespace
 
 int k_thermal_greens(afq_handle *h, int slice_ix) {
-    return ts_launch_greens<double>(h, h->th_stack, h->th_G, nullptr, ts_first_bin(h, slice_ix), -1, 2 * h->nw);
+    return th_launch_greens(h, h->th_G, ts_first_bin(h, slice_ix), -1, 2 * h->nw);
 }
 
 extern "C" {
@@ -190,11 +341,27 @@ int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int n
     if (!h) return AFQ_EINVAL;
     h->th_kind = TH_NONE;
     if (!BT || !BT_inv || !BH1 || !auxf) AFQ_FAIL(h, AFQ_EINVAL, "afq_thermal_configure: null operand");
-    const ThEntry me = {"afq_thermal_configure: ", 0, AFQ_EUNSUPPORTED,
+    const ThEntry me = {"afq_thermal_configure: ", AFQ_THERMAL_DELAYED, AFQ_EUNSUPPORTED,
                         "thermal walkers: charge_decomposition is not supported (spin decomposition only)", AFQ_SYS_HUBBARD,
                         "thermal walkers: Hubbard systems only (no Generic / UEG)", "all"};
     AFQ_TRY(th_screen_options(h, me, options));
-    if (h->M > TH_MAXM) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: M = " + std::to_string(h->M) + " > 64 sites do not fit a work-group's LDS");
+    const bool delayed = (options & AFQ_THERMAL_DELAYED) != 0;
+    if (delayed) {
+        const int M = h->M, mmax = th_delayed_bound();
+        const std::string head = "thermal walkers (delayed_updates): M = " + std::to_string(M) + " sites ", tail = " (M <= " + std::to_string(mmax) + ")";
+        const struct { const char *what; size_t bytes; } need[3] = {
+            {"the wide Green's function (thermal_greens_wide_kernel)", ts_greens_wide_lds<double>(M)},
+            {"the delayed slice kernel (thermal_slice_delayed_kernel)", th_slice_delayed_lds(M)},
+            {"the wrap (thermal_wrap_kernel)", th_wrap_lds(M)}};
+        if (M > TW_COLS)
+            AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "are more than the " + std::to_string(TW_COLS) + " columns of a wave, two per lane" + tail);
+        for (const auto &k : need)
+            if (k.bytes > TH_LDS_MAX)
+                AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(k.bytes) + " bytes of LDS for " + k.what +
+                         ", a work-group has " + std::to_string(TH_LDS_MAX) + tail);
+    } else if (h->M > TH_MAXM)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: M = " + std::to_string(h->M) + " > 64 sites do not fit a work-group's LDS"
+                 "; AFQ_THERMAL_DELAYED (delayed_updates) reaches M = " + std::to_string(th_delayed_bound()));
     AFQ_TRY(th_screen_state(h, me, ntime_slices, stack_size, nstblz));
     hipSetDevice(h->device);
     const int M = h->M, nbins = ntime_slices / stack_size;
@@ -222,11 +389,22 @@ int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int n
     if ((rc = dev_alloc(h, LT_WALKERS, &h->th_G, 2 * mm * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_G0, 2 * mm)) ||
         (rc = dev_alloc(h, LT_WALKERS, &h->th_stack, 2 * mm * n * nbins)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_u, (size_t)M * n)) ||
         (rc = dev_alloc(h, LT_WALKERS, &h->th_fields, (size_t)M * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_nav, n))) return rc;
+    // the wide Green's function's scratch, four [M, M] per (walker, spin); a handle configured without the bit holds none
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->th_wscratch, delayed ? 2 * ts_greens_wide_scratch(M) * n : (size_t)0))) return rc;
+    h->th_delayed = delayed;
     if ((rc = ensure_G(h))) return rc;                  // c128 [nw, 2, M, M]: the one-body density matrices of afq_thermal_energy
     for (int f = 0; f < 2; ++f) for (int s = 0; s < 2; ++s) h->th_auxf[f][s] = auxf[2 * f + s];
     h->th_L = ntime_slices; h->th_ss = stack_size; h->th_nbins = nbins; h->th_nstblz = nstblz;
     h->th_kind = TH_REAL;
     return afq_thermal_reset(h);
+}
+
+int afq_thermal_delayed_max_basis(void) { return th_delayed_bound(); }
+
+int afq_thermal_device_allocations(afq_handle *h, int64_t *out) {
+    if (!h || !out) return AFQ_EINVAL;
+    *out = h->mem.allocations;
+    return AFQ_OK;
 }
 
 int afq_thermal_reset(afq_handle *h) {
@@ -239,7 +417,7 @@ int afq_thermal_reset(afq_handle *h) {
     // the trial's G once, from walker 0's fresh bins (every bin is BT^stack_size), then broadcast
     for (int n = 0; n < nbins; ++n)
         AFQ_HIP(h, hipMemcpyAsync(h->th_stack + (long)n * per, h->th_BTpow, sizeof(double) * per, hipMemcpyDeviceToDevice, h->stream));
-    AFQ_TRY(ts_launch_greens<double>(h, h->th_stack, h->th_G0, nullptr, ts_first_bin(h, 0), 0, 2));
+    AFQ_TRY(th_launch_greens(h, h->th_G0, ts_first_bin(h, 0), 0, 2));
     AFQ_LAUNCH(h, thermal_reset_kernel, dim3((unsigned)((per + 255) / 256), h->nw), dim3(256), 0, h->stream, h->th_stack,
                h->th_G, h->weight, h->th_BTpow, h->th_G0, nbins, per, h->nw);
     AFQ_POST(h);
@@ -269,7 +447,13 @@ int afq_thermal_propagate(afq_handle *h, const double *u, int32_t *fields_out, d
     a.fields = h->th_fields; a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
     for (int f = 0; f < 2; ++f) for (int s = 0; s < 2; ++s) { a.auxf[f][s] = h->th_auxf[f][s]; a.delta[f][s] = h->th_auxf[f][s] - 1.0; }
     a.exp_eshift = exp(eshift);
-    {
+    if (h->th_delayed) {
+        static size_t lds_set[AFQ_MAX_DEVICES] = {0};
+        const size_t lds = th_slice_delayed_lds(M);
+        AFQ_HIP(h, afq_raise_lds((const void *)thermal_slice_delayed_kernel, lds, lds_set));
+        AFQ_LAUNCH(h, thermal_slice_delayed_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a);
+        AFQ_POST(h);
+    } else {
         static size_t lds_set[AFQ_MAX_DEVICES] = {0};
         const size_t lds = th_slice_lds(M);
         AFQ_HIP(h, afq_raise_lds((const void *)thermal_slice_kernel, lds, lds_set));
@@ -279,6 +463,8 @@ int afq_thermal_propagate(afq_handle *h, const double *u, int32_t *fields_out, d
     th_advance(h);
     if (h->th_slice % h->th_nstblz == 0) AFQ_TRY(k_thermal_greens(h, h->th_slice - 1));
     if (h->th_slice < h->th_L) {
+        static size_t lds_set[AFQ_MAX_DEVICES] = {0};
+        AFQ_HIP(h, afq_raise_lds((const void *)thermal_wrap_kernel, th_wrap_lds(M), lds_set));      // (beyond 64 KiB at M > 90)
         AFQ_LAUNCH(h, thermal_wrap_kernel, dim3(2 * h->nw), dim3(TH_THREADS), th_wrap_lds(M), h->stream, h->th_G, h->th_BT,
                    h->th_BTinv, M);
         AFQ_POST(h);
@@ -317,6 +503,8 @@ int afq_thermal_estimates(afq_handle *h, int what, double *cols_out, double *per
     if (two && h->th_kind != TH_CPLX_DIAG)
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "afq_thermal_estimates: two_rdm is the structure factor of the UEG walkers (no Hubbard)");
     const bool cx = th_complex(h);
+    if (avg && !cx && h->th_delayed)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "afq_thermal_estimates: average_gf is not supported on a delayed_updates handle (AFQ_THERMAL_DELAYED has no sweep kernel)");
     if (avg && cx && h->thc_wide)
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "afq_thermal_estimates: average_gf is not supported on a wide_basis handle (AFQ_THERMAL_WIDE has no sweep kernel)");
     const int M = h->M, nw = h->nw, nbins = h->th_nbins, nbt = avg ? nbins : 1;

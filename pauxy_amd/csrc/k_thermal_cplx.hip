@@ -453,7 +453,7 @@ __global__ void thermal_creset_kernel(cplx *stack, cplx *G, cplx *right, cplx *M
 // G and det of nblocks / 2 walkers by the engine the handle was configured with
 static int thc_launch_greens(afq_handle *h, cplx *G, cplx *det, int first, int src_w, int nblocks) {
     if (h->thc_wide)
-        return ts_launch_greens_wide(h, h->thc_stack, G, det, h->thc_tscratch, first, src_w, nblocks);
+        return ts_launch_greens_wide<cplx>(h, h->thc_stack, G, det, h->thc_tscratch, first, src_w, nblocks);
     if (h->thc_streamed)
         return ts_launch_greens_streamed<cplx>(h, h->thc_stack, G, det, h->thc_tscratch, first, src_w, nblocks);
     return ts_launch_greens<cplx>(h, h->thc_stack, G, det, first, src_w, nblocks);
@@ -524,7 +524,7 @@ int thc_route_of(afq_handle *h, const std::string &me, int options, ThcRoute *ro
     return AFQ_OK;
 }
 
-const ThcLds THC_WIDE_GREENS = {"the wide Green's function (thermal_cgreens_wide_kernel)", ts_greens_wide_lds, ""};
+const ThcLds THC_WIDE_GREENS = {"the wide Green's function (thermal_cgreens_wide_kernel)", ts_greens_wide_lds<cplx>, ""};
 
 // M within what every kernel of `need` and lane = column hold; else the refusal names the first of them that does not
 // fit, with its bytes, and the largest M that passes.  who: "" or ", Hubbard"; unit: what M counts.
@@ -569,6 +569,9 @@ int thc_configure_common(afq_handle *h, ThKind kind, int ntime_slices, int stack
     // spin), of which the wide slice kernels use the walker's first two; a handle configured without either holds none
     const size_t tscratch = route == THC_STREAMED ? 4 * mm * n : route == THC_WIDE ? 2 * ts_greens_wide_scratch(h->M) * n : (size_t)0;
     if ((rc = dev_alloc(h, LT_WALKERS, &h->thc_tscratch, tscratch))) return rc;
+    // (a handle that held real walkers on the delayed route: their scratch and their flag go with them)
+    if ((rc = dev_alloc(h, LT_WALKERS, &h->th_wscratch, (size_t)0))) return rc;
+    h->th_delayed = false;
     h->thc_streamed = route == THC_STREAMED;
     h->thc_wide = route == THC_WIDE;
     if ((rc = ensure_G(h))) return rc;                  // c128 [nw, 2, M, M]: the one-body density matrices
@@ -706,7 +709,7 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
 
 int afq_thermal_wide_max_basis(void) {
     int m = TW_COLS;
-    while (m > 1 && (ts_greens_wide_lds(m) > THC_LDS_MAX || thc_slice_wide_lds(m) > THC_LDS_MAX || thd_slice_wide_lds(m) > THC_LDS_MAX)) --m;
+    while (m > 1 && (ts_greens_wide_lds<cplx>(m) > THC_LDS_MAX || thc_slice_wide_lds(m) > THC_LDS_MAX || thd_slice_wide_lds(m) > THC_LDS_MAX)) --m;
     return m;
 }
 

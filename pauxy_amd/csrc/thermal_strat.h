@@ -20,6 +20,7 @@
 //                             handle by AFQ_THERMAL_STREAMED_GREENS; the same bits as the resident kernel.
 //   thermal_greens_wide_kernel (thermal_wide.h)  the same algorithm with one matrix in LDS and two columns per lane,
 //                             chosen per handle by AFQ_THERMAL_WIDE: a complex walker to M = 95; the same G to rounding.
+//                             With T = double (AFQ_THERMAL_DELAYED, k_thermal.hip) a real walker to M = 128.
 //
 //   thermal_greens_sweep_kernel<T>, thermal_greens_streamed_sweep_kernel<cplx>  the same two engines (their bodies are
 //                             the device functions ts_greens_body / ts_greens_streamed_body, which the kernels above
@@ -531,6 +532,7 @@ inline int th_screen_options(afq_handle *h, const ThEntry &e, int options) {
         AFQ_FAIL(h, AFQ_EINVAL, e.me + "streamed_greens belongs to the continuous fields (the real walkers fit to M = 64 as they are)");
     if (options & AFQ_THERMAL_WIDE & ~e.allowed)
         AFQ_FAIL(h, AFQ_EINVAL, e.me + "wide_basis belongs to the continuous fields (the real walkers work one lane per column, M <= 64)");
+    if (options & AFQ_THERMAL_DELAYED & ~e.allowed) AFQ_FAIL(h, AFQ_EINVAL, e.me + "delayed_updates belongs to the discrete fields");
     if (options & ~e.allowed) AFQ_FAIL(h, AFQ_EINVAL, e.me + "unknown option bits");
     if (!h->kind || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, e.me + "set the system and allocate the walkers first");
     if (h->kind != e.system) AFQ_FAIL(h, AFQ_EUNSUPPORTED, e.system_text);

@@ -1,8 +1,10 @@
-// The stratified Green's function of a complex thermal walker beyond one lane per column (AFQ_THERMAL_WIDE): the
+// The stratified Green's function of a thermal walker beyond one lane per column (T = cplx: AFQ_THERMAL_WIDE, the
+// continuous fields; T = double: AFQ_THERMAL_DELAYED, the discrete fields, thermal_greens_wide_kernel in the trace): the
 // algorithm of thermal_strat.h -- column-pivoted Householder QR of the first bin, norms recomputed every step, ties to
 // the lower index; C = (B Q) D, Q D t = C, T <- t T for every further bin; D split at |D| = 1; one pivoted solve of
-// (D_b Q^H + D_s T) G = D_b Q^H; det G by LU with partial pivoting -- with ONE M x (M | 1) complex matrix in LDS and a
-// lane that owns two columns (c and c + 64), so M <= 128 lanes-wise and M <= 95 by the 160 KiB of a compute unit.
+// (D_b Q^H + D_s T) G = D_b Q^H; det G by LU with partial pivoting -- with ONE M x (M | 1) matrix of T in LDS and a
+// lane that owns two columns (c and c + 64), so M <= 128 lanes-wise; the 160 KiB of a compute unit hold a complex matrix
+// to M = 95 and a real one beyond the lanes (141,824 B at M = 128).
 //
 // Everything but the one matrix lives in the work-group's own scratch in device memory, four [M, M] buffers (pitch M):
 //   Ta, Tb   T, used in turn by T <- t T (ts_gemm with both operands read from scratch by its loaders);
@@ -30,25 +32,26 @@
 
 namespace {
 
-typedef TsScalar<cplx> TwS;
-
 // LDS of the wide Green's kernel: one matrix; D[128], v[128], part[512], aux[384] scalars; perm[128]
-inline size_t ts_greens_wide_lds(int M) { return sizeof(cplx) * (ts_mat(M) + 128 + 128 + 512 + 384) + sizeof(int) * TW_COLS; }
+template <class T> inline size_t ts_greens_wide_lds(int M) { return sizeof(T) * (ts_mat(M) + 128 + 128 + 512 + 384) + sizeof(int) * TW_COLS; }
 // scalars of device scratch per work-group
 __host__ __device__ inline size_t ts_greens_wide_scratch(int M) { return 4 * (size_t)M * M; }
 
-__device__ inline cplx tw_sum4(const cplx *p) { return TwS::add(TwS::add(p[0], p[128]), TwS::add(p[256], p[384])); }
+template <class T> __device__ inline T tw_sum4(const T *p) {
+    typedef TsScalar<T> S;
+    return S::add(S::add(p[0], p[128]), S::add(p[256], p[384]));
+}
 
 // W[j.., cc] <- (I - tau v v^H) W[j.., cc] for the columns cmin <= cc < M, two per lane and four row classes per column;
 // v[j .. M - 1] in LDS, written behind a barrier.  One barrier inside; none behind the update.  part: 512 scalars.
-__device__ inline void tw_reflect_left(cplx *W, int M, int LD, int j, int cmin, const cplx *v, double tau, cplx *part) {
+template <class T> __device__ inline void tw_reflect_left(T *W, int M, int LD, int j, int cmin, const T *v, double tau, T *part) {
     const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int cc = c + 64 * h;
         if (cc >= cmin && cc < M) {
-            cplx s = TwS::zero();
-            for (int i = j + q; i < M; i += 4) TwS::fma(s, TwS::conj(v[i]), W[i * LD + cc]);
+            T s = TsScalar<T>::zero();
+            for (int i = j + q; i < M; i += 4) TsScalar<T>::fma(s, TsScalar<T>::conj(v[i]), W[i * LD + cc]);
             part[q * 128 + cc] = s;
         }
     }
@@ -57,8 +60,8 @@ __device__ inline void tw_reflect_left(cplx *W, int M, int LD, int j, int cmin, 
     for (int h = 0; h < 2; ++h) {
         const int cc = c + 64 * h;
         if (cc >= cmin && cc < M) {
-            const cplx s = TwS::scale(tw_sum4(part + cc), -tau);
-            for (int i = j + q; i < M; i += 4) TwS::fma(W[i * LD + cc], s, v[i]);
+            const T s = TsScalar<T>::scale(tw_sum4<T>(part + cc), -tau);
+            for (int i = j + q; i < M; i += 4) TsScalar<T>::fma(W[i * LD + cc], s, v[i]);
         }
     }
 }
@@ -67,8 +70,8 @@ __device__ inline void tw_reflect_left(cplx *W, int M, int LD, int j, int cmin, 
 // holds R, column j below the diagonal reflector j (v_0 = 1 implied), tau[j] its factor, perm[j] the original column now
 // at position j.  The pivot of step j: the remaining column of the largest norm over the rows j.., recomputed every
 // step, ties to the lower index; every wave runs the search on its own over both columns of its lanes.
-__device__ void tw_qrcp(cplx *W, int M, int LD, int *perm, cplx *v, cplx *part, double *tau) {
-    typedef TwS S;
+template <class T> __device__ void tw_qrcp(T *W, int M, int LD, int *perm, T *v, T *part, double *tau) {
+    typedef TsScalar<T> S;
     const int tid = threadIdx.x, c = tid & 63, q = tid >> 6;
     if (tid < M) perm[tid] = tid;
     __syncthreads();
@@ -79,7 +82,7 @@ __device__ void tw_qrcp(cplx *W, int M, int LD, int *perm, cplx *v, cplx *part, 
             if (cc >= j && cc < M) {
                 double s = 0.0;
                 for (int i = j + q; i < M; i += 4) S::abs2(s, W[i * LD + cc]);
-                part[q * 128 + cc].x = s;
+                S::re(part[q * 128 + cc]) = s;
             }
         }
         __syncthreads();
@@ -89,22 +92,22 @@ __device__ void tw_qrcp(cplx *W, int M, int LD, int *perm, cplx *v, cplx *part, 
         for (int h = 0; h < 2; ++h) {                                // (low column first: a tie stays with it)
             const int cc = c + 64 * h;
             if (cc >= j && cc < M) {
-                const double n = (part[cc].x + part[128 + cc].x) + (part[256 + cc].x + part[384 + cc].x);
+                const double n = (S::re(part[cc]) + S::re(part[128 + cc])) + (S::re(part[256 + cc]) + S::re(part[384 + cc]));
                 if (n > nrm2) { nrm2 = n; piv = cc; }
             }
         }
         ts_wave_argmax(nrm2, piv);
         if (piv != j) {
-            if (tid < M) { const cplx t = W[tid * LD + j]; W[tid * LD + j] = W[tid * LD + piv]; W[tid * LD + piv] = t; }
+            if (tid < M) { const T t = W[tid * LD + j]; W[tid * LD + j] = W[tid * LD + piv]; W[tid * LD + piv] = t; }
             if (tid == TH_THREADS - 1) { const int t = perm[j]; perm[j] = perm[piv]; perm[piv] = t; }
         }
         __syncthreads();
-        const cplx x0 = W[j * LD + j];
+        const T x0 = W[j * LD + j];
         const double nrm = sqrt(nrm2), ax0 = S::abs(x0);
-        const cplx ph = ax0 > 0.0 ? S::unit(x0, ax0) : S::real(1.0);
-        const cplx alpha = S::scale(S::neg(ph), nrm);               // H x = alpha e_0, |x_0 - alpha| = |x_0| + ||x||
+        const T ph = ax0 > 0.0 ? S::unit(x0, ax0) : S::real(1.0);
+        const T alpha = S::scale(S::neg(ph), nrm);                  // H x = alpha e_0, |x_0 - alpha| = |x_0| + ||x||
         const double tj = nrm > 0.0 ? (nrm + ax0) / nrm : 0.0;
-        const cplx den = S::scale(ph, ax0 + nrm);                   // x_0 - alpha, no cancellation
+        const T den = S::scale(ph, ax0 + nrm);                      // x_0 - alpha, no cancellation
         if (tid < M - j)
             v[j + tid] = (tid == 0 || !(nrm > 0.0)) ? S::real(tid == 0 ? 1.0 : 0.0) : S::div(W[(j + tid) * LD + j], den);
         if (tid == 0) tau[j] = tj;
@@ -117,12 +120,12 @@ __device__ void tw_qrcp(cplx *W, int M, int LD, int *perm, cplx *v, cplx *part, 
 }
 
 // Behind tw_qrcp: t = D^-1 R P^T into tdst [M, M] (device), the reflectors transposed into Pn, D = diag R.
-__device__ inline void tw_store_qr(const cplx *W, int M, int LD, const int *perm, cplx *tdst, cplx *Pn, cplx *D) {
-    typedef TwS S;
+template <class T> __device__ inline void tw_store_qr(const T *W, int M, int LD, const int *perm, T *tdst, T *Pn, T *D) {
+    typedef TsScalar<T> S;
     const int tid = threadIdx.x;
     for (int e = tid; e < M * M; e += TH_THREADS) {
         const int i = e / M, j = e % M;
-        const cplx w = W[i * LD + j];
+        const T w = W[i * LD + j];
         tdst[i * M + perm[j]] = j >= i ? S::div(w, W[i * LD + i]) : S::zero();
         if (i > j) Pn[j * M + i] = w;
     }
@@ -131,22 +134,22 @@ __device__ inline void tw_store_qr(const cplx *W, int M, int LD, const int *perm
 }
 
 // reflector j out of Pn into v[j .. M - 1]
-__device__ inline void tw_load_reflector(cplx *v, const cplx *Pn, int M, int j) {
+template <class T> __device__ inline void tw_load_reflector(T *v, const T *Pn, int M, int j) {
     const int tid = threadIdx.x;
-    if (tid < M - j) v[j + tid] = tid == 0 ? TwS::real(1.0) : Pn[j * M + j + tid];
+    if (tid < M - j) v[j + tid] = tid == 0 ? TsScalar<T>::real(1.0) : Pn[j * M + j + tid];
 }
 
 // W <- W H_0 H_1 .. H_(M-1) = W Q: row r of W by the two threads r and r + 128 (the k of even and of odd distance from
 // j), then every element of the trailing columns by the whole work-group.  v0, v1: 128 scalars each, used in turn.
-__device__ void tw_apply_right(cplx *W, int M, int LD, const cplx *Pn, const double *tau, cplx *v0, cplx *v1, cplx *part) {
-    typedef TwS S;
+template <class T> __device__ void tw_apply_right(T *W, int M, int LD, const T *Pn, const double *tau, T *v0, T *v1, T *part) {
+    typedef TsScalar<T> S;
     const int tid = threadIdx.x, r = tid & 127, hh = tid >> 7;
     for (int j = 0; j < M; ++j) {
-        cplx *v = (j & 1) ? v1 : v0;
+        T *v = (j & 1) ? v1 : v0;
         tw_load_reflector(v, Pn, M, j);
         __syncthreads();
         if (r < M) {
-            cplx s = S::zero();
+            T s = S::zero();
             for (int i = j + hh; i < M; i += 2) S::fma(s, W[r * LD + i], v[i]);
             part[hh * 128 + r] = s;
         }
@@ -155,7 +158,7 @@ __device__ void tw_apply_right(cplx *W, int M, int LD, const cplx *Pn, const dou
         const int n = M - j;
         for (int e = tid; e < M * n; e += TH_THREADS) {
             const int rr = e / n, i = j + e % n;
-            const cplx s = S::scale(S::add(part[rr], part[128 + rr]), -tj);
+            const T s = S::scale(S::add(part[rr], part[128 + rr]), -tj);
             S::fma(W[rr * LD + i], s, S::conj(v[i]));
         }
     }
@@ -163,11 +166,11 @@ __device__ void tw_apply_right(cplx *W, int M, int LD, const cplx *Pn, const dou
 }
 
 // W <- Q^H = H_(M-1) .. H_0 I
-__device__ void tw_build_qt(cplx *W, int M, int LD, const cplx *Pn, const double *tau, cplx *v0, cplx *v1, cplx *part) {
+template <class T> __device__ void tw_build_qt(T *W, int M, int LD, const T *Pn, const double *tau, T *v0, T *v1, T *part) {
     const int tid = threadIdx.x;
-    for (int e = tid; e < M * M; e += TH_THREADS) { const int r = e / M, c = e % M; W[r * LD + c] = TwS::real(r == c ? 1.0 : 0.0); }
+    for (int e = tid; e < M * M; e += TH_THREADS) { const int r = e / M, c = e % M; W[r * LD + c] = TsScalar<T>::real(r == c ? 1.0 : 0.0); }
     for (int j = 0; j < M; ++j) {
-        cplx *v = (j & 1) ? v1 : v0;
+        T *v = (j & 1) ? v1 : v0;
         tw_load_reflector(v, Pn, M, j);
         __syncthreads();
         tw_reflect_left(W, M, LD, j, 0, v, tau[j], part);
@@ -178,10 +181,10 @@ __device__ void tw_build_qt(cplx *W, int M, int LD, const cplx *Pn, const double
 // LU of X [M, M] (LDS) with partial (row) pivoting, in place: the multipliers below the diagonal, rows exchanged whole,
 // rperm[i] the original row now at i.  Returns the product of the pivots with the sign of the exchanges (the same value
 // in every thread).  DET: a zero pivot ends the factorisation with 0 (uniform over the work-group).  colv: 128 scalars.
-template <bool DET> __device__ cplx tw_lu(cplx *X, int M, int LD, int *rperm, cplx *colv) {
-    typedef TwS S;
+template <bool DET, class T> __device__ T tw_lu(T *X, int M, int LD, int *rperm, T *colv) {
+    typedef TsScalar<T> S;
     const int tid = threadIdx.x, c = tid & 63;
-    cplx det = S::real(1.0);
+    T det = S::real(1.0);
     if (tid < M) rperm[tid] = tid;
     for (int k = 0; k < M; ++k) {
         double a = -1.0;
@@ -197,15 +200,15 @@ template <bool DET> __device__ cplx tw_lu(cplx *X, int M, int LD, int *rperm, cp
         ts_wave_argmax(a, p);
         __syncthreads();                                  // (every wave has read column k before rows move)
         if (p != k) {
-            if (tid < M) { const cplx t = X[k * LD + tid]; X[k * LD + tid] = X[p * LD + tid]; X[p * LD + tid] = t; }
+            if (tid < M) { const T t = X[k * LD + tid]; X[k * LD + tid] = X[p * LD + tid]; X[p * LD + tid] = t; }
             if (tid == TH_THREADS - 1) { const int t = rperm[k]; rperm[k] = rperm[p]; rperm[p] = t; }
             det = S::neg(det);
         }
         __syncthreads();
-        const cplx piv = X[k * LD + k];                   // (the same value in every thread: uniform branches below)
+        const T piv = X[k * LD + k];                      // (the same value in every thread: uniform branches below)
         det = S::mul(det, piv);
         if (DET && S::is_zero(piv)) return S::zero();
-        if (tid > k && tid < M) { const cplx m = S::div(X[tid * LD + k], piv); colv[tid] = m; X[tid * LD + k] = m; }
+        if (tid > k && tid < M) { const T m = S::div(X[tid * LD + k], piv); colv[tid] = m; X[tid * LD + k] = m; }
         __syncthreads();
         const int n = M - k - 1;
         for (int e = tid; e < n * n; e += TH_THREADS) {
@@ -219,11 +222,11 @@ template <bool DET> __device__ cplx tw_lu(cplx *X, int M, int LD, int *rperm, cp
 
 // L U G = R' with the factors transposed in LUt (device: column k at LUt + k M) and R' [M, M] in LDS, which G
 // overwrites.  c0, c1: 128 scalars each, used in turn; rowr: 128 scalars.
-__device__ void tw_substitute(cplx *R, int M, int LD, const cplx *LUt, cplx *c0, cplx *c1, cplx *rowr) {
-    typedef TwS S;
+template <class T> __device__ void tw_substitute(T *R, int M, int LD, const T *LUt, T *c0, T *c1, T *rowr) {
+    typedef TsScalar<T> S;
     const int tid = threadIdx.x;
     for (int k = 0; k < M - 1; ++k) {                     // L y = R', unit diagonal
-        cplx *cv = (k & 1) ? c1 : c0;
+        T *cv = (k & 1) ? c1 : c0;
         if (tid > k && tid < M) cv[tid] = LUt[k * M + tid];
         __syncthreads();
         const int n = M - k - 1;
@@ -236,7 +239,7 @@ __device__ void tw_substitute(cplx *R, int M, int LD, const cplx *LUt, cplx *c0,
     for (int k = M - 1; k >= 0; --k) {                    // U G = y
         if (tid < k) c0[tid] = LUt[k * M + tid];
         if (tid < M) {
-            const cplx x = S::div(R[k * LD + tid], LUt[k * M + k]);
+            const T x = S::div(R[k * LD + tid], LUt[k * M + k]);
             rowr[tid] = x;
             R[k * LD + tid] = x;
         }
@@ -250,28 +253,29 @@ __device__ void tw_substitute(cplx *R, int M, int LD, const cplx *LUt, cplx *c0,
 }
 
 // The work of one work-group, as ts_greens_body; scr: the work-group's own ts_greens_wide_scratch(M) scalars.
-__device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const cplx *Bw, cplx *scr, int M, int nbins, int first,
-                                                    cplx *Gd, cplx *Gd2, cplx *detd) {
-    typedef TwS S;
+template <class T>
+__device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first,
+                                                    T *Gd, T *Gd2, T *detd) {
+    typedef TsScalar<T> S;
     const int LD = M | 1, tid = threadIdx.x;
     const size_t mat = ts_mat(M);
-    cplx *W = (cplx *)smem;
-    cplx *D = W + mat, *v = D + 128, *part = v + 128, *aux = part + 512;
+    T *W = (T *)smem;
+    T *D = W + mat, *v = D + 128, *part = v + 128, *aux = part + 512;
     int *perm = (int *)(aux + 384);
-    double *tau = (double *)aux;                                     // 128 doubles: aux[0 .. 63]
-    cplx *v1 = aux + 64;                                             // the second reflector buffer: aux[64 .. 191]
+    double *tau = (double *)aux;                                     // 128 doubles: aux[0 .. 63] of cplx, [0 .. 127] of double
+    T *v1 = aux + 128 * sizeof(double) / sizeof(T);                  // the second reflector buffer: the 128 scalars behind tau
     const long mm = (long)M * M;
-    cplx *Tin = scr, *Tout = scr + mm, *Pn = scr + 2 * mm, *Xs = scr + 3 * mm;
+    T *Tin = scr, *Tout = scr + mm, *Pn = scr + 2 * mm, *Xs = scr + 3 * mm;
 
     {
-        const cplx *B = Bw + (long)first * 2 * mm;
+        const T *B = Bw + (long)first * 2 * mm;
         for (int e = tid; e < M * M; e += TH_THREADS) W[(e / M) * LD + e % M] = B[e];
     }
     __syncthreads();
     tw_qrcp(W, M, LD, perm, v, part, tau);
     tw_store_qr(W, M, LD, perm, Tin, Pn, D);                         // T = D^-1 R P^T
     for (int n = 1; n < nbins; ++n) {
-        const cplx *B = Bw + (long)((first + n) % nbins) * 2 * mm;
+        const T *B = Bw + (long)((first + n) % nbins) * 2 * mm;
         for (int e = tid; e < M * M; e += TH_THREADS) W[(e / M) * LD + e % M] = B[e];
         __syncthreads();
         tw_apply_right(W, M, LD, Pn, tau, v, v1, part);              // B Q
@@ -283,21 +287,21 @@ __device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const c
         tw_qrcp(W, M, LD, perm, v, part, tau);
         tw_store_qr(W, M, LD, perm, Xs, Pn, D);
         // T <- t T
-        ts_gemm<cplx>(M, [&](int r, int k) { return Xs[r * M + k]; }, [&](int k, int c) { return Tin[k * M + c]; },
-                      [&](int r, int c, cplx x) { Tout[r * M + c] = x; });
+        ts_gemm<T>(M, [&](int r, int k) { return Xs[r * M + k]; }, [&](int k, int c) { return Tin[k * M + c]; },
+                   [&](int r, int c, T x) { Tout[r * M + c] = x; });
         __syncthreads();
-        cplx *t = Tin; Tin = Tout; Tout = t;
+        T *t = Tin; Tin = Tout; Tout = t;
     }
     // (D_b Q^H + D_s T) G = D_b Q^H, D_b = 1 / |D| and D_s = D / |D| where |D| > 1, else D_b = 1 and D_s = D
     tw_build_qt(W, M, LD, Pn, tau, v, v1, part);
     for (int e = tid; e < M * M; e += TH_THREADS) {
         const int i = e / M, j = e % M;
-        const cplx d = D[i];
+        const T d = D[i];
         const double ad = S::abs(d);
         const double db = ad > 1.0 ? 1.0 / ad : 1.0;
-        const cplx ds = ad > 1.0 ? S::unit(d, ad) : d;
-        const cplx r = S::scale(W[i * LD + j], db);
-        cplx x = r;
+        const T ds = ad > 1.0 ? S::unit(d, ad) : d;
+        const T r = S::scale(W[i * LD + j], db);
+        T x = r;
         S::fma(x, ds, Tin[i * M + j]);
         W[i * LD + j] = x;
         Xs[i * M + j] = r;
@@ -310,35 +314,37 @@ __device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const c
     __syncthreads();
     tw_substitute(W, M, LD, Pn, aux, aux + 128, aux + 256);
     for (int e = tid; e < M * M; e += TH_THREADS) {
-        const cplx g = W[(e / M) * LD + e % M];
+        const T g = W[(e / M) * LD + e % M];
         Gd[e] = g;
         if (Gd2) Gd2[e] = g;
     }
     if (!detd) return;
     __syncthreads();
-    const cplx dg = tw_lu<true>(W, M, LD, perm, aux);
+    const T dg = tw_lu<true>(W, M, LD, perm, aux);
     if (tid == 0) *detd = dg;
 }
 
 // One work-group per (walker, spin), as thermal_greens_streamed_kernel; scratch [gridDim.x, 4, M, M]: block b's at b.
-__global__ __launch_bounds__(TH_THREADS) void thermal_greens_wide_kernel(const cplx *stack, cplx *G, cplx *det, cplx *scratch, int M,
+template <class T>
+__global__ __launch_bounds__(TH_THREADS) void thermal_greens_wide_kernel(const T *stack, T *G, T *det, T *scratch, int M,
                                                                           int nbins, int first, int src_w) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int w = src_w < 0 ? blockIdx.x >> 1 : src_w, s = blockIdx.x & 1;
     const long mm = (long)M * M;
     const long slot = (long)(src_w < 0 ? w : 0) * 2 + s;
-    ts_greens_wide_body(smem, stack + ((long)w * nbins * 2 + s) * mm, scratch + (long)blockIdx.x * ts_greens_wide_scratch(M), M,
+    ts_greens_wide_body<T>(smem, stack + ((long)w * nbins * 2 + s) * mm, scratch + (long)blockIdx.x * ts_greens_wide_scratch(M), M,
                         nbins, first, G + slot * mm, nullptr, det ? det + slot : nullptr);
 }
 
-// Its own name in the trace, as the streamed form has
-inline int ts_launch_greens_wide(afq_handle *h, const cplx *stack, cplx *G, cplx *det, cplx *scratch, int first, int src_w,
+// Its own name in the trace, as the streamed form has; the real walkers' is thermal_greens_wide_kernel
+template <class T>
+inline int ts_launch_greens_wide(afq_handle *h, const T *stack, T *G, T *det, T *scratch, int first, int src_w,
                                  int nblocks) {
     static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-    const size_t lds = ts_greens_wide_lds(h->M);
-    AFQ_HIP(h, afq_raise_lds((const void *)thermal_greens_wide_kernel, lds, lds_set));
-    afq_note_launch(h, "thermal_cgreens_wide_kernel");
-    hipLaunchKernelGGL(thermal_greens_wide_kernel, dim3(nblocks), dim3(TH_THREADS), lds, h->stream, stack, G, det, scratch, h->M,
+    const size_t lds = ts_greens_wide_lds<T>(h->M);
+    AFQ_HIP(h, afq_raise_lds((const void *)thermal_greens_wide_kernel<T>, lds, lds_set));
+    afq_note_launch(h, std::is_same<T, cplx>::value ? "thermal_cgreens_wide_kernel" : "thermal_greens_wide_kernel");
+    hipLaunchKernelGGL(thermal_greens_wide_kernel<T>, dim3(nblocks), dim3(TH_THREADS), lds, h->stream, stack, G, det, scratch, h->M,
                        h->th_nbins, first, src_w);
     AFQ_POST(h);
     return AFQ_OK;

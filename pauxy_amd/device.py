@@ -480,6 +480,12 @@ class AfqDevice(object):
                                                 _p(out.get('one_rdm')), _p(out.get('two_rdm'))))
         return out
 
+    def thermal_device_allocations(self):
+        """Device blocks the handle has allocated so far (afq_thermal_device_allocations)."""
+        out = numpy.zeros(1, dtype=numpy.int64)
+        self._ck(self.lib.afq_thermal_device_allocations(self.h, _p(out)))
+        return int(out[0])
+
     def thermal_set_sweep_budget(self, nbytes=0):
         """Bytes of scratch (G, P and the streamed T) the averaged sweep takes at a time; 0: the library's default."""
         self._ck(self.lib.afq_thermal_set_sweep_budget(self.h, int(nbytes)))

@@ -175,6 +175,9 @@ class Mixed(object):
         then are the last of those Green's functions', as in the reference, whose loop leaves it on the walker."""
         from pauxy_amd import _lib as L
         ns, es = self.names, self.estimates
+        if self.average_gf and getattr(psi, 'delayed_updates', False):         # (before the device is configured)
+            raise NotImplementedError("mixed estimator: average_gf is not supported on a population with delayed_updates "
+                                      "(the sweep kernels are the resident engine's; M <= 64 without the key)")
         psi.ensure_configured()
         if psi.dev.thermal_state()[0] != psi.time_slice:                # (the library evaluates at ITS slice counter)
             raise RuntimeError("mixed estimator: the population's time slice and the library's differ")

@@ -25,6 +25,15 @@ def _wide_max_basis():
         return 95
 
 
+def _delayed_max_basis():
+    """The delayed route's bound as the library computes it from its kernels' LDS (k_thermal.hip) and the 128 columns of
+    two per lane; a library that does not export it, or none built yet, leaves the literal."""
+    try:
+        return int(L.load().afq_thermal_delayed_max_basis())
+    except (L.AfqLibraryError, AttributeError):
+        return 128
+
+
 # The largest basis of the complex walkers by (kind, route): what fits the 160 KiB of LDS of a work-group.  The route is
 # streamed_greens (False / True) or 'wide' (walkers: {wide_basis: True}: one complex matrix in LDS, two columns per lane).
 MAX_BASIS = {
@@ -34,6 +43,8 @@ MAX_BASIS = {
     ('hubbard_continuous', False): 47,   # ts_greens_lds<cplx>
     ('hubbard_continuous', True): 63,    # thd_slice_lds (k_thermal_cplx.hip): two complex matrices and BH1
     ('hubbard_continuous', 'wide'): _wide_max_basis(),    # ts_greens_wide_lds
+    # the real walkers with walkers: {delayed_updates: True}: ts_greens_wide_lds<double> fits, the lanes bind
+    ('discrete', 'delayed'): _delayed_max_basis(),
 }
 # how the refusal speaks of a kind: whose walkers, what M counts, what the slice kernel keeps in LDS
 _BOUND_WORDS = {'planewave': ("thermal walkers", "plane waves", "three complex matrices"),
@@ -167,10 +178,23 @@ class ThermalWalkers(object):
         if self.wide_basis and self.streamed_greens:
             raise NotImplementedError("thermal walkers: wide_basis and streamed_greens are two placements of the same "
                                       "matrices: ask for one")
+        # the slice by delayed updates and the wide real Green's function (k_thermal.hip, AFQ_THERMAL_DELAYED)
+        self.delayed_updates = bool(walker_opts.get('delayed_updates', False))
+        if self.delayed_updates and self.kind != 'discrete':
+            raise NotImplementedError("thermal walkers: delayed_updates belongs to the discrete fields (Hubbard walkers "
+                                      "with Hirsch fields; the complex walkers have wide_basis)")
         if self.kind != 'discrete':
             self._check_bound(self.kind, system.nbasis)
-        if system.nbasis > 64 and not self.wide_basis:
-            raise NotImplementedError("thermal walkers: M = %d > 64 sites is not supported" % system.nbasis)
+        if self.delayed_updates:
+            bound = MAX_BASIS['discrete', 'delayed']
+            if system.nbasis > bound:
+                raise NotImplementedError("thermal walkers: M = %d > %d sites is not supported with delayed_updates (the "
+                                          "wide Green's function works two columns per lane, 128 in all)"
+                                          % (system.nbasis, bound))
+        elif system.nbasis > 64 and not self.wide_basis:
+            raise NotImplementedError("thermal walkers: M = %d > 64 sites is not supported%s" % (
+                system.nbasis, " (walkers: {delayed_updates: True} reaches M = %d)" % MAX_BASIS['discrete', 'delayed']
+                if self.kind == 'discrete' else ""))
         self.nwalkers = qmc.nwalkers
         self.ntot_walkers = qmc.ntot_walkers
         self.walker_type = 'thermal'
@@ -239,7 +263,11 @@ class ThermalWalkers(object):
         if self.configured is not None and self.time_slice != 0:
             raise RuntimeError("thermal walkers: %s changed in the middle of a path"
                                % _CHANGED[kind if self.configured[0] == kind else None])
-        configure(L.THERMAL_WIDE if self.wide_basis else L.THERMAL_STREAMED_GREENS if self.streamed_greens else 0)
+        if self.delayed_updates and kind != 'discrete':
+            raise NotImplementedError("thermal walkers: delayed_updates belongs to the discrete fields (a '%s' "
+                                      "propagator moves complex walkers)" % getattr(prop, 'hs_type', kind))
+        configure(L.THERMAL_WIDE if self.wide_basis else L.THERMAL_STREAMED_GREENS if self.streamed_greens
+                  else L.THERMAL_DELAYED if self.delayed_updates else 0)
         self.kind, self.configured = kind, (kind, key)
 
     def _configure_discrete(self, prop):
@@ -255,7 +283,7 @@ class ThermalWalkers(object):
         def configure(options):
             _, auxf, _, _, BH1 = thermal_constants(self.system, self.trial, self.dt)
             self.dev.thermal_configure(self.num_slices, self.stack_size, nstblz, self.trial.dmat, self.trial.dmat_inv,
-                                       BH1, auxf)
+                                       BH1, auxf, options)
             self.nstblz = nstblz
         return nstblz, configure
 

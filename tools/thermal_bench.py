@@ -7,11 +7,13 @@ The three kernels are timed with event pairs around every launch (afq_launch_tra
   thermal_slice_kernel    the M single-site updates of every walker and its stack update (once per slice)
   thermal_greens_kernel   the stratified G from the stack (every nstblz slices, and once per reset)
   thermal_wrap_kernel     G <- BT G BT^-1 (every slice but the last of a path)
+With --delayed the handle is configured with AFQ_THERMAL_DELAYED and the first two are thermal_slice_delayed_kernel and
+thermal_greens_wide_kernel; --nx / --ny choose the lattice (ny defaults to nx; beyond 64 sites only with --delayed).
 `slice_ms` = all three over the slices run; `path_wall_ms` the host's wall time of a path, uniforms and copies included
 (median and spread over the paths).  The event pairs cost a few microseconds per launch: the wall time is taken in a
 separate pass without them.
 
-  python tools/thermal_bench.py [--paths 5] [--warmup 2] [--stack-size N] [--nstblz N] [--out FILE]
+  python tools/thermal_bench.py [--nx 8] [--ny 8] [--delayed] [--paths 5] [--warmup 2] [--stack-size N] [--nstblz N] [--out FILE]
 """
 import argparse
 import json
@@ -24,12 +26,14 @@ import numpy
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from pauxy_amd import _lib as L_                                          # noqa: E402
 from pauxy_amd.device import AfqDevice                                     # noqa: E402
 from pauxy_amd.propagation.thermal_hubbard import thermal_constants       # noqa: E402
 from pauxy_amd.systems import Hubbard                                      # noqa: E402
 from pauxy_amd.trial_density import OneBody                                # noqa: E402
 
 KERNELS = ('thermal_slice_kernel', 'thermal_greens_kernel', 'thermal_wrap_kernel')
+KERNELS_DELAYED = ('thermal_slice_delayed_kernel', 'thermal_greens_wide_kernel', 'thermal_wrap_kernel')
 
 
 def one_path(dev, rng, L):
@@ -42,6 +46,8 @@ def one_path(dev, rng, L):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--nx', type=int, default=8)
+    ap.add_argument('--ny', type=int, default=None)
+    ap.add_argument('--delayed', action='store_true')
     ap.add_argument('--walkers', type=int, default=256)
     ap.add_argument('--beta', type=float, default=2.0)
     ap.add_argument('--dt', type=float, default=0.05)
@@ -51,8 +57,9 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
-    M = a.nx * a.nx
-    system = Hubbard(a.nx, a.nx, M // 2 - 1, M // 2 - 1, 4.0, mu=1.0)
+    ny = a.ny or a.nx
+    M = a.nx * ny
+    system = Hubbard(a.nx, ny, M // 2 - 1, M // 2 - 1, 4.0, mu=1.0)
     trial = OneBody(system, a.beta, a.dt)
     opts = {} if a.stack_size is None else {'stack_size': a.stack_size}
     ss = opts.get('stack_size', trial.stack_size)
@@ -62,7 +69,8 @@ def main():
     dev = AfqDevice(0)
     dev.set_system_hubbard(numpy.asarray(system.T, dtype=complex), system.U, system.nup, system.ndown)
     dev.walkers_alloc(a.walkers)
-    dev.thermal_configure(L, ss, nstblz, trial.dmat, trial.dmat_inv, BH1, auxf)
+    dev.thermal_configure(L, ss, nstblz, trial.dmat, trial.dmat_inv, BH1, auxf,
+                          L_.THERMAL_DELAYED if a.delayed else 0)
     rng = numpy.random.RandomState(5)
     for _ in range(a.warmup):
         one_path(dev, rng, L)
@@ -76,11 +84,11 @@ def main():
         one_path(dev, rng, L)
     trace = dev.launch_trace_get()
     dev.launch_trace(False)
-    res = {'system': 'Hubbard %dx%d U=4 mu=1' % (a.nx, a.nx), 'M': M, 'walkers': a.walkers, 'beta': a.beta, 'dt': a.dt,
+    res = {'system': 'Hubbard %dx%d U=4 mu=1' % (a.nx, ny), 'M': M, 'route': 'delayed' if a.delayed else 'direct', 'walkers': a.walkers, 'beta': a.beta, 'dt': a.dt,
            'slices': L, 'stack_size': ss, 'nbins': L // ss, 'nstblz': nstblz, 'trial_mu': trial.mu, 'paths': a.paths,
            'kernels': {}}
     total = 0.0
-    for k in KERNELS:
+    for k in (KERNELS_DELAYED if a.delayed else KERNELS):
         n, ms = trace.get(k, (0, 0.0))
         res['kernels'][k] = {'launches': n, 'total_ms': ms, 'mean_ms': ms / n if n else 0.0}
         total += ms
