@@ -237,6 +237,10 @@ int k_prop_fused_supported(afq_handle *h) {
 // Shape class of the closed-shell body with V resident in registers (k_fused_closed.h), and the form the handle asks for
 // (afq_set_propagator_closed_form): closed walkers of any other shape, and all of them in mode 1, take the streamed deal.
 int k_prop_closed_resident(afq_handle *h) {
+    // LDS of the body against the launch's (k_prop_fused): both images of T, psi^H B as A fragments (1 KB per k-step) and the
+    // three partial products of the split deal (4 KB each); a shape that did not fit would take the streamed deal
+    const size_t KS = (h->M + 3) / 4, NCH = (h->M + 7) / 8;
+    if (KS * (2 * 2048 + 1024) + 3 * 4096 > NCH * 8192 + (size_t)PF_D * 16384) return 0;
     return PF_NW == 8 && k_prop_fused_supported(h) && h->prop_closed_mode != 1 && h->bh1_same && h->bh1_real &&
            h->na == h->nb && h->na > 16 && h->na <= 32 && h->M > 96 && h->M <= 104 && h->exp_order > 0;
 }
