@@ -36,7 +36,7 @@ void free_walkers(afq_handle *h) {
     h->msd_fb_gbar = false;
     h->nbp = 0; h->bpo_two = h->bpo_ekt = h->bpo_sf = h->bpo_corr = h->bpo_pair = 0; h->bpo_nL = 0; h->it_nmax = 0;
     h->rdm_on = false; h->sf_on = false;
-    h->th_kind = TH_NONE; h->th_delayed = false;
+    h->th_kind = TH_NONE; h->th_engine = TH_ENGINE_RESIDENT;
     h->nw = 0;
 }
 

@@ -45,6 +45,10 @@ enum { T_GREENS = 0, T_ONEBODY, T_FB, T_VHS, T_EXP, T_OVLP, T_QR, T_ENERGY, T_CO
 // The kind of thermal walker a handle holds: none, real (afq_thermal_configure), complex with a diagonal trial
 // (afq_thermal_configure_continuous), complex with a dense trial (afq_thermal_configure_hubbard_continuous)
 enum ThKind { TH_NONE = 0, TH_REAL, TH_CPLX_DIAG, TH_CPLX_DENSE };
+// Where a thermal handle's Green's function (and, WIDE, its slice kernel) keeps its matrices: the route chosen by the
+// option bits of the configure call.  RESIDENT: all in LDS.  STREAMED (AFQ_THERMAL_STREAMED_GREENS, complex walkers): T in
+// device memory.  WIDE (AFQ_THERMAL_WIDE, complex; AFQ_THERMAL_DELAYED, real): one matrix in LDS, two columns per lane.
+enum ThEngine { TH_ENGINE_RESIDENT = 0, TH_ENGINE_STREAMED, TH_ENGINE_WIDE };
 
 // Whether the hand-over buffers of the handle (t0_next, t0_ready) describe the walkers as they are now.  A launch of the
 // fused propagator that produced sets `current`; everything that writes phi, moves a walker to another slot, changes the
@@ -258,6 +262,11 @@ struct afq_handle {
 
     // ---- finite-temperature walkers (k_thermal.hip; walkers/thermal.py, walkers/stack.py, thermal_propagation/hubbard.py)
     ThKind th_kind = TH_NONE;       // which configure entry point succeeded last: what kind of thermal walker the handle holds
+    ThEngine th_engine = TH_ENGINE_RESIDENT;   // and by which route: set by the configure calls alone
+    // the route's scratch in device memory, in scalars of the walker's kind; allocated by the configure calls alone.
+    // STREAMED: [nw, 2, 2, M, M], T of the Green's kernel, two buffers per work-group; WIDE: [nw, 2, 4, M, M], four per
+    // work-group, of which the wide slice kernels use the walker's first two; RESIDENT: null
+    void *th_scratch = nullptr;
     int th_L = 0, th_ss = 0, th_nbins = 0, th_nstblz = 0;   // time slices, stack_size, bins, stabilisation period
     int th_slice = 0, th_block = 0, th_counter = 0;          // PropagatorStack.time_slice / block / counter (every walker's)
     double th_auxf[2][2];           // [field][spin], the chemical-potential shift folded in
@@ -269,8 +278,6 @@ struct afq_handle {
     double *th_u = nullptr;         // [nw, M] uniforms of the slice
     int *th_fields = nullptr;       // [nw, M] chosen fields (-1: both probabilities vanished)
     double *th_nav = nullptr;       // [nw]
-    bool th_delayed = false;        // AFQ_THERMAL_DELAYED: the delayed slice kernel and the wide real Green's function
-    double *th_wscratch = nullptr;  // [nw, 2, 4, M, M] the wide Green's function's scratch (a delayed handle; else none)
     // continuous fields (k_thermal_cplx.hip; thermal_propagation/planewave.py, continuous.py with hubbard.py:199-250): the
     // walker's matrices are complex, thc_* are its state
     cplx *thc_G = nullptr;          // [nw, 2, M, M]
@@ -286,10 +293,6 @@ struct afq_handle {
     double *thc_BTpow = nullptr;    // BT^stack_size
     double *thc_left = nullptr;     // [stack_size, ..] left_k = BT^stack_size BT_inv^(k + 1)
     double *thc_bh1 = nullptr;      // BH1
-    bool thc_streamed = false;      // AFQ_THERMAL_STREAMED_GREENS: every Green's function by the streamed kernel
-    bool thc_wide = false;          // AFQ_THERMAL_WIDE: the wide Green's function and slice kernels (one matrix in LDS)
-    cplx *thc_tscratch = nullptr;   // [nw, 2, 2, M, M] T of the streamed kernel, two buffers per work-group; wide:
-                                    // [nw, 2, 4, M, M], four per work-group (else null)
     // the dense trial's alone (afq_thermal_configure_hubbard_continuous)
     double thd_mf_const[2] = {1.0, 0.0};   // exp(-dt mf_core) (re, im)
     double thd_sqrt_u = 0.0;        // iu_fac = i sqrt(U)
@@ -429,6 +432,8 @@ struct afq_handle {
 
 inline bool th_thermal(const afq_handle *h) { return h->th_kind != TH_NONE; }
 inline bool th_complex(const afq_handle *h) { return h->th_kind == TH_CPLX_DIAG || h->th_kind == TH_CPLX_DENSE; }
+// AFQ_THERMAL_DELAYED: the real walkers on the wide engine take the delayed slice kernel
+inline bool th_delayed_slice(const afq_handle *h) { return h->th_kind == TH_REAL && h->th_engine == TH_ENGINE_WIDE; }
 
 #define AFQ_HIP(h, call)                                                        \
     do {                                                                        \

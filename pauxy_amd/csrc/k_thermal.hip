@@ -5,7 +5,8 @@
 // of nbins products of stack_size propagators each, f64 [nbins, 2, M, M].  The slice counter, the block and the in-bin
 // counter are the same for every walker and live on the handle; the driver moves the population through the slices
 // together.  M <= 64: a walker's working set stays in LDS.  A handle configured with AFQ_THERMAL_DELAYED takes the second
-// route below and reaches M = 128 = afq_thermal_delayed_max_basis().
+// route below (th_engine WIDE: th_launch_greens<double> and the slice launch read it) and reaches M = 128 =
+// afq_thermal_delayed_max_basis().  Every kernel with dynamic LDS is launched by th_launch (thermal_strat.h).
 //
 //   thermal_greens_kernel   G of every (walker, spin) from the stack: thermal_strat.h's engine with T = double.
 //   thermal_slice_kernel    one work-group per walker, both spins' G in LDS: the M single-site updates of
@@ -24,7 +25,6 @@
 #include <cstring>
 
 #define TH_MAXM 64
-#define TH_LDS_MAX (160 * 1024)
 #define TD_KB 16                // sites per panel of the delayed updates (a multiple of the MFMA's k = 4)
 #define TD_CP (TD_KB + 1)       // pitch of the [M, TD_KB] panels in LDS: a column read walks the banks
 
@@ -321,16 +321,10 @@ int th_delayed_bound() {
     return m;
 }
 
-// G of nblocks / 2 walkers by the engine the handle was configured with
-int th_launch_greens(afq_handle *h, double *G, int first, int src_w, int nblocks) {
-    if (h->th_delayed) return ts_launch_greens_wide<double>(h, h->th_stack, G, nullptr, h->th_wscratch, first, src_w, nblocks);
-    return ts_launch_greens<double>(h, h->th_stack, G, nullptr, first, src_w, nblocks);
-}
-
 }  // namespace
 
 int k_thermal_greens(afq_handle *h, int slice_ix) {
-    return th_launch_greens(h, h->th_G, ts_first_bin(h, slice_ix), -1, 2 * h->nw);
+    return th_launch_greens<double>(h, h->th_stack, h->th_G, nullptr, ts_first_bin(h, slice_ix), -1, dim3(2 * h->nw));
 }
 
 extern "C" {
@@ -346,20 +340,12 @@ int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int n
                         "thermal walkers: Hubbard systems only (no Generic / UEG)", "all"};
     AFQ_TRY(th_screen_options(h, me, options));
     const bool delayed = (options & AFQ_THERMAL_DELAYED) != 0;
-    if (delayed) {
-        const int M = h->M, mmax = th_delayed_bound();
-        const std::string head = "thermal walkers (delayed_updates): M = " + std::to_string(M) + " sites ", tail = " (M <= " + std::to_string(mmax) + ")";
-        const struct { const char *what; size_t bytes; } need[3] = {
-            {"the wide Green's function (thermal_greens_wide_kernel)", ts_greens_wide_lds<double>(M)},
-            {"the delayed slice kernel (thermal_slice_delayed_kernel)", th_slice_delayed_lds(M)},
-            {"the wrap (thermal_wrap_kernel)", th_wrap_lds(M)}};
-        if (M > TW_COLS)
-            AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "are more than the " + std::to_string(TW_COLS) + " columns of a wave, two per lane" + tail);
-        for (const auto &k : need)
-            if (k.bytes > TH_LDS_MAX)
-                AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(k.bytes) + " bytes of LDS for " + k.what +
-                         ", a work-group has " + std::to_string(TH_LDS_MAX) + tail);
-    } else if (h->M > TH_MAXM)
+    if (delayed)
+        AFQ_TRY(th_screen_bound(h, "thermal walkers (delayed_updates)", "sites", TW_COLS, true,
+                                {{"the wide Green's function (thermal_greens_wide_kernel)", ts_greens_wide_lds<double>, ""},
+                                 {"the delayed slice kernel (thermal_slice_delayed_kernel)", th_slice_delayed_lds, ""},
+                                 {"the wrap (thermal_wrap_kernel)", th_wrap_lds, ""}}));
+    else if (h->M > TH_MAXM)
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: M = " + std::to_string(h->M) + " > 64 sites do not fit a work-group's LDS"
                  "; AFQ_THERMAL_DELAYED (delayed_updates) reaches M = " + std::to_string(th_delayed_bound()));
     AFQ_TRY(th_screen_state(h, me, ntime_slices, stack_size, nstblz));
@@ -390,8 +376,8 @@ int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int n
         (rc = dev_alloc(h, LT_WALKERS, &h->th_stack, 2 * mm * n * nbins)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_u, (size_t)M * n)) ||
         (rc = dev_alloc(h, LT_WALKERS, &h->th_fields, (size_t)M * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_nav, n))) return rc;
     // the wide Green's function's scratch, four [M, M] per (walker, spin); a handle configured without the bit holds none
-    if ((rc = dev_alloc(h, LT_WALKERS, &h->th_wscratch, delayed ? 2 * ts_greens_wide_scratch(M) * n : (size_t)0))) return rc;
-    h->th_delayed = delayed;
+    if ((rc = dev_alloc(h, LT_WALKERS, (double **)&h->th_scratch, delayed ? 2 * ts_greens_wide_scratch(M) * n : (size_t)0))) return rc;
+    h->th_engine = delayed ? TH_ENGINE_WIDE : TH_ENGINE_RESIDENT;
     if ((rc = ensure_G(h))) return rc;                  // c128 [nw, 2, M, M]: the one-body density matrices of afq_thermal_energy
     for (int f = 0; f < 2; ++f) for (int s = 0; s < 2; ++s) h->th_auxf[f][s] = auxf[2 * f + s];
     h->th_L = ntime_slices; h->th_ss = stack_size; h->th_nbins = nbins; h->th_nstblz = nstblz;
@@ -417,7 +403,7 @@ int afq_thermal_reset(afq_handle *h) {
     // the trial's G once, from walker 0's fresh bins (every bin is BT^stack_size), then broadcast
     for (int n = 0; n < nbins; ++n)
         AFQ_HIP(h, hipMemcpyAsync(h->th_stack + (long)n * per, h->th_BTpow, sizeof(double) * per, hipMemcpyDeviceToDevice, h->stream));
-    AFQ_TRY(th_launch_greens(h, h->th_G0, ts_first_bin(h, 0), 0, 2));
+    AFQ_TRY(th_launch_greens<double>(h, h->th_stack, h->th_G0, nullptr, ts_first_bin(h, 0), 0, dim3(2)));
     AFQ_LAUNCH(h, thermal_reset_kernel, dim3((unsigned)((per + 255) / 256), h->nw), dim3(256), 0, h->stream, h->th_stack,
                h->th_G, h->weight, h->th_BTpow, h->th_G0, nbins, per, h->nw);
     AFQ_POST(h);
@@ -447,28 +433,14 @@ int afq_thermal_propagate(afq_handle *h, const double *u, int32_t *fields_out, d
     a.fields = h->th_fields; a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
     for (int f = 0; f < 2; ++f) for (int s = 0; s < 2; ++s) { a.auxf[f][s] = h->th_auxf[f][s]; a.delta[f][s] = h->th_auxf[f][s] - 1.0; }
     a.exp_eshift = exp(eshift);
-    if (h->th_delayed) {
-        static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-        const size_t lds = th_slice_delayed_lds(M);
-        AFQ_HIP(h, afq_raise_lds((const void *)thermal_slice_delayed_kernel, lds, lds_set));
-        AFQ_LAUNCH(h, thermal_slice_delayed_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a);
-        AFQ_POST(h);
-    } else {
-        static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-        const size_t lds = th_slice_lds(M);
-        AFQ_HIP(h, afq_raise_lds((const void *)thermal_slice_kernel, lds, lds_set));
-        AFQ_LAUNCH(h, thermal_slice_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a);
-        AFQ_POST(h);
-    }
+    if (th_delayed_slice(h))
+        AFQ_TRY(th_launch<thermal_slice_delayed_kernel>(h, "thermal_slice_delayed_kernel", dim3(h->nw), th_slice_delayed_lds(M), a));
+    else
+        AFQ_TRY(th_launch<thermal_slice_kernel>(h, "thermal_slice_kernel", dim3(h->nw), th_slice_lds(M), a));
     th_advance(h);
     if (h->th_slice % h->th_nstblz == 0) AFQ_TRY(k_thermal_greens(h, h->th_slice - 1));
-    if (h->th_slice < h->th_L) {
-        static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-        AFQ_HIP(h, afq_raise_lds((const void *)thermal_wrap_kernel, th_wrap_lds(M), lds_set));      // (beyond 64 KiB at M > 90)
-        AFQ_LAUNCH(h, thermal_wrap_kernel, dim3(2 * h->nw), dim3(TH_THREADS), th_wrap_lds(M), h->stream, h->th_G, h->th_BT,
-                   h->th_BTinv, M);
-        AFQ_POST(h);
-    }
+    if (h->th_slice < h->th_L)                          // (its LDS is beyond 64 KiB at M > 90)
+        AFQ_TRY(th_launch<thermal_wrap_kernel>(h, "thermal_wrap_kernel", dim3(2 * h->nw), th_wrap_lds(M), h->th_G, h->th_BT, h->th_BTinv, M));
     if (fields_out) return copy_out(h, fields_out, h->th_fields, sizeof(int) * (size_t)M * h->nw);
     return AFQ_OK;
 }
@@ -503,10 +475,9 @@ int afq_thermal_estimates(afq_handle *h, int what, double *cols_out, double *per
     if (two && h->th_kind != TH_CPLX_DIAG)
         AFQ_FAIL(h, AFQ_EUNSUPPORTED, "afq_thermal_estimates: two_rdm is the structure factor of the UEG walkers (no Hubbard)");
     const bool cx = th_complex(h);
-    if (avg && !cx && h->th_delayed)
-        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "afq_thermal_estimates: average_gf is not supported on a delayed_updates handle (AFQ_THERMAL_DELAYED has no sweep kernel)");
-    if (avg && cx && h->thc_wide)
-        AFQ_FAIL(h, AFQ_EUNSUPPORTED, "afq_thermal_estimates: average_gf is not supported on a wide_basis handle (AFQ_THERMAL_WIDE has no sweep kernel)");
+    if (avg && h->th_engine == TH_ENGINE_WIDE)
+        AFQ_FAIL(h, AFQ_EUNSUPPORTED, cx ? "afq_thermal_estimates: average_gf is not supported on a wide_basis handle (AFQ_THERMAL_WIDE has no sweep kernel)"
+                                         : "afq_thermal_estimates: average_gf is not supported on a delayed_updates handle (AFQ_THERMAL_DELAYED has no sweep kernel)");
     const int M = h->M, nw = h->nw, nbins = h->th_nbins, nbt = avg ? nbins : 1;
     const size_t mm = (size_t)M * M, n = nw, nq4 = two ? 4 * (size_t)h->nq : 0;
     // the small results, fetched in one copy: cols [nw, 4], per_bin [nbt, nw, 4], one_rdm [2, M, M], two_rdm c128 [2, 2, nq];
@@ -529,7 +500,7 @@ int afq_thermal_estimates(afq_handle *h, int what, double *cols_out, double *per
     } else {
         // G [cb, nw, 2, M, M], P c128 of the same shape and, streamed, T [cb, 2 nw, 2, M, M]: cb whole bins under the budget
         const size_t gsz = cx ? sizeof(cplx) : sizeof(double);
-        const size_t b_P = sizeof(cplx) * 2 * mm * n, b_G = gsz * 2 * mm * n, b_T = h->thc_streamed && cx ? sizeof(cplx) * 4 * mm * n : 0;
+        const size_t b_P = sizeof(cplx) * 2 * mm * n, b_G = gsz * 2 * mm * n, b_T = h->th_engine == TH_ENGINE_STREAMED ? sizeof(cplx) * 4 * mm * n : 0;
         const size_t budget = h->th_sw_budget ? h->th_sw_budget : TH_SWEEP_BUDGET;
         size_t cb = budget / (b_P + b_G + b_T);
         cb = cb < 1 ? 1 : cb > (size_t)nbins ? (size_t)nbins : cb;
@@ -544,7 +515,7 @@ int afq_thermal_estimates(afq_handle *h, int what, double *cols_out, double *per
                 AFQ_TRY(k_thermal_c_sweep_greens(h, (cplx *)Gs, Ts, ts0, nb));
                 AFQ_TRY(k_thermal_c_sweep_rdm(h, (const cplx *)Gs, P, nav + (size_t)ts0 * n, nb * nw));
             } else {
-                AFQ_TRY(ts_launch_greens_sweep<double>(h, h->th_stack, (double *)Gs, h->th_G, nullptr, ts0, nb));
+                AFQ_TRY(th_launch_greens<double>(h, h->th_stack, h->th_G, nullptr, 0, -1, dim3(2 * nw, nb), (double *)Gs, nullptr, ts0));
                 AFQ_TRY(ts_launch_rdm_n<double>(h, (const double *)Gs, P, nav + (size_t)ts0 * n, nb * nw));
             }
             AFQ_TRY(th_energy_n(h, P, nb * nw, E + 3 * (size_t)ts0 * n, &two_src));

@@ -5,14 +5,17 @@
 // `right` c128 [2, M, M] and M0_s = det G_s c128 [2].  The slice counter, the block and the in-bin counter are the
 // handle's, as for the real walkers of k_thermal.hip.  A walker's working set stays in LDS: 4 complex matrices of pitch
 // M | 1, which the 160 KiB of a compute unit hold up to M = 47 (the plane-wave shells: 7, 19, 27, 33; 57 does not fit).
-// With AFQ_THERMAL_STREAMED_GREENS the Green's function keeps 2 matrices in LDS and T in the handle's thc_tscratch; the
+// With AFQ_THERMAL_STREAMED_GREENS the Green's function keeps 2 matrices in LDS and T in the handle's th_scratch; the
 // bound is then the slice kernel's three matrices: M = 57, the next shell.  81 is refused on both of these routes.
-// With AFQ_THERMAL_WIDE the handle takes a third route: thermal_wide.h's engine and the two wide slice kernels below
-// keep ONE complex matrix in LDS and the rest in thc_tscratch, and a lane owns two columns: M <= 95, which holds the
-// shells of 81 and 93 plane waves and the Hubbard lattices to 9 x 9.
+// With AFQ_THERMAL_WIDE the handle takes a third route: thermal_wide.h's engine and the wide instantiations of the two
+// slice kernels below keep ONE complex matrix in LDS and the rest in th_scratch, and a lane owns two columns: M <= 95,
+// which holds the shells of 81 and 93 plane waves and the Hubbard lattices to 9 x 9.
+// The route is the handle's th_engine: th_launch_greens<cplx> (thermal_wide.h) and the two slice launches read it, and
+// nothing else does.  The names below are the launch trace's; each slice kernel is one template over where its matrices
+// live (IN_LDS, or one matrix in LDS and the rest in th_scratch).
 //
 //   thermal_cgreens_kernel  G and det G of every (walker, spin) from the stack: thermal_strat.h's engine with T = cplx.
-//   thermal_cgreens_streamed_kernel  the same from thermal_strat.h's streamed form, for a handle configured with the bit.
+//   thermal_cgreens_streamed_kernel  the same with the streamed placement, for a handle configured with the bit.
 //   thermal_cgreens_wide_kernel  thermal_wide.h's engine, for a handle configured with AFQ_THERMAL_WIDE.
 //   thermal_cslice_wide_kernel, thermal_cslice_dense_wide_kernel  the two slice kernels below with one matrix in LDS.
 //   thermal_cslice_kernel   one work-group per walker: BV = sum_{n <= 6} VHS^n / n! by five Horner products in LDS,
@@ -35,7 +38,6 @@
 #include "thermal_wide.h"
 #include <cstring>
 
-#define THC_LDS_MAX (160 * 1024)
 #define THC_LANES 64            // the engine works lane = column
 
 namespace {
@@ -49,29 +51,45 @@ struct ThcSliceArgs {
     int M, nbins, block, counter;
 };
 
-__global__ __launch_bounds__(TH_THREADS) void thermal_cslice_kernel(ThcSliceArgs a) {
+// One matrix in LDS (AFQ_THERMAL_WIDE): V alone; the Horner iterates live in the walker's scratch in device memory
+inline size_t thc_slice_wide_lds(int M) { return sizeof(cplx) * ts_mat(M); }
+
+// One work-group per walker.  V, the A operand of all five Horner products, is in LDS.  IN_LDS: so are the Horner
+// iterates T_n, two matrices of pitch M | 1 used in turn, and BV = T_1 is read where it is.  Otherwise (the wide route)
+// the T_n live in two [M, M] buffers of the walker's scratch (scratch + w stride, pitch M; a work-group reads back only
+// what it wrote, across a barrier), and behind the Horner chain BV takes V's place in LDS as the A operand of
+// right <- B right.  Every element goes through the same operations in the same order -- the same ts_gemm with other
+// loaders -- so the two instantiations give the same bits where both run.
+template <bool IN_LDS> __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_kernel(ThcSliceArgs a, cplx *scratch, long stride) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int M = a.M, LD = M | 1, tid = threadIdx.x, w = blockIdx.x;
     const size_t mat = ts_mat(M);
-    cplx *V = (cplx *)smem, *T1 = V + mat, *T2 = T1 + mat;
     const long mm = (long)M * M;
+    cplx *V = (cplx *)smem;
+    TsMatView<cplx> T1 = {V + mat, LD}, T2 = {V + 2 * mat, LD};
+    if (!IN_LDS) { T1 = {scratch + (long)w * stride, M}; T2 = {T1.p + mm, M}; }
     const cplx *Vw = a.vhs + (long)w * mm;
     // Horner: T_6 = I + V / 6, T_n = I + V T_{n + 1} / n, BV = T_1
     for (int e = tid; e < M * M; e += TH_THREADS) {
         const int r = e / M, c = e % M;
         const cplx x = Vw[e];
         V[r * LD + c] = x;
-        T1[r * LD + c] = cmake(x.x / 6.0 + (r == c ? 1.0 : 0.0), x.y / 6.0);
+        T1(r, c) = cmake(x.x / 6.0 + (r == c ? 1.0 : 0.0), x.y / 6.0);
     }
     __syncthreads();
     for (int n = 5; n >= 1; --n) {
         const double dn = (double)n;
-        ts_gemm<cplx>(M, [&](int r, int k) { return V[r * LD + k]; }, [&](int k, int c) { return T1[k * LD + c]; },
-                 [&](int r, int c, cplx x) { T2[r * LD + c] = cmake(x.x / dn + (r == c ? 1.0 : 0.0), x.y / dn); });
+        ts_gemm<cplx>(M, [&](int r, int k) { return V[r * LD + k]; }, [&](int k, int c) { return T1(k, c); },
+                 [&](int r, int c, cplx x) { T2(r, c) = cmake(x.x / dn + (r == c ? 1.0 : 0.0), x.y / dn); });
         __syncthreads();
-        cplx *t = T1; T1 = T2; T2 = t;
+        const TsMatView<cplx> t = T1; T1 = T2; T2 = t;
     }
-    const cplx *BV = T1;
+    TsMatView<cplx> BV = T1;
+    if (!IN_LDS) {
+        for (int e = tid; e < M * M; e += TH_THREADS) V[(e / M) * LD + e % M] = T1.p[e];
+        __syncthreads();
+        BV = {V, LD};
+    }
     for (int s = 0; s < 2; ++s) {
         const double *d = a.bh1 + s * M, *lf = a.left + s * M;
         cplx *R = a.right + ((long)w * 2 + s) * mm;
@@ -80,74 +98,20 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_kernel(ThcSliceArgs
         if (a.counter == 0) {
             for (int e = tid; e < M * M; e += TH_THREADS) {
                 const int r = e / M, c = e % M;
-                T2[r * LD + c] = cscale(cscale(BV[r * LD + c], d[c]), d[r]);
-            }
-        } else {
-            ts_gemm<cplx>(M, [&](int r, int k) { return cscale(cscale(BV[r * LD + k], d[k]), d[r]); },
-                     [&](int k, int c) { return R[k * M + c]; }, [&](int r, int c, cplx x) { T2[r * LD + c] = x; });
-        }
-        __syncthreads();
-        for (int e = tid; e < M * M; e += TH_THREADS) {
-            const int r = e / M, c = e % M;
-            const cplx x = T2[r * LD + c];
-            R[e] = x;
-            S[e] = cscale(x, lf[r]);
-        }
-        __syncthreads();
-    }
-}
-
-// thermal_cslice_kernel with one matrix in LDS (AFQ_THERMAL_WIDE): V, the A operand of all five Horner products, stays
-// in LDS; the Horner iterates T_n live in two [M, M] buffers of the walker's scratch in device memory, used in turn (a
-// work-group reads back only what it wrote, across a barrier).  Behind the Horner chain BV takes V's place in LDS as the
-// A operand of right <- B right.  Every element goes through thermal_cslice_kernel's operations in their order -- the
-// same ts_gemm with other loaders -- so the two kernels give the same bits where both run.
-inline size_t thc_slice_wide_lds(int M) { return sizeof(cplx) * ts_mat(M); }
-
-__global__ __launch_bounds__(TH_THREADS) void thermal_cslice_wide_kernel(ThcSliceArgs a, cplx *scratch, long stride) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int M = a.M, LD = M | 1, tid = threadIdx.x, w = blockIdx.x;
-    cplx *V = (cplx *)smem;
-    const long mm = (long)M * M;
-    cplx *T1 = scratch + (long)w * stride, *T2 = T1 + mm;           // pitch M
-    const cplx *Vw = a.vhs + (long)w * mm;
-    for (int e = tid; e < M * M; e += TH_THREADS) {
-        const int r = e / M, c = e % M;
-        const cplx x = Vw[e];
-        V[r * LD + c] = x;
-        T1[e] = cmake(x.x / 6.0 + (r == c ? 1.0 : 0.0), x.y / 6.0);
-    }
-    __syncthreads();
-    for (int n = 5; n >= 1; --n) {
-        const double dn = (double)n;
-        ts_gemm<cplx>(M, [&](int r, int k) { return V[r * LD + k]; }, [&](int k, int c) { return T1[k * M + c]; },
-                 [&](int r, int c, cplx x) { T2[r * M + c] = cmake(x.x / dn + (r == c ? 1.0 : 0.0), x.y / dn); });
-        __syncthreads();
-        cplx *t = T1; T1 = T2; T2 = t;
-    }
-    for (int e = tid; e < M * M; e += TH_THREADS) V[(e / M) * LD + e % M] = T1[e];
-    __syncthreads();
-    const cplx *BV = V;
-    for (int s = 0; s < 2; ++s) {
-        const double *d = a.bh1 + s * M, *lf = a.left + s * M;
-        cplx *R = a.right + ((long)w * 2 + s) * mm;
-        cplx *S = a.stack + (((long)w * a.nbins + a.block) * 2 + s) * mm;
-        if (a.counter == 0) {
-            for (int e = tid; e < M * M; e += TH_THREADS) {
-                const int r = e / M, c = e % M;
-                const cplx x = cscale(cscale(BV[r * LD + c], d[c]), d[r]);
+                const cplx x = cscale(cscale(BV(r, c), d[c]), d[r]);
                 R[e] = x;
                 S[e] = cscale(x, lf[r]);
             }
             continue;
         }
-        ts_gemm<cplx>(M, [&](int r, int k) { return cscale(cscale(BV[r * LD + k], d[k]), d[r]); },
-                 [&](int k, int c) { return R[k * M + c]; }, [&](int r, int c, cplx x) { T2[r * M + c] = x; });
+        ts_gemm<cplx>(M, [&](int r, int k) { return cscale(cscale(BV(r, k), d[k]), d[r]); },
+                 [&](int k, int c) { return R[k * M + c]; }, [&](int r, int c, cplx x) { T2(r, c) = x; });
         __syncthreads();
         for (int e = tid; e < M * M; e += TH_THREADS) {
-            const cplx x = T2[e];
+            const int r = e / M, c = e % M;
+            const cplx x = T2(r, c);
             R[e] = x;
-            S[e] = cscale(x, lf[e / M]);
+            S[e] = cscale(x, lf[r]);
         }
         __syncthreads();
     }
@@ -318,15 +282,41 @@ __device__ inline void thd_gemm_rc(int M, LA la, LB lb, ST st) {
     }
 }
 
+// LDS of the slice kernel with one staging matrix (AFQ_THERMAL_WIDE): the matrix and bv[128]
+inline size_t thd_slice_wide_lds(int M) { return sizeof(cplx) * (ts_mat(M) + TW_COLS); }
+
+// An operand of the next product where the product can read it.  IN_LDS: where it is.  Otherwise it is copied from the
+// walker's scratch into the one staging matrix Z in LDS, behind a barrier.  `also`, where given, gets a copy in device
+// memory on the way (pitch M).
+template <bool IN_LDS> __device__ inline TsMatView<cplx> thd_staged(TsMatView<cplx> src, cplx *Z, cplx *also, int M) {
+    if (IN_LDS && !also) return src;
+    const int LD = M | 1;
+    for (int e = threadIdx.x; e < M * M; e += TH_THREADS) {
+        const int r = e / M, c = e % M;
+        const cplx x = src(r, c);
+        if (also) also[e] = x;
+        if (!IN_LDS) Z[r * LD + c] = x;
+    }
+    if (IN_LDS) return src;
+    __syncthreads();
+    return {Z, LD};
+}
+
 // One work-group per walker.  Per spin: B = BH1 (BV BH1) with the diagonal BV folded into the loader of the product's
 // complex operand; right <- B right (right = B at in-bin counter 0); bin[block] = left_k right.
-__global__ __launch_bounds__(TH_THREADS) void thermal_cslice_dense_kernel(ThdSliceArgs a) {
+// IN_LDS: B and the new right are two complex matrices in LDS, beside bv[64] and BH1_s (real).  Otherwise (the wide
+// route) one staging matrix in LDS holds in turn BH1_s, B_s (the A operand of right <- B right) and the new right (the B
+// operand of left_k right); B_s and the new right pass through two [M, M] buffers of the walker's scratch in device
+// memory (scratch + w stride, pitch M).  The products are the same with other loaders: the same bits where both run.
+template <bool IN_LDS> __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_dense_kernel(ThdSliceArgs a, cplx *scratch, long stride) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int M = a.M, LD = M | 1, tid = threadIdx.x, w = blockIdx.x;
     const size_t mat = ts_mat(M);
-    cplx *B = (cplx *)smem, *T2 = B + mat, *bv = T2 + mat;
-    double *H = (double *)(bv + 64);
     const long mm = (long)M * M;
+    cplx *Z = (cplx *)smem, *bv = Z + (IN_LDS ? 2 : 1) * mat;
+    double *H = IN_LDS ? (double *)(bv + 64) : (double *)Z;
+    TsMatView<cplx> B = {Z, LD}, T2 = {Z + mat, LD};
+    if (!IN_LDS) { B = {scratch + (long)w * stride, M}; T2 = {B.p + mm, M}; }
     if (tid < M) bv[tid] = a.bv[(long)w * M + tid];
     for (int s = 0; s < 2; ++s) {
         const double *Hs = a.bh1 + s * mm, *lf = a.left + s * mm;
@@ -335,62 +325,18 @@ __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_dense_kernel(ThdSli
         for (int e = tid; e < M * M; e += TH_THREADS) H[(e / M) * LD + e % M] = Hs[e];
         __syncthreads();
         thd_gemm_rc(M, [&](int r, int k) { return H[r * LD + k]; }, [&](int k, int c) { return cscale(bv[k], H[k * LD + c]); },
-                    [&](int r, int c, cplx x) { B[r * LD + c] = x; });
+                    [&](int r, int c, cplx x) { B(r, c) = x; });
         __syncthreads();
-        const cplx *Rn = B;
+        TsMatView<cplx> Rn = B;
         if (a.counter != 0) {
-            ts_gemm<cplx>(M, [&](int r, int k) { return B[r * LD + k]; }, [&](int k, int c) { return R[k * M + c]; },
-                          [&](int r, int c, cplx x) { T2[r * LD + c] = x; });
+            const TsMatView<cplx> Bs = thd_staged<IN_LDS>(B, Z, nullptr, M);
+            ts_gemm<cplx>(M, [&](int r, int k) { return Bs(r, k); }, [&](int k, int c) { return R[k * M + c]; },
+                          [&](int r, int c, cplx x) { T2(r, c) = x; });
             __syncthreads();
             Rn = T2;
         }
-        for (int e = tid; e < M * M; e += TH_THREADS) R[e] = Rn[(e / M) * LD + e % M];
-        thd_gemm_rc(M, [&](int r, int k) { return lf[r * M + k]; }, [&](int k, int c) { return Rn[k * LD + c]; },
-                    [&](int r, int c, cplx x) { S[r * M + c] = x; });
-        __syncthreads();
-    }
-}
-
-// thermal_cslice_dense_kernel with one staging matrix in LDS (AFQ_THERMAL_WIDE), which holds in turn BH1_s (real, the
-// operand of both products that make B_s), B_s (the A operand of right <- B right) and the new right (the B operand of
-// left_k right); B_s and the new right pass through two [M, M] buffers of the walker's scratch in device memory.  The
-// products are thermal_cslice_dense_kernel's with other loaders: the same bits where both run.
-inline size_t thd_slice_wide_lds(int M) { return sizeof(cplx) * (ts_mat(M) + TW_COLS); }
-
-__global__ __launch_bounds__(TH_THREADS) void thermal_cslice_dense_wide_kernel(ThdSliceArgs a, cplx *scratch, long stride) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int M = a.M, LD = M | 1, tid = threadIdx.x, w = blockIdx.x;
-    const size_t mat = ts_mat(M);
-    cplx *Z = (cplx *)smem, *bv = Z + mat;
-    double *H = (double *)Z;
-    const long mm = (long)M * M;
-    cplx *B0 = scratch + (long)w * stride, *B1 = B0 + mm;           // pitch M
-    if (tid < M) bv[tid] = a.bv[(long)w * M + tid];
-    for (int s = 0; s < 2; ++s) {
-        const double *Hs = a.bh1 + s * mm, *lf = a.left + s * mm;
-        cplx *R = a.right + ((long)w * 2 + s) * mm;
-        cplx *S = a.stack + (((long)w * a.nbins + a.block) * 2 + s) * mm;
-        for (int e = tid; e < M * M; e += TH_THREADS) H[(e / M) * LD + e % M] = Hs[e];
-        __syncthreads();
-        thd_gemm_rc(M, [&](int r, int k) { return H[r * LD + k]; }, [&](int k, int c) { return cscale(bv[k], H[k * LD + c]); },
-                    [&](int r, int c, cplx x) { B0[r * M + c] = x; });
-        __syncthreads();
-        const cplx *Rn = B0;
-        if (a.counter != 0) {
-            for (int e = tid; e < M * M; e += TH_THREADS) Z[(e / M) * LD + e % M] = B0[e];
-            __syncthreads();
-            ts_gemm<cplx>(M, [&](int r, int k) { return Z[r * LD + k]; }, [&](int k, int c) { return R[k * M + c]; },
-                          [&](int r, int c, cplx x) { B1[r * M + c] = x; });
-            __syncthreads();
-            Rn = B1;
-        }
-        for (int e = tid; e < M * M; e += TH_THREADS) {
-            const cplx x = Rn[e];
-            R[e] = x;
-            Z[(e / M) * LD + e % M] = x;
-        }
-        __syncthreads();
-        thd_gemm_rc(M, [&](int r, int k) { return lf[r * M + k]; }, [&](int k, int c) { return Z[k * LD + c]; },
+        const TsMatView<cplx> Rs = thd_staged<IN_LDS>(Rn, Z, R, M);
+        thd_gemm_rc(M, [&](int r, int k) { return lf[r * M + k]; }, [&](int k, int c) { return Rs(k, c); },
                     [&](int r, int c, cplx x) { S[r * M + c] = x; });
         __syncthreads();
     }
@@ -450,17 +396,8 @@ __global__ void thermal_creset_kernel(cplx *stack, cplx *G, cplx *right, cplx *M
 
 }  // namespace
 
-// G and det of nblocks / 2 walkers by the engine the handle was configured with
-static int thc_launch_greens(afq_handle *h, cplx *G, cplx *det, int first, int src_w, int nblocks) {
-    if (h->thc_wide)
-        return ts_launch_greens_wide<cplx>(h, h->thc_stack, G, det, h->thc_tscratch, first, src_w, nblocks);
-    if (h->thc_streamed)
-        return ts_launch_greens_streamed<cplx>(h, h->thc_stack, G, det, h->thc_tscratch, first, src_w, nblocks);
-    return ts_launch_greens<cplx>(h, h->thc_stack, G, det, first, src_w, nblocks);
-}
-
 int k_thermal_c_greens(afq_handle *h, int slice_ix) {
-    return thc_launch_greens(h, h->thc_G, h->thc_det, ts_first_bin(h, slice_ix), -1, 2 * h->nw);
+    return th_launch_greens<cplx>(h, h->thc_stack, h->thc_G, h->thc_det, ts_first_bin(h, slice_ix), -1, dim3(2 * h->nw));
 }
 
 // walkers/handler.py:424-430: bins, G, weight.  The reference's reset leaves walker.M0 at the determinant the last path
@@ -473,7 +410,7 @@ int k_thermal_c_reset(afq_handle *h, bool with_m0) {
     AFQ_LAUNCH(h, thermal_creset_kernel, dim3((unsigned)((per + 255) / 256), 1), dim3(256), 0, h->stream, h->thc_stack, h->thc_G,
                h->thc_right, h->thc_M0, h->weight, h->thc_BTpow, h->thc_G0, h->thc_M00, nbins, M, 1, 0, dense);
     AFQ_POST(h);
-    AFQ_TRY(thc_launch_greens(h, h->thc_G0, h->thc_M00, ts_first_bin(h, 0), 0, 2));
+    AFQ_TRY(th_launch_greens<cplx>(h, h->thc_stack, h->thc_G0, h->thc_M00, ts_first_bin(h, 0), 0, dim3(2)));
     AFQ_LAUNCH(h, thermal_creset_kernel, dim3((unsigned)((per + 255) / 256), h->nw), dim3(256), 0, h->stream, h->thc_stack,
                h->thc_G, h->thc_right, h->thc_M0, h->weight, h->thc_BTpow, h->thc_G0, h->thc_M00, nbins, M, 0, with_m0 ? 1 : 0, dense);
     AFQ_POST(h);
@@ -482,8 +419,7 @@ int k_thermal_c_reset(afq_handle *h, bool with_m0) {
 }
 
 int k_thermal_c_sweep_greens(afq_handle *h, cplx *Gs, cplx *Ts, int ts0, int nb) {
-    if (h->thc_streamed) return ts_launch_greens_streamed_sweep<cplx>(h, h->thc_stack, Gs, h->thc_G, h->thc_det, Ts, ts0, nb);
-    return ts_launch_greens_sweep<cplx>(h, h->thc_stack, Gs, h->thc_G, h->thc_det, ts0, nb);
+    return th_launch_greens<cplx>(h, h->thc_stack, h->thc_G, h->thc_det, 0, -1, dim3(2 * h->nw, nb), Gs, Ts, ts0);
 }
 
 int k_thermal_c_sweep_rdm(afq_handle *h, const cplx *Gs, cplx *P, double *nav, int n) { return ts_launch_rdm_n<cplx>(h, Gs, P, nav, n); }
@@ -504,55 +440,30 @@ namespace {
 
 // ---- configuring: what the two entry points share
 
-// One kernel's LDS as the refusal words it: "need <bytes(M)> bytes of LDS for <what>, a work-group has .. <hint>"
-struct ThcLds {
-    const char *what;
-    size_t (*bytes)(int M);
-    const char *hint;
-};
 const char *const THC_RESIDENT_HINT = "; AFQ_THERMAL_STREAMED_GREENS (streamed_greens) keeps T in device memory and reaches further";
 
-// Which Green's function and slice kernels a handle runs: chosen by the option bits of its configuration.
-enum ThcRoute { THC_RESIDENT, THC_STREAMED, THC_WIDE };
-
 // STREAMED_GREENS and WIDE name two placements of the same working set: together they mean nothing
-int thc_route_of(afq_handle *h, const std::string &me, int options, ThcRoute *route) {
+int thc_engine_of(afq_handle *h, const std::string &me, int options, ThEngine *engine) {
     const bool streamed = (options & AFQ_THERMAL_STREAMED_GREENS) != 0, wide = (options & AFQ_THERMAL_WIDE) != 0;
     if (streamed && wide)
         AFQ_FAIL(h, AFQ_EINVAL, me + "wide_basis and streamed_greens are two placements of the same matrices: ask for one");
-    *route = wide ? THC_WIDE : streamed ? THC_STREAMED : THC_RESIDENT;
+    *engine = wide ? TH_ENGINE_WIDE : streamed ? TH_ENGINE_STREAMED : TH_ENGINE_RESIDENT;
     return AFQ_OK;
 }
 
-const ThcLds THC_WIDE_GREENS = {"the wide Green's function (thermal_cgreens_wide_kernel)", ts_greens_wide_lds<cplx>, ""};
+const ThLds THC_WIDE_GREENS = {"the wide Green's function (thermal_cgreens_wide_kernel)", ts_greens_wide_lds<cplx>, ""};
 
-// M within what every kernel of `need` and lane = column hold; else the refusal names the first of them that does not
-// fit, with its bytes, and the largest M that passes.  who: "" or ", Hubbard"; unit: what M counts.
-int thc_screen_bound(afq_handle *h, const char *who, const char *unit, ThcRoute route, std::initializer_list<ThcLds> need) {
-    const int lanes = route == THC_WIDE ? TW_COLS : THC_LANES;       // (wide: two columns per lane)
-    auto fits = [&](int m) {
-        for (const ThcLds &k : need)
-            if (k.bytes(m) > THC_LDS_MAX) return false;
-        return m <= lanes;
-    };
-    const int M = h->M;
-    if (fits(M)) return AFQ_OK;
-    int mmax = M;
-    while (mmax > 1 && !fits(mmax)) --mmax;
-    const std::string head = std::string("thermal walkers with continuous fields") + who + (route == THC_STREAMED ? " (streamed_greens)" : route == THC_WIDE ? " (wide_basis)" : "") +
-                             ": M = " + std::to_string(M) + " " + unit + " ";
-    const std::string tail = " (M <= " + std::to_string(mmax) + ")";
-    for (const ThcLds &k : need)
-        if (k.bytes(M) > THC_LDS_MAX)
-            AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(k.bytes(M)) + " bytes of LDS for " + k.what +
-                     ", a work-group has " + std::to_string(THC_LDS_MAX) + tail + k.hint);
-    AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "are more than the " + (route == THC_WIDE ? std::to_string(TW_COLS) + " columns of a wave, two per lane"
-                                                                          : std::to_string(THC_LANES) + " lanes of a wave, one per column") + tail);
+// th_screen_bound in the words of the continuous fields: the kernels first, then lane = column (wide: two columns per
+// lane).  who: "" or ", Hubbard"; unit: what M counts.
+int thc_screen_bound(afq_handle *h, const char *who, const char *unit, ThEngine engine, std::initializer_list<ThLds> need) {
+    return th_screen_bound(h, std::string("thermal walkers with continuous fields") + who +
+                           (engine == TH_ENGINE_STREAMED ? " (streamed_greens)" : engine == TH_ENGINE_WIDE ? " (wide_basis)" : ""),
+                           unit, engine == TH_ENGINE_WIDE ? TW_COLS : THC_LANES, false, need);
 }
 
 // Behind an entry point's own checks: its host-built tables (`per` numbers per slice: 2 M diagonals or 2 M M), the
 // walkers' buffers, the path's shape, the kind, and a fresh population.
-int thc_configure_common(afq_handle *h, ThKind kind, int ntime_slices, int stack_size, double dt, ThcRoute route, double fb_bound,
+int thc_configure_common(afq_handle *h, ThKind kind, int ntime_slices, int stack_size, double dt, ThEngine engine, double fb_bound,
                          const double *BTpow, const double *left, const double *bh1, size_t per, const double *mf_shift) {
     const size_t mm = (size_t)h->M * h->M, n = h->nw;
     const int nbins = ntime_slices / stack_size;
@@ -567,13 +478,9 @@ int thc_configure_common(afq_handle *h, ThKind kind, int ntime_slices, int stack
         (rc = dev_alloc(h, LT_WALKERS, &h->thc_det, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_nav, n))) return rc;
     // T of the streamed Green's kernel, two buffers per (walker, spin); the wide route's scratch, four per (walker,
     // spin), of which the wide slice kernels use the walker's first two; a handle configured without either holds none
-    const size_t tscratch = route == THC_STREAMED ? 4 * mm * n : route == THC_WIDE ? 2 * ts_greens_wide_scratch(h->M) * n : (size_t)0;
-    if ((rc = dev_alloc(h, LT_WALKERS, &h->thc_tscratch, tscratch))) return rc;
-    // (a handle that held real walkers on the delayed route: their scratch and their flag go with them)
-    if ((rc = dev_alloc(h, LT_WALKERS, &h->th_wscratch, (size_t)0))) return rc;
-    h->th_delayed = false;
-    h->thc_streamed = route == THC_STREAMED;
-    h->thc_wide = route == THC_WIDE;
+    const size_t scratch = engine == TH_ENGINE_STREAMED ? 4 * mm * n : engine == TH_ENGINE_WIDE ? 2 * ts_greens_wide_scratch(h->M) * n : (size_t)0;
+    if ((rc = dev_alloc(h, LT_WALKERS, (cplx **)&h->th_scratch, scratch))) return rc;
+    h->th_engine = engine;
     if ((rc = ensure_G(h))) return rc;                  // c128 [nw, 2, M, M]: the one-body density matrices
     h->thc_fb_bound = fb_bound;
     h->dt = dt; h->sqrt_dt = std::pow(dt, 0.5);        // (the handle's time step, as afq_set_propagator sets it)
@@ -597,21 +504,11 @@ int thc_slice_diag(afq_handle *h) {
     a.vhs = h->vhs; a.right = h->thc_right; a.stack = h->thc_stack; a.bh1 = h->thc_bh1;
     a.left = h->thc_left + (size_t)h->th_counter * 2 * M;
     a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
-    if (h->thc_wide) {
-        static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-        const size_t lds = thc_slice_wide_lds(M);
-        AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_wide_kernel, lds, lds_set));
-        AFQ_LAUNCH(h, thermal_cslice_wide_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a, h->thc_tscratch,
-                   (long)(2 * ts_greens_wide_scratch(M)));
-        AFQ_POST(h);
-        return AFQ_OK;
-    }
-    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-    const size_t lds = thc_slice_lds(M);
-    AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_kernel, lds, lds_set));
-    AFQ_LAUNCH(h, thermal_cslice_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a);
-    AFQ_POST(h);
-    return AFQ_OK;
+    cplx *const scratch = (cplx *)h->th_scratch;
+    const long stride = (long)(2 * ts_greens_wide_scratch(M));       // a walker's: both spins' of the Green's kernel
+    if (h->th_engine == TH_ENGINE_WIDE)
+        return th_launch<thermal_cslice_kernel<false>>(h, "thermal_cslice_wide_kernel", dim3(h->nw), thc_slice_wide_lds(M), a, scratch, stride);
+    return th_launch<thermal_cslice_kernel<true>>(h, "thermal_cslice_kernel", dim3(h->nw), thc_slice_lds(M), a, scratch, stride);
 }
 
 // Hubbard: the force bias, the clip at 1, xs, cmf, cfb and the diagonal of BV from P's diagonal, and the slice kernel
@@ -625,21 +522,12 @@ int thc_slice_dense(afq_handle *h) {
     a.bv = h->vhs; a.right = h->thc_right; a.stack = h->thc_stack; a.bh1 = h->thc_bh1;
     a.left = h->thc_left + (size_t)h->th_counter * 2 * M * M;
     a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
-    if (h->thc_wide) {
-        static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-        const size_t lds = thd_slice_wide_lds(M);
-        AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_dense_wide_kernel, lds, lds_set));
-        AFQ_LAUNCH(h, thermal_cslice_dense_wide_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a, h->thc_tscratch,
-                   (long)(2 * ts_greens_wide_scratch(M)));
-        AFQ_POST(h);
-        return AFQ_OK;
-    }
-    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-    const size_t lds = thd_slice_lds(M);
-    AFQ_HIP(h, afq_raise_lds((const void *)thermal_cslice_dense_kernel, lds, lds_set));
-    AFQ_LAUNCH(h, thermal_cslice_dense_kernel, dim3(h->nw), dim3(TH_THREADS), lds, h->stream, a);
-    AFQ_POST(h);
-    return AFQ_OK;
+    cplx *const scratch = (cplx *)h->th_scratch;
+    const long stride = (long)(2 * ts_greens_wide_scratch(M));       // a walker's: both spins' of the Green's kernel
+    if (h->th_engine == TH_ENGINE_WIDE)
+        return th_launch<thermal_cslice_dense_kernel<false>>(h, "thermal_cslice_dense_wide_kernel", dim3(h->nw), thd_slice_wide_lds(M), a,
+                                                             scratch, stride);
+    return th_launch<thermal_cslice_dense_kernel<true>>(h, "thermal_cslice_dense_kernel", dim3(h->nw), thd_slice_lds(M), a, scratch, stride);
 }
 
 // the phaseless weight from the determinant ratio; the dense kind's carries the constant of the mean-field shift
@@ -669,13 +557,13 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
                         "thermal walkers with continuous fields: UEG systems only (no Generic, no continuous Hubbard)", "both"};
     if (!BT || !BT_inv || !BH1 || !mf_shift) AFQ_FAIL(h, AFQ_EINVAL, me.me + "null operand");
     AFQ_TRY(th_screen_options(h, me, options));
-    ThcRoute route;
-    AFQ_TRY(thc_route_of(h, me.me, options, &route));
-    const ThcLds slice = {"the slice kernel (thermal_cslice_kernel)", thc_slice_lds, ""};
-    if (route == THC_WIDE)
+    ThEngine route;
+    AFQ_TRY(thc_engine_of(h, me.me, options, &route));
+    const ThLds slice = {"the slice kernel (thermal_cslice_kernel)", thc_slice_lds, ""};
+    if (route == TH_ENGINE_WIDE)
         AFQ_TRY(thc_screen_bound(h, "", "plane waves", route, {THC_WIDE_GREENS,
                 {"the wide slice kernel (thermal_cslice_wide_kernel)", thc_slice_wide_lds, ""}}));
-    else if (route == THC_STREAMED)
+    else if (route == TH_ENGINE_STREAMED)
         AFQ_TRY(thc_screen_bound(h, "", "plane waves", route, {slice,
                 {"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}}));
     else
@@ -709,7 +597,7 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
 
 int afq_thermal_wide_max_basis(void) {
     int m = TW_COLS;
-    while (m > 1 && (ts_greens_wide_lds<cplx>(m) > THC_LDS_MAX || thc_slice_wide_lds(m) > THC_LDS_MAX || thd_slice_wide_lds(m) > THC_LDS_MAX)) --m;
+    while (m > 1 && (ts_greens_wide_lds<cplx>(m) > TH_LDS_MAX || thc_slice_wide_lds(m) > TH_LDS_MAX || thd_slice_wide_lds(m) > TH_LDS_MAX)) --m;
     return m;
 }
 
@@ -731,13 +619,13 @@ int afq_thermal_configure_hubbard_continuous(afq_handle *h, int ntime_slices, in
                         "thermal walkers with continuous fields and a dense trial: Hubbard systems only (no Generic)", "both"};
     if (!BT || !BT_inv || !BH1 || !mf_shift || !mf_const_fac) AFQ_FAIL(h, AFQ_EINVAL, me.me + "null operand");
     AFQ_TRY(th_screen_options(h, me, options));
-    ThcRoute route;
-    AFQ_TRY(thc_route_of(h, me.me, options, &route));
-    const bool streamed = route == THC_STREAMED;
-    const ThcLds greens = route == THC_WIDE ? THC_WIDE_GREENS : streamed ? ThcLds{"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}
-                                   : ThcLds{"the complex Green's function (thermal_cgreens_kernel)", ts_greens_lds<cplx>, THC_RESIDENT_HINT};
-    const ThcLds slice = route == THC_WIDE ? ThcLds{"the wide slice kernel (thermal_cslice_dense_wide_kernel)", thd_slice_wide_lds, ""}
-                                           : ThcLds{"the slice kernel (thermal_cslice_dense_kernel)", thd_slice_lds, ""};
+    ThEngine route;
+    AFQ_TRY(thc_engine_of(h, me.me, options, &route));
+    const bool streamed = route == TH_ENGINE_STREAMED;
+    const ThLds greens = route == TH_ENGINE_WIDE ? THC_WIDE_GREENS : streamed ? ThLds{"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}
+                                   : ThLds{"the complex Green's function (thermal_cgreens_kernel)", ts_greens_lds<cplx>, THC_RESIDENT_HINT};
+    const ThLds slice = route == TH_ENGINE_WIDE ? ThLds{"the wide slice kernel (thermal_cslice_dense_wide_kernel)", thd_slice_wide_lds, ""}
+                                                : ThLds{"the slice kernel (thermal_cslice_dense_kernel)", thd_slice_lds, ""};
     AFQ_TRY(thc_screen_bound(h, ", Hubbard", "sites", route, {greens, slice}));
     AFQ_TRY(th_screen_state(h, me, ntime_slices, stack_size, 1));
     if (!(dt > 0.0)) AFQ_FAIL(h, AFQ_EINVAL, me.me + "dt must be positive");
@@ -765,7 +653,7 @@ int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi
     AFQ_TRY(h->th_kind == TH_CPLX_DENSE ? thc_slice_dense(h) : thc_slice_diag(h));
     th_advance(h);
     // G = [I + S_{nbins - 1} .. S_0]^-1 on the walker's current bins, Mnew = det G, the weight
-    AFQ_TRY(thc_launch_greens(h, h->thc_G, h->thc_det, 0, -1, 2 * h->nw));
+    AFQ_TRY(th_launch_greens<cplx>(h, h->thc_stack, h->thc_G, h->thc_det, 0, -1, dim3(2 * h->nw)));
     AFQ_TRY(thc_weight(h));
     if (xi_out) return copy_out(h, xi_out, h->xi, sizeof(double) * nf);
     return AFQ_OK;

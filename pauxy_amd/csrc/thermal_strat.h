@@ -1,8 +1,9 @@
 // The stratified Green's function of a finite-temperature walker, once for both walker kinds: T = double for the
 // discrete Hirsch fields of k_thermal.hip, T = cplx for the continuous fields of k_thermal_cplx.hip.
 //
-//   thermal_greens_kernel<T>  one work-group per (walker, spin): G = [I + B_L .. B_1]^-1 from the stack by the
-//                             stratified (graded) decomposition.  Q D T = B_first by column-pivoted QR with Householder
+//   thermal_greens_kernel<T, E, SWEEP>  the one kernel of every engine E.  One work-group per (walker, spin):
+//                             G = [I + B_L .. B_1]^-1 from the stack by the stratified (graded) decomposition.
+//                             Q D T = B_first by column-pivoted QR with Householder
 //                             reflectors H = I - tau v v^H (alpha = -x_0 / |x_0| ||x||, tau = (||x|| + |x_0|) / ||x||
 //                             real); for every further bin C = (B Q) D, Q D t = C, T <- t T; then with D = D_b^-1 D_s
 //                             split at |D| = 1 (D_b = 1 / |D|, D_s = D / |D| where |D| > 1)
@@ -12,21 +13,25 @@
 //                             step for double and four for cplx, tiles padded by zero operands); the Householder panels
 //                             and the pivot search are plain wave code.  det G, where asked for, is the product of the
 //                             pivots of an LU with partial pivoting of a copy of G in the matrix the solve has used up.
-//   thermal_rdm_kernel<T>     P_s = I - G_s^T as c128 for the force bias and the energy, nav = Re(tr P_up + tr P_down).
-// A walker's working set stays in LDS: 4 matrices of pitch M | 1 in units of T, which the 160 KiB of a compute unit hold
-// up to M = 64 for double and M = 47 for cplx.
-//   thermal_greens_streamed_kernel<cplx>  the same engine with T in device memory and t read out of W: 2 matrices in
-//                             LDS, which hold a complex walker to M = 64 (117,536 B at the M = 57 shell).  Chosen per
-//                             handle by AFQ_THERMAL_STREAMED_GREENS; the same bits as the resident kernel.
-//   thermal_greens_wide_kernel (thermal_wide.h)  the same algorithm with one matrix in LDS and two columns per lane,
-//                             chosen per handle by AFQ_THERMAL_WIDE: a complex walker to M = 95; the same G to rounding.
-//                             With T = double (AFQ_THERMAL_DELAYED, k_thermal.hip) a real walker to M = 128.
-//
-//   thermal_greens_sweep_kernel<T>, thermal_greens_streamed_sweep_kernel<cplx>  the same two engines (their bodies are
-//                             the device functions ts_greens_body / ts_greens_streamed_body, which the kernels above
-//                             call too) on a grid (2 nw, bins): work-group (x, y) makes G of (walker, spin) x at
-//                             slice_ix = (ts0 + y) stack_size into a scratch [bins, nw, 2, M, M] -- the averaged
+//                             SWEEP: the same work on a grid (2 nw, bins): work-group (x, y) makes G of (walker, spin) x
+//                             at slice_ix = (ts0 + y) stack_size into a scratch [bins, nw, 2, M, M] -- the averaged
 //                             estimators' sweep of afq_thermal_estimates, one launch whatever the number of bins.
+//   thermal_rdm_kernel<T>     P_s = I - G_s^T as c128 for the force bias and the energy, nav = Re(tr P_up + tr P_down).
+//
+// An engine says where the chain's matrices live, what that costs in LDS and in device scratch, and what the launch is
+// called in the trace (the names are per walker kind and engine, not per template: the benchmarks key on them):
+//   TsResident<T>   ts_greens_body with W, Qt, T and t in LDS: 4 matrices of pitch M | 1 in units of T, which the
+//                   160 KiB of a compute unit hold up to M = 64 for double and M = 47 for cplx.
+//                   thermal_greens_kernel / thermal_cgreens_kernel, .._sweep_kernel.
+//   TsStreamed<cplx>  the same ts_greens_body with T in device memory and t read out of W: 2 matrices in LDS, which
+//                   hold a complex walker to M = 64 (117,536 B at the M = 57 shell).  AFQ_THERMAL_STREAMED_GREENS; the
+//                   same bits as the resident placement.  thermal_cgreens_streamed_kernel, .._streamed_sweep_kernel.
+//                   There is no TsStreamed<double>: the real walkers fit to M = 64 as they are.
+//   TsWide<T>       (thermal_wide.h) another body, ts_greens_wide_body: one matrix in LDS and two columns per lane;
+//                   the same G to rounding.  AFQ_THERMAL_WIDE: a complex walker to M = 95; AFQ_THERMAL_DELAYED: a real
+//                   walker to M = 128.  thermal_cgreens_wide_kernel / thermal_greens_wide_kernel; no sweep.
+// th_launch is the one way a thermal kernel with dynamic LDS is launched; ts_launch_greens<T, E> the one launcher of the
+// Green's kernels; th_launch_greens<T> (thermal_wide.h) picks E by the handle's th_engine.
 //
 // TsScalar<T> is the arithmetic the routines are written in.  Restricted to real numbers the complex formulas round as
 // the real ones do: a product with +-1 and a negation are exact, so alpha = -unit(x_0) ||x||, x_0 - alpha =
@@ -40,6 +45,7 @@
 #include <type_traits>
 
 #define TH_THREADS 256
+#define TH_LDS_MAX (160 * 1024)
 
 namespace {
 
@@ -265,23 +271,34 @@ __host__ __device__ inline int ts_first_of(int slice_ix, int stack_size, int nbi
     if (bin_ix == nbins) bin_ix = -1;
     return (bin_ix + 1) % nbins;
 }
-// LDS of the Green's kernel: 4 matrices, D[64], v[64], part[512], aux[192] scalars, perm[64]
-template <class T> inline size_t ts_greens_lds(int M) { return sizeof(T) * (4 * ts_mat(M) + 64 + 64 + 512 + 192) + sizeof(int) * 64; }
 
-// G[w, s] and det G[w, s] from the bins of walker w in the order first, first + 1, .. (mod nbins).
-// stack [nw, nbins, 2, M, M]; src_w < 0: block b works on walker b / 2, otherwise every block works on walker src_w and
-// writes walker 0's place (grid of 2 blocks).  det may be null.
+// A matrix where a placement keeps it: LDS at pitch M | 1, or the work-group's scratch in device memory at pitch M
+template <class T> struct TsMatView {
+    T *p; int ld;
+    __device__ T &operator()(int r, int c) const { return p[r * ld + c]; }
+};
+
+// LDS of the resident placement: 4 matrices, D[64], v[64], part[512], aux[192] scalars, perm[64]
+template <class T> inline size_t ts_greens_lds(int M) { return sizeof(T) * (4 * ts_mat(M) + 64 + 64 + 512 + 192) + sizeof(int) * 64; }
+// LDS of the streamed placement: W and Qt, and the same vectors
+template <class T> inline size_t ts_greens_streamed_lds(int M) { return sizeof(T) * (2 * ts_mat(M) + 64 + 64 + 512 + 192) + sizeof(int) * 64; }
+
 // The work of one work-group: G of one (walker, spin) from its bins Bw (bin b at Bw + b * 2 * M * M) in the order first,
-// first + 1, .. (mod nbins), into Gd [M, M] and, where given, into Gd2 as well; det G into *detd where given.
-template <class T>
-__device__ __forceinline__ void ts_greens_body(unsigned char *smem, const T *Bw, int M, int nbins, int first, T *Gd, T *Gd2,
-                                               T *detd) {
+// first + 1, .. (mod nbins), into Gd [M, M] and, where given, into Gd2 as well; det G into *detd where given.  P places
+// the matrices (TsResident, TsStreamed below); scr: the work-group's own P::scratch(M) scalars of device memory.  Every
+// element goes through the same operations in the same order whatever P is, so the placements give the same bits; a
+// work-group reads from device memory only what it has written itself, across a __syncthreads().
+template <class T, class P>
+__device__ __forceinline__ void ts_greens_body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first, T *Gd,
+                                               T *Gd2, T *detd) {
     typedef TsScalar<T> S;
     const int LD = M | 1, tid = threadIdx.x;
-    const size_t mat = ts_mat(M);
-    T *W = (T *)smem, *Qt = W + mat, *Tm = Qt + mat, *X = Tm + mat;
-    T *D = X + mat, *v = D + 64, *part = v + 64, *aux = part + 512;
-    int *perm = (int *)(aux + 192);
+    P pl(smem, scr, M);
+    T *W = pl.W, *const Qt = pl.Qt;                                  // LDS: the QR sweeps them four times per column
+    TsMatView<T> Tc = pl.Tcur, Tn = pl.Tnext;                        // T and the result of t T, used in turn
+    T *const D = pl.vec, *const v = D + 64, *const part = v + 64, *const aux = part + 512;
+    int *const perm = (int *)(aux + 192);
+    int *const iperm = (int *)aux;                                   // (aux is the solve's: free until the chain is done)
     const long mm = (long)M * M;
 
     {
@@ -293,7 +310,7 @@ __device__ __forceinline__ void ts_greens_body(unsigned char *smem, const T *Bw,
     // T = D^-1 R P^T
     for (int e = tid; e < M * M; e += TH_THREADS) {
         const int i = e / M, j = e % M;
-        Tm[i * LD + perm[j]] = j >= i ? S::div(W[i * LD + j], W[i * LD + i]) : S::zero();
+        Tc(i, perm[j]) = j >= i ? S::div(W[i * LD + j], W[i * LD + i]) : S::zero();
     }
     if (tid < M) D[tid] = W[tid * LD + tid];
     __syncthreads();
@@ -304,19 +321,27 @@ __device__ __forceinline__ void ts_greens_body(unsigned char *smem, const T *Bw,
                    [&](int r, int c, T x) { W[r * LD + c] = S::mul(x, D[c]); });
         __syncthreads();
         ts_qrcp(W, Qt, M, LD, perm, v, part);
-        for (int e = tid; e < M * M; e += TH_THREADS) {
-            const int i = e / M, j = e % M;
-            X[i * LD + perm[j]] = j >= i ? S::div(W[i * LD + j], W[i * LD + i]) : S::zero();
-        }
+        // t = D^-1 R P^T: stored in LDS where the placement has the room, else read out of W through the inverse
+        // permutation by the loader of t T
+        if constexpr (P::stores_t) {
+            for (int e = tid; e < M * M; e += TH_THREADS) {
+                const int i = e / M, j = e % M;
+                pl.X[i * LD + perm[j]] = j >= i ? S::div(W[i * LD + j], W[i * LD + i]) : S::zero();
+            }
+        } else if (tid < M) iperm[perm[tid]] = tid;
         if (tid < M) D[tid] = W[tid * LD + tid];
         __syncthreads();
-        // T <- t T (into W, whose R is used up; then the two change names)
-        ts_gemm<T>(M, [&](int r, int k) { return X[r * LD + k]; }, [&](int k, int c) { return Tm[k * LD + c]; },
-                   [&](int r, int c, T x) { W[r * LD + c] = x; });
+        // T <- t T
+        ts_gemm<T>(M, [&](int r, int k) {
+                       if constexpr (P::stores_t) return pl.X[r * LD + k];
+                       else { const int j = iperm[k]; return j >= r ? S::div(W[r * LD + j], W[r * LD + r]) : S::zero(); }
+                   },
+                   [&](int k, int c) { return Tc(k, c); }, [&](int r, int c, T x) { Tn(r, c) = x; });
         __syncthreads();
-        T *t = Tm; Tm = W; W = t;
+        pl.turn(W, Tc, Tn);
     }
     // (D_b Q^H + D_s T) G = D_b Q^H, D_b = 1 / |D| and D_s = D / |D| where |D| > 1, else D_b = 1 and D_s = D
+    T *const X = pl.solve_x(W), *const R = pl.solve_rhs(W);
     for (int e = tid; e < M * M; e += TH_THREADS) {
         const int i = e / M, j = e % M;
         const T d = D[i];
@@ -325,16 +350,16 @@ __device__ __forceinline__ void ts_greens_body(unsigned char *smem, const T *Bw,
         const T ds = ad > 1.0 ? S::unit(d, ad) : d;
         const T r = S::scale(Qt[i * LD + j], db);
         T x = r;
-        S::fma(x, ds, Tm[i * LD + j]);
+        S::fma(x, ds, Tc(i, j));
         X[i * LD + j] = x;
-        W[i * LD + j] = r;
+        R[i * LD + j] = r;
     }
     __syncthreads();
-    ts_solve(X, W, M, LD, aux, aux + 64, aux + 128);
+    ts_solve(X, R, M, LD, aux, aux + 64, aux + 128);
     // (only the complex walkers carry determinants: the real kernel holds no code for them)
     const bool want_det = std::is_same<T, cplx>::value && detd;
     for (int e = tid; e < M * M; e += TH_THREADS) {
-        const T g = W[(e / M) * LD + e % M];
+        const T g = R[(e / M) * LD + e % M];
         Gd[e] = g;
         if (Gd2) Gd2[e] = g;
         if (want_det) X[(e / M) * LD + e % M] = g;
@@ -345,132 +370,89 @@ __device__ __forceinline__ void ts_greens_body(unsigned char *smem, const T *Bw,
     if (tid == 0) *detd = dg;
 }
 
-template <class T>
-__global__ __launch_bounds__(TH_THREADS) void thermal_greens_kernel(const T *stack, T *G, T *det, int M, int nbins, int first,
-                                                                     int src_w) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int w = src_w < 0 ? blockIdx.x >> 1 : src_w, s = blockIdx.x & 1;
-    const long mm = (long)M * M;
-    const long slot = (long)(src_w < 0 ? w : 0) * 2 + s;
-    ts_greens_body<T>(smem, stack + ((long)w * nbins * 2 + s) * mm, M, nbins, first, G + slot * mm, nullptr,
-                      det ? det + slot : nullptr);
-}
+// The resident engine: W, Qt, T and X (t of the chain, then the matrix of the closing solve) in LDS.  t T goes into W,
+// whose R is used up, and the two change names; the solve's right-hand side D_b Q^H is built in the W of the end.
+template <class T> struct TsResident {
+    static constexpr bool stores_t = true, has_sweep = true;
+    static size_t lds(int M) { return ts_greens_lds<T>(M); }
+    __host__ __device__ static size_t scratch(int) { return 0; }
+    static const char *name(bool sweep) {
+        return std::is_same<T, cplx>::value ? (sweep ? "thermal_cgreens_sweep_kernel" : "thermal_cgreens_kernel")
+                                            : (sweep ? "thermal_greens_sweep_kernel" : "thermal_greens_kernel");
+    }
+    T *W, *Qt, *X, *vec;
+    TsMatView<T> Tcur, Tnext;
+    __device__ TsResident(unsigned char *smem, T *, int M) {
+        const size_t mat = ts_mat(M);
+        W = (T *)smem; Qt = W + mat; Tcur = {Qt + mat, M | 1}; X = Tcur.p + mat; vec = X + mat;
+        Tnext = {W, M | 1};
+    }
+    __device__ void turn(T *&w, TsMatView<T> &tc, TsMatView<T> &tn) const { w = tc.p; tc.p = tn.p; tn.p = w; }
+    __device__ T *solve_x(T *) const { return X; }
+    __device__ T *solve_rhs(T *w) const { return w; }
+    __device__ __forceinline__ static void body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first, T *Gd, T *Gd2, T *detd) {
+        ts_greens_body<T, TsResident<T>>(smem, Bw, scr, M, nbins, first, Gd, Gd2, detd);
+    }
+};
 
-// The sweep of the averaged estimators (afq_thermal_estimates): work-group (x, y) makes G of (walker, spin) x at
-// slice_ix = (ts0 + y) stack_size, for every y at once, into Gs [gridDim.y, nw, 2, M, M].  The last bin of the path
+// The streamed engine: W and Qt stay in LDS; T, touched once per bin as the B operand and the result of t T, lives in
+// the work-group's own scratch, two [M, M] buffers of pitch M used in turn; t is never stored.  The closing solve runs
+// in the two LDS matrices: D_b Q^H in place in Qt, its matrix in W.  The complex walkers' alone.
+template <class T> struct TsStreamed;
+template <> struct TsStreamed<cplx> {
+    static constexpr bool stores_t = false, has_sweep = true;
+    static size_t lds(int M) { return ts_greens_streamed_lds<cplx>(M); }
+    __host__ __device__ static size_t scratch(int M) { return 2 * (size_t)M * M; }
+    static const char *name(bool sweep) { return sweep ? "thermal_cgreens_streamed_sweep_kernel" : "thermal_cgreens_streamed_kernel"; }
+    cplx *W, *Qt, *X = nullptr, *vec;
+    TsMatView<cplx> Tcur, Tnext;
+    __device__ TsStreamed(unsigned char *smem, cplx *scr, int M) {
+        const size_t mat = ts_mat(M);
+        W = (cplx *)smem; Qt = W + mat; vec = Qt + mat;
+        Tcur = {scr, M}; Tnext = {scr + (long)M * M, M};
+    }
+    __device__ void turn(cplx *&, TsMatView<cplx> &tc, TsMatView<cplx> &tn) const { cplx *t = tc.p; tc.p = tn.p; tn.p = t; }
+    __device__ cplx *solve_x(cplx *w) const { return w; }
+    __device__ cplx *solve_rhs(cplx *) const { return Qt; }
+    __device__ __forceinline__ static void body(unsigned char *smem, const cplx *Bw, cplx *scr, int M, int nbins, int first, cplx *Gd, cplx *Gd2,
+                                cplx *detd) {
+        ts_greens_body<cplx, TsStreamed<cplx>>(smem, Bw, scr, M, nbins, first, Gd, Gd2, detd);
+    }
+};
+
+// What a Green's launch works on.  One Green's function per (walker, spin), grid (nblocks): with src_w < 0 block b works
+// on walker b / 2, otherwise every block works on walker src_w and writes walker 0's place (grid of 2 blocks); the chain
+// starts at bin `first`.  The sweep, grid (2 nw, bins): work-group (x, y) makes G of (walker, spin) x at slice_ix =
+// (ts0 + y) stack_size, for every y at once, into Gs [gridDim.y, nw, 2, M, M]; the last bin of the path
 // (ts = nbins - 1) also goes to the walkers' own G and det: what afq_thermal_greens leaves there.
-template <class T>
-__global__ __launch_bounds__(TH_THREADS) void thermal_greens_sweep_kernel(const T *stack, T *Gs, T *G, T *det, int M, int nbins,
-                                                                           int stack_size, int ts0) {
+template <class T> struct TsGreensArgs {
+    const T *stack;             // [nw, nbins, 2, M, M]
+    T *G, *det;                 // [nw, 2, M, M], [nw, 2]; det may be null (and is, for the real walkers)
+    T *scratch;                 // [work-groups, E::scratch(M)]: every work-group its own (null for the resident engine)
+    int M, nbins;
+    int first, src_w;           // one Green's function per (walker, spin)
+    T *Gs;                      // the sweep
+    int stack_size, ts0;
+};
+
+template <class T, template <class> class E, bool SWEEP>
+__global__ __launch_bounds__(TH_THREADS) void thermal_greens_kernel(TsGreensArgs<T> a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int w = blockIdx.x >> 1, s = blockIdx.x & 1, ts = ts0 + (int)blockIdx.y;
-    const long mm = (long)M * M, slot = (long)w * 2 + s;
-    const bool last = ts == nbins - 1;
-    ts_greens_body<T>(smem, stack + ((long)w * nbins * 2 + s) * mm, M, nbins, ts_first_of(ts * stack_size, stack_size, nbins),
-                      Gs + ((long)blockIdx.y * gridDim.x + blockIdx.x) * mm, last ? G + slot * mm : nullptr,
-                      last && det ? det + slot : nullptr);
-}
-
-// LDS of the streamed Green's kernel: W and Qt, D[64], v[64], part[512], aux[192] scalars, perm[64]
-template <class T> inline size_t ts_greens_streamed_lds(int M) { return sizeof(T) * (2 * ts_mat(M) + 64 + 64 + 512 + 192) + sizeof(int) * 64; }
-
-// The same G and det G with T outside LDS: W and Qt, which the QR sweeps four times per column, stay; T, touched once
-// per bin as the B operand and the result of t T, lives in the work-group's own scratch in device memory, two [M, M]
-// buffers used in turn (scratch [gridDim.x, 2, M, M], block b's at b); t = D^-1 R P^T is never stored: the A loader of
-// t T reads it out of W through the inverse permutation.  Every element goes through the operations of
-// thermal_greens_kernel in their order, so the two kernels give the same bits.  A work-group reads only what it has
-// written itself, across a __syncthreads().  Instantiated for cplx alone (the real walkers fit to M = 64 as they are).
-// The streamed work of one work-group, as ts_greens_body; Tin: the work-group's own [2, M, M] in device memory.
-template <class T>
-__device__ __forceinline__ void ts_greens_streamed_body(unsigned char *smem, const T *Bw, T *Tin, int M, int nbins, int first,
-                                                        T *Gd, T *Gd2, T *detd) {
-    typedef TsScalar<T> S;
-    const int LD = M | 1, tid = threadIdx.x;
-    const size_t mat = ts_mat(M);
-    T *W = (T *)smem, *Qt = W + mat;
-    T *D = Qt + mat, *v = D + 64, *part = v + 64, *aux = part + 512;
-    int *perm = (int *)(aux + 192);
-    int *iperm = (int *)aux;                                         // (aux is the solve's: free until the chain is done)
+    const int M = a.M, s = blockIdx.x & 1;
     const long mm = (long)M * M;
-    T *Tout = Tin + mm;                                              // pitch M
-
-    {
-        const T *B = Bw + (long)first * 2 * mm;
-        for (int e = tid; e < M * M; e += TH_THREADS) W[(e / M) * LD + e % M] = B[e];
+    if (SWEEP) {
+        const int w = blockIdx.x >> 1, ts = a.ts0 + (int)blockIdx.y;
+        const long slot = (long)w * 2 + s, wg = (long)blockIdx.y * gridDim.x + blockIdx.x;
+        const bool last = ts == a.nbins - 1;
+        E<T>::body(smem, a.stack + ((long)w * a.nbins * 2 + s) * mm, a.scratch + wg * (long)E<T>::scratch(M), M, a.nbins,
+                   ts_first_of(ts * a.stack_size, a.stack_size, a.nbins), a.Gs + wg * mm, last ? a.G + slot * mm : nullptr,
+                   last && a.det ? a.det + slot : nullptr);
+    } else {
+        const int w = a.src_w < 0 ? blockIdx.x >> 1 : a.src_w;
+        const long slot = (long)(a.src_w < 0 ? w : 0) * 2 + s;
+        E<T>::body(smem, a.stack + ((long)w * a.nbins * 2 + s) * mm, a.scratch + (long)blockIdx.x * (long)E<T>::scratch(M), M,
+                   a.nbins, a.first, a.G + slot * mm, nullptr, a.det ? a.det + slot : nullptr);
     }
-    __syncthreads();
-    ts_qrcp(W, Qt, M, LD, perm, v, part);
-    // T = D^-1 R P^T
-    for (int e = tid; e < M * M; e += TH_THREADS) {
-        const int i = e / M, j = e % M;
-        Tin[i * M + perm[j]] = j >= i ? S::div(W[i * LD + j], W[i * LD + i]) : S::zero();
-    }
-    if (tid < M) D[tid] = W[tid * LD + tid];
-    __syncthreads();
-    for (int n = 1; n < nbins; ++n) {
-        const T *B = Bw + (long)((first + n) % nbins) * 2 * mm;
-        // W = (B Q) D, Q[k][c] = conj(Qt[c][k])
-        ts_gemm<T>(M, [&](int r, int k) { return B[r * M + k]; }, [&](int k, int c) { return S::conj(Qt[c * LD + k]); },
-                   [&](int r, int c, T x) { W[r * LD + c] = S::mul(x, D[c]); });
-        __syncthreads();
-        ts_qrcp(W, Qt, M, LD, perm, v, part);
-        if (tid < M) { iperm[perm[tid]] = tid; D[tid] = W[tid * LD + tid]; }
-        __syncthreads();
-        // T <- t T, t[r][k] = (D^-1 R)[r][iperm[k]]
-        ts_gemm<T>(M, [&](int r, int k) { const int j = iperm[k]; return j >= r ? S::div(W[r * LD + j], W[r * LD + r]) : S::zero(); },
-                   [&](int k, int c) { return Tin[k * M + c]; }, [&](int r, int c, T x) { Tout[r * M + c] = x; });
-        __syncthreads();
-        T *t = Tin; Tin = Tout; Tout = t;
-    }
-    // (D_b Q^H + D_s T) G = D_b Q^H: R = D_b Q^H in place in Qt, X = R + D_s T into W, whose R is used up
-    for (int e = tid; e < M * M; e += TH_THREADS) {
-        const int i = e / M, j = e % M;
-        const T d = D[i];
-        const double ad = S::abs(d);
-        const double db = ad > 1.0 ? 1.0 / ad : 1.0;
-        const T ds = ad > 1.0 ? S::unit(d, ad) : d;
-        const T r = S::scale(Qt[i * LD + j], db);
-        T x = r;
-        S::fma(x, ds, Tin[i * M + j]);
-        W[i * LD + j] = x;
-        Qt[i * LD + j] = r;
-    }
-    __syncthreads();
-    ts_solve(W, Qt, M, LD, aux, aux + 64, aux + 128);
-    for (int e = tid; e < M * M; e += TH_THREADS) {
-        const T g = Qt[(e / M) * LD + e % M];
-        Gd[e] = g;
-        if (Gd2) Gd2[e] = g;
-        if (detd) W[(e / M) * LD + e % M] = g;
-    }
-    if (!detd) return;
-    __syncthreads();
-    const T dg = ts_det(W, M, LD, aux);
-    if (tid == 0) *detd = dg;
-}
-
-template <class T>
-__global__ __launch_bounds__(TH_THREADS) void thermal_greens_streamed_kernel(const T *stack, T *G, T *det, T *scratch, int M,
-                                                                              int nbins, int first, int src_w) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int w = src_w < 0 ? blockIdx.x >> 1 : src_w, s = blockIdx.x & 1;
-    const long mm = (long)M * M;
-    const long slot = (long)(src_w < 0 ? w : 0) * 2 + s;
-    ts_greens_streamed_body<T>(smem, stack + ((long)w * nbins * 2 + s) * mm, scratch + (long)blockIdx.x * 2 * mm, M, nbins, first,
-                               G + slot * mm, nullptr, det ? det + slot : nullptr);
-}
-
-// thermal_greens_sweep_kernel by the streamed engine; scratch [gridDim.y, gridDim.x, 2, M, M]: every work-group its own
-template <class T>
-__global__ __launch_bounds__(TH_THREADS) void thermal_greens_streamed_sweep_kernel(const T *stack, T *Gs, T *G, T *det, T *scratch,
-                                                                                    int M, int nbins, int stack_size, int ts0) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int w = blockIdx.x >> 1, s = blockIdx.x & 1, ts = ts0 + (int)blockIdx.y;
-    const long mm = (long)M * M, slot = (long)w * 2 + s, wg = (long)blockIdx.y * gridDim.x + blockIdx.x;
-    const bool last = ts == nbins - 1;
-    ts_greens_streamed_body<T>(smem, stack + ((long)w * nbins * 2 + s) * mm, scratch + wg * 2 * mm, M, nbins,
-                               ts_first_of(ts * stack_size, stack_size, nbins), Gs + wg * mm, last ? G + slot * mm : nullptr,
-                               last && det ? det + slot : nullptr);
 }
 
 // P_s = I - G_s^T as c128 [nw, 2, M, M], nav = Re(tr P_up + tr P_down) (nav may be null)
@@ -559,55 +541,25 @@ inline void th_advance(afq_handle *h) {
 // first bin of the chain for the Green's function at slice_ix (walkers/thermal.py:477-492)
 inline int ts_first_bin(const afq_handle *h, int slice_ix) { return ts_first_of(slice_ix, h->th_ss, h->th_nbins); }
 
-// The launch trace names the kernel by walker kind, not by its template: the benchmarks' tables are keyed by these names.
-template <class T> int ts_launch_greens(afq_handle *h, const T *stack, T *G, T *det, int first, int src_w, int nblocks) {
-    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-    const size_t lds = ts_greens_lds<T>(h->M);
-    AFQ_HIP(h, afq_raise_lds((const void *)thermal_greens_kernel<T>, lds, lds_set));
-    afq_note_launch(h, std::is_same<T, cplx>::value ? "thermal_cgreens_kernel" : "thermal_greens_kernel");
-    hipLaunchKernelGGL(thermal_greens_kernel<T>, dim3(nblocks), dim3(TH_THREADS), lds, h->stream, stack, G, det, h->M,
-                       h->th_nbins, first, src_w);
+// The one launch of a thermal kernel that takes dynamic LDS, TH_THREADS threads a work-group: the kernel's LDS attribute
+// raised once per device, `name` into the launch trace, the launch on the handle's stream and its check.
+template <auto Kern, class... Args> int th_launch(afq_handle *h, const char *name, dim3 grid, size_t lds, Args... args) {
+    static size_t lds_set[AFQ_MAX_DEVICES] = {0};                    // (one per kernel: Kern is a template argument)
+    AFQ_HIP(h, afq_raise_lds((const void *)Kern, lds, lds_set));
+    afq_note_launch(h, name);
+    hipLaunchKernelGGL(Kern, grid, dim3(TH_THREADS), lds, h->stream, args...);
     AFQ_POST(h);
     return AFQ_OK;
 }
 
-// The streamed form; scratch [nblocks, 2, M, M].  Its own name in the trace: thermal_cgreens_kernel stays the resident one.
-template <class T> int ts_launch_greens_streamed(afq_handle *h, const T *stack, T *G, T *det, T *scratch, int first, int src_w,
-                                                 int nblocks) {
-    static_assert(std::is_same<T, cplx>::value, "the streamed Green's function is the complex walkers' alone");
-    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-    const size_t lds = ts_greens_streamed_lds<T>(h->M);
-    AFQ_HIP(h, afq_raise_lds((const void *)thermal_greens_streamed_kernel<T>, lds, lds_set));
-    afq_note_launch(h, "thermal_cgreens_streamed_kernel");
-    hipLaunchKernelGGL(thermal_greens_streamed_kernel<T>, dim3(nblocks), dim3(TH_THREADS), lds, h->stream, stack, G, det, scratch,
-                       h->M, h->th_nbins, first, src_w);
-    AFQ_POST(h);
-    return AFQ_OK;
-}
-
-// The sweep's launches: nb bins from ts0 on, Gs [nb, nw, 2, M, M] (and Ts [nb, 2 nw, 2, M, M] of the streamed engine);
-// G, det: the walkers' own, written by the path's last bin (det null for the real walkers).  Their own names in the trace.
-template <class T> int ts_launch_greens_sweep(afq_handle *h, const T *stack, T *Gs, T *G, T *det, int ts0, int nb) {
-    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-    const size_t lds = ts_greens_lds<T>(h->M);
-    AFQ_HIP(h, afq_raise_lds((const void *)thermal_greens_sweep_kernel<T>, lds, lds_set));
-    afq_note_launch(h, std::is_same<T, cplx>::value ? "thermal_cgreens_sweep_kernel" : "thermal_greens_sweep_kernel");
-    hipLaunchKernelGGL(thermal_greens_sweep_kernel<T>, dim3(2 * h->nw, nb), dim3(TH_THREADS), lds, h->stream, stack, Gs, G, det,
-                       h->M, h->th_nbins, h->th_ss, ts0);
-    AFQ_POST(h);
-    return AFQ_OK;
-}
-
-template <class T> int ts_launch_greens_streamed_sweep(afq_handle *h, const T *stack, T *Gs, T *G, T *det, T *Ts, int ts0, int nb) {
-    static_assert(std::is_same<T, cplx>::value, "the streamed Green's function is the complex walkers' alone");
-    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-    const size_t lds = ts_greens_streamed_lds<T>(h->M);
-    AFQ_HIP(h, afq_raise_lds((const void *)thermal_greens_streamed_sweep_kernel<T>, lds, lds_set));
-    afq_note_launch(h, "thermal_cgreens_streamed_sweep_kernel");
-    hipLaunchKernelGGL(thermal_greens_streamed_sweep_kernel<T>, dim3(2 * h->nw, nb), dim3(TH_THREADS), lds, h->stream, stack, Gs, G,
-                       det, Ts, h->M, h->th_nbins, h->th_ss, ts0);
-    AFQ_POST(h);
-    return AFQ_OK;
+// The one launcher of the Green's kernels: LDS and the name in the trace are the engine's.  a.scratch holds
+// E::scratch(M) scalars for every work-group of the grid.
+template <class T, template <class> class E> int ts_launch_greens(afq_handle *h, const TsGreensArgs<T> &a, dim3 grid, bool sweep) {
+    if constexpr (E<T>::has_sweep) {
+        if (sweep) return th_launch<thermal_greens_kernel<T, E, true>>(h, E<T>::name(true), grid, E<T>::lds(a.M), a);
+    }
+    if (sweep) AFQ_FAIL(h, AFQ_EUNSUPPORTED, std::string(E<T>::name(false)) + " has no sweep");
+    return th_launch<thermal_greens_kernel<T, E, false>>(h, E<T>::name(false), grid, E<T>::lds(a.M), a);
 }
 
 // P_s = I - G_s^T of n Green's functions G [n, 2, M, M] into P, nav [n] (or null): the sweep's own scratch

@@ -11,7 +11,8 @@
 //   Pn       the reflectors of the last QR, transposed (reflector j contiguous at Pn + j M, v_0 = 1 implied); at the
 //            end the LU factors of the solve, transposed as well (column k contiguous);
 //   Xs       t = D^-1 R P^T of the bins behind the first; at the end the right-hand side D_b Q^H.
-// A work-group reads back only what it has written itself, across a __syncthreads() (the discipline of thc_tscratch).
+// A work-group reads back only what it has written itself, across a __syncthreads(): the discipline of every user of
+// the handle's th_scratch.
 //
 // Q is never accumulated.  The QR leaves reflector j below the diagonal of column j of W and tau_j in LDS; behind the QR
 // t and the reflectors go to scratch, the next bin B is loaded into the same LDS matrix, H_0 .. H_(M-1) are applied to
@@ -25,8 +26,14 @@
 // The invariants of the other engines hold: no loop whose trip count depends on data, exits that are uniform over the
 // work-group (a zero pivot of det G, seen by every thread alike), every wave at every barrier; the same bits on repeat
 // and at any grid position.
+//
+// The engine enters thermal_strat.h's one kernel and one launcher as TsWide<T>.  Behind it, what needs every engine in
+// sight: th_launch_greens<T>, which picks the engine by the handle's th_engine, and th_screen_bound, the one refusal of
+// an M that a route's kernels or lanes do not hold.
 #pragma once
 #include "thermal_strat.h"
+#include <initializer_list>
+#include <string>
 
 #define TW_COLS 128             // two columns per lane
 
@@ -252,7 +259,8 @@ template <class T> __device__ void tw_substitute(T *R, int M, int LD, const T *L
     }
 }
 
-// The work of one work-group, as ts_greens_body; scr: the work-group's own ts_greens_wide_scratch(M) scalars.
+// The work of one work-group, as ts_greens_body (another algorithm: its own body); scr: the work-group's own
+// ts_greens_wide_scratch(M) scalars.
 template <class T>
 __device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first,
                                                     T *Gd, T *Gd2, T *detd) {
@@ -324,30 +332,65 @@ __device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const T
     if (tid == 0) *detd = dg;
 }
 
-// One work-group per (walker, spin), as thermal_greens_streamed_kernel; scratch [gridDim.x, 4, M, M]: block b's at b.
-template <class T>
-__global__ __launch_bounds__(TH_THREADS) void thermal_greens_wide_kernel(const T *stack, T *G, T *det, T *scratch, int M,
-                                                                          int nbins, int first, int src_w) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int w = src_w < 0 ? blockIdx.x >> 1 : src_w, s = blockIdx.x & 1;
-    const long mm = (long)M * M;
-    const long slot = (long)(src_w < 0 ? w : 0) * 2 + s;
-    ts_greens_wide_body<T>(smem, stack + ((long)w * nbins * 2 + s) * mm, scratch + (long)blockIdx.x * ts_greens_wide_scratch(M), M,
-                        nbins, first, G + slot * mm, nullptr, det ? det + slot : nullptr);
+// The wide engine of thermal_greens_kernel (thermal_strat.h): scratch [work-groups, 4, M, M].  Its own names in the
+// trace; no sweep.
+template <class T> struct TsWide {
+    static constexpr bool has_sweep = false;
+    static size_t lds(int M) { return ts_greens_wide_lds<T>(M); }
+    __host__ __device__ static size_t scratch(int M) { return ts_greens_wide_scratch(M); }
+    static const char *name(bool) { return std::is_same<T, cplx>::value ? "thermal_cgreens_wide_kernel" : "thermal_greens_wide_kernel"; }
+    __device__ __forceinline__ static void body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first, T *Gd, T *Gd2, T *detd) {
+        ts_greens_wide_body<T>(smem, Bw, scr, M, nbins, first, Gd, Gd2, detd);
+    }
+};
+
+// Every Green's launch of a handle, by the engine it was configured with (th_engine).  G and det of grid.x / 2 walkers
+// from `stack`, the chain starting at bin `first` (src_w as TsGreensArgs has it), in the handle's own scratch; with Gs
+// the sweep instead: grid (2 nw, bins), the bins from ts0 on into Gs, in the scratch Ts.
+template <class T> int th_launch_greens(afq_handle *h, const T *stack, T *G, T *det, int first, int src_w, dim3 grid,
+                                        T *Gs = nullptr, T *Ts = nullptr, int ts0 = 0) {
+    const bool sweep = Gs != nullptr;
+    const TsGreensArgs<T> a = {stack, G, det, sweep ? Ts : (T *)h->th_scratch, h->M, h->th_nbins, first, src_w, Gs, h->th_ss, ts0};
+    if (h->th_engine == TH_ENGINE_WIDE) return ts_launch_greens<T, TsWide>(h, a, grid, sweep);
+    if constexpr (std::is_same<T, cplx>::value) {                    // (the real walkers have no streamed engine)
+        if (h->th_engine == TH_ENGINE_STREAMED) return ts_launch_greens<T, TsStreamed>(h, a, grid, sweep);
+    }
+    return ts_launch_greens<T, TsResident>(h, a, grid, sweep);
 }
 
-// Its own name in the trace, as the streamed form has; the real walkers' is thermal_greens_wide_kernel
-template <class T>
-inline int ts_launch_greens_wide(afq_handle *h, const T *stack, T *G, T *det, T *scratch, int first, int src_w,
-                                 int nblocks) {
-    static size_t lds_set[AFQ_MAX_DEVICES] = {0};
-    const size_t lds = ts_greens_wide_lds<T>(h->M);
-    AFQ_HIP(h, afq_raise_lds((const void *)thermal_greens_wide_kernel<T>, lds, lds_set));
-    afq_note_launch(h, std::is_same<T, cplx>::value ? "thermal_cgreens_wide_kernel" : "thermal_greens_wide_kernel");
-    hipLaunchKernelGGL(thermal_greens_wide_kernel<T>, dim3(nblocks), dim3(TH_THREADS), lds, h->stream, stack, G, det, scratch, h->M,
-                       h->th_nbins, first, src_w);
-    AFQ_POST(h);
-    return AFQ_OK;
+// ---- the bound on M of a configure entry point
+
+// One kernel's LDS as the refusal words it: "need <bytes(M)> bytes of LDS for <what>, a work-group has .. <hint>"
+struct ThLds {
+    const char *what;
+    size_t (*bytes)(int M);
+    const char *hint;
+};
+
+// M within what every kernel of `need` holds and within `lanes` columns (64: one per lane; TW_COLS: two); else the
+// refusal "<who>: M = <M> <unit> ..." names the first that does not fit -- the columns before the kernels with
+// lanes_first, behind them without -- with its bytes, and the largest M that passes.
+inline int th_screen_bound(afq_handle *h, const std::string &who, const char *unit, int lanes, bool lanes_first,
+                           std::initializer_list<ThLds> need) {
+    auto fits = [&](int m) {
+        for (const ThLds &k : need)
+            if (k.bytes(m) > TH_LDS_MAX) return false;
+        return m <= lanes;
+    };
+    const int M = h->M;
+    if (fits(M)) return AFQ_OK;
+    int mmax = M;
+    while (mmax > 1 && !fits(mmax)) --mmax;
+    const std::string head = who + ": M = " + std::to_string(M) + " " + unit + " ";
+    const std::string tail = " (M <= " + std::to_string(mmax) + ")";
+    const std::string columns = head + "are more than the " + (lanes == TW_COLS ? std::to_string(TW_COLS) + " columns of a wave, two per lane"
+                                                                                 : std::to_string(lanes) + " lanes of a wave, one per column") + tail;
+    if (lanes_first && M > lanes) AFQ_FAIL(h, AFQ_EUNSUPPORTED, columns);
+    for (const ThLds &k : need)
+        if (k.bytes(M) > TH_LDS_MAX)
+            AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(k.bytes(M)) + " bytes of LDS for " + k.what +
+                     ", a work-group has " + std::to_string(TH_LDS_MAX) + tail + k.hint);
+    AFQ_FAIL(h, AFQ_EUNSUPPORTED, columns);
 }
 
 }  // namespace
