@@ -77,7 +77,7 @@ struct afq_handle_full : afq_handle {
 };
 static afq_host_cache *cache_of(afq_handle *h) { return &static_cast<afq_handle_full *>(h)->cache; }
 
-static int build_psiB(afq_handle *h);
+static int step_operands(afq_handle *h);
 
 static int upload_psi(afq_handle *h, const double *psi) {
     const size_t n = (size_t)h->M * h->nt;
@@ -103,23 +103,24 @@ static int upload_psi(afq_handle *h, const double *psi) {
     }
     rc = dev_upload(h, LT_TRIAL, &o.psic, pc.data(), n);
     select_det(h, h->cur_det, true);
-    return rc ? rc : build_psiB(h);
+    return rc ? rc : step_operands(h);
 }
 
-// psiB_cT = psi^H B (afq_internal.h) from the host copies of the trial and the propagator: after every upload of either.
-// Anything but a single real closed trial with one real one-body matrix for both spins leaves the slot null, and the fused
-// propagator's tail then evaluates the overlap matrix itself.  B2 = B B (the step hand-over) is made here too, under the same
-// conditions and in the same lifetime slot; a new trial or propagator drops the hand-over that was made with the old one.
-static int build_psiB(afq_handle *h) {
+// The fused step's operands for this trial and propagator (StepState, step_state.h): psiB_cT = psi^H B from the host copies of
+// the two, after every upload of either.  Anything but a single real closed trial with one real one-body matrix for both spins
+// leaves the slot null, and the fused propagator's tail then evaluates the overlap matrix itself.  B2 = B B (the step hand-over)
+// is made here too, under the same conditions and in the same lifetime slot; a new trial or propagator drops the hand-over that
+// was made with the old one.
+static int step_operands(afq_handle *h) {
     afq_host_cache *c = cache_of(h);
     const int M = h->M, nt = h->nt, na = h->na;
     const bool ok = h->have_prop && h->ndet <= 1 && h->psi_stride == 0 && h->psi_real && h->psi_closed &&
                     h->bh1_real && h->bh1_same && c->psi.size() == (size_t)2 * M * nt && c->BH1.size() == (size_t)M * M;
-    h->psiB_psi = nullptr; h->psiB_bh1 = nullptr; h->b2_bh1 = nullptr;
-    h->handover.drop();
+    StepState &st = h->step;
+    st.operands_gone();
     if (!ok) {
-        const int rc0 = dev_alloc(h, LT_TRIAL, &h->B2, 0);
-        return rc0 ? rc0 : dev_alloc(h, LT_TRIAL, &h->psiB_cT, 0);
+        const int rc0 = dev_alloc(h, LT_TRIAL, &st.B2, 0);
+        return rc0 ? rc0 : dev_alloc(h, LT_TRIAL, &st.psiB_cT, 0);
     }
     std::vector<double> pb((size_t)na * M, 0.0);
     for (int m = 0; m < M; ++m)
@@ -129,9 +130,9 @@ static int build_psiB(afq_handle *h) {
             double *out = &pb[(size_t)i * M];
             for (int k = 0; k < M; ++k) out[k] += p * brow[k];
         }
-    int rc = dev_upload(h, LT_TRIAL, &h->psiB_cT, pb.data(), pb.size());
-    if (!rc) { h->psiB_psi = h->dets[h->cur_det].psi; h->psiB_bh1 = h->BH1; }
+    int rc = dev_upload(h, LT_TRIAL, &st.psiB_cT, pb.data(), pb.size());
     if (rc) return rc;
+    st.made_psiB(h->dets[h->cur_det].psi, h->BH1);
     // B2 = B B for the step hand-over (the next step's opening pass as (B B) S, k_fused_closed.h): extended accumulation, one
     // rounding per element
     std::vector<double> b2((size_t)M * M);
@@ -145,8 +146,8 @@ static int build_psiB(afq_handle *h) {
         }
         for (int k = 0; k < M; ++k) b2[(size_t)m * M + k] = (double)acc[k];
     }
-    rc = dev_upload(h, LT_TRIAL, &h->B2, b2.data(), b2.size());
-    if (!rc) h->b2_bh1 = h->BH1;
+    rc = dev_upload(h, LT_TRIAL, &st.B2, b2.data(), b2.size());
+    if (!rc) st.made_B2(h->BH1);
     return rc;
 }
 
@@ -303,7 +304,7 @@ static int upload_rchol(afq_handle *h, const double *rchol, bool real) {
 
 int afq_set_system_generic(afq_handle *h, int M, int K, int na, int nb, const double *hs_pot,
                            const double *rchol, const double *H1, double ecore) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !hs_pot || !rchol || !H1) return AFQ_EINVAL;
     int rc = set_dims(h, AFQ_SYS_GENERIC, M, K, na, nb);
     if (rc) return rc;
@@ -351,7 +352,7 @@ int afq_set_system_generic(afq_handle *h, int M, int K, int na, int nb, const do
 // complex Cholesky vectors: Re and Im parts as two transposed real panels (afq_internal.h: hs_cplx)
 int afq_set_system_generic_c128(afq_handle *h, int M, int K, int na, int nb, const double *hs_pot,
                                 const double *rchol, const double *H1, double ecore) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !hs_pot || !rchol || !H1) return AFQ_EINVAL;
     if (M <= 0 || K <= 0) AFQ_FAIL(h, AFQ_EINVAL, "bad dimensions");
     const size_t mm = (size_t)M * M, nq = (size_t)(na + nb) * M;
@@ -413,7 +414,7 @@ int afq_set_system_generic_c128(afq_handle *h, int M, int K, int na, int nb, con
 }
 
 int afq_set_system_hubbard(afq_handle *h, int M, int na, int nb, double U, const double *T) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !T) return AFQ_EINVAL;
     int rc = set_dims(h, AFQ_SYS_HUBBARD, M, M, na, nb);
     if (rc) return rc;
@@ -449,7 +450,7 @@ int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64
                        const int64_t *kpq_i, const int64_t *kpq_kpq, const int64_t *pmq_off,
                        const int64_t *pmq_i, const int64_t *pmq_pmq, const double *vqvec, double vol,
                        const double *H1diag, double ecore) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !iA_colptr || !iB_colptr || !kpq_off || !pmq_off || !vqvec || !H1diag) return AFQ_EINVAL;
     int rc = set_dims(h, AFQ_SYS_UEG, M, 2 * nq, na, nb);
     if (rc) return rc;
@@ -533,7 +534,7 @@ int afq_set_system_ueg(afq_handle *h, int M, int nq, int na, int nb, const int64
 }
 
 int afq_set_trial(afq_handle *h, const double *psi) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !psi) return AFQ_EINVAL;
     if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "set the system before the trial");
     if (h->ndet > 1) AFQ_FAIL(h, AFQ_ESTATE, "a multi-determinant trial is set; set the system again first");
@@ -546,7 +547,7 @@ int afq_set_trial(afq_handle *h, const double *psi) {
 }
 
 int afq_set_trial_multi(afq_handle *h, int ndet, const double *psi, const double *coeffs, const double *rchol) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !psi || !coeffs || !rchol || ndet < 1) return AFQ_EINVAL;
     if (h->kind != AFQ_SYS_GENERIC) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "multi-determinant trials need a generic system");
     if (h->nw) AFQ_FAIL(h, AFQ_ESTATE, "set the trial before allocating walkers");
@@ -590,7 +591,7 @@ int afq_set_trial_multi(afq_handle *h, int ndet, const double *psi, const double
 
 int afq_set_propagator(afq_handle *h, const double *BH1, const double *mf_shift, double dt, int exp_order,
                        int flags) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !BH1 || !mf_shift || dt <= 0 || exp_order < 0) return AFQ_EINVAL;
     if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "set the system before the propagator");
     hipSetDevice(h->device);
@@ -613,7 +614,7 @@ int afq_set_propagator(afq_handle *h, const double *BH1, const double *mf_shift,
     h->vhs_diag = h->kind == AFQ_SYS_HUBBARD;
     h->nv = (h->kind == AFQ_SYS_HUBBARD && (flags & AFQ_PROP_HUBBARD_SPIN)) ? 2 : 1;
     h->have_prop = true;
-    if ((rc = build_psiB(h))) return rc;
+    if ((rc = step_operands(h))) return rc;
     if (h->nw && (old_nv != h->nv || old_diag != h->vhs_diag || !h->vhs)) {
         // (diagonal potential: a second block of the same size holds its Taylor factors)
         const size_t per = h->vhs_diag ? (size_t)2 * h->nv * h->M : (size_t)h->nv * h->M * h->M;
@@ -624,7 +625,7 @@ int afq_set_propagator(afq_handle *h, const double *BH1, const double *mf_shift,
 
 // ------------------------------------------------------------------ walkers
 int afq_walkers_alloc(afq_handle *h, int nw) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || nw <= 0) return AFQ_EINVAL;
     if (!h->kind) AFQ_FAIL(h, AFQ_ESTATE, "set the system before allocating walkers");
     hipSetDevice(h->device);
@@ -738,7 +739,7 @@ static int ensure_spin_ghalf(afq_handle *h);
 
 int afq_walkers_set(afq_handle *h, int field, const void *host, int first, int count) {
     if (h && (field == AFQ_F_PHI || field == AFQ_F_GHALF)) { h->gf.drop(); h->gf.rewritten(); }
-    if (h && field == AFQ_F_PHI) h->handover.drop();
+    if (h && field == AFQ_F_PHI) h->step.handover.drop();
     if (!h || !host) return AFQ_EINVAL;
     if (!h->nw) AFQ_FAIL(h, AFQ_ESTATE, "no walkers allocated");
     if (first < 0 || count < 0 || first + count > h->nw) AFQ_FAIL(h, AFQ_EINVAL, "walker range out of bounds");
@@ -779,7 +780,7 @@ int afq_walkers_device_ptr(afq_handle *h, int field, void **dev_ptr, int64_t *by
         if ((rc = ensure_spin_ghalf(h))) return rc;
     }
     h->gf.drop(); h->gf.enabled = false;                 // the caller may write through the pointer
-    if (field == AFQ_F_PHI) { h->handover.drop(); h->handover.enabled = false; }
+    if (field == AFQ_F_PHI) { h->step.handover.drop(); h->step.handover.enabled = false; }
     *dev_ptr = base;
     if (bytes_per_walker) *bytes_per_walker = (int64_t)bytes;
     return AFQ_OK;
@@ -895,27 +896,11 @@ static int force_bias(afq_handle *h, bool with_xbar = true) {
 static int local_energy(afq_handle *h);
 static int local_energy_dets(afq_handle *h);
 
-// Whether THIS step runs its closing Green's function (with the overlap and the weight update) as the tail of the fused
-// propagator's launch: begin and finish in one call (the weight update needs the energy shift), announced with
-// afq_estimates_fuse_next, of the resident closed-shell shape class, and of the kind whose closing evaluation may skip the
-// per-spin store (afq_propagate_finish, GreensRequest::may_skip_store) -- the tail leaves overlap + spin sum behind, nothing
-// else.  Every other step runs the two launches.
-// afq_set_step_fusion_scope(1) drops the first two conditions: an unannounced step's tail stores the per-spin Ghalf too (the
-// request afq_propagate_finish would have made), and the tail of a begin without a finish in the same call evaluates Green's
-// function and overlap only -- the shift is not known yet -- and leaves the weight update to afq_propagate_finish.
-static bool step_fuses(afq_handle *h) {
-    const bool in_scope = h->step_fusion_scope == 1 || (h->step_one_call && h->fuse_est_req);
-    return in_scope && h->step_fusion_mode != 0 && h->gf.enabled && h->ndet == 1 &&
-           h->kind == AFQ_SYS_GENERIC && (h->flags & AFQ_PROP_HYBRID) && (h->flags & AFQ_PROP_FORCE_BIAS) &&
-           !(h->flags & AFQ_PROP_FREE_PROJECTION) && !h->rdm_on && h->nbp == 0 && h->psi_stride == 0 && !h->hirsch &&
-           !k_greens_big_supported(h) && k_fb_use_sum(h) && k_step_fusion_shape(h);
-}
-
 int afq_propagate(afq_handle *h, const double *xi, double eshift_re, double eshift_im) {
-    if (h) { h->step_one_call = true; h->step_eshift = cmake(eshift_re, eshift_im); }
+    if (h) { h->step.one_call = true; h->step.eshift = cmake(eshift_re, eshift_im); }
     const int rc = afq_propagate_begin(h, xi);
-    if (h) h->step_one_call = false;
-    if (rc && h) h->step_tail_done = false;
+    if (h) h->step.one_call = false;
+    if (rc && h) h->step.tail_done = false;
     return rc ? rc : afq_propagate_finish(h, eshift_re, eshift_im);
 }
 
@@ -971,7 +956,7 @@ int afq_propagate_begin(afq_handle *h, const double *xi) {
             else if ((rc = local_energy(h))) return rc;
         }
     }
-    if (k_ueg_fast_supported(h) || hubbard_fused || !k_prop_fused_supported(h)) h->handover.drop();   // (not the fused propagator)
+    if (k_ueg_fast_supported(h) || hubbard_fused || !k_prop_fused_supported(h)) h->step.handover.drop();   // (not the fused propagator)
     if (k_ueg_fast_supported(h)) {
         // plane waves: force bias from the occupied rows of G, fields, and the ~2 nq coefficients that ARE the HS
         // potential, in one launch; B exp(V) B from those coefficients in a second one (k_ueg.hip)
@@ -1023,27 +1008,27 @@ int afq_propagate_begin(afq_handle *h, const double *xi) {
     }
     // symmetric L_n and the fused propagator as the only consumer: the HS potential is stored as its upper
     // triangle only (no scattered mirror writes) and the propagator fetches V[k][row] for k < row
-    h->vhs_upper = fused && h->hs_sym;
+    h->step.vhs_upper = fused && h->hs_sym;
     { PhaseTimer t(h, T_VHS); rc = build_vhs(h); }                                  // :161
-    if (rc) { h->vhs_upper = false; return rc; }
-    if (fused && step_fuses(h)) {
+    if (rc) { h->step.vhs_upper = false; return rc; }
+    if (fused && k_step_fuses(h)) {
         PhaseTimer t(h, T_EXP);                                                     // :251, :162-171, :258, :261-292
         // the closing evaluation of afq_propagate_finish, asked for here with the same request and run by the propagator's launch
         // (scope 1: without the shift -- begin alone -- the weight update stays with finish; unannounced, somebody may read
         //  the per-spin Ghalf)
         GreensRequest req;
-        req.ride_weight = h->step_one_call;
-        if (h->step_one_call) req.eshift = h->step_eshift;
+        req.ride_weight = h->step.one_call;
+        if (h->step.one_call) req.eshift = h->step.eshift;
         req.may_skip_store = h->fuse_est_req;
-        h->step_tail_res = GreensResult();
-        rc = k_prop_fused_greens(h, req, &h->step_tail_res, h->step_fusion_mode == 2);
-        h->vhs_upper = false;
+        h->step.tail_res = GreensResult();
+        rc = k_prop_fused_greens(h, req, &h->step.tail_res, h->step.get(StepState::FUSION) == 2);
+        h->step.vhs_upper = false;
         if (rc) return rc;
-        h->step_tail_done = true;
+        h->step.tail_done = true;
     } else if (fused) {
         PhaseTimer t(h, T_EXP);                                                     // :251, :162-171, :258
         rc = k_prop_fused(h);
-        h->vhs_upper = false;
+        h->step.vhs_upper = false;
         if (rc) return rc;
     } else {
         { PhaseTimer t(h, T_EXP); if ((rc = apply_exp(h, h->vhs))) return rc; }    // :162-171
@@ -1072,11 +1057,11 @@ int afq_propagate_finish(afq_handle *h, double eshift_re, double eshift_im) {
         GreensResult res;
         req.ride_weight = h->ndet == 1 && !le_msd;          // single determinant: k_greens may take the weight update along
         req.eshift = cmake(eshift_re, eshift_im);
-        if (h->step_tail_done) {
+        if (h->step.tail_done) {
             // (the propagator's launch has evaluated it: overlap and spin sum; the per-spin store unless the step was announced
             //  ahead of it; the weight update unless begin ran without the shift -- weight_rode is false then and it runs below)
-            h->step_tail_done = false;
-            res = h->step_tail_res;
+            h->step.tail_done = false;
+            res = h->step.tail_res;
             h->gf.keep(res.store_skipped ? GreensCache::SUM_ONLY : GreensCache::FULL);
         } else if (h->gf.enabled && !fp) {
             // afq_estimates_fuse_next told us that nothing but the next step's force bias will read this Green's function
@@ -1144,7 +1129,7 @@ int afq_log_ovlp_sums(afq_handle *h, double *sums3) {
 int afq_reortho(afq_handle *h, double *detR_out) {
     AFQ_API(h, "afq_reortho");
     if (!h) return AFQ_EINVAL;
-    h->handover.drop();                 // (phi -> phi R^-1: the Green's function survives the QR, B phi does not)
+    h->step.handover.drop();            // (phi -> phi R^-1: the Green's function survives the QR, B phi does not)
     int rc = need_ready(h, false);
     if (rc) { h->gf.drop(); return rc; }
     // Ghalf = (phi^T psi*)^-1 phi^T does not change when phi -> phi R^-1, so a Green's function kept from
@@ -1207,40 +1192,15 @@ int afq_set_exchange_algorithm(afq_handle *h, int mode) {
     return AFQ_OK;
 }
 
-int afq_set_propagator_closed_form(afq_handle *h, int mode) {
-    if (!h || mode < 0 || mode > 2) return AFQ_EINVAL;
-    h->prop_closed_mode = mode;
-    h->handover.drop();
-    return AFQ_OK;
+// the switches of the fused step: validated, stored and the hand-over dropped by their owner (StepState::set)
+static int set_step_switch(afq_handle *h, StepState::Switch which, int value) {
+    return h && h->step.set(which, value) ? AFQ_OK : AFQ_EINVAL;        // (a refused value leaves the handle untouched)
 }
-
-int afq_set_step_fusion(afq_handle *h, int mode) {
-    if (!h || mode < 0 || mode > 2) return AFQ_EINVAL;
-    h->step_fusion_mode = mode;
-    h->handover.drop();
-    return AFQ_OK;
-}
-
-int afq_set_step_fusion_scope(afq_handle *h, int scope) {
-    if (!h || scope < 0 || scope > 1) return AFQ_EINVAL;
-    h->step_fusion_scope = scope;
-    h->handover.drop();
-    return AFQ_OK;
-}
-
-int afq_set_step_tail_overlap(afq_handle *h, int on) {
-    if (!h || on < 0 || on > 1) return AFQ_EINVAL;
-    h->step_tail_overlap = on;
-    h->handover.drop();
-    return AFQ_OK;
-}
-
-int afq_set_step_handover(afq_handle *h, int on) {
-    if (!h || on < 0 || on > 1) return AFQ_EINVAL;
-    h->step_handover = on;
-    h->handover.drop();
-    return AFQ_OK;
-}
+int afq_set_propagator_closed_form(afq_handle *h, int mode) { return set_step_switch(h, StepState::CLOSED_FORM, mode); }
+int afq_set_step_fusion(afq_handle *h, int mode) { return set_step_switch(h, StepState::FUSION, mode); }
+int afq_set_step_fusion_scope(afq_handle *h, int scope) { return set_step_switch(h, StepState::SCOPE, scope); }
+int afq_set_step_tail_overlap(afq_handle *h, int on) { return set_step_switch(h, StepState::TAIL_OVERLAP, on); }
+int afq_set_step_handover(afq_handle *h, int on) { return set_step_switch(h, StepState::HANDOVER, on); }
 
 int afq_propagator_closed_form(afq_handle *h, int *mode) {
     if (!h || !mode) return AFQ_EINVAL;
@@ -1319,7 +1279,7 @@ int afq_vhs(afq_handle *h, const double *xs, double *vhs_out) {
 }
 
 int afq_apply_exponential(afq_handle *h, const double *vhs) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !vhs) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;
@@ -1341,7 +1301,7 @@ int afq_apply_exponential(afq_handle *h, const double *vhs) {
 }
 
 int afq_kinetic(afq_handle *h) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;
@@ -1371,7 +1331,7 @@ int afq_popcontrol_comb(afq_handle *h, double r, double target_weight, int32_t *
     if (h) h->scal_cache_valid = false;
     AFQ_API(h, "afq_popcontrol_comb");
     if (!h) return AFQ_EINVAL;
-    h->handover.drop();                 // (walkers change slots: the images do not travel with the clones)
+    h->step.handover.drop();            // (walkers change slots: the images do not travel with the clones)
     const bool thermal = th_thermal(h) && h->nw;              // thermal walkers: no trial determinant, G and the bins travel
     int rc = AFQ_OK;
     if (thermal) {
@@ -1403,7 +1363,7 @@ int afq_popcontrol_pair_branch(afq_handle *h, const double *u, int nu, double ta
     if (h) h->scal_cache_valid = false;
     AFQ_API(h, "afq_popcontrol_pair_branch");
     if (!h) return AFQ_EINVAL;
-    h->handover.drop();
+    h->step.handover.drop();
     if (th_thermal(h)) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "thermal walkers: pair_branch population control is not supported (comb only)");
     int rc = need_ready(h, false);
     if (rc) { h->gf.drop(); return rc; }
@@ -1485,7 +1445,7 @@ int afq_walker_pack(afq_handle *h, int iw, void *dev_buf) {
 }
 
 int afq_walker_unpack(afq_handle *h, int iw, const void *dev_buf) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !dev_buf) return AFQ_EINVAL;
     int rc = need_walkers(h);
     if (rc) return rc;
@@ -1494,7 +1454,7 @@ int afq_walker_unpack(afq_handle *h, int iw, const void *dev_buf) {
 }
 
 int afq_walkers_copy(afq_handle *h, int src, int dst) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h) return AFQ_EINVAL;
     int rc = need_walkers(h);
     if (rc) return rc;
@@ -1824,7 +1784,7 @@ static int hirsch_ready(afq_handle *h) {
 }
 
 int afq_set_propagator_hirsch(afq_handle *h, const double *bt2, double dt, int charge_decomposition) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !bt2 || dt <= 0) return AFQ_EINVAL;
     if (h->kind != AFQ_SYS_HUBBARD) AFQ_FAIL(h, AFQ_ESTATE, "the Hirsch transformation needs a Hubbard system");
     if (h->ndet > 1) AFQ_FAIL(h, AFQ_EUNSUPPORTED, "Hirsch propagator: single-determinant trials");
@@ -1835,7 +1795,7 @@ int afq_set_propagator_hirsch(afq_handle *h, const double *bt2, double dt, int c
     for (size_t i = 0, n = (size_t)2 * h->M * h->M; i < n && h->bh1_real; ++i) h->bh1_real = bt2[2 * i + 1] == 0.0;
     h->bh1_same = false;
     cache_of(h)->BH1.clear();
-    if ((rc = build_psiB(h))) return rc;
+    if ((rc = step_operands(h))) return rc;
     // propagation/hubbard.py:66-82
     typedef std::complex<double> C;
     C gamma, auxf[2][2], wfac[2];
@@ -1874,7 +1834,7 @@ int afq_set_propagator_hirsch(afq_handle *h, const double *bt2, double dt, int c
 }
 
 int afq_hirsch_kinetic(afq_handle *h) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1883,7 +1843,7 @@ int afq_hirsch_kinetic(afq_handle *h) {
 }
 
 int afq_hirsch_two_body(afq_handle *h, const double *u, int32_t *fields_out, int32_t *used_out) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !u) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1896,7 +1856,7 @@ int afq_hirsch_two_body(afq_handle *h, const double *u, int32_t *fields_out, int
 }
 
 int afq_hirsch_finish(afq_handle *h, double eshift) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1908,7 +1868,7 @@ int afq_hirsch_finish(afq_handle *h, double eshift) {
 
 int afq_propagate_hirsch(afq_handle *h, double eshift) {
     AFQ_API(h, "afq_propagate_hirsch");
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -1942,7 +1902,7 @@ int afq_hirsch_free_projection(afq_handle *h, int on) {
 
 int afq_propagate_hirsch_free(afq_handle *h, const double *u, int32_t *fields_out, double eshift) {
     AFQ_API(h, "afq_propagate_hirsch_free");
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h) return AFQ_EINVAL;
     int rc = hirsch_ready(h);
     if (rc) return rc;
@@ -2030,8 +1990,8 @@ int afq_launch_trace_get(afq_handle *h, char *names_out, int names_len, double *
 
 int afq_propagator_issued_flops(afq_handle *h, double *open_per_walker, double *closed_per_walker) {
     if (!h || !open_per_walker || !closed_per_walker) return AFQ_EINVAL;
-    *open_per_walker = h->prop_issued_open;
-    *closed_per_walker = h->prop_issued_closed;
+    *open_per_walker = h->step.issued.open;
+    *closed_per_walker = h->step.issued.closed;
     return AFQ_OK;
 }
 

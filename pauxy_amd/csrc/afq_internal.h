@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/afqmc_hip.h"
 #include "greens_cache.h"
+#include "step_state.h"
 #include "dev_mem.h"
 
 typedef double2 cplx;   // (x = re, y = im), same bytes as numpy complex128
@@ -50,18 +51,6 @@ enum ThKind { TH_NONE = 0, TH_REAL, TH_CPLX_DIAG, TH_CPLX_DENSE };
 // device memory.  WIDE (AFQ_THERMAL_WIDE, complex; AFQ_THERMAL_DELAYED, real): one matrix in LDS, two columns per lane.
 enum ThEngine { TH_ENGINE_RESIDENT = 0, TH_ENGINE_STREAMED, TH_ENGINE_WIDE };
 
-// Whether the hand-over buffers of the handle (t0_next, t0_ready) describe the walkers as they are now.  A launch of the
-// fused propagator that produced sets `current`; everything that writes phi, moves a walker to another slot, changes the
-// propagator, the trial, the Taylor order or a mode switch of the step drops it, and so does every propagator launch that is
-// not that kernel with the early overlap (k_prop_fused drops on entry and sets again behind a launch that produced).  A device
-// pointer to phi handed out (afq_walkers_device_ptr) turns it off for the life of the handle: the caller may write through it.
-struct StepHandover {
-    bool current = false;
-    bool enabled = true;
-    void drop() { current = false; }
-    void produced() { current = enabled; }
-};
-
 struct afq_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -96,11 +85,6 @@ struct afq_handle {
     bool atil_unavailable = false;  // automatic mode: Atil did not fit when it was to be built -> T-intermediate kernel
     bool rchol_same = false;        // alpha and beta blocks of rchol are bitwise equal
     int exx_mode = 0;               // afq_set_exchange_algorithm: 0 auto, 1 T-intermediate (exx_kernel), 2 quadratic form
-    int step_fusion_mode = 2;       // afq_set_step_fusion: 0 never, 1 tail behind the 4-multiplication body, 2 behind the 3-multiplication one
-    int step_fusion_scope = 0;      // afq_set_step_fusion_scope: 0 announced one-call steps, 1 every step of the shape class
-    int step_tail_overlap = 1;      // afq_set_step_tail_overlap: the mode-2 tail's overlap matrix and inverse under the closing pass
-    int step_handover = 1;          // afq_set_step_handover: that launch also makes the next step's opening one-body pass
-    int prop_closed_mode = 0;       // afq_set_propagator_closed_form: 0 auto, 1 streamed deal, 2 V resident in registers (where eligible)
     cplx *exq_y = nullptr;          // [2 * slices, nw, ceil(N M / 16)] per-tile partial sums of the quadratic form
     size_t exq_y_len = 0;
     cplx *H1 = nullptr;             // [2, M, M]
@@ -149,15 +133,6 @@ struct afq_handle {
     long psi_stride = 0;            // elements between per-walker 'trials' (back-propagation only; 0 = shared psi)
     bool psi_real = false;          // every imaginary part of the uploaded trial is exactly zero
     bool psi_closed = false;        // na == nb and the alpha and beta blocks of the (single, shared) trial are bitwise equal
-    // psi^H B for the fused propagator's early overlap (k_fused_closed.h): psiB_cT[i][k] = sum_m psi[m][i] BH1[0][m][k], [na, M]
-    // real, made on the host whenever the trial or the propagator is uploaded; null unless the trial is single, real and
-    // closed and BH1 real and the same for both spins
-    double *psiB_cT = nullptr;
-    const void *psiB_psi = nullptr, *psiB_bh1 = nullptr;    // the device trial and propagator it was made for (never dereferenced)
-    // B2 = Re(BH1[0]) . Re(BH1[0]), [M, M] real, for the step hand-over (k_fused_closed.h): made with psiB_cT, under the same
-    // conditions, in long double on the host; b2_bh1 is the device propagator it was made for (never dereferenced)
-    double *B2 = nullptr;
-    const void *b2_bh1 = nullptr;
     // Closed-shell populations (round 5).  The Green's function kernel checks every walker's spin blocks for bitwise equality
     // (greens_small_kernel); a walker that fails raises closed_bad to the epoch of that launch (gf.closed says which Ghalf
     // the verdict is about).  The host never reads the flag.
@@ -305,7 +280,6 @@ struct afq_handle {
     bool have_prop = false;
     cplx *BH1 = nullptr;            // [2, M, M]
     double cap_frac = 0.0, cap_total = -1.0;   // afq_set_weight_cap: cap applied inside the weight-update kernel
-    bool vhs_upper = false;         // set around build_vhs + k_prop_fused: VHS[w] holds only its upper triangle
     bool bh1_same = false;          // BH1[0] and BH1[1] are bitwise equal
     bool bh1_real = false;          // every imaginary part of BH1 is exactly zero (real trial, real L_n)
     cplx *mf_shift = nullptr;       // [K]
@@ -336,12 +310,7 @@ struct afq_handle {
     cplx *gdiag = nullptr;          // Hubbard: diag(G_s) as partial sums over row blocks of Ghalf, [2 nw, gdiag_parts, M]
     int gdiag_parts = 0;
     GreensCache gf;                 // what ghalf / ghalf_sum / gdiag / vbias / ovlp_new hold for the current walkers
-    // The step hand-over of the fused propagator's 3-multiplication tail kernel: t0_next[w] holds T_0 = B phi[w] of the NEXT
-    // step as the resident body's image of T, t0_ready[w] says for which walkers (written by every launch of that kernel);
-    // both are allocated the first time a launch can produce.  `handover` says whether they are about the CURRENT phi.
-    unsigned char *t0_next = nullptr;   // [nw][ceil(M / 4) * 2048 B]
-    int *t0_ready = nullptr;            // [nw]
-    StepHandover handover;
+    StepState step;                 // the fused step: switches, host-made operands, hand-over, transients, counts (step_state.h)
     cplx *xbar = nullptr, *xs = nullptr;              // [nw, K]
     cplx *cmf = nullptr, *cfb = nullptr;              // [nw]
     cplx *vhs = nullptr;            // [nw, nv, M, M] or [nw, nv, M] when vhs_diag
@@ -358,11 +327,6 @@ struct afq_handle {
     double *gfrag = nullptr;        // Ghalf in MFMA fragment order (energy kernel B operand)
     size_t gfrag_len = 0;
     bool prop_pending = false;                      // afq_propagate_begin done, afq_propagate_finish outstanding
-    // afq_propagate (begin and finish in one call): the energy shift is known while the propagator is launched, which may then
-    // take the step's closing Green's function along as its tail; step_tail_done tells the finish half that it has, with what result
-    bool step_one_call = false, step_tail_done = false;
-    cplx step_eshift = {0.0, 0.0};
-    GreensResult step_tail_res;
     double *est_stage = nullptr;                    // mapped host memory: estimator sums + scal[4] + sequence number
     unsigned long long est_seq = 0;
     double scal_cache[AFQ_NSCAL] = {0};   // scal[] as of the last afq_estimates_get_end; stale after a population control
@@ -371,7 +335,6 @@ struct afq_handle {
     unsigned ktrace_mask = 0;          // bit k: event pairs around the launches of kernel kind k
     std::vector<hipEvent_t> ktrace_ev[AFQ_K_COUNT];   // start/stop pairs
     double issued_flops[AFQ_K_COUNT] = {0, 0, 0, 0, 0};   // matrix-pipe flops of the last launch of each kind (afq_kernel_issued_flops)
-    double prop_issued_open = 0.0, prop_issued_closed = 0.0;   // per walker, last fused-propagator launch (afq_propagator_issued_flops)
     int ktrace_used[AFQ_K_COUNT] = {0, 0, 0, 0, 0};
     int ktrace_stride[AFQ_K_COUNT] = {1, 1, 1, 1, 1}, ktrace_seen[AFQ_K_COUNT] = {0, 0, 0, 0, 0};   // every n-th launch of a kind is timed
     // afq_launch_trace: an event pair around EVERY launch, keyed by the launch's breadcrumb name (a profile pass, not
@@ -429,6 +392,10 @@ struct afq_handle {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_energy_ms = 0.0;
 };
+
+// An entry point that rewrites phi, the trial or the propagator: neither the cached Green's function nor the step hand-over
+// describes the walkers any more
+inline void drop_walk_caches(afq_handle *h) { if (h) { h->gf.drop(); h->step.handover.drop(); } }
 
 inline bool th_thermal(const afq_handle *h) { return h->th_kind != TH_NONE; }
 inline bool th_complex(const afq_handle *h) { return h->th_kind == TH_CPLX_DIAG || h->th_kind == TH_CPLX_DENSE; }
@@ -598,15 +565,15 @@ bool k_fb_use_sum(afq_handle *h);                           // force bias runs o
 int k_vhs_generic(afq_handle *h);                           // xs -> vhs
 int k_apply_exponential(afq_handle *h, const cplx *vhs);    // phi <- sum_n vhs^n/n! phi
 int k_full_G(afq_handle *h);                                // G = conj(psi) ghalf
-// k_fused.hip
+// k_fused.hip: reads of the launch plan (step_plan.h) made of the handle as it is
 int k_prop_fused_supported(afq_handle *h);
-int k_prop_closed_resident(afq_handle *h);
+int k_prop_closed_resident(afq_handle *h);                  // closed walkers take the body with V resident in registers
+bool k_step_fuses(afq_handle *h);                           // THIS step runs its closing Green's function as the tail
 struct GreensLaunch;
 // phi <- B exp(V) B phi for live walkers, in place; with `tail` (k_prop_fused_greens, k_small.hip) the Green's function, overlap and weight
 // update of EVERY walker's new phi behind it in the same launch, the resident closed-shell body with 3-multiplication Taylor
 // products when mul3
 int k_prop_fused(afq_handle *h, const GreensLaunch *tail = nullptr, bool mul3 = false);
-int k_step_fusion_shape(afq_handle *h);                    // the shape class whose announced steps run the tail
 // k_hirsch.hip
 int k_hirsch_alive(afq_handle *h, int mode);
 int k_hirsch_kinetic(afq_handle *h);

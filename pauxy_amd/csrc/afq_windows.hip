@@ -151,7 +151,7 @@ int bp_backward(afq_handle *h, int nd, int nstblz, cplx *stack, cplx *ot, double
         } else {
             if ((rc = k_bp_fields(h, i))) return rc;
             {
-                Lent<bool> l_upper(h->vhs_upper, fused && h->hs_sym);
+                Lent<bool> l_upper(h->step.vhs_upper, fused && h->hs_sym);
                 if ((rc = build_vhs(h))) return rc;
                 for (int d = 0; fused && d < nd; ++d) {
                     Lent<cplx *> l_slab(h->phi, A + d * slab);
@@ -190,7 +190,7 @@ size_t bpo_two_len(const afq_handle *h) {
 
 int bp_update(afq_handle *h, const double *phi_bp0, int nstblz, int restore_weights, int eval_energy,
               int reset, double *est_out, double *two_rdm_out, double *fock_out) {
-    if (h) { h->gf.drop(); h->handover.drop(); }
+    drop_walk_caches(h);
     if (!h || !phi_bp0 || !est_out || nstblz < 1 || restore_weights < 0 || restore_weights > 2) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;
@@ -354,7 +354,7 @@ int afq_bp_update_msd(afq_handle *h, int ndet, const double *dets, const double 
     AFQ_API(h, "afq_bp_update_msd");
     // read-only on the walk, as afq_itcf_update: the Green's function the last step left for the next one stays valid
     GreensCache::ReadOnly read_only(h ? &h->gf : nullptr);
-    if (h) h->handover.drop();          // (the window borrows phi and the step machinery)
+    if (h) h->step.handover.drop();     // (the window borrows phi and the step machinery)
     if (!h || !dets || !coeffs || !est_out || ndet < 1 || nstblz < 1 || restore_weights < 0 || restore_weights > 2)
         return AFQ_EINVAL;
     int rc = need_ready(h, true);
@@ -518,7 +518,7 @@ int afq_itcf_update(afq_handle *h, const double *psi_T, int nstblz, double *spgf
     // the window is read-only on the walk: the Green's function the last step left for the next one stays valid (a window
     // that fails half way leaves it invalid, which only costs a recomputation)
     GreensCache::ReadOnly read_only(h ? &h->gf : nullptr);
-    if (h) h->handover.drop();          // (the window borrows phi and the step machinery)
+    if (h) h->step.handover.drop();     // (the window borrows phi and the step machinery)
     if (!h || !psi_T || !spgf_out || !denom_out || nstblz < 1) return AFQ_EINVAL;
     int rc = need_ready(h, true);
     if (rc) return rc;

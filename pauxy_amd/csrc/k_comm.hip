@@ -663,7 +663,7 @@ int stage_unpack(afq_handle *h, bool with_greens, bool pack_too = false) {
     // of this rank's population carries over because the unpack kernel checks the walkers that arrive (closed_half)
     const bool closed_too = with_greens && h->closed_bad && h->gf.closed.current(h->gf) && h->na == h->nb;
     h->gf.cloned(closed_too ? GreensCache::CLOSED : 0);
-    h->handover.drop();                                           // (the step hand-over does not travel with a walker)
+    h->step.handover.drop();                                      // (the step hand-over does not travel with a walker)
     afq_comm_state *c = cs_of(h);
     if (c->nranks > 1) {
         PackArgs p;
@@ -1094,7 +1094,7 @@ int afq_popcontrol_comb_local(afq_handle **hs, int n, double r, double target, i
         hipSetDevice(h->device);
         h->scal_cache_valid = false;
         keep[i] = h->gf.take() == GreensCache::FULL && h->ndet == 1;       // (never the spin sum alone: the pairs ship Ghalf)
-        h->handover.drop();
+        h->step.handover.drop();
     }
     // a cached Green's function travels only if every rank has one (the slots of a pair must agree)
     bool with_greens = true;

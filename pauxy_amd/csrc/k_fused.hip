@@ -28,22 +28,20 @@
 
 #include "mfma_gemm_wg.h"
 #include "greens_small.h"
+#include "step_plan.h"
 
 #define PF_D 3
-// waves per work-group: 8 (product) or 16 (experiment: -DPF_NW=16; four waves per SIMD, 2 x 1 tile deals)
-#ifndef PF_NW
+// waves per work-group.  (Sixteen -- four waves per SIMD, 2 x 1 tile deals -- ran in the same time as eight, HISTORY.md; that
+// variant is no longer in the source.)
 #define PF_NW 8
-#endif
 #define PF_NT (64 * PF_NW)
-// waves that refill the operand ring: all of them (PF_LW == PF_NW: two fragments per wave and chunk), or the last PF_LW.
-// Measured NEGATIVE (round 4, C3): PF_LW = 4 -- waves 4-7, the lighter half of the contiguous-column deal, issuing four
+// waves that refill the operand ring: all of them, two fragments per wave and chunk.
+// Measured NEGATIVE (round 4, C3): the last four only -- waves 4-7, the lighter half of the contiguous-column deal, issuing four
 // LDS-DMA instructions per chunk each so that the waves with the 2 x 2 tile blocks never stall in DMA issue -- 149.3 us
 // against 140.2 us: four back-to-back DMA instructions hold a wave for several hundred cycles and the chunk barrier makes
-// everybody wait for it.
-#ifndef PF_LW
+// everybody wait for it (NEGATIVES.md; profiles/r06_prop_fused_loader_deal_experiment.patch).
 #define PF_LW PF_NW
-#endif
-#define PF_FPW (16 / PF_LW)      // operand fragments each refilling wave moves per chunk
+#define PF_FPW (16 / PF_LW)      // operand fragments each wave moves per chunk
 
 struct PropFusedArgs {
     int M, na, nb, nt, order;
@@ -154,8 +152,8 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a) {
 #undef PF_LEAVE
 }
 
-// The same with the step's closing Green's function as its tail (a step of the resident shape class, see step_fuses in
-// afq_api.hip): behind whichever body the walker took -- or none, a dead walker's overlap is evaluated like any other -- every
+// The same with the step's closing Green's function as its tail (a step of the resident shape class, see k_step_fuses
+// below): behind whichever body the walker took -- or none, a dead walker's overlap is evaluated like any other -- every
 // wave waits for its stores of phi, one barrier makes them the work-group's, and greens_small_body runs on the same dynamic
 // LDS: the walker's new phi, both overlap matrices, their inverses, Ghalf (its spin sum alone on an announced step) and the
 // weight update where the shift is known, as greens_small_kernel<true, true> with the same arguments would leave them.  A
@@ -230,157 +228,103 @@ __global__ __launch_bounds__(PF_NT) void prop_fused_kernel(PropFusedArgs a, Gree
     greens_small_body<true, true, true>(ga, wa, w, smem, stored_closed, &early);
 }
 
-int k_prop_fused_supported(afq_handle *h) {
-    return !h->vhs_diag && h->nv == 1 && h->M <= 104 && h->na <= 32 && h->nb <= 32 && h->nb > 0;
+// ---- the host side.  What a launch is, is decided by step_plan() (step_plan.h) from the facts gathered here; the code below
+// reads the plan.
+static_assert(PF_D == STEP_PLAN_RING, "the plan sizes the launch's LDS for this operand ring");
+
+// The handle as the plan sees it: system, propagator, population, switches (no step, no tail)
+static StepFacts step_facts(afq_handle *h) {
+    const StepState &st = h->step;
+    StepFacts f;
+    f.M = h->M; f.na = h->na; f.nb = h->nb; f.nw = h->nw; f.order = h->exp_order;
+    f.nv = h->nv; f.vhs_diag = h->vhs_diag; f.same_b = h->bh1_same; f.b_real = h->bh1_real;
+    f.closed_mode = st.get(StepState::CLOSED_FORM);
+    f.fusion_mode = st.get(StepState::FUSION); f.fusion_scope = st.get(StepState::SCOPE);
+    f.tail_overlap = st.get(StepState::TAIL_OVERLAP) != 0; f.handover = st.get(StepState::HANDOVER) != 0;
+    return f;
 }
 
-// Shape class of the closed-shell body with V resident in registers (k_fused_closed.h), and the form the handle asks for
-// (afq_set_propagator_closed_form): closed walkers of any other shape, and all of them in mode 1, take the streamed deal.
-int k_prop_closed_resident(afq_handle *h) {
-    // LDS of the body against the launch's (k_prop_fused): both images of T, psi^H B as A fragments (1 KB per k-step) and the
-    // three partial products of the split deal (4 KB each); a shape that did not fit would take the streamed deal
-    const size_t KS = (h->M + 3) / 4, NCH = (h->M + 7) / 8;
-    if (KS * (2 * 2048 + 1024) + 3 * 4096 > NCH * 8192 + (size_t)PF_D * 16384) return 0;
-    return PF_NW == 8 && k_prop_fused_supported(h) && h->prop_closed_mode != 1 && h->bh1_same && h->bh1_real &&
-           h->na == h->nb && h->na > 16 && h->na <= 32 && h->M > 96 && h->M <= 104 && h->exp_order > 0;
+int k_prop_fused_supported(afq_handle *h) { return step_plan(step_facts(h)).supported; }
+// (the form the handle asks for included, afq_set_propagator_closed_form)
+int k_prop_closed_resident(afq_handle *h) { return step_plan(step_facts(h)).resident_class; }
+
+// Whether THIS step runs its closing Green's function (with the overlap and the weight update) as the tail of the fused
+// propagator's launch: begin and finish in one call (the weight update needs the energy shift), announced with
+// afq_estimates_fuse_next, of the resident closed-shell shape class, and of the kind whose closing evaluation may skip the
+// per-spin store (afq_propagate_finish, GreensRequest::may_skip_store) -- the tail leaves overlap + spin sum behind, nothing
+// else.  Every other step runs the two launches.
+// afq_set_step_fusion_scope(1) drops the first two conditions: an unannounced step's tail stores the per-spin Ghalf too (the
+// request afq_propagate_finish would have made), and the tail of a begin without a finish in the same call evaluates Green's
+// function and overlap only -- the shift is not known yet -- and leaves the weight update to afq_propagate_finish.
+bool k_step_fuses(afq_handle *h) {
+    StepFacts f = step_facts(h);
+    f.one_call = h->step.one_call;
+    f.announced = h->fuse_est_req;
+    f.plain_step = h->gf.enabled && h->ndet == 1 && h->kind == AFQ_SYS_GENERIC && (h->flags & AFQ_PROP_HYBRID) &&
+                   (h->flags & AFQ_PROP_FORCE_BIAS) && !(h->flags & AFQ_PROP_FREE_PROJECTION) && !h->rdm_on && h->nbp == 0 &&
+                   h->psi_stride == 0 && !h->hirsch && !k_greens_big_supported(h) && k_fb_use_sum(h);
+    return step_plan(f).fuses;
 }
 
-// Shape class of the announced steps that run their closing Green's function as the propagator's tail: the resident class,
-// with the tail's LDS image (greens_fill's size: both overlap matrices, their inverses, the walker) inside the propagator's own
-int k_step_fusion_shape(afq_handle *h) {
-    if (!k_prop_closed_resident(h)) return 0;
-    const size_t nmax = h->na, NCH = (h->M + 7) / 8;
-    const size_t tail = sizeof(cplx) * (2 * (nmax * nmax + 2 * nmax) + ((2 * nmax + 3) / 4 + 1) + (size_t)h->M * h->nt);
-    return tail <= NCH * 8192 + (size_t)PF_D * 16384;
-}
+// The eight instantiations, in the order of StepVariant (step_plan.h): the kernel, its breadcrumb / launch-trace name and the
+// dynamic-LDS cap raised so far per device.  The kernels differ in their argument lists; every launch passes the same array of
+// argument addresses, of which each kernel takes the ones it has.  (The entries stand in the order in which the host code
+// instantiated the kernels before there was a table: the device code is emitted in that order.)
+typedef void (*PropKernel)(PropFusedArgs);
+typedef void (*PropTail4Kernel)(PropFusedArgs, GreensArgs, WeightArgs, const double *);
+typedef void (*PropTail3Kernel)(PropFusedArgs, GreensArgs, WeightArgs, const double *, StepHandoverArgs);
+struct PropVariant { const void *kern; const char *name; size_t lds_set[AFQ_MAX_DEVICES]; };
+#define PROP_VARIANT(type, kern) {(const void *)static_cast<type>(kern), #kern, {0}}
+static PropVariant prop_variants[PV_COUNT] = {
+    PROP_VARIANT(PropTail3Kernel, (prop_fused_kernel<false, 7, true, true>)),
+    PROP_VARIANT(PropTail4Kernel, (prop_fused_kernel<false, 7, true, false>)),
+    PROP_VARIANT(PropKernel, (prop_fused_kernel<true, 6>)), PROP_VARIANT(PropKernel, (prop_fused_kernel<true, 0>)),
+    PROP_VARIANT(PropKernel, (prop_fused_kernel<false, 7>)), PROP_VARIANT(PropKernel, (prop_fused_kernel<false, 6>)),
+    PROP_VARIANT(PropKernel, (prop_fused_kernel<false, 5>)), PROP_VARIANT(PropKernel, (prop_fused_kernel<false, 0>))};
+#undef PROP_VARIANT
 
 int k_prop_fused(afq_handle *h, const GreensLaunch *tail, bool mul3) {
+    StepState &st = h->step;
+    StepFacts f = step_facts(h);
+    if (tail) {
+        // (afq_propagate has checked the step and k_step_fuses the shape; the launch is named for the propagator it is)
+        f.tail = true; f.mul3 = mul3; f.tail_lds = tail->lds;
+        f.tail_psi_real = tail->a.psi_real; f.tail_psi_closed = tail->a.psi_closed; f.tail_shared_psi = tail->a.psi_stride == 0;
+        f.tail_spin_sum = tail->a.gsum && tail->a.ghalf && !tail->a.oinv;
+        f.psiB_ready = st.psiB_ready(tail->a.psi, h->BH1);
+    }
+    f.B2_ready = st.B2_ready(h->BH1);
+    f.handover_enabled = st.handover.enabled; f.handover_current = st.handover_current();
+    const StepPlan p = step_plan(f);
+    st.handover.drop();             // whatever this launch turns out to be, the hand-over of the launch before is gone with it
+    if (p.produces && (!st.t0_next || !st.t0_ready)) {
+        AFQ_TRY(dev_alloc(h, LT_WALKERS, &st.t0_next, (size_t)h->nw * ((h->M + 3) / 4) * 2048, "step hand-over image"));
+        AFQ_TRY(dev_alloc(h, LT_WALKERS, &st.t0_ready, (size_t)h->nw, "step hand-over flags"));
+    }
+    st.issued = plan_issued_flops(p);
+    h->issued_flops[AFQ_K_PROPAGATOR] = st.issued.total;
+    if (p.refusal) AFQ_FAIL(h, AFQ_ESTATE, p.refusal);
+
     PropFusedArgs a;
     a.M = h->M; a.na = h->na; a.nb = h->nb; a.nt = h->nt; a.order = h->exp_order;
-    a.vhs_upper = h->vhs_upper ? 1 : 0;
-    a.same_b = h->bh1_same ? 1 : 0;
-    a.b_real = h->bh1_real ? 1 : 0;
-    a.rem4 = (h->M > 96 && h->M <= 100) ? 1 : 0;
-    // (hybrid column tiling of the two-slots-per-spin layout -- both spins with 17 .. 28 electrons, their second slots as
-    //  4-column units -- measured NEGATIVE at C3, round 4: 148.6 us against 145.5 us -- three 4x4x4 units need 9 MFMA + 3 add
-    //  instructions where the padded 16x16x4 tile needs 3 + 1, and a wave that multiplies mostly units is bound by
-    //  instruction issue, not by the matrix pipe)
-    a.hyb = 0;
-    // contiguous columns: one one-body matrix for both spins (the HS potential never depends on the spin), 48 < na + nb <= 56
-    // (a third unit per row tile would unbalance the deal and push wave 7 over 256 registers)
-    a.contig = 0; a.symcols = 0;
-    if (a.rem4 && a.same_b && h->na > 16 && h->nb > 16 && h->nt > 48 && h->nt <= 56 && PF_NW == 8) {
-        a.contig = 1;
-        a.hyb = (h->nt - 48 + 3) / 4;
-    }
-    a.symcols = (a.contig && h->na == h->nb) ? 1 : 0;
-    a.closed_try = 0;           // (set below, once the deal is known)
+    a.vhs_upper = st.vhs_upper ? 1 : 0;
+    a.same_b = f.same_b ? 1 : 0; a.b_real = f.b_real ? 1 : 0;
+    a.rem4 = p.rem4; a.hyb = p.hyb; a.symcols = p.symcols; a.closed_try = p.closed_try; a.contig = p.contig;
     a.BH1 = h->BH1; a.vhs = h->vhs; a.phi = h->phi; a.alive = h->alive; a.zero16 = h->zero_page;
     a.n_closed = h->counters + 3;
-    const int NCH = (h->M + 7) / 8;
-    const size_t lds = (size_t)NCH * 8192 + (size_t)PF_D * 16384;
-    static size_t lds_set[8][AFQ_MAX_DEVICES] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
-    const bool narrow = h->na <= 16 && h->nb <= 16;
-    // the overlap matrix and its inverse under the closing pass of the resident body (afq_set_step_tail_overlap): the
-    // 3-multiplication tail of a step whose closed walkers take the tail's one-spin path against a real trial -- psiB_cT exists
-    // for such a trial and one real one-body matrix only (afq_api.hip)
-    const bool early = tail && mul3 && h->step_tail_overlap && h->psiB_cT && k_prop_closed_resident(h) &&
-                       tail->a.psi_real && tail->a.psi_closed && tail->a.psi_stride == 0 &&
-                       (const void *)tail->a.psi == h->psiB_psi && (const void *)h->BH1 == h->psiB_bh1 &&
-                       tail->a.gsum && tail->a.ghalf && !tail->a.oinv;
-    // The step hand-over (afq_handle::handover): what the launch before left is taken only when the host still holds it current
-    // and this launch is the kernel that made it; whatever this launch turns out to be, the old one is gone with it.
-    const bool consumes = early && h->handover.current && h->handover.enabled && h->t0_next && h->t0_ready;
-    h->handover.drop();
-    const bool produces = early && h->step_handover && h->handover.enabled && h->B2 && (const void *)h->BH1 == h->b2_bh1;
-    if (produces && (!h->t0_next || !h->t0_ready)) {
-        AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->t0_next, (size_t)h->nw * ((h->M + 3) / 4) * 2048, "step hand-over image"));
-        AFQ_TRY(dev_alloc(h, LT_WALKERS, &h->t0_ready, (size_t)h->nw, "step hand-over flags"));
-    }
+    a.resident = p.resident;
+    const double *psiB = p.early ? st.psiB_cT : nullptr;
+    StepHandoverArgs ho;
+    ho.t0_next = st.t0_next; ho.ready = st.t0_ready; ho.B2 = st.B2; ho.n_handed = h->counters + 9;
+    ho.consume = p.consumes ? 1 : 0; ho.produce = p.produces ? 1 : 0;
+    void *args[] = {&a, tail ? (void *)&tail->a : nullptr, tail ? (void *)&tail->wa : nullptr, &psiB, &ho};
+
     KernelTrace kt(h, AFQ_K_PROPAGATOR);
-    {   // matrix-pipe flops of this launch: (order complex products by 3 multiplications + 2 one-body applications by 2 or
-        // 3) x k-steps of 4 x existing 16 x 16 tiles (2048 flop per v_mfma_f64_16x16x4, 512 per 4x4x4 remainder unit)
-        const int nrt_ = (h->M + 15) / 16, ct = (h->na + 15) / 16 + (h->nb + 15) / 16;
-        const double ksteps = 2.0 * NCH;
-        const double per_pass = ksteps * (2048.0 * (a.rem4 ? nrt_ - 1 : nrt_) * ct + 512.0 * (a.rem4 ? ct : 0));
-        // contiguous columns: three full slots + hyb units per row tile in the Taylor products, four remainder units in all
-        const double taylor_pass = a.contig ? ksteps * (2048.0 * (nrt_ - 1) * 3 + 512.0 * (nrt_ - 1) * a.hyb + 512.0 * 4) : per_pass;
-        h->issued_flops[AFQ_K_PROPAGATOR] = (3.0 * h->exp_order * taylor_pass + 2.0 * (a.b_real ? 2.0 : 3.0) * per_pass) * h->nw;
-        h->prop_issued_open = h->issued_flops[AFQ_K_PROPAGATOR] / h->nw;
-        // a closed-shell walker (afq_counters [3]) issues the alpha slots only in its Taylor products: two column slots x the
-        // row tiles (+ two remainder units in the M <= 100 deal), one slot when narrow; its one-body passes multiply every slot.
-        // Waves that repeat a tile (five row tiles, narrow) and row tiles that do not exist are not counted, as above
-        const int cta = (h->na + 15) / 16;
-        const double closed_pass = ksteps * (2048.0 * (a.rem4 ? nrt_ - 1 : nrt_) * cta + 512.0 * (a.rem4 ? cta : 0));
-        h->prop_issued_closed = 3.0 * h->exp_order * closed_pass + 2.0 * (a.b_real ? 2.0 : 3.0) * per_pass;
-        // ... through the resident body: seven padded row tiles x the two alpha slots x ceil(M / 4) k-steps in every product
-        // (4-multiplication Taylor products, two real products in each of the two one-body passes)
-        // (the one-body passes the launch really issues: the opening one unless the walkers start from the hand-over, the
-        //  closing one, and the next step's opening one where the launch produces -- two in steady state, as without it)
-        if (k_prop_closed_resident(h)) {
-            const double passes = (consumes ? 0.0 : 1.0) + 1.0 + (produces ? 1.0 : 0.0);
-            h->prop_issued_closed = ((tail && mul3 ? 3.0 : 4.0) * h->exp_order + passes * 2.0) * ((h->M + 3) / 4) * 2048.0 * 7 * 2;
-        }
-        if (tail) {
-            // ... and the tail's (greens_small_body, n <= 32): the overlap matrix as (n / 16)^2 tiles per spin over the k-steps of M
-            // in whole groups of four, two multiplications per k-step against a real trial, else three; O^-1 phi^T as (n / 16) x
-            // (M / 16) tiles per spin over ceil(n / 4) k-steps of three.  A closed walker evaluates one spin.  (The same count
-            // whether the tail stores the per-spin Ghalf or not and whether the weight update rides: those are stores and
-            // one thread's scalar arithmetic, no MFMA.)
-            const double t16 = (h->na + 15) / 16, m16 = (h->M + 15) / 16;
-            const double ks1 = 4.0 * (((h->M + 3) / 4 + 3) / 4), ks3 = (h->na + 3) / 4;
-            const double spin = 2048.0 * (t16 * t16 * ks1 * (tail->a.psi_real ? 2.0 : 3.0) + t16 * m16 * ks3 * 3.0);
-            h->prop_issued_open += 2.0 * spin;
-            h->prop_issued_closed += (tail->a.psi_closed ? 1.0 : 2.0) * spin;
-            // ... with the overlap matrix made early by the resident body (psi^H B times the Taylor sum: four tiles over the
-            // ceil(M / 4) k-steps, two real multiplications each) in place of the tail's own
-            if (early) h->prop_issued_closed += 2048.0 * (4.0 * ((h->M + 3) / 4) * 2.0 - t16 * t16 * ks1 * 2.0);
-            h->issued_flops[AFQ_K_PROPAGATOR] = h->prop_issued_open * h->nw;
-        }
-    }
-    // every tile of the deal present: wide with 5-7 row tiles (waves 4-7 own the tiles from 4 on) and two column tiles
-    // per spin, or narrow with six row tiles
-    const int nrt = (h->M + 15) / 16;
-    const bool nofull = PF_NW != 8;
-    const int full = nofull ? 0 : narrow ? (nrt == 6 ? 6 : 0) : (nrt >= 5 && h->na > 16 && h->nb > 16 ? nrt : 0);
-    // closed-shell deals: one matrix for both spins (the chain then acts on the spin blocks alike), as many electrons of
-    // either spin, and a deal without holes: the contiguous-column deal with twins in like slots (symcols), or two slots per spin
-    a.closed_try = (a.same_b && h->na == h->nb && h->exp_order > 0 && full != 0 && PF_NW == 8 &&
-                    (!a.contig || a.symcols)) ? 1 : 0;
-    a.resident = (a.closed_try && full == 7 && k_prop_closed_resident(h)) ? 1 : 0;
-#define PF_LAUNCH_(NARROW_, FULL_, SLOT_)                                                                     \
-    do {                                                                                                      \
-        AFQ_HIP(h, afq_raise_lds((const void *)prop_fused_kernel<NARROW_, FULL_>, lds, lds_set[SLOT_]));      \
-        AFQ_LAUNCH(h, (prop_fused_kernel<NARROW_, FULL_>), dim3(h->nw), dim3(PF_NT), lds, h->stream, a);      \
-    } while (0)
-    if (tail) {
-        // (afq_propagate has checked the step and k_step_fusion_shape the shape; the launch is named for the propagator it is)
-        if (full != 7 || !a.resident || tail->lds > lds)
-            AFQ_FAIL(h, AFQ_ESTATE, "internal: a Green's function tail on a propagator launch outside its shape class");
-        if (mul3) {
-            void (*const kern)(PropFusedArgs, GreensArgs, WeightArgs, const double *, StepHandoverArgs) =
-                prop_fused_kernel<false, 7, true, true>;
-            AFQ_HIP(h, afq_raise_lds((const void *)kern, lds, lds_set[6]));
-            const double *psiB = early ? h->psiB_cT : nullptr;
-            StepHandoverArgs ho;
-            ho.t0_next = h->t0_next; ho.ready = h->t0_ready; ho.B2 = h->B2; ho.n_handed = h->counters + 9;
-            ho.consume = consumes ? 1 : 0; ho.produce = produces ? 1 : 0;
-            AFQ_LAUNCH(h, (prop_fused_kernel<false, 7, true, true>), dim3(h->nw), dim3(PF_NT), lds, h->stream, a, tail->a, tail->wa, psiB, ho);
-        } else {
-            const double *psiB = nullptr;
-            void (*const kern)(PropFusedArgs, GreensArgs, WeightArgs, const double *) = prop_fused_kernel<false, 7, true, false>;
-            AFQ_HIP(h, afq_raise_lds((const void *)kern, lds, lds_set[7]));
-            AFQ_LAUNCH(h, (prop_fused_kernel<false, 7, true, false>), dim3(h->nw), dim3(PF_NT), lds, h->stream, a, tail->a, tail->wa, psiB);
-        }
-    }
-    else if (narrow && full) PF_LAUNCH_(true, 6, 0);
-    else if (narrow) PF_LAUNCH_(true, 0, 1);
-    else if (full == 7) PF_LAUNCH_(false, 7, 2);
-    else if (full == 6) PF_LAUNCH_(false, 6, 3);
-    else if (full == 5) PF_LAUNCH_(false, 5, 4);
-    else PF_LAUNCH_(false, 0, 5);
-#undef PF_LAUNCH_
+    PropVariant &v = prop_variants[p.variant];
+    AFQ_HIP(h, afq_raise_lds(v.kern, p.lds, v.lds_set));
+    afq_note_launch(h, v.name);
+    (void)hipLaunchKernel(v.kern, dim3(h->nw), dim3(PF_NT), args, p.lds, h->stream);      // (AFQ_POST reads the launch's error)
     AFQ_POST(h);
-    if (produces) h->handover.produced();
+    if (p.produces) st.handover.produced();
     return AFQ_OK;
 }

@@ -103,7 +103,7 @@
     }
     // The resident body (host-checked shape class: a.resident) takes the closed walker from here.  The two ring chunks
     // issued above have landed (the barrier of the check waits for them) in LDS the body does not use.
-    if constexpr (!NARROW && FULL == 7 && PF_NW == 8) {
+    if constexpr (!NARROW && FULL == 7) {
         if (closed && a.resident) {
             if (M <= 100) PF_RESIDENT(25);
             else PF_RESIDENT(26);
@@ -221,7 +221,6 @@
             if (!prepared) prepare();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         };
-#if PF_NW == 8
         if (FULL) {
             // the half-chunk pipeline of the Taylor products below (see there): refill, fragment reads and address
             // arithmetic between the MFMA groups of the sub-step in flight
@@ -279,17 +278,7 @@
                 half(a1, b1, a0, b0, sl + rt * 2048 + lane * 16, tf_l + ((c + 1) * 4 + slot0) * 2048 + lane * 16, 0, more, more);
             }
         } else
-#endif
         {
-#if PF_NW == 16
-        // four waves per SIMD: the other waves' MFMAs cover this wave's LDS reads, one register set is enough
-        d2_t avA[2], bvA[NSL][2];
-        for (int c = 0; c < NCH; ++c) {
-            load_frags(next_chunk(), c, avA, bvA);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            mfmas(avA, bvA);
-        }
-#else
         // fragments of chunk c+1 are read while the MFMAs of chunk c run (two register sets)
         d2_t avA[2], bvA[NSL][2], avB[2], bvB[NSL][2];
         load_frags(next_chunk(), 0, avA, bvA);
@@ -302,7 +291,6 @@
                 mfmas(avB, bvB);
             }
         }
-#endif
         }
         if (!to_global) __builtin_amdgcn_s_barrier();            // everyone finished reading these T columns
         int lk_e = lk, lr_e = lr;                                // laundered: keeps the store addresses from being
@@ -448,7 +436,6 @@
     };
     auto one_body_stage = [&](bool to_global) __attribute__((always_inline)) {
         using I2 = std::integral_constant<int, 2>;
-#if PF_NW == 8
         if constexpr (FULL == 7) {
             bool col_deal = a.rem4 && a.same_b;
             if (col_deal) {
@@ -462,20 +449,6 @@
                 return;
             }
         }
-#endif
-#if PF_NW == 16
-        // two waves per row tile: each takes half of the column slots
-        using I1 = std::integral_constant<int, 1>;
-        const int rt = wave >> 1, h2 = wave & 1;
-        if (a.same_b) {
-            if (a.b_real) one_body(I2{}, 2 * h2, to_global, std::true_type{}, rt);
-            else one_body(I2{}, 2 * h2, to_global, std::false_type{}, rt);
-        } else if (a.b_real) {
-            one_body(I1{}, h2, to_global, std::true_type{}, rt); one_body(I1{}, 2 + h2, to_global, std::true_type{}, rt);
-        } else {
-            one_body(I1{}, h2, to_global, std::false_type{}, rt); one_body(I1{}, 2 + h2, to_global, std::false_type{}, rt);
-        }
-#else
         if (NARROW && FULL) {                // column slots 0 and 2 only (see SS in one_body)
             using I1 = std::integral_constant<int, 1>;
             if (a.same_b) {
@@ -497,7 +470,6 @@
         } else {
             one_body(I2{}, 0, to_global, std::false_type{}, wave); one_body(I2{}, 2, to_global, std::false_type{}, wave);
         }
-#endif
     };
 
     // (s_setprio for either half of the waves only moves the barrier wait from one SIMD partner to the other:
@@ -594,7 +566,6 @@
                 if (!prepared) prepare();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             };
-#if PF_NW == 8
             if (FULL) {
                 // Every instruction that is not an MFMA sits BETWEEN two MFMA groups of the same wave (program order is
                 // pinned with sched_barrier), in the 64-cycle shadows of the MFMAs: the refill of the operand ring, the
@@ -669,16 +640,7 @@
                     half(a1, b1, q1, a0, b0, q0, sl + r0 * 2048 + lane * 16, tf_l + ((c + 1) * 4 + c0) * 2048 + lane * 16, sl + rem_a, 0, more, more);
                 }
             } else
-#endif
             {
-#if PF_NW == 16
-            d2_t avA[NI][2], bvA[NJ][2];
-            for (int c = 0; c < NCH; ++c) {
-                load_frags(next_chunk(), c, avA, bvA);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                mfmas(avA, bvA);
-            }
-#else
             d2_t avA[NI][2], bvA[NJ][2], avB[NI][2], bvB[NJ][2];
             if (STAG) {
                 // X = fragments of the chunk whose sub-step 1 is still owed, Y = the set being filled
@@ -719,14 +681,13 @@
                     }
                 }
             }
-#endif
             }
             // Everyone has to be through with T_{n-1} before it is overwritten -- but behind the last chunk barrier of the
             // half-chunk pipeline only the LAST chunk of T is still being read.  A wave whose tiles end below that chunk
             // (every wave of the full M <= 100 deal: the last chunk belongs to the remainder unit) stores first and takes the
             // barrier afterwards, just ahead of the remainder unit's store: the epilogue arithmetic of a wave then runs
             // while its SIMD partner still multiplies, instead of behind it.
-            const bool store_first = PF_NW == 8 && FULL != 0 && 2 * (r0 + NI) <= NCH - 1;
+            const bool store_first = FULL != 0 && 2 * (r0 + NI) <= NCH - 1;
             if (!store_first) __builtin_amdgcn_s_barrier();
             // T_n = product / n goes back to T as the next right-hand operand; after the last term T receives the SUM instead
             // (wave-uniform branch: two straight-line store sequences rather than a select per element)
@@ -948,16 +909,6 @@
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
-#if PF_NW == 16
-    {
-        // SIMD s (waves s, s + 4, s + 8, s + 12) owns column tile s: row tiles (0,1) (2,3) (4,5) (6); 7 tiles per SIMD
-        using I1 = std::integral_constant<int, 1>;
-        using I2 = std::integral_constant<int, 2>;
-        const int g = wave >> 2;
-        if (g & 1) taylor(I2{}, I1{}, std::true_type{}, 2 * g, wave & 3, g == 3 ? 1 : 2, std::false_type{});
-        else taylor(I2{}, I1{}, std::false_type{}, 2 * g, wave & 3, 2, std::false_type{});
-    }
-#else
     if (NARROW && FULL) {
         // six row tiles, one column tile per spin: waves 0-3 a pair of the row tiles 0-3, waves 4-7 one of the tiles 4, 5
         using I1 = std::integral_constant<int, 1>;
@@ -1037,7 +988,6 @@
     }
     else if (FULL >= 5) taylor(std::integral_constant<int, FULL >= 5 ? FULL - 4 : 1>{}, std::integral_constant<int, 1>{}, std::true_type{}, 4, wave - 4, FULL - 4, std::false_type{});
     else taylor(std::integral_constant<int, 3>{}, std::integral_constant<int, 1>{}, std::true_type{}, 4, wave - 4, 3, std::false_type{});
-#endif
     if (a.order == 0) lds_barrier();
 
     one_body_stage(true);
