@@ -829,6 +829,22 @@ int afq_rng_philox4x32(afq_handle *h, const uint32_t *ctr_key, uint32_t *out, in
  * launches that completed.  Environment: AFQ_DEBUG_SYNC=1, AFQ_DEBUG_MARKERS=1 set them at afq_create.     */
 int afq_debug(afq_handle *h, int sync_every_launch, int markers);
 int afq_last_launch(afq_handle *h, char *buf, int len, uint64_t *queued, uint64_t *retired);
+/* Guard bands and poison on the handle's device memory, a debugging mode selected by the environment at afq_create:
+ * AFQ_DEBUG_GUARD=1 puts a band of AFQ_DEBUG_GUARD_BYTES (a multiple of 4096; 4096 by default) in front of and behind every
+ * device block of the handle -- its owned blocks, its per-call buffers and the plane-wave tables -- filled with a 32-bit word
+ * that reads as NaN as a float and as a double; AFQ_DEBUG_GUARD=2 also fills the block itself before it is handed out, with
+ * a second NaN word where its elements are double, complex or float and with zeros elsewhere (an index is never poisoned).
+ * Both bands of a block are compared with the pattern, after a device synchronisation, before the block is freed.  The
+ * communicator's windows and exchange buffers (afq_comm_*) stay out of the mode: peers address them.  Unset or 0: nothing of
+ * this happens.
+ *   afq_debug_guard_check   the same comparison for every live block of the handle, without freeing (which call broke a band)
+ *   afq_debug_guard_report  the number of violations logged by this process so far; their text, one per line ("<block>:
+ *                           <front|back> band, first differing byte at offset <o> of a block of <n> bytes, word 0x...", o
+ *                           relative to the block: -1 is the byte in front of it, n the first behind it), goes to buf[n]
+ *   afq_debug_guard_reset   clears that log                                                                        */
+int afq_debug_guard_check(afq_handle *h);
+int afq_debug_guard_report(char *buf, int n);
+void afq_debug_guard_reset(void);
 /* counters: [0]=nfb_trig (continuous.py:150), [1]=nhe_trig (:210,213), [2]=overlap matrices the blocked
  * Gauss-Jordan flagged as poorly conditioned block-wise and handed to the step-by-step kernel (diagnostic),
  * [3]=walker steps the fused propagator took through its closed-shell deal (spin blocks bitwise equal)       */

@@ -125,6 +125,9 @@ SIGNATURES = {
     "afq_rng_philox4x32": [_h, c_void_p, c_void_p, c_int],
     "afq_debug": [_h, c_int, c_int],
     "afq_last_launch": [_h, c_void_p, c_int, POINTER(c_uint64), POINTER(c_uint64)],
+    "afq_debug_guard_check": [_h],
+    "afq_debug_guard_report": [c_char_p, c_int],       # (no handle: the log is the process's)
+    "afq_debug_guard_reset": [],                       # void
     "afq_comm_unique_id": [c_void_p],
     "afq_comm_available": [],
     "afq_comm_init": [_h, c_void_p, c_int, c_int],

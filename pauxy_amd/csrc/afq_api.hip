@@ -207,9 +207,12 @@ int afq_create(int device_id, afq_handle **out) {
     h->device = device_id;
     if (hipStreamCreate(&h->stream) != hipSuccess) { delete h; return AFQ_EHIP; }
     hipEventCreate(&h->ev0); hipEventCreate(&h->ev1);
-    if (dev_alloc(h, LT_HANDLE, &h->estimates, AFQ_EST_COUNT_) || dev_alloc(h, LT_HANDLE, &h->counters, AFQ_NCOUNTERS) ||
-        dev_alloc(h, LT_HANDLE, &h->closed_bad, 1) || dev_alloc(h, LT_HANDLE, &h->scal, AFQ_NSCAL) ||
-        dev_alloc(h, LT_HANDLE, (char **)&h->zero_page, 256)) { h->mem.release(LT_HANDLE); delete h; return AFQ_ENOMEM; }
+    // AFQ_DEBUG_GUARD=1 / 2 (dev_guard.h): guard bands round every device block of this handle, and typed poison in it; read
+    // before the first allocation, with the other diagnostics of the environment below
+    h->mem.guard = guard_cfg_from_env();
+    if (dev_alloc(h, LT_HANDLE, &h->estimates, AFQ_EST_COUNT_, "estimates") || dev_alloc(h, LT_HANDLE, &h->counters, AFQ_NCOUNTERS, "counters") ||
+        dev_alloc(h, LT_HANDLE, &h->closed_bad, 1, "closed_bad") || dev_alloc(h, LT_HANDLE, &h->scal, AFQ_NSCAL, "scal") ||
+        dev_alloc(h, LT_HANDLE, (char **)&h->zero_page, 256, "zero_page")) { h->mem.release(LT_HANDLE); delete h; return AFQ_ENOMEM; }
     hipMemset(h->estimates, 0, sizeof(cplx) * AFQ_EST_COUNT_);
     hipMemset(h->counters, 0, sizeof(unsigned long long) * AFQ_NCOUNTERS);
     hipMemset(h->closed_bad, 0, sizeof(unsigned long long));
@@ -246,6 +249,18 @@ int afq_destroy(afq_handle *h) {
     delete static_cast<afq_handle_full *>(h);
     return AFQ_OK;
 }
+
+// ---- AFQ_DEBUG_GUARD (dev_guard.h): the bands of every live block of the handle, and the process-wide log of violations
+int afq_debug_guard_check(afq_handle *h) {
+    if (!h) return AFQ_EINVAL;
+    hipSetDevice(h->device);
+    guard_check_owner(&h->mem);
+    return AFQ_OK;
+}
+
+int afq_debug_guard_report(char *buf, int n) { return guard_report(buf, n); }
+
+void afq_debug_guard_reset(void) { guard_reset(); }
 
 const char *afq_last_error(afq_handle *h) { return h ? h->err.c_str() : "null handle"; }
 
@@ -632,7 +647,8 @@ int afq_walkers_alloc(afq_handle *h, int nw) {
     free_walkers(h);
     const size_t per = (size_t)h->M * h->nt, K = h->K, n = nw;
     int rc = 0;
-    auto walk = [&](auto &slot, size_t cnt) { return rc = dev_alloc(h, LT_WALKERS, &slot, cnt); };
+    auto walk_as = [&](auto &slot, size_t cnt, const char *what) { return rc = dev_alloc(h, LT_WALKERS, &slot, cnt, what); };
+#define walk(slot, cnt) walk_as(slot, cnt, "walkers: " #slot)
     if (walk(h->phi, per * n) || walk(h->phi_t, per * n) || walk(h->phi_t2, per * n) ||
         walk(h->weight, n) || walk(h->unscaled, n) || walk(h->detR, n) || walk(h->log_detR, n) ||
         walk(h->ot, n) || walk(h->ehyb, n) || walk(h->phase, n) || walk(h->eloc, n) ||
@@ -666,7 +682,8 @@ int afq_walkers_alloc(afq_handle *h, int nw) {
         const size_t pv = h->kind == AFQ_SYS_HUBBARD ? (size_t)4 * h->M : (size_t)h->M * h->M;
         if (walk(h->vhs, pv * n)) return rc;
     }
-    if ((rc = dev_alloc(h, LT_WALKERS, (char **)&h->pack_tmp, std::max((size_t)nw * 2 * sizeof(int), (size_t)4096)))) return rc;
+#undef walk
+    if ((rc = dev_alloc(h, LT_WALKERS, (char **)&h->pack_tmp, std::max((size_t)nw * 2 * sizeof(int), (size_t)4096), "walkers: h->pack_tmp"))) return rc;
     h->nw = nw;
     select_det(h, h->cur_det, true);              // ghalf / vbias: the selected determinant's slices
     h->cap_frac = 0.0; h->cap_total = -1.0;       // a cap armed for an earlier population does not carry over

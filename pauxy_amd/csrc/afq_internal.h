@@ -11,6 +11,7 @@
 #include "dev_mem.h"
 
 typedef double2 cplx;   // (x = re, y = im), same bytes as numpy complex128
+template <> struct DevFloating<cplx> : std::true_type {};      // (dev_guard.h: a block of cplx is poisoned like one of double)
 
 __host__ __device__ inline cplx cmake(double r, double i) { return make_double2(r, i); }
 __host__ __device__ inline cplx cadd(cplx a, cplx b) { return cmake(a.x + b.x, a.y + b.y); }
@@ -466,18 +467,19 @@ inline int dev_nomem(afq_handle *h, const char *what, size_t bytes, hipError_t e
 }
 template <class T> static int dev_alloc(afq_handle *h, Lifetime lt, T **p, size_t n, const char *what = "device buffer",
                                         size_t *len = nullptr) {
-    const hipError_t e = h->mem.replace(lt, (void **)p, n * sizeof(T), len);
+    const hipError_t e = h->mem.replace(lt, (void **)p, n * sizeof(T), len, DevFloating<T>::value, what);
     return e == hipSuccess ? AFQ_OK : dev_nomem(h, what, n * sizeof(T), e);
 }
-template <class T> static int dev_upload(afq_handle *h, Lifetime lt, T **p, const void *src, size_t n) {
-    int rc = dev_alloc(h, lt, p, n);
+template <class T> static int dev_upload(afq_handle *h, Lifetime lt, T **p, const void *src, size_t n,
+                                         const char *what = "device buffer") {
+    int rc = dev_alloc(h, lt, p, n, what);
     if (rc) return rc;
     if (n) AFQ_HIP(h, hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
     return AFQ_OK;
 }
 // ensure: allocate if the slot is null (a block of this lifetime is never of another size)
-template <class T> static int dev_ensure(afq_handle *h, Lifetime lt, T **p, size_t n) {
-    return *p ? AFQ_OK : dev_alloc(h, lt, p, n);
+template <class T> static int dev_ensure(afq_handle *h, Lifetime lt, T **p, size_t n, const char *what = "device buffer") {
+    return *p ? AFQ_OK : dev_alloc(h, lt, p, n, what);
 }
 // grow: at least n elements; queued work may still read the block that is freed.  Failure leaves null and *len == 0.
 template <class T> static int dev_grow(afq_handle *h, Lifetime lt, T **p, size_t *len, size_t n, const char *what) {
@@ -490,7 +492,7 @@ template <class T> static int dev_grow(afq_handle *h, Lifetime lt, T **p, size_t
 
 // a per-call buffer (freed when its DevTemp leaves scope), filled from the host when src is given
 template <class T> static int dev_temp(afq_handle *h, DevTemp<T> &t, size_t n, const void *src = nullptr) {
-    const hipError_t e = t.alloc(n);
+    const hipError_t e = t.alloc(n, &h->mem);
     if (e != hipSuccess) return dev_nomem(h, "per-call buffer", n * sizeof(T), e);
     if (src) AFQ_HIP(h, hipMemcpy(t.p, src, n * sizeof(T), hipMemcpyHostToDevice));
     return AFQ_OK;

@@ -21,8 +21,13 @@
 //   Lent<>                       points a VIEW field (or phi / G / BH1 / xs / ot / detR, which no release runs under)
 //                                at foreign memory for a scope; it is never handed a slot that release would free
 // The communicator (afq_comm_state) and the plane-wave tables (ueg_fast) own their memory in their own structs.
+//
+// Every block here is allocated by guard_alloc and freed by guard_free (dev_guard.h): with AFQ_DEBUG_GUARD unset these are
+// hipMalloc and hipFree; set, the block sits between two bands that are checked when it is freed.  The plane-wave tables
+// allocate the same way.  The communicator's windows and exchange buffers (k_comm.hip) stay out of the guard mode: they are
+// exported to peers, which address them by their base.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "dev_guard.h"
 #include <vector>
 
 enum Lifetime { LT_HANDLE = 0, LT_SYSTEM, LT_TRIAL, LT_WALKERS, LT_COUNT };
@@ -31,24 +36,26 @@ struct DevMem {
     struct Slot { void **p; size_t *len; };
     std::vector<Slot> owned[LT_COUNT];
     long allocations = 0;       // blocks allocated so far (afq_thermal_device_allocations: a test that nothing allocates per call)
+    GuardCfg guard;             // AFQ_DEBUG_GUARD / AFQ_DEBUG_GUARD_BYTES as afq_create found them
 
-    // frees what the slot holds, allocates bytes (0: leaves it null) and enters the slot under lt; *len is zeroed
-    hipError_t replace(Lifetime lt, void **p, size_t bytes, size_t *len) {
+    // frees what the slot holds, allocates bytes (0: leaves it null) and enters the slot under lt; *len is zeroed.  floating:
+    // the element type is double, cplx or float (what the guard mode's poison goes by); what: the block's name in its log
+    hipError_t replace(Lifetime lt, void **p, size_t bytes, size_t *len, bool floating = false, const char *what = "device buffer") {
         std::vector<Slot> &v = owned[lt];
         size_t i = 0;
         while (i < v.size() && v[i].p != p) ++i;
         if (i == v.size()) v.push_back({p, len});
-        if (*p) { hipFree(*p); *p = nullptr; }
+        if (*p) { guard_free(*p); *p = nullptr; }
         if (len) *len = 0;
         if (!bytes) return hipSuccess;
-        const hipError_t e = hipMalloc(p, bytes);
+        const hipError_t e = guard_alloc(guard, p, bytes, floating, what, this);
         if (e != hipSuccess) *p = nullptr;
         else ++allocations;
         return e;
     }
     void release(Lifetime lt) {
         for (const Slot &s : owned[lt]) {
-            if (*s.p) { hipFree(*s.p); *s.p = nullptr; }
+            if (*s.p) { guard_free(*s.p); *s.p = nullptr; }
             if (s.len) *s.len = 0;
         }
         owned[lt].clear();
@@ -61,7 +68,10 @@ template <class T> struct DevTemp {
     DevTemp() = default;
     DevTemp(const DevTemp &) = delete;
     DevTemp &operator=(const DevTemp &) = delete;
-    ~DevTemp() { if (p) hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, n * sizeof(T)); }
+    ~DevTemp() { if (p) guard_free(p); }
+    // mem: the handle's memory, whose guard mode the buffer takes (none: a plain allocation)
+    hipError_t alloc(size_t n, const DevMem *mem = nullptr, const char *what = "per-call buffer") {
+        return guard_alloc(mem ? mem->guard : GuardCfg(), (void **)&p, n * sizeof(T), DevFloating<T>::value, what, mem);
+    }
     operator T *() const { return p; }
 };

@@ -180,10 +180,10 @@ static int energy_full_g(afq_handle *h, const LT *Lf, const cplx *G_dev, int ng,
     const size_t per_n = (size_t)ng2 * M * M * sizeof(cplx);
     int nc = (int)std::max<size_t>(1, std::min<size_t>((size_t)K, ((size_t)3 << 29) / per_n));
     DevTemp<cplx> sT, spart, sX, sexx;
-    AFQ_HIP(h, sT.alloc(per_n / sizeof(cplx) * nc));
-    AFQ_HIP(h, spart.alloc((size_t)ng2 * nc));
-    AFQ_HIP(h, sX.alloc((size_t)ng2 * K));
-    AFQ_HIP(h, sexx.alloc((size_t)ng2));
+    AFQ_HIP(h, sT.alloc(per_n / sizeof(cplx) * nc, &h->mem));
+    AFQ_HIP(h, spart.alloc((size_t)ng2 * nc, &h->mem));
+    AFQ_HIP(h, sX.alloc((size_t)ng2 * K, &h->mem));
+    AFQ_HIP(h, sexx.alloc((size_t)ng2, &h->mem));
     cplx *T = sT.p, *part = spart.p, *X = sX.p, *exx = sexx.p;
     AFQ_HIP(h, hipMemsetAsync(exx, 0, sizeof(cplx) * (size_t)ng2, h->stream));
     {

@@ -74,9 +74,9 @@ struct UegFast {
 UegFast *uf_of(afq_handle *h) { return (UegFast *)h->ueg_fast; }
 
 template <class T> int upload_vec(afq_handle *h, T **dst, const std::vector<T> &v) {
-    if (*dst) { hipFree(*dst); *dst = nullptr; }
+    if (*dst) { guard_free(*dst); *dst = nullptr; }
     const size_t n = v.empty() ? 1 : v.size();
-    AFQ_HIP(h, hipMalloc((void **)dst, sizeof(T) * n));
+    AFQ_HIP(h, guard_alloc(h->mem.guard, (void **)dst, sizeof(T) * n, DevFloating<T>::value, "plane-wave table", &h->mem));
     if (!v.empty()) AFQ_HIP(h, hipMemcpy(*dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
     return AFQ_OK;
 }
@@ -496,7 +496,7 @@ void k_ueg_fast_free(afq_handle *h) {
     if (!f) return;
     for (void *p : {(void *)f->elem_id, (void *)f->coef_q, (void *)f->coef_v, (void *)f->psic_rows, (void *)f->fb_off, (void *)f->fb_idx,
                     (void *)f->fb_val, (void *)f->vcoef, (void *)f->bdiag})
-        if (p) hipFree(p);
+        if (p) guard_free(p);
     delete f;
     h->ueg_fast = nullptr;
 }
@@ -649,9 +649,10 @@ int k_ueg_fast_supported(afq_handle *h) {
 static int ueg_field_args(afq_handle *h, UegFieldArgs &a, FieldRng &rng, size_t &lds, size_t &live_end) {
     UegFast *f = uf_of(h);
     if (f->vcoef_nw != h->nw || !f->vcoef) {
-        if (f->vcoef) hipFree(f->vcoef);
+        if (f->vcoef) guard_free(f->vcoef);
         f->vcoef = nullptr;
-        AFQ_HIP(h, hipMalloc(&f->vcoef, sizeof(cplx) * (size_t)h->nw * (f->ncoef + 1)));
+        AFQ_HIP(h, guard_alloc(h->mem.guard, (void **)&f->vcoef, sizeof(cplx) * (size_t)h->nw * (f->ncoef + 1), true,
+                               "plane-wave potential coefficients", &h->mem));
         f->vcoef_nw = h->nw;
     }
     rng = FieldRng();

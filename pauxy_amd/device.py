@@ -755,6 +755,17 @@ class AfqDevice(object):
         self.lib.afq_last_launch(self.h, buf, 1024, ctypes.byref(q), ctypes.byref(r))
         return buf.value.decode(errors='replace'), q.value, r.value
 
+    def guard_check(self):
+        """AFQ_DEBUG_GUARD: compare the bands of every live device block of the handle with their pattern; what differs goes
+        to the process-wide log (guard_report)."""
+        self._ck(self.lib.afq_debug_guard_check(self.h))
+
+    def guard_report(self):
+        """(number of band violations this process has logged, their text)."""
+        buf = ctypes.create_string_buffer(16384)
+        n = int(self.lib.afq_debug_guard_report(buf, 16384))
+        return n, buf.value.decode(errors='replace')
+
     def rng_seed(self, seed, stream=0):
         self._ck(self.lib.afq_rng_seed(self.h, int(seed), int(stream)))
 

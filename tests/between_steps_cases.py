@@ -858,6 +858,9 @@ EXEMPT = {
     'afq_comm_set_transport': 'needs peer processes', 'afq_comm_set_capacity': 'needs peer processes',
     'afq_comm_set_timeout': 'needs peer processes', 'afq_comm_probe': 'needs peer processes',
     'afq_comm_stats': 'pure getter of counters', 'afq_comm_parent_ix': 'needs peer processes',
+    'afq_debug_guard_check': 'reads the guard bands, touches no walker state',
+    'afq_debug_guard_report': 'reads the log of guard-band violations, touches no walker state',
+    'afq_debug_guard_reset': 'clears the log of guard-band violations, touches no walker state',
 }
 
 

@@ -533,6 +533,11 @@ def test_blocked_gauss_jordan_hands_badly_placed_pivots_to_the_step_by_step_kern
         return psi_s @ numpy.linalg.solve(psi_s.conj().T @ psi_s, T)
 
     for s, (o, n) in enumerate(((0, na), (na, nb))):
+        if n <= 32:
+            # (a spin of one or two tiles keeps its ordinary walkers: with 17 orbitals, a leading tile of 1e-10 leaves ONE
+            #  row and column of ordinary size -- condition number 9e10, not "well conditioned as a whole" -- and no fp64
+            #  inverse meets the tolerances below.  No shape of this test's own list has such a spin.)
+            continue
         psi_s = model.psi[:, o:o + n]
         noise = 1e-3 * (rng.rand(n, n) - 0.5 + 1j * (rng.rand(n, n) - 0.5))
         phi[1][:, o:o + n] = with_overlap(numpy.eye(n)[::-1] + 0j, psi_s)                 # (1) exact zeros in the tile
