@@ -669,6 +669,8 @@ int afq_estimates_get_end(afq_handle *h, double *est_out /* c128[10] */);
 #define AFQ_THERMAL_WIDE            32  /* honoured by the two continuous entry points (below), refused here by name */
 #define AFQ_THERMAL_DELAYED         128 /* honoured by afq_thermal_configure alone: the delayed-update route (below);
                                            AFQ_EINVAL on the two continuous entry points, by name */
+#define AFQ_THERMAL_FAR             256 /* honoured by the two continuous entry points (below), refused here by name
+                                           (64 stays an unknown bit on every entry point) */
 int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int nstblz, const double *BT,
                           const double *BT_inv, const double *BH1, const double *auxf, int options);
 /* With AFQ_THERMAL_DELAYED in options the handle takes the real walkers' second route, for any M >= 1: every Green's
@@ -702,15 +704,15 @@ int afq_thermal_state(afq_handle *h, int32_t *out4);
  * slice_ix = ts stack_size and its (E, T, V, nav) -- per_bin_out f64[nbins, nw, 4] in that order, each bit for bit the
  * loop's -- and cols_out their SUMS, added in ts order from zero (the caller multiplies by the weight and divides by
  * nbins, mixed.py:195-199).  The whole sweep is one launch per stage (Green's functions on a grid (2 nw, bins), P, energy,
- * sums) whatever nbins is, taken in chunks of whole bins when its scratch (G, P, and T of the streamed engine: per bin
- * 2 M M nw (sizeof G + 16) bytes, + 64 M M nw streamed) exceeds the budget: 2 GiB unless
+ * sums) whatever nbins is, taken in chunks of whole bins when its scratch (G, P, and the engine's own scratch for every
+ * work-group: per bin 2 M M nw (sizeof G + 16) bytes, + 64 M M nw streamed, + 32 nw (4 M M + M (M | 1)) far) exceeds the budget: 2 GiB unless
  * afq_thermal_set_sweep_budget says otherwise (0: the default; a chunk holds at least one bin; chunking changes no bit).
  * Afterwards the walkers' G (and det, complex kinds) are what afq_thermal_greens(h, (nbins - 1) stack_size) leaves.
  * ONE_RDM: one_rdm_out f64[2, M, M] = sum_w weight_w Re G_w of the G the call leaves, every walker in walker order.
  * TWO_RDM (UEG): two_rdm_out f64[2, 2, nq] = sum_w weight_w Re two_rdm[P_w] of the same G, from the pair sums of the
  * energy launch.  AFQ_ESTATE: no thermal configuration; AFQ_EINVAL: unknown bits in what, a needed output NULL;
  * AFQ_EUNSUPPORTED: TWO_RDM on a Hubbard handle; AVERAGE_GF on a handle configured with AFQ_THERMAL_WIDE or
- * AFQ_THERMAL_DELAYED. */
+ * AFQ_THERMAL_DELAYED (a handle configured with AFQ_THERMAL_FAR runs it). */
 #define AFQ_THERMAL_EST_AVERAGE_GF 1
 #define AFQ_THERMAL_EST_ONE_RDM    2
 #define AFQ_THERMAL_EST_TWO_RDM    4   /* UEG walkers only: AFQ_EUNSUPPORTED otherwise */
@@ -741,6 +743,17 @@ int afq_thermal_set_sweep_budget(afq_handle *h, size_t bytes);
  * bins are the same bits.  afq_thermal_reset / _greens / _energy / _state, the comb, afq_walkers_copy and the pack
  * serve a wide handle; afq_thermal_estimates runs ONE_RDM and TWO_RDM on it and refuses AVERAGE_GF by name
  * (AFQ_EUNSUPPORTED: the wide route has no sweep kernel yet).
+ * With AFQ_THERMAL_FAR the handle takes a fourth route (the bit beside AFQ_THERMAL_WIDE or AFQ_THERMAL_STREAMED_GREENS
+ * is AFQ_EINVAL): the wide route with no matrix in LDS.  The Green's function (thermal_cgreens_far_kernel) is the wide
+ * body with its one matrix as a fifth buffer of pitch M | 1 behind the four [M, M] of the work-group's scratch --
+ * nw * 2 * (4 M^2 + M (M | 1)) * 16 bytes of device memory of the handle's, allocated by the configure call -- and the
+ * vectors alone in LDS (18,944 bytes); the slice kernels (thermal_cslice_far_kernel, Hubbard:
+ * thermal_cslice_dense_far_kernel) read every operand where it lies in device memory.  The same arithmetic behind other
+ * loaders: G, det G, right, the bins, M0 and the weights are the bits of the wide route wherever both run.  The bound
+ * is the 128 columns of two per lane: M <= 128 = afq_thermal_far_max_basis(), which holds the shell of 123 plane waves
+ * and the 10 x 10, 11 x 11 and 8 x 16 Hubbard lattices; above it AFQ_EUNSUPPORTED with M and the numbers.  A far handle
+ * is served as a wide one is, and afq_thermal_estimates runs AVERAGE_GF on it as well: the sweep is the same kernel on a
+ * grid (2 nw, bins) (thermal_cgreens_far_sweep_kernel), every work-group in a scratch of its own.
  *   afq_thermal_configure_continuous  after afq_set_system_ueg (index lists over ALL plane waves, for the energy) and
  *                          afq_walkers_alloc; no trial determinant, no afq_set_propagator.  BT, BT_inv, BH1
  *                          f64[2, M, M]: the trial's dmat and its inverse (diagonal) and
@@ -751,7 +764,8 @@ int afq_thermal_set_sweep_budget(afq_handle *h, size_t bytes);
  *                          AFQ_THERMAL_* bits of what the caller was asked for, refused by name.  Ends with
  *                          afq_thermal_reset.  AFQ_EUNSUPPORTED: the option bits, a system that is not the UEG,
  *                          M > 47 (the message carries M and the bytes; M > 57 with
- *                          AFQ_THERMAL_STREAMED_GREENS, M > 95 with AFQ_THERMAL_WIDE), a trial that is not diagonal, more than
+ *                          AFQ_THERMAL_STREAMED_GREENS, M > 95 with AFQ_THERMAL_WIDE, M > 128 with
+ *                          AFQ_THERMAL_FAR), a trial that is not diagonal, more than
  *                          one rank, back-propagation / ITCF / mixed RDM on the handle.
  *   afq_thermal_propagate_continuous  one time slice of every walker, dead ones included: P = I - G^T,
  *                          xbar = -sqrt(dt) P.[iA | iB] (|xbar_i| > fb_bound: unit modulus), xs = xi - xbar, cmf = -sqrt(dt) xs.mf_shift,
@@ -775,6 +789,8 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
 int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi_out);
 /* the largest M a handle configured with AFQ_THERMAL_WIDE admits (no handle, no device) */
 int afq_thermal_wide_max_basis(void);
+/* the largest M a handle configured with AFQ_THERMAL_FAR admits (no handle, no device) */
+int afq_thermal_far_max_basis(void);
 
 /* ---- finite-temperature AFQMC with continuous fields: thermal walkers of the Hubbard model --------------------
  * thermal_propagation/continuous.py:84-120,202-257 (Continuous, phaseless, force bias, hybrid weight) with
@@ -786,8 +802,8 @@ int afq_thermal_wide_max_basis(void);
  *                          expm(-dt/2 (h1e_mod - i sqrt(U) diag(mf_shift) + sign mu)); mf_shift c128[M] =
  *                          i sqrt(U) diag(P_up + P_dn) of the trial; mf_const_fac c128[1] = exp(-dt mf_shift.mf_shift / 2).
  *                          left_k = BT^stack_size BT_inv^(k + 1) is built on the host in the reference's order.
- *                          options: AFQ_THERMAL_STREAMED_GREENS or AFQ_THERMAL_WIDE is honoured (both: AFQ_EINVAL; with
- *                          WIDE the bound is M <= 95, as above), the other AFQ_THERMAL_* bits are
+ *                          options: AFQ_THERMAL_STREAMED_GREENS, AFQ_THERMAL_WIDE or AFQ_THERMAL_FAR is honoured (two
+ *                          of them: AFQ_EINVAL; with WIDE the bound is M <= 95, with FAR M <= 128, as above), the other AFQ_THERMAL_* bits are
  *                          refused by name.  Without WIDE the bound on M is the smallest of the slice kernel's
  *                          40 M (M | 1) + 1024 bytes of LDS (M <= 63), the Green's kernel's (M <= 47 resident, 64
  *                          streamed) and the 64 lanes of a wave: M <= 47, and M <= 63 with the bit.  Above it

@@ -50,7 +50,8 @@ enum ThKind { TH_NONE = 0, TH_REAL, TH_CPLX_DIAG, TH_CPLX_DENSE };
 // Where a thermal handle's Green's function (and, WIDE, its slice kernel) keeps its matrices: the route chosen by the
 // option bits of the configure call.  RESIDENT: all in LDS.  STREAMED (AFQ_THERMAL_STREAMED_GREENS, complex walkers): T in
 // device memory.  WIDE (AFQ_THERMAL_WIDE, complex; AFQ_THERMAL_DELAYED, real): one matrix in LDS, two columns per lane.
-enum ThEngine { TH_ENGINE_RESIDENT = 0, TH_ENGINE_STREAMED, TH_ENGINE_WIDE };
+// FAR (AFQ_THERMAL_FAR, complex): the wide route with that matrix in device memory as well, M <= 128.
+enum ThEngine { TH_ENGINE_RESIDENT = 0, TH_ENGINE_STREAMED, TH_ENGINE_WIDE, TH_ENGINE_FAR };
 
 struct afq_handle {
     int device = 0;

@@ -498,9 +498,10 @@ int afq_thermal_estimates(afq_handle *h, int what, double *cols_out, double *per
                    cols, per_bin);
         AFQ_POST(h);
     } else {
-        // G [cb, nw, 2, M, M], P c128 of the same shape and, streamed, T [cb, 2 nw, 2, M, M]: cb whole bins under the budget
+        // G [cb, nw, 2, M, M], P c128 of the same shape and the engine's own scratch for every work-group of the grid,
+        // [cb, 2 nw, scratch(M)] (none for the resident engine): cb whole bins under the budget
         const size_t gsz = cx ? sizeof(cplx) : sizeof(double);
-        const size_t b_P = sizeof(cplx) * 2 * mm * n, b_G = gsz * 2 * mm * n, b_T = h->th_engine == TH_ENGINE_STREAMED ? sizeof(cplx) * 4 * mm * n : 0;
+        const size_t b_P = sizeof(cplx) * 2 * mm * n, b_G = gsz * 2 * mm * n, b_T = gsz * 2 * n * th_greens_scratch(h);
         const size_t budget = h->th_sw_budget ? h->th_sw_budget : TH_SWEEP_BUDGET;
         size_t cb = budget / (b_P + b_G + b_T);
         cb = cb < 1 ? 1 : cb > (size_t)nbins ? (size_t)nbins : cb;
@@ -515,7 +516,7 @@ int afq_thermal_estimates(afq_handle *h, int what, double *cols_out, double *per
                 AFQ_TRY(k_thermal_c_sweep_greens(h, (cplx *)Gs, Ts, ts0, nb));
                 AFQ_TRY(k_thermal_c_sweep_rdm(h, (const cplx *)Gs, P, nav + (size_t)ts0 * n, nb * nw));
             } else {
-                AFQ_TRY(th_launch_greens<double>(h, h->th_stack, h->th_G, nullptr, 0, -1, dim3(2 * nw, nb), (double *)Gs, nullptr, ts0));
+                AFQ_TRY(th_launch_greens<double>(h, h->th_stack, h->th_G, nullptr, 0, -1, dim3(2 * nw, nb), (double *)Gs, (double *)Ts, ts0));
                 AFQ_TRY(ts_launch_rdm_n<double>(h, (const double *)Gs, P, nav + (size_t)ts0 * n, nb * nw));
             }
             AFQ_TRY(th_energy_n(h, P, nb * nw, E + 3 * (size_t)ts0 * n, &two_src));

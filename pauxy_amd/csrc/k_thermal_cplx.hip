@@ -10,10 +10,15 @@
 // With AFQ_THERMAL_WIDE the handle takes a third route: thermal_wide.h's engine and the wide instantiations of the two
 // slice kernels below keep ONE complex matrix in LDS and the rest in th_scratch, and a lane owns two columns: M <= 95,
 // which holds the shells of 81 and 93 plane waves and the Hubbard lattices to 9 x 9.
+// With AFQ_THERMAL_FAR a fourth: the wide route with that one matrix in th_scratch as well -- thermal_wide.h's body with W
+// as a fifth scratch buffer, and the far instantiations of the slice kernels, which read every operand where it lies in
+// device memory -- so that the lanes alone bind: M <= 128, which holds the shell of 123 plane waves and the Hubbard
+// lattices 10 x 10, 11 x 11 and 8 x 16.  The same bits as the wide route wherever both run.
 // The route is the handle's th_engine: th_launch_greens<cplx> (thermal_wide.h) and the two slice launches read it, and
 // nothing else does.  The names below are the launch trace's; each slice kernel is one template over where its matrices
-// live (IN_LDS, or one matrix in LDS and the rest in th_scratch).
+// live (ThcPlace: all in LDS; one matrix in LDS and the rest in th_scratch; none in LDS).
 //
+//   thermal_cgreens_far_kernel, thermal_cslice_far_kernel, thermal_cslice_dense_far_kernel  the far route's three.
 //   thermal_cgreens_kernel  G and det G of every (walker, spin) from the stack: thermal_strat.h's engine with T = cplx.
 //   thermal_cgreens_streamed_kernel  the same with the streamed placement, for a handle configured with the bit.
 //   thermal_cgreens_wide_kernel  thermal_wide.h's engine, for a handle configured with AFQ_THERMAL_WIDE.
@@ -53,15 +58,22 @@ struct ThcSliceArgs {
 
 // One matrix in LDS (AFQ_THERMAL_WIDE): V alone; the Horner iterates live in the walker's scratch in device memory
 inline size_t thc_slice_wide_lds(int M) { return sizeof(cplx) * ts_mat(M); }
+// (no matrix in LDS, AFQ_THERMAL_FAR: thc_slice_far_lds of thermal_wide.h -- V is read where k_vhs_ueg left it)
 
-// One work-group per walker.  V, the A operand of all five Horner products, is in LDS.  IN_LDS: so are the Horner
-// iterates T_n, two matrices of pitch M | 1 used in turn, and BV = T_1 is read where it is.  Otherwise (the wide route)
-// the T_n live in two [M, M] buffers of the walker's scratch (scratch + w stride, pitch M; a work-group reads back only
-// what it wrote, across a barrier), and behind the Horner chain BV takes V's place in LDS as the A operand of
-// right <- B right.  Every element goes through the same operations in the same order -- the same ts_gemm with other
-// loaders -- so the two instantiations give the same bits where both run.
-template <bool IN_LDS> __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_kernel(ThcSliceArgs a, cplx *scratch, long stride) {
+// Where a slice kernel keeps its matrices: all in LDS; one in LDS and the rest in the walker's scratch in device memory
+// (the wide route); none in LDS (the far route)
+enum ThcPlace { THC_IN_LDS, THC_ONE_IN_LDS, THC_NONE_IN_LDS };
+
+// One work-group per walker.  V, the A operand of all five Horner products, is in LDS.  THC_IN_LDS: so are the Horner
+// iterates T_n, two matrices of pitch M | 1 used in turn, and BV = T_1 is read where it is.  THC_ONE_IN_LDS (the wide
+// route): the T_n live in two [M, M] buffers of the walker's scratch (scratch + w stride, pitch M; a work-group reads
+// back only what it wrote, across a barrier), and behind the Horner chain BV takes V's place in LDS as the A operand of
+// right <- B right.  THC_NONE_IN_LDS (the far route): the T_n in scratch as well, V read from a.vhs in device memory
+// and BV from the scratch buffer the Horner chain leaves it in.  Every element goes through the same operations in the
+// same order -- the same ts_gemm with other loaders -- so the instantiations give the same bits where they run.
+template <ThcPlace P> __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_kernel(ThcSliceArgs a, cplx *scratch, long stride) {
     extern __shared__ __align__(16) unsigned char smem[];
+    constexpr bool IN_LDS = P == THC_IN_LDS, FAR = P == THC_NONE_IN_LDS;
     const int M = a.M, LD = M | 1, tid = threadIdx.x, w = blockIdx.x;
     const size_t mat = ts_mat(M);
     const long mm = (long)M * M;
@@ -73,19 +85,19 @@ template <bool IN_LDS> __global__ __launch_bounds__(TH_THREADS) void thermal_csl
     for (int e = tid; e < M * M; e += TH_THREADS) {
         const int r = e / M, c = e % M;
         const cplx x = Vw[e];
-        V[r * LD + c] = x;
+        if (!FAR) V[r * LD + c] = x;
         T1(r, c) = cmake(x.x / 6.0 + (r == c ? 1.0 : 0.0), x.y / 6.0);
     }
     __syncthreads();
     for (int n = 5; n >= 1; --n) {
         const double dn = (double)n;
-        ts_gemm<cplx>(M, [&](int r, int k) { return V[r * LD + k]; }, [&](int k, int c) { return T1(k, c); },
+        ts_gemm<cplx>(M, [&](int r, int k) { return FAR ? Vw[r * M + k] : V[r * LD + k]; }, [&](int k, int c) { return T1(k, c); },
                  [&](int r, int c, cplx x) { T2(r, c) = cmake(x.x / dn + (r == c ? 1.0 : 0.0), x.y / dn); });
         __syncthreads();
         const TsMatView<cplx> t = T1; T1 = T2; T2 = t;
     }
     TsMatView<cplx> BV = T1;
-    if (!IN_LDS) {
+    if (P == THC_ONE_IN_LDS) {
         for (int e = tid; e < M * M; e += TH_THREADS) V[(e / M) * LD + e % M] = T1.p[e];
         __syncthreads();
         BV = {V, LD};
@@ -285,19 +297,21 @@ __device__ inline void thd_gemm_rc(int M, LA la, LB lb, ST st) {
 // LDS of the slice kernel with one staging matrix (AFQ_THERMAL_WIDE): the matrix and bv[128]
 inline size_t thd_slice_wide_lds(int M) { return sizeof(cplx) * (ts_mat(M) + TW_COLS); }
 
-// An operand of the next product where the product can read it.  IN_LDS: where it is.  Otherwise it is copied from the
-// walker's scratch into the one staging matrix Z in LDS, behind a barrier.  `also`, where given, gets a copy in device
-// memory on the way (pitch M).
-template <bool IN_LDS> __device__ inline TsMatView<cplx> thd_staged(TsMatView<cplx> src, cplx *Z, cplx *also, int M) {
-    if (IN_LDS && !also) return src;
+// (no matrix in LDS, AFQ_THERMAL_FAR: thd_slice_far_lds of thermal_wide.h -- bv[128] alone)
+// An operand of the next product where the product can read it.  THC_IN_LDS and THC_NONE_IN_LDS: where it is (LDS, or
+// the walker's scratch).  THC_ONE_IN_LDS: it is copied from the walker's scratch into the one staging matrix Z in LDS,
+// behind a barrier.  `also`, where given, gets a copy in device memory on the way (pitch M).
+template <ThcPlace P> __device__ inline TsMatView<cplx> thd_staged(TsMatView<cplx> src, cplx *Z, cplx *also, int M) {
+    constexpr bool STAGE = P == THC_ONE_IN_LDS;
+    if (!STAGE && !also) return src;
     const int LD = M | 1;
     for (int e = threadIdx.x; e < M * M; e += TH_THREADS) {
         const int r = e / M, c = e % M;
         const cplx x = src(r, c);
         if (also) also[e] = x;
-        if (!IN_LDS) Z[r * LD + c] = x;
+        if (STAGE) Z[r * LD + c] = x;
     }
-    if (IN_LDS) return src;
+    if (!STAGE) return src;
     __syncthreads();
     return {Z, LD};
 }
@@ -307,13 +321,16 @@ template <bool IN_LDS> __device__ inline TsMatView<cplx> thd_staged(TsMatView<cp
 // IN_LDS: B and the new right are two complex matrices in LDS, beside bv[64] and BH1_s (real).  Otherwise (the wide
 // route) one staging matrix in LDS holds in turn BH1_s, B_s (the A operand of right <- B right) and the new right (the B
 // operand of left_k right); B_s and the new right pass through two [M, M] buffers of the walker's scratch in device
-// memory (scratch + w stride, pitch M).  The products are the same with other loaders: the same bits where both run.
-template <bool IN_LDS> __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_dense_kernel(ThdSliceArgs a, cplx *scratch, long stride) {
+// memory (scratch + w stride, pitch M).  THC_NONE_IN_LDS (the far route): B_s and the new right in scratch as well, and
+// every operand read where it lies: BH1_s in a.bh1, B_s and the new right in scratch; LDS holds bv alone.  The products
+// are the same with other loaders: the same bits where they run.
+template <ThcPlace P> __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_dense_kernel(ThdSliceArgs a, cplx *scratch, long stride) {
     extern __shared__ __align__(16) unsigned char smem[];
+    constexpr bool IN_LDS = P == THC_IN_LDS, FAR = P == THC_NONE_IN_LDS;
     const int M = a.M, LD = M | 1, tid = threadIdx.x, w = blockIdx.x;
     const size_t mat = ts_mat(M);
     const long mm = (long)M * M;
-    cplx *Z = (cplx *)smem, *bv = Z + (IN_LDS ? 2 : 1) * mat;
+    cplx *Z = (cplx *)smem, *bv = Z + (IN_LDS ? 2 : FAR ? 0 : 1) * mat;
     double *H = IN_LDS ? (double *)(bv + 64) : (double *)Z;
     TsMatView<cplx> B = {Z, LD}, T2 = {Z + mat, LD};
     if (!IN_LDS) { B = {scratch + (long)w * stride, M}; T2 = {B.p + mm, M}; }
@@ -322,20 +339,20 @@ template <bool IN_LDS> __global__ __launch_bounds__(TH_THREADS) void thermal_csl
         const double *Hs = a.bh1 + s * mm, *lf = a.left + s * mm;
         cplx *R = a.right + ((long)w * 2 + s) * mm;
         cplx *S = a.stack + (((long)w * a.nbins + a.block) * 2 + s) * mm;
-        for (int e = tid; e < M * M; e += TH_THREADS) H[(e / M) * LD + e % M] = Hs[e];
+        if (!FAR) for (int e = tid; e < M * M; e += TH_THREADS) H[(e / M) * LD + e % M] = Hs[e];
         __syncthreads();
-        thd_gemm_rc(M, [&](int r, int k) { return H[r * LD + k]; }, [&](int k, int c) { return cscale(bv[k], H[k * LD + c]); },
-                    [&](int r, int c, cplx x) { B(r, c) = x; });
+        const auto bh = [&](int r, int k) { return FAR ? Hs[r * M + k] : H[r * LD + k]; };
+        thd_gemm_rc(M, bh, [&](int k, int c) { return cscale(bv[k], bh(k, c)); }, [&](int r, int c, cplx x) { B(r, c) = x; });
         __syncthreads();
         TsMatView<cplx> Rn = B;
         if (a.counter != 0) {
-            const TsMatView<cplx> Bs = thd_staged<IN_LDS>(B, Z, nullptr, M);
+            const TsMatView<cplx> Bs = thd_staged<P>(B, Z, nullptr, M);
             ts_gemm<cplx>(M, [&](int r, int k) { return Bs(r, k); }, [&](int k, int c) { return R[k * M + c]; },
                           [&](int r, int c, cplx x) { T2(r, c) = x; });
             __syncthreads();
             Rn = T2;
         }
-        const TsMatView<cplx> Rs = thd_staged<IN_LDS>(Rn, Z, R, M);
+        const TsMatView<cplx> Rs = thd_staged<P>(Rn, Z, R, M);
         thd_gemm_rc(M, [&](int r, int k) { return lf[r * M + k]; }, [&](int k, int c) { return Rs(k, c); },
                     [&](int r, int c, cplx x) { S[r * M + c] = x; });
         __syncthreads();
@@ -442,23 +459,37 @@ namespace {
 
 const char *const THC_RESIDENT_HINT = "; AFQ_THERMAL_STREAMED_GREENS (streamed_greens) keeps T in device memory and reaches further";
 
-// STREAMED_GREENS and WIDE name two placements of the same working set: together they mean nothing
+// STREAMED_GREENS, WIDE and FAR name three placements of the same working set: any two together mean nothing
 int thc_engine_of(afq_handle *h, const std::string &me, int options, ThEngine *engine) {
-    const bool streamed = (options & AFQ_THERMAL_STREAMED_GREENS) != 0, wide = (options & AFQ_THERMAL_WIDE) != 0;
+    const bool streamed = (options & AFQ_THERMAL_STREAMED_GREENS) != 0, wide = (options & AFQ_THERMAL_WIDE) != 0,
+               far = (options & AFQ_THERMAL_FAR) != 0;
     if (streamed && wide)
         AFQ_FAIL(h, AFQ_EINVAL, me + "wide_basis and streamed_greens are two placements of the same matrices: ask for one");
-    *engine = wide ? TH_ENGINE_WIDE : streamed ? TH_ENGINE_STREAMED : TH_ENGINE_RESIDENT;
+    if (far && wide)
+        AFQ_FAIL(h, AFQ_EINVAL, me + "far_basis and wide_basis are two placements of the same matrices: ask for one");
+    if (far && streamed)
+        AFQ_FAIL(h, AFQ_EINVAL, me + "far_basis and streamed_greens are two placements of the same matrices: ask for one");
+    *engine = far ? TH_ENGINE_FAR : wide ? TH_ENGINE_WIDE : streamed ? TH_ENGINE_STREAMED : TH_ENGINE_RESIDENT;
     return AFQ_OK;
 }
 
 const ThLds THC_WIDE_GREENS = {"the wide Green's function (thermal_cgreens_wide_kernel)", ts_greens_wide_lds<cplx>, ""};
 
+// two columns per lane: the wide route and the far route
+inline bool thc_two_columns(ThEngine engine) { return engine == TH_ENGINE_WIDE || engine == TH_ENGINE_FAR; }
+// scalars of th_scratch per work-group of the handle's Green's kernel; a walker's share is both spins'
+inline size_t thc_greens_scratch(ThEngine engine, int M) {
+    return engine == TH_ENGINE_FAR ? ts_greens_far_scratch(M) : engine == TH_ENGINE_WIDE ? ts_greens_wide_scratch(M)
+         : engine == TH_ENGINE_STREAMED ? TsStreamed<cplx>::scratch(M) : (size_t)0;
+}
+
 // th_screen_bound in the words of the continuous fields: the kernels first, then lane = column (wide: two columns per
 // lane).  who: "" or ", Hubbard"; unit: what M counts.
 int thc_screen_bound(afq_handle *h, const char *who, const char *unit, ThEngine engine, std::initializer_list<ThLds> need) {
     return th_screen_bound(h, std::string("thermal walkers with continuous fields") + who +
-                           (engine == TH_ENGINE_STREAMED ? " (streamed_greens)" : engine == TH_ENGINE_WIDE ? " (wide_basis)" : ""),
-                           unit, engine == TH_ENGINE_WIDE ? TW_COLS : THC_LANES, false, need);
+                           (engine == TH_ENGINE_STREAMED ? " (streamed_greens)" : engine == TH_ENGINE_WIDE ? " (wide_basis)"
+                            : engine == TH_ENGINE_FAR ? " (far_basis)" : ""),
+                           unit, thc_two_columns(engine) ? TW_COLS : THC_LANES, false, need);
 }
 
 // Behind an entry point's own checks: its host-built tables (`per` numbers per slice: 2 M diagonals or 2 M M), the
@@ -477,8 +508,9 @@ int thc_configure_common(afq_handle *h, ThKind kind, int ntime_slices, int stack
         (rc = dev_alloc(h, LT_WALKERS, &h->thc_M0, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_M00, (size_t)2)) ||
         (rc = dev_alloc(h, LT_WALKERS, &h->thc_det, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_nav, n))) return rc;
     // T of the streamed Green's kernel, two buffers per (walker, spin); the wide route's scratch, four per (walker,
-    // spin), of which the wide slice kernels use the walker's first two; a handle configured without either holds none
-    const size_t scratch = engine == TH_ENGINE_STREAMED ? 4 * mm * n : engine == TH_ENGINE_WIDE ? 2 * ts_greens_wide_scratch(h->M) * n : (size_t)0;
+    // spin), of which the wide slice kernels use the walker's first two; the far route's, W behind the four; a handle
+    // configured without any of them holds none
+    const size_t scratch = 2 * thc_greens_scratch(engine, h->M) * n;
     if ((rc = dev_alloc(h, LT_WALKERS, (cplx **)&h->th_scratch, scratch))) return rc;
     h->th_engine = engine;
     if ((rc = ensure_G(h))) return rc;                  // c128 [nw, 2, M, M]: the one-body density matrices
@@ -505,10 +537,12 @@ int thc_slice_diag(afq_handle *h) {
     a.left = h->thc_left + (size_t)h->th_counter * 2 * M;
     a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
     cplx *const scratch = (cplx *)h->th_scratch;
-    const long stride = (long)(2 * ts_greens_wide_scratch(M));       // a walker's: both spins' of the Green's kernel
+    const long stride = (long)(2 * thc_greens_scratch(h->th_engine, M));     // a walker's: both spins' of the Green's kernel
+    if (h->th_engine == TH_ENGINE_FAR)
+        return th_launch<thermal_cslice_kernel<THC_NONE_IN_LDS>>(h, "thermal_cslice_far_kernel", dim3(h->nw), thc_slice_far_lds(M), a, scratch, stride);
     if (h->th_engine == TH_ENGINE_WIDE)
-        return th_launch<thermal_cslice_kernel<false>>(h, "thermal_cslice_wide_kernel", dim3(h->nw), thc_slice_wide_lds(M), a, scratch, stride);
-    return th_launch<thermal_cslice_kernel<true>>(h, "thermal_cslice_kernel", dim3(h->nw), thc_slice_lds(M), a, scratch, stride);
+        return th_launch<thermal_cslice_kernel<THC_ONE_IN_LDS>>(h, "thermal_cslice_wide_kernel", dim3(h->nw), thc_slice_wide_lds(M), a, scratch, stride);
+    return th_launch<thermal_cslice_kernel<THC_IN_LDS>>(h, "thermal_cslice_kernel", dim3(h->nw), thc_slice_lds(M), a, scratch, stride);
 }
 
 // Hubbard: the force bias, the clip at 1, xs, cmf, cfb and the diagonal of BV from P's diagonal, and the slice kernel
@@ -523,11 +557,14 @@ int thc_slice_dense(afq_handle *h) {
     a.left = h->thc_left + (size_t)h->th_counter * 2 * M * M;
     a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
     cplx *const scratch = (cplx *)h->th_scratch;
-    const long stride = (long)(2 * ts_greens_wide_scratch(M));       // a walker's: both spins' of the Green's kernel
+    const long stride = (long)(2 * thc_greens_scratch(h->th_engine, M));     // a walker's: both spins' of the Green's kernel
+    if (h->th_engine == TH_ENGINE_FAR)
+        return th_launch<thermal_cslice_dense_kernel<THC_NONE_IN_LDS>>(h, "thermal_cslice_dense_far_kernel", dim3(h->nw), thd_slice_far_lds(M), a,
+                                                                       scratch, stride);
     if (h->th_engine == TH_ENGINE_WIDE)
-        return th_launch<thermal_cslice_dense_kernel<false>>(h, "thermal_cslice_dense_wide_kernel", dim3(h->nw), thd_slice_wide_lds(M), a,
-                                                             scratch, stride);
-    return th_launch<thermal_cslice_dense_kernel<true>>(h, "thermal_cslice_dense_kernel", dim3(h->nw), thd_slice_lds(M), a, scratch, stride);
+        return th_launch<thermal_cslice_dense_kernel<THC_ONE_IN_LDS>>(h, "thermal_cslice_dense_wide_kernel", dim3(h->nw), thd_slice_wide_lds(M), a,
+                                                                      scratch, stride);
+    return th_launch<thermal_cslice_dense_kernel<THC_IN_LDS>>(h, "thermal_cslice_dense_kernel", dim3(h->nw), thd_slice_lds(M), a, scratch, stride);
 }
 
 // the phaseless weight from the determinant ratio; the dense kind's carries the constant of the mean-field shift
@@ -552,7 +589,7 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
     AFQ_API(h, "afq_thermal_configure_continuous");
     if (!h) return AFQ_EINVAL;
     h->th_kind = TH_NONE;
-    const ThEntry me = {"afq_thermal_configure_continuous: ", AFQ_THERMAL_STREAMED_GREENS | AFQ_THERMAL_WIDE, AFQ_EINVAL,
+    const ThEntry me = {"afq_thermal_configure_continuous: ", AFQ_THERMAL_STREAMED_GREENS | AFQ_THERMAL_WIDE | AFQ_THERMAL_FAR, AFQ_EINVAL,
                         "afq_thermal_configure_continuous: charge_decomposition belongs to the discrete fields", AFQ_SYS_UEG,
                         "thermal walkers with continuous fields: UEG systems only (no Generic, no continuous Hubbard)", "both"};
     if (!BT || !BT_inv || !BH1 || !mf_shift) AFQ_FAIL(h, AFQ_EINVAL, me.me + "null operand");
@@ -560,7 +597,9 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
     ThEngine route;
     AFQ_TRY(thc_engine_of(h, me.me, options, &route));
     const ThLds slice = {"the slice kernel (thermal_cslice_kernel)", thc_slice_lds, ""};
-    if (route == TH_ENGINE_WIDE)
+    if (route == TH_ENGINE_FAR)
+        AFQ_TRY(thc_screen_bound(h, "", "plane waves", route, {THC_FAR_GREENS, THC_FAR_SLICE}));
+    else if (route == TH_ENGINE_WIDE)
         AFQ_TRY(thc_screen_bound(h, "", "plane waves", route, {THC_WIDE_GREENS,
                 {"the wide slice kernel (thermal_cslice_wide_kernel)", thc_slice_wide_lds, ""}}));
     else if (route == TH_ENGINE_STREAMED)
@@ -601,6 +640,8 @@ int afq_thermal_wide_max_basis(void) {
     return m;
 }
 
+int afq_thermal_far_max_basis(void) { return th_far_bound(); }
+
 int afq_thermal_left_table(int M, int stack_size, const double *BT, const double *BT_inv, double *BTpow_out, double *left_out) {
     if (M < 1 || stack_size < 1 || !BT || !BT_inv || !BTpow_out || !left_out) return AFQ_EINVAL;
     thd_left_table(M, stack_size, BT, BT_inv, BTpow_out, left_out);
@@ -613,7 +654,7 @@ int afq_thermal_configure_hubbard_continuous(afq_handle *h, int ntime_slices, in
     AFQ_API(h, "afq_thermal_configure_hubbard_continuous");
     if (!h) return AFQ_EINVAL;
     h->th_kind = TH_NONE;
-    const ThEntry me = {"afq_thermal_configure_hubbard_continuous: ", AFQ_THERMAL_STREAMED_GREENS | AFQ_THERMAL_WIDE, AFQ_EINVAL,
+    const ThEntry me = {"afq_thermal_configure_hubbard_continuous: ", AFQ_THERMAL_STREAMED_GREENS | AFQ_THERMAL_WIDE | AFQ_THERMAL_FAR, AFQ_EINVAL,
                         "afq_thermal_configure_hubbard_continuous: charge_decomposition belongs to the discrete fields (the "
                         "continuous form is the charge form alone)", AFQ_SYS_HUBBARD,
                         "thermal walkers with continuous fields and a dense trial: Hubbard systems only (no Generic)", "both"};
@@ -622,9 +663,9 @@ int afq_thermal_configure_hubbard_continuous(afq_handle *h, int ntime_slices, in
     ThEngine route;
     AFQ_TRY(thc_engine_of(h, me.me, options, &route));
     const bool streamed = route == TH_ENGINE_STREAMED;
-    const ThLds greens = route == TH_ENGINE_WIDE ? THC_WIDE_GREENS : streamed ? ThLds{"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}
+    const ThLds greens = route == TH_ENGINE_FAR ? THC_FAR_GREENS : route == TH_ENGINE_WIDE ? THC_WIDE_GREENS : streamed ? ThLds{"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}
                                    : ThLds{"the complex Green's function (thermal_cgreens_kernel)", ts_greens_lds<cplx>, THC_RESIDENT_HINT};
-    const ThLds slice = route == TH_ENGINE_WIDE ? ThLds{"the wide slice kernel (thermal_cslice_dense_wide_kernel)", thd_slice_wide_lds, ""}
+    const ThLds slice = route == TH_ENGINE_FAR ? THD_FAR_SLICE : route == TH_ENGINE_WIDE ? ThLds{"the wide slice kernel (thermal_cslice_dense_wide_kernel)", thd_slice_wide_lds, ""}
                                                 : ThLds{"the slice kernel (thermal_cslice_dense_kernel)", thd_slice_lds, ""};
     AFQ_TRY(thc_screen_bound(h, ", Hubbard", "sites", route, {greens, slice}));
     AFQ_TRY(th_screen_state(h, me, ntime_slices, stack_size, 1));

@@ -29,7 +29,11 @@
 //                   There is no TsStreamed<double>: the real walkers fit to M = 64 as they are.
 //   TsWide<T>       (thermal_wide.h) another body, ts_greens_wide_body: one matrix in LDS and two columns per lane;
 //                   the same G to rounding.  AFQ_THERMAL_WIDE: a complex walker to M = 95; AFQ_THERMAL_DELAYED: a real
-//                   walker to M = 128.  thermal_cgreens_wide_kernel / thermal_greens_wide_kernel; no sweep.
+//                   walker to M = 128.  thermal_cgreens_wide_kernel / thermal_greens_wide_kernel, .._sweep_kernel
+//                   (afq_thermal_estimates still refuses AVERAGE_GF on the handles of these two bits: only TsFar's runs).
+//   TsFar<T>        (thermal_wide.h) ts_greens_wide_body with its one matrix in the work-group's scratch as well: no
+//                   matrix in LDS, the bits of TsWide.  AFQ_THERMAL_FAR: a complex walker to M = 128.
+//                   thermal_cgreens_far_kernel, thermal_cgreens_far_sweep_kernel.
 // th_launch is the one way a thermal kernel with dynamic LDS is launched; ts_launch_greens<T, E> the one launcher of the
 // Green's kernels; th_launch_greens<T> (thermal_wide.h) picks E by the handle's th_engine.
 //
@@ -514,6 +518,8 @@ inline int th_screen_options(afq_handle *h, const ThEntry &e, int options) {
         AFQ_FAIL(h, AFQ_EINVAL, e.me + "streamed_greens belongs to the continuous fields (the real walkers fit to M = 64 as they are)");
     if (options & AFQ_THERMAL_WIDE & ~e.allowed)
         AFQ_FAIL(h, AFQ_EINVAL, e.me + "wide_basis belongs to the continuous fields (the real walkers work one lane per column, M <= 64)");
+    if (options & AFQ_THERMAL_FAR & ~e.allowed)
+        AFQ_FAIL(h, AFQ_EINVAL, e.me + "far_basis belongs to the continuous fields (the real walkers reach M = 128 with delayed_updates)");
     if (options & AFQ_THERMAL_DELAYED & ~e.allowed) AFQ_FAIL(h, AFQ_EINVAL, e.me + "delayed_updates belongs to the discrete fields");
     if (options & ~e.allowed) AFQ_FAIL(h, AFQ_EINVAL, e.me + "unknown option bits");
     if (!h->kind || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, e.me + "set the system and allocate the walkers first");

@@ -30,6 +30,12 @@
 // The engine enters thermal_strat.h's one kernel and one launcher as TsWide<T>.  Behind it, what needs every engine in
 // sight: th_launch_greens<T>, which picks the engine by the handle's th_engine, and th_screen_bound, the one refusal of
 // an M that a route's kernels or lanes do not hold.
+//
+// TsFar<T> (AFQ_THERMAL_FAR, the complex walkers) is the same body with the one matrix out of LDS as well: W is a fifth
+// buffer of the work-group's scratch, M x (M | 1) behind the four [M, M], and LDS holds the vectors alone (18,944 B for
+// cplx).  Where W lives is the body's one template parameter; every helper takes W as a pointer and every element goes
+// through the same operations in the same order, so the two placements give the same bits where both run.  The lanes
+// bind: M <= 128, which holds the shell of 123 plane waves and the lattices 10 x 10, 11 x 11 and 8 x 16.
 #pragma once
 #include "thermal_strat.h"
 #include <initializer_list>
@@ -43,6 +49,10 @@ namespace {
 template <class T> inline size_t ts_greens_wide_lds(int M) { return sizeof(T) * (ts_mat(M) + 128 + 128 + 512 + 384) + sizeof(int) * TW_COLS; }
 // scalars of device scratch per work-group
 __host__ __device__ inline size_t ts_greens_wide_scratch(int M) { return 4 * (size_t)M * M; }
+// LDS of the far Green's kernel: the same vectors and no matrix
+template <class T> inline size_t ts_greens_far_lds(int) { return sizeof(T) * (128 + 128 + 512 + 384) + sizeof(int) * TW_COLS; }
+// its scratch: the four [M, M] buffers and W [M, M | 1] behind them
+__host__ __device__ inline size_t ts_greens_far_scratch(int M) { return 4 * (size_t)M * M + ts_mat(M); }
 
 template <class T> __device__ inline T tw_sum4(const T *p) {
     typedef TsScalar<T> S;
@@ -260,19 +270,20 @@ template <class T> __device__ void tw_substitute(T *R, int M, int LD, const T *L
 }
 
 // The work of one work-group, as ts_greens_body (another algorithm: its own body); scr: the work-group's own
-// ts_greens_wide_scratch(M) scalars.
-template <class T>
+// ts_greens_wide_scratch(M) scalars, or with FAR ts_greens_far_scratch(M): W then lies behind the four buffers in
+// device memory and the vectors start at smem.
+template <class T, bool FAR>
 __device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first,
                                                     T *Gd, T *Gd2, T *detd) {
     typedef TsScalar<T> S;
     const int LD = M | 1, tid = threadIdx.x;
     const size_t mat = ts_mat(M);
-    T *W = (T *)smem;
-    T *D = W + mat, *v = D + 128, *part = v + 128, *aux = part + 512;
+    const long mm = (long)M * M;
+    T *W = FAR ? scr + 4 * mm : (T *)smem;
+    T *D = FAR ? (T *)smem : W + mat, *v = D + 128, *part = v + 128, *aux = part + 512;
     int *perm = (int *)(aux + 384);
     double *tau = (double *)aux;                                     // 128 doubles: aux[0 .. 63] of cplx, [0 .. 127] of double
     T *v1 = aux + 128 * sizeof(double) / sizeof(T);                  // the second reflector buffer: the 128 scalars behind tau
-    const long mm = (long)M * M;
     T *Tin = scr, *Tout = scr + mm, *Pn = scr + 2 * mm, *Xs = scr + 3 * mm;
 
     {
@@ -333,14 +344,31 @@ __device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const T
 }
 
 // The wide engine of thermal_greens_kernel (thermal_strat.h): scratch [work-groups, 4, M, M].  Its own names in the
-// trace; no sweep.
+// trace.  The sweep is the one kernel's: every work-group of the grid (2 nw, bins) works in a scratch of its own.
 template <class T> struct TsWide {
-    static constexpr bool has_sweep = false;
+    static constexpr bool has_sweep = true;
     static size_t lds(int M) { return ts_greens_wide_lds<T>(M); }
     __host__ __device__ static size_t scratch(int M) { return ts_greens_wide_scratch(M); }
-    static const char *name(bool) { return std::is_same<T, cplx>::value ? "thermal_cgreens_wide_kernel" : "thermal_greens_wide_kernel"; }
+    static const char *name(bool sweep) {
+        return std::is_same<T, cplx>::value ? (sweep ? "thermal_cgreens_wide_sweep_kernel" : "thermal_cgreens_wide_kernel")
+                                            : (sweep ? "thermal_greens_wide_sweep_kernel" : "thermal_greens_wide_kernel");
+    }
     __device__ __forceinline__ static void body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first, T *Gd, T *Gd2, T *detd) {
-        ts_greens_wide_body<T>(smem, Bw, scr, M, nbins, first, Gd, Gd2, detd);
+        ts_greens_wide_body<T, false>(smem, Bw, scr, M, nbins, first, Gd, Gd2, detd);
+    }
+};
+
+// The far engine: the wide body with W in the work-group's scratch as well, [work-groups, 4 M M + M (M | 1)].
+template <class T> struct TsFar {
+    static constexpr bool has_sweep = true;
+    static size_t lds(int M) { return ts_greens_far_lds<T>(M); }
+    __host__ __device__ static size_t scratch(int M) { return ts_greens_far_scratch(M); }
+    static const char *name(bool sweep) {
+        return std::is_same<T, cplx>::value ? (sweep ? "thermal_cgreens_far_sweep_kernel" : "thermal_cgreens_far_kernel")
+                                            : (sweep ? "thermal_greens_far_sweep_kernel" : "thermal_greens_far_kernel");
+    }
+    __device__ __forceinline__ static void body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first, T *Gd, T *Gd2, T *detd) {
+        ts_greens_wide_body<T, true>(smem, Bw, scr, M, nbins, first, Gd, Gd2, detd);
     }
 };
 
@@ -352,10 +380,18 @@ template <class T> int th_launch_greens(afq_handle *h, const T *stack, T *G, T *
     const bool sweep = Gs != nullptr;
     const TsGreensArgs<T> a = {stack, G, det, sweep ? Ts : (T *)h->th_scratch, h->M, h->th_nbins, first, src_w, Gs, h->th_ss, ts0};
     if (h->th_engine == TH_ENGINE_WIDE) return ts_launch_greens<T, TsWide>(h, a, grid, sweep);
-    if constexpr (std::is_same<T, cplx>::value) {                    // (the real walkers have no streamed engine)
+    if constexpr (std::is_same<T, cplx>::value) {                    // (the real walkers have no streamed and no far engine)
+        if (h->th_engine == TH_ENGINE_FAR) return ts_launch_greens<T, TsFar>(h, a, grid, sweep);
         if (h->th_engine == TH_ENGINE_STREAMED) return ts_launch_greens<T, TsStreamed>(h, a, grid, sweep);
     }
     return ts_launch_greens<T, TsResident>(h, a, grid, sweep);
+}
+
+// scalars of scratch per work-group of the handle's Green's kernel, whatever the walker kind: what the sweep of
+// afq_thermal_estimates sizes its chunks from
+inline size_t th_greens_scratch(const afq_handle *h) {
+    return h->th_engine == TH_ENGINE_FAR ? TsFar<cplx>::scratch(h->M) : h->th_engine == TH_ENGINE_WIDE ? TsWide<cplx>::scratch(h->M)
+         : h->th_engine == TH_ENGINE_STREAMED ? TsStreamed<cplx>::scratch(h->M) : (size_t)0;
 }
 
 // ---- the bound on M of a configure entry point
@@ -391,6 +427,22 @@ inline int th_screen_bound(afq_handle *h, const std::string &who, const char *un
             AFQ_FAIL(h, AFQ_EUNSUPPORTED, head + "need " + std::to_string(k.bytes(M)) + " bytes of LDS for " + k.what +
                      ", a work-group has " + std::to_string(TH_LDS_MAX) + tail + k.hint);
     AFQ_FAIL(h, AFQ_EUNSUPPORTED, columns);
+}
+
+// ---- the far route's kernels as th_screen_bound asks for them, and the bound they leave.  The two slice kernels are
+// k_thermal_cplx.hip's; their LDS is stated here, beside the Green's kernel's, so that one place holds what the route
+// keeps in LDS: no matrix.
+inline size_t thc_slice_far_lds(int) { return 0; }                            // thermal_cslice_far_kernel: nothing
+inline size_t thd_slice_far_lds(int) { return 2 * sizeof(double) * TW_COLS; } // thermal_cslice_dense_far_kernel: bv[128] of cplx
+const ThLds THC_FAR_GREENS = {"the far Green's function (thermal_cgreens_far_kernel)", ts_greens_far_lds<cplx>, ""};
+const ThLds THC_FAR_SLICE = {"the far slice kernel (thermal_cslice_far_kernel)", thc_slice_far_lds, ""};
+const ThLds THD_FAR_SLICE = {"the far slice kernel (thermal_cslice_dense_far_kernel)", thd_slice_far_lds, ""};
+
+// the largest M the far route admits: what th_screen_bound lets through with these kernels and TW_COLS columns
+inline int th_far_bound() {
+    int m = TW_COLS;
+    while (m > 1 && (ts_greens_far_lds<cplx>(m) > TH_LDS_MAX || thc_slice_far_lds(m) > TH_LDS_MAX || thd_slice_far_lds(m) > TH_LDS_MAX)) --m;
+    return m;
 }
 
 }  // namespace

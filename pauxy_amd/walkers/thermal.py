@@ -25,6 +25,15 @@ def _wide_max_basis():
         return 95
 
 
+def _far_max_basis():
+    """The far route's bound as the library computes it (k_thermal_cplx.hip): no matrix in LDS, so the 128 columns of two
+    per lane bind; a library that does not export it, or none built yet, leaves the literal."""
+    try:
+        return int(L.load().afq_thermal_far_max_basis())
+    except (L.AfqLibraryError, AttributeError):
+        return 128
+
+
 def _delayed_max_basis():
     """The delayed route's bound as the library computes it from its kernels' LDS (k_thermal.hip) and the 128 columns of
     two per lane; a library that does not export it, or none built yet, leaves the literal."""
@@ -35,14 +44,17 @@ def _delayed_max_basis():
 
 
 # The largest basis of the complex walkers by (kind, route): what fits the 160 KiB of LDS of a work-group.  The route is
-# streamed_greens (False / True) or 'wide' (walkers: {wide_basis: True}: one complex matrix in LDS, two columns per lane).
+# streamed_greens (False / True), 'wide' (walkers: {wide_basis: True}: one complex matrix in LDS, two columns per lane)
+# or 'far' (walkers: {far_basis: True}: the wide route with that matrix in device memory as well).
 MAX_BASIS = {
     ('planewave', False): 47,            # ts_greens_lds<cplx> (thermal_strat.h): four complex matrices
     ('planewave', True): 57,             # thc_slice_lds (k_thermal_cplx.hip): three complex matrices
     ('planewave', 'wide'): _wide_max_basis(),             # ts_greens_wide_lds (thermal_wide.h): one complex matrix
+    ('planewave', 'far'): _far_max_basis(),               # the lanes: two columns each
     ('hubbard_continuous', False): 47,   # ts_greens_lds<cplx>
     ('hubbard_continuous', True): 63,    # thd_slice_lds (k_thermal_cplx.hip): two complex matrices and BH1
     ('hubbard_continuous', 'wide'): _wide_max_basis(),    # ts_greens_wide_lds
+    ('hubbard_continuous', 'far'): _far_max_basis(),      # the lanes
     # the real walkers with walkers: {delayed_updates: True}: ts_greens_wide_lds<double> fits, the lanes bind
     ('discrete', 'delayed'): _delayed_max_basis(),
 }
@@ -178,6 +190,19 @@ class ThermalWalkers(object):
         if self.wide_basis and self.streamed_greens:
             raise NotImplementedError("thermal walkers: wide_basis and streamed_greens are two placements of the same "
                                       "matrices: ask for one")
+        # the wide route with no matrix in LDS (thermal_wide.h, AFQ_THERMAL_FAR)
+        self.far_basis = bool(walker_opts.get('far_basis', False))
+        if self.far_basis and self.kind == 'discrete':
+            raise NotImplementedError("thermal walkers: far_basis belongs to the continuous fields (Hubbard walkers "
+                                      "with discrete fields reach M = 128 with delayed_updates; with "
+                                      "hubbard_stratonovich: 'continuous' the driver announces the complex walkers, and "
+                                      "walkers: {continuous_fields: True} does so by hand)")
+        if self.far_basis and self.wide_basis:
+            raise NotImplementedError("thermal walkers: far_basis and wide_basis are two placements of the same "
+                                      "matrices: ask for one")
+        if self.far_basis and self.streamed_greens:
+            raise NotImplementedError("thermal walkers: far_basis and streamed_greens are two placements of the same "
+                                      "matrices: ask for one")
         # the slice by delayed updates and the wide real Green's function (k_thermal.hip, AFQ_THERMAL_DELAYED)
         self.delayed_updates = bool(walker_opts.get('delayed_updates', False))
         if self.delayed_updates and self.kind != 'discrete':
@@ -191,7 +216,7 @@ class ThermalWalkers(object):
                 raise NotImplementedError("thermal walkers: M = %d > %d sites is not supported with delayed_updates (the "
                                           "wide Green's function works two columns per lane, 128 in all)"
                                           % (system.nbasis, bound))
-        elif system.nbasis > 64 and not self.wide_basis:
+        elif system.nbasis > 64 and not self.wide_basis and not self.far_basis:
             raise NotImplementedError("thermal walkers: M = %d > 64 sites is not supported%s" % (
                 system.nbasis, " (walkers: {delayed_updates: True} reaches M = %d)" % MAX_BASIS['discrete', 'delayed']
                 if self.kind == 'discrete' else ""))
@@ -266,7 +291,8 @@ class ThermalWalkers(object):
         if self.delayed_updates and kind != 'discrete':
             raise NotImplementedError("thermal walkers: delayed_updates belongs to the discrete fields (a '%s' "
                                       "propagator moves complex walkers)" % getattr(prop, 'hs_type', kind))
-        configure(L.THERMAL_WIDE if self.wide_basis else L.THERMAL_STREAMED_GREENS if self.streamed_greens
+        configure(L.THERMAL_FAR if self.far_basis else L.THERMAL_WIDE if self.wide_basis
+                  else L.THERMAL_STREAMED_GREENS if self.streamed_greens
                   else L.THERMAL_DELAYED if self.delayed_updates else 0)
         self.kind, self.configured = kind, (kind, key)
 
@@ -278,6 +304,9 @@ class ThermalWalkers(object):
         if self.wide_basis:
             raise NotImplementedError("thermal walkers: wide_basis belongs to the continuous fields (Hubbard walkers "
                                       "with discrete fields work one lane per column, M <= 64)")
+        if self.far_basis:
+            raise NotImplementedError("thermal walkers: far_basis belongs to the continuous fields (Hubbard walkers "
+                                      "with discrete fields reach M = 128 with delayed_updates)")
         nstblz = self.nstblz if prop is None else prop.nstblz
 
         def configure(options):
@@ -316,6 +345,13 @@ class ThermalWalkers(object):
                 raise NotImplementedError("%s: M = %d > %d %s is not supported with wide_basis (the wide Green's function "
                                           "keeps one complex matrix of 16 M (M | 1) bytes and 18,944 bytes of vectors in the "
                                           "160 KiB of LDS)" % (who, M, bound, unit))
+            return
+        if getattr(self, 'far_basis', False):
+            bound = MAX_BASIS[kind, 'far']
+            if M > bound:
+                raise NotImplementedError("%s: M = %d > %d %s is not supported with far_basis (the far Green's function "
+                                          "keeps no matrix in LDS; a lane owns two columns, 128 in all)"
+                                          % (who, M, bound, unit))
             return
         bound = MAX_BASIS[kind, self.streamed_greens]
         if M > bound:

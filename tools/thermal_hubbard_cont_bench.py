@@ -15,10 +15,12 @@ The kernels are timed with event pairs around every launch (afq_launch_trace) ov
   thermal_cweight_mf_kernel      the phaseless weight update with mf_const_fac
 With `--wide` the engines run in turn are the wide route alone (AFQ_THERMAL_WIDE: thermal_cgreens_wide_kernel and
 thermal_cslice_dense_wide_kernel, one matrix in LDS), which is the only one above 63 sites (`--nx 8`).
+With `--far` the far route (AFQ_THERMAL_FAR: thermal_cgreens_far_kernel and thermal_cslice_dense_far_kernel, no matrix
+in LDS) runs in turn with the wide route to 95 sites and alone above (`--nx 8 --ny 16`: M = 128).
 `slice_ms` = all of them over the slices run; `path_kernel_ms` = the same per path; `path_wall_ms` the host's wall time
 of a path, fields and copies included, taken in a separate pass without the event pairs.
 
-  python tools/thermal_hubbard_cont_bench.py [--rounds 3] [--paths 5] [--warmup 2] [--nx 6] [--stack-size 5] [--wide] [--out FILE]
+  python tools/thermal_hubbard_cont_bench.py [--rounds 3] [--paths 5] [--warmup 2] [--nx 6] [--ny NX] [--stack-size 5] [--wide | --far] [--out FILE]
 """
 import argparse
 import json
@@ -38,13 +40,13 @@ from pauxy_amd.systems import Hubbard                                           
 from pauxy_amd.trial_density import OneBody                                     # noqa: E402
 
 GREENS = {'resident': 'thermal_cgreens_kernel', 'streamed': 'thermal_cgreens_streamed_kernel',
-          'wide': 'thermal_cgreens_wide_kernel'}
-OPTIONS = {'resident': 0, 'streamed': L.THERMAL_STREAMED_GREENS, 'wide': L.THERMAL_WIDE}
+          'wide': 'thermal_cgreens_wide_kernel', 'far': 'thermal_cgreens_far_kernel'}
+OPTIONS = {'resident': 0, 'streamed': L.THERMAL_STREAMED_GREENS, 'wide': L.THERMAL_WIDE, 'far': L.THERMAL_FAR}
 SMALL = ('thermal_crdm_kernel', 'thermal_cfields_dense_kernel', 'thermal_cweight_mf_kernel')
 
 
 def slice_of(engine):
-    return 'thermal_cslice_dense_wide_kernel' if engine == 'wide' else 'thermal_cslice_dense_kernel'
+    return {'wide': 'thermal_cslice_dense_wide_kernel', 'far': 'thermal_cslice_dense_far_kernel'}.get(engine, 'thermal_cslice_dense_kernel')
 
 
 class Qmc(object):
@@ -65,8 +67,8 @@ def spread(values):
 
 
 def run(a, engine):
-    M = a.nx * a.nx
-    system = Hubbard(a.nx, a.nx, M // 2 - 1, M // 2 - 1, 4.0, mu=1.0)
+    M = a.nx * a.ny
+    system = Hubbard(a.nx, a.ny, M // 2 - 1, M // 2 - 1, 4.0, mu=1.0)
     trial = OneBody(system, a.beta, a.dt)
     nslices = trial.num_slices
     prop = Continuous({}, Qmc(a.dt), system, trial)
@@ -90,7 +92,7 @@ def run(a, engine):
         one_path(dev, rng, nslices, M00)
     trace = dev.launch_trace_get()
     dev.launch_trace(False)
-    res = {'system': 'Hubbard %dx%d U=4 mu=1' % (a.nx, a.nx), 'M': M, 'walkers': a.walkers, 'beta': a.beta, 'dt': a.dt,
+    res = {'system': 'Hubbard %dx%d U=4 mu=1' % (a.nx, a.ny), 'M': M, 'walkers': a.walkers, 'beta': a.beta, 'dt': a.dt,
            'slices': nslices, 'stack_size': a.stack_size, 'nbins': nslices // a.stack_size, 'trial_mu': trial.mu,
            'paths': a.paths, 'engine': engine, 'kernels': {}}
     total = 0.0
@@ -111,6 +113,7 @@ def run(a, engine):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--nx', type=int, default=6)
+    ap.add_argument('--ny', type=int, default=0, help='0: a square lattice, nx x nx')
     ap.add_argument('--walkers', type=int, default=256)
     ap.add_argument('--beta', type=float, default=1.0)
     ap.add_argument('--dt', type=float, default=0.05)
@@ -119,9 +122,14 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--rounds', type=int, default=3, help='runs of each engine, resident and streamed in turn')
     ap.add_argument('--wide', action='store_true', help='the wide route alone (AFQ_THERMAL_WIDE); with --nx 6 beside the other two')
+    ap.add_argument('--far', action='store_true', help='the far route (AFQ_THERMAL_FAR), beside the wide route to 95 sites')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
-    names = (('resident', 'streamed', 'wide') if a.nx * a.nx <= 47 else ('wide',)) if a.wide else ('resident', 'streamed')
+    a.ny = a.ny or a.nx
+    if a.far:
+        names = ('wide', 'far') if a.nx * a.ny <= 95 else ('far',)
+    else:
+        names = (('resident', 'streamed', 'wide') if a.nx * a.ny <= 47 else ('wide',)) if a.wide else ('resident', 'streamed')
     runs = {name: [] for name in names}
     for _ in range(a.rounds):
         for name in names:
@@ -138,10 +146,11 @@ def main():
                      'path_kernel_ms': spread([r['path_kernel_ms'] for r in runs[name]]),
                      'path_wall_ms': spread([r['path_wall_ms']['median'] for r in runs[name]]),
                      'finite': all(r['finite'] for r in runs[name])}
-    for other, base in (('streamed', 'resident'), ('wide', 'streamed')):
+    for other, base in (('streamed', 'resident'), ('wide', 'streamed'), ('far', 'wide')):
         if other in res and base in res:
             res['%s_over_%s' % (other, base)] = {k: res[other][k]['median'] / res[base][k]['median']
-                                                 for k in ('slice_ms', 'greens_mean_ms', 'path_wall_ms')}
+                                                 for k in ('slice_ms', 'greens_mean_ms', 'path_wall_ms') +
+                                                 (('slice_kernel_mean_ms',) if other == 'far' else ())}
     res['runs'] = runs
     print(json.dumps(res))
     if a.out:

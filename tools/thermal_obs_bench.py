@@ -6,12 +6,14 @@ afq_thermal_energy per bin (one launch per stage and one host round trip per bin
 Shapes, each on the stacks one propagated path leaves (beta = 1 in 20 slices of dt = 0.05, OneBody trial):
   UEG rs = 1, ecut = 2 (M = 33), 2 + 2, mu = 0.245: 4 bins (stack_size 5) and 20 bins (stack_size 1), 256 and 16 walkers
   Hubbard 8 x 8, U = 4, mu = 1, discrete fields:    2 bins (stack_size 10), 256 walkers
+With `--far` instead the sweep on the wide body: UEG rs = 1, ecut = 3 (M = 81) on a handle configured with
+AFQ_THERMAL_FAR, 4 bins, 16 and 256 walkers.
 Per shape `--rounds` alternating runs of the two; a run is the host's wall time of `--reps` calls after `--warmup`,
 per call, the copies of the results to the host included (both ways end with one).  Medians and (min - max) over the
 rounds; `same_bits` says that the sweep's sums equalled the loop's, added in bin order, on this run.  Measured, not
 tuned: there is no target.
 
-  python tools/thermal_obs_bench.py [--rounds 3] [--reps 10] [--warmup 2] [--out profiles/thermal_observables.json]
+  python tools/thermal_obs_bench.py [--rounds 3] [--reps 10] [--warmup 2] [--far] [--out profiles/thermal_observables.json]
 """
 import argparse
 import json
@@ -24,6 +26,7 @@ import numpy
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from pauxy_amd import _lib as L                                                 # noqa: E402
 from pauxy_amd.device import AfqDevice                                          # noqa: E402
 from pauxy_amd.propagation.thermal_hubbard import thermal_constants            # noqa: E402
 from pauxy_amd.propagation.thermal_planewave import planewave_constants        # noqa: E402
@@ -32,21 +35,26 @@ from pauxy_amd.trial_density import OneBody                                     
 
 BETA, DT = 1.0, 0.05
 SHAPES = [('ueg', 5, 256), ('ueg', 5, 16), ('ueg', 1, 256), ('ueg', 1, 16), ('hubbard', 10, 256)]
+FAR_SHAPES = [('ueg_far', 5, 16), ('ueg_far', 5, 256)]
 
 
-def ueg_device(stack_size, nw):
-    s = UEG(1.0, 2, 2, 2.0, full_lists=True, mu=0.245)
+def ueg_device(stack_size, nw, ecut=2.0, options=0):
+    s = UEG(1.0, 2, 2, ecut, full_lists=True, mu=0.245)
     trial = OneBody(s, BETA, DT)
     BH1, mf_shift = planewave_constants(s, trial, DT)
     dev = AfqDevice(0)
     dev.set_system_ueg(s.iA, s.iB, s.ikpq_i, s.ikpq_kpq, s.ipmq_i, s.ipmq_pmq, s.vqvec, s.vol,
                        numpy.array([s.H1[0].diagonal(), s.H1[1].diagonal()]), s.ecore, s.nup, s.ndown)
     dev.walkers_alloc(nw)
-    dev.thermal_configure_continuous(trial.num_slices, stack_size, DT, trial.dmat, trial.dmat_inv, BH1, mf_shift)
+    dev.thermal_configure_continuous(trial.num_slices, stack_size, DT, trial.dmat, trial.dmat_inv, BH1, mf_shift, options=options)
     rng = numpy.random.RandomState(5)
     for _ in range(trial.num_slices):
         dev.thermal_propagate_continuous(rng.normal(size=(nw, dev.K)))
-    return dev, 'UEG rs=1 ecut=2 2+2 mu=0.245', trial.num_slices
+    return dev, 'UEG rs=1 ecut=%g 2+2 mu=0.245%s' % (ecut, ' far_basis' if options else ''), trial.num_slices
+
+
+def ueg_far_device(stack_size, nw):
+    return ueg_device(stack_size, nw, 3.0, L.THERMAL_FAR)
 
 
 def hubbard_device(stack_size, nw):
@@ -90,11 +98,13 @@ def main():
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--far', action='store_true', help='the sweep on a far handle at M = 81 instead of the shapes above')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     shapes = []
-    for kind, stack_size, nw in SHAPES:
-        dev, system, nslices = (ueg_device if kind == 'ueg' else hubbard_device)(stack_size, nw)
+    makers = {'ueg': ueg_device, 'hubbard': hubbard_device, 'ueg_far': ueg_far_device}
+    for kind, stack_size, nw in (FAR_SHAPES if a.far else SHAPES):
+        dev, system, nslices = makers[kind](stack_size, nw)
         nbins = nslices // stack_size
         try:
             rows = loop(dev, nbins, stack_size)

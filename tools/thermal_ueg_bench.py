@@ -6,14 +6,17 @@
 The kernels are timed with event pairs around every launch (afq_launch_trace) over `--paths` whole paths after
 `--warmup` paths; the fields come from the host (numpy), as in a run.  Per kernel: launches, total and mean ms.
   thermal_crdm_kernel      P = I - G^T of every walker
-  vbias_ueg_lds_kernel     the plane-wave force bias of P (k_models.hip)
+  vbias_ueg_lds_kernel     the plane-wave force bias of P (k_models.hip); vbias_ueg_kernel where P does not fit its LDS
+                           (M = 123): one of the two has no launches
   thermal_cfields_kernel   clip, shifted fields, cmf, cfb
   vhs_ueg_kernel           the plane-wave HS potential (k_models.hip)
   thermal_cslice_kernel    BV by five Horner products, B, right <- B right, the bin
   thermal_cgreens_kernel   the complex stratified G of all bins and det G (every slice, and once per reset);
                            with --streamed thermal_cgreens_streamed_kernel, T in device memory (needed above M = 47);
                            with --wide thermal_cgreens_wide_kernel and thermal_cslice_wide_kernel, one matrix in LDS
-                           (AFQ_THERMAL_WIDE, needed above M = 57: ecut 3.0 is M = 81, ecut 4.0 is M = 93)
+                           (AFQ_THERMAL_WIDE, needed above M = 57: ecut 3.0 is M = 81, ecut 4.0 is M = 93);
+                           with --far thermal_cgreens_far_kernel and thermal_cslice_far_kernel, no matrix in LDS
+                           (AFQ_THERMAL_FAR, needed above M = 95: ecut 4.5 is M = 123)
   thermal_cweight_kernel   the phaseless weight update
 `slice_ms` = all of them over the slices run; `path_wall_ms` the host's wall time of a path, fields and copies included
 (median and spread over the paths), taken in a separate pass without the event pairs.
@@ -21,10 +24,10 @@ The kernels are timed with event pairs around every launch (afq_launch_trace) ov
 With `--alternate N` the resident and the streamed engine are run in turn, N times each, on the same shape (M <= 47):
 the JSON then holds every run's figures under `runs` and the median and spread of slice_ms, of the Green's kernel's
 mean and of the path's wall time per engine.  `--alternate N --wide` sets the streamed and the wide route side by side
-instead (M <= 57).
+instead (M <= 57), `--alternate N --far` the wide and the far route (M <= 95).
 
   python tools/thermal_ueg_bench.py [--paths 5] [--warmup 2] [--ecut 2.0] [--stack-size 5]
-                                    [--streamed | --wide | --alternate N [--wide]] [--out FILE]
+                                    [--streamed | --wide | --far | --alternate N [--wide | --far]] [--out FILE]
 """
 import argparse
 import json
@@ -44,13 +47,15 @@ from pauxy_amd.systems import UEG                                               
 from pauxy_amd.trial_density import OneBody                                     # noqa: E402
 
 GREENS = {'resident': 'thermal_cgreens_kernel', 'streamed': 'thermal_cgreens_streamed_kernel',
-          'wide': 'thermal_cgreens_wide_kernel'}
-OPTIONS = {'resident': 0, 'streamed': L.THERMAL_STREAMED_GREENS, 'wide': L.THERMAL_WIDE}
+          'wide': 'thermal_cgreens_wide_kernel', 'far': 'thermal_cgreens_far_kernel'}
+SLICE = {'resident': 'thermal_cslice_kernel', 'streamed': 'thermal_cslice_kernel', 'wide': 'thermal_cslice_wide_kernel',
+         'far': 'thermal_cslice_far_kernel'}
+OPTIONS = {'resident': 0, 'streamed': L.THERMAL_STREAMED_GREENS, 'wide': L.THERMAL_WIDE, 'far': L.THERMAL_FAR}
 
 
 def kernels_of(engine):
-    return ('thermal_crdm_kernel', 'vbias_ueg_lds_kernel', 'thermal_cfields_kernel', 'vhs_ueg_kernel',
-            'thermal_cslice_wide_kernel' if engine == 'wide' else 'thermal_cslice_kernel', GREENS[engine],
+    return ('thermal_crdm_kernel', 'vbias_ueg_lds_kernel', 'vbias_ueg_kernel', 'thermal_cfields_kernel', 'vhs_ueg_kernel',
+            SLICE[engine], GREENS[engine],
             'thermal_cweight_kernel')
 
 
@@ -77,12 +82,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--streamed', action='store_true', help='AFQ_THERMAL_STREAMED_GREENS: T of the Green\'s function in device memory')
     ap.add_argument('--wide', action='store_true', help='AFQ_THERMAL_WIDE: one matrix in LDS, two columns per lane')
+    ap.add_argument('--far', action='store_true', help='AFQ_THERMAL_FAR: no matrix in LDS, two columns per lane')
     ap.add_argument('--alternate', type=int, default=0, help='N runs each of the resident and the streamed engine, in turn '
-                    '(with --wide: of the streamed and the wide route)')
+                    '(with --wide: of the streamed and the wide route; with --far: of the wide and the far route)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.alternate > 0:
-        base, other = ('streamed', 'wide') if a.wide else ('resident', 'streamed')
+        base, other = ('wide', 'far') if a.far else ('streamed', 'wide') if a.wide else ('resident', 'streamed')
         runs = {base: [], other: []}
         for _ in range(a.alternate):
             for name in (base, other):
@@ -93,13 +99,14 @@ def main():
             g = GREENS[name]
             res[name] = {'slice_ms': spread([r['slice_ms'] for r in runs[name]]),
                          'greens_mean_ms': spread([r['kernels'][g]['mean_ms'] for r in runs[name]]),
+                         'slice_kernel_mean_ms': spread([r['kernels'][SLICE[name]]['mean_ms'] for r in runs[name]]),
                          'path_wall_ms': spread([r['path_wall_ms']['median'] for r in runs[name]]),
                          'finite': all(r['finite'] for r in runs[name])}
         res['%s_over_%s' % (other, base)] = {k: res[other][k]['median'] / res[base][k]['median']
-                                             for k in ('slice_ms', 'greens_mean_ms', 'path_wall_ms')}
+                                             for k in ('slice_ms', 'greens_mean_ms', 'slice_kernel_mean_ms', 'path_wall_ms')}
         res['runs'] = runs
     else:
-        res = run(a, 'wide' if a.wide else 'streamed' if a.streamed else 'resident')
+        res = run(a, 'far' if a.far else 'wide' if a.wide else 'streamed' if a.streamed else 'resident')
     print(json.dumps(res))
     if a.out:
         with open(a.out, 'w') as f:
