@@ -671,6 +671,7 @@ int afq_estimates_get_end(afq_handle *h, double *est_out /* c128[10] */);
                                            AFQ_EINVAL on the two continuous entry points, by name */
 #define AFQ_THERMAL_FAR             256 /* honoured by the two continuous entry points (below), refused here by name
                                            (64 stays an unknown bit on every entry point) */
+#define AFQ_THERMAL_QUAD 512            /* honoured by the two continuous entry points (below), refused here by name */
 int afq_thermal_configure(afq_handle *h, int ntime_slices, int stack_size, int nstblz, const double *BT,
                           const double *BT_inv, const double *BH1, const double *auxf, int options);
 /* With AFQ_THERMAL_DELAYED in options the handle takes the real walkers' second route, for any M >= 1: every Green's
@@ -712,7 +713,7 @@ int afq_thermal_state(afq_handle *h, int32_t *out4);
  * TWO_RDM (UEG): two_rdm_out f64[2, 2, nq] = sum_w weight_w Re two_rdm[P_w] of the same G, from the pair sums of the
  * energy launch.  AFQ_ESTATE: no thermal configuration; AFQ_EINVAL: unknown bits in what, a needed output NULL;
  * AFQ_EUNSUPPORTED: TWO_RDM on a Hubbard handle; AVERAGE_GF on a handle configured with AFQ_THERMAL_WIDE or
- * AFQ_THERMAL_DELAYED (a handle configured with AFQ_THERMAL_FAR runs it). */
+ * AFQ_THERMAL_DELAYED (a handle configured with AFQ_THERMAL_FAR or AFQ_THERMAL_QUAD runs it). */
 #define AFQ_THERMAL_EST_AVERAGE_GF 1
 #define AFQ_THERMAL_EST_ONE_RDM    2
 #define AFQ_THERMAL_EST_TWO_RDM    4   /* UEG walkers only: AFQ_EUNSUPPORTED otherwise */
@@ -754,6 +755,17 @@ int afq_thermal_set_sweep_budget(afq_handle *h, size_t bytes);
  * and the 10 x 10, 11 x 11 and 8 x 16 Hubbard lattices; above it AFQ_EUNSUPPORTED with M and the numbers.  A far handle
  * is served as a wide one is, and afq_thermal_estimates runs AVERAGE_GF on it as well: the sweep is the same kernel on a
  * grid (2 nw, bins) (thermal_cgreens_far_sweep_kernel), every work-group in a scratch of its own.
+ * With AFQ_THERMAL_QUAD the handle takes a fifth route (the bit beside AFQ_THERMAL_FAR, AFQ_THERMAL_WIDE or
+ * AFQ_THERMAL_STREAMED_GREENS is AFQ_EINVAL): the far route with four columns per lane.  The Green's function
+ * (thermal_cgreens_quad_kernel) is the far body with a lane owning the columns c, c + 64, c + 128 and c + 192 and its
+ * vectors in LDS at 256 entries (37,888 bytes); the scratch is the far route's, nw * 2 * (4 M^2 + M (M | 1)) * 16
+ * bytes (2.7 GB at M = 256 and 256 walkers), allocated by the configure call; the slice kernels
+ * (thermal_cslice_quad_kernel, Hubbard: thermal_cslice_dense_quad_kernel) are the far ones with bv at 256 entries.
+ * Every column goes through the far route's operations in the far route's order: G, det G, right, the bins, M0 and the
+ * weights are the bits of the far route wherever both run.  The bound is the 256 columns of four per lane:
+ * M <= 256 = afq_thermal_quad_max_basis(), which holds the shells of 147 to 251 plane waves and the 12 x 12 and
+ * 16 x 16 Hubbard lattices; above it AFQ_EUNSUPPORTED with M and the numbers.  A quad handle is served as a far one is,
+ * AVERAGE_GF included (thermal_cgreens_quad_sweep_kernel).
  *   afq_thermal_configure_continuous  after afq_set_system_ueg (index lists over ALL plane waves, for the energy) and
  *                          afq_walkers_alloc; no trial determinant, no afq_set_propagator.  BT, BT_inv, BH1
  *                          f64[2, M, M]: the trial's dmat and its inverse (diagonal) and
@@ -765,7 +777,7 @@ int afq_thermal_set_sweep_budget(afq_handle *h, size_t bytes);
  *                          afq_thermal_reset.  AFQ_EUNSUPPORTED: the option bits, a system that is not the UEG,
  *                          M > 47 (the message carries M and the bytes; M > 57 with
  *                          AFQ_THERMAL_STREAMED_GREENS, M > 95 with AFQ_THERMAL_WIDE, M > 128 with
- *                          AFQ_THERMAL_FAR), a trial that is not diagonal, more than
+ *                          AFQ_THERMAL_FAR, M > 256 with AFQ_THERMAL_QUAD), a trial that is not diagonal, more than
  *                          one rank, back-propagation / ITCF / mixed RDM on the handle.
  *   afq_thermal_propagate_continuous  one time slice of every walker, dead ones included: P = I - G^T,
  *                          xbar = -sqrt(dt) P.[iA | iB] (|xbar_i| > fb_bound: unit modulus), xs = xi - xbar, cmf = -sqrt(dt) xs.mf_shift,
@@ -791,6 +803,8 @@ int afq_thermal_propagate_continuous(afq_handle *h, const double *xi, double *xi
 int afq_thermal_wide_max_basis(void);
 /* the largest M a handle configured with AFQ_THERMAL_FAR admits (no handle, no device) */
 int afq_thermal_far_max_basis(void);
+/* the largest M a handle configured with AFQ_THERMAL_QUAD admits (no handle, no device) */
+int afq_thermal_quad_max_basis(void);
 
 /* ---- finite-temperature AFQMC with continuous fields: thermal walkers of the Hubbard model --------------------
  * thermal_propagation/continuous.py:84-120,202-257 (Continuous, phaseless, force bias, hybrid weight) with
@@ -802,8 +816,8 @@ int afq_thermal_far_max_basis(void);
  *                          expm(-dt/2 (h1e_mod - i sqrt(U) diag(mf_shift) + sign mu)); mf_shift c128[M] =
  *                          i sqrt(U) diag(P_up + P_dn) of the trial; mf_const_fac c128[1] = exp(-dt mf_shift.mf_shift / 2).
  *                          left_k = BT^stack_size BT_inv^(k + 1) is built on the host in the reference's order.
- *                          options: AFQ_THERMAL_STREAMED_GREENS, AFQ_THERMAL_WIDE or AFQ_THERMAL_FAR is honoured (two
- *                          of them: AFQ_EINVAL; with WIDE the bound is M <= 95, with FAR M <= 128, as above), the other AFQ_THERMAL_* bits are
+ *                          options: AFQ_THERMAL_STREAMED_GREENS, AFQ_THERMAL_WIDE, AFQ_THERMAL_FAR or AFQ_THERMAL_QUAD is honoured (two
+ *                          of them: AFQ_EINVAL; with WIDE the bound is M <= 95, with FAR M <= 128, with QUAD M <= 256, as above), the other AFQ_THERMAL_* bits are
  *                          refused by name.  Without WIDE the bound on M is the smallest of the slice kernel's
  *                          40 M (M | 1) + 1024 bytes of LDS (M <= 63), the Green's kernel's (M <= 47 resident, 64
  *                          streamed) and the 64 lanes of a wave: M <= 47, and M <= 63 with the bit.  Above it

@@ -27,6 +27,7 @@ THERMAL_STREAMED_GREENS = 16
 THERMAL_WIDE = 32
 THERMAL_DELAYED = 128          # (64 stays unknown)
 THERMAL_FAR = 256
+THERMAL_QUAD = 512
 THERMAL_EST_AVERAGE_GF, THERMAL_EST_ONE_RDM, THERMAL_EST_TWO_RDM = 1, 2, 4      # afq_thermal_estimates
 AFQ_EINVAL, AFQ_ESTATE, AFQ_EUNSUPPORTED = -1, -2, -5
 
@@ -172,6 +173,7 @@ SIGNATURES = {
     "afq_thermal_left_table": [c_int, c_int, _dp, _dp, _dp, _dp],
     "afq_thermal_wide_max_basis": [],
     "afq_thermal_far_max_basis": [],
+    "afq_thermal_quad_max_basis": [],
     "afq_thermal_delayed_max_basis": [],
     "afq_thermal_device_allocations": [_h, c_void_p],
     "afq_thermal_estimates": [_h, c_int, _dp, _dp, _dp, _dp],

@@ -51,7 +51,8 @@ enum ThKind { TH_NONE = 0, TH_REAL, TH_CPLX_DIAG, TH_CPLX_DENSE };
 // option bits of the configure call.  RESIDENT: all in LDS.  STREAMED (AFQ_THERMAL_STREAMED_GREENS, complex walkers): T in
 // device memory.  WIDE (AFQ_THERMAL_WIDE, complex; AFQ_THERMAL_DELAYED, real): one matrix in LDS, two columns per lane.
 // FAR (AFQ_THERMAL_FAR, complex): the wide route with that matrix in device memory as well, M <= 128.
-enum ThEngine { TH_ENGINE_RESIDENT = 0, TH_ENGINE_STREAMED, TH_ENGINE_WIDE, TH_ENGINE_FAR };
+// QUAD (AFQ_THERMAL_QUAD, complex): the far route with four columns per lane, M <= 256.
+enum ThEngine { TH_ENGINE_RESIDENT = 0, TH_ENGINE_STREAMED, TH_ENGINE_WIDE, TH_ENGINE_FAR, TH_ENGINE_QUAD };
 
 struct afq_handle {
     int device = 0;

@@ -14,11 +14,15 @@
 // as a fifth scratch buffer, and the far instantiations of the slice kernels, which read every operand where it lies in
 // device memory -- so that the lanes alone bind: M <= 128, which holds the shell of 123 plane waves and the Hubbard
 // lattices 10 x 10, 11 x 11 and 8 x 16.  The same bits as the wide route wherever both run.
+// With AFQ_THERMAL_QUAD a fifth: the far route with four columns per lane (thermal_wide.h's TsQuad) and the far
+// instantiations of the slice kernels launched under their own names, bv at 256 entries: M <= 256, which holds the shells to 251
+// plane waves and the Hubbard lattices 12 x 12 and 16 x 16.  The same bits as the far route wherever both run.
 // The route is the handle's th_engine: th_launch_greens<cplx> (thermal_wide.h) and the two slice launches read it, and
 // nothing else does.  The names below are the launch trace's; each slice kernel is one template over where its matrices
 // live (ThcPlace: all in LDS; one matrix in LDS and the rest in th_scratch; none in LDS).
 //
 //   thermal_cgreens_far_kernel, thermal_cslice_far_kernel, thermal_cslice_dense_far_kernel  the far route's three.
+//   thermal_cgreens_quad_kernel, thermal_cslice_quad_kernel, thermal_cslice_dense_quad_kernel  the quad route's three.
 //   thermal_cgreens_kernel  G and det G of every (walker, spin) from the stack: thermal_strat.h's engine with T = cplx.
 //   thermal_cgreens_streamed_kernel  the same with the streamed placement, for a handle configured with the bit.
 //   thermal_cgreens_wide_kernel  thermal_wide.h's engine, for a handle configured with AFQ_THERMAL_WIDE.
@@ -71,6 +75,8 @@ enum ThcPlace { THC_IN_LDS, THC_ONE_IN_LDS, THC_NONE_IN_LDS };
 // right <- B right.  THC_NONE_IN_LDS (the far route): the T_n in scratch as well, V read from a.vhs in device memory
 // and BV from the scratch buffer the Horner chain leaves it in.  Every element goes through the same operations in the
 // same order -- the same ts_gemm with other loaders -- so the instantiations give the same bits where they run.
+// The quad route launches the THC_NONE_IN_LDS instantiation under its own name: the kernel keeps no vector, so nothing in
+// it knows how many columns a lane of the Green's kernel owns.
 template <ThcPlace P> __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_kernel(ThcSliceArgs a, cplx *scratch, long stride) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr bool IN_LDS = P == THC_IN_LDS, FAR = P == THC_NONE_IN_LDS;
@@ -324,6 +330,9 @@ template <ThcPlace P> __device__ inline TsMatView<cplx> thd_staged(TsMatView<cpl
 // memory (scratch + w stride, pitch M).  THC_NONE_IN_LDS (the far route): B_s and the new right in scratch as well, and
 // every operand read where it lies: BH1_s in a.bh1, B_s and the new right in scratch; LDS holds bv alone.  The products
 // are the same with other loaders: the same bits where they run.
+// bv holds M entries of the dynamic LDS the launch gives: thd_slice_far_lds (128 entries) on the far route, and the same
+// THC_NONE_IN_LDS instantiation with thd_slice_quad_lds (256 entries) under the quad route's name.  It is filled by the
+// threads tid < M, so M <= TH_THREADS.
 template <ThcPlace P> __global__ __launch_bounds__(TH_THREADS) void thermal_cslice_dense_kernel(ThdSliceArgs a, cplx *scratch, long stride) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr bool IN_LDS = P == THC_IN_LDS, FAR = P == THC_NONE_IN_LDS;
@@ -459,17 +468,23 @@ namespace {
 
 const char *const THC_RESIDENT_HINT = "; AFQ_THERMAL_STREAMED_GREENS (streamed_greens) keeps T in device memory and reaches further";
 
-// STREAMED_GREENS, WIDE and FAR name three placements of the same working set: any two together mean nothing
+// STREAMED_GREENS, WIDE, FAR and QUAD name four placements of the same working set: any two together mean nothing
 int thc_engine_of(afq_handle *h, const std::string &me, int options, ThEngine *engine) {
     const bool streamed = (options & AFQ_THERMAL_STREAMED_GREENS) != 0, wide = (options & AFQ_THERMAL_WIDE) != 0,
-               far = (options & AFQ_THERMAL_FAR) != 0;
+               far = (options & AFQ_THERMAL_FAR) != 0, quad = (options & AFQ_THERMAL_QUAD) != 0;
     if (streamed && wide)
         AFQ_FAIL(h, AFQ_EINVAL, me + "wide_basis and streamed_greens are two placements of the same matrices: ask for one");
     if (far && wide)
         AFQ_FAIL(h, AFQ_EINVAL, me + "far_basis and wide_basis are two placements of the same matrices: ask for one");
     if (far && streamed)
         AFQ_FAIL(h, AFQ_EINVAL, me + "far_basis and streamed_greens are two placements of the same matrices: ask for one");
-    *engine = far ? TH_ENGINE_FAR : wide ? TH_ENGINE_WIDE : streamed ? TH_ENGINE_STREAMED : TH_ENGINE_RESIDENT;
+    if (quad && far)
+        AFQ_FAIL(h, AFQ_EINVAL, me + "quad_basis and far_basis are two placements of the same matrices: ask for one");
+    if (quad && wide)
+        AFQ_FAIL(h, AFQ_EINVAL, me + "quad_basis and wide_basis are two placements of the same matrices: ask for one");
+    if (quad && streamed)
+        AFQ_FAIL(h, AFQ_EINVAL, me + "quad_basis and streamed_greens are two placements of the same matrices: ask for one");
+    *engine = quad ? TH_ENGINE_QUAD : far ? TH_ENGINE_FAR : wide ? TH_ENGINE_WIDE : streamed ? TH_ENGINE_STREAMED : TH_ENGINE_RESIDENT;
     return AFQ_OK;
 }
 
@@ -479,17 +494,17 @@ const ThLds THC_WIDE_GREENS = {"the wide Green's function (thermal_cgreens_wide_
 inline bool thc_two_columns(ThEngine engine) { return engine == TH_ENGINE_WIDE || engine == TH_ENGINE_FAR; }
 // scalars of th_scratch per work-group of the handle's Green's kernel; a walker's share is both spins'
 inline size_t thc_greens_scratch(ThEngine engine, int M) {
-    return engine == TH_ENGINE_FAR ? ts_greens_far_scratch(M) : engine == TH_ENGINE_WIDE ? ts_greens_wide_scratch(M)
+    return engine == TH_ENGINE_FAR || engine == TH_ENGINE_QUAD ? ts_greens_far_scratch(M) : engine == TH_ENGINE_WIDE ? ts_greens_wide_scratch(M)
          : engine == TH_ENGINE_STREAMED ? TsStreamed<cplx>::scratch(M) : (size_t)0;
 }
 
 // th_screen_bound in the words of the continuous fields: the kernels first, then lane = column (wide: two columns per
-// lane).  who: "" or ", Hubbard"; unit: what M counts.
+// lane, quad: four).  who: "" or ", Hubbard"; unit: what M counts.
 int thc_screen_bound(afq_handle *h, const char *who, const char *unit, ThEngine engine, std::initializer_list<ThLds> need) {
     return th_screen_bound(h, std::string("thermal walkers with continuous fields") + who +
                            (engine == TH_ENGINE_STREAMED ? " (streamed_greens)" : engine == TH_ENGINE_WIDE ? " (wide_basis)"
-                            : engine == TH_ENGINE_FAR ? " (far_basis)" : ""),
-                           unit, thc_two_columns(engine) ? TW_COLS : THC_LANES, false, need);
+                            : engine == TH_ENGINE_FAR ? " (far_basis)" : engine == TH_ENGINE_QUAD ? " (quad_basis)" : ""),
+                           unit, engine == TH_ENGINE_QUAD ? TQ_COLS : thc_two_columns(engine) ? TW_COLS : THC_LANES, false, need);
 }
 
 // Behind an entry point's own checks: its host-built tables (`per` numbers per slice: 2 M diagonals or 2 M M), the
@@ -508,8 +523,9 @@ int thc_configure_common(afq_handle *h, ThKind kind, int ntime_slices, int stack
         (rc = dev_alloc(h, LT_WALKERS, &h->thc_M0, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->thc_M00, (size_t)2)) ||
         (rc = dev_alloc(h, LT_WALKERS, &h->thc_det, 2 * n)) || (rc = dev_alloc(h, LT_WALKERS, &h->th_nav, n))) return rc;
     // T of the streamed Green's kernel, two buffers per (walker, spin); the wide route's scratch, four per (walker,
-    // spin), of which the wide slice kernels use the walker's first two; the far route's, W behind the four; a handle
-    // configured without any of them holds none
+    // spin), of which the wide slice kernels use the walker's first two; the far and the quad route's, W behind the
+    // four (nw 2 (4 M M + M (M | 1)) scalars, in size_t: 2.7 GB at M = 256 and 256 walkers); a handle configured
+    // without any of them holds none
     const size_t scratch = 2 * thc_greens_scratch(engine, h->M) * n;
     if ((rc = dev_alloc(h, LT_WALKERS, (cplx **)&h->th_scratch, scratch))) return rc;
     h->th_engine = engine;
@@ -538,6 +554,8 @@ int thc_slice_diag(afq_handle *h) {
     a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
     cplx *const scratch = (cplx *)h->th_scratch;
     const long stride = (long)(2 * thc_greens_scratch(h->th_engine, M));     // a walker's: both spins' of the Green's kernel
+    if (h->th_engine == TH_ENGINE_QUAD)
+        return th_launch<thermal_cslice_kernel<THC_NONE_IN_LDS>>(h, "thermal_cslice_quad_kernel", dim3(h->nw), thc_slice_quad_lds(M), a, scratch, stride);
     if (h->th_engine == TH_ENGINE_FAR)
         return th_launch<thermal_cslice_kernel<THC_NONE_IN_LDS>>(h, "thermal_cslice_far_kernel", dim3(h->nw), thc_slice_far_lds(M), a, scratch, stride);
     if (h->th_engine == TH_ENGINE_WIDE)
@@ -558,6 +576,9 @@ int thc_slice_dense(afq_handle *h) {
     a.M = M; a.nbins = h->th_nbins; a.block = h->th_block; a.counter = h->th_counter;
     cplx *const scratch = (cplx *)h->th_scratch;
     const long stride = (long)(2 * thc_greens_scratch(h->th_engine, M));     // a walker's: both spins' of the Green's kernel
+    if (h->th_engine == TH_ENGINE_QUAD)
+        return th_launch<thermal_cslice_dense_kernel<THC_NONE_IN_LDS>>(h, "thermal_cslice_dense_quad_kernel", dim3(h->nw), thd_slice_quad_lds(M), a,
+                                                                                scratch, stride);
     if (h->th_engine == TH_ENGINE_FAR)
         return th_launch<thermal_cslice_dense_kernel<THC_NONE_IN_LDS>>(h, "thermal_cslice_dense_far_kernel", dim3(h->nw), thd_slice_far_lds(M), a,
                                                                        scratch, stride);
@@ -589,7 +610,7 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
     AFQ_API(h, "afq_thermal_configure_continuous");
     if (!h) return AFQ_EINVAL;
     h->th_kind = TH_NONE;
-    const ThEntry me = {"afq_thermal_configure_continuous: ", AFQ_THERMAL_STREAMED_GREENS | AFQ_THERMAL_WIDE | AFQ_THERMAL_FAR, AFQ_EINVAL,
+    const ThEntry me = {"afq_thermal_configure_continuous: ", AFQ_THERMAL_STREAMED_GREENS | AFQ_THERMAL_WIDE | AFQ_THERMAL_FAR | AFQ_THERMAL_QUAD, AFQ_EINVAL,
                         "afq_thermal_configure_continuous: charge_decomposition belongs to the discrete fields", AFQ_SYS_UEG,
                         "thermal walkers with continuous fields: UEG systems only (no Generic, no continuous Hubbard)", "both"};
     if (!BT || !BT_inv || !BH1 || !mf_shift) AFQ_FAIL(h, AFQ_EINVAL, me.me + "null operand");
@@ -597,7 +618,9 @@ int afq_thermal_configure_continuous(afq_handle *h, int ntime_slices, int stack_
     ThEngine route;
     AFQ_TRY(thc_engine_of(h, me.me, options, &route));
     const ThLds slice = {"the slice kernel (thermal_cslice_kernel)", thc_slice_lds, ""};
-    if (route == TH_ENGINE_FAR)
+    if (route == TH_ENGINE_QUAD)
+        AFQ_TRY(thc_screen_bound(h, "", "plane waves", route, {THC_QUAD_GREENS, THC_QUAD_SLICE}));
+    else if (route == TH_ENGINE_FAR)
         AFQ_TRY(thc_screen_bound(h, "", "plane waves", route, {THC_FAR_GREENS, THC_FAR_SLICE}));
     else if (route == TH_ENGINE_WIDE)
         AFQ_TRY(thc_screen_bound(h, "", "plane waves", route, {THC_WIDE_GREENS,
@@ -642,6 +665,8 @@ int afq_thermal_wide_max_basis(void) {
 
 int afq_thermal_far_max_basis(void) { return th_far_bound(); }
 
+int afq_thermal_quad_max_basis(void) { return th_quad_bound(); }
+
 int afq_thermal_left_table(int M, int stack_size, const double *BT, const double *BT_inv, double *BTpow_out, double *left_out) {
     if (M < 1 || stack_size < 1 || !BT || !BT_inv || !BTpow_out || !left_out) return AFQ_EINVAL;
     thd_left_table(M, stack_size, BT, BT_inv, BTpow_out, left_out);
@@ -654,7 +679,7 @@ int afq_thermal_configure_hubbard_continuous(afq_handle *h, int ntime_slices, in
     AFQ_API(h, "afq_thermal_configure_hubbard_continuous");
     if (!h) return AFQ_EINVAL;
     h->th_kind = TH_NONE;
-    const ThEntry me = {"afq_thermal_configure_hubbard_continuous: ", AFQ_THERMAL_STREAMED_GREENS | AFQ_THERMAL_WIDE | AFQ_THERMAL_FAR, AFQ_EINVAL,
+    const ThEntry me = {"afq_thermal_configure_hubbard_continuous: ", AFQ_THERMAL_STREAMED_GREENS | AFQ_THERMAL_WIDE | AFQ_THERMAL_FAR | AFQ_THERMAL_QUAD, AFQ_EINVAL,
                         "afq_thermal_configure_hubbard_continuous: charge_decomposition belongs to the discrete fields (the "
                         "continuous form is the charge form alone)", AFQ_SYS_HUBBARD,
                         "thermal walkers with continuous fields and a dense trial: Hubbard systems only (no Generic)", "both"};
@@ -663,9 +688,9 @@ int afq_thermal_configure_hubbard_continuous(afq_handle *h, int ntime_slices, in
     ThEngine route;
     AFQ_TRY(thc_engine_of(h, me.me, options, &route));
     const bool streamed = route == TH_ENGINE_STREAMED;
-    const ThLds greens = route == TH_ENGINE_FAR ? THC_FAR_GREENS : route == TH_ENGINE_WIDE ? THC_WIDE_GREENS : streamed ? ThLds{"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}
+    const ThLds greens = route == TH_ENGINE_QUAD ? THC_QUAD_GREENS : route == TH_ENGINE_FAR ? THC_FAR_GREENS : route == TH_ENGINE_WIDE ? THC_WIDE_GREENS : streamed ? ThLds{"the streamed Green's function (thermal_cgreens_streamed_kernel)", ts_greens_streamed_lds<cplx>, ""}
                                    : ThLds{"the complex Green's function (thermal_cgreens_kernel)", ts_greens_lds<cplx>, THC_RESIDENT_HINT};
-    const ThLds slice = route == TH_ENGINE_FAR ? THD_FAR_SLICE : route == TH_ENGINE_WIDE ? ThLds{"the wide slice kernel (thermal_cslice_dense_wide_kernel)", thd_slice_wide_lds, ""}
+    const ThLds slice = route == TH_ENGINE_QUAD ? THD_QUAD_SLICE : route == TH_ENGINE_FAR ? THD_FAR_SLICE : route == TH_ENGINE_WIDE ? ThLds{"the wide slice kernel (thermal_cslice_dense_wide_kernel)", thd_slice_wide_lds, ""}
                                                 : ThLds{"the slice kernel (thermal_cslice_dense_kernel)", thd_slice_lds, ""};
     AFQ_TRY(thc_screen_bound(h, ", Hubbard", "sites", route, {greens, slice}));
     AFQ_TRY(th_screen_state(h, me, ntime_slices, stack_size, 1));

@@ -34,6 +34,8 @@
 //   TsFar<T>        (thermal_wide.h) ts_greens_wide_body with its one matrix in the work-group's scratch as well: no
 //                   matrix in LDS, the bits of TsWide.  AFQ_THERMAL_FAR: a complex walker to M = 128.
 //                   thermal_cgreens_far_kernel, thermal_cgreens_far_sweep_kernel.
+//   TsQuad<cplx>    (thermal_wide.h) TsFar's placement with four columns per lane: the bits of TsFar to M = 128.
+//                   AFQ_THERMAL_QUAD: a complex walker to M = 256.  thermal_cgreens_quad_kernel, .._quad_sweep_kernel.
 // th_launch is the one way a thermal kernel with dynamic LDS is launched; ts_launch_greens<T, E> the one launcher of the
 // Green's kernels; th_launch_greens<T> (thermal_wide.h) picks E by the handle's th_engine.
 //
@@ -520,6 +522,8 @@ inline int th_screen_options(afq_handle *h, const ThEntry &e, int options) {
         AFQ_FAIL(h, AFQ_EINVAL, e.me + "wide_basis belongs to the continuous fields (the real walkers work one lane per column, M <= 64)");
     if (options & AFQ_THERMAL_FAR & ~e.allowed)
         AFQ_FAIL(h, AFQ_EINVAL, e.me + "far_basis belongs to the continuous fields (the real walkers reach M = 128 with delayed_updates)");
+    if (options & AFQ_THERMAL_QUAD & ~e.allowed)
+        AFQ_FAIL(h, AFQ_EINVAL, e.me + "quad_basis belongs to the continuous fields (the real walkers reach M = 128 with delayed_updates)");
     if (options & AFQ_THERMAL_DELAYED & ~e.allowed) AFQ_FAIL(h, AFQ_EINVAL, e.me + "delayed_updates belongs to the discrete fields");
     if (options & ~e.allowed) AFQ_FAIL(h, AFQ_EINVAL, e.me + "unknown option bits");
     if (!h->kind || !h->nw) AFQ_FAIL(h, AFQ_ESTATE, e.me + "set the system and allocate the walkers first");

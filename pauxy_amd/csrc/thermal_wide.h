@@ -36,12 +36,20 @@
 // cplx).  Where W lives is the body's one template parameter; every helper takes W as a pointer and every element goes
 // through the same operations in the same order, so the two placements give the same bits where both run.  The lanes
 // bind: M <= 128, which holds the shell of 123 plane waves and the lattices 10 x 10, 11 x 11 and 8 x 16.
+//
+// TsQuad<cplx> (AFQ_THERMAL_QUAD) is the far placement with four columns per lane.  The columns a lane owns are the
+// body's third template parameter NC (2: TsWide, TsFar; 4: TsQuad), and every vector of the body -- D, v, part, aux with
+// tau and the second reflector buffer in it, perm, the colv / rowr of the LU and the substitution -- is sized and
+// addressed by COLS = 64 NC.  A column meets the same operations in the same order whatever NC is, so the quad engine
+// gives the far engine's bits to M = 128, and reaches M <= 256: the shells to 251 plane waves and the lattices 12 x 12
+// and 16 x 16.  LDS: 37,888 B.  The invariants above hold for it unchanged.
 #pragma once
 #include "thermal_strat.h"
 #include <initializer_list>
 #include <string>
 
 #define TW_COLS 128             // two columns per lane
+#define TQ_COLS 256             // four columns per lane (TsQuad)
 
 namespace {
 
@@ -53,31 +61,36 @@ __host__ __device__ inline size_t ts_greens_wide_scratch(int M) { return 4 * (si
 template <class T> inline size_t ts_greens_far_lds(int) { return sizeof(T) * (128 + 128 + 512 + 384) + sizeof(int) * TW_COLS; }
 // its scratch: the four [M, M] buffers and W [M, M | 1] behind them
 __host__ __device__ inline size_t ts_greens_far_scratch(int M) { return 4 * (size_t)M * M + ts_mat(M); }
+// LDS of the quad Green's kernel: the far kernel's vectors at 256 columns -- D[256], v[256], part[1024], aux[768]; perm[256]
+template <class T> inline size_t ts_greens_quad_lds(int) { return sizeof(T) * (TQ_COLS + TQ_COLS + 4 * TQ_COLS + 3 * TQ_COLS) + sizeof(int) * TQ_COLS; }
 
-template <class T> __device__ inline T tw_sum4(const T *p) {
+// NC, here and below: the columns a lane owns (2 or 4); COLS = 64 NC is the pitch of every vector of the body
+template <int NC, class T> __device__ inline T tw_sum4(const T *p) {
     typedef TsScalar<T> S;
-    return S::add(S::add(p[0], p[128]), S::add(p[256], p[384]));
+    constexpr int COLS = 64 * NC;
+    return S::add(S::add(p[0], p[COLS]), S::add(p[2 * COLS], p[3 * COLS]));
 }
 
-// W[j.., cc] <- (I - tau v v^H) W[j.., cc] for the columns cmin <= cc < M, two per lane and four row classes per column;
-// v[j .. M - 1] in LDS, written behind a barrier.  One barrier inside; none behind the update.  part: 512 scalars.
-template <class T> __device__ inline void tw_reflect_left(T *W, int M, int LD, int j, int cmin, const T *v, double tau, T *part) {
+// W[j.., cc] <- (I - tau v v^H) W[j.., cc] for the columns cmin <= cc < M, NC per lane and four row classes per column;
+// v[j .. M - 1] in LDS, written behind a barrier.  One barrier inside; none behind the update.  part: 4 COLS scalars.
+template <int NC, class T> __device__ inline void tw_reflect_left(T *W, int M, int LD, int j, int cmin, const T *v, double tau, T *part) {
+    constexpr int COLS = 64 * NC;
     const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < NC; ++h) {
         const int cc = c + 64 * h;
         if (cc >= cmin && cc < M) {
             T s = TsScalar<T>::zero();
             for (int i = j + q; i < M; i += 4) TsScalar<T>::fma(s, TsScalar<T>::conj(v[i]), W[i * LD + cc]);
-            part[q * 128 + cc] = s;
+            part[q * COLS + cc] = s;
         }
     }
     __syncthreads();
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < NC; ++h) {
         const int cc = c + 64 * h;
         if (cc >= cmin && cc < M) {
-            const T s = TsScalar<T>::scale(tw_sum4<T>(part + cc), -tau);
+            const T s = TsScalar<T>::scale(tw_sum4<NC, T>(part + cc), -tau);
             for (int i = j + q; i < M; i += 4) TsScalar<T>::fma(W[i * LD + cc], s, v[i]);
         }
     }
@@ -86,30 +99,31 @@ template <class T> __device__ inline void tw_reflect_left(T *W, int M, int LD, i
 // Column-pivoted Householder QR of W [M, M] (LDS, pitch LD), in place: W P = Q R.  On return the upper triangle of W
 // holds R, column j below the diagonal reflector j (v_0 = 1 implied), tau[j] its factor, perm[j] the original column now
 // at position j.  The pivot of step j: the remaining column of the largest norm over the rows j.., recomputed every
-// step, ties to the lower index; every wave runs the search on its own over both columns of its lanes.
-template <class T> __device__ void tw_qrcp(T *W, int M, int LD, int *perm, T *v, T *part, double *tau) {
+// step, ties to the lower index; every wave runs the search on its own over the NC columns of its lanes.
+template <int NC, class T> __device__ void tw_qrcp(T *W, int M, int LD, int *perm, T *v, T *part, double *tau) {
     typedef TsScalar<T> S;
+    constexpr int COLS = 64 * NC;
     const int tid = threadIdx.x, c = tid & 63, q = tid >> 6;
     if (tid < M) perm[tid] = tid;
     __syncthreads();
     for (int j = 0; j < M; ++j) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
+        for (int h = 0; h < NC; ++h) {
             const int cc = c + 64 * h;
             if (cc >= j && cc < M) {
                 double s = 0.0;
                 for (int i = j + q; i < M; i += 4) S::abs2(s, W[i * LD + cc]);
-                S::re(part[q * 128 + cc]) = s;
+                S::re(part[q * COLS + cc]) = s;
             }
         }
         __syncthreads();
         double nrm2 = -1.0;
         int piv = j;
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {                                // (low column first: a tie stays with it)
+        for (int h = 0; h < NC; ++h) {                                // (low column first: a tie stays with it)
             const int cc = c + 64 * h;
             if (cc >= j && cc < M) {
-                const double n = (S::re(part[cc]) + S::re(part[128 + cc])) + (S::re(part[256 + cc]) + S::re(part[384 + cc]));
+                const double n = (S::re(part[cc]) + S::re(part[COLS + cc])) + (S::re(part[2 * COLS + cc]) + S::re(part[3 * COLS + cc]));
                 if (n > nrm2) { nrm2 = n; piv = cc; }
             }
         }
@@ -129,7 +143,7 @@ template <class T> __device__ void tw_qrcp(T *W, int M, int LD, int *perm, T *v,
             v[j + tid] = (tid == 0 || !(nrm > 0.0)) ? S::real(tid == 0 ? 1.0 : 0.0) : S::div(W[(j + tid) * LD + j], den);
         if (tid == 0) tau[j] = tj;
         __syncthreads();
-        tw_reflect_left(W, M, LD, j, j + 1, v, tj, part);
+        tw_reflect_left<NC>(W, M, LD, j, j + 1, v, tj, part);
         // column j: R's diagonal, and the reflector where the zeros would be
         if (c == (j & 63) && nrm > 0.0) for (int i = j + q; i < M; i += 4) W[i * LD + j] = i == j ? alpha : v[i];
         __syncthreads();
@@ -157,25 +171,31 @@ template <class T> __device__ inline void tw_load_reflector(T *v, const T *Pn, i
 }
 
 // W <- W H_0 H_1 .. H_(M-1) = W Q: row r of W by the two threads r and r + 128 (the k of even and of odd distance from
-// j), then every element of the trailing columns by the whole work-group.  v0, v1: 128 scalars each, used in turn.
-template <class T> __device__ void tw_apply_right(T *W, int M, int LD, const T *Pn, const double *tau, T *v0, T *v1, T *part) {
+// j; with four columns per lane the pair takes row r + 128 as well), then every element of the trailing columns by the
+// whole work-group.  v0, v1: COLS scalars each, used in turn.
+template <int NC, class T> __device__ void tw_apply_right(T *W, int M, int LD, const T *Pn, const double *tau, T *v0, T *v1, T *part) {
     typedef TsScalar<T> S;
+    constexpr int COLS = 64 * NC;
     const int tid = threadIdx.x, r = tid & 127, hh = tid >> 7;
     for (int j = 0; j < M; ++j) {
         T *v = (j & 1) ? v1 : v0;
         tw_load_reflector(v, Pn, M, j);
         __syncthreads();
-        if (r < M) {
-            T s = S::zero();
-            for (int i = j + hh; i < M; i += 2) S::fma(s, W[r * LD + i], v[i]);
-            part[hh * 128 + r] = s;
+#pragma unroll
+        for (int g = 0; g < NC / 2; ++g) {
+            const int rw = r + 128 * g;
+            if (rw < M) {
+                T s = S::zero();
+                for (int i = j + hh; i < M; i += 2) S::fma(s, W[rw * LD + i], v[i]);
+                part[hh * COLS + rw] = s;
+            }
         }
         __syncthreads();
         const double tj = tau[j];
         const int n = M - j;
         for (int e = tid; e < M * n; e += TH_THREADS) {
             const int rr = e / n, i = j + e % n;
-            const T s = S::scale(S::add(part[rr], part[128 + rr]), -tj);
+            const T s = S::scale(S::add(part[rr], part[COLS + rr]), -tj);
             S::fma(W[rr * LD + i], s, S::conj(v[i]));
         }
     }
@@ -183,22 +203,23 @@ template <class T> __device__ void tw_apply_right(T *W, int M, int LD, const T *
 }
 
 // W <- Q^H = H_(M-1) .. H_0 I
-template <class T> __device__ void tw_build_qt(T *W, int M, int LD, const T *Pn, const double *tau, T *v0, T *v1, T *part) {
+template <int NC, class T> __device__ void tw_build_qt(T *W, int M, int LD, const T *Pn, const double *tau, T *v0, T *v1, T *part) {
     const int tid = threadIdx.x;
     for (int e = tid; e < M * M; e += TH_THREADS) { const int r = e / M, c = e % M; W[r * LD + c] = TsScalar<T>::real(r == c ? 1.0 : 0.0); }
     for (int j = 0; j < M; ++j) {
         T *v = (j & 1) ? v1 : v0;
         tw_load_reflector(v, Pn, M, j);
         __syncthreads();
-        tw_reflect_left(W, M, LD, j, 0, v, tau[j], part);
+        tw_reflect_left<NC>(W, M, LD, j, 0, v, tau[j], part);
     }
     __syncthreads();
 }
 
 // LU of X [M, M] (LDS) with partial (row) pivoting, in place: the multipliers below the diagonal, rows exchanged whole,
 // rperm[i] the original row now at i.  Returns the product of the pivots with the sign of the exchanges (the same value
-// in every thread).  DET: a zero pivot ends the factorisation with 0 (uniform over the work-group).  colv: 128 scalars.
-template <bool DET, class T> __device__ T tw_lu(T *X, int M, int LD, int *rperm, T *colv) {
+// in every thread).  DET: a zero pivot ends the factorisation with 0 (uniform over the work-group).  colv: COLS scalars;
+// a lane searches its NC rows from the low one up.
+template <int NC, bool DET, class T> __device__ T tw_lu(T *X, int M, int LD, int *rperm, T *colv) {
     typedef TsScalar<T> S;
     const int tid = threadIdx.x, c = tid & 63;
     T det = S::real(1.0);
@@ -207,7 +228,7 @@ template <bool DET, class T> __device__ T tw_lu(T *X, int M, int LD, int *rperm,
         double a = -1.0;
         int p = k;
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
+        for (int h = 0; h < NC; ++h) {
             const int rr = c + 64 * h;
             if (rr >= k && rr < M) {
                 const double ar = S::abs(X[rr * LD + k]);
@@ -238,7 +259,7 @@ template <bool DET, class T> __device__ T tw_lu(T *X, int M, int LD, int *rperm,
 }
 
 // L U G = R' with the factors transposed in LUt (device: column k at LUt + k M) and R' [M, M] in LDS, which G
-// overwrites.  c0, c1: 128 scalars each, used in turn; rowr: 128 scalars.
+// overwrites.  c0, c1: M <= COLS scalars each, used in turn; rowr: as many (no lane owns a column here: nothing to widen).
 template <class T> __device__ void tw_substitute(T *R, int M, int LD, const T *LUt, T *c0, T *c1, T *rowr) {
     typedef TsScalar<T> S;
     const int tid = threadIdx.x;
@@ -272,18 +293,19 @@ template <class T> __device__ void tw_substitute(T *R, int M, int LD, const T *L
 // The work of one work-group, as ts_greens_body (another algorithm: its own body); scr: the work-group's own
 // ts_greens_wide_scratch(M) scalars, or with FAR ts_greens_far_scratch(M): W then lies behind the four buffers in
 // device memory and the vectors start at smem.
-template <class T, bool FAR>
+template <class T, bool FAR, int NC>
 __device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first,
                                                     T *Gd, T *Gd2, T *detd) {
     typedef TsScalar<T> S;
+    constexpr int COLS = 64 * NC;                                    // 128 or 256: what every vector below holds
     const int LD = M | 1, tid = threadIdx.x;
     const size_t mat = ts_mat(M);
     const long mm = (long)M * M;
     T *W = FAR ? scr + 4 * mm : (T *)smem;
-    T *D = FAR ? (T *)smem : W + mat, *v = D + 128, *part = v + 128, *aux = part + 512;
-    int *perm = (int *)(aux + 384);
-    double *tau = (double *)aux;                                     // 128 doubles: aux[0 .. 63] of cplx, [0 .. 127] of double
-    T *v1 = aux + 128 * sizeof(double) / sizeof(T);                  // the second reflector buffer: the 128 scalars behind tau
+    T *D = FAR ? (T *)smem : W + mat, *v = D + COLS, *part = v + COLS, *aux = part + 4 * COLS;
+    int *perm = (int *)(aux + 3 * COLS);
+    double *tau = (double *)aux;                                     // COLS doubles: the first half of as many cplx, all of as many double
+    T *v1 = aux + COLS * sizeof(double) / sizeof(T);                 // the second reflector buffer: the COLS scalars behind tau
     T *Tin = scr, *Tout = scr + mm, *Pn = scr + 2 * mm, *Xs = scr + 3 * mm;
 
     {
@@ -291,19 +313,19 @@ __device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const T
         for (int e = tid; e < M * M; e += TH_THREADS) W[(e / M) * LD + e % M] = B[e];
     }
     __syncthreads();
-    tw_qrcp(W, M, LD, perm, v, part, tau);
+    tw_qrcp<NC>(W, M, LD, perm, v, part, tau);
     tw_store_qr(W, M, LD, perm, Tin, Pn, D);                         // T = D^-1 R P^T
     for (int n = 1; n < nbins; ++n) {
         const T *B = Bw + (long)((first + n) % nbins) * 2 * mm;
         for (int e = tid; e < M * M; e += TH_THREADS) W[(e / M) * LD + e % M] = B[e];
         __syncthreads();
-        tw_apply_right(W, M, LD, Pn, tau, v, v1, part);              // B Q
+        tw_apply_right<NC>(W, M, LD, Pn, tau, v, v1, part);              // B Q
         for (int e = tid; e < M * M; e += TH_THREADS) {
             const int r = e / M, c = e % M;
             W[r * LD + c] = S::mul(W[r * LD + c], D[c]);             // (B Q) D
         }
         __syncthreads();
-        tw_qrcp(W, M, LD, perm, v, part, tau);
+        tw_qrcp<NC>(W, M, LD, perm, v, part, tau);
         tw_store_qr(W, M, LD, perm, Xs, Pn, D);
         // T <- t T
         ts_gemm<T>(M, [&](int r, int k) { return Xs[r * M + k]; }, [&](int k, int c) { return Tin[k * M + c]; },
@@ -312,7 +334,7 @@ __device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const T
         T *t = Tin; Tin = Tout; Tout = t;
     }
     // (D_b Q^H + D_s T) G = D_b Q^H, D_b = 1 / |D| and D_s = D / |D| where |D| > 1, else D_b = 1 and D_s = D
-    tw_build_qt(W, M, LD, Pn, tau, v, v1, part);
+    tw_build_qt<NC>(W, M, LD, Pn, tau, v, v1, part);
     for (int e = tid; e < M * M; e += TH_THREADS) {
         const int i = e / M, j = e % M;
         const T d = D[i];
@@ -326,12 +348,12 @@ __device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const T
         Xs[i * M + j] = r;
     }
     __syncthreads();
-    tw_lu<false>(W, M, LD, perm, aux);
+    tw_lu<NC, false>(W, M, LD, perm, aux);
     for (int e = tid; e < M * M; e += TH_THREADS) { const int r = e / M, c = e % M; Pn[c * M + r] = W[r * LD + c]; }
     __syncthreads();
     for (int e = tid; e < M * M; e += TH_THREADS) { const int r = e / M, c = e % M; W[r * LD + c] = Xs[perm[r] * M + c]; }
     __syncthreads();
-    tw_substitute(W, M, LD, Pn, aux, aux + 128, aux + 256);
+    tw_substitute(W, M, LD, Pn, aux, aux + COLS, aux + 2 * COLS);
     for (int e = tid; e < M * M; e += TH_THREADS) {
         const T g = W[(e / M) * LD + e % M];
         Gd[e] = g;
@@ -339,7 +361,7 @@ __device__ __forceinline__ void ts_greens_wide_body(unsigned char *smem, const T
     }
     if (!detd) return;
     __syncthreads();
-    const T dg = tw_lu<true>(W, M, LD, perm, aux);
+    const T dg = tw_lu<NC, true>(W, M, LD, perm, aux);
     if (tid == 0) *detd = dg;
 }
 
@@ -354,7 +376,7 @@ template <class T> struct TsWide {
                                             : (sweep ? "thermal_greens_wide_sweep_kernel" : "thermal_greens_wide_kernel");
     }
     __device__ __forceinline__ static void body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first, T *Gd, T *Gd2, T *detd) {
-        ts_greens_wide_body<T, false>(smem, Bw, scr, M, nbins, first, Gd, Gd2, detd);
+        ts_greens_wide_body<T, false, 2>(smem, Bw, scr, M, nbins, first, Gd, Gd2, detd);
     }
 };
 
@@ -368,7 +390,21 @@ template <class T> struct TsFar {
                                             : (sweep ? "thermal_greens_far_sweep_kernel" : "thermal_greens_far_kernel");
     }
     __device__ __forceinline__ static void body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first, T *Gd, T *Gd2, T *detd) {
-        ts_greens_wide_body<T, true>(smem, Bw, scr, M, nbins, first, Gd, Gd2, detd);
+        ts_greens_wide_body<T, true, 2>(smem, Bw, scr, M, nbins, first, Gd, Gd2, detd);
+    }
+};
+
+// The quad engine (AFQ_THERMAL_QUAD, the complex walkers): the far placement with four columns per lane -- c, c + 64,
+// c + 128 and c + 192 -- and every vector in LDS at 256 entries, so that the lanes hold M <= 256.  A column goes through
+// the far engine's operations in the far engine's order (the four row-class sums added as tw_sum4 adds them, a lane's
+// columns searched from the low one up with a strict >, then ts_wave_argmax): the far engine's bits where both run.
+template <class T> struct TsQuad {
+    static constexpr bool has_sweep = true;
+    static size_t lds(int M) { return ts_greens_quad_lds<T>(M); }
+    __host__ __device__ static size_t scratch(int M) { return ts_greens_far_scratch(M); }
+    static const char *name(bool sweep) { return sweep ? "thermal_cgreens_quad_sweep_kernel" : "thermal_cgreens_quad_kernel"; }
+    __device__ __forceinline__ static void body(unsigned char *smem, const T *Bw, T *scr, int M, int nbins, int first, T *Gd, T *Gd2, T *detd) {
+        ts_greens_wide_body<T, true, 4>(smem, Bw, scr, M, nbins, first, Gd, Gd2, detd);
     }
 };
 
@@ -380,7 +416,8 @@ template <class T> int th_launch_greens(afq_handle *h, const T *stack, T *G, T *
     const bool sweep = Gs != nullptr;
     const TsGreensArgs<T> a = {stack, G, det, sweep ? Ts : (T *)h->th_scratch, h->M, h->th_nbins, first, src_w, Gs, h->th_ss, ts0};
     if (h->th_engine == TH_ENGINE_WIDE) return ts_launch_greens<T, TsWide>(h, a, grid, sweep);
-    if constexpr (std::is_same<T, cplx>::value) {                    // (the real walkers have no streamed and no far engine)
+    if constexpr (std::is_same<T, cplx>::value) {                    // (the real walkers have no streamed, far or quad engine)
+        if (h->th_engine == TH_ENGINE_QUAD) return ts_launch_greens<T, TsQuad>(h, a, grid, sweep);
         if (h->th_engine == TH_ENGINE_FAR) return ts_launch_greens<T, TsFar>(h, a, grid, sweep);
         if (h->th_engine == TH_ENGINE_STREAMED) return ts_launch_greens<T, TsStreamed>(h, a, grid, sweep);
     }
@@ -390,7 +427,8 @@ template <class T> int th_launch_greens(afq_handle *h, const T *stack, T *G, T *
 // scalars of scratch per work-group of the handle's Green's kernel, whatever the walker kind: what the sweep of
 // afq_thermal_estimates sizes its chunks from
 inline size_t th_greens_scratch(const afq_handle *h) {
-    return h->th_engine == TH_ENGINE_FAR ? TsFar<cplx>::scratch(h->M) : h->th_engine == TH_ENGINE_WIDE ? TsWide<cplx>::scratch(h->M)
+    return h->th_engine == TH_ENGINE_QUAD ? TsQuad<cplx>::scratch(h->M)
+         : h->th_engine == TH_ENGINE_FAR ? TsFar<cplx>::scratch(h->M) : h->th_engine == TH_ENGINE_WIDE ? TsWide<cplx>::scratch(h->M)
          : h->th_engine == TH_ENGINE_STREAMED ? TsStreamed<cplx>::scratch(h->M) : (size_t)0;
 }
 
@@ -403,7 +441,7 @@ struct ThLds {
     const char *hint;
 };
 
-// M within what every kernel of `need` holds and within `lanes` columns (64: one per lane; TW_COLS: two); else the
+// M within what every kernel of `need` holds and within `lanes` columns (64: one per lane; TW_COLS: two; TQ_COLS: four); else the
 // refusal "<who>: M = <M> <unit> ..." names the first that does not fit -- the columns before the kernels with
 // lanes_first, behind them without -- with its bytes, and the largest M that passes.
 inline int th_screen_bound(afq_handle *h, const std::string &who, const char *unit, int lanes, bool lanes_first,
@@ -419,7 +457,8 @@ inline int th_screen_bound(afq_handle *h, const std::string &who, const char *un
     while (mmax > 1 && !fits(mmax)) --mmax;
     const std::string head = who + ": M = " + std::to_string(M) + " " + unit + " ";
     const std::string tail = " (M <= " + std::to_string(mmax) + ")";
-    const std::string columns = head + "are more than the " + (lanes == TW_COLS ? std::to_string(TW_COLS) + " columns of a wave, two per lane"
+    const std::string columns = head + "are more than the " + (lanes == TQ_COLS ? std::to_string(TQ_COLS) + " columns of a wave, four per lane"
+                                                                 : lanes == TW_COLS ? std::to_string(TW_COLS) + " columns of a wave, two per lane"
                                                                                  : std::to_string(lanes) + " lanes of a wave, one per column") + tail;
     if (lanes_first && M > lanes) AFQ_FAIL(h, AFQ_EUNSUPPORTED, columns);
     for (const ThLds &k : need)
@@ -442,6 +481,20 @@ const ThLds THD_FAR_SLICE = {"the far slice kernel (thermal_cslice_dense_far_ker
 inline int th_far_bound() {
     int m = TW_COLS;
     while (m > 1 && (ts_greens_far_lds<cplx>(m) > TH_LDS_MAX || thc_slice_far_lds(m) > TH_LDS_MAX || thd_slice_far_lds(m) > TH_LDS_MAX)) --m;
+    return m;
+}
+
+// ---- the quad route's kernels and its bound: the far route's reads and writes with every vector at TQ_COLS entries
+inline size_t thc_slice_quad_lds(int) { return 0; }                            // thermal_cslice_quad_kernel: nothing
+inline size_t thd_slice_quad_lds(int) { return 2 * sizeof(double) * TQ_COLS; } // thermal_cslice_dense_quad_kernel: bv[256] of cplx
+static_assert(TQ_COLS <= TH_THREADS, "bv, a column exchange and a reflector load work one thread per entry: M <= TH_THREADS");
+const ThLds THC_QUAD_GREENS = {"the quad Green's function (thermal_cgreens_quad_kernel)", ts_greens_quad_lds<cplx>, ""};
+const ThLds THC_QUAD_SLICE = {"the quad slice kernel (thermal_cslice_quad_kernel)", thc_slice_quad_lds, ""};
+const ThLds THD_QUAD_SLICE = {"the quad slice kernel (thermal_cslice_dense_quad_kernel)", thd_slice_quad_lds, ""};
+
+inline int th_quad_bound() {
+    int m = TQ_COLS;
+    while (m > 1 && (ts_greens_quad_lds<cplx>(m) > TH_LDS_MAX || thc_slice_quad_lds(m) > TH_LDS_MAX || thd_slice_quad_lds(m) > TH_LDS_MAX)) --m;
     return m;
 }
 

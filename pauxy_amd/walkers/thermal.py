@@ -34,6 +34,15 @@ def _far_max_basis():
         return 128
 
 
+def _quad_max_basis():
+    """The quad route's bound as the library computes it (k_thermal_cplx.hip): the far placement with four columns per
+    lane, 256 in all; a library that does not export it, or none built yet, leaves the literal."""
+    try:
+        return int(L.load().afq_thermal_quad_max_basis())
+    except (L.AfqLibraryError, AttributeError):
+        return 256
+
+
 def _delayed_max_basis():
     """The delayed route's bound as the library computes it from its kernels' LDS (k_thermal.hip) and the 128 columns of
     two per lane; a library that does not export it, or none built yet, leaves the literal."""
@@ -44,17 +53,20 @@ def _delayed_max_basis():
 
 
 # The largest basis of the complex walkers by (kind, route): what fits the 160 KiB of LDS of a work-group.  The route is
-# streamed_greens (False / True), 'wide' (walkers: {wide_basis: True}: one complex matrix in LDS, two columns per lane)
-# or 'far' (walkers: {far_basis: True}: the wide route with that matrix in device memory as well).
+# streamed_greens (False / True), 'wide' (walkers: {wide_basis: True}: one complex matrix in LDS, two columns per lane),
+# 'far' (walkers: {far_basis: True}: the wide route with that matrix in device memory as well) or 'quad'
+# (walkers: {quad_basis: True}: the far route with four columns per lane).
 MAX_BASIS = {
     ('planewave', False): 47,            # ts_greens_lds<cplx> (thermal_strat.h): four complex matrices
     ('planewave', True): 57,             # thc_slice_lds (k_thermal_cplx.hip): three complex matrices
     ('planewave', 'wide'): _wide_max_basis(),             # ts_greens_wide_lds (thermal_wide.h): one complex matrix
     ('planewave', 'far'): _far_max_basis(),               # the lanes: two columns each
+    ('planewave', 'quad'): _quad_max_basis(),             # the lanes: four columns each
     ('hubbard_continuous', False): 47,   # ts_greens_lds<cplx>
     ('hubbard_continuous', True): 63,    # thd_slice_lds (k_thermal_cplx.hip): two complex matrices and BH1
     ('hubbard_continuous', 'wide'): _wide_max_basis(),    # ts_greens_wide_lds
     ('hubbard_continuous', 'far'): _far_max_basis(),      # the lanes
+    ('hubbard_continuous', 'quad'): _quad_max_basis(),    # the lanes
     # the real walkers with walkers: {delayed_updates: True}: ts_greens_wide_lds<double> fits, the lanes bind
     ('discrete', 'delayed'): _delayed_max_basis(),
 }
@@ -203,6 +215,17 @@ class ThermalWalkers(object):
         if self.far_basis and self.streamed_greens:
             raise NotImplementedError("thermal walkers: far_basis and streamed_greens are two placements of the same "
                                       "matrices: ask for one")
+        # the far route with four columns per lane (thermal_wide.h, AFQ_THERMAL_QUAD)
+        self.quad_basis = bool(walker_opts.get('quad_basis', False))
+        if self.quad_basis and self.kind == 'discrete':
+            raise NotImplementedError("thermal walkers: quad_basis belongs to the continuous fields (Hubbard walkers "
+                                      "with discrete fields reach M = 128 with delayed_updates; with "
+                                      "hubbard_stratonovich: 'continuous' the driver announces the complex walkers, and "
+                                      "walkers: {continuous_fields: True} does so by hand)")
+        for other in ('far_basis', 'wide_basis', 'streamed_greens'):
+            if self.quad_basis and getattr(self, other):
+                raise NotImplementedError("thermal walkers: quad_basis and %s are two placements of the same "
+                                          "matrices: ask for one" % other)
         # the slice by delayed updates and the wide real Green's function (k_thermal.hip, AFQ_THERMAL_DELAYED)
         self.delayed_updates = bool(walker_opts.get('delayed_updates', False))
         if self.delayed_updates and self.kind != 'discrete':
@@ -216,7 +239,7 @@ class ThermalWalkers(object):
                 raise NotImplementedError("thermal walkers: M = %d > %d sites is not supported with delayed_updates (the "
                                           "wide Green's function works two columns per lane, 128 in all)"
                                           % (system.nbasis, bound))
-        elif system.nbasis > 64 and not self.wide_basis and not self.far_basis:
+        elif system.nbasis > 64 and not self.wide_basis and not self.far_basis and not self.quad_basis:
             raise NotImplementedError("thermal walkers: M = %d > 64 sites is not supported%s" % (
                 system.nbasis, " (walkers: {delayed_updates: True} reaches M = %d)" % MAX_BASIS['discrete', 'delayed']
                 if self.kind == 'discrete' else ""))
@@ -291,7 +314,7 @@ class ThermalWalkers(object):
         if self.delayed_updates and kind != 'discrete':
             raise NotImplementedError("thermal walkers: delayed_updates belongs to the discrete fields (a '%s' "
                                       "propagator moves complex walkers)" % getattr(prop, 'hs_type', kind))
-        configure(L.THERMAL_FAR if self.far_basis else L.THERMAL_WIDE if self.wide_basis
+        configure(L.THERMAL_QUAD if self.quad_basis else L.THERMAL_FAR if self.far_basis else L.THERMAL_WIDE if self.wide_basis
                   else L.THERMAL_STREAMED_GREENS if self.streamed_greens
                   else L.THERMAL_DELAYED if self.delayed_updates else 0)
         self.kind, self.configured = kind, (kind, key)
@@ -306,6 +329,9 @@ class ThermalWalkers(object):
                                       "with discrete fields work one lane per column, M <= 64)")
         if self.far_basis:
             raise NotImplementedError("thermal walkers: far_basis belongs to the continuous fields (Hubbard walkers "
+                                      "with discrete fields reach M = 128 with delayed_updates)")
+        if self.quad_basis:
+            raise NotImplementedError("thermal walkers: quad_basis belongs to the continuous fields (Hubbard walkers "
                                       "with discrete fields reach M = 128 with delayed_updates)")
         nstblz = self.nstblz if prop is None else prop.nstblz
 
@@ -351,6 +377,13 @@ class ThermalWalkers(object):
             if M > bound:
                 raise NotImplementedError("%s: M = %d > %d %s is not supported with far_basis (the far Green's function "
                                           "keeps no matrix in LDS; a lane owns two columns, 128 in all)"
+                                          % (who, M, bound, unit))
+            return
+        if getattr(self, 'quad_basis', False):
+            bound = MAX_BASIS[kind, 'quad']
+            if M > bound:
+                raise NotImplementedError("%s: M = %d > %d %s is not supported with quad_basis (the quad Green's function "
+                                          "keeps no matrix in LDS; a lane owns four columns, 256 in all)"
                                           % (who, M, bound, unit))
             return
         bound = MAX_BASIS[kind, self.streamed_greens]

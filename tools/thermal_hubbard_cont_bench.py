@@ -17,10 +17,12 @@ With `--wide` the engines run in turn are the wide route alone (AFQ_THERMAL_WIDE
 thermal_cslice_dense_wide_kernel, one matrix in LDS), which is the only one above 63 sites (`--nx 8`).
 With `--far` the far route (AFQ_THERMAL_FAR: thermal_cgreens_far_kernel and thermal_cslice_dense_far_kernel, no matrix
 in LDS) runs in turn with the wide route to 95 sites and alone above (`--nx 8 --ny 16`: M = 128).
+With `--quad` the quad route (AFQ_THERMAL_QUAD: thermal_cgreens_quad_kernel and thermal_cslice_dense_quad_kernel, four
+columns per lane) runs in turn with the far route to 128 sites and alone above (`--nx 12`: M = 144; `--nx 16`: M = 256).
 `slice_ms` = all of them over the slices run; `path_kernel_ms` = the same per path; `path_wall_ms` the host's wall time
 of a path, fields and copies included, taken in a separate pass without the event pairs.
 
-  python tools/thermal_hubbard_cont_bench.py [--rounds 3] [--paths 5] [--warmup 2] [--nx 6] [--ny NX] [--stack-size 5] [--wide | --far] [--out FILE]
+  python tools/thermal_hubbard_cont_bench.py [--rounds 3] [--paths 5] [--warmup 2] [--nx 6] [--ny NX] [--stack-size 5] [--wide | --far | --quad] [--out FILE]
 """
 import argparse
 import json
@@ -40,13 +42,15 @@ from pauxy_amd.systems import Hubbard                                           
 from pauxy_amd.trial_density import OneBody                                     # noqa: E402
 
 GREENS = {'resident': 'thermal_cgreens_kernel', 'streamed': 'thermal_cgreens_streamed_kernel',
-          'wide': 'thermal_cgreens_wide_kernel', 'far': 'thermal_cgreens_far_kernel'}
-OPTIONS = {'resident': 0, 'streamed': L.THERMAL_STREAMED_GREENS, 'wide': L.THERMAL_WIDE, 'far': L.THERMAL_FAR}
+          'wide': 'thermal_cgreens_wide_kernel', 'far': 'thermal_cgreens_far_kernel', 'quad': 'thermal_cgreens_quad_kernel'}
+OPTIONS = {'resident': 0, 'streamed': L.THERMAL_STREAMED_GREENS, 'wide': L.THERMAL_WIDE, 'far': L.THERMAL_FAR,
+           'quad': L.THERMAL_QUAD}
 SMALL = ('thermal_crdm_kernel', 'thermal_cfields_dense_kernel', 'thermal_cweight_mf_kernel')
 
 
 def slice_of(engine):
-    return {'wide': 'thermal_cslice_dense_wide_kernel', 'far': 'thermal_cslice_dense_far_kernel'}.get(engine, 'thermal_cslice_dense_kernel')
+    return {'wide': 'thermal_cslice_dense_wide_kernel', 'far': 'thermal_cslice_dense_far_kernel',
+            'quad': 'thermal_cslice_dense_quad_kernel'}.get(engine, 'thermal_cslice_dense_kernel')
 
 
 class Qmc(object):
@@ -123,10 +127,13 @@ def main():
     ap.add_argument('--rounds', type=int, default=3, help='runs of each engine, resident and streamed in turn')
     ap.add_argument('--wide', action='store_true', help='the wide route alone (AFQ_THERMAL_WIDE); with --nx 6 beside the other two')
     ap.add_argument('--far', action='store_true', help='the far route (AFQ_THERMAL_FAR), beside the wide route to 95 sites')
+    ap.add_argument('--quad', action='store_true', help='the quad route (AFQ_THERMAL_QUAD), beside the far route to 128 sites')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     a.ny = a.ny or a.nx
-    if a.far:
+    if a.quad:
+        names = ('far', 'quad') if a.nx * a.ny <= 128 else ('quad',)
+    elif a.far:
         names = ('wide', 'far') if a.nx * a.ny <= 95 else ('far',)
     else:
         names = (('resident', 'streamed', 'wide') if a.nx * a.ny <= 47 else ('wide',)) if a.wide else ('resident', 'streamed')
@@ -146,11 +153,11 @@ def main():
                      'path_kernel_ms': spread([r['path_kernel_ms'] for r in runs[name]]),
                      'path_wall_ms': spread([r['path_wall_ms']['median'] for r in runs[name]]),
                      'finite': all(r['finite'] for r in runs[name])}
-    for other, base in (('streamed', 'resident'), ('wide', 'streamed'), ('far', 'wide')):
+    for other, base in (('streamed', 'resident'), ('wide', 'streamed'), ('far', 'wide'), ('quad', 'far')):
         if other in res and base in res:
             res['%s_over_%s' % (other, base)] = {k: res[other][k]['median'] / res[base][k]['median']
                                                  for k in ('slice_ms', 'greens_mean_ms', 'path_wall_ms') +
-                                                 (('slice_kernel_mean_ms',) if other == 'far' else ())}
+                                                 (('slice_kernel_mean_ms',) if other in ('far', 'quad') else ())}
     res['runs'] = runs
     print(json.dumps(res))
     if a.out:

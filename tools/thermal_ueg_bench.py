@@ -16,7 +16,9 @@ The kernels are timed with event pairs around every launch (afq_launch_trace) ov
                            with --wide thermal_cgreens_wide_kernel and thermal_cslice_wide_kernel, one matrix in LDS
                            (AFQ_THERMAL_WIDE, needed above M = 57: ecut 3.0 is M = 81, ecut 4.0 is M = 93);
                            with --far thermal_cgreens_far_kernel and thermal_cslice_far_kernel, no matrix in LDS
-                           (AFQ_THERMAL_FAR, needed above M = 95: ecut 4.5 is M = 123)
+                           (AFQ_THERMAL_FAR, needed above M = 95: ecut 4.5 is M = 123);
+                           with --quad thermal_cgreens_quad_kernel and thermal_cslice_quad_kernel, four columns per lane
+                           (AFQ_THERMAL_QUAD, needed above M = 128: ecut 5.0 is M = 147)
   thermal_cweight_kernel   the phaseless weight update
 `slice_ms` = all of them over the slices run; `path_wall_ms` the host's wall time of a path, fields and copies included
 (median and spread over the paths), taken in a separate pass without the event pairs.
@@ -24,10 +26,11 @@ The kernels are timed with event pairs around every launch (afq_launch_trace) ov
 With `--alternate N` the resident and the streamed engine are run in turn, N times each, on the same shape (M <= 47):
 the JSON then holds every run's figures under `runs` and the median and spread of slice_ms, of the Green's kernel's
 mean and of the path's wall time per engine.  `--alternate N --wide` sets the streamed and the wide route side by side
-instead (M <= 57), `--alternate N --far` the wide and the far route (M <= 95).
+instead (M <= 57), `--alternate N --far` the wide and the far route (M <= 95), `--alternate N --quad` the far and the
+quad route (M <= 128).
 
   python tools/thermal_ueg_bench.py [--paths 5] [--warmup 2] [--ecut 2.0] [--stack-size 5]
-                                    [--streamed | --wide | --far | --alternate N [--wide | --far]] [--out FILE]
+                                    [--streamed | --wide | --far | --quad | --alternate N [--wide | --far | --quad]] [--out FILE]
 """
 import argparse
 import json
@@ -47,10 +50,11 @@ from pauxy_amd.systems import UEG                                               
 from pauxy_amd.trial_density import OneBody                                     # noqa: E402
 
 GREENS = {'resident': 'thermal_cgreens_kernel', 'streamed': 'thermal_cgreens_streamed_kernel',
-          'wide': 'thermal_cgreens_wide_kernel', 'far': 'thermal_cgreens_far_kernel'}
+          'wide': 'thermal_cgreens_wide_kernel', 'far': 'thermal_cgreens_far_kernel', 'quad': 'thermal_cgreens_quad_kernel'}
 SLICE = {'resident': 'thermal_cslice_kernel', 'streamed': 'thermal_cslice_kernel', 'wide': 'thermal_cslice_wide_kernel',
-         'far': 'thermal_cslice_far_kernel'}
-OPTIONS = {'resident': 0, 'streamed': L.THERMAL_STREAMED_GREENS, 'wide': L.THERMAL_WIDE, 'far': L.THERMAL_FAR}
+         'far': 'thermal_cslice_far_kernel', 'quad': 'thermal_cslice_quad_kernel'}
+OPTIONS = {'resident': 0, 'streamed': L.THERMAL_STREAMED_GREENS, 'wide': L.THERMAL_WIDE, 'far': L.THERMAL_FAR,
+           'quad': L.THERMAL_QUAD}
 
 
 def kernels_of(engine):
@@ -83,12 +87,14 @@ def main():
     ap.add_argument('--streamed', action='store_true', help='AFQ_THERMAL_STREAMED_GREENS: T of the Green\'s function in device memory')
     ap.add_argument('--wide', action='store_true', help='AFQ_THERMAL_WIDE: one matrix in LDS, two columns per lane')
     ap.add_argument('--far', action='store_true', help='AFQ_THERMAL_FAR: no matrix in LDS, two columns per lane')
+    ap.add_argument('--quad', action='store_true', help='AFQ_THERMAL_QUAD: no matrix in LDS, four columns per lane')
     ap.add_argument('--alternate', type=int, default=0, help='N runs each of the resident and the streamed engine, in turn '
-                    '(with --wide: of the streamed and the wide route; with --far: of the wide and the far route)')
+                    '(with --wide: of the streamed and the wide route; with --far: of the wide and the far route; with --quad: of the '
+                    'far and the quad route)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.alternate > 0:
-        base, other = ('wide', 'far') if a.far else ('streamed', 'wide') if a.wide else ('resident', 'streamed')
+        base, other = ('far', 'quad') if a.quad else ('wide', 'far') if a.far else ('streamed', 'wide') if a.wide else ('resident', 'streamed')
         runs = {base: [], other: []}
         for _ in range(a.alternate):
             for name in (base, other):
@@ -106,7 +112,7 @@ def main():
                                              for k in ('slice_ms', 'greens_mean_ms', 'slice_kernel_mean_ms', 'path_wall_ms')}
         res['runs'] = runs
     else:
-        res = run(a, 'far' if a.far else 'wide' if a.wide else 'streamed' if a.streamed else 'resident')
+        res = run(a, 'quad' if a.quad else 'far' if a.far else 'wide' if a.wide else 'streamed' if a.streamed else 'resident')
     print(json.dumps(res))
     if a.out:
         with open(a.out, 'w') as f:
